@@ -714,7 +714,13 @@ def main():
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher / sharding / reduction plumbing on CPU (gloo): the step runs the PyTorch model "
                          "definition instead of the HIP path; the line is marked dry_launch and is not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- the [graphs, out] float32 model outputs of "
+                         "its batch -- as DIR/output.npy (DIR/output_rank<r>.npy on ranks > 0); the inputs are seeded, so two "
+                         "builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -900,6 +906,14 @@ def main():
     repeats = max(1, args.repeats)
     times = [timed_region() for _ in range(repeats)]
     elapsed = float(np.median(times))
+    if args.dump_outputs:
+        # the last timed step forwarded batch (steps - 1) mod batches into its output buffer; read it back before the side legs
+        # below reuse the buffers (timed_region synchronised, so the copy waits for nothing)
+        last = outs[(args.steps - 1) % len(batches)].detach().cpu().numpy().astype(np.float32)
+        assert last.nbytes <= 64 << 20, last.shape
+        dump = Path(args.dump_outputs)
+        dump.mkdir(parents=True, exist_ok=True)
+        np.save(dump / ("output.npy" if rank == 0 else f"output_rank{rank}.npy"), last)
 
     graphs_done = float(sum(batches[i % len(batches)].num_graphs for i in range(args.steps)))
     # the same region in the other form of the step (see can_prep_next above)

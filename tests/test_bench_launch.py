@@ -70,3 +70,29 @@ def test_a_rank_that_dies_at_startup_fails_the_launch_within_seconds():
     assert dt < 30.0, dt
     assert "ranks failed" in p.stderr and "(1, 3)" in p.stderr
     assert not [l for l in p.stdout.splitlines() if l.strip()]  # no JSON line from a failed launch
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the outputs of the last timed step (step K - 1 forwards batch (K - 1) mod --batches) as float32
+    DIR/output.npy; the inputs are seeded, so a second run writes the same array."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+    from gnnbuilder_amd import synthetic
+
+    for run in ("a", "b"):
+        p = _run(["--gpus", "1", "--dry-launch", "--workload", "tiny", "--steps", "5", "--warmup", "1", "--repeats", "2",
+                  "--batches", "3", "--dump-outputs", str(tmp_path / run)])
+        assert p.returncode == 0, p.stderr
+        assert json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])["steps"] == 5
+    a, b = np.load(tmp_path / "a" / "output.npy"), np.load(tmp_path / "b" / "output.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    model = bench.build_model(bench.WORKLOADS["tiny"])
+    g = synthetic.make_batch("qm9", 64, seed=(5 - 1) % 3)
+    with torch.no_grad():
+        want = model(torch.from_numpy(g.x), torch.from_numpy(g.coo.T.astype(np.int64)),
+                     torch.from_numpy(np.repeat(np.arange(g.num_graphs), np.diff(g.node_ptr)))).numpy()
+    assert a.shape == want.shape == (64, model.spec()["mlp_out"])
+    assert np.abs(a - want).max() < 1e-5

@@ -82,7 +82,8 @@ def test_bench_line_keeps_the_contract(tmp_path):
     from pathlib import Path
 
     root = Path(__file__).resolve().parent.parent
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--batches", "4"],
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--batches", "4",
+                        "--dump-outputs", str(tmp_path / "dump")],
                        capture_output=True, text=True, timeout=600, cwd=str(root))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -114,3 +115,14 @@ def test_bench_line_keeps_the_contract(tmp_path):
     # CSR-included and CSR-excluded rates on the SAME pipeline
     pt = d["prepared_topology"]
     assert pt["batches_in_flight_per_gpu"] == d["config"]["batches_in_flight_per_gpu"] and pt["ms_per_step"] <= d["ms_per_step"] * 1.1
+    # --dump-outputs: the last timed step (step 19 of 20) forwarded batch 19 mod 4 = 3 of rank 0 (seed 3); its outputs match the oracle
+    import bench
+    from oracle import oracle as O
+
+    got = np.load(tmp_path / "dump" / "output.npy")
+    model = bench.build_model(bench.WORKLOADS["c2"])
+    batch = synthetic.make_batch("qm9", 4096, seed=3)
+    ref = O.forward_batched(model.spec(), [p.numpy() for p in model.canonical_params()], batch.x, batch.coo, batch.node_ptr,
+                            batch.edge_ptr)
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    assert np.abs(got - ref).max() < 1e-4 * max(1.0, float(np.abs(ref).max()))
