@@ -20,12 +20,13 @@ from helpers import canon, make_model, to_dev  # noqa: E402
 from gnnbuilder_amd import runtime  # noqa: E402
 from gnnbuilder_amd.batching import pack_graphs  # noqa: E402
 from oracle import oracle as O  # noqa: E402
+import ref64 as R  # noqa: E402
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 ZF = len(sys.argv) > 3 and sys.argv[3] == "zf"
 dev = torch.device("cuda:0")
-worst = worst_reduced = 0.0
+worst = worst_reduced = worst_ratio = 0.0
 for it in range(cases):
     conv = "gcn" if ZF else rng.choice(["gcn", "gin"])
     L = 2 if ZF else int(rng.integers(2, 7))
@@ -106,10 +107,18 @@ for it in range(cases):
     if not took or not err < 1e-4:
         print(f"FAIL case {it}: {tag}: fused={took} err={err:.3e}")
         sys.exit(1)
+    if math != 2:  # the fp32 budget against float64 (tests/ref64.py); math 2 (bf16x3) is reduced precision by design
+        try:
+            e, e32 = R.budget(got, R.forward64(model, batch, batch.x), ref)
+        except AssertionError as exc:
+            print(f"FAIL case {it}: {tag}: {exc}")
+            sys.exit(1)
+        worst_ratio = max(worst_ratio, R.ratio(e, e32))
     if it % 10 == 0:
         print(f"case {it}: {tag}: err {err:.2e}", flush=True)
     cm.close()
 runtime.set_option("stage_cut", 0)
 runtime.set_option("zf_head", 0)
 runtime.set_option("math", 0)
-print(f"{cases} cases, worst relative error {worst:.3e}" + f"; math 2 / 3 (bf16x3 / f16x3) cases: {worst_reduced:.3e}")
+print(f"{cases} cases, worst relative error {worst:.3e}" + f"; math 2 / 3 (bf16x3 / f16x3) cases: {worst_reduced:.3e}" +
+      f"; worst e/e32 against float64 (math 0 / 1 / 3): {worst_ratio:.2f}")

@@ -21,11 +21,12 @@ from helpers import canon, make_model, to_dev  # noqa: E402
 from gnnbuilder_amd import runtime  # noqa: E402
 from gnnbuilder_amd.batching import pack_graphs  # noqa: E402
 from oracle import oracle as O  # noqa: E402
+import ref64 as R  # noqa: E402
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 dev = torch.device("cuda:0")
-worst = worst_reduced = 0.0
+worst = worst_reduced = worst_ratio = 0.0
 MATH_DRAWN = len(sys.argv) > 3 and sys.argv[3] == "math"
 OPTS = {"fuse_pool": 1, "pna_fold_lin": 1, "first_ring": 1, "gemm_tail_split": 2, "pna_pagg": 1, "pna_first": 1, "sage_first_mean": 1}
 try:
@@ -98,6 +99,12 @@ try:
         if not err < 1e-4 or not np.array_equal(got, again):
             print(f"FAIL case {it}: {tag}: err={err:.3e} repeatable={np.array_equal(got, again)}")
             sys.exit(1)
+        try:  # the fp32 budget against float64 (tests/ref64.py), in every math mode drawn here (0, 1, 3)
+            e, e32 = R.budget(got, R.forward64(model, batch, batch.x), ref)
+        except AssertionError as exc:
+            print(f"FAIL case {it}: {tag}: {exc}")
+            sys.exit(1)
+        worst_ratio = max(worst_ratio, R.ratio(e, e32))
         if it % 10 == 0:
             print(f"case {it}: {tag}: err {err:.2e}", flush=True)
         cm.close()
@@ -105,4 +112,5 @@ finally:
     for k, v in OPTS.items():
         runtime.set_option(k, v)
     runtime.set_option("math", 0)
-print(f"{cases} cases, worst relative error {worst:.3e}" + (f"; math 3 (f16x3) cases: {worst_reduced:.3e}" if MATH_DRAWN else ""))
+print(f"{cases} cases, worst relative error {worst:.3e}" + (f"; math 3 (f16x3) cases: {worst_reduced:.3e}" if MATH_DRAWN else "") +
+      f"; worst e/e32 against float64: {worst_ratio:.2f}")

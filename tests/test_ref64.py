@@ -1,0 +1,225 @@
+"""The float64 reference (tests/ref64.py) and its acceptance rule, without a GPU.
+
+The reference is pinned: its conv modules reproduce the reference's PyG goldens, and the whole-model evaluation agrees with
+the fp32 oracle as closely as two evaluations of the same model can.  The rule has power: each fault below is the kind of
+precision slip a kernel can make, applied to a float64 copy of the model, and ``budget`` must reject every one of them
+while an honest fp32 evaluation (``model.float()``, another summation order than the oracle's) passes."""
+import copy
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import gnnbuilder_amd as gnnb
+import golden_util as G
+import ref64 as R
+from gnnbuilder_amd import synthetic
+from gnnbuilder_amd.batching import pack_graphs
+from helpers import batch_vector, canon, make_model
+from oracle import oracle as O
+
+CONV_STATE = {
+    "gcn": (gnnb.GCNConv_GNNB, ["conv.lin.weight", "conv.bias"], {}),
+    "gin": (gnnb.GINConv_GNNB, ["mlp.linear_0.weight", "mlp.linear_0.bias", "mlp.linear_1.weight", "mlp.linear_1.bias"],
+            {"eps": G.conv_kwargs("gin")["eps"]}),
+    "sage": (gnnb.SAGEConv_GNNB, ["conv.lin_l.weight", "conv.lin_l.bias", "conv.lin_r.weight"], {}),
+    "pna": (gnnb.PNAConv_GNNB, ["conv.pre_nns.0.0.weight", "conv.pre_nns.0.0.bias", "conv.post_nns.0.0.weight",
+                                "conv.post_nns.0.0.bias", "conv.lin.weight", "conv.lin.bias"],
+            {"delta": G.conv_kwargs("pna")["delta"]}),
+}
+
+
+def oracle(model, batch, x=None):
+    return O.forward_batched(model.spec(), canon(model), batch.x if x is None else x, batch.coo, batch.node_ptr, batch.edge_ptr)
+
+
+def with_output_activation(model, cls):
+    model.output_activation = cls
+    model.output_activation_module = cls(dim=-1)
+    return model
+
+
+@pytest.mark.parametrize("kind", ["gcn", "gin", "sage", "pna"])
+def test_float64_conv_layers_reproduce_pyg_golden(kind):
+    cls, names, kw = CONV_STATE[kind]
+    conv = cls(G.F, G.F, **kw)
+    sd = conv.state_dict()
+    for n, w in zip(names, G.conv_weights(kind)):
+        sd[n] = torch.from_numpy(np.array(w))
+    conv.load_state_dict(sd)
+    x, coo = G.graph()
+    assert np.abs(R.layer64(conv, x, coo) - G.conv_golden(kind)).max() < 1e-6
+
+
+def test_float64_weight_free_convs_reproduce_pyg_golden():
+    x, coo = G.graph()
+    assert np.abs(R.simple64(x, coo) - G.conv_golden("simple")).max() < 1e-6
+    assert np.abs(R.lg64(x, coo) - G.conv_golden("lg")).max() < 1e-6
+    gine = R.gine64(x, coo, G.edge_features(), G.gine_weights(), eps=G.conv_kwargs("gine")["eps"])
+    assert np.abs(gine - G.f32("tb_gine_output", (G.N, G.F))).max() < 1e-6
+
+
+def test_float64_weight_free_convs_on_batches_match_the_oracle():
+    rng = np.random.default_rng(3)
+    b = synthetic.make_batch("molhiv", 20, seed=4)
+    x = rng.uniform(-1, 1, (b.num_nodes, 7)).astype(np.float32)
+    ea = rng.uniform(-1, 1, (b.num_edges, 5)).astype(np.float32)
+    ws = [rng.uniform(-0.5, 0.5, s).astype(np.float32) for s in ((7, 5), (7,), (16, 7), (16,), (12, 16), (12,))]
+    for g in range(b.num_graphs):
+        lo, hi = b.node_ptr[g], b.node_ptr[g + 1]
+        xg, cg = x[lo:hi], b.coo[b.edge_ptr[g]:b.edge_ptr[g + 1]] - lo
+        for kind, f64 in (("simple", R.simple64), ("lg", R.lg64)):
+            assert np.abs(f64(xg, cg) - O.conv(kind, xg, cg, [])).max() < 4e-6
+        eg = ea[b.edge_ptr[g]:b.edge_ptr[g + 1]]
+        assert np.abs(R.gine64(xg, cg, eg, ws, eps=0.3) - O.gine_conv(xg, cg, eg, ws, eps=0.3)).max() < 4e-6
+
+
+def test_pool64_keeps_trailing_empty_graphs():
+    b = pack_graphs([(np.ones((2, 3), np.float32), np.zeros((0, 2), np.int32)), (np.zeros((0, 3), np.float32), np.zeros((0, 2), np.int32))])
+    p = R.pool64(np.array([[1.0, -2, 3], [-1, -4, 5]]), b, ("add", "mean", "max"))
+    assert p.shape == (2, 9)
+    assert np.array_equal(p[0], [0, -6, 8, 0, -3, 4, 1, -2, 5]) and not p[1].any()
+
+
+@pytest.mark.parametrize("act", ["relu", "tanh", "gelu", "sigmoid"])
+@pytest.mark.parametrize("conv", ["gcn", "gin", "sage", "pna"])
+def test_forward64_agrees_with_the_fp32_oracle(conv, act):
+    batch = synthetic.make_batch("qm9", 80, seed=5)
+    for skip, pools, out_act in ((True, ("add", "mean", "max"), None), (False, ("max", "add"), torch.nn.Softmax),
+                                 (True, ("mean", "max"), torch.nn.LogSoftmax)):
+        model = make_model(conv, hidden=32, layers=3, act=act, skip=skip, pools=pools, mlp_act=act, task_out=5, seed=2)
+        if out_act is not None:
+            with_output_activation(model, out_act)
+        ref, base = R.forward64(model, batch, batch.x), oracle(model, batch)
+        s = np.abs(ref).max()
+        assert np.abs(base - ref).max() <= 4e-6 * s, (skip, pools, out_act)
+        assert np.array_equal(R.run(copy.deepcopy(model), batch, batch.x), model(torch.from_numpy(batch.x), R.edge_index(batch.coo),
+                                                                                 torch.from_numpy(batch_vector(batch))).detach().numpy())
+
+
+# --------------------------------------------------------------------------- the budget has power
+# (2-layer d128 models on 500 QM9-shaped graphs: the shape of the benched stack)
+def fault_model(act="relu"):
+    return make_model("gcn", hidden=128, layers=2, act=act, mlp_act=act, seed=7)
+
+
+def fault_batch():
+    return synthetic.make_batch("qm9", 500, seed=9)
+
+
+class _Pool(gnnb.GlobalPooling):
+    """Global pooling with one deliberate slip: ``max_from_zero`` (max starts at 0, not at the first row) or ``mean_rel``
+    (the mean columns scaled by 1 + mean_rel, as an unrefined reciprocal of the node count would leave them)."""
+
+    def __init__(self, aggrs, max_from_zero=False, mean_rel=0.0):
+        super().__init__(aggrs)
+        self.max_from_zero, self.mean_rel = max_from_zero, mean_rel
+
+    def forward(self, x, index=None, dim_size=None):
+        outs, d = [], x.size(1)
+        for a in self.aggrs:
+            o = gnnb.GlobalPooling([a])(x, index, dim_size)
+            if a == "max" and self.max_from_zero:
+                o = x.new_zeros(dim_size, d).scatter_reduce(0, index.unsqueeze(-1).expand(-1, d), x, "amax", include_self=True)
+            if a == "mean":
+                o = o * (1.0 + self.mean_rel)
+            outs.append(o)
+        return torch.cat(outs, dim=-1)
+
+
+def _gcn_dinv_fp16(self, x, edge_index):
+    n = x.size(0)
+    edge_index = edge_index[:, edge_index[0] != edge_index[1]]
+    src, dst = edge_index[0], edge_index[1]
+    deg = torch.zeros(n, dtype=x.dtype).index_add_(0, dst, torch.ones_like(dst, dtype=x.dtype))
+    dinv = (deg + 1.0).pow(-0.5).half().to(x.dtype)
+    h = self.lin(x)
+    out = h * (dinv * dinv).unsqueeze(-1)
+    out = out.index_add(0, dst, h[src] * (dinv[src] * dinv[dst]).unsqueeze(-1))
+    return out + self.bias
+
+
+def _drop_hub_edge(batch):
+    coo = batch.coo
+    real = coo[coo[:, 0] != coo[:, 1]]
+    hub = int(np.bincount(real[:, 1]).argmax())
+    k = int(np.flatnonzero((coo[:, 1] == hub) & (coo[:, 0] != hub))[0])
+    return np.delete(coo, k, axis=0)
+
+
+def _negative_batch():
+    """QM9-shaped graphs plus a 1-node and a 0-node graph; features scaled so that tanh with a last-layer bias of -2 leaves
+    every pooled activation negative."""
+    b = fault_batch()
+    graphs = [b.graph(g) for g in range(b.num_graphs)]
+    graphs[3] = (graphs[3][0][:1], np.zeros((0, 2), np.int32))
+    graphs[7] = (graphs[7][0][:0], np.zeros((0, 2), np.int32))
+    return pack_graphs([(0.25 * x, c) for x, c in graphs])
+
+
+def _negative_model():
+    model = fault_model("tanh")
+    with torch.no_grad():
+        model.gnn_convs[-1].conv.bias.fill_(-2.0)
+    return model
+
+
+def _apply(fault, m64, batch):
+    """Put ``fault`` into the float64 model ``m64``; returns the edges to run it on."""
+    if fault == "a_weights_16_bits":
+        w = m64.gnn_convs[1].conv.lin.weight
+        with torch.no_grad():
+            w.copy_(torch.from_numpy(R.round_bits(w.numpy(), 16)))
+    elif fault == "b_hub_edge_dropped":
+        return _drop_hub_edge(batch)
+    elif fault == "c_gcn_dinv_fp16":
+        for c in m64.gnn_convs:
+            c.conv.forward = types.MethodType(_gcn_dinv_fp16, c.conv)
+    elif fault == "d_gelu_tanh_form":
+        for i in range(len(m64.gnn_activations)):
+            m64.gnn_activations[i] = torch.nn.GELU(approximate="tanh")
+        m64.mlp_head.mlp = torch.nn.Sequential(*[torch.nn.GELU(approximate="tanh") if isinstance(m, torch.nn.GELU) else m
+                                                 for m in m64.mlp_head.mlp])
+    elif fault == "e_max_pool_from_zero":
+        m64.global_pooling = _Pool(m64.global_pooling.aggrs, max_from_zero=True)
+    elif fault == "f_mean_pool_rcp_2e-12":
+        m64.global_pooling = _Pool(m64.global_pooling.aggrs, mean_rel=2.0 ** -12)
+    return batch.coo
+
+
+FAULTS = {"a_weights_16_bits": "relu", "b_hub_edge_dropped": "relu", "c_gcn_dinv_fp16": "relu", "d_gelu_tanh_form": "gelu",
+          "e_max_pool_from_zero": "tanh", "f_mean_pool_rcp_2e-12": "relu"}
+
+
+@pytest.mark.parametrize("fault", list(FAULTS))
+def test_budget_rejects_the_injected_fault(fault):
+    model = _negative_model() if fault.startswith("e_") else fault_model(FAULTS[fault])
+    batch = _negative_batch() if fault.startswith("e_") else fault_batch()
+    ref, base = R.forward64(model, batch, batch.x), oracle(model, batch)
+    if fault.startswith("e_"):
+        m64 = copy.deepcopy(model).double()
+        h = R._t(batch.x)
+        with torch.no_grad():
+            for conv, act in zip(m64.gnn_convs, m64.gnn_activations):
+                h = act(conv(h, R.edge_index(batch.coo)))
+        assert h.max() < 0, "the case needs every last-layer activation negative"
+        assert (np.diff(batch.node_ptr) == 0).any() and (np.diff(batch.node_ptr) == 1).any()
+    # an honest fp32 evaluation in another summation order passes ...
+    R.budget(R.run(copy.deepcopy(model).float(), batch, batch.x), ref, base, what="model.float()")
+    # ... the fault does not
+    m64 = copy.deepcopy(model).double()
+    coo = _apply(fault, m64, batch)
+    with pytest.raises(AssertionError, match="e32"):
+        R.budget(R.run(m64, batch, batch.x, coo), ref, base)
+
+
+def test_budget_reports_the_worst_element():
+    ref = np.array([[1.0, -2.0], [0.5, 0.25]])
+    base = ref + 1e-7
+    got = ref.copy()
+    got[1, 0] += 1e-5
+    with pytest.raises(AssertionError, match=r"worst element \(1, 0\)"):
+        R.budget(got, ref, base)
+    assert R.budget(ref + 2e-7, ref, base)[1] == pytest.approx(5e-8)
+    assert R.errors(np.zeros(3), np.zeros(3), np.zeros(3))[:2] == (0.0, 0.0)
