@@ -15,7 +15,12 @@ the ranks are the launcher's.  WORLD_SIZE != --gpus is an error.
 The timed region (K steps between barrier + synchronize on both sides, MAX over ranks) is repeated
 `--repeats` times; `value` is computed from the MEDIAN repeat, min / max are reported beside it.
 
-Prints ONE JSON line on rank 0 (contract in the task prompt) with these extra objects:
+A plain run does only what `value` needs: set up, warm up, time the K steps (`--repeats` regions), write the outputs
+(`--dump-outputs`) and print the line.  Everything else -- the other form of the step, the opt-in math modes, the
+CSR-excluded rate, the roofline legs, BASELINE's other configs, the CPU baselines -- runs behind `--full`, after `value` is
+computed (the --no-* options drop single legs of a --full run).
+
+Prints ONE JSON line on rank 0 (contract in the task prompt); with --full it carries these extra objects:
   roofline      -- the kernel that dominates the timed step.  c2 and c3 (GCN / GIN stacks, graphs within the
                    max_graph_nodes promise) run the fused stack kernel k_gcn2_fused: bound = fp32 MFMA (c3 without
                    the promise: the K=N=128 update GEMM, k_linear_wlds); c4 / c5: the large-K segmented GEMM (k_linear_dma);
@@ -706,9 +711,14 @@ def main():
                     help="1: 2-layer GCN workloads on molecule-sized graphs run the software-pipelined step as `value` (gnnb_forward_prepared_prep_next: "
                          "forward of batch i + graph prep of the stream's next batch in one call, the prep as extra workgroups of the readout kernel); "
                          "0 (default): gnnb_forward_batched per step, the pipelined form reported beside it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the brief c3 / c4 / c5 legs of the default (c2, one GPU) line")
+    ap.add_argument("--full", action="store_true",
+                    help="after `value`, run every side leg as well: the other form of the step, the opt-in math modes, the "
+                         "CSR-excluded rate, the roofline legs, the c3 / c4 / c5 legs (c2, one GPU) and the CPU baselines; "
+                         "without it the run measures `value` alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the roofline legs, the opt-in math modes and the other form of the step")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the brief c3 / c4 / c5 legs of the c2, one-GPU line")
     ap.add_argument("--roofline-only", action="store_true",
                     help="only the HBM-regime gather-aggregate loop (for a rocprofv3 run whose kernel average is that loop)")
     ap.add_argument("--dry-launch", action="store_true",
@@ -740,6 +750,10 @@ def main():
     from gnnbuilder_amd.batching import shard_bounds
 
     dry = args.dry_launch
+    # the side legs run under --full only (a --dry-launch line has none); `roofline` also covers the opt-in math modes and the
+    # other form of the step
+    full = args.full and not dry
+    roofline = full and not args.no_roofline
     if os.environ.get("BENCH_TEST_FAIL_RANK") == str(rank):  # launcher test hook: this rank dies at start-up
         print(f"bench.py: rank {rank} exiting 3 (BENCH_TEST_FAIL_RANK)", file=sys.stderr)
         sys.exit(3)
@@ -864,7 +878,7 @@ def main():
         can_prep_next = (w["conv"] == "gcn" and w["layers"] == 2 and bool(max_graph) and max_graph <= 64 and
                          all(sg is None for sg in segs) and args.steps > nstreams)
         prep_next = can_prep_next and args.prep_next == "1"
-        can_prep_next = can_prep_next and (prep_next or not args.no_roofline)  # (the other form is a side leg of the full line)
+        can_prep_next = can_prep_next and (prep_next or roofline)  # (the other form is a side leg of the --full line)
         if can_prep_next:
             pipe.enable_prep_next(model, max_graph, max_degree)
 
@@ -918,7 +932,7 @@ def main():
     graphs_done = float(sum(batches[i % len(batches)].num_graphs for i in range(args.steps)))
     # the same region in the other form of the step (see can_prep_next above)
     other_form = None
-    if not dry and can_prep_next and not args.no_roofline:
+    if can_prep_next and roofline:
         other = plain_step if prep_next else pipelined_step
         for i in range(args.warmup):
             other(i)
@@ -934,7 +948,7 @@ def main():
     # opt-in math mode (NOT the headline): the wide update of the fused GCN stack as six bf16 MFMA products of
     # an exact 3-way split of both fp32 operands, fp32 accumulate; same steps, same batches
     split_rate = None
-    if not dry and not args.no_roofline:
+    if roofline:
         runtime.set_option("math", 1)
         for i in range(args.warmup):
             step(i)
@@ -944,7 +958,7 @@ def main():
         split_ms = el2 / args.steps * 1e3
     # opt-in REDUCED-precision mode (never `value`): k_gcn2_zf's wide update on hi + mid bf16 pieces, three products ("bf16x3")
     reduced = None
-    if not dry and not args.no_roofline and (w["conv"] in ("sage", "pna", "gin") or (w["conv"] == "gcn" and w["layers"] > 2)):
+    if roofline and (w["conv"] in ("sage", "pna", "gin") or (w["conv"] == "gcn" and w["layers"] > 2)):
         reduced = {"how": "gnnb_set_option(\"math\", 3) / GNNB_MATH=3: the layer-by-layer LDS-DMA GEMMs / the wide products of the GIN and deep-GCN "
                           "stack kernel as 3 fp16 MFMA products (hi.hi + hi.mid + mid.hi) on "
                           "round-to-nearest hi + mid fp16 pieces of both operands, fp32 accumulate: ~22 significant bits per product, fp16's RANGE "
@@ -959,7 +973,7 @@ def main():
         el3 = float(np.median([timed_region() for _ in range(repeats)]))
         runtime.set_option("math", 0)
         reduced["f16x3"] = {"value": graphs_done / el3, "unit": "graphs/s", "ms_per_step": el3 / args.steps * 1e3}
-    if not dry and not args.no_roofline and w["conv"] == "gcn" and w["layers"] == 2:
+    if roofline and w["conv"] == "gcn" and w["layers"] == 2:
         reduced = {"how": "gnnb_set_option(\"math\", 2 | 3) / GNNB_MATH: H.W1^T of k_gcn2_zf as 3 MFMA products (hi.hi + hi.mid + mid.hi) on round-to-nearest "
                           "hi + mid 16-bit pieces of both operands, fp32 accumulate.  2 = bf16 pieces: ~18 significant bits per product, fp32's "
                           "range; 3 = fp16 pieces: ~22 bits, fp16's RANGE (|values| < 65504, pieces below 6e-8 lost).  REDUCED precision, "
@@ -978,7 +992,7 @@ def main():
     # `value` -- the same streams, one prepared batch per workspace, the same K-step region and statistic -- so the two are
     # comparable; the one-stream figure (a single workspace, forwards back to back) is kept beside it
     ms_noprep = ms_noprep_1s = ms_noprep_1s_lat = None
-    if not dry:
+    if full:
         pipe.prepare_topology()
         for i in range(max(args.warmup, pipe.nstreams)):
             pipe.step_prepared(i)
@@ -1092,7 +1106,7 @@ def main():
     if reduced is not None:
         result["opt_in_math_reduced_precision"] = reduced
 
-    if not args.no_roofline:
+    if roofline:
         alg_bytes, agg = measure_aggregate_roofline(cm, dev_batches[0], w["hidden"], dev)
         ceiling = copy_ceiling(batches[0].num_nodes, w["hidden"], dev)
         if "copy_same_launch_shape" in agg:
@@ -1172,7 +1186,7 @@ def main():
             result["roofline"] = gather
         result["roofline_gather_aggregate"] = gather
         result["roofline_update"] = upd
-    if world == 1 and args.workload == "c2" and not args.no_other_configs:
+    if full and world == 1 and args.workload == "c2" and not args.no_other_configs:
         # BASELINE's other single-GPU configs, briefly (appended after `value` was computed: the C2 region is untouched)
         del pipe, cm
         torch.cuda.synchronize()
@@ -1183,7 +1197,7 @@ def main():
             except Exception as e:  # never lose the bench line to a side leg
                 oc.append({"name": name, "error": repr(e)})
         result["other_configs"] = oc
-    if not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(model, batches)
 
     print(json.dumps(result))

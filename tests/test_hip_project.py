@@ -74,7 +74,7 @@ def test_generated_top_symbol_via_ctypes(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_line_keeps_the_contract(tmp_path):
-    """bench.py prints ONE JSON line with the contract's keys plus the roofline / cpu_baseline objects
+    """bench.py --full prints ONE JSON line with the contract's keys plus the roofline / cpu_baseline objects
     (short run, bounded CPU sample)."""
     import json
     import subprocess
@@ -83,7 +83,7 @@ def test_bench_line_keeps_the_contract(tmp_path):
 
     root = Path(__file__).resolve().parent.parent
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--batches", "4",
-                        "--dump-outputs", str(tmp_path / "dump")],
+                        "--full", "--dump-outputs", str(tmp_path / "dump")],
                        capture_output=True, text=True, timeout=600, cwd=str(root))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -116,6 +116,48 @@ def test_bench_line_keeps_the_contract(tmp_path):
     pt = d["prepared_topology"]
     assert pt["batches_in_flight_per_gpu"] == d["config"]["batches_in_flight_per_gpu"] and pt["ms_per_step"] <= d["ms_per_step"] * 1.1
     # --dump-outputs: the last timed step (step 19 of 20) forwarded batch 19 mod 4 = 3 of rank 0 (seed 3); its outputs match the oracle
+    import bench
+    from oracle import oracle as O
+
+    got = np.load(tmp_path / "dump" / "output.npy")
+    model = bench.build_model(bench.WORKLOADS["c2"])
+    batch = synthetic.make_batch("qm9", 4096, seed=3)
+    ref = O.forward_batched(model.spec(), [p.numpy() for p in model.canonical_params()], batch.x, batch.coo, batch.node_ptr,
+                            batch.edge_ptr)
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    assert np.abs(got - ref).max() < 1e-4 * max(1.0, float(np.abs(ref).max()))
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_measures_value_alone(tmp_path):
+    """bench.py without --full: the contract's keys, `value` from the repeats of the timed region, and none of the side legs
+    (they run under --full only); --dump-outputs still writes the last timed step."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parent.parent
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--batches", "4",
+                        "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=300, cwd=str(root))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "repeats"):
+        assert k in d, k
+    assert d["metric"] == "graphs/sec whole-node (batched QM9, GCN d=128)" and d["unit"] == "graphs/s" and d["dtype"] == "f32"
+    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["higher_is_better"] is True
+    assert d["value"] > 1e6 and d["repeats"]["value_min"] <= d["value"] <= d["repeats"]["value_max"]
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 * 20 - 20 * 4096) < 1e-6 * 20 * 4096
+    assert d["config"]["path"] == "stack_zf"
+    for k in ("roofline", "roofline_gather_aggregate", "roofline_update", "cpu_baseline", "other_configs", "opt_in_math_bf16x6",
+              "opt_in_math_reduced_precision", "prep_next_pipeline", "forward_batched_per_step"):
+        assert k not in d, k
+    assert d["prepared_topology"] is None and d["ms_per_step_prepared_topology"] is None
+    # step 19 of 20 forwarded batch 19 mod 4 = 3 (seed 3)
     import bench
     from oracle import oracle as O
 

@@ -105,7 +105,7 @@ def test_bench_two_gpus_one_batch_shard_on_the_hip_path():
     """`python bench.py --gpus 2 --shard one-batch`: the command the driver's scaling run issues (its own ranks, nccl =
     RCCL, the HIP path -- no --dry-launch), on the plumbing-sized workload; one JSON line, both ranks counted."""
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--workload", "tiny", "--shard", "one-batch",
-                        "--steps", "5", "--warmup", "2", "--repeats", "3", "--batches", "2", "--no-cpu-baseline"],
+                        "--steps", "5", "--warmup", "2", "--repeats", "3", "--batches", "2", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=_clean_env(), timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]

@@ -2,7 +2,7 @@
 # Collect the round's rocprofv3 evidence on a GPU box (run through gpurun); outputs under gpurun_out/prof/.
 #   tools/profile_r.sh [workloads ...]      (default: c2 c3 c3t c4 c5)
 # Per workload w:
-#   plain_$w.log  `python3 bench.py --workload w --steps 100` WITHOUT the profiler: the JSON line that is kept (under the
+#   plain_$w.log  `python3 bench.py --full --workload w --steps 100` WITHOUT the profiler: the JSON line that is kept (under the
 #                 profiler the back-to-back HIP-event loops of the roofline legs run up to 2x slower -- its per-dispatch
 #                 instrumentation -- so the line printed there is not a measurement of them)
 #   bench_$w/     rocprofv3 --kernel-trace --stats of the same command: the per-kernel table
@@ -18,7 +18,7 @@ OUT=$R/gpurun_out/prof
 rm -rf "$OUT"; mkdir -p "$OUT"
 WL=${@:-c2 c3 c4 c5}
 for w in $WL; do
-  extra="--no-other-configs"   # (every tracked line keeps its cpu_baseline; the brief c3 / c4 / c5 legs of the default line would mix their kernels into the c2 table)
+  extra="--full --no-other-configs"   # (every tracked line keeps its roofline and cpu_baseline; the brief c3 / c4 / c5 legs of the c2 line would mix their kernels into the c2 table)
   python3 bench.py --workload $w --steps 100 $extra > "$OUT/plain_$w.log" 2>&1
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_$w" -o bench -- python3 bench.py --workload $w --steps 100 $extra > "$OUT/bench_$w.log" 2>&1
   case $w in ref6_*) continue;; esac   # (the published-model workloads: the line and the kernel table only)
