@@ -462,7 +462,7 @@ int gnnb_model_create(const gnnb_model_desc *desc, const float *const *host_para
                 if (fo > 32) { // (any input width: whole 32-wide chunks take k_linear_dma's row-class mode, others the generic kernel's)
                     const size_t K5 = 5 * fi;
                     std::vector<float> wc((size_t)GNNB_DEG_CLASSES * fo * K5), bc((size_t)GNNB_DEG_CLASSES * fo);
-                    std::vector<double> wa(4 * fi), sq(fi);
+                    std::vector<double> wa(4 * fi), sq(fi), sqw(fi);
                     const float *wq = p[0]; // W_pre [F, 2F]: columns [0, F) act on the destination x_i (lib:1801-1802), bias p[1]
                     for (int c = 0; c < GNNB_DEG_CLASSES; c++) {
                         const float lg = logf((float)std::max(c, 1) + 1.0f);
@@ -478,12 +478,18 @@ int gnnb_model_create(const gnnb_model_desc *desc, const float *const *host_para
                             if (c > 0) {
                                 for (size_t k = 0; k < fi; k++)
                                     sq[k] = wa[k] + wa[fi + k] + wa[2 * fi + k]; // S_c[o][k]: max + min + mean
-                                for (size_t j = 0; j < fi; j++) {               // (S_c Wq)[o][j] = sum_k S_c[o][k] Wq[k][j]
-                                    double a = (double)src[j];
-                                    for (size_t k = 0; k < fi; k++)
-                                        a += sq[k] * (double)wq[k * 2 * fi + j];
-                                    dst[o * K5 + j] = (float)a;
+                                // (S_c Wq)[o][j] = sum_k S_c[o][k] Wq[k][j], k ascending from src[j] as before, but walked
+                                // along Wq's rows: the column walk (stride 2F) made a 1024-wide PNA layer's upload ~80 s
+                                for (size_t j = 0; j < fi; j++)
+                                    sqw[j] = (double)src[j];
+                                for (size_t k = 0; k < fi; k++) {
+                                    const double s = sq[k];
+                                    const float *wr = wq + k * 2 * fi;
+                                    for (size_t j = 0; j < fi; j++)
+                                        sqw[j] += s * (double)wr[j];
                                 }
+                                for (size_t j = 0; j < fi; j++)
+                                    dst[o * K5 + j] = (float)sqw[j];
                                 for (size_t k = 0; k < fi; k++)
                                     bsum += sq[k] * (double)p[1][k];
                             } else {
@@ -1084,7 +1090,7 @@ int gnnb_pna_product_aggregate(gnnb_workspace *ws, const float *x_dev, const flo
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_pna_product_aggregate");
     hipError_t he = launch_pna_pagg(ws->t, x_dev, width, wb_dev, ldw, out_dev, (hipStream_t)stream);
     if (he == hipErrorNotSupported)
-        return fail(GNNB_ERR_INVALID, "gnnb_pna_product_aggregate takes widths 128 / 64 / 32, 16-byte aligned operands and a workspace "
+        return fail(GNNB_ERR_INVALID, "gnnb_pna_product_aggregate takes widths 128 / 64 / 32, 16-byte aligned operands, an ldw that is a multiple of 4 and a workspace "
                                       "whose max_graph_nodes promise fits a 64-row stage (promise + tile rows - 1 <= 64), without a large "
                                       "segment; the option pna_pagg must be on (it is %s)", options().pna_pagg ? "on" : "OFF");
     GNNB_HIP_TRY(he);
@@ -1113,7 +1119,8 @@ int gnnb_aggregate(gnnb_workspace *ws, int agg_kind, const float *x_dev, const f
     return GNNB_OK;
 }
 
-static int build_gemm(GemmArgs &g, const gnnb_gemm_seg *segs, int num_segs, const float *w, int ldw)
+// rows: M of the call (0: nothing is read, so an empty operand may come without an address -- torch gives none)
+static int build_gemm(GemmArgs &g, const gnnb_gemm_seg *segs, int num_segs, const float *w, int ldw, int rows = 1)
 {
     if (num_segs < 1 || num_segs > 4 || !segs)
         return fail(GNNB_ERR_INVALID, "gnnb_linear takes 1..4 segments");
@@ -1123,7 +1130,7 @@ static int build_gemm(GemmArgs &g, const gnnb_gemm_seg *segs, int num_segs, cons
     g.cpre[0] = 0;
     for (int s = 0; s < 4; s++) {
         if (s < num_segs) {
-            if (!segs[s].a_dev || segs[s].k < 1 || segs[s].lda < segs[s].k)
+            if ((!segs[s].a_dev && rows > 0) || segs[s].k < 1 || segs[s].lda < segs[s].k)
                 return fail(GNNB_ERR_INVALID, "bad GEMM segment %d", s);
             g.a[s] = segs[s].a_dev;
             g.rs[s] = segs[s].rowscale_dev;
@@ -1147,12 +1154,12 @@ static int build_gemm(GemmArgs &g, const gnnb_gemm_seg *segs, int num_segs, cons
 static int linear_segs(const StreamK *sk_owned, const gnnb_gemm_seg *segs, int num_segs, const float *w_dev, int ldw,
                        const float *bias_dev, const float *skip_dev, float *y_dev, int M, int N, int act, void *stream)
 {
-    if (!w_dev || !y_dev || M < 0 || N < 1)
+    if (!w_dev || (!y_dev && M > 0) || M < 0 || N < 1)
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_linear");
     if (act < 0 || act > GNNB_ACT_NONE)
         return fail(GNNB_ERR_INVALID, "unknown activation %d", act);
     GemmArgs g;
-    int rc = build_gemm(g, segs, num_segs, w_dev, ldw);
+    int rc = build_gemm(g, segs, num_segs, w_dev, ldw, M);
     if (rc != GNNB_OK)
         return rc;
     GNNB_HIP_TRY(launch_linear(g, w_dev, ldw, bias_dev, skip_dev, y_dev, M, N, act, (hipStream_t)stream, nullptr, nullptr, sk_owned));

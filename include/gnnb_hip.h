@@ -290,7 +290,8 @@ int gnnb_aggregate(gnnb_workspace *ws, int agg_kind, const float *x_dev, const f
  * 2 width - 1: pass weight + width, ldw = 2 width) -- the reference's per-edge `linear` (gnn_builder_lib.h:1807) split per
  * node, + pna_conv_agg (:1750-1834) without a destination term (the degree-class form folds that term into the post-NN's
  * weights).  p never goes to HBM: whole graphs are staged in LDS, so the workspace needs a max_graph_nodes promise that fits
- * a 64-row stage; widths 128 / 64 / 32.  The forward takes this route by itself (option pna_pagg); this entry exists for
+ * a 64-row stage; widths 128 / 64 / 32; x_dev, wb_dev and out_dev 16-byte aligned and ldw a multiple of 4 (anything else:
+ * GNNB_ERR_INVALID, nothing launched).  The forward takes this route by itself (option pna_pagg); this entry exists for
  * measurements and tests. */
 int gnnb_pna_product_aggregate(gnnb_workspace *ws, const float *x_dev, const float *wb_dev, int ldw, float *out_dev, int width,
                                void *stream);
@@ -308,7 +309,8 @@ int gnnb_edge_index_table_to_host(gnnb_workspace *ws, int32_t *edge_index_table 
 /* Dense update on the matrix cores: for up to 4 K-segments s,
  *   Y[M,N] = act( sum_s (rowscale_s[m] * A_s[M,K_s]) . W[:, koff_s : koff_s+K_s]^T + bias + skip )
  * W is row-major [N, ldw] (torch Linear layout); A_s row-major with leading dim lda_s.
- * One segment with rowscale NULL is a plain batched `linear` (gnn_builder_lib.h:808-905). */
+ * One segment with rowscale NULL is a plain batched `linear` (gnn_builder_lib.h:808-905).
+ * M = 0 returns GNNB_OK and touches nothing; a_dev, rowscale_dev, skip_dev and y_dev may then be NULL. */
 typedef struct gnnb_gemm_seg {
     const float *a_dev;        /* [M, lda] */
     const float *rowscale_dev; /* [M] or NULL */

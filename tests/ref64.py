@@ -4,6 +4,12 @@
 copy; ``layer64`` / ``pool64`` are its stage entry points.  GINE / Simple / LGConv have no ``GNNModel`` form: ``gine64``,
 ``simple64`` and ``lg64`` restate the oracle's formulas in float64 numpy.
 
+The stage entry points (``gnnb_aggregate``, ``gnnb_linear``, ...) have float64 restatements of their own: ``gcn_agg64``,
+``sum_agg64``, ``mean_agg64``, ``pna_agg64``, ``simple64``, ``lg64`` (``gnnb_hip.h`` ``gnnb_agg``) and ``linear64``.  Each takes
+a ``dtype``: float32 gives the fp32 evaluation the budget measures against -- neighbours summed in CSR order (COO order per
+destination: ``np.add.at`` is sequential), the self term last, as the kernels do.  ``workspace_edges`` applies the documented
+self-loop rule (``gnnb_hip.h``, ``gnnb_graph_prep``): the tables of a GCN workspace hold no explicit ``(v, v)`` edge.
+
 ``budget(got, ref, base)`` asks a result to be as accurate as a plain fp32 evaluation of the same model: with
 ``s = max|ref|``, ``e = max|got - ref| / s`` and ``e32 = max|base - ref| / s`` (``base``: the fp32 oracle's output for the
 same inputs) it accepts ``e <= K * e32 + F``.  K and F are calibrated on the MI355X.
@@ -68,26 +74,128 @@ def pool64(h, batch, pools):
 
 def _csr_sums(x, coo, n, scale=None):
     src, dst = np.asarray(coo).reshape(-1, 2).T
-    out = np.zeros((n, x.shape[1]), np.float64)
+    out = np.zeros((n, x.shape[1]), x.dtype)
     msg = x[src] if scale is None else x[src] * scale[:, None]
     np.add.at(out, dst, msg)
     return out
 
 
-def simple64(x, coo):
+def workspace_edges(coo, gcn_workspace):
+    """The edges a workspace's tables hold: a GCN workspace drops every explicit self loop (``gnnb_graph_prep``)."""
+    coo = np.asarray(coo).reshape(-1, 2)
+    return coo[coo[:, 0] != coo[:, 1]] if gcn_workspace else coo
+
+
+def _in_deg(coo, n):
+    return np.bincount(np.asarray(coo).reshape(-1, 2)[:, 1], minlength=n)[:n]
+
+
+def simple64(x, coo, dtype=np.float64):
     """SimpleConv (sum aggregation): ``sum_j x_j``."""
-    x = np.asarray(x, np.float64)
+    x = np.asarray(x, dtype)
     return _csr_sums(x, coo, x.shape[0])
 
 
-def lg64(x, coo):
+def lg64(x, coo, dtype=np.float64):
     """LGConv: ``sum_j x_j / sqrt(d_i d_j)`` with d = in-degree (every edge, self loops included), no self term."""
-    x = np.asarray(x, np.float64)
+    x = np.asarray(x, dtype)
     src, dst = np.asarray(coo).reshape(-1, 2).T
-    deg = np.bincount(dst, minlength=x.shape[0]).astype(np.float64)
+    deg = _in_deg(coo, x.shape[0]).astype(dtype)
     prod = deg[dst] * deg[src]
-    s = np.where(prod > 0, 1.0 / np.sqrt(np.maximum(prod, 1.0)), 0.0)
+    s = np.where(prod > 0, dtype(1) / np.sqrt(np.maximum(prod, dtype(1))), dtype(0)).astype(dtype)
     return _csr_sums(x, coo, x.shape[0], s)
+
+
+def gcn_agg64(x, coo, dtype=np.float64):
+    """PyG ``gcn_norm`` aggregate with exactly one self loop per node: ``sum_j x_j / sqrt(d_i d_j) + x_i / d_i``,
+    d = 1 + in-degree over ``coo`` (pass ``workspace_edges(coo, True)`` for a GCN workspace: its explicit self loops are
+    replaced, not counted; on any other workspace they are ordinary edges)."""
+    x = np.asarray(x, dtype)
+    src, dst = np.asarray(coo).reshape(-1, 2).T
+    dinv = (dtype(1) / np.sqrt(_in_deg(coo, x.shape[0]).astype(dtype) + dtype(1))).astype(dtype)
+    out = _csr_sums(x, coo, x.shape[0], (dinv[dst] * dinv[src]).astype(dtype))
+    return out + x * (dinv * dinv)[:, None]
+
+
+def sum_agg64(x, coo, eps=0.0, dtype=np.float64):
+    """GIN's aggregate: ``sum_j x_j + (1 + eps) x_i`` (``1 + eps`` formed in fp32, as the kernels take ``eps``)."""
+    x = np.asarray(x, dtype)
+    return _csr_sums(x, coo, x.shape[0]) + x * dtype(np.float32(1) + np.float32(eps))
+
+
+def mean_agg64(x, coo, dtype=np.float64):
+    """SAGE's aggregate: ``mean_j x_j``, 0 without a neighbour."""
+    x = np.asarray(x, dtype)
+    deg = _in_deg(coo, x.shape[0]).astype(dtype)
+    return _csr_sums(x, coo, x.shape[0]) / np.maximum(deg, dtype(1))[:, None]
+
+
+def gine_agg64(x, coo, edge_term, eps=0.0, dtype=np.float64):
+    """GINE's aggregate (``gnnb_aggregate_edges``): ``(1 + eps) x_i + sum_j relu(x_j + edge_term[e])``, ``edge_term`` [E, w]
+    in COO order."""
+    x = np.asarray(x, dtype)
+    src, dst = np.asarray(coo).reshape(-1, 2).T
+    out = np.zeros_like(x)
+    np.add.at(out, dst, np.maximum(x[src] + np.asarray(edge_term, dtype), dtype(0)))
+    return out + x * dtype(np.float32(1) + np.float32(eps))
+
+
+PNA_STD_EPS = 1e-5
+
+
+def pna_agg64(x, coo, q=None, dtype=np.float64, clamp=True):
+    """PNA's aggregate ``[max | min | mean | std]_j (q_i + x_j)`` ([N, 4w]); ``q`` None: no destination term.  PyG's std:
+    ``sqrt(max(E[h^2] - E[h]^2, 1e-5))``, 0 where that is <= ``sqrt(1e-5)``; in-degree 0 gives 0 everywhere.
+    ``clamp=False`` is the fault the tests inject (the plain ``sqrt(max(var, 0))``)."""
+    x = np.asarray(x, dtype)
+    n, w = x.shape
+    src, dst = np.asarray(coo).reshape(-1, 2).T
+    h = x[src] + (np.asarray(q, dtype)[dst] if q is not None else dtype(0))
+    deg = _in_deg(coo, n)
+    s1, s2 = np.zeros((n, w), dtype), np.zeros((n, w), dtype)
+    np.add.at(s1, dst, h)
+    np.add.at(s2, dst, h * h)
+    mx, mn = np.full((n, w), -np.inf, dtype), np.full((n, w), np.inf, dtype)
+    np.maximum.at(mx, dst, h)
+    np.minimum.at(mn, dst, h)
+    has = (deg > 0)[:, None]
+    d = np.maximum(deg, 1).astype(dtype)[:, None]
+    mean = s1 / d
+    var = s2 / d - mean * mean
+    if clamp:
+        sd = np.sqrt(np.maximum(var, dtype(PNA_STD_EPS)))
+        sd = np.where(sd <= np.sqrt(dtype(PNA_STD_EPS)), dtype(0), sd)
+    else:
+        sd = np.sqrt(np.maximum(var, dtype(0)))
+    z = dtype(0)
+    return np.concatenate([np.where(has, mx, z), np.where(has, mn, z), np.where(has, mean, z), np.where(has, sd, z)], 1).astype(dtype)
+
+
+ACTS64 = {"none": lambda v: v, "relu": lambda v: torch.relu(v), "tanh": torch.tanh, "sigmoid": torch.sigmoid,
+          "gelu": lambda v: torch.nn.functional.gelu(v)}
+
+
+def linear64(segments, weight, bias=None, skip=None, act="none", dtype=torch.float64):
+    """``gnnb_linear``: ``act(sum_s (rowscale_s * A_s) . W[:, koff_s : koff_s + K_s]^T + bias + skip)``.  ``segments``:
+    (A [M, K_s], rowscale [M] or None) tensors or arrays, any strides; float32 ``dtype`` is the torch CPU fp32 product, its
+    4-column chunks summed in K order (one BLAS call over the whole K would sum more accurately than any GPU kernel, and
+    differently on every CPU)."""
+    t = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)  # noqa: E731
+    w = t(weight)
+    acc, koff = None, 0
+    for a, rs in segments:
+        a = t(a)
+        if rs is not None:
+            a = a * t(rs)[:, None]
+        for c in range(0, a.shape[1], 4):  # (fp32: 4-column chunks accumulated in order, as the kernels' MFMA K steps)
+            p = a[:, c:c + 4] @ w[:, koff + c:koff + min(c + 4, a.shape[1])].T
+            acc = p if acc is None else acc + p
+        koff += a.shape[1]
+    if bias is not None:
+        acc = acc + t(bias)
+    if skip is not None:
+        acc = acc + t(skip)
+    return ACTS64[act](acc).numpy()
 
 
 def gine64(x, coo, edge_attr, weights, eps=0.0):

@@ -16,7 +16,7 @@ import golden_util as G
 import ref64 as R
 from gnnbuilder_amd import synthetic
 from gnnbuilder_amd.batching import pack_graphs
-from helpers import batch_vector, canon, make_model
+from helpers import batch_vector, canon, grid_features, make_model
 from oracle import oracle as O
 
 CONV_STATE = {
@@ -223,3 +223,124 @@ def test_budget_reports_the_worst_element():
         R.budget(got, ref, base)
     assert R.budget(ref + 2e-7, ref, base)[1] == pytest.approx(5e-8)
     assert R.errors(np.zeros(3), np.zeros(3), np.zeros(3))[:2] == (0.0, 0.0)
+
+
+# --------------------------------------------------------------------------- the stage restatements (gnnb_agg, gnnb_linear)
+def _isolating(cls, f, *args):
+    """``cls`` (a conv module) in float64 with weights that leave its aggregate alone: GCN W = I, b = 0; GIN's MLP I + 8 /
+    I - 8 (the shift keeps ReLU off every value it sees); SAGE lin_l = I, lin_r = 0; PNA pre-NN [I | I] (h = x_i + x_j) or
+    [0 | I] (h = x_j), post-NN the four identity-scaled aggregates, lin = I."""
+    conv = cls(f, 4 * f if cls is gnnb.PNAConv_GNNB else f, *args).double()
+    eye = torch.eye(f, dtype=torch.float64)
+    with torch.no_grad():
+        for p in conv.parameters():
+            p.zero_()
+        if cls is gnnb.GCNConv_GNNB:
+            conv.conv.lin.weight.copy_(eye)
+        elif cls is gnnb.GINConv_GNNB:
+            conv.mlp.linear_0.weight.copy_(eye), conv.mlp.linear_0.bias.fill_(8.0)
+            conv.mlp.linear_1.weight.copy_(eye), conv.mlp.linear_1.bias.fill_(-8.0)
+        elif cls is gnnb.SAGEConv_GNNB:
+            conv.conv.lin_l.weight.copy_(eye)
+        else:
+            conv.conv.pre_nns[0][0].weight[:, f:].copy_(eye)
+            conv.conv.post_nns[0][0].weight[:, f:5 * f].copy_(torch.eye(4 * f, dtype=torch.float64))
+            conv.conv.lin.weight.copy_(torch.eye(4 * f, dtype=torch.float64))
+    return conv
+
+
+def _stage_graph(fin=13, seed=5):
+    from helpers import edge_batch
+    return edge_batch(6, fin, seed, hub=False)
+
+
+def test_float64_aggregates_match_the_conv_modules():
+    b = _stage_graph()
+    x, coo = b.x, b.coo
+    loopless = R.workspace_edges(coo, True)
+    assert len(loopless) < len(coo), "the batch needs explicit self loops"
+    f = x.shape[1]
+    # GCN: the module replaces the explicit self loops by one per node -- a GCN workspace's tables
+    assert np.abs(R.gcn_agg64(x, loopless) - R.layer64(_isolating(gnnb.GCNConv_GNNB, f), x, coo)).max() < 1e-12
+    assert np.abs(R.sum_agg64(x, coo, 0.25) - R.layer64(_isolating(gnnb.GINConv_GNNB, f, None, 0.25), x, coo)).max() < 1e-12
+    assert np.abs(R.mean_agg64(x, coo) - R.layer64(_isolating(gnnb.SAGEConv_GNNB, f), x, coo)).max() < 1e-12
+    pna = _isolating(gnnb.PNAConv_GNNB, f)
+    assert np.abs(R.pna_agg64(x, coo) - R.layer64(pna, x, coo)).max() < 1e-12
+    with torch.no_grad():
+        pna.conv.pre_nns[0][0].weight[:, :f].copy_(torch.eye(f, dtype=torch.float64))
+    assert np.abs(R.pna_agg64(x, coo, q=x) - R.layer64(pna, x, coo)).max() < 1e-12
+    # the weight-free forms and GINE's aggregate agree with the fp32 oracle's, graph by graph
+    ea = np.random.default_rng(1).uniform(-1, 1, (b.num_edges, f)).astype(np.float32)
+    eye, zf = np.eye(f, dtype=np.float32), np.zeros(f, np.float32)
+    for g in range(b.num_graphs):
+        lo, hi = b.node_ptr[g], b.node_ptr[g + 1]
+        if hi == lo:
+            continue
+        xg, cg = x[lo:hi], b.coo[b.edge_ptr[g]:b.edge_ptr[g + 1]] - lo
+        for kind, f64 in (("simple", R.simple64), ("lg", R.lg64)):
+            assert np.abs(f64(xg, cg) - O.conv(kind, xg, cg, [])).max() < 4e-6
+        # (GINE with We = I, be = 0 on edge features = the edge term; its MLP shifted past ReLU as above)
+        gine = O.gine_conv(xg, cg, ea[b.edge_ptr[g]:b.edge_ptr[g + 1]], [eye, zf, eye, zf + 8, eye, zf - 8], eps=-0.3)
+        assert np.abs(R.gine_agg64(xg, cg, ea[b.edge_ptr[g]:b.edge_ptr[g + 1]], -0.3) - gine).max() < 4e-6
+
+
+def test_float32_forms_are_fp32_evaluations():
+    """The ``dtype=np.float32`` forms (the budget's base) stay within fp32 rounding of float64 -- and are not float64."""
+    b = _stage_graph(33, 6)
+    x, coo, q = b.x, R.workspace_edges(b.coo, False), np.random.default_rng(2).uniform(-1, 1, b.x.shape).astype(np.float32)
+    for name, fn in (("gcn", R.gcn_agg64), ("sum", lambda *a, **k: R.sum_agg64(*a, eps=-0.5, **k)), ("mean", R.mean_agg64),
+                     ("pna", lambda *a, **k: R.pna_agg64(*a, q=q, **k)), ("lg", R.lg64), ("simple", R.simple64)):
+        ref, base = fn(x, coo), fn(x, coo, dtype=np.float32)
+        assert base.dtype == np.float32, name
+        e32 = R.errors(base, ref, base)[1]
+        # (PNA's std sqrt(E[h^2] - E[h]^2) magnifies the rounding of a small variance: its fp32 error is the largest)
+        assert 0 < e32 < (1e-4 if name == "pna" else 1e-6), (name, e32)
+    segs = [(x, None), (x[:, 3:20], q[:, 0])]
+    w = np.random.default_rng(3).uniform(-0.5, 0.5, (7, 50))
+    ref = R.linear64(segs, w, w[0, :7], act="gelu")
+    e32 = R.errors(R.linear64(segs, w, w[0, :7], act="gelu", dtype=torch.float32), ref, ref)[0]
+    assert 0 < e32 < 1e-6
+    want = x.astype(np.float64) @ w[:, :33].T + (x[:, 3:20].astype(np.float64) * q[:, :1]) @ w[:, 33:].T + w[0, :7]
+    assert np.abs(ref - torch.nn.functional.gelu(torch.from_numpy(want)).numpy()).max() < 1e-12
+
+
+def _stage_fault(fault):
+    """(float64 reference, fp32 evaluation, faulted evaluation) of one stage with one fault of the kind the stage tests target."""
+    rng = np.random.default_rng(17)
+    if fault == "g_odd_width_last_column_dropped":
+        b = _stage_graph(33, 7)
+        ref, base = R.sum_agg64(b.x, b.coo, 0.25), R.sum_agg64(b.x, b.coo, 0.25, dtype=np.float32)
+        got = base.copy()
+        got[:, -1] = 0.0
+    elif fault == "h_row_read_with_stride_k":
+        M, K, lda = 300, 33, 37
+        buf = rng.uniform(-1, 1, (M, lda)).astype(np.float32)
+        w, bias = rng.uniform(-0.3, 0.3, (31, K)).astype(np.float32), rng.uniform(-0.1, 0.1, 31).astype(np.float32)
+        a = buf[:, :K]
+        ref, base = R.linear64([(a, None)], w, bias, act="tanh"), R.linear64([(a, None)], w, bias, act="tanh", dtype=torch.float32)
+        wrong = a.copy()
+        wrong[M - 1] = buf.reshape(-1)[(M - 1) * K:M * K]  # (the last row addressed with lda = K)
+        got = R.linear64([(wrong, None)], w, bias, act="tanh", dtype=torch.float32)
+    elif fault == "i_pna_std_without_clamp":
+        b = _stage_graph(16, 8)
+        x = grid_features(b.num_nodes, 16, 8)
+        ref, base = R.pna_agg64(x, b.coo), R.pna_agg64(x, b.coo, dtype=np.float32)
+        got = R.pna_agg64(x, b.coo, dtype=np.float32, clamp=False)
+    else:  # "j_gcn_counts_an_explicit_self_loop"
+        b = _stage_graph(16, 9)
+        ws = R.workspace_edges(b.coo, True)
+        ref, base = R.gcn_agg64(b.x, ws), R.gcn_agg64(b.x, ws, dtype=np.float32)
+        got = R.gcn_agg64(b.x, b.coo, dtype=np.float32)
+    return ref, base, got
+
+
+STAGE_FAULTS = ["g_odd_width_last_column_dropped", "h_row_read_with_stride_k", "i_pna_std_without_clamp",
+                "j_gcn_counts_an_explicit_self_loop"]
+
+
+@pytest.mark.parametrize("fault", STAGE_FAULTS)
+def test_budget_rejects_the_injected_stage_fault(fault):
+    ref, base, got = _stage_fault(fault)
+    R.budget(base, ref, base, what="fp32 evaluation")  # (trivially: e = e32)
+    with pytest.raises(AssertionError, match="e32"):
+        R.budget(got, ref, base)
