@@ -1421,8 +1421,11 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
             float *q = ws->tmp0, *pp = ws->tmp1;
             // degree-class form (gnnb_workspace_set_max_degree; decided here: it folds the destination's pre-NN term into x's
             // class weights, so q is not computed and the aggregate runs without a destination term)
+            // (the row-class GEMM addresses a row of its operands as a 32-bit byte offset on the operand's base, row * 16 fi
+            // for the aggregate: the form applies while that stays below 2^32 -- 2^21 rows at fi = 128, 2^20 at fi = 256; larger
+            // batches take the general form below, decided here, before anything of the layer is enqueued)
             const bool classes = p.size() >= 10 && options().pna_fold_lin && options().pna_classes && whole && ws->deg_ready && M > 0 && !fpx &&
-                                 ws->deg_delta == model->desc.pna_delta && fo > 32;
+                                 ws->deg_delta == model->desc.pna_delta && fo > 32 && (uint64_t)M * 16 * fi + 512 <= 0xffffffffull;
             if (!classes && (rc = linear1(R(cur, fi), fi, fi, p[0], 2 * fi, p[1], nullptr, Rw(q, fi), M, fi, GNNB_ACT_NONE, stream)))
                 return rc;
             // the source half p = x . Wb^T and its aggregate: in one kernel, p on chip, where the degree-class form (no destination

@@ -465,7 +465,12 @@ __global__ __launch_bounds__(1024) void k_aggregate_ring(
         const float *sdinv = reinterpret_cast<const float *>(sb + off_dinv);
         const int32_t *scol = reinterpret_cast<const int32_t *>(sb + off_col) - e0_; // indexed by the CSR slot itself
         int nst = 0;
-        if (VEC == 4 && (MODE == GNNB_AGG_GCN || MODE == GNNB_AGG_SUM || MODE == GNNB_AGG_MEAN || MODE == GNNB_AGG_SIMPLE) && nvec <= G) {
+        // The lean path's LDS addresses are 24-bit products of batch-global ids (__mul24 keeps the sign-extended low 24 bits):
+        // exact relative to the stage's first row only while every id of the stage lies in one window [2^23 + k 2^24,
+        // 2^23 + (k+1) 2^24).  A stage that straddles a window edge (one in 2^24 nodes) takes the general path below.
+        const bool win24 = (((uint32_t)nb_ + 0x800000u) >> 24) == (((uint32_t)(nb_ + rows_ - 1) + 0x800000u) >> 24);
+        if (VEC == 4 && (MODE == GNNB_AGG_GCN || MODE == GNNB_AGG_SUM || MODE == GNNB_AGG_MEAN || MODE == GNNB_AGG_SIMPLE) && nvec <= G &&
+            win24) {
             // lean path (LdsRowF): one column pass (a lane group covers the row), two rows per lane group in flight
             const int w4 = w * 4;
             const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_vptr)sb;

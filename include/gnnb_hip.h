@@ -161,7 +161,9 @@ int gnnb_workspace_set_max_graph_nodes(gnnb_workspace *ws, int n);
  * promise of d <= 15 (molecules: <= 6) a PNA layer's 13 F-wide post-NN product [x | A | amp A | att A] . W^T is evaluated as
  * the 5 F-wide [x | A] . (W_x | W_1 + amp(d) W_2 + att(d) W_3)^T with the rows sorted by degree class and one pre-combined
  * weight matrix per class (formed in double at gnnb_model_create): the same mathematics, 2.6x fewer flops.  Applies when
- * the batch is prepared with the model's own pna_delta.  VALIDATED on the device by every graph prep like the node
+ * the batch is prepared with the model's own pna_delta, and while the batch's rows x 16 x (layer input width) bytes + 512
+ * stay below 2^32 (the class GEMM's 32-bit row offsets: up to 2^21 - 1 rows at width 128, 2^20 - 1 at 256); larger
+ * batches run the general form, with the same results.  VALIDATED on the device by every graph prep like the node
  * promise (flag 32 of gnnb_workspace_check).  Other conv types ignore it. */
 int gnnb_workspace_set_max_degree(gnnb_workspace *ws, int d);
 

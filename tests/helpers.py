@@ -5,6 +5,7 @@ import torch
 
 import gnnbuilder_amd as gnnb
 from gnnbuilder_amd import synthetic
+from gnnbuilder_amd.batching import GraphBatch
 
 CONVS = {"gcn": gnnb.GCNConv_GNNB, "gin": gnnb.GINConv_GNNB, "sage": gnnb.SAGEConv_GNNB, "pna": gnnb.PNAConv_GNNB}
 ACTS = {"relu": torch.nn.ReLU, "gelu": torch.nn.GELU, "sigmoid": torch.nn.Sigmoid, "tanh": torch.nn.Tanh}
@@ -78,3 +79,87 @@ def grid_features(n, w, seed):
     land on its two sides) -- and many lie below it, where the clamp decides."""
     rng = np.random.default_rng(seed)
     return (np.round(rng.uniform(-1, 1, (n, w)) * 4) / 4 + rng.uniform(-1e-3, 1e-3, (n, w))).astype(np.float32)
+
+
+def _local_coo(batch):
+    """The batch's edges with graph-local ids (``batch.coo`` minus each edge's graph start)."""
+    return batch.coo.astype(np.int64) - np.repeat(batch.node_ptr[:-1].astype(np.int64), np.diff(batch.edge_ptr))[:, None]
+
+
+def _assemble(sizes, esizes, lcoo):
+    """A GraphBatch from per-graph node / edge counts and the concatenated graph-local edges; ``x`` has width 0 (features
+    of huge batches live on the device: ``huge_x``)."""
+    node_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    edge_ptr = np.concatenate([[0], np.cumsum(esizes)]).astype(np.int64)
+    assert node_ptr[-1] < 2 ** 31 and edge_ptr[-1] < 2 ** 31
+    coo = (lcoo + np.repeat(node_ptr[:-1], esizes)[:, None]).astype(np.int32)
+    return GraphBatch(x=np.zeros((int(node_ptr[-1]), 0), np.float32), coo=np.ascontiguousarray(coo),
+                      node_ptr=node_ptr.astype(np.int32), edge_ptr=edge_ptr.astype(np.int32))
+
+
+def huge_batch(num_nodes, seed, shape="qm9", base_graphs=4096, place=()):
+    """At least ``num_nodes`` nodes of whole graphs: a seeded ``synthetic.make_batch`` of ``base_graphs`` graphs tiled with
+    offset arithmetic (no Python loop per graph).  ``place``: (node id, graph-local coo [e, 2], node count) triples in
+    increasing node order; each graph is put where it straddles its node id (``id - first node = n // 2``) behind one
+    edge-less filler graph that closes the gap.  ``x`` has width 0: ``huge_x`` makes the features."""
+    b = synthetic.make_batch(shape, base_graphs, seed=seed)
+    sizes0, esz0, lcoo0 = np.diff(b.node_ptr).astype(np.int64), np.diff(b.edge_ptr).astype(np.int64), _local_coo(b)
+    reps = num_nodes // b.num_nodes + 2
+    sizes, esz = np.tile(sizes0, reps), np.tile(esz0, reps)
+    lcoo = np.tile(lcoo0, (reps, 1))
+    nptr = np.concatenate([[0], np.cumsum(sizes)])
+    eptr = np.concatenate([[0], np.cumsum(esz)])
+    ps, pe, pc = [], [], []
+    g, shift = 0, 0  # next tiled graph; nodes inserted in front of it so far
+    for node, coo, n in place:
+        start = int(node) - int(n) // 2
+        g1 = int(np.searchsorted(nptr, start - shift, "right")) - 1  # the tiled graphs that end at or before `start`
+        assert g1 >= g, "place: node ids too close together"
+        ps.append(sizes[g:g1]), pe.append(esz[g:g1]), pc.append(lcoo[eptr[g]:eptr[g1]])
+        gap = start - int(nptr[g1]) - shift
+        if gap:
+            ps.append([gap]), pe.append([0]), pc.append(np.zeros((0, 2), np.int64))
+        coo = np.asarray(coo, np.int64).reshape(-1, 2)
+        ps.append([n]), pe.append([len(coo)]), pc.append(coo)
+        shift += gap + int(n)
+        g = g1
+    g1 = int(np.searchsorted(nptr, num_nodes - shift, "left"))
+    ps.append(sizes[g:g1]), pe.append(esz[g:g1]), pc.append(lcoo[eptr[g]:eptr[g1]])
+    out = _assemble(np.concatenate(ps).astype(np.int64), np.concatenate(pe).astype(np.int64), np.concatenate(pc))
+    assert out.num_nodes >= num_nodes
+    return out
+
+
+def huge_x(num_nodes, width, seed, device="cpu"):
+    """uniform(-1, 1) features [num_nodes, width] from their own seeded generator, made where they are used."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    return torch.empty((num_nodes, width), dtype=torch.float32, device=device).uniform_(-1.0, 1.0, generator=gen)
+
+
+def sub_batch(batch, graph_ids):
+    """Graphs ``graph_ids`` (increasing) of ``batch`` as a batch of their own, nodes and edges renumbered; returns
+    (sub-batch, the sub-batch's nodes as ids of ``batch``).  ``x`` is taken along where ``batch`` has it."""
+    gids = np.asarray(graph_ids, np.int64)
+    assert np.all(np.diff(gids) > 0)
+    n0, n1 = batch.node_ptr[gids].astype(np.int64), batch.node_ptr[gids + 1].astype(np.int64)
+    e0, e1 = batch.edge_ptr[gids].astype(np.int64), batch.edge_ptr[gids + 1].astype(np.int64)
+    sizes, esz = n1 - n0, e1 - e0
+    ranges = lambda lo, cnt: np.repeat(lo - np.concatenate([[0], np.cumsum(cnt)[:-1]]), cnt) + np.arange(cnt.sum())  # noqa: E731
+    rows, edges = ranges(n0, sizes), ranges(e0, esz)
+    lcoo = batch.coo[edges].astype(np.int64) - np.repeat(n0, esz)[:, None]
+    sub = _assemble(sizes, esz, lcoo)
+    if batch.x.shape[1]:
+        sub.x = np.ascontiguousarray(batch.x[rows])
+    return sub, rows
+
+
+def sample_graphs(batch, seed, count=256, nodes=()):
+    """The graphs a test at scale checks: the first, the last, ``count`` seeded random ones and the ones holding node ids
+    ``nodes`` and their neighbours on both sides (increasing, unique)."""
+    B = batch.num_graphs
+    g = [0, B - 1] + list(np.random.default_rng(seed).integers(0, B, count))
+    for v in nodes:
+        k = int(np.searchsorted(batch.node_ptr, v, "right")) - 1
+        g += [max(k - 1, 0), k, min(k + 1, B - 1)]
+    return np.unique(np.asarray(g, np.int64))

@@ -9,6 +9,7 @@ The stage entry points (``gnnb_aggregate``, ``gnnb_linear``, ...) have float64 r
 a ``dtype``: float32 gives the fp32 evaluation the budget measures against -- neighbours summed in CSR order (COO order per
 destination: ``np.add.at`` is sequential), the self term last, as the kernels do.  ``workspace_edges`` applies the documented
 self-loop rule (``gnnb_hip.h``, ``gnnb_graph_prep``): the tables of a GCN workspace hold no explicit ``(v, v)`` edge.
+``agg_rows64`` and ``linear64(rows=...)`` give chosen rows only, for batches of millions of nodes.
 
 ``budget(got, ref, base)`` asks a result to be as accurate as a plain fp32 evaluation of the same model: with
 ``s = max|ref|``, ``e = max|got - ref| / s`` and ``e32 = max|base - ref| / s`` (``base``: the fp32 oracle's output for the
@@ -106,13 +107,15 @@ def lg64(x, coo, dtype=np.float64):
     return _csr_sums(x, coo, x.shape[0], s)
 
 
-def gcn_agg64(x, coo, dtype=np.float64):
+def gcn_agg64(x, coo, dtype=np.float64, deg=None):
     """PyG ``gcn_norm`` aggregate with exactly one self loop per node: ``sum_j x_j / sqrt(d_i d_j) + x_i / d_i``,
     d = 1 + in-degree over ``coo`` (pass ``workspace_edges(coo, True)`` for a GCN workspace: its explicit self loops are
-    replaced, not counted; on any other workspace they are ordinary edges)."""
+    replaced, not counted; on any other workspace they are ordinary edges).  ``deg``: the in-degrees, where ``coo`` holds only
+    part of the edges (``agg_rows64``)."""
     x = np.asarray(x, dtype)
     src, dst = np.asarray(coo).reshape(-1, 2).T
-    dinv = (dtype(1) / np.sqrt(_in_deg(coo, x.shape[0]).astype(dtype) + dtype(1))).astype(dtype)
+    deg = _in_deg(coo, x.shape[0]) if deg is None else deg
+    dinv = (dtype(1) / np.sqrt(deg.astype(dtype) + dtype(1))).astype(dtype)
     out = _csr_sums(x, coo, x.shape[0], (dinv[dst] * dinv[src]).astype(dtype))
     return out + x * (dinv * dinv)[:, None]
 
@@ -123,10 +126,10 @@ def sum_agg64(x, coo, eps=0.0, dtype=np.float64):
     return _csr_sums(x, coo, x.shape[0]) + x * dtype(np.float32(1) + np.float32(eps))
 
 
-def mean_agg64(x, coo, dtype=np.float64):
+def mean_agg64(x, coo, dtype=np.float64, deg=None):
     """SAGE's aggregate: ``mean_j x_j``, 0 without a neighbour."""
     x = np.asarray(x, dtype)
-    deg = _in_deg(coo, x.shape[0]).astype(dtype)
+    deg = (_in_deg(coo, x.shape[0]) if deg is None else deg).astype(dtype)
     return _csr_sums(x, coo, x.shape[0]) / np.maximum(deg, dtype(1))[:, None]
 
 
@@ -138,6 +141,34 @@ def gine_agg64(x, coo, edge_term, eps=0.0, dtype=np.float64):
     out = np.zeros_like(x)
     np.add.at(out, dst, np.maximum(x[src] + np.asarray(edge_term, dtype), dtype(0)))
     return out + x * dtype(np.float32(1) + np.float32(eps))
+
+
+def agg_rows64(kind, coo, num_nodes, rows, fetch, eps=0.0, dtype=np.float64):
+    """Rows ``rows`` (unique node ids) of ``gcn_agg64`` / ``sum_agg64`` / ``mean_agg64`` / ``simple64`` (``kind`` gcn / sum /
+    mean / simple) over a graph of ``num_nodes`` nodes, reading only the features they need: ``fetch(ids)`` returns the rows
+    ``ids`` (increasing) of x.  The same operations in the same order as the full form -- the rows' in-edges in COO order,
+    in-degrees over every edge -- so the values are identical to the full form's at those rows."""
+    rows = np.asarray(rows, np.int64)
+    src, dst = np.asarray(coo).reshape(-1, 2).T
+    pos = np.full(num_nodes, -1, np.int64)
+    pos[rows] = np.arange(len(rows))
+    assert len(np.unique(rows)) == len(rows)
+    sel = pos[dst] >= 0
+    need = np.unique(np.concatenate([rows, src[sel]]))
+    loc = lambda ids: np.searchsorted(need, ids)  # noqa: E731
+    lcoo = np.stack([loc(src[sel]), loc(dst[sel])], 1)
+    x = np.asarray(fetch(need))
+    assert x.shape[0] == len(need)
+    if kind == "gcn":
+        out = gcn_agg64(x, lcoo, dtype, deg=_in_deg(coo, num_nodes)[need])
+    elif kind == "mean":
+        out = mean_agg64(x, lcoo, dtype)
+    elif kind == "sum":
+        out = sum_agg64(x, lcoo, eps, dtype)
+    else:
+        assert kind == "simple", kind
+        out = simple64(x, lcoo, dtype)
+    return out[loc(rows)]
 
 
 PNA_STD_EPS = 1e-5
@@ -175,11 +206,17 @@ ACTS64 = {"none": lambda v: v, "relu": lambda v: torch.relu(v), "tanh": torch.ta
           "gelu": lambda v: torch.nn.functional.gelu(v)}
 
 
-def linear64(segments, weight, bias=None, skip=None, act="none", dtype=torch.float64):
+def linear64(segments, weight, bias=None, skip=None, act="none", dtype=torch.float64, rows=None):
     """``gnnb_linear``: ``act(sum_s (rowscale_s * A_s) . W[:, koff_s : koff_s + K_s]^T + bias + skip)``.  ``segments``:
     (A [M, K_s], rowscale [M] or None) tensors or arrays, any strides; float32 ``dtype`` is the torch CPU fp32 product, its
     4-column chunks summed in K order (one BLAS call over the whole K would sum more accurately than any GPU kernel, and
-    differently on every CPU)."""
+    differently on every CPU).  ``rows``: only those rows of the result (A, rowscale and skip are indexed first: a device
+    tensor of any size gives up just those rows)."""
+    if rows is not None:
+        r = torch.as_tensor(np.asarray(rows, np.int64))
+        pick = lambda a: None if a is None else (a[r.to(a.device)].cpu() if torch.is_tensor(a) else np.asarray(a)[np.asarray(rows)])  # noqa: E731
+        segments = [(pick(a), pick(rs)) for a, rs in segments]
+        skip = pick(skip)
     t = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)  # noqa: E731
     w = t(weight)
     acc, koff = None, 0

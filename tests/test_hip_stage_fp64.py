@@ -255,7 +255,7 @@ def test_aggregate(gcn_ws, width, kind, eps, self_term, agg_batch, workspaces):
         cm = workspaces[(gcn_ws, bal)]
         xd, qd = on_device(x, off), (on_device(q, off) if q is not None else None)
         out = on_device(np.full_like(ref, np.nan), off)  # (NaN: a row the kernel skips fails the budget)
-        with options(agg_form=form):
+        with options(agg_form=form, agg_balance=bal):  # (read at graph prep for the cut table AND at launch, which uses it)
             cm.aggregate(kind, xd, self_term=qd, eps=eps, out=out)
         cm.check()
         record(f"aggregate {kind}{' q' if self_term else ''} form{form}", out.cpu().numpy(), ref, base)
