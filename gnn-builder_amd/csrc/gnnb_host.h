@@ -1,0 +1,121 @@
+// gnnb_host.h -- what the host translation units of libgnnb_hip.so share (gnnb_model.hip: description and weight upload;
+// gnnb_runtime.hip: workspace, graph prep, forward, C-ABI utilities): the two handle structs, the error helpers and the
+// dimension helpers of a model description.  Host only: no kernel unit includes it.
+#pragma once
+
+#include <vector>
+
+#include "gnnb_internal.h"
+
+namespace gnnb {
+
+// sets the calling thread's gnnb_last_error() text and returns `code` (gnnb_runtime.hip)
+int fail(int code, const char *fmt, ...);
+
+#define GNNB_HIP_TRY(expr)                                                                        \
+    do {                                                                                          \
+        hipError_t _e = (expr);                                                                   \
+        if (_e != hipSuccess)                                                                     \
+            return fail(GNNB_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),      \
+                        __FILE__, __LINE__);                                                      \
+    } while (0)
+
+struct LayerDims {
+    int fin, fout;
+};
+
+// canonical parameter tensors per conv layer (-1: unknown conv type)
+inline int conv_slots(int conv)
+{
+    switch (conv) {
+    case GNNB_CONV_GCN: return 2;
+    case GNNB_CONV_GIN: return 4;
+    case GNNB_CONV_SAGE: return 3;
+    case GNNB_CONV_PNA: return 6;
+    default: return -1;
+    }
+}
+
+// gnnbuilder/models.py:519-549
+inline LayerDims layer_dims(const gnnb_model_desc &d, int l)
+{
+    if (d.num_layers == 1)
+        return {d.in_dim, d.out_dim};
+    if (l == 0)
+        return {d.in_dim, d.hidden_dim};
+    if (l == d.num_layers - 1)
+        return {d.hidden_dim, d.out_dim};
+    return {d.hidden_dim, d.hidden_dim};
+}
+
+inline int gnn_out_width(const gnnb_model_desc &d) { return d.num_layers == 0 ? d.in_dim : d.out_dim; }
+
+// gnnbuilder/models.py:398-415
+inline void mlp_dims(const gnnb_model_desc &d, int i, int *din, int *dout)
+{
+    const int pooled = d.num_pools * gnn_out_width(d);
+    *din = (i == 0) ? pooled : d.mlp_hidden;
+    *dout = (i == d.mlp_num_linear - 1) ? d.mlp_out : d.mlp_hidden;
+}
+
+} // namespace gnnb
+
+struct gnnb_model {
+    gnnb_model_desc desc;
+    float *blob = nullptr; // all weights, device
+    size_t blob_floats = 0;
+    // per conv layer device pointers (canonical slots; SAGE slot 0 is the fused [Wl|Wr])
+    std::vector<std::vector<const float *>> conv;
+    std::vector<const float *> head_w, head_b;
+    const float *zf_w1f = nullptr; // 2-layer GCN: layer 1's weight once more, in MFMA-fragment order (see k_gcn2_zf)
+    // GIN stacks (k_gcn2_fused<GIN>): every wide matrix once more in EXECUTION order, each hidden x hidden at one stride --
+    // Wb0 | Wa1 Wb1 | ... | Wa(L-1) Wb(L-1) -- and the biases likewise.  A last layer narrower than hidden (the reference's
+    // benchmark model: 128 -> 64, models.py:530-545) is zero-padded to hidden x hidden: its extra output columns are
+    // act(0 + 0) and never leave the kernel.  nullptr when the model is no GIN stack the kernel takes.
+    const float *gin_w = nullptr, *gin_b = nullptr;
+    gnnb::HeadArgs *head_dev = nullptr; // the MLP head's {weights, biases, widths} once more in device memory: k_gcn2_zf reads it at the
+                                        // end of a workgroup's life (by value the 42 dwords stayed in scalar registers through its stage loop)
+    int device = 0;
+};
+
+struct gnnb_workspace {
+    gnnb_model_desc desc;
+    int max_graphs = 0, max_nodes = 0, max_edges = 0;
+    char *blob = nullptr;
+    size_t bytes = 0;
+    gnnb::BatchTables t{};
+    float *act[2] = {nullptr, nullptr}; // ping-pong node embeddings [max_nodes, maxw]
+    float *agg = nullptr;               // aggregate output [max_nodes, aggw]
+    float *tmp0 = nullptr, *tmp1 = nullptr; // GIN hidden / PNA p,q
+    float *pooled = nullptr;            // [max_graphs, np*d]
+    float *mlp[2] = {nullptr, nullptr}; // [max_graphs, max(mlp_hidden, mlp_out)]
+    bool prepared = false;
+    float2 *pool_part = nullptr; // pieces of graphs that cross the 32-row blocks of the pooling GEMM epilogue (PoolEpilogue::part)
+    bool gcoef_ready = false; // t.gcoef holds the prepared batch's GCN coefficients (ensure_gcoef)
+    int max_graph_nodes = 0; // caller's promise (0 = none)
+    int max_degree = 0;      // caller's promise on the in-degree (0 = none): gnnb_workspace_set_max_degree
+    // PNA degree classes of the prepared batch (launch_degree_classes): valid when deg_ready; deg_delta = the delta it was prepared with
+    int32_t *deg_work = nullptr, *deg_perm = nullptr, *deg_tile_cls = nullptr;
+    int deg_max_tiles = 0;
+    bool deg_ready = false;
+    float deg_delta = 0.0f;
+    int32_t *plan_scratch = nullptr; // k_stage_cut's binary-lifting tables (GCN / GIN workspaces: stage_cut_levels x (max tiles + 1) ints)
+    float prep_delta = 0.0f; // the delta the prepared batch's amp / att tables were computed with (PNA workspaces; 0: none)
+    int last_path = GNNB_PATH_NONE; // which kernels the last forward on this workspace ran (gnnb_workspace_last_path)
+    // "large segment" of the NEXT batches (gnnb_workspace_set_large_segment): graphs [large_g, B) -- nodes from large_n,
+    // edges from large_e -- are exempt from the max_graph_nodes promise and run layer by layer; -1 = no such segment
+    int large_g = -1, large_n = -1, large_e = -1;
+    // fork / join for the large segment: its small kernels run on `side` beside the stack kernel on the caller's stream
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int device = 0;
+    int32_t *err_host = nullptr; // host-mapped word the prep kernel drops "flagged" into (lazy detection, see gnnb_graph_prep)
+    gnnb::StreamK sk{};      // this workspace's own stream-K scratch (k_linear_dma's large-K tail; part == nullptr: the model has no such GEMM)
+    char *stage = nullptr;   // device staging of the host-buffer entry (x | coo | node_ptr | edge_ptr | out), sized for
+    size_t stage_bytes = 0;  // the workspace's capacities; allocated by the first gnnb_forward_batched_host call
+};
+
+namespace gnnb {
+// the model's MLP head as the readout kernels take it (gnnb_model.hip): the ONLY place that fills a HeadArgs
+HeadArgs model_head_args(const gnnb_model *model);
+} // namespace gnnb

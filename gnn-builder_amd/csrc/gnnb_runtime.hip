@@ -10,6 +10,7 @@
 //   compute_mlp_head (:454-530)                -> k_linear chain
 // There is no CPU fallback: every entry point fails with GNNB_ERR_NO_DEVICE / GNNB_ERR_HIP when
 // the GPU path cannot run.
+#include <cctype>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -18,13 +19,13 @@
 #include <string>
 #include <vector>
 
-#include "gnnb_internal.h"
+#include "gnnb_host.h"
 
 namespace gnnb {
 
 static thread_local std::string g_last_error;
 
-static int fail(int code, const char *fmt, ...)
+int fail(int code, const char *fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -35,33 +36,23 @@ static int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define GNNB_HIP_TRY(expr)                                                                        \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess)                                                                     \
-            return fail(GNNB_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),      \
-                        __FILE__, __LINE__);                                                      \
-    } while (0)
-
-static int env_int(const char *name, int dflt)
+// an option's default: the environment variable GNNB_<NAME> (atoi, not validated) or the table's
+static int option_default(const char *name, int dflt)
 {
-    const char *v = getenv(name);
+    char var[64] = "GNNB_";
+    size_t n = strlen(var);
+    for (const char *c = name; *c && n + 1 < sizeof(var); c++)
+        var[n++] = (char)toupper((unsigned char)*c);
+    var[n] = 0;
+    const char *v = getenv(var);
     return (v && *v) ? atoi(v) : dflt;
 }
 
 Options &options()
 {
-    static Options o = {env_int("GNNB_TILE_ROWS", 8), env_int("GNNB_AGG_LDS_KB", 0),
-                                                env_int("GNNB_AGG_RING_WAVES", 0),    env_int("GNNB_AGG_RING_SLOTS", 2),
-                        env_int("GNNB_AGG_RING_WG_PER_CU", 1), env_int("GNNB_AGG_NT_STORE", 1), env_int("GNNB_AGG_BALANCE", 0),
-                        env_int("GNNB_GEMM_VARIANT", 0),
-                        env_int("GNNB_GEMM_MAX_WG_PER_CU", 2), env_int("GNNB_GEMM_DMA", 1),
-                        env_int("GNNB_GEMM_WLDS", 1),             env_int("GNNB_GEMM_WLDS_SLOTS", 2),
-                        env_int("GNNB_FUSE_NARROW", 1), env_int("GNNB_FIRST_RING", 1),    env_int("GNNB_FUSE_ZF", 1),   env_int("GNNB_LARGE_FORK", 2), env_int("GNNB_ZF_SHAPE", 2),
-                        env_int("GNNB_FUSE_GCN2", 1),         env_int("GNNB_FUSE_HEAD", 1), env_int("GNNB_FUSE_POOL", 1),
-                        env_int("GNNB_HEAD_SMALL", 1),        env_int("GNNB_HEAD_SPLIT", 0),
-                        env_int("GNNB_MATH", 0),              env_int("GNNB_GEMM_TAIL_SPLIT", 2), env_int("GNNB_PNA_FOLD_LIN", 1), env_int("GNNB_PNA_CLASSES", 1), env_int("GNNB_FOLD_SKIP", 1), env_int("GNNB_SAGE_FIRST_MEAN", 1), env_int("GNNB_PNA_FIRST", 1), env_int("GNNB_PNA_PAGG", 1), env_int("GNNB_STAGE_CUT", 0), env_int("GNNB_ZF_HEAD", 0),
-                        env_int("GNNB_AGG_FORM", 0), env_int("GNNB_AGG_RG_R", 0), env_int("GNNB_AGG_RG_WGS", 0), env_int("GNNB_AGG_RG_FLAGS", 1), env_int("GNNB_PREP_GROUP", 4), env_int("GNNB_HEAD_PAIRS", 1), env_int("GNNB_GUEST_PREP", 1)};
+#define GNNB_OPTION_DEFAULT(name, dflt, accepts) option_default(#name, dflt),
+    static Options o = {GNNB_OPTIONS(GNNB_OPTION_DEFAULT)};
+#undef GNNB_OPTION_DEFAULT
     return o;
 }
 
@@ -84,155 +75,9 @@ MathScope::~MathScope()
     tl_flag = prev_flag;
 }
 
-// ---------------------------------------------------------------------------------------
-struct LayerDims {
-    int fin, fout;
-};
-
-static int conv_slots(int conv)
-{
-    switch (conv) {
-    case GNNB_CONV_GCN: return 2;
-    case GNNB_CONV_GIN: return 4;
-    case GNNB_CONV_SAGE: return 3;
-    case GNNB_CONV_PNA: return 6;
-    default: return -1;
-    }
-}
-
-// gnnbuilder/models.py:519-549
-static LayerDims layer_dims(const gnnb_model_desc &d, int l)
-{
-    if (d.num_layers == 1)
-        return {d.in_dim, d.out_dim};
-    if (l == 0)
-        return {d.in_dim, d.hidden_dim};
-    if (l == d.num_layers - 1)
-        return {d.hidden_dim, d.out_dim};
-    return {d.hidden_dim, d.hidden_dim};
-}
-
-static int gnn_out_width(const gnnb_model_desc &d) { return d.num_layers == 0 ? d.in_dim : d.out_dim; }
-
-// gnnbuilder/models.py:398-415
-static void mlp_dims(const gnnb_model_desc &d, int i, int *din, int *dout)
-{
-    const int pooled = d.num_pools * gnn_out_width(d);
-    *din = (i == 0) ? pooled : d.mlp_hidden;
-    *dout = (i == d.mlp_num_linear - 1) ? d.mlp_out : d.mlp_hidden;
-}
-
-static int validate_desc(const gnnb_model_desc *d)
-{
-    if (!d)
-        return fail(GNNB_ERR_INVALID, "null model description");
-    if (conv_slots(d->conv_type) < 0)
-        return fail(GNNB_ERR_INVALID, "unsupported conv_type %d", d->conv_type);
-    if (d->num_layers < 0 || d->num_layers > GNNB_MAX_LAYERS)
-        return fail(GNNB_ERR_INVALID, "num_layers %d out of range", d->num_layers);
-    if (d->in_dim < 1 || d->out_dim < 1 || (d->num_layers > 1 && d->hidden_dim < 1))
-        return fail(GNNB_ERR_INVALID, "feature dims must be positive");
-    if (d->num_layers == 0 && d->in_dim != d->out_dim) // models.py:512-518
-        return fail(GNNB_ERR_INVALID, "gnn_num_layers=0 needs gnn_output_dim == graph_input_feature_dim");
-    if (d->activation < 0 || d->activation > GNNB_ACT_TANH || d->mlp_activation < 0 ||
-        d->mlp_activation > GNNB_ACT_TANH)
-        return fail(GNNB_ERR_INVALID, "unsupported activation"); // models.py:362
-    if (d->num_pools < 1 || d->num_pools > 3)
-        return fail(GNNB_ERR_INVALID, "num_pools must be 1..3"); // models.py:332-333
-    for (int i = 0; i < d->num_pools; i++)
-        if (d->pools[i] < 0 || d->pools[i] > GNNB_POOL_MAX)
-            return fail(GNNB_ERR_INVALID, "unsupported pooling %d", d->pools[i]);
-    if (d->mlp_num_linear < 1 || d->mlp_num_linear > GNNB_MAX_LAYERS || d->mlp_out < 1 ||
-        (d->mlp_num_linear > 1 && d->mlp_hidden < 1))
-        return fail(GNNB_ERR_INVALID, "bad MLP head shape");
-    if (d->conv_type == GNNB_CONV_PNA && !(d->pna_delta > 0.0f))
-        return fail(GNNB_ERR_INVALID, "pna_delta must be > 0");
-    if (d->output_activation < GNNB_OUT_NONE || d->output_activation > GNNB_OUT_LOG_SOFTMAX)
-        return fail(GNNB_ERR_INVALID, "unsupported output_activation %d", d->output_activation);
-    if (d->fpx_w != 0 && (d->fpx_w < 2 || d->fpx_w > 32 || d->fpx_i < 1 || d->fpx_i > 33 || d->fpx_i > d->fpx_w ||
-                          d->fpx_w - d->fpx_i > 24))
-        return fail(GNNB_ERR_INVALID, "fixed-point emulation takes 2 <= W <= 32, 1 <= I <= W, W - I <= 24 (fp32 carries the "
-                                      "grid values exactly only up to 24 fractional bits)");
-    if (d->math < -1 || d->math > 3)
-        return fail(GNNB_ERR_INVALID, "math must be -1 (follow the process-wide option) or 0 .. 3 (fp32, bf16x6, bf16x3, f16x3)");
-    return GNNB_OK;
-}
-
 } // namespace gnnb
 
 using namespace gnnb;
-
-struct gnnb_model {
-    gnnb_model_desc desc;
-    float *blob = nullptr; // all weights, device
-    size_t blob_floats = 0;
-    // per conv layer device pointers (canonical slots; SAGE slot 0 is the fused [Wl|Wr])
-    std::vector<std::vector<const float *>> conv;
-    std::vector<const float *> head_w, head_b;
-    const float *zf_w1f = nullptr; // 2-layer GCN: layer 1's weight once more, in MFMA-fragment order (see k_gcn2_zf)
-    // GIN stacks (k_gcn2_fused<GIN>): every wide matrix once more in EXECUTION order, each hidden x hidden at one stride --
-    // Wb0 | Wa1 Wb1 | ... | Wa(L-1) Wb(L-1) -- and the biases likewise.  A last layer narrower than hidden (the reference's
-    // benchmark model: 128 -> 64, models.py:530-545) is zero-padded to hidden x hidden: its extra output columns are
-    // act(0 + 0) and never leave the kernel.  nullptr when the model is no GIN stack the kernel takes.
-    const float *gin_w = nullptr, *gin_b = nullptr;
-    HeadArgs *head_dev = nullptr; // the MLP head's {weights, biases, widths} once more in device memory: k_gcn2_zf reads it at the
-                                  // end of a workgroup's life (by value the 42 dwords stayed in scalar registers through its stage loop)
-    int device = 0;
-};
-
-struct gnnb_workspace {
-    gnnb_model_desc desc;
-    int max_graphs = 0, max_nodes = 0, max_edges = 0;
-    char *blob = nullptr;
-    size_t bytes = 0;
-    BatchTables t{};
-    float *act[2] = {nullptr, nullptr}; // ping-pong node embeddings [max_nodes, maxw]
-    float *agg = nullptr;               // aggregate output [max_nodes, aggw]
-    float *tmp0 = nullptr, *tmp1 = nullptr; // GIN hidden / PNA p,q
-    float *pooled = nullptr;            // [max_graphs, np*d]
-    float *mlp[2] = {nullptr, nullptr}; // [max_graphs, max(mlp_hidden, mlp_out)]
-    bool prepared = false;
-    float2 *pool_part = nullptr; // pieces of graphs that cross the 32-row blocks of the pooling GEMM epilogue (PoolEpilogue::part)
-    bool gcoef_ready = false; // t.gcoef holds the prepared batch's GCN coefficients (ensure_gcoef)
-    int max_graph_nodes = 0; // caller's promise (0 = none)
-    int max_degree = 0;      // caller's promise on the in-degree (0 = none): gnnb_workspace_set_max_degree
-    // PNA degree classes of the prepared batch (launch_degree_classes): valid when deg_ready; deg_delta = the delta it was prepared with
-    int32_t *deg_work = nullptr, *deg_perm = nullptr, *deg_tile_cls = nullptr;
-    int deg_max_tiles = 0;
-    bool deg_ready = false;
-    float deg_delta = 0.0f;
-    int32_t *plan_scratch = nullptr; // k_stage_cut's binary-lifting tables (GCN / GIN workspaces: stage_cut_levels x (max tiles + 1) ints)
-    float prep_delta = 0.0f; // the delta the prepared batch's amp / att tables were computed with (PNA workspaces; 0: none)
-    int last_path = GNNB_PATH_NONE; // which kernels the last forward on this workspace ran (gnnb_workspace_last_path)
-    // "large segment" of the NEXT batches (gnnb_workspace_set_large_segment): graphs [large_g, B) -- nodes from large_n,
-    // edges from large_e -- are exempt from the max_graph_nodes promise and run layer by layer; -1 = no such segment
-    int large_g = -1, large_n = -1, large_e = -1;
-    // fork / join for the large segment: its small kernels run on `side` beside the stack kernel on the caller's stream
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int device = 0;
-    int32_t *err_host = nullptr; // host-mapped word the prep kernel drops "flagged" into (lazy detection, see gnnb_graph_prep)
-    StreamK sk{};            // this workspace's own stream-K scratch (k_linear_dma's large-K tail; part == nullptr: the model has no such GEMM)
-    char *stage = nullptr;   // device staging of the host-buffer entry (x | coo | node_ptr | edge_ptr | out), sized for
-    size_t stage_bytes = 0;  // the workspace's capacities; allocated by the first gnnb_forward_batched_host call
-};
-
-static HeadArgs model_head_args(const gnnb_model *model)
-{
-    const gnnb_model_desc &d = model->desc;
-    HeadArgs head;
-    memset(&head, 0, sizeof(head));
-    head.nlin = d.mlp_num_linear;
-    for (int i = 0; i < head.nlin && i < 8; i++) {
-        int din, dout;
-        mlp_dims(d, i, &din, &dout);
-        head.w[i] = model->head_w[i];
-        head.b[i] = model->head_b[i];
-        head.dims[i] = din;
-        head.dims[i + 1] = dout;
-    }
-    return head;
-}
 
 // ---------------------------------------------------------------------------------------
 extern "C" {
@@ -260,368 +105,15 @@ int gnnb_set_option(const char *name, int value)
     Options &o = options();
     if (!name)
         return fail(GNNB_ERR_INVALID, "null option name");
-    if (!strcmp(name, "tile_rows") && value >= 4)
-        o.tile_rows = value;
-    else if (!strcmp(name, "agg_lds_kb") && value >= 0 && value <= 160)
-        o.agg_lds_kb = value; // 0 = default of the selected form
-    else if (!strcmp(name, "agg_ring_waves") && (value == 0 || value == 1 || value == 2 || value == 4 || value == 8 || value == 16))
-        o.agg_ring_waves = value;
-    else if (!strcmp(name, "agg_ring_slots") && value >= 1 && value <= 4)
-        o.agg_ring_slots = value;
-    else if (!strcmp(name, "agg_ring_wg_per_cu") && value >= 1 && value <= 4)
-        o.agg_ring_wg_per_cu = value;
-    else if (!strcmp(name, "agg_nt_store") && value >= 0 && value <= 1)
-        o.agg_nt_store = value;
-    else if (!strcmp(name, "agg_balance") && value >= 0 && value <= 1)
-        o.agg_balance = value;
-    else if (!strcmp(name, "sage_first_mean") && value >= 0 && value <= 1)
-        o.sage_first_mean = value;
-    else if (!strcmp(name, "pna_first") && value >= 0 && value <= 1)
-        o.pna_first = value;
-    else if (!strcmp(name, "pna_pagg") && value >= 0 && value <= 1)
-        o.pna_pagg = value;
-    else if (!strcmp(name, "stage_cut") && value >= 0 && value <= 1)
-        o.stage_cut = value;
-    else if (!strcmp(name, "zf_head") && value >= 0 && value <= 1)
-        o.zf_head = value;
-    else if (!strcmp(name, "prep_group") && (value == 1 || value == 4))
-        o.prep_group = value;
-    else if (!strcmp(name, "head_pairs") && value >= 0 && value <= 1)
-        o.head_pairs = value;
-    else if (!strcmp(name, "guest_prep") && value >= 0 && value <= 1)
-        o.guest_prep = value;
-    else if (!strcmp(name, "agg_form") && value >= 0 && value <= 2)
-        o.agg_form = value;
-    else if (!strcmp(name, "agg_rg_r") && value >= 0 && value <= 4)
-        o.agg_rg_r = value;
-    else if (!strcmp(name, "agg_rg_wgs") && value >= 0 && value <= 64)
-        o.agg_rg_wgs = value;
-    else if (!strcmp(name, "agg_rg_flags") && value >= 0 && value <= 15)
-        o.agg_rg_flags = value;
-    else if (!strcmp(name, "fuse_narrow") && value >= 0 && value <= 1)
-        o.fuse_narrow = value;
-    else if (!strcmp(name, "first_ring") && value >= 0 && value <= 1)
-        o.first_ring = value;
-    else if (!strcmp(name, "fuse_gcn2") && value >= 0 && value <= 1)
-        o.fuse_gcn2 = value;
-    else if (!strcmp(name, "fuse_zf") && value >= 0 && value <= 1)
-        o.fuse_zf = value;
-    else if (!strcmp(name, "zf_shape") && value >= 0 && value <= 2)
-        o.zf_shape = value;
-    else if (!strcmp(name, "large_fork") && value >= 0 && value <= 2)
-        o.large_fork = value;
-    else if (!strcmp(name, "fuse_head") && value >= 0 && value <= 1)
-        o.fuse_head = value;
-    else if (!strcmp(name, "fuse_pool") && value >= 0 && value <= 1)
-        o.fuse_pool = value;
-    else if (!strcmp(name, "head_split") && value >= 0 && value <= 1)
-        o.head_split = value;
-    else if (!strcmp(name, "head_small") && value >= 0 && value <= 1)
-        o.head_small = value;
-    else if (!strcmp(name, "math") && value >= 0 && value <= 3)
-        o.math = value;
-    else if (!strcmp(name, "gemm_variant") && value >= 0 && value <= 1)
-        o.gemm_variant = value;
-    else if (!strcmp(name, "gemm_dma") && value >= 0 && value <= 1)
-        o.gemm_dma = value;
-    else if (!strcmp(name, "gemm_tail_split") && value >= 0 && value <= 2)
-        o.gemm_tail_split = value;
-    else if (!strcmp(name, "pna_fold_lin") && value >= 0 && value <= 1)
-        o.pna_fold_lin = value;
-    else if (!strcmp(name, "pna_classes") && value >= 0 && value <= 1)
-        o.pna_classes = value;
-    else if (!strcmp(name, "fold_skip") && value >= 0 && value <= 1)
-        o.fold_skip = value;
-    else if (!strcmp(name, "gemm_wlds") && value >= 0 && value <= 1)
-        o.gemm_wlds = value;
-    else if (!strcmp(name, "gemm_wlds_slots") && value >= 1 && value <= 4)
-        o.gemm_wlds_slots = value;
-    else if (!strcmp(name, "gemm_max_wg_per_cu") && value >= 1 && value <= 8)
-        o.gemm_max_wg_per_cu = value;
-    else
-        return fail(GNNB_ERR_INVALID, "unknown option or bad value: %s=%d", name, value);
-    return GNNB_OK;
-}
-
-int gnnb_model_num_params(const gnnb_model_desc *desc)
-{
-    int rc = validate_desc(desc);
-    if (rc != GNNB_OK)
-        return rc;
-    return conv_slots(desc->conv_type) * desc->num_layers + 2 * desc->mlp_num_linear;
-}
-
-int gnnb_model_create(const gnnb_model_desc *desc, const float *const *host_params, int num_params,
-                      gnnb_model **out_model)
-{
-    if (!out_model)
-        return fail(GNNB_ERR_INVALID, "null out_model");
-    *out_model = nullptr;
-    int expect = gnnb_model_num_params(desc);
-    if (expect < 0)
-        return expect;
-    if (num_params != expect || !host_params)
-        return fail(GNNB_ERR_INVALID, "expected %d parameter tensors, got %d", expect, num_params);
-    for (int i = 0; i < num_params; i++)
-        if (!host_params[i])
-            return fail(GNNB_ERR_INVALID, "parameter %d is NULL", i);
-    if (gnnb_device_count() <= 0)
-        return fail(GNNB_ERR_NO_DEVICE, "no HIP device visible: the MI355X path cannot run");
-
-    const gnnb_model_desc &d = *desc;
-    // host staging image: every tensor padded to a 16-byte boundary
-    std::vector<float> img;
-    const bool fpx = d.fpx_w > 0;
-    const float q_inv = fpx ? ldexpf(1.0f, d.fpx_w - d.fpx_i) : 1.0f, q_step = fpx ? ldexpf(1.0f, -(d.fpx_w - d.fpx_i)) : 1.0f;
-    const float q_span = fpx ? ldexpf(1.0f, d.fpx_i) : 1.0f, q_half = fpx ? ldexpf(1.0f, d.fpx_i - 1) : 1.0f;
-    auto push = [&](const float *src, size_t n) -> size_t {
-        size_t off = img.size();
-        img.insert(img.end(), src, src + n);
-        if (fpx) // W_TYPE = ap_fixed<W, I>: the weights live on the grid (model.h.jinja:41-45)
-            for (size_t i = off; i < off + n; i++) {
-                float v = floorf(img[i] * q_inv) * q_step;
-                img[i] = v - q_span * floorf((v + q_half) / q_span);
-            }
-        while (img.size() % 4)
-            img.push_back(0.0f);
-        return off;
-    };
-    std::vector<std::vector<size_t>> conv_off(d.num_layers);
-    std::vector<size_t> hw, hb;
-    const int slots = conv_slots(d.conv_type);
-    int pi = 0;
-    for (int l = 0; l < d.num_layers; l++) {
-        const LayerDims ld = layer_dims(d, l);
-        const size_t fi = ld.fin, fo = ld.fout;
-        const float *const *p = host_params + pi;
-        // the layer's skip connection (middle layers: y = conv(x) + x, models.py:562-564) where x itself is an operand of
-        // the layer's GEMM (GraphSAGE's root term, PNA's x segment): folded into that operand's weights as + I, so that the
-        // [N, out] skip operand is not read again in the epilogue (45 of 293 us of a 128-wide PNA layer's GEMM went there:
-        // 32-byte pieces of 128-byte lines)
-        const bool skip_fold = d.skip && l != 0 && l != d.num_layers - 1 && fi == fo && !fpx;
-        switch (d.conv_type) {
-        case GNNB_CONV_GCN:
-            conv_off[l] = {push(p[0], fo * fi), push(p[1], fo)};
-            break;
-        case GNNB_CONV_GIN: // hidden = out_channels (models.py:90)
-            conv_off[l] = {push(p[0], fo * fi), push(p[1], fo), push(p[2], fo * fo), push(p[3], fo)};
-            break;
-        case GNNB_CONV_SAGE: {
-            // fuse lin_l and lin_r into one [out, 2*in] matrix: [Wl | Wr]
-            std::vector<float> cat(fo * 2 * fi);
-            for (size_t o = 0; o < fo; o++) {
-                memcpy(&cat[o * 2 * fi], p[0] + o * fi, fi * sizeof(float));
-                memcpy(&cat[o * 2 * fi + fi], p[2] + o * fi, fi * sizeof(float));
-            }
-            conv_off[l] = {push(cat.data(), cat.size()), push(p[1], fo)};
-            if (skip_fold) { // slot 2: [Wl | Wr + I]
-                for (size_t o = 0; o < fo; o++)
-                    cat[o * 2 * fi + fi + o] += 1.0f;
-                conv_off[l].push_back(push(cat.data(), cat.size()));
-            }
-            break;
-        }
-        case GNNB_CONV_PNA:
-            conv_off[l] = {push(p[0], fi * 2 * fi), push(p[1], fi), push(p[2], fo * 13 * fi),
-                           push(p[3], fo),          push(p[4], fo * fo), push(p[5], fo)};
-            // slots 6, 7: `lin` folded into the post-NN.  PNAConv applies them back to back with nothing in between
-            // (out = W_lin (W_post [x | S] + b_post) + b_lin, gnn_builder_lib.h:2081-2157), so
-            // W' = W_lin W_post [out, 13 F] and b' = W_lin b_post + b_lin (formed in double, rounded once) give the layer
-            // in ONE 13F-wide GEMM whose epilogue carries the skip operand and the activation: the out x out GEMM and the
-            // [N, out] hand-over between the two are gone (3 x ~55 us of a BASELINE config 4 step).  Not under the
-            // fixed-point emulation: the folded matrix is not on the weight grid.
-            if (!fpx) {
-                const size_t K13 = 13 * fi;
-                std::vector<double> acc(K13);
-                std::vector<float> wm(fo * K13), bm(fo);
-                for (size_t o = 0; o < fo; o++) {
-                    std::fill(acc.begin(), acc.end(), 0.0);
-                    double ab = (double)p[5][o];
-                    for (size_t h = 0; h < fo; h++) {
-                        const double wl = (double)p[4][o * fo + h];
-                        const float *wp = p[2] + h * K13;
-                        for (size_t k = 0; k < K13; k++)
-                            acc[k] += wl * (double)wp[k];
-                        ab += wl * (double)p[3][h];
-                    }
-                    if (skip_fold)
-                        acc[o] += 1.0; // (+ I on the x segment: the skip connection)
-                    for (size_t k = 0; k < K13; k++)
-                        wm[o * K13 + k] = (float)acc[k];
-                    bm[o] = (float)ab;
-                }
-                conv_off[l].push_back(push(wm.data(), wm.size()));
-                conv_off[l].push_back(push(bm.data(), bm.size()));
-                // slots 8, 9: the degree-class form (gnnb_workspace_set_max_degree): for every in-degree c = 0 .. 15 the matrix
-                //   ( W'_x + S_c Wq | W'_1 + amp W'_2 + att W'_3 ),  [out, 5 F],   and the bias  b' + S_c bq,
-                // of the folded W' above; amp / att as graph prep computes them (k_prep.hip: logf(d + 1) / delta and its
-                // reciprocal, d = max(c, 1)).  S_c = the max + min + mean column blocks of the class's A matrix: the
-                // destination's own pre-NN term q_i = Wq x_i + bq shifts max, min and mean of its messages by q_i and
-                // leaves std alone (gnn_builder_lib.h:1801-1850), so it is folded into x's weights too and the q GEMM is
-                // not run at all.  Class 0 (no messages: the four aggregates are 0, not q) carries no S term.
-                if (fo > 32) { // (any input width: whole 32-wide chunks take k_linear_dma's row-class mode, others the generic kernel's)
-                    const size_t K5 = 5 * fi;
-                    std::vector<float> wc((size_t)GNNB_DEG_CLASSES * fo * K5), bc((size_t)GNNB_DEG_CLASSES * fo);
-                    std::vector<double> wa(4 * fi), sq(fi), sqw(fi);
-                    const float *wq = p[0]; // W_pre [F, 2F]: columns [0, F) act on the destination x_i (lib:1801-1802), bias p[1]
-                    for (int c = 0; c < GNNB_DEG_CLASSES; c++) {
-                        const float lg = logf((float)std::max(c, 1) + 1.0f);
-                        const double amp = (double)(lg / d.pna_delta), att = (double)(d.pna_delta / lg);
-                        float *dst = &wc[(size_t)c * fo * K5];
-                        for (size_t o = 0; o < fo; o++) {
-                            const float *src = &wm[o * K13];
-                            for (size_t k = 0; k < 4 * fi; k++)
-                                wa[k] = (double)src[fi + k] + amp * (double)src[5 * fi + k] + att * (double)src[9 * fi + k];
-                            for (size_t k = 0; k < 4 * fi; k++)
-                                dst[o * K5 + fi + k] = (float)wa[k];
-                            double bsum = (double)bm[o];
-                            if (c > 0) {
-                                for (size_t k = 0; k < fi; k++)
-                                    sq[k] = wa[k] + wa[fi + k] + wa[2 * fi + k]; // S_c[o][k]: max + min + mean
-                                // (S_c Wq)[o][j] = sum_k S_c[o][k] Wq[k][j], k ascending from src[j] as before, but walked
-                                // along Wq's rows: the column walk (stride 2F) made a 1024-wide PNA layer's upload ~80 s
-                                for (size_t j = 0; j < fi; j++)
-                                    sqw[j] = (double)src[j];
-                                for (size_t k = 0; k < fi; k++) {
-                                    const double s = sq[k];
-                                    const float *wr = wq + k * 2 * fi;
-                                    for (size_t j = 0; j < fi; j++)
-                                        sqw[j] += s * (double)wr[j];
-                                }
-                                for (size_t j = 0; j < fi; j++)
-                                    dst[o * K5 + j] = (float)sqw[j];
-                                for (size_t k = 0; k < fi; k++)
-                                    bsum += sq[k] * (double)p[1][k];
-                            } else {
-                                for (size_t j = 0; j < fi; j++)
-                                    dst[o * K5 + j] = src[j];
-                            }
-                            bc[(size_t)c * fo + o] = (float)bsum;
-                        }
-                    }
-                    conv_off[l].push_back(push(wc.data(), wc.size()));
-                    conv_off[l].push_back(push(bc.data(), bc.size()));
-                }
-            }
-            break;
-        }
-        pi += slots;
+    const int v = value;
+#define GNNB_OPTION_SET(opt, dflt, accepts)                                                        \
+    if (!strcmp(name, #opt) && (accepts)) {                                                        \
+        o.opt = v;                                                                                 \
+        return GNNB_OK;                                                                            \
     }
-    // k_gcn2_zf reads its 16-column slice of the last GCN layer's weight as MFMA B fragments: lane (li, lg) of the wave that
-    // owns slice s takes W[16 s + li][16 q + 4 lg .. + 3] for q = 0 .. K/16 - 1.  Straight from the [out][in] matrix that is
-    // 16 rows x 64 B per load instruction (half of every 128-B line unused, 32 MB of L2 traffic per launch over the chip);
-    // a second copy in fragment order -- float4 index ((s K/16 + q) 4 + lg) 16 + li -- makes every load instruction one
-    // contiguous KiB.  Rows past `out` are zero.
-    size_t w1f_off = 0;
-    bool have_w1f = false;
-    if (d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128) {
-        const int K = d.hidden_dim, KQ = K / 16, NS = (d.out_dim + 15) / 16;
-        std::vector<float> frag((size_t)NS * 16 * K, 0.0f);
-        const float *w1 = &img[conv_off[1][0]]; // (the image copy: already on the fixed-point grid when fpx is set)
-        for (int s = 0; s < NS; s++)
-            for (int q = 0; q < KQ; q++)
-                for (int lg = 0; lg < 4; lg++)
-                    for (int li = 0; li < 16; li++) {
-                        const int n = 16 * s + li;
-                        if (n >= d.out_dim)
-                            continue;
-                        for (int e = 0; e < 4; e++)
-                            frag[((((size_t)s * KQ + q) * 4 + lg) * 16 + li) * 4 + e] = w1[(size_t)n * K + 16 * q + 4 * lg + e];
-                    }
-        const bool fpx_save = fpx;
-        (void)fpx_save;
-        // (push() would quantise again: harmless -- the grid is idempotent)
-        w1f_off = push(frag.data(), frag.size());
-        have_w1f = true;
-    }
-    size_t gin_w_off = 0, gin_b_off = 0;
-    bool have_gin = false;
-    if (d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
-        d.out_dim <= d.hidden_dim && d.out_dim % 4 == 0) {
-        const size_t h = d.hidden_dim, ho = d.out_dim;
-        const int L = d.num_layers, nm = 2 * L - 1;
-        std::vector<float> gw((size_t)nm * h * h, 0.0f), gb((size_t)nm * h, 0.0f);
-        auto put = [&](int idx, size_t off_w, size_t off_b, size_t rows, size_t cols) { // [rows, cols] -> top-left of slot idx
-            for (size_t r = 0; r < rows; r++)
-                memcpy(&gw[(size_t)idx * h * h + r * h], &img[off_w + r * cols], cols * sizeof(float));
-            memcpy(&gb[(size_t)idx * h], &img[off_b], rows * sizeof(float));
-        };
-        put(0, conv_off[0][2], conv_off[0][3], L == 1 ? ho : h, L == 1 ? ho : h); // (layer 0's second linear)
-        for (int l = 1; l < L; l++) {
-            const size_t fo = l == L - 1 ? ho : h;
-            put(2 * l - 1, conv_off[l][0], conv_off[l][1], fo, h); // Wa [fo, h]
-            put(2 * l, conv_off[l][2], conv_off[l][3], fo, fo);     // Wb [fo, fo]
-        }
-        gin_w_off = push(gw.data(), gw.size());
-        gin_b_off = push(gb.data(), gb.size());
-        have_gin = true;
-    }
-    for (int i = 0; i < d.mlp_num_linear; i++) {
-        int din, dout;
-        mlp_dims(d, i, &din, &dout);
-        hw.push_back(push(host_params[pi], (size_t)din * dout));
-        hb.push_back(push(host_params[pi + 1], (size_t)dout));
-        pi += 2;
-    }
-
-    gnnb_model *m = new gnnb_model();
-    m->desc = d;
-    (void)hipGetDevice(&m->device);
-    m->blob_floats = img.size();
-    hipError_t e = hipMalloc((void **)&m->blob, std::max<size_t>(img.size(), 4) * sizeof(float));
-    if (e == hipSuccess && !img.empty())
-        e = hipMemcpy(m->blob, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (m->blob)
-            (void)hipFree(m->blob);
-        delete m;
-        return fail(GNNB_ERR_HIP, "weight upload failed: %s", hipGetErrorString(e));
-    }
-    m->conv.resize(d.num_layers);
-    for (int l = 0; l < d.num_layers; l++)
-        for (size_t off : conv_off[l])
-            m->conv[l].push_back(m->blob + off);
-    if (have_w1f)
-        m->zf_w1f = m->blob + w1f_off;
-    if (have_gin) {
-        m->gin_w = m->blob + gin_w_off;
-        m->gin_b = m->blob + gin_b_off;
-    }
-    for (int i = 0; i < d.mlp_num_linear; i++) {
-        m->head_w.push_back(m->blob + hw[i]);
-        m->head_b.push_back(m->blob + hb[i]);
-    }
-    if (d.mlp_num_linear <= 8) { // (best effort: without the device copy the stack kernels leave the head to its own launch)
-        const HeadArgs h = model_head_args(m);
-        if (hipMalloc((void **)&m->head_dev, sizeof(HeadArgs)) != hipSuccess ||
-            hipMemcpy(m->head_dev, &h, sizeof(HeadArgs), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            if (m->head_dev)
-                (void)hipFree(m->head_dev);
-            m->head_dev = nullptr;
-        }
-    }
-    *out_model = m;
-    return GNNB_OK;
-}
-
-void gnnb_model_destroy(gnnb_model *model)
-{
-    if (!model)
-        return;
-    if (model->blob)
-        (void)hipFree(model->blob);
-    if (model->head_dev)
-        (void)hipFree(model->head_dev);
-    delete model;
-}
-
-int gnnb_model_get_desc(const gnnb_model *model, gnnb_model_desc *out_desc)
-{
-    if (!model || !out_desc)
-        return fail(GNNB_ERR_INVALID, "null argument");
-    *out_desc = model->desc;
-    return GNNB_OK;
+    GNNB_OPTIONS(GNNB_OPTION_SET)
+#undef GNNB_OPTION_SET
+    return fail(GNNB_ERR_INVALID, "unknown option or bad value: %s=%d", name, value);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -812,25 +304,64 @@ int gnnb_workspace_set_max_degree(gnnb_workspace *ws, int d)
 static BatchTables small_segment(const gnnb_workspace *ws);
 
 // ---------------------------------------------------------------------------------------
+// The prep plan: what graph prep has to know about a workspace, each question answered in ONE place.  All of it is a handful
+// of integer tests on the workspace and the options: nothing here allocates or looks anything up.
+
+// A GCN / GIN model of two or more layers under a max_graph_nodes promise, with the stack kernels on: the batch (its small
+// segment) is meant for the LDS-resident stack kernels, so the node tiles are sized for their stages
+static bool stack_promised(const gnnb_workspace *ws)
+{
+    const gnnb_model_desc &d = ws->desc;
+    return options().fuse_gcn2 && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 && ws->max_graph_nodes > 0;
+}
+
+// ... and the WHOLE batch is expected there: no large segment, no fixed-point emulation.  Such a batch needs neither the
+// row-balanced aggregate ranges nor the GCN coefficient table.  (One predicate for three sites that used to spell it out: the
+// two that ask about the coefficient table are inside conv_type == GCN, where "GCN or GIN" adds nothing; the one that asks
+// about the aggregate ranges ANDs large_g < 0 beside it -- !(P && large_g < 0) && large_g < 0 == !P && large_g < 0 -- so the
+// truth tables coincide.)
+static bool stack_expected(const gnnb_workspace *ws) { return stack_promised(ws) && ws->large_g < 0 && ws->desc.fpx_w <= 0; }
+
+// Which stack kernel a promised batch gets and how many rows its stages hold: a 2-layer fp32 GCN stack runs k_gcn2_zf (96- or
+// 176-row stages), everything else k_gcn2_fused (64 rows; 48 in the bf16x6 mode, which only the 2-layer GCN form has)
+struct StackKernel {
+    bool zf, bf6;
+    int stage_rows;
+};
+static StackKernel promised_stack_kernel(const gnnb_workspace *ws)
+{
+    const gnnb_model_desc &d = ws->desc;
+    const bool gcn2 = d.conv_type == GNNB_CONV_GCN && d.num_layers == 2;
+    StackKernel k;
+    k.zf = gcn2 && options().fuse_zf;
+    k.bf6 = !k.zf && launch_math() && gcn2;
+    k.stage_rows = k.zf ? zf_stage_rows(d.in_dim, ws->max_graph_nodes) : k.bf6 ? GNNB_G2_STAGE_ROWS_BF6 : GNNB_G2_STAGE_ROWS;
+    return k;
+}
+
+// PNA under a degree promise: graph prep sorts the rows into degree classes behind the tables
+static bool wants_degree_classes(const gnnb_workspace *ws)
+{
+    return ws->desc.conv_type == GNNB_CONV_PNA && ws->max_degree > 0 && ws->max_degree <= GNNB_DEG_MAX && options().pna_classes && ws->deg_perm &&
+           ws->large_g < 0 && ws->desc.fpx_w <= 0;
+}
+
+// The stage-cut planner MAY run behind the tables: the option is on and the workspace was created with its scratch.  (Coarse on
+// purpose: it is asked before tile counts exist.  What graph_prep_impl launches under is this AND the conditions at the site.)
+static bool may_plan_stage_cuts(const gnnb_workspace *ws) { return options().stage_cut && ws->plan_scratch; }
+
+// GCN: the coefficient table is produced behind the tables unless the whole batch is expected on the stack kernels
+static bool wants_gcoef_at_prep(const gnnb_workspace *ws) { return ws->desc.conv_type == GNNB_CONV_GCN && !stack_expected(ws); }
+
 // Can this workspace's graph prep run as a guest of the forward's readout kernel (k_head_small's extra workgroups)?  The molecule
 // path (promise <= 64 nodes) of a batch that needs NOTHING launched behind its tables: no stage cuts, no degree classes, no
-// coefficient table -- the conditions below are the ones graph_prep_impl launches those under.
+// coefficient table -- the same predicates graph_prep_impl launches those under.
 static bool guest_prep_eligible(const gnnb_workspace *ws, int num_nodes)
 {
     if (!options().guest_prep || ws->max_graph_nodes <= 0 || ws->max_graph_nodes > 64 || ws->large_g >= 0 || num_nodes <= 0)
         return false;
-    if (options().stage_cut && ws->plan_scratch)
-        return false;
-    if (ws->desc.conv_type == GNNB_CONV_PNA && ws->max_degree > 0 && ws->max_degree <= GNNB_DEG_MAX && options().pna_classes && ws->deg_perm &&
-        ws->desc.fpx_w <= 0)
-        return false;
-    if (ws->desc.conv_type == GNNB_CONV_GCN) {
-        const bool stack_expected = options().fuse_gcn2 && ws->desc.num_layers >= 2 && ws->max_graph_nodes > 0 && ws->large_g < 0 && ws->desc.fpx_w <= 0;
-        if (!stack_expected)
-            return false;
-    }
     // (the row-balanced aggregate ranges are part of the prep kernel itself: nothing behind it)
-    return true;
+    return !may_plan_stage_cuts(ws) && !wants_degree_classes(ws) && !wants_gcoef_at_prep(ws);
 }
 
 // defer != nullptr (and guest_prep_eligible): everything gnnb_graph_prep does EXCEPT the launch -- *defer receives the kernel's arguments
@@ -887,17 +418,13 @@ static int graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int
     t.tile_rows = std::max((int)options().tile_rows, 4);
     // A 2-layer GCN with a promise takes the fused stack only if a whole tile (tile_rows - 1 + largest graph) fits
     // one 64-row stage (48 in the bf16x6 mode): for graphs of 50..61 nodes finer tiles (8, 4) keep that path open
-    if (options().fuse_gcn2 && (ws->desc.conv_type == GNNB_CONV_GCN || ws->desc.conv_type == GNNB_CONV_GIN) && ws->desc.num_layers >= 2 &&
-        ws->max_graph_nodes > 0) {
-        // (a 2-layer fp32 GCN stack runs k_gcn2_zf with its 96-row stages; everything else k_gcn2_fused)
-        const bool zf = ws->desc.conv_type == GNNB_CONV_GCN && ws->desc.num_layers == 2 && options().fuse_zf;
-        const bool bf6 = !zf && launch_math() && ws->desc.conv_type == GNNB_CONV_GCN && ws->desc.num_layers == 2; // (the only bf16x6 stack form)
-        const int stage_rows = zf ? zf_stage_rows(ws->desc.in_dim, ws->max_graph_nodes) : bf6 ? GNNB_G2_STAGE_ROWS_BF6 : GNNB_G2_STAGE_ROWS;
-        while (t.tile_rows > 4 && ws->max_graph_nodes + t.tile_rows - 1 > stage_rows)
+    if (stack_promised(ws)) {
+        const StackKernel k = promised_stack_kernel(ws);
+        while (t.tile_rows > 4 && ws->max_graph_nodes + t.tile_rows - 1 > k.stage_rows)
             t.tile_rows >>= 1;
         // very large batches: coarser tiles (while a tile still fits a stage) keep the per-workgroup tile table in LDS
-        const long tile_cap = zf ? gcn2_zf_tile_capacity(ws->desc.in_dim, ws->max_graph_nodes) : gcn2_fused_tile_capacity();
-        while ((num_nodes + t.tile_rows - 1) / t.tile_rows > tile_cap && ws->max_graph_nodes + 2 * t.tile_rows - 1 <= stage_rows)
+        const long tile_cap = k.zf ? gcn2_zf_tile_capacity(ws->desc.in_dim, ws->max_graph_nodes) : gcn2_fused_tile_capacity();
+        while ((num_nodes + t.tile_rows - 1) / t.tile_rows > tile_cap && ws->max_graph_nodes + 2 * t.tile_rows - 1 <= k.stage_rows)
             t.tile_rows <<= 1;
     }
     t.num_tiles = (num_nodes + t.tile_rows - 1) / t.tile_rows;
@@ -905,10 +432,8 @@ static int graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int
     // not for a batch that is expected on the stack kernels entirely (their graph prep is on the pipeline's critical path
     // and pays for every instruction), not with a large segment (its aggregates walk a tile sub-range)
     {
-        const bool stack_expected = options().fuse_gcn2 && (ws->desc.conv_type == GNNB_CONV_GCN || ws->desc.conv_type == GNNB_CONV_GIN) &&
-                                    ws->desc.num_layers >= 2 && ws->max_graph_nodes > 0 && ws->desc.fpx_w <= 0;
         const int rings = aggregate_ring_grid();
-        t.agg_cut_n = (options().agg_balance && !stack_expected && ws->large_g < 0 && rings <= 4096 && (rings & (rings - 1)) == 0 &&
+        t.agg_cut_n = (options().agg_balance && !stack_expected(ws) && ws->large_g < 0 && rings <= 4096 && (rings & (rings - 1)) == 0 &&
                        t.num_tiles >= rings) ? rings : 0;
     }
     if (!(pna_delta > 0.0f))
@@ -939,14 +464,12 @@ static int graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int
     // the conv-stack kernel's workgroup runs as whole stages of the global greedy stage list (k_plan.hip), right behind the tables
     // on the prep stream: for the batches that k_gcn2_fused takes (GIN stacks, GCN stacks deeper than two layers, the bf16x6 mode)
     t.stage_cut_n = 0;
-    if (options().stage_cut && options().fuse_gcn2 && ws->plan_scratch && ws->max_graph_nodes > 0 && ws->desc.fpx_w <= 0 && num_nodes > 0) {
-        const bool zf_route = ws->desc.conv_type == GNNB_CONV_GCN && ws->desc.num_layers == 2 && options().fuse_zf;
-        const bool bf6 = !zf_route && launch_math() && ws->desc.conv_type == GNNB_CONV_GCN && ws->desc.num_layers == 2;
-        const int cap = bf6 ? GNNB_G2_STAGE_ROWS_BF6 : GNNB_G2_STAGE_ROWS;
+    if (may_plan_stage_cuts(ws) && stack_promised(ws) && ws->desc.fpx_w <= 0 && num_nodes > 0) { // (the scratch exists for GCN / GIN stacks only)
+        const StackKernel k = promised_stack_kernel(ws);
         const BatchTables ts = small_segment(ws);
         const int grid = gcn2_fused_grid(ts.num_tiles);
-        if (!zf_route && ws->max_graph_nodes + t.tile_rows - 1 <= cap && grid <= t.stage_cut_cap && ts.num_tiles > 0) {
-            GNNB_HIP_TRY(launch_stage_cut(t.tile_first, ts.num_tiles, ts.num_nodes, cap, grid, gcn2_fused_tile_window(), ws->plan_scratch,
+        if (!k.zf && ws->max_graph_nodes + t.tile_rows - 1 <= k.stage_rows && grid <= t.stage_cut_cap && ts.num_tiles > 0) {
+            GNNB_HIP_TRY(launch_stage_cut(t.tile_first, ts.num_tiles, ts.num_nodes, k.stage_rows, grid, gcn2_fused_tile_window(), ws->plan_scratch,
                                           t.stage_cut, (hipStream_t)stream));
             t.stage_cut_n = grid;
         }
@@ -954,8 +477,7 @@ static int graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int
     ws->gcoef_ready = false;
     // PNA under a degree promise: the rows sorted into degree classes, right behind the tables on the prep stream
     ws->deg_ready = false;
-    if (ws->desc.conv_type == GNNB_CONV_PNA && ws->max_degree > 0 && ws->max_degree <= GNNB_DEG_MAX && options().pna_classes &&
-        ws->deg_perm && ws->large_g < 0 && ws->desc.fpx_w <= 0) {
+    if (wants_degree_classes(ws)) {
         ws->deg_max_tiles = (num_nodes + 127) / 128 + GNNB_DEG_CLASSES;
         GNNB_HIP_TRY(launch_degree_classes(t, ws->max_degree, ws->deg_work, ws->deg_perm, ws->deg_tile_cls, ws->deg_max_tiles,
                                            (hipStream_t)stream));
@@ -968,13 +490,9 @@ static int graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int
     // ordered against the prep see a finished table.  Only a workspace whose whole batch is expected on the LDS-resident
     // stack kernels (promise set, no large segment) skips it; should that forward fall back after all, ensure_gcoef
     // launches the table kernel in front of the first aggregate (the one lazy case left).
-    if (ws->desc.conv_type == GNNB_CONV_GCN && num_nodes > 0) {
-        const bool stack_expected = options().fuse_gcn2 && ws->desc.num_layers >= 2 && ws->max_graph_nodes > 0 &&
-                                    ws->large_g < 0 && ws->desc.fpx_w <= 0;
-        if (!stack_expected) {
-            GNNB_HIP_TRY(launch_gcn_coef(ws->t, (hipStream_t)stream));
-            ws->gcoef_ready = true;
-        }
+    if (wants_gcoef_at_prep(ws) && num_nodes > 0) {
+        GNNB_HIP_TRY(launch_gcn_coef(ws->t, (hipStream_t)stream));
+        ws->gcoef_ready = true;
     }
     return GNNB_OK;
 }
@@ -1204,6 +722,7 @@ int gnnb_global_pool(gnnb_workspace *ws, const float *x_dev, int d, const int32_
 }
 
 // ---------------------------------------------------------------------------------------
+// one plain GEMM through the stand-alone entry (its stream-K scratch: per (device, stream), not a workspace's)
 static int linear1(const float *a, int lda, int k, const float *w, int ldw, const float *bias,
                    const float *skip, float *y, int M, int N, int act, void *stream)
 {
@@ -1211,6 +730,42 @@ static int linear1(const float *a, int lda, int k, const float *w, int ldw, cons
     return gnnb_linear(&seg, 1, w, ldw, bias, skip, y, M, N, act, stream);
 }
 
+// One attempt at a launcher that may decline: it ran (TOOK), it launched nothing and the next form is tried (DECLINED:
+// hipErrorNotSupported), or it failed -- FAILED: "<what> launch failed: ..." is the error text and GNNB_ERR_HIP the code to return
+enum Attempt { TOOK, DECLINED, FAILED };
+static Attempt attempt(hipError_t he, const char *what)
+{
+    if (he == hipSuccess)
+        return TOOK;
+    if (he == hipErrorNotSupported)
+        return DECLINED;
+    (void)fail(GNNB_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(he));
+    return FAILED;
+}
+
+// fixed-point emulation only: put a finished tensor on the model's ap_fixed<W, I> grid
+static int quantize(const gnnb_model_desc &d, float *buf, size_t n, void *stream)
+{
+    if (d.fpx_w <= 0)
+        return GNNB_OK;
+    GNNB_HIP_TRY(launch_quantize(buf, buf, n, d.fpx_w, d.fpx_i, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+// global pooling in the epilogue of the last conv layer's GEMM: into ws->pooled, by the model's pools
+static PoolEpilogue pool_epilogue(const gnnb_workspace *ws, const gnnb_model_desc &d)
+{
+    PoolEpilogue pe;
+    pe.node_graph = ws->t.node_graph;
+    pe.graph_ptr = ws->t.graph_ptr;
+    pe.pooled = ws->pooled;
+    pe.part = ws->pool_part;
+    pe.num_graphs = ws->t.num_graphs;
+    pe.np = d.num_pools;
+    for (int k = 0; k < 3; k++)
+        pe.pools[k] = k < d.num_pools ? d.pools[k] : 0;
+    return pe;
+}
 
 // Middle layers of a GCN stack for the fused kernel: every one hidden -> hidden, weights / biases at one constant
 // stride in the model blob (it is laid out layer by layer, so they are -- checked, not assumed).  nl = 0: not eligible.
@@ -1264,21 +819,16 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
     const int N = ws->t.num_nodes, M = N - row_lo;
     int rc;
     const bool fpx = d.fpx_w > 0;
-    auto quant = [&](float *buf, size_t n) -> int {
-        if (!fpx)
-            return GNNB_OK;
-        GNNB_HIP_TRY(launch_quantize(buf, buf, n, d.fpx_w, d.fpx_i, (hipStream_t)stream));
-        return GNNB_OK;
-    };
     BatchTables tv = ws->t;
     tv.tile_lo = tile_lo;
     const StreamK *const sko = ws->sk.part ? &ws->sk : nullptr; // this workspace's stream-K scratch
-    auto gnnb_linear = [&](const gnnb_gemm_seg *segs, int num_segs, const float *w_dev, int ldw, const float *bias_dev, const float *skip_dev,
-                           float *y_dev, int M_, int N_, int act, void *st) -> int {
+    // the layers' GEMMs, on the workspace's scratch (unlike the stand-alone gnnb_linear / linear1)
+    auto ws_linear = [&](const gnnb_gemm_seg *segs, int num_segs, const float *w_dev, int ldw, const float *bias_dev, const float *skip_dev,
+                         float *y_dev, int M_, int N_, int act, void *st) -> int {
         return linear_segs(sko, segs, num_segs, w_dev, ldw, bias_dev, skip_dev, y_dev, M_, N_, act, st);
     };
-    auto linear1 = [&](const float *a, int lda, int k, const float *w, int ldw, const float *bias, const float *skip_, float *y, int M_, int N_,
-                       int act, void *st) -> int {
+    auto ws_linear1 = [&](const float *a, int lda, int k, const float *w, int ldw, const float *bias, const float *skip_, float *y, int M_, int N_,
+                          int act, void *st) -> int {
         gnnb_gemm_seg seg = {a, nullptr, lda, k};
         return linear_segs(sko, &seg, 1, w, ldw, bias, skip_, y, M_, N_, act, st);
     };
@@ -1316,35 +866,34 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
         case GNNB_CONV_GCN:
             // aggregate at the input width, then transform (the reference's order, lib:1346-1379)
             if (whole && options().fuse_narrow && fi <= 32) {
-                hipError_t he = launch_conv_gather(ws->t, GNNB_AGG_GCN, 0.f, cur, fi, fi, p[0], fi, p[1], skip, nxt,
-                                                   fo, d.activation, (hipStream_t)stream);
-                if (he == hipSuccess)
+                const Attempt at = attempt(launch_conv_gather(ws->t, GNNB_AGG_GCN, 0.f, cur, fi, fi, p[0], fi, p[1], skip, nxt,
+                                                              fo, d.activation, (hipStream_t)stream), "fused narrow conv");
+                if (at == FAILED)
+                    return GNNB_ERR_HIP;
+                if (at == TOOK)
                     break;
-                if (he != hipErrorNotSupported)
-                    return fail(GNNB_ERR_HIP, "fused narrow conv launch failed: %s", hipGetErrorString(he));
             }
             if ((rc = aggregate(GNNB_AGG_GCN, cur, nullptr, ws->agg, fi, 0.f)))
                 return rc;
-            if ((rc = linear1(R(ws->agg, fi), fi, fi, p[0], fi, p[1], R(skip, fi), Rw(nxt, fo), M, fo, d.activation, stream)))
+            if ((rc = ws_linear1(R(ws->agg, fi), fi, fi, p[0], fi, p[1], R(skip, fi), Rw(nxt, fo), M, fo, d.activation, stream)))
                 return rc;
             break;
         case GNNB_CONV_GIN: {
             bool fused = false;
             if (whole && options().fuse_narrow && fi <= 32) {
-                hipError_t he = launch_conv_gather(ws->t, GNNB_AGG_SUM, d.gin_eps, cur, fi, fi, p[0], fi, p[1], nullptr,
-                                                   ws->tmp0, fo, GNNB_ACT_RELU, (hipStream_t)stream);
-                if (he == hipSuccess)
-                    fused = true;
-                else if (he != hipErrorNotSupported)
-                    return fail(GNNB_ERR_HIP, "fused narrow conv launch failed: %s", hipGetErrorString(he));
+                const Attempt at = attempt(launch_conv_gather(ws->t, GNNB_AGG_SUM, d.gin_eps, cur, fi, fi, p[0], fi, p[1], nullptr,
+                                                              ws->tmp0, fo, GNNB_ACT_RELU, (hipStream_t)stream), "fused narrow conv");
+                if (at == FAILED)
+                    return GNNB_ERR_HIP;
+                fused = at == TOOK;
             }
             if (!fused) {
                 if ((rc = aggregate(GNNB_AGG_SUM, cur, nullptr, ws->agg, fi, d.gin_eps)))
                     return rc;
-                if ((rc = linear1(R(ws->agg, fi), fi, fi, p[0], fi, p[1], nullptr, Rw(ws->tmp0, fo), M, fo, GNNB_ACT_RELU, stream)))
+                if ((rc = ws_linear1(R(ws->agg, fi), fi, fi, p[0], fi, p[1], nullptr, Rw(ws->tmp0, fo), M, fo, GNNB_ACT_RELU, stream)))
                     return rc;
             }
-            if ((rc = linear1(R(ws->tmp0, fo), fo, fo, p[2], fo, p[3], R(skip, fo), Rw(nxt, fo), M, fo, d.activation, stream)))
+            if ((rc = ws_linear1(R(ws->tmp0, fo), fo, fo, p[2], fo, p[3], R(skip, fo), Rw(nxt, fo), M, fo, d.activation, stream)))
                 return rc;
             break;
         }
@@ -1352,22 +901,22 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
             if (whole && options().fuse_narrow && 2 * fi <= 32 && l + 1 < d.num_layers && skip == nullptr && !fpx) {
                 // narrow input AND a layer behind it: the stage's output rows stay in LDS and the next layer's mean aggregate is
                 // taken from there -- its aggregate kernel (a full read and write of [N, fo]) is not run
-                hipError_t he = launch_sage_first_mean(ws->t, cur, fi, p[0], 2 * fi, p[1], nxt, ws->agg, fo, d.activation, (hipStream_t)stream);
-                if (he == hipSuccess) {
+                const Attempt at = attempt(launch_sage_first_mean(ws->t, cur, fi, p[0], 2 * fi, p[1], nxt, ws->agg, fo, d.activation, (hipStream_t)stream), "first-layer + mean");
+                if (at == FAILED)
+                    return GNNB_ERR_HIP;
+                if (at == TOOK) {
                     mean_ready = true;
                     break;
                 }
-                if (he != hipErrorNotSupported)
-                    return fail(GNNB_ERR_HIP, "first-layer + mean launch failed: %s", hipGetErrorString(he));
             }
             if (whole && options().fuse_narrow && 2 * fi <= 32) {
                 // narrow input: [mean_j x_j | x_i] is produced inside the GEMM's A stage (K = 2 F_in)
-                hipError_t he = launch_conv_gather(ws->t, GNNB_AGG_MEAN, 0.f, cur, fi, 2 * fi, p[0], 2 * fi, p[1], skip, nxt,
-                                                   fo, d.activation, (hipStream_t)stream, fi);
-                if (he == hipSuccess)
+                const Attempt at = attempt(launch_conv_gather(ws->t, GNNB_AGG_MEAN, 0.f, cur, fi, 2 * fi, p[0], 2 * fi, p[1], skip, nxt,
+                                                              fo, d.activation, (hipStream_t)stream, fi), "fused narrow conv");
+                if (at == FAILED)
+                    return GNNB_ERR_HIP;
+                if (at == TOOK)
                     break;
-                if (he != hipErrorNotSupported)
-                    return fail(GNNB_ERR_HIP, "fused narrow conv launch failed: %s", hipGetErrorString(he));
             }
             if (!mean_ready && (rc = aggregate(GNNB_AGG_MEAN, cur, nullptr, ws->agg, fi, 0.f)))
                 return rc;
@@ -1381,41 +930,33 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
                 GemmArgs g;
                 if ((rc = build_gemm(g, segs, 2, p[0], 2 * fi)))
                     return rc;
-                PoolEpilogue pe;
-                pe.node_graph = ws->t.node_graph;
-                pe.graph_ptr = ws->t.graph_ptr;
-                pe.pooled = ws->pooled;
-                pe.part = ws->pool_part;
-                pe.num_graphs = ws->t.num_graphs;
-                pe.np = d.num_pools;
-                for (int k = 0; k < 3; k++)
-                    pe.pools[k] = k < d.num_pools ? d.pools[k] : 0;
-                hipError_t he = launch_linear(g, p[0], 2 * fi, p[1], nullptr, nxt, M, fo, d.activation, (hipStream_t)stream, &pe);
-                if (he == hipSuccess) {
+                const PoolEpilogue pe = pool_epilogue(ws, d);
+                const Attempt at = attempt(launch_linear(g, p[0], 2 * fi, p[1], nullptr, nxt, M, fo, d.activation, (hipStream_t)stream, &pe), "pooling GEMM");
+                if (at == FAILED)
+                    return GNNB_ERR_HIP;
+                if (at == TOOK) {
                     GNNB_HIP_TRY(launch_pool_combine(pe, M, fo, (hipStream_t)stream));
                     *pooled_in_epilogue = true;
                     break;
                 }
-                if (he != hipErrorNotSupported)
-                    return fail(GNNB_ERR_HIP, "pooling GEMM launch failed: %s", hipGetErrorString(he));
             }
             if (skip_fold && p.size() >= 3 && options().fold_skip) { // (slot 2: [Wl | Wr + I])
-                if ((rc = gnnb_linear(segs, 2, p[2], 2 * fi, p[1], nullptr, Rw(nxt, fo), M, fo, d.activation, stream)))
+                if ((rc = ws_linear(segs, 2, p[2], 2 * fi, p[1], nullptr, Rw(nxt, fo), M, fo, d.activation, stream)))
                     return rc;
                 break;
             }
-            if ((rc = gnnb_linear(segs, 2, p[0], 2 * fi, p[1], R(skip, fi), Rw(nxt, fo), M, fo, d.activation, stream)))
+            if ((rc = ws_linear(segs, 2, p[0], 2 * fi, p[1], R(skip, fi), Rw(nxt, fo), M, fo, d.activation, stream)))
                 return rc;
             break;
         }
         case GNNB_CONV_PNA: {
             // a narrow input (the first layer): the whole layer in one kernel, whole graphs staged in LDS (k_pna_first.hip)
             if (whole && fi <= 12 && skip == nullptr && !fpx && p.size() >= 8 && options().pna_fold_lin && ws->prep_delta == d.pna_delta) {
-                hipError_t he = launch_pna_first(ws->t, cur, fi, p[0], p[1], p[6], 13 * fi, p[7], nxt, fo, d.activation, (hipStream_t)stream);
-                if (he == hipSuccess)
+                const Attempt at = attempt(launch_pna_first(ws->t, cur, fi, p[0], p[1], p[6], 13 * fi, p[7], nxt, fo, d.activation, (hipStream_t)stream), "narrow PNA layer");
+                if (at == FAILED)
+                    return GNNB_ERR_HIP;
+                if (at == TOOK)
                     break;
-                if (he != hipErrorNotSupported)
-                    return fail(GNNB_ERR_HIP, "narrow PNA layer launch failed: %s", hipGetErrorString(he));
             }
             // h_ij = Wpre [x_i || x_j] + b  ==  (Wpre[:, :F] x_i + b) + Wpre[:, F:] x_j
             float *q = ws->tmp0, *pp = ws->tmp1;
@@ -1426,20 +967,19 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
             // batches take the general form below, decided here, before anything of the layer is enqueued)
             const bool classes = p.size() >= 10 && options().pna_fold_lin && options().pna_classes && whole && ws->deg_ready && M > 0 && !fpx &&
                                  ws->deg_delta == model->desc.pna_delta && fo > 32 && (uint64_t)M * 16 * fi + 512 <= 0xffffffffull;
-            if (!classes && (rc = linear1(R(cur, fi), fi, fi, p[0], 2 * fi, p[1], nullptr, Rw(q, fi), M, fi, GNNB_ACT_NONE, stream)))
+            if (!classes && (rc = ws_linear1(R(cur, fi), fi, fi, p[0], 2 * fi, p[1], nullptr, Rw(q, fi), M, fi, GNNB_ACT_NONE, stream)))
                 return rc;
             // the source half p = x . Wb^T and its aggregate: in one kernel, p on chip, where the degree-class form (no destination
             // term) and the max_graph_nodes promise (whole graphs in a stage) allow; else GEMM -> [N, F] -> aggregate
             bool pagg = false;
             if (classes) {
-                hipError_t he = launch_pna_pagg(ws->t, cur, fi, p[0] + fi, 2 * fi, ws->agg, (hipStream_t)stream);
-                if (he == hipSuccess)
-                    pagg = true;
-                else if (he != hipErrorNotSupported)
-                    return fail(GNNB_ERR_HIP, "PNA product + aggregate launch failed: %s", hipGetErrorString(he));
+                const Attempt at = attempt(launch_pna_pagg(ws->t, cur, fi, p[0] + fi, 2 * fi, ws->agg, (hipStream_t)stream), "PNA product + aggregate");
+                if (at == FAILED)
+                    return GNNB_ERR_HIP;
+                pagg = at == TOOK;
             }
             if (!pagg) {
-                if ((rc = linear1(R(cur, fi), fi, fi, p[0] + fi, 2 * fi, nullptr, nullptr, Rw(pp, fi), M, fi, GNNB_ACT_NONE, stream)))
+                if ((rc = ws_linear1(R(cur, fi), fi, fi, p[0] + fi, 2 * fi, nullptr, nullptr, Rw(pp, fi), M, fi, GNNB_ACT_NONE, stream)))
                     return rc;
                 if ((rc = aggregate(GNNB_AGG_PNA, pp, classes ? nullptr : q, ws->agg, fi, 0.f)))
                     return rc;
@@ -1475,37 +1015,29 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
                     GemmArgs g;
                     if ((rc = build_gemm(g, segs, 4, p[6], 13 * fi)))
                         return rc;
-                    PoolEpilogue pe;
-                    pe.node_graph = ws->t.node_graph;
-                    pe.graph_ptr = ws->t.graph_ptr;
-                    pe.pooled = ws->pooled;
-                    pe.part = ws->pool_part;
-                    pe.num_graphs = ws->t.num_graphs;
-                    pe.np = d.num_pools;
-                    for (int k = 0; k < 3; k++)
-                        pe.pools[k] = k < d.num_pools ? d.pools[k] : 0;
-                    hipError_t he = launch_linear(g, p[6], 13 * fi, p[7], nullptr, nxt, M, fo, d.activation, (hipStream_t)stream, &pe);
-                    if (he == hipSuccess) {
+                    const PoolEpilogue pe = pool_epilogue(ws, d);
+                    const Attempt at = attempt(launch_linear(g, p[6], 13 * fi, p[7], nullptr, nxt, M, fo, d.activation, (hipStream_t)stream, &pe), "pooling GEMM");
+                    if (at == FAILED)
+                        return GNNB_ERR_HIP;
+                    if (at == TOOK) {
                         GNNB_HIP_TRY(launch_pool_combine(pe, M, fo, (hipStream_t)stream));
                         *pooled_in_epilogue = true;
                         break;
                     }
-                    if (he != hipErrorNotSupported)
-                        return fail(GNNB_ERR_HIP, "pooling GEMM launch failed: %s", hipGetErrorString(he));
                 }
-                if ((rc = gnnb_linear(segs, 4, p[6], 13 * fi, p[7], skip_fold ? nullptr : R(skip, fo), Rw(nxt, fo), M, fo, d.activation, stream)))
+                if ((rc = ws_linear(segs, 4, p[6], 13 * fi, p[7], skip_fold ? nullptr : R(skip, fo), Rw(nxt, fo), M, fo, d.activation, stream)))
                     return rc;
                 break;
             }
             float *hid = ws->tmp0; // q is dead after the aggregate
-            if ((rc = gnnb_linear(segs, 4, p[2], 13 * fi, p[3], nullptr, Rw(hid, fo), M, fo, GNNB_ACT_NONE, stream)))
+            if ((rc = ws_linear(segs, 4, p[2], 13 * fi, p[3], nullptr, Rw(hid, fo), M, fo, GNNB_ACT_NONE, stream)))
                 return rc;
-            if ((rc = linear1(R(hid, fo), fo, fo, p[4], fo, p[5], R(skip, fo), Rw(nxt, fo), M, fo, d.activation, stream)))
+            if ((rc = ws_linear1(R(hid, fo), fo, fo, p[4], fo, p[5], R(skip, fo), Rw(nxt, fo), M, fo, d.activation, stream)))
                 return rc;
             break;
         }
         }
-        if ((rc = quant(Rw(nxt, fo), (size_t)M * fo)))
+        if ((rc = quantize(d, Rw(nxt, fo), (size_t)M * fo, stream)))
             return rc;
         cur = nxt;
         which ^= 1;
@@ -1515,8 +1047,6 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
     return GNNB_OK;
 }
 
-// The LDS-resident conv stack + pooling for this model on the prepared batch -> ws->pooled.  hipErrorNotSupported when
-// no stack kernel takes the model / batch (the caller runs layer by layer); *path says which kernel ran.
 // The large segment through the small-footprint per-layer kernel (k_conv_rows) + pooling, all on stream `s`; fills
 // ws->pooled rows [large_g, B).  hipErrorNotSupported (nothing launched) when a layer does not suit that kernel.
 static hipError_t large_segment_small(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, hipStream_t s)
@@ -1570,6 +1100,8 @@ static BatchTables small_segment(const gnnb_workspace *ws)
     return t;
 }
 
+// The LDS-resident conv stack + pooling for this model on the prepared batch -> ws->pooled.  hipErrorNotSupported when
+// no stack kernel takes the model / batch (the caller runs layer by layer); *path says which kernel ran.
 // head_out != nullptr: the stack kernel may run the MLP head on the graphs of `t` as well (k_gcn2_zf does when the head's
 // activation is the conv stack's and its shape suits: *head_fused); out rows [0, t.num_graphs) are then complete
 static hipError_t launch_conv_stack(const gnnb_model *model, gnnb_workspace *ws, const BatchTables &t, const float *x_dev,
@@ -1595,6 +1127,38 @@ static hipError_t launch_conv_stack(const gnnb_model *model, gnnb_workspace *ws,
                                d.num_pools, ws->pooled, s, deep);
     }
     return he;
+}
+
+// The readout of graphs [g0, B) from the pooled matrix in one launch (k_head_small / k_pool_mlp's pre-pooled form);
+// hipErrorNotSupported (nothing launched) when the head does not fit it
+static hipError_t launch_readout_pooled(const gnnb_model *model, gnnb_workspace *ws, int g0, float *out_dev, hipStream_t s)
+{
+    const gnnb_model_desc &d = model->desc;
+    const int gw = gnn_out_width(d);
+    return launch_pool_mlp(nullptr, ws->t.graph_ptr + g0, ws->t.num_graphs - g0, gw, d.pools, d.num_pools, model_head_args(model), d.mlp_activation,
+                           out_dev + (size_t)g0 * d.mlp_out, s, ws->pooled + (size_t)g0 * d.num_pools * gw);
+}
+
+// ... and as a plain GEMM chain (a head too large for the readout kernels; the fixed-point emulation, each layer's output put
+// on the grid).  Through the stand-alone GEMM entry: the head's GEMMs never use the workspace's stream-K scratch.
+static int run_head_chain(const gnnb_model *model, gnnb_workspace *ws, int g0, float *out_dev, void *stream)
+{
+    const gnnb_model_desc &d = model->desc;
+    const int M = ws->t.num_graphs - g0;
+    const float *h = ws->pooled + (size_t)g0 * d.num_pools * gnn_out_width(d);
+    for (int i = 0; i < d.mlp_num_linear; i++) {
+        int din, dout, rc;
+        mlp_dims(d, i, &din, &dout);
+        const bool last = (i == d.mlp_num_linear - 1);
+        float *y = last ? out_dev + (size_t)g0 * d.mlp_out : ws->mlp[i & 1];
+        if ((rc = linear1(h, din, din, model->head_w[i], din, model->head_b[i], nullptr, y, M, dout,
+                          last ? GNNB_ACT_NONE : d.mlp_activation, stream)))
+            return rc;
+        if ((rc = quantize(d, y, (size_t)M * dout, stream)))
+            return rc;
+        h = y;
+    }
+    return GNNB_OK;
 }
 
 static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, float *out_dev,
@@ -1654,12 +1218,6 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;
     int rc;
     const bool fpx = d.fpx_w > 0;
-    auto quant = [&](float *buf, size_t n) -> int { // (fixed-point emulation only: put a finished tensor on the grid)
-        if (!fpx)
-            return GNNB_OK;
-        GNNB_HIP_TRY(launch_quantize(buf, buf, n, d.fpx_w, d.fpx_i, (hipStream_t)stream));
-        return GNNB_OK;
-    };
     if (fpx) { // the input features enter as F_TYPE values: a quantised copy (the caller's buffer is not written)
         GNNB_HIP_TRY(launch_quantize(x_dev, ws->act[1], (size_t)N * d.in_dim, d.fpx_w, d.fpx_i, (hipStream_t)stream));
         x_dev = ws->act[1]; // (the layer loop never writes the buffer it reads)
@@ -1713,34 +1271,18 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
                                                 ws->pooled + (size_t)ws->large_g * d.num_pools * gwl, (hipStream_t)stream));
                 ws->last_path |= GNNB_PATH_LARGE_LAYERWISE;
             }
-            const HeadArgs head = model_head_args(model);
             // (the stack kernel ran the head on its own graphs: what is left are the graphs of the large segment, if any)
             const int hg0 = head_fused ? (seg ? ws->large_g : B) : 0;
             if (hg0 >= B)
                 return GNNB_OK;
-            const size_t pw = (size_t)d.num_pools * d.out_dim;
-            he = launch_pool_mlp(nullptr, ws->t.graph_ptr + hg0, B - hg0, d.out_dim, d.pools, d.num_pools, head, d.mlp_activation,
-                                 out_dev + (size_t)hg0 * d.mlp_out, (hipStream_t)stream, ws->pooled + (size_t)hg0 * pw);
-            if (he == hipSuccess)
-                return GNNB_OK;
-            if (he != hipErrorNotSupported)
-                return fail(GNNB_ERR_HIP, "readout launch failed: %s", hipGetErrorString(he));
-            // head too large for the fused readout: plain GEMM chain on the pooled matrix
-            const float *h = ws->pooled + (size_t)hg0 * pw;
-            for (int i = 0; i < d.mlp_num_linear; i++) {
-                int din, dout;
-                mlp_dims(d, i, &din, &dout);
-                const bool last = (i == d.mlp_num_linear - 1);
-                float *y = last ? out_dev + (size_t)hg0 * d.mlp_out : ws->mlp[i & 1];
-                if ((rc = linear1(h, din, din, model->head_w[i], din, model->head_b[i], nullptr, y, B - hg0, dout,
-                                  last ? GNNB_ACT_NONE : d.mlp_activation, stream)))
-                    return rc;
-                h = y;
-            }
-            return GNNB_OK;
+            const Attempt at = attempt(launch_readout_pooled(model, ws, hg0, out_dev, (hipStream_t)stream), "readout");
+            if (at != DECLINED)
+                return at == TOOK ? GNNB_OK : GNNB_ERR_HIP;
+            // head too large for the fused readout: plain GEMM chain on the pooled matrix (no fixed-point emulation on this route)
+            return run_head_chain(model, ws, hg0, out_dev, stream);
         }
-        if (he != hipErrorNotSupported)
-            return fail(GNNB_ERR_HIP, "fused GCN stack launch failed: %s", hipGetErrorString(he));
+        if (attempt(he, "fused GCN stack") == FAILED)
+            return GNNB_ERR_HIP;
     }
 
     ws->last_path = GNNB_PATH_LAYERWISE;
@@ -1750,92 +1292,45 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
         return rc;
 
     const int gw = gnn_out_width(d);
-    if (pooled_done) {
+    const bool head_fits = d.mlp_num_linear <= 8; // (what a HeadArgs holds)
+    if (pooled_done && head_fits) {
         // (the last layer's GEMM pooled in its epilogue: ws->pooled is complete, the readout takes it as the stack path does)
-        HeadArgs head;
-        memset(&head, 0, sizeof(head));
-        head.nlin = d.mlp_num_linear;
-        if (head.nlin <= 8) {
-            for (int i = 0; i < head.nlin; i++) {
-                int din, dout;
-                mlp_dims(d, i, &din, &dout);
-                head.w[i] = model->head_w[i];
-                head.b[i] = model->head_b[i];
-                head.dims[i] = din;
-                head.dims[i + 1] = dout;
-            }
-            hipError_t he = launch_pool_mlp(nullptr, ws->t.graph_ptr, B, gw, d.pools, d.num_pools, head, d.mlp_activation, out_dev,
-                                            (hipStream_t)stream, ws->pooled);
-            if (he == hipSuccess)
-                return GNNB_OK;
-            if (he != hipErrorNotSupported)
-                return fail(GNNB_ERR_HIP, "readout launch failed: %s", hipGetErrorString(he));
-        }
-    } else if (!fpx) {
+        const Attempt at = attempt(launch_readout_pooled(model, ws, 0, out_dev, (hipStream_t)stream), "readout");
+        if (at != DECLINED)
+            return at == TOOK ? GNNB_OK : GNNB_ERR_HIP;
+    } else if (!pooled_done && !fpx && head_fits) {
         // fused readout (pooling + whole MLP head, one launch) when the head fits LDS
-        HeadArgs head;
-        memset(&head, 0, sizeof(head));
-        head.nlin = d.mlp_num_linear;
-        if (head.nlin <= 8) {
-            for (int i = 0; i < head.nlin; i++) {
-                int din, dout;
-                mlp_dims(d, i, &din, &dout);
-                head.w[i] = model->head_w[i];
-                head.b[i] = model->head_b[i];
-                head.dims[i] = din;
-                head.dims[i + 1] = dout;
-            }
-            hipError_t he = hipErrorNotSupported;
-            if (options().head_split) {
-                // pooling pass (HBM-bound, every CU) + the small readout on the pooled matrix: neither needs the
-                // 119 KB of LDS of the one-launch form, so both share CUs with other batches' kernels
-                if ((rc = gnnb_global_pool(ws, cur, gw, d.pools, d.num_pools, ws->pooled, stream)))
-                    return rc;
-                he = launch_pool_mlp(nullptr, ws->t.graph_ptr, B, gw, d.pools, d.num_pools, head, d.mlp_activation, out_dev,
-                                     (hipStream_t)stream, ws->pooled);
-            } else {
-                he = launch_pool_mlp(cur, ws->t.graph_ptr, B, gw, d.pools, d.num_pools, head, d.mlp_activation, out_dev,
-                                     (hipStream_t)stream);
-            }
-            if (he == hipSuccess)
-                return GNNB_OK;
-            if (he != hipErrorNotSupported)
-                return fail(GNNB_ERR_HIP, "fused readout launch failed: %s", hipGetErrorString(he));
-            // The head's weights do not fit LDS (SAGE d = 256 with three pools: 768 x 64 floats): pooling pass, then
-            // the small readout that takes its weights from L2 as MFMA operands -- one launch over B / 16 workgroups
-            // instead of a chain of GEMMs with M = B rows (64 workgroups of the 128-row tile at B = 8192: 51 us)
-            if (!options().head_split && options().head_small) {
-                if ((rc = gnnb_global_pool(ws, cur, gw, d.pools, d.num_pools, ws->pooled, stream)))
-                    return rc;
-                he = launch_pool_mlp(nullptr, ws->t.graph_ptr, B, gw, d.pools, d.num_pools, head, d.mlp_activation, out_dev,
-                                     (hipStream_t)stream, ws->pooled);
-                if (he == hipSuccess)
-                    return GNNB_OK;
-                if (he != hipErrorNotSupported)
-                    return fail(GNNB_ERR_HIP, "readout launch failed: %s", hipGetErrorString(he));
-                pooled_done = true;
-            }
+        hipError_t he = hipErrorNotSupported;
+        if (options().head_split) {
+            // pooling pass (HBM-bound, every CU) + the small readout on the pooled matrix: neither needs the
+            // 119 KB of LDS of the one-launch form, so both share CUs with other batches' kernels
+            if ((rc = gnnb_global_pool(ws, cur, gw, d.pools, d.num_pools, ws->pooled, stream)))
+                return rc;
+            he = launch_readout_pooled(model, ws, 0, out_dev, (hipStream_t)stream);
+        } else {
+            he = launch_pool_mlp(cur, ws->t.graph_ptr, B, gw, d.pools, d.num_pools, model_head_args(model), d.mlp_activation, out_dev,
+                                 (hipStream_t)stream);
+        }
+        Attempt at = attempt(he, "fused readout");
+        if (at != DECLINED)
+            return at == TOOK ? GNNB_OK : GNNB_ERR_HIP;
+        // The head's weights do not fit LDS (SAGE d = 256 with three pools: 768 x 64 floats): pooling pass, then
+        // the small readout that takes its weights from L2 as MFMA operands -- one launch over B / 16 workgroups
+        // instead of a chain of GEMMs with M = B rows (64 workgroups of the 128-row tile at B = 8192: 51 us)
+        if (!options().head_split && options().head_small) {
+            if ((rc = gnnb_global_pool(ws, cur, gw, d.pools, d.num_pools, ws->pooled, stream)))
+                return rc;
+            at = attempt(launch_readout_pooled(model, ws, 0, out_dev, (hipStream_t)stream), "readout");
+            if (at != DECLINED)
+                return at == TOOK ? GNNB_OK : GNNB_ERR_HIP;
+            pooled_done = true;
         }
     }
     if (!pooled_done && (rc = gnnb_global_pool(ws, cur, gw, d.pools, d.num_pools, ws->pooled, stream)))
         return rc;
-    if ((rc = quant(ws->pooled, (size_t)B * d.num_pools * gw)))
+    if ((rc = quantize(d, ws->pooled, (size_t)B * d.num_pools * gw, stream)))
         return rc;
-
-    const float *h = ws->pooled;
-    for (int i = 0; i < d.mlp_num_linear; i++) {
-        int din, dout;
-        mlp_dims(d, i, &din, &dout);
-        const bool last = (i == d.mlp_num_linear - 1);
-        float *y = last ? out_dev : ws->mlp[i & 1];
-        if ((rc = linear1(h, din, din, model->head_w[i], din, model->head_b[i], nullptr, y, B, dout,
-                          last ? GNNB_ACT_NONE : d.mlp_activation, stream)))
-            return rc;
-        if ((rc = quant(y, (size_t)B * dout)))
-            return rc;
-        h = y;
-    }
-    return GNNB_OK;
+    return run_head_chain(model, ws, 0, out_dev, stream);
 }
 
 int gnnb_forward_batched(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev,
@@ -1940,34 +1435,53 @@ int gnnb_forward_batched_host(const gnnb_model *model, gnnb_workspace *ws, const
 }
 
 // ---------------------------------------------------------------------------------------
+} // extern "C"
+
+// The event-timed loop behind the *_timed entries: `warmup` launches, then `iters` launches between two events on `s`;
+// launch(i) -> GNNB_OK or an error (which ends the loop and is returned).  *out_us = microseconds per launch.
+template <typename F> static int timed_loop(hipStream_t s, int warmup, int iters, F launch, float *out_us)
+{
+    struct Events { // (destroyed on every return path)
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events()
+        {
+            if (e0)
+                (void)hipEventDestroy(e0);
+            if (e1)
+                (void)hipEventDestroy(e1);
+        }
+    } ev;
+    GNNB_HIP_TRY(hipEventCreate(&ev.e0));
+    GNNB_HIP_TRY(hipEventCreate(&ev.e1));
+    int rc = GNNB_OK;
+    for (int i = 0; i < warmup && rc == GNNB_OK; i++)
+        rc = launch(i);
+    if (rc != GNNB_OK)
+        return rc;
+    GNNB_HIP_TRY(hipStreamSynchronize(s));
+    GNNB_HIP_TRY(hipEventRecord(ev.e0, s));
+    for (int i = 0; i < iters && rc == GNNB_OK; i++)
+        rc = launch(i);
+    GNNB_HIP_TRY(hipEventRecord(ev.e1, s));
+    GNNB_HIP_TRY(hipEventSynchronize(ev.e1));
+    float ms = 0.f;
+    GNNB_HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *out_us = ms * 1000.0f / (float)iters;
+    return rc;
+}
+
+extern "C" {
+
 int gnnb_aggregate_timed(gnnb_workspace *ws, int agg_kind, const float *const *x_dev_list,
                          const float *self_dev, float *const *out_dev_list, int nbuf, int width,
                          float eps, int iters, void *stream, float *out_us_per_launch)
 {
     if (!x_dev_list || !out_dev_list || nbuf < 1 || iters < 1 || !out_us_per_launch)
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_timed");
-    hipStream_t s = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    GNNB_HIP_TRY(hipEventCreate(&e0));
-    GNNB_HIP_TRY(hipEventCreate(&e1));
-    int rc = GNNB_OK;
-    for (int i = 0; i < nbuf && rc == GNNB_OK; i++) // warm-up, also touches every buffer
-        rc = gnnb_aggregate(ws, agg_kind, x_dev_list[i], self_dev, out_dev_list[i], width, eps, stream);
-    if (rc == GNNB_OK) {
-        GNNB_HIP_TRY(hipStreamSynchronize(s));
-        GNNB_HIP_TRY(hipEventRecord(e0, s));
-        for (int i = 0; i < iters && rc == GNNB_OK; i++)
-            rc = gnnb_aggregate(ws, agg_kind, x_dev_list[i % nbuf], self_dev, out_dev_list[i % nbuf], width,
-                                eps, stream);
-        GNNB_HIP_TRY(hipEventRecord(e1, s));
-        GNNB_HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        GNNB_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        *out_us_per_launch = ms * 1000.0f / (float)iters;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
+    // (the warm-up also touches every buffer)
+    return timed_loop((hipStream_t)stream, nbuf, iters, [&](int i) {
+        return gnnb_aggregate(ws, agg_kind, x_dev_list[i % nbuf], self_dev, out_dev_list[i % nbuf], width, eps, stream);
+    }, out_us_per_launch);
 }
 
 int gnnb_gcn_stack_timed(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, int iters,
@@ -1981,35 +1495,15 @@ int gnnb_gcn_stack_timed(const gnnb_model *model, gnnb_workspace *ws, const floa
     const G2Deep deep = gcn_stack_middle_layers(model);
     if (deep.nl < 2)
         return fail(GNNB_ERR_INVALID, "the fused stack exists for GCN / GIN models of two or more layers");
-    hipStream_t s = (hipStream_t)stream;
     // (as the forward launches it: with the MLP head inside where k_gcn2_zf takes it; its output goes to a workspace buffer)
     bool head_fused = false;
-    auto launch = [&]() { return launch_conv_stack(model, ws, small_segment(ws), x_dev, deep, s, &ws->last_path, ws->mlp[0], &head_fused); };
-    hipEvent_t e0, e1;
-    GNNB_HIP_TRY(hipEventCreate(&e0));
-    GNNB_HIP_TRY(hipEventCreate(&e1));
-    int rc = GNNB_OK;
-    hipError_t he = hipSuccess;
-    for (int i = 0; i < 3 && he == hipSuccess; i++)
-        he = launch();
-    if (he == hipErrorNotSupported)
-        rc = fail(GNNB_ERR_INVALID, "fused stack not eligible (shape, or no max_graph_nodes promise)");
-    else if (he != hipSuccess)
-        rc = fail(GNNB_ERR_HIP, "fused GCN stack launch failed: %s", hipGetErrorString(he));
-    if (rc == GNNB_OK) {
-        GNNB_HIP_TRY(hipStreamSynchronize(s));
-        GNNB_HIP_TRY(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; i++)
-            (void)launch();
-        GNNB_HIP_TRY(hipEventRecord(e1, s));
-        GNNB_HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        GNNB_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        *out_us_per_launch = ms * 1000.0f / (float)iters;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
+    return timed_loop((hipStream_t)stream, 3, iters, [&](int) {
+        const Attempt at = attempt(launch_conv_stack(model, ws, small_segment(ws), x_dev, deep, (hipStream_t)stream, &ws->last_path, ws->mlp[0], &head_fused),
+                                   "fused GCN stack");
+        if (at == DECLINED)
+            return fail(GNNB_ERR_INVALID, "fused stack not eligible (shape, or no max_graph_nodes promise)");
+        return at == TOOK ? (int)GNNB_OK : (int)GNNB_ERR_HIP;
+    }, out_us_per_launch);
 }
 
 int gnnb_linear_timed(const float *a_dev, int lda, int k, const float *w_dev, int ldw,
@@ -2018,28 +1512,8 @@ int gnnb_linear_timed(const float *a_dev, int lda, int k, const float *w_dev, in
 {
     if (iters < 1 || !out_us_per_launch)
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_linear_timed");
-    hipStream_t s = (hipStream_t)stream;
-    gnnb_gemm_seg seg = {a_dev, nullptr, lda, k};
-    hipEvent_t e0, e1;
-    GNNB_HIP_TRY(hipEventCreate(&e0));
-    GNNB_HIP_TRY(hipEventCreate(&e1));
-    int rc = GNNB_OK;
-    for (int i = 0; i < 3 && rc == GNNB_OK; i++)
-        rc = gnnb_linear(&seg, 1, w_dev, ldw, bias_dev, nullptr, y_dev, M, N, act, stream);
-    if (rc == GNNB_OK) {
-        GNNB_HIP_TRY(hipStreamSynchronize(s));
-        GNNB_HIP_TRY(hipEventRecord(e0, s));
-        for (int i = 0; i < iters && rc == GNNB_OK; i++)
-            rc = gnnb_linear(&seg, 1, w_dev, ldw, bias_dev, nullptr, y_dev, M, N, act, stream);
-        GNNB_HIP_TRY(hipEventRecord(e1, s));
-        GNNB_HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        GNNB_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        *out_us_per_launch = ms * 1000.0f / (float)iters;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
+    return timed_loop((hipStream_t)stream, 3, iters, [&](int) { return linear1(a_dev, lda, k, w_dev, ldw, bias_dev, nullptr, y_dev, M, N, act, stream); },
+                      out_us_per_launch);
 }
 
 // ---------------------------------------------------------------------------------------

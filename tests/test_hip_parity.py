@@ -1536,6 +1536,43 @@ def test_fused_gcn_stack_of_more_than_two_layers(dev, layers, hidden, out_dim, a
             runtime.set_option("fuse_gcn2", 1)
 
 
+_ENV_OPTION_CHILD = '''
+import sys
+sys.path[:0] = [%(root)r, %(tests)r]
+import numpy as np
+import torch
+from gnnbuilder_amd import runtime, synthetic
+from helpers import make_model, to_dev
+model = make_model("gcn", hidden=64, layers=2, task_out=5)
+batch = synthetic.make_batch("qm9", 64, seed=3)
+cm = runtime.CompiledModel.from_model(model, batch.num_graphs, batch.num_nodes, batch.num_edges,
+                                      max_graph_nodes=int(np.diff(batch.node_ptr).max()))
+out = cm.forward(*to_dev(batch, torch.device("cuda:0")))
+cm.check()
+torch.cuda.synchronize()
+assert np.isfinite(out.cpu().numpy()).all()
+print("last_path=" + cm.last_path())
+'''
+
+
+@pytest.mark.parametrize("env,path", [({"GNNB_FUSE_GCN2": "0"}, "layerwise"), ({"GNNB_FUSE_ZF": "0"}, "stack"), ({}, "stack_zf")])
+def test_environment_sets_an_options_default(dev, env, path):
+    """An option's default is its environment variable GNNB_<NAME> where that is set: a 2-layer GCN with a promise takes
+    k_gcn2_zf, k_gcn2_fused with GNNB_FUSE_ZF=0 and the layer-wise kernels with GNNB_FUSE_GCN2=0.  The options are read once
+    per process, so each case runs in a fresh child process of its own."""
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    child_env = {k: v for k, v in os.environ.items() if k not in ("GNNB_FUSE_GCN2", "GNNB_FUSE_ZF")}
+    child_env.update(env)
+    run = subprocess.run([sys.executable, "-c", _ENV_OPTION_CHILD % {"root": str(root), "tests": str(root / "tests")}],
+                         capture_output=True, text=True, env=child_env, timeout=600)
+    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-4000:])
+    assert f"last_path={path}" in run.stdout.splitlines(), run.stdout[-2000:]
+
+
 @pytest.mark.parametrize("layers,hidden,act,skip,shape,eps", [
     (2, 128, "relu", True, "qm9", 0.0), (3, 128, "relu", True, "qm9", 0.2), (3, 64, "tanh", False, "esol", 0.0),
     (4, 32, "gelu", True, "qm9", -0.3), (5, 128, "sigmoid", True, "esol", 0.1)])
