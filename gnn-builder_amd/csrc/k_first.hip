@@ -25,16 +25,7 @@ namespace gnnb {
 // Graphs larger than a stage (no max_graph_nodes promise on this path) are taken in pieces whose sources are read from
 // global memory (L2) instead of LDS -- same arithmetic, same order.
 // Sums run in CSR order with the self term last, as k_aggregate_ring and the reference do.
-#ifndef F1_CAP_ROWS
-#define F1_CAP_ROWS 128
-#endif
-#ifndef F1_ABLATE   // development: 1 no stores, 2 no MFMA, 4 no P0, 8 no DMA (timing only: WRONG results)
-#define F1_ABLATE 0
-#endif
-#ifndef F1_NT_STORE
-#define F1_NT_STORE 1
-#endif
-static constexpr int F1_NW = 8, F1_WG = F1_NW * 64, F1_CAP = F1_CAP_ROWS, F1_ECAP = 8 * F1_CAP_ROWS; // rows / CSR entries per stage
+static constexpr int F1_NW = 8, F1_WG = F1_NW * 64, F1_CAP = 128, F1_ECAP = 8 * F1_CAP; // rows / CSR entries per stage
 
 struct F1Stage {
     int ok, nb, rows, e0, ne, direct, next_t, next_row; // direct: the piece's sources are read from global memory
@@ -114,7 +105,7 @@ __global__ __launch_bounds__(F1_WG, 2) void k_conv_first(
     };
     int vm = 0; // vector-memory instructions this wave has issued (DMA + stores): counted waits (VM operations retire in order)
     auto issue = [&](const F1Stage &st, int bb) {
-        if (!st.ok || st.direct || st.rows <= 0 || (F1_ABLATE & 8))
+        if (!st.ok || st.direct || st.rows <= 0)
             return;
         char *base = smem + (size_t)bb * in_b;
         const int nx = st.rows * F;
@@ -289,8 +280,7 @@ __global__ __launch_bounds__(F1_WG, 2) void k_conv_first(
                 }
             }
         };
-        if (F1_ABLATE & 4) {
-        } else if (cur.direct)
+        if (cur.direct)
             p0(IntTag<1>{});
         else
             p0(IntTag<0>{});
@@ -321,7 +311,7 @@ __global__ __launch_bounds__(F1_WG, 2) void k_conv_first(
                 for (int q = 0; q < KQ; q++)
 #pragma unroll
                     for (int t = 0; t < 4; t++) {
-                        if (q * 4 + t >= nsteps || (F1_ABLATE & 2)) // (wave-uniform: this k step holds no feature)
+                        if (q * 4 + t >= nsteps) // (wave-uniform: this k step holds no feature)
                             break;
                         const float av = t == 0 ? a4[q].x : (t == 1 ? a4[q].y : (t == 2 ? a4[q].z : a4[q].w));
                         acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[0][q * 4 + t], av, acc[0], 0, 0, 0);
@@ -344,14 +334,10 @@ __global__ __launch_bounds__(F1_WG, 2) void k_conv_first(
                     for (int ps = 0; ps < 2; ps++) {
                         const int rr = ps * 8 + (lane >> 3), cc = (lane & 7) * 4;
                         const float4 v = *reinterpret_cast<const float4 *>(ST + rr * 36 + cc);
-                        if (u * 16 + rr < rows && !(F1_ABLATE & 1)) {
+                        if (u * 16 + rr < rows) {
                             float *yp = Y + (size_t)(nb + u * 16 + rr) * Nout + cw * 32 + cc;
-#if F1_NT_STORE
                             agg_f32x4 tv = {v.x, v.y, v.z, v.w};
                             __builtin_nontemporal_store(tv, reinterpret_cast<agg_f32x4 *>(yp));
-#else
-                            *reinterpret_cast<float4 *>(yp) = v;
-#endif
                         }
                     }
                     continue;
@@ -364,14 +350,10 @@ __global__ __launch_bounds__(F1_WG, 2) void k_conv_first(
                     const int c0 = (cw * SPW + j) * 16 + 4 * lg;
                     float4 v = make_float4(act_t<ACT>(acc[j][0]), act_t<ACT>(acc[j][1]), act_t<ACT>(acc[j][2]), act_t<ACT>(acc[j][3]));
                     float *yp = Y + (size_t)(nb + row) * Nout + c0;
-                    if (row < rows && c0 < Nout && !(F1_ABLATE & 1)) {
+                    if (row < rows && c0 < Nout) {
                         if (vec_out && c0 + 3 < Nout) {
-#if F1_NT_STORE
                             agg_f32x4 tv = {v.x, v.y, v.z, v.w};
                             __builtin_nontemporal_store(tv, reinterpret_cast<agg_f32x4 *>(yp));
-#else
-                            *reinterpret_cast<float4 *>(yp) = v;
-#endif
                         } else {
                             yp[0] = v.x;
                             if (c0 + 1 < Nout) yp[1] = v.y;

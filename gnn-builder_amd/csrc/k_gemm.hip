@@ -213,10 +213,7 @@ static constexpr int DM = 128, DN = 128, DWG = 256, DNBUF = 2, DNW = DWG / 64, D
 // {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} of the 32-row fragment -- puts rows r and r + 8 (mod 16) of one parity on the same slot:
 // every fragment read a two-way conflict.  Rows are 128 B: the row's parity selects the half of the 256-B bank window, so the key
 // must separate the EIGHT rows of one parity inside a group: key = (row >> 1) & 7 does (even rows of the first group: 0 1 6 7 2 3 4 5).
-#ifndef DMA_KEY_SHIFT
-#define DMA_KEY_SHIFT 1
-#endif
-__device__ __forceinline__ int dkey(int r) { return (r >> DMA_KEY_SHIFT) & 7; }
+__device__ __forceinline__ int dkey(int r) { return (r >> 1) & 7; }
 static constexpr int DBUF_B = (DM + DN) * BK * 4; // 32 KB: A chunk | W chunk
 // MATH 1 (opt-in, gnnb_set_option("math", 1)): the same chunks, but each 16-wide k block is multiplied as six
 // v_mfma_f32_32x32x16_bf16 products of an exact 3-way bf16 split of BOTH operands (see split3), the fragments split in
@@ -247,7 +244,7 @@ __global__ __launch_bounds__(DWG) void k_linear_dma(GemmArgs g, const float *__r
     const uint32_t smem_a = (uint32_t)(uintptr_t)(lds_vptr)smem;
     // DMA lane geometry: an instruction covers 8 rows x eight 16-B pieces; LDS slot p of row r holds piece p ^ dkey(r)
     const int drow = lane >> 3;
-    // (the key of local row r0 + drow, r0 a multiple of 8: with DMA_KEY_SHIFT 1 it carries bit 3 of r0 -- two lane constants)
+    // (the key of local row r0 + drow, r0 a multiple of 8: with the key's shift of 1 it carries bit 3 of r0 -- two lane constants)
     const uint32_t dpiece_b0 = (uint32_t)(((lane & 7) ^ dkey(drow)) << 4), dpiece_b1 = (uint32_t)(((lane & 7) ^ dkey(8 + drow)) << 4);
 
     // PERSISTENT over work items (grid = what is resident: two workgroups per CU); the chunk pipeline runs straight
@@ -902,22 +899,7 @@ __global__ __launch_bounds__(DWG) void k_linear_dma(GemmArgs g, const float *__r
 // ds_read_b128 fragment reads conflict-free:  slot = chunk ^ (row & (P-1)).
 // Lane (i = l&15, g = l>>4) reads chunk 4q+g of row i: k = 16q+4g .. +3; MFMA step (q,s) contracts
 // k in {16q + 4g + s : g = 0..3}, the same k-permutation on A and W.
-#ifndef GNNB_LR_SR
-#define GNNB_LR_SR 2
-#endif
-// a full stage's vector epilogue issues 2*SR 16-B stores per wave
-#define GNNB_STR2(x) #x
-#define GNNB_STR(x) GNNB_STR2(x)
-#if GNNB_LR_SR == 1
-#define GNNB_LR_NSTORES 2
-#elif GNNB_LR_SR == 2
-#define GNNB_LR_NSTORES 4
-#elif GNNB_LR_SR == 3
-#define GNNB_LR_NSTORES 6
-#else
-#define GNNB_LR_NSTORES 8
-#endif
-#define GNNB_LR_COUNTED_WAIT "s_waitcnt vmcnt(" GNNB_STR(GNNB_LR_NSTORES) ") lgkmcnt(0)\n\ts_barrier"
+static constexpr int LR_SR = 2; // 16-row units per stage
 
 
 // Optional fused gather: when `rec` is set the A stage is not copied from memory but PRODUCED -- the
@@ -943,7 +925,7 @@ __global__ __launch_bounds__(WG, MATH ? 2 : 3) void k_linear_reg(
     const float *__restrict__ bias, const float *__restrict__ skip, float *__restrict__ Y, int M, int N,
     int act, int rg_log2, int P, int vec_out, GatherDesc gd)
 {
-    constexpr int SR = GNNB_LR_SR; // 16-row units per stage
+    constexpr int SR = LR_SR;
     constexpr int EPI_LD = 36; // padded row of the epilogue transpose scratch
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1132,8 +1114,10 @@ __global__ __launch_bounds__(WG, MATH ? 2 : 3) void k_linear_reg(
         issue(0, 0);
     int b = 0;
     for (int j = 0; j < nstages; j++, b ^= 1) {
-        if (prev_counted)
-            asm volatile(GNNB_LR_COUNTED_WAIT ::: "memory");
+        if (prev_counted) {
+            static_assert(2 * SR == 4, "a full stage's vector epilogue issues 2 * SR 16-B stores per wave: the counted wait names that number");
+            asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        }
         else
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if (j + 1 < nstages) {
@@ -1311,10 +1295,10 @@ static hipError_t launch_linear_reg_t(const float *A, int lda, int K, const floa
     // waves: N <= 32 -> 4 row groups x 1 column slice; N <= 64 -> 2 x 2; else 1 x 4 (128 cols / WG)
     const int rg_log2 = N <= 32 ? 2 : (N <= 64 ? 1 : 0);
     const int cols_per_wg = 128 >> rg_log2;
-    const int stage_rows = (16 * GNNB_LR_SR) << rg_log2;
+    const int stage_rows = (16 * LR_SR) << rg_log2;
     const int gy = (N + cols_per_wg - 1) / cols_per_wg;
     const size_t buf = (((size_t)stage_rows * K * 4) + 15) & ~(size_t)15;
-    const size_t lds = 2 * buf + 4 * 16 * GNNB_LR_SR * 36 * 4; // two stage buffers + per-wave epilogue scratch
+    const size_t lds = 2 * buf + 4 * 16 * LR_SR * 36 * 4; // two stage buffers + per-wave epilogue scratch
     const int vec_out = (N % 4 == 0) && (((uintptr_t)Y & 15) == 0) && (bias == nullptr || ((uintptr_t)bias & 15) == 0) &&
                         (skip == nullptr || ((uintptr_t)skip & 15) == 0);
     int P = 1;

@@ -394,13 +394,11 @@ static constexpr int HS_THREADS = 256;
 // REGISTER BUDGET (round 6): 72 (a launch bound of seven waves per SIMD; 67 used).  Beside k_gcn2_zf's four 96-register waves a
 // SIMD has 128 registers left: this kernel's wave and a graph-prep wave (56) of the stream's next batch then run side by side
 // instead of one after the other -- BASELINE config 2, three batches in flight: 40.4-41.6 -> 37.6-37.7 us per step.
-#ifndef GNNB_HS_WAVES
-#define GNNB_HS_WAVES 7
-#endif
+static constexpr int HS_WAVES = 7; // waves per SIMD of the plain, paired-operand form (the register budget above)
 // PAIRS = false (option head_pairs = 0): four operand slices in flight, 82 registers -- the faster form when NOTHING shares the chip (one
 // stream of forwards: 49.8 vs 51.9 us per forward at BASELINE config 2), the slower one in the pipeline.
 template <int ACT, bool GUEST, bool PAIRS = true>
-__global__ __launch_bounds__(HS_THREADS, (GUEST || !PAIRS) ? 5 : GNNB_HS_WAVES) /* (the guest form carries the prep's code) */ void k_head_small(PrepParams guest_kernarg, int prep_blocks, const float *__restrict__ pooled, int B,
+__global__ __launch_bounds__(HS_THREADS, (GUEST || !PAIRS) ? 5 : HS_WAVES) /* (the guest form carries the prep's code) */ void k_head_small(PrepParams guest_kernarg, int prep_blocks, const float *__restrict__ pooled, int B,
                                                              HeadArgs head, float *__restrict__ out, int ldact)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -126,9 +126,6 @@ __device__ __forceinline__ void g2_h3_store(char *buf, int rowb, int midoff, int
     *reinterpret_cast<_Float16 *>(p) = h;
     *reinterpret_cast<_Float16 *>(p + midoff) = m;
 }
-#ifndef GNNB_H3_PROBE // (development: 0 = no probe, 1 / 2 / 3 / 4 / 5 = forms measured against the register budget, see below)
-#define GNNB_H3_PROBE 6
-#endif
 template <int ACT, int KQ32, int NU>
 __device__ __forceinline__ void g2_mma_h3(const char *__restrict__ planes, int rowb, int midoff, const float (&wr)[KQ32 * 8], float bias,
                                           int rg, int nrg, int li, int lg, float (&v)[NU][4], int *sflag, int rows)
@@ -179,61 +176,6 @@ __device__ __forceinline__ void g2_mma_h3(const char *__restrict__ planes, int r
     // in the rows the stage holds; rows past its end are stale LDS.  Seen -> one LDS word, which the kernel's last instructions turn
     // into the workspace's flag: nothing of the probe lives in a register outside this epilogue -- carried through the stage as a
     // scalar mask beside the flag word's address it spilled SGPRs into vector lanes in the variants that sit at 128 registers)
-#if GNNB_H3_PROBE == 0
-#pragma unroll
-    for (int k = 0; k < NU; k++)
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            v[k][r] = act_t<ACT>((NU == 1 ? acc[0][r] + acc[1][r] : acc[k][r]) + bias);
-#elif GNNB_H3_PROBE == 1
-    RangeProbe rp;
-#pragma unroll
-    for (int k = 0; k < NU; k++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const float pre = (NU == 1 ? acc[0][r] + acc[1][r] : acc[k][r]) + bias;
-            rp.see(pre, (rg + k * nrg) * 16 + lg * 4 + r < rows);
-            v[k][r] = act_t<ACT>(pre);
-        }
-    if (rp.any() && li + lg == 0)
-        *sflag = 1;
-#elif GNNB_H3_PROBE == 2
-    // one probe value per lane: t stays 0 while every accumulator of the stage's rows is finite (inf * 0 and nan * 0 are nan)
-    float t = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NU; k++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const float pre = (NU == 1 ? acc[0][r] + acc[1][r] : acc[k][r]) + bias;
-            t = __builtin_fmaf((rg + k * nrg) * 16 + lg * 4 + r < rows ? pre : 0.0f, 0.0f, t);
-            v[k][r] = act_t<ACT>(pre);
-        }
-    if (t != t)
-        *sflag = 1;
-#elif GNNB_H3_PROBE == 4 // experiment: no row mask
-    float t = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NU; k++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const float pre = (NU == 1 ? acc[0][r] + acc[1][r] : acc[k][r]) + bias;
-            t = __builtin_fmaf(pre, 0.0f, t);
-            v[k][r] = act_t<ACT>(pre);
-        }
-    if (t != t)
-        *sflag = 1;
-#elif GNNB_H3_PROBE == 5 // experiment: no row mask, probe folded into v (no branch)
-    float t = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NU; k++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const float pre = (NU == 1 ? acc[0][r] + acc[1][r] : acc[k][r]) + bias;
-            t = __builtin_fmaf(pre, 0.0f, t);
-            v[k][r] = act_t<ACT>(pre);
-        }
-    asm volatile("" :: "v"(t));
-#elif GNNB_H3_PROBE == 6
     // one probe value per lane over ALL sixteen rows of the units (t stays 0 while every accumulator is finite: inf * 0 and
     // nan * 0 are nan); only when that trips -- rare -- the rows are looked at one by one against the stage's end (rows past it
     // are stale LDS): the row masks, a scalar register pair each, exist inside that branch only
@@ -258,22 +200,6 @@ __device__ __forceinline__ void g2_mma_h3(const char *__restrict__ planes, int r
 #pragma unroll
         for (int r = 0; r < 4; r++)
             v[k][r] = act_t<ACT>((NU == 1 ? acc[0][r] + acc[1][r] : acc[k][r]) + bias);
-#elif GNNB_H3_PROBE == 3
-    // as 2, the row mask formed arithmetically (no compare: every v_cmp result is a scalar register pair, and these variants spill those)
-    float t = 0.0f;
-    const int lim = rows - rg * 16 - lg * 4; // rows of the stage from this lane's first row of unit 0 on
-#pragma unroll
-    for (int k = 0; k < NU; k++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const float pre = (NU == 1 ? acc[0][r] + acc[1][r] : acc[k][r]) + bias;
-            const int m = (k * nrg * 16 + r - lim) >> 31; // all ones while the row is inside the stage
-            t = __builtin_fmaf(__int_as_float(__float_as_int(pre) & m), 0.0f, t);
-            v[k][r] = act_t<ACT>(pre);
-        }
-    if (t != t)
-        *sflag = 1;
-#endif
 }
 // (units in groups of at most two, as g2_mma_s)
 template <int ACT, int KQ32, int NU>
@@ -1206,12 +1132,7 @@ hipError_t launch_gcn2_fused(const BatchTables &t, const float *x, int f0, const
         else if (kq0 == 2 && kq1 == 4) go(atag, IntTag<2>{}, IntTag<4>{});
         else go(atag, IntTag<2>{}, IntTag<2>{});
     };
-#ifdef GNNB_DEV_DEEPH3 // development builds: the deep-GCN f16x3 variants that sit at the 128-register budget, nothing else
-    if (act == GNNB_ACT_RELU)
-        go2(IntTag<GNNB_ACT_RELU>{}, IntTag<1>{}, IntTag<8>{}, IntTag<0>{}, IntTag<1>{}, IntTag<1>{});
-    else
-        go2(IntTag<GNNB_ACT_SIGMOID>{}, IntTag<2>{}, IntTag<8>{}, IntTag<0>{}, IntTag<1>{}, IntTag<1>{});
-#elif defined(GNNB_DEV_FAST) // development builds: only the BASELINE config 2 / 3 instantiations (seconds instead of minutes to compile)
+#ifdef GNNB_DEV_FAST // development builds: only the BASELINE config 2 / 3 instantiations (seconds instead of minutes to compile)
     if (act == GNNB_ACT_RELU && kq0 == 1 && kq1 == 8 && !deep.gin && !math && deep.nl == 2)
         go2(IntTag<GNNB_ACT_RELU>{}, IntTag<1>{}, IntTag<8>{}, IntTag<0>{}, IntTag<0>{}, IntTag<0>{});
     else if (act == GNNB_ACT_RELU && kq0 == 1 && kq1 == 8 && deep.gin && launch_math() == 3)

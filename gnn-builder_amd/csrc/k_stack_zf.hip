@@ -68,58 +68,38 @@ namespace gnnb {
 // two stages hold its rows and ran a third: the kernel ends with its slowest workgroup), ~143 KB of LDS leave room for the
 // readout / graph-prep kernels of the other batches in flight; 0 = two workgroups of 8 waves per CU, stages of up to 96
 // rows (159 KB: nothing co-resides), the only shape for input widths of 17 .. 32.
-#ifndef ZF_PRIO
-#define ZF_PRIO 2
-#endif
-// build-time switches: measured alternatives of this kernel, kept compilable (same-box A/B on BASELINE config 2, wide shape:
-// DESIGN 3.5a "round 4")
-#ifndef ZF_K12         // input widths <= 12: three MFMA k steps per unit in M0 (k = lg + 4 t) instead of four: 38.9 -> 38.55 us
-#define ZF_K12 1
-#endif
-#ifndef ZF_DMA_IN_M1   // the next stage's DMA issued behind the H barrier instead of at the stage top: +-0 (wide), -0.25 us (96-row shape)
-#define ZF_DMA_IN_M1 1
-#endif
-#ifndef ZF_PIN         // scheduler barriers pin "request block q + 1's fragments, THEN issue block q's MFMAs" in zf_mma (left alone the
-#define ZF_PIN 1       // compiler sinks every ds_read to just above its first use): 38.73 -> 38.55 us, 99 VGPRs
-#endif
-#ifndef ZF_SWZ         // H / Z rows unpadded, 16-B chunks XOR-swizzled by the row index: LDS bank conflicts 33 % -> 16 % of LDS cycles and the
-#define ZF_SWZ 0       // kernel 1.7 us SLOWER (38.8 -> 40.5 us, 117 VGPRs): the conflicts sit in M1's fragment reads, where the
-#endif                 // LDS array is < 25 % busy -- they cost nothing; the swizzle's address arithmetic does
+constexpr int ZF_PRIO = 2; // wave priority of the narrow phases (see "Wave priority" at the top of the stage loop)
+// (the alternatives of this kernel that were built, measured and dropped: DESIGN 3.5a and 8)
 
 // accumulate NU 16-row units (rows row0[k] + li) x the wave's 16-column slice over K = 16 KQ:
 // acc[k] += Wslice . A[rows of unit k][:]^T -- the TRANSPOSED tile (weight fragment as the first MFMA operand), so that
 // lane (li, lg) ends up with FOUR CONSECUTIVE columns 16 s + 4 lg .. + 3 of row row0[k] + li: the tile goes back to LDS as
 // one conflict-free ds_write_b128 per lane and unit instead of four ds_write_b32 (64 B/clk/CU; the H and Z write-backs
-// were ~1 k cycles per stage each).  Fragments of k block q+1 are requested before the MFMAs of block q.
-// kmask >= 0: the rows of A are stored with their 16-B chunks XOR-swizzled by (row & kmask) (row0 multiples of 16, so the
-// key of a lane's row is li & kmask): chunk 4 q + lg of the row sits at 4 (q ^ kq) + (lg ^ (li & 3)), kq = (li >> 2) & (kmask >> 2)
+// were ~1 k cycles per stage each).  Fragments of k block q+1 are requested before the MFMAs of block q: the scheduler
+// barriers pin that order (left alone the compiler sinks every ds_read to just above its first use).
 template <int KQ, int NU>
 __device__ __forceinline__ void zf_mma(const float *__restrict__ A, int lda, const float (&wr)[KQ * 4], const int (&row0)[NU],
-                                       int li, int lg, f32x4 (&acc)[NU], int nt = 4, int kmask = -1)
+                                       int li, int lg, f32x4 (&acc)[NU], int nt = 4)
 {
     const float *ap[NU];
-    const int lgs = kmask >= 0 ? (lg ^ (li & 3 & kmask)) : lg;
-    const int kq = kmask >= 0 ? ((li >> 2) & (kmask >> 2)) : 0;
 #pragma unroll
     for (int k = 0; k < NU; k++)
-        ap[k] = A + (row0[k] + li) * lda + lgs * 4;
+        ap[k] = A + (row0[k] + li) * lda + lg * 4;
     float4 a4[NU], an[NU];
 #pragma unroll
     for (int k = 0; k < NU; k++)
-        a4[k] = *reinterpret_cast<const float4 *>(ap[k] + 16 * kq);
+        a4[k] = *reinterpret_cast<const float4 *>(ap[k]);
 #pragma unroll
     for (int q = 0; q < KQ; q++) {
         if (q + 1 < KQ) {
 #pragma unroll
             for (int k = 0; k < NU; k++)
-                an[k] = *reinterpret_cast<const float4 *>(ap[k] + 16 * ((q + 1) ^ kq));
+                an[k] = *reinterpret_cast<const float4 *>(ap[k] + 16 * (q + 1));
         }
-#if ZF_PIN
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int t = 0; t < 4; t++) {
-            if (t >= nt) // (wave-uniform; nt = 3: the block's fourth k step holds zeros on both sides -- narrow inputs, ZF_K12)
+            if (t >= nt) // (wave-uniform; nt = 3: the block's fourth k step holds zeros on both sides -- input widths <= 12)
                 break;
 #pragma unroll
             for (int k = 0; k < NU; k++) {
@@ -127,9 +107,7 @@ __device__ __forceinline__ void zf_mma(const float *__restrict__ A, int lda, con
                 acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[q * 4 + t], av, acc[k], 0, 0, 0);
             }
         }
-#if ZF_PIN
         __builtin_amdgcn_sched_barrier(0);
-#endif
         if (q + 1 < KQ) {
 #pragma unroll
             for (int k = 0; k < NU; k++)
@@ -233,9 +211,7 @@ __device__ __forceinline__ void zf_mma_bf3(const char *__restrict__ Hb, int ldhb
     }
 #pragma unroll
     for (int q = 0; q < KQ32; q++) {
-#if ZF_PIN
         __builtin_amdgcn_sched_barrier(0);
-#endif
         const u32x4 wh = {__float_as_uint(wr[q * 8 + 0]), __float_as_uint(wr[q * 8 + 1]), __float_as_uint(wr[q * 8 + 2]), __float_as_uint(wr[q * 8 + 3])};
         const u32x4 wm = {__float_as_uint(wr[q * 8 + 4]), __float_as_uint(wr[q * 8 + 5]), __float_as_uint(wr[q * 8 + 6]), __float_as_uint(wr[q * 8 + 7])};
         // (the two small products first, then the large one; unit by unit inside a product: consecutive MFMAs never share an accumulator)
@@ -248,9 +224,7 @@ __device__ __forceinline__ void zf_mma_bf3(const char *__restrict__ Hb, int ldhb
 #pragma unroll
         for (int k = 0; k < NU; k++)
             acc[k] = mfma_16x3<MX>(wh, ah[k], acc[k]);
-#if ZF_PIN
         __builtin_amdgcn_sched_barrier(0);
-#endif
         if (q + 1 < KQ32) {
 #pragma unroll
             for (int k = 0; k < NU; k++) {
@@ -296,7 +270,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
     int32_t *__restrict__ err, int32_t *__restrict__ err_host // MX != 0: the workspace's flag word (GNNB_FLAG_RANGE: a non-finite Z, gnnb_device.h RangeProbe)
 #ifdef GNNB_ZF_ABLATE
     , unsigned long long *dbg_span // [2]: min start / max end wall clock (100 MHz) over the workgroups of this launch
-    , int dbg // development only (-DGNNB_ZF_ABLATE): bit 0 skips P1, 1 skips P0', 2 skips M1, 3 skips M0, 4 skips the Z write
+    , int dbg // development only (-DGNNB_ZF_ABLATE): bit 0 skips P1, 1 skips P0', 2 skips M1, 3 skips M0, 4 skips the Z write; 32 / 64: early returns
 #define ZF_ON(bit) (!(dbg & (1 << (bit))))
 #else
 #define ZF_ON(bit) true
@@ -333,23 +307,9 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
     const int rows_b = xs_b + ZF_CAP * 32;
     constexpr int small_b = ZF_CAP * 4 + ((GMAX + 1) * 4 + 15) / 16 * 16;
     constexpr int a0_b = ZF_CAP * LD0 * 4;
-#if ZF_SWZ
-    // H / Z rows: 32, 64 or 128 floats, NOT padded; the 16-B chunks of row r are stored XOR-swizzled by r & kmask.  A
-    // ds_read_b128 is served in four groups of sixteen lanes ({0-3, 12-15, 20-27}, ...): the fragment reads of M0 / M1 put
-    // rows {-4..3} at chunk lg and rows {4..11} at chunk lg + 1 into one group -- with a padded row (33 slots) two of the
-    // sixteen always met on one slot (a third of the kernel's LDS cycles are conflicts, most of them here); XOR by the row index maps the two
-    // row sets onto disjoint slot sets whatever the chunk.  The region starts on a 512-B boundary so that a row's base
-    // and its key do not share bits: P1 forms a neighbour's address as (record offset) ^ (the lane's chunk << 4).
-    const int ldh = (h0 > 64 || h1 > 64) ? 128 : ((h0 > 32 || h1 > 32) ? 64 : 32);
-    const int kmask = (ldh >= 64 ? 16 : 8) - 1;
-    const int hoff = (rows_b + 2 * small_b + a0_b + 511) & ~511;
-#else
     const int ldh = (h0 > h1 ? h0 : h1) + 4; // padded H / Z row (floats): conflict-free fragment reads, base + immediate
-    const int kmask = -1;
     const int hoff = rows_b + 2 * small_b + a0_b;
-#endif
     const int ldhb = ldh * 4;
-    auto hswz = [&](int row) { return ZF_SWZ ? ((row & kmask) << 4) : 0; }; // a row's key, as a byte offset
     constexpr int rec_b = ZF_CAP * 48;
     float *A0 = reinterpret_cast<float *>(smem + rows_b + 2 * small_b);
     float *H = reinterpret_cast<float *>(smem + hoff);
@@ -370,29 +330,13 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
     } span_end{dbg_span};
     if (dbg & 32)
         return; // (launch overhead alone)
-    // de-phasing experiment: bits 8..15 = delay in units of 0.25 us for half of the workgroups, bits 16..17 = which half
-    // (0: the second half of the grid, 1: odd block ids, 2: odd groups of eight, 3: odd groups of 256/8)
-    if ((dbg >> 8) & 255) {
-        const int sel = (dbg >> 16) & 3, b_ = blockIdx.x;
-        const bool mine = sel == 0 ? b_ >= (int)gridDim.x / 2 : (sel == 1 ? (b_ & 1) : (sel == 2 ? ((b_ >> 3) & 1) : ((b_ >> 8) & 1)));
-        if (mine) {
-            const unsigned long long t_ = wall_clock64(), dt = 25ull * ((dbg >> 8) & 255);
-            while (wall_clock64() - t_ < dt)
-                __builtin_amdgcn_s_sleep(16);
-        }
-    }
 #endif
     // ---- the workgroup's run of node tiles: equal tile counts (= equal rows up to one graph).  (A ticket hand-out of
     // fixed-size chunks was built and measured: a chunk must fit a stage whatever its last graph's overhang, i.e. 64
     // nominal rows of a 96-row stage, which turns two stages per workgroup into 2.25 -- three rounds, 55 us instead of 44.
     // The planner below uses the capacity adaptively instead: what one stage's overhang takes the other gives.)
-#ifdef ZF_OLD_CUTS // (development A/B: the two 64-bit software divisions every wave ran until round 6)
-    const int t0 = (int)(((long long)blockIdx.x * num_tiles) / gridDim.x);
-    const int t1 = (int)(((long long)(blockIdx.x + 1) * num_tiles) / gridDim.x);
-#else
     int t0, t1;
     run_cuts(blockIdx.x, gridDim.x, (unsigned)num_tiles, t0, t1); // (32-bit: gnnb_device.h)
-#endif
     if (t1 <= t0)
         return;
     // Every wave fetches the run's tile-table entries into REGISTERS (lane l: tile t0 + l; the launcher keeps runs below
@@ -547,9 +491,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
         const int n0c = (wave & ((1 << cs0l) - 1)) * 16 + li, n1c = (wave & ((1 << cs1l) - 1)) * 16 + li;
 #pragma unroll
         for (int q = 0; q < KQ0; q++) {
-            [[maybe_unused]] const int k = 16 * q + 4 * lg;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-#if ZF_K12
             // k step t of block q multiplies input feature 16 q + lg + 4 t (A0 is stored to match, phase_p0): a model of
             // up to 12 input features (QM9: 11) leaves the fourth step of its only block empty -- M0 skips it
             if (n0c < h0) {
@@ -560,10 +502,6 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                 v.z = kk + 8 < f0 ? wrow[kk + 8] : 0.f;
                 v.w = kk + 12 < f0 ? wrow[kk + 12] : 0.f;
             }
-#else
-            if (n0c < h0)
-                v = load4_guard(W0 + (size_t)n0c * f0 + k, f0 - k, false);
-#endif
             w0r[q * 4 + 0] = v.x;
             w0r[q * 4 + 1] = v.y;
             w0r[q * 4 + 2] = v.z;
@@ -572,7 +510,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
         if constexpr (MX != 0) {
             // (bf16x3: per 32-wide k block the lane's eight k values 32 q + 8 lg .. + 7 of weight row n1c, split into hi and
             // mid bf16 pieces HERE -- once per workgroup, ~100 instructions -- and kept in the same 4 KQ1 registers)
-            static_assert(KQ1 % 2 == 0 && !ZF_SWZ, "bf16x3: whole 32-wide k blocks, padded rows");
+            static_assert(KQ1 % 2 == 0, "bf16x3: whole 32-wide k blocks");
 #pragma unroll
             for (int q = 0; q < KQ1 / 2; q++) {
                 float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
@@ -691,21 +629,11 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
 #pragma unroll
                 for (int t = 0; t < T0; t++) {
                     const int f = l8 + 8 * t;
-#if ZF_K12
                     const int fp = (f & ~15) | ((f & 3) << 2) | ((f >> 2) & 3); // (feature lg + 4 t sits at position 4 lg + t of its block)
-#else
-                    const int fp = f;
-#endif
                     A0[i * LD0 + fp] = f < f0 ? acc[t] + xself[t] * (di * di) : 0.0f;
                 }
                 if (l8 == 0) {
-#if ZF_SWZ
-                    // (LDS byte address of the neighbour's row + its swizzle key: P1 XORs its chunk offset in)
-                    REC[3 * i] = make_int4(hoff + jl[0] * ldhb + hswz(jl[0]), hoff + jl[1] * ldhb + hswz(jl[1]),
-                                           hoff + jl[2] * ldhb + hswz(jl[2]), hoff + jl[3] * ldhb + hswz(jl[3]));
-#else
                     REC[3 * i] = make_int4(jl[0] * ldhb, jl[1] * ldhb, jl[2] * ldhb, jl[3] * ldhb);
-#endif
                     REC[3 * i + 1] = make_int4(__float_as_int(c[0]), __float_as_int(c[1]), __float_as_int(c[2]), __float_as_int(c[3]));
                     REC[3 * i + 2] = make_int4(__float_as_int(di * di), r0.x, deg, __float_as_int(di));
                 }
@@ -776,18 +704,13 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
         pgraphs += cur.gb - cur.ga;
         punits += units;
 #endif
-        // ---- top: the next stage's inputs start their way to LDS (ROWS: P0 of `cur` was its last reader)
-#if !ZF_DMA_IN_M1
-        issue_small(nxt, b ^ 1, tv & 63, wv);
-        issue_rows(nxt, b ^ 1, tv & 63, wv);
-#endif
         ZF_PT(1);
 
         // ---- M0: H = act(A0 . W0^T + b0)   (wave: column slice x row group)
         if (ZF_ON(3)) {
             const int n0c = (wv & ((1 << cs0l) - 1)) * 16 + li;
             const int rg0 = wv >> cs0l;
-            const int nt0 = (ZF_K12 && KQ0 == 1 && f0 <= 12) ? 3 : 4;
+            const int nt0 = (KQ0 == 1 && f0 <= 12) ? 3 : 4;
             auto m0 = [&](auto nutag, int ubase) {
                 constexpr int NU = decltype(nutag)::value;
                 int row0[NU];
@@ -816,7 +739,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                     } else {
 #pragma unroll
                     for (int k = 0; k < NU; k++)
-                        *reinterpret_cast<float4 *>(H + (row0[k] + li) * ldh + (ZF_SWZ ? 4 * ((((n0c - li) >> 2) + lg) ^ (li & kmask)) : (n0c - li) + 4 * lg)) =
+                        *reinterpret_cast<float4 *>(H + (row0[k] + li) * ldh + ((n0c - li) + 4 * lg)) =
                             make_float4(act_t<ACT>(acc[k][0]), act_t<ACT>(acc[k][1]), act_t<ACT>(acc[k][2]), act_t<ACT>(acc[k][3]));
                     }
                 }
@@ -840,14 +763,12 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
         ZF_PT(2);
         g2_barrier(); // H complete
         ZF_PT(3);
-#if ZF_DMA_IN_M1
         // ---- the next stage's inputs start their way to LDS HERE (ROWS: P0 of `cur` was its last reader): at the stage top
         // the ~40 scalar / vector instructions and two or three LDS-DMA issues per wave stood in front of M0 with nothing
         // beside them (0.9-2.2 k cycles per stage); here they run beside the other waves' MFMA stream, and the data still
         // has all of M1 to land
         issue_small(nxt, b ^ 1, tv & 63, wv);
         issue_rows(nxt, b ^ 1, tv & 63, wv);
-#endif
 
         // ---- M1: Z = H . W1^T for the wave's column slice and its units: stays in the accumulators across the barrier
         // (the ONLY phase at low priority: see the note on s_setprio at the top of the stage loop)
@@ -874,7 +795,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                 if constexpr (MX != 0)
                     zf_mma_bf3<MX, KQ1 / 2, NU>(reinterpret_cast<const char *>(H), ldhb, 2 * h0, w1r, row0, li, lg, acc);
                 else
-                    zf_mma<KQ1, NU>(H, ldh, w1r, row0, li, lg, acc, 4, kmask);
+                    zf_mma<KQ1, NU>(H, ldh, w1r, row0, li, lg, acc);
 #pragma unroll
                 for (int k = 0; k < NU; k++)
                     if (UB + k < ZMAX)
@@ -916,7 +837,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
 #pragma unroll
             for (int k = 0; k < ZMAX; k++)
                 if (k < nu1)
-                    *reinterpret_cast<float4 *>(H + ((rg1 + k * nrg1) * 16 + li) * ldh + (ZF_SWZ ? 4 * ((((n1c - li) >> 2) + lg) ^ (li & kmask)) : (n1c - li) + 4 * lg)) =
+                    *reinterpret_cast<float4 *>(H + ((rg1 + k * nrg1) * 16 + li) * ldh + ((n1c - li) + 4 * lg)) =
                         make_float4(z[k][0], z[k][1], z[k][2], z[k][3]);
         }
         g2_barrier(); // Z complete
@@ -942,10 +863,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
             // (round 4, wide shape: letting the parts fill ALL sixteen waves -- eight graphs x two parts -- is 0.25 us SLOWER,
             // 40.15 vs 39.9 us: the row walk of a task shortens from 4.1 k to 2.9 k cycles, but every task pays its ~1.9 k
             // cycles of set-up, combine and stores, and the next stage's P0 loses its idle waves)
-#ifndef ZF_P1_FILL // (development A/B: 1 = column parts until the tasks fill ALL waves)
-#define ZF_P1_FILL 0
-#endif
-            while (pow2 && csl < 2 && (ngr << (csl + 1)) <= (ZF_P1_FILL ? G2_NW : G2_NW / 2) && (nv >> (csl + 1)) >= 4)
+            while (pow2 && csl < 2 && (ngr << (csl + 1)) <= G2_NW / 2 && (nv >> (csl + 1)) >= 4)
                 csl++;
         }
         if (ZF_ON(0)) {
@@ -981,16 +899,11 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                 r1g = min(__builtin_amdgcn_readfirstlane(r1g) - nb, rows);
                 const bool lane_on = gl * 4 < wpart;
                 const int col0 = lane_on ? cpart * wpart + gl * 4 : 0; // this lane's first column
-                const char *Hl = reinterpret_cast<const char *>(H) + col0 * 4; // its chunk of row 0 (unswizzled layout)
-                [[maybe_unused]] const int cx = col0 * 4; // its chunk as a byte offset inside a row: XORed into a row's swizzled base
+                const char *Hl = reinterpret_cast<const char *>(H) + col0 * 4; // its chunk of row 0
                 // (LDS byte address of this lane's chunk of row i)
-                auto hrow = [&](int i) { return ZF_SWZ ? smem + ((hoff + i * ldhb + hswz(i)) ^ cx) : Hl + i * ldhb; };
+                auto hrow = [&](int i) { return Hl + i * ldhb; };
                 const float4 bias = *reinterpret_cast<const float4 *>(SB1 + col0);
                 V sum = V::splat(0.0f), mx = V::splat(-INFINITY);
-#ifdef GNNB_ZF_ABLATE
-                if (dbg & (1 << 20)) // (what would P1 cost if two waves shared a graph's rows?  half of the rows: WRONG results)
-                    r1g = r0g + ((r1g - r0g + 1) >> 1);
-#endif
                 const int n = max(r1g - r0g, 0);
                 // Row loop, written for instruction count (in this phase every instruction of the wave is on the
                 // workgroup's critical path, and VALU issue is what the phase is bound by): running pointers instead of
@@ -998,13 +911,8 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                 // waves of the SIMD cover the two LDS round trips), full passes without predication and one predicated
                 // tail pass, maxima through v_max_f32 directly (fmaxf adds a canonicalising v_max per operand).
                 const char *prec = reinterpret_cast<const char *>(REC) + (r0g + sr) * 48;
-#if ZF_SWZ
-                int pself = r0g + sr; // (the row index: its address is formed per pass, the key changes with the row)
-                const int dself = S;
-#else
                 const char *pself = Hl + (r0g + sr) * ldhb;
                 const int dself = ldhb << (6 - glog2);
-#endif
                 const int drec = 48 << (6 - glog2);
                 auto vmax_raw = [](float a, float b2) {
                     float r;
@@ -1023,17 +931,6 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                     r.da = *reinterpret_cast<const int4 *>(pr + 32);
                     return r;
                 };
-#if ZF_SWZ
-                auto load_rows = [&](const RowRec &r, int ps) {
-                    RowDat d;
-                    d.n0 = V::load(reinterpret_cast<const float *>(smem + (r.ja.x ^ cx))); // unused slots alias the row itself (coefficient 0)
-                    d.n1 = V::load(reinterpret_cast<const float *>(smem + (r.ja.y ^ cx)));
-                    d.n2 = V::load(reinterpret_cast<const float *>(smem + (r.ja.z ^ cx)));
-                    d.n3 = V::load(reinterpret_cast<const float *>(smem + (r.ja.w ^ cx)));
-                    d.self = V::load(reinterpret_cast<const float *>(hrow(ps)));
-                    return d;
-                };
-#else
                 auto load_rows = [&](const RowRec &r, const char *ps) {
                     RowDat d;
                     d.n0 = V::load(reinterpret_cast<const float *>(Hl + r.ja.x)); // unused slots alias the row itself (coefficient 0)
@@ -1043,7 +940,6 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                     d.self = V::load(reinterpret_cast<const float *>(ps));
                     return d;
                 };
-#endif
                 auto finish_row = [&](const RowRec &r, const RowDat &d, bool active) {
                     const int4 ca = r.ca, da = r.da;
                     V acc;
@@ -1093,11 +989,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                     const bool active = sr < ntail;
                     if (!active) { // (inactive lane groups re-read the graph's first row)
                         prec = reinterpret_cast<const char *>(REC) + r0g * 48;
-#if ZF_SWZ
-                        pself = r0g;
-#else
                         pself = Hl + r0g * ldhb;
-#endif
                     }
                     one_row(active);
                 }
@@ -1139,11 +1031,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                     sum.v = make_float4(v[0], v[1], v[2], v[3]);
                     mx.v = make_float4(v[4], v[5], v[6], v[7]);
                 }
-#ifndef ZF_P1_LEAN // (development A/B: 0 = the round-5 form of the pooled stores)
-#define ZF_P1_LEAN 1
-#endif
                 if (sr == 0 && lane_on) {
-#if ZF_P1_LEAN
                     // (n is wave-uniform: ONE branch for the empty graph instead of a select per value and pool, and the reciprocal
                     // as v_rcp + one Newton step -- 3 instructions -- instead of the 11 of an IEEE division: ~25 vector
                     // instructions less per task, and every task's set-up is on the phase's critical path)
@@ -1165,19 +1053,6 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                             rr = mx;
                         rr.store(pooled + ((size_t)(cur.ga + gi) * np + kk) * h1p + col0);
                     }
-#else
-#pragma unroll
-                    for (int kk = 0; kk < 3; kk++) {
-                        if (kk >= np)
-                            break;
-                        V rr = sum;
-                        if (pools[kk] == GNNB_POOL_MEAN)
-                            rr = n > 0 ? vmul(sum, V::splat(1.0f / (float)n)) : V::splat(0.0f);
-                        else if (pools[kk] == GNNB_POOL_MAX)
-                            rr = n > 0 ? mx : V::splat(0.0f);
-                        rr.store(pooled + ((size_t)(cur.ga + gi) * np + kk) * h1p + col0);
-                    }
-#endif
                 }
             };
             // two loops, not one with a choice inside: a select between the LDS table and global memory is
@@ -1191,28 +1066,6 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
         }
         ZF_PT(7);
 
-#ifdef GNNB_ZF_ABLATE
-        // development: the waves WITHOUT a graph (8 .. 15 at BASELINE config 2) run a whole M1's worth of MFMAs beside P1 (one
-        // column slice x ALL units each; results dropped) -- does the row walk overlap with a matrix stream on the same SIMDs?
-        if ((dbg & (1 << 21)) && wv >= G2_NW / 2) {
-            __builtin_amdgcn_s_setprio(0);
-            for (int u = 0; u < units; u += 3) {
-                int row0[3];
-                f32x4 acc[3];
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    row0[k] = min(u + k, units - 1) * 16;
-                    acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                }
-                if constexpr (MX == 0)
-                    zf_mma<KQ1, 3>(H, ldh, w1r, row0, li, lg, acc, 4, kmask);
-#pragma unroll
-                for (int k = 0; k < 3; k++)
-                    asm volatile("" ::"v"(acc[k]));
-            }
-            __builtin_amdgcn_s_setprio(ZF_PRIO);
-        }
-#endif
         // ---- P0 of the NEXT stage (its rows landed before the last barrier but one), starting on the first wave that
         // had no graph to reduce
         if (nxt.ok && ZF_ON(1))
@@ -1345,25 +1198,14 @@ hipError_t ZF_LAUNCH_NAME(const BatchTables &t, const float *x, int f0, const fl
     const int gmax = cap <= 96 ? 64 : 128;
     const int xs_b = ((cap * f0 * 4) + 15) & ~15;
     const int rows_b = xs_b + cap * 32, small_b = cap * 4 + ((gmax + 1) * 4 + 15) / 16 * 16;
-#if ZF_SWZ
-    const int ldh = (h0 > 64 || h1 > 64) ? 128 : ((h0 > 32 || h1 > 32) ? 64 : 32); // (as the kernel's carve)
-    const size_t hoff = ((size_t)rows_b + 2 * (size_t)small_b + (size_t)cap * 16 * kq0 * 4 + 511) & ~(size_t)511;
-#else
-    const int ldh = (h0 > h1 ? h0 : h1) + 4;
+    const int ldh = (h0 > h1 ? h0 : h1) + 4; // (as the kernel's carve)
     const size_t hoff = (size_t)rows_b + 2 * (size_t)small_b + (size_t)cap * 16 * kq0 * 4;
-#endif
     const int ecap = cap <= 96 ? 512 : 1024;
     const size_t lds = hoff + (size_t)cap * ldh * 4 +
                        2 * (size_t)cap * 48 + 2 * (size_t)ecap * 4 + 512 + 32 + 512 + 768;
 
     if (lds > 160 * 1024)
         return hipErrorNotSupported;
-#ifdef GNNB_ZF_ABLATE
-    // development: GNNB_ZF_ONE=1 asks for > 80 KB of LDS so that only ONE 8-wave workgroup fits a CU (does the MFMA phase
-    // of two waves per SIMD saturate the matrix pipe on its own?)
-    const size_t lds_req = getenv("GNNB_ZF_ONE") && atoi(getenv("GNNB_ZF_ONE")) ? std::max(lds, (size_t)96 * 1024) : lds;
-#define lds lds_req
-#endif
     const int p0 = pools[0], p1 = num_pools > 1 ? pools[1] : 0, p2 = num_pools > 2 ? pools[2] : 0;
     // the MLP head inside the kernel (the caller offers it when the head's activation is the stack's): the small form's
     // shape conditions, its input = the pooled row, and its activation tiles (one per group of four waves) inside the H region
@@ -1475,9 +1317,6 @@ hipError_t ZF_LAUNCH_NAME(const BatchTables &t, const float *x, int f0, const fl
         *head_fused = head_dev != nullptr;
     return rc;
 }
-#ifdef GNNB_ZF_ABLATE
-#undef lds
-#endif
 #undef ZF_LAUNCH_NAME
 
 } // namespace gnnb

@@ -37,13 +37,6 @@ for w in $WL; do
     rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU --output-format csv -d "$OUT/pmc_${w}_lds" -o lds -- python3 bench.py --workload $w --roofline-only > "$OUT/pmc_${w}_lds.log" 2>&1
   fi
 done
-# k_gcn2_zf built with its H / Z rows XOR-swizzled (-DZF_SWZ=1, gnn-builder_amd/libgnnb_v_swz.so when present): the LDS bank
-# conflicts of the shipped kernel's fragment reads, gone -- and what that costs
-if [ -f "$R/gnn-builder_amd/libgnnb_v_swz.so" ]; then
-  GNNB_HIP_LIB=$R/gnn-builder_amd/libgnnb_v_swz.so python3 bench.py --workload c2 --roofline-only > "$OUT/swz_roofline.log" 2>&1
-  GNNB_HIP_LIB=$R/gnn-builder_amd/libgnnb_v_swz.so rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU --output-format csv -d "$OUT/pmc_swz_lds" -o lds -- python3 bench.py --workload c2 --roofline-only > "$OUT/pmc_swz_lds.log" 2>&1
-  GNNB_HIP_LIB=$R/gnn-builder_amd/libgnnb_v_swz.so rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d "$OUT/pmc_swz_inst" -o inst -- python3 bench.py --workload c2 --roofline-only > "$OUT/pmc_swz_inst.log" 2>&1
-fi
 # keep the merge small: the per-dispatch traces are not needed once the stats exist
 find "$OUT" -name "*kernel_trace.csv" -delete
 find "$OUT" -name "*.csv" | xargs ls -la | head -60

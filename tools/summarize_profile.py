@@ -131,24 +131,3 @@ for wdir in sorted(src.glob("bench_*")):
             s2["note_busy"] = "SQ_VALU_MFMA_BUSY_CYCLES is summed over the 1024 SIMDs: / 1024 = matrix-pipe cycles per SIMD"
         (dst / f"{tag}_{w}_gcn2_pmc.json").write_text(json.dumps(s2, indent=2) + "\n")
     print(w, "done")
-
-# the swizzled build of k_gcn2_zf (profile_r.sh): conflicts and time beside the shipped kernel's
-swz = src / "swz_roofline.log"
-if swz.exists():
-    meas = [l for l in swz.read_text().splitlines() if l.startswith("{")]
-    pm = {}
-    for sub in ("pmc_swz_lds", "pmc_swz_inst"):
-        for p in (src / sub).rglob("*counter_collection.csv"):
-            acc = collections.defaultdict(list)
-            for r in csv.DictReader(open(p)):
-                if "k_gcn2_zf" in r["Kernel_Name"]:
-                    acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
-            for k, v in acc.items():
-                pm[k] = {"launches": len(v), "mean": sum(v) / len(v)}
-    if meas and pm:
-        m = json.loads(meas[-1])
-        out = {"what": "k_gcn2_zf built with -DZF_SWZ=1 (H / Z rows unpadded, 16-B chunks XOR-swizzled by the row index): NOT the shipped kernel",
-               "events_us_per_launch": (m.get("fused_stack") or {}).get("us"), "raw_counters_per_launch": pm}
-        if "SQ_LDS_BANK_CONFLICT" in pm and "SQ_LDS_IDX_ACTIVE" in pm:
-            out["lds_bank_conflict_share_of_lds_cycles"] = pm["SQ_LDS_BANK_CONFLICT"]["mean"] / pm["SQ_LDS_IDX_ACTIVE"]["mean"]
-        (dst / f"{tag}_c2_gcn2_swizzled_build_pmc.json").write_text(json.dumps(out, indent=2) + "\n")
