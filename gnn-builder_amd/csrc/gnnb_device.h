@@ -331,10 +331,6 @@ __device__ __forceinline__ float lg_coef(int di, int dj)
     return pr > 0 ? __frsqrt_rn((float)pr) : 0.0f; // (v_rsq_f32: 1 ulp; the oracle's 1/sqrt differs by < 2e-7 relative)
 }
 
-static constexpr int BM = 128;
-static constexpr int BK = 32;
-static constexpr int LDS_LD = BK + 4; // padded row, floats
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ inline float act_apply(float v, int act)

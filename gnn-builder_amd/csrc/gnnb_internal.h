@@ -265,7 +265,7 @@ struct PoolEpilogue {
     float2 *part = nullptr;              // [ceil(M / 32), 2, N] {sum, max} of a block's first / last open piece
     int32_t num_graphs = 0, np = 0, pools[3] = {0, 0, 0};
 };
-// Stream-K tail of k_linear_dma (k_gemm.hip): q chunks per run; part[2 * workgroup + segment][4 waves][64 x 64 lanes]
+// Stream-K tail of k_linear_dma (k_linear_dma.hip; planned by plan_linear_dma, gnnb_gemm.h): q chunks per run; part[2 * workgroup + segment][4 waves][64 x 64 lanes]
 // accumulators, cnt[first workgroup of a shared tile] arrival counters (zero between launches).  q = 0: off.
 struct StreamK {
     int q = 0;
@@ -287,7 +287,7 @@ constexpr int GNNB_DEG_MAX = GNNB_DEG_CLASSES - 1;
 // the batch's rows sorted into degree classes (k_misc.hip); work = 256 x 16 ints, perm = max_tiles * 128, tile_cls = max_tiles
 hipError_t launch_degree_classes(const BatchTables &t, int promise, int32_t *work, int32_t *perm, int32_t *tile_cls, int max_tiles,
                                  hipStream_t s);
-// Row classes of k_linear_dma (PNA under a degree promise, k_gemm.hip): perm[position in the class-sorted space] = row or -1,
+// Row classes of k_linear_dma (PNA under a degree promise, k_linear_dma.hip): perm[position in the class-sorted space] = row or -1,
 // tile_cls[128-row tile of that space] = class, whose weight matrix starts w_stride floats after the previous one's.
 struct RowClasses {
     const int32_t *perm = nullptr;

@@ -31,7 +31,7 @@ hipError_t launch_output_activation(float *out, int num_graphs, int n, int kind,
 }
 
 // ---- degree classes (PNA under a degree promise <= GNNB_DEG_CLASSES): the batch's rows sorted by in-degree (0 .. 15) into
-// 128-row tiles of ONE class each, for k_linear_dma's row-class mode (k_gemm.hip).  perm[position] = row (-1: padding),
+// 128-row tiles of ONE class each, for k_linear_dma's row-class mode (k_linear_dma.hip).  perm[position] = row (-1: padding),
 // tile_cls[tile] = class = in-degree.  A STABLE counting sort without atomics (same-address atomics from every wave of the batch
 // cost 150 us per pass at BASELINE config 4): GNNB_DEG_RUNS waves take one contiguous run of rows each -- count per (run,
 // class) -> one workgroup turns the counts into bases (classes padded to whole tiles, runs in order) -> every wave places its

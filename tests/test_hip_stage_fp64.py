@@ -9,7 +9,7 @@ reached on purpose and compared with a float64 restatement of the same operation
 ``base`` is an fp32 evaluation of the same formula: the ref64 forms in float32 (neighbours in CSR order, self term last) for
 the aggregates and pooling, a float32 torch CPU product for the GEMMs.
 
-Where each form is reached (gnnb_runtime.hip ``build_gemm``, k_gemm.hip ``launch_linear``, k_aggregate.hip ``launch_aggregate``):
+Where each form is reached (gnnb_runtime.hip ``build_gemm``, gemm_launch.hip ``launch_linear``, k_aggregate.hip ``launch_aggregate``):
   * scalar GEMM operands (``avec`` / ``wvec`` = 0): the ``a_slice`` / ``w_slice`` / ``offset`` layouts and every odd K;
   * scalar epilogue (``vec`` = 0): odd N, or the ``offset`` layout (bias, skip, out one float in);
   * scalar aggregate / pooling / GINE forms (``v4`` = 0): odd widths and the offset x / self_dev / out views;
@@ -87,7 +87,7 @@ def on_device(a, offset=False):
 
 
 # --------------------------------------------------------------------------- gnnb_linear
-# every GEMM family, forced through the options that choose it (k_gemm.hip launch_linear); the predicates then still pick
+# every GEMM family, forced through the options that choose it (gemm_launch.hip launch_linear); the predicates then still pick
 # the family's scalar form (or the next family) from the operands' layout
 FAMILIES = {"wlds": {}, "reg": {"gemm_wlds": 0}, "dma_tail2": {"gemm_variant": 1}, "dma_tail1": {"gemm_variant": 1, "gemm_tail_split": 1},
             "dma_tail0": {"gemm_variant": 1, "gemm_tail_split": 0}, "generic": {"gemm_variant": 1, "gemm_dma": 0}}

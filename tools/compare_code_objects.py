@@ -28,8 +28,9 @@ def run(*cmd, **kw):
 
 
 def kernels(lib: Path, tmp: Path) -> dict:
-    """{kernel name: [(sha256 of its function's bytes, byte count, metadata tuple), ...]} over every gfx950 code object in `lib`, in
-    bundle order (a template instantiated in two translation units is a weak symbol in both code objects: one entry each)."""
+    """{kernel name: [(sha256 of its function's bytes, byte count, metadata tuple), ...]} over every gfx950 code object in `lib`
+    (a template instantiated in two translation units is a weak symbol in both code objects: one entry each), the entries of a
+    name sorted -- a multiset: which translation unit holds a copy, and so the bundle order, is not the kernels' business."""
     fat = tmp / "fat.bin"
     run(LLVM / "llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", lib, tmp / "unused.so")
     data = fat.read_bytes()
@@ -74,7 +75,7 @@ def kernels(lib: Path, tmp: Path) -> dict:
                 out.setdefault(f[7], []).append((hashlib.sha256(body).hexdigest(), size, meta[f[7]]))
         missing = set(meta) - set(out)
         assert not missing, f"{co}: kernels without a function symbol: {sorted(missing)[:3]}"
-    return out
+    return {k: sorted(v, key=repr) for k, v in out.items()}
 
 
 def main() -> int:
