@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <map>
 #include <mutex>
+#include <tuple>
 #include <utility>
 
 #include "gnnb_internal.h"
@@ -33,8 +34,8 @@ static hipError_t ensure_dynamic_lds(const void *kern, size_t lds)
     return e;
 }
 
-// CUs of the CURRENT device (cached per device under a lock: a process may drive several GPUs)
-static int device_cu_count()
+// CUs of the CURRENT device (cached per device under a lock: a process may drive several GPUs; inline: one map for the library)
+inline int device_cu_count()
 {
     static std::mutex mu;
     static std::map<int, int> cus;
@@ -48,6 +49,43 @@ static int device_cu_count()
     const int n = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
     cus[dev] = n;
     return n;
+}
+
+// Resident workgroups per CU of `kern` at this block size and dynamic LDS size, capped at `want` (what its launcher is built for),
+// and the CUs of the CURRENT device: the persistent kernels' grid.  The occupancy query costs microseconds, so it is remembered
+// per (device, kernel, threads, lds) under a lock -- launches may come from several host threads and go to several devices.
+// (inline, like device_cu_count: ONE map for the whole library, whichever unit asks.)
+struct Occupancy {
+    int blocks, cus;
+};
+inline Occupancy kernel_occupancy(const void *kern, int threads, size_t lds, int want)
+{
+    struct Key {
+        int dev;
+        const void *kern;
+        int threads;
+        size_t lds;
+        bool operator<(const Key &o) const { return std::tie(dev, kern, threads, lds) < std::tie(o.dev, o.kern, o.threads, o.lds); }
+    };
+    static std::mutex mu;
+    static std::map<Key, Occupancy> seen; // (blocks uncapped)
+    Key k{0, kern, threads, lds};
+    (void)hipGetDevice(&k.dev);
+    Occupancy o;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = seen.find(k);
+        if (it == seen.end()) {
+            int nb = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds) != hipSuccess || nb < 1)
+                nb = 1;
+            it = seen.emplace(k, Occupancy{nb, device_cu_count()}).first;
+        }
+        o = it->second;
+    }
+    if (o.blocks > want)
+        o.blocks = want;
+    return o;
 }
 
 static constexpr int WG = 256; // 4 wavefronts

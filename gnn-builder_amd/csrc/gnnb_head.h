@@ -1,5 +1,5 @@
 // gnnb_head.h -- the MLP head on pooled rows as a device function: k_head_small (k_readout.hip) runs it as a kernel of its
-// own, k_gcn2_zf (k_stack_zf.hip) runs it at the end of every workgroup's life on the graphs that workgroup pooled (round 5:
+// own, k_gcn2_zf (k_stack_zf.h) runs it at the end of every workgroup's life on the graphs that workgroup pooled (round 5:
 // conv stack + pooling + head in ONE launch -- reference compute_gnn_head -> compute_global_graph_pooling ->
 // compute_mlp_head inside one top, templates/model.cpp.jinja:737-765).
 #pragma once

@@ -57,9 +57,10 @@ struct BatchTables {
 constexpr int GNNB_FLAG_RANGE = 64;
 constexpr int GNNB_G2_STAGE_ROWS = 64;     // rows per stage of the fused 2-layer GCN kernel (4 MFMA units)
 constexpr int GNNB_G2_STAGE_ROWS_BF6 = 48; // ... in the opt-in bf16x6 math mode (3 units)
-// rows per stage of the transform-first 2-layer GCN kernel k_gcn2_zf for input width f0 and the promised graph size (176 or 96)
-int zf_stage_rows(int f0, int promise);
-long gcn2_zf_tile_capacity(int f0, int promise); // node tiles it can walk in one launch
+// what graph prep asks about k_gcn2_zf, the transform-first 2-layer GCN kernel (k_stack_zf.hip; the values are the launch plan's
+// own: gnnb_stack_plan.h): rows per stage for input width f0 under the zf_shape option (176 or 96) ...
+int zf_stage_rows(int f0);
+long gcn2_zf_tile_capacity(int f0); // ... and the node tiles it can walk in one launch (ZF_TCAP per resident workgroup)
 
 // One tuning knob: a relaxed atomic int.  The knobs are process-wide and may be set (gnnb_set_option) while other threads launch
 // -- round-5 review: "35+ knobs, unsynchronised".  Every read and write is now a single atomic access: no data race; a launcher that
@@ -327,7 +328,8 @@ struct G2Deep {
     int gin = 0;
     float eps = 0.0f;
 };
-long gcn2_fused_tile_capacity();
+// what graph prep asks about k_gcn2_fused (k_stack.hip; the values are the launch plan's own: gnnb_stack_plan.h, G2_TCAP)
+long gcn2_fused_tile_capacity();          // node tiles it can walk in one launch
 int gcn2_fused_grid(int num_tiles);       // workgroups k_gcn2_fused launches for that many node tiles (CUs x 2, at most one per tile)
 int gcn2_fused_tile_window();             // tiles a workgroup's run may span (its tile-table window in LDS)
 // the conv-stack kernels' runs as whole stages of the global greedy stage list (k_plan.hip): cut [G + 2] (cut[G + 1] = valid)
@@ -338,7 +340,8 @@ hipError_t launch_gcn2_fused(const BatchTables &t, const float *x, int f0, const
                              int h0, const float *w1, const float *b1, int h1, int act,
                              const int32_t *pools, int num_pools, float *pooled, hipStream_t s, const G2Deep &deep = G2Deep{});
 
-// The same stack for exactly two GCN layers in fp32 math, last layer transformed before it is aggregated (k_stack_zf.hip)
+// The same stack for exactly two GCN layers in fp32 math, last layer transformed before it is aggregated (k_stack_zf.h; the two
+// entry points are the two translation units that instantiate it)
 // head != nullptr: the MLP head (activation = `act`) runs inside the kernel too when its shape allows (*head_fused says so):
 // out [B, mlp_out] is then complete and the caller launches no readout for these graphs
 hipError_t launch_gcn2_zf(const BatchTables &t, const float *x, int f0, const float *w0, const float *b0,

@@ -335,7 +335,7 @@ static StackKernel promised_stack_kernel(const gnnb_workspace *ws)
     StackKernel k;
     k.zf = gcn2 && options().fuse_zf;
     k.bf6 = !k.zf && launch_math() && gcn2;
-    k.stage_rows = k.zf ? zf_stage_rows(d.in_dim, ws->max_graph_nodes) : k.bf6 ? GNNB_G2_STAGE_ROWS_BF6 : GNNB_G2_STAGE_ROWS;
+    k.stage_rows = k.zf ? zf_stage_rows(d.in_dim) : k.bf6 ? GNNB_G2_STAGE_ROWS_BF6 : GNNB_G2_STAGE_ROWS;
     return k;
 }
 
@@ -423,7 +423,7 @@ static int graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int
         while (t.tile_rows > 4 && ws->max_graph_nodes + t.tile_rows - 1 > k.stage_rows)
             t.tile_rows >>= 1;
         // very large batches: coarser tiles (while a tile still fits a stage) keep the per-workgroup tile table in LDS
-        const long tile_cap = k.zf ? gcn2_zf_tile_capacity(ws->desc.in_dim, ws->max_graph_nodes) : gcn2_fused_tile_capacity();
+        const long tile_cap = k.zf ? gcn2_zf_tile_capacity(ws->desc.in_dim) : gcn2_fused_tile_capacity();
         while ((num_nodes + t.tile_rows - 1) / t.tile_rows > tile_cap && ws->max_graph_nodes + 2 * t.tile_rows - 1 <= k.stage_rows)
             t.tile_rows <<= 1;
     }
@@ -1112,7 +1112,7 @@ static hipError_t launch_conv_stack(const gnnb_model *model, gnnb_workspace *ws,
     hipError_t he = hipErrorNotSupported;
     if (head_fused)
         *head_fused = false;
-    if (!deep.gin && L == 2) { // two GCN layers, fp32: the transform-first form with 96-row stages (k_stack_zf.hip)
+    if (!deep.gin && L == 2) { // two GCN layers, fp32: the transform-first form with 96-row stages (k_stack_zf.h)
         const bool offer = head_out != nullptr && model->head_dev != nullptr && d.mlp_num_linear <= 8 && d.mlp_activation == d.activation;
         const HeadArgs head = model_head_args(model);
         he = launch_gcn2_zf(t, x_dev, d.in_dim, model->conv[0][0], model->conv[0][1], d.hidden_dim, model->conv[1][0],

@@ -1,14 +1,35 @@
-// gnnb_stack.h -- pieces shared by the LDS-resident conv-stack kernels (k_stack.hip: k_gcn2_fused; k_stack_zf.hip: k_gcn2_zf)
+// gnnb_stack.h -- pieces shared by the LDS-resident conv-stack kernels (k_stack.hip: k_gcn2_fused; k_stack_zf.h: k_gcn2_zf): device
+// helpers and the launchers' common host side.  Their carves, plans and capacities (ZF_TCAP, G2_TCAP): gnnb_stack_plan.h
 #pragma once
 #include "gnnb_device.h"
+#include "gnnb_stack_plan.h"
 
 namespace gnnb {
 
-__host__ __device__ constexpr int g2_units(int math) { return math ? 3 : 4; }
 static_assert(16 * g2_units(0) == GNNB_G2_STAGE_ROWS && 16 * g2_units(1) == GNNB_G2_STAGE_ROWS_BF6, "graph prep picks the tile size against these");
-static constexpr int G2_TCAP = 64;           // tile-table entries a workgroup keeps in LDS
-static constexpr int G2_WG = 512;            // 8 waves; two workgroups per CU = 4 waves per SIMD
-static constexpr int G2_NW = G2_WG / 64;
+
+// ---- host side: what the two launchers do alike
+// the operands both kernels read with vector loads: w1, pooled (and zf's b1, when there is one) at 16 B, x at 4 B
+inline bool stack_operands_aligned(const float *x, const float *w1, const float *pooled, const float *b1)
+{
+    return !((((uintptr_t)w1) & 15) || (((uintptr_t)pooled) & 15) || (((uintptr_t)x) & 3) || (b1 && (((uintptr_t)b1) & 15)));
+}
+// up to three pooling kinds as kernel arguments (0 past the model's count)
+struct StackPools {
+    int p0, p1, p2;
+    StackPools(const int32_t *pools, int n) : p0(pools[0]), p1(n > 1 ? pools[1] : 0), p2(n > 2 ? pools[2] : 0) {}
+};
+// the (KQ0, KQ1) instantiations both kernels exist in: input width in one or two 16-wide k blocks x hidden width 128 / 64 / 32
+template <class ActTag, class Go>
+inline void stack_dispatch_kq(int kq0, int kq1, ActTag atag, Go &&go)
+{
+    if (kq0 == 1 && kq1 == 8) go(atag, IntTag<1>{}, IntTag<8>{});
+    else if (kq0 == 1 && kq1 == 4) go(atag, IntTag<1>{}, IntTag<4>{});
+    else if (kq0 == 1 && kq1 == 2) go(atag, IntTag<1>{}, IntTag<2>{});
+    else if (kq0 == 2 && kq1 == 8) go(atag, IntTag<2>{}, IntTag<8>{});
+    else if (kq0 == 2 && kq1 == 4) go(atag, IntTag<2>{}, IntTag<4>{});
+    else go(atag, IntTag<2>{}, IntTag<2>{});
+}
 
 struct G2Stage {
     int ta, tb, nb, rows, ga, gb;

@@ -33,7 +33,7 @@ struct PaStage {
 };
 
 // MX = 2 ("f16x3", opt-in REDUCED precision: gnnb_set_option("math", 3)): the product on the fp16 matrix cores, hi + mid fp16
-// pieces of both operands, three products per 32-wide k block (k_stack_zf.hip / gnnb_device.h).  The x rows arrive by DMA as
+// pieces of both operands, three products per 32-wide k block (k_stack_zf.h / gnnb_device.h).  The x rows arrive by DMA as
 // fp32, and split by every wave that reads them the pieces would cost what the matrix cores save -- so the stage's rows are
 // split ONCE, cooperatively and in place (every thread reads its eight values, barrier, writes 16 B into each of the two planes
 // of the same padded row), in front of M: two barriers more per stage.  P still goes back over the rows in fp32.

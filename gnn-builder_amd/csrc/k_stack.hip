@@ -114,7 +114,7 @@ __device__ __forceinline__ void g2_mma_s(const float *__restrict__ Asrc, int lda
 // 128-wide product lives in LDS as hi + mid fp16 pieces, two planes inside the SAME padded fp32 row ([hi: h0 x 2 B][mid: h0 x 2 B]
 // [pad]; the producer -- P1, or the product before -- writes them), the weight slice as hi + mid pieces in the same 4 KQ
 // registers; three v_mfma_f32_16x16x32_f16 per 32-wide k block (mid.hi... hi.mid, hi.hi) instead of eight fp32 MFMAs of twice
-// the passes.  Chunks of rows 4..11 (mod 16) are stored with the lowest bit of their index flipped (k_stack_zf.hip: conflict-
+// the passes.  Chunks of rows 4..11 (mod 16) are stored with the lowest bit of their index flipped (k_stack_zf.h: conflict-
 // free fragment reads); ONE fragment buffer (block q + 1 requested behind block q's MFMAs: the register budget is 128).
 __device__ __forceinline__ int g2_h3_key(int row) { return ((row & 15) + 4) >> 3 & 1; }
 // byte offset of element (row, column c) inside its plane (add row * row bytes, + 2 h0 for the mid plane)
@@ -313,19 +313,18 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
     constexpr bool G2_W0_PER_STAGE = DEEP || GIN || (MATH && KQ0 == 2); // the narrow slice re-read per stage (see M0)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
-    // ---- LDS carve (bytes, every region 16-B aligned):
-    //   rows  xs | srec                ONE buffer: read by P0 only, refilled right behind P0
-    //   small sdinv | node_ptr of <= 64 graphs (+ end)   TWO buffers (P1 and the pooling still read them)
-    //   H | A1 (A0 lives in the head of A1: P0 writes it, M0 reads it, P1 overwrites it) | REC | tile tables
-    const int xs_b = ((G2_CAP * f0 * 4) + 15) & ~15;
-    const int rows_b = xs_b + G2_CAP * 32;
-    const int small_b = G2_CAP * 4 + 272;
-    const int ldh = (h0 > h1 ? h0 : h1) + 4;          // padded H row (floats)
+    // ---- LDS carve: the regions, their order and their sizes are G2Carve's (gnnb_stack_plan.h; the launcher's LDS size is the same
+    // carve's total())
+    const G2Carve cv{G2_CAP, f0, KQ0, h0, h1, MATH};
+    const int xs_b = cv.xs_b();
+    const int rows_b = cv.rows_b();
+    const int small_b = cv.small_b();
+    const int ldh = cv.ldh();          // padded H row (floats)
     // NOTE: LDS pointers are always derived arithmetically from `smem`.  Indexing an array of LDS
     // pointers with a runtime value makes the compiler lose the address space and emit FLAT loads,
     // whose s_waitcnt vmcnt(0) also waits for the in-flight DMA of the next stage.
     constexpr int LD0 = 16 * KQ0; // A0 row: F0 values zero-padded to whole 16-wide MFMA k blocks
-    float *H = reinterpret_cast<float *>(smem + rows_b + 2 * small_b);
+    float *H = reinterpret_cast<float *>(smem + rows_b + 2 * small_b); // (= smem + cv.h_off())
     float *A1 = H + G2_CAP * ldh;
     float *A0 = A1;
     // per-row aggregation record written by P0, read by P1: {byte offsets of the 4 inline neighbour rows in H}
@@ -336,10 +335,10 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
     // (8 lanes x 16 B per cycle, consecutive rows) then fall into distinct bank groups AND their addresses are
     // base + immediate -- the swizzle cost two VALU operations per read, and VALU issue is what this kernel
     // runs out of
-    const int lda1 = h0 + 4, prow_b = h0 * 2 + 16;
+    const int lda1 = h0 + 4, prow_b = h0 * 2 + 16; // (= cv.lda1(), cv.prow_b(), cv.plane_b(): spelt out here -- taken from the carve these two lines move the f16x3 deep variants' ISA)
     const int plane_b = G2_CAP * prow_b;
-    int4 *REC = reinterpret_cast<int4 *>(reinterpret_cast<char *>(A1) + (MATH ? 3 * plane_b : G2_CAP * lda1 * 4));
-    int32_t *stile = reinterpret_cast<int32_t *>(REC + 3 * G2_CAP);
+    int4 *REC = reinterpret_cast<int4 *>(reinterpret_cast<char *>(A1) + cv.a1_used_b());
+    int32_t *stile = reinterpret_cast<int32_t *>(REC + STACK_ROW_REC_Q * G2_CAP);
     int32_t *sgraph = stile + (G2_TCAP + 1);
     // (f16x3: "a reduced product of this workgroup gave a non-finite value" -- the last word of the first SMALL buffer's slack:
     // the DMA writes 65 of its 68 graph-boundary words)
@@ -391,10 +390,10 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
         if (st.ta >= t1)
             return;
         dma_dwords_u(x + (size_t)st.nb * f0, smem, st.rows * f0, wave, lane, G2_NW);
-        const char *grec = reinterpret_cast<const char *>(node_rec + 2 * (size_t)st.nb);
-        const int rbytes = st.rows * 32;
-        if (wave * 1024 + lane * 16 < rbytes) // <= 64 rows * 32 B = 2 KiB: waves 0 and 1
-            dma16_to_lds_u(grec + wave * 1024 + lane * 16, smem + xs_b + wave * 1024);
+        const char *grec = reinterpret_cast<const char *>(node_rec + STACK_NODE_REC_Q * (size_t)st.nb);
+        const int rbytes = st.rows * STACK_NODE_REC_B;
+        if (wave * STACK_REC_DMA_B + lane * 16 < rbytes) // <= 64 rows * 32 B = 2 KiB: waves 0 and 1
+            dma16_to_lds_u(grec + wave * STACK_REC_DMA_B + lane * 16, smem + xs_b + wave * STACK_REC_DMA_B);
     };
     // its normalisers and graph boundaries -> small buffer bb: at the top of the stage before
     auto issue_small = [&](const G2Stage &st, int bb, int lane, int wave) {
@@ -407,7 +406,7 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
             dma4_to_lds_u(dinv + st.nb + lane, base);
         // graph boundaries of the stage for the pooling phase (first 64 graphs; more only if empty
         // graphs pile up, those are read from global memory)
-        const int ng = min(st.gb - st.ga, 64) + 1;
+        const int ng = min(st.gb - st.ga, STACK_GRAPH_WIN) + 1;
         if (wave == 3 && lane < ng)
             dma4_to_lds_u(node_ptr + st.ga + lane, base + G2_CAP * 4);
         if (wave == 4 && lane + 64 < ng)
@@ -567,7 +566,7 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
             const int i = tv >> 3, l8 = tv & 7;
             const bool active = i < rows;
             const int ic = active ? i : 0;
-            const int4 r0 = srec[2 * ic], r1 = srec[2 * ic + 1];
+            const int4 r0 = srec[STACK_NODE_REC_Q * ic], r1 = srec[STACK_NODE_REC_Q * ic + 1];
             const int deg = r0.y;
             const int jl[4] = {r0.z - nb, r0.w - nb, r1.x - nb, r1.y - nb};
             const float di = GIN ? 1.0f : sdinv[ic];
@@ -616,9 +615,9 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
                     A0[i * LD0 + f] = f < f0 ? acc[t] + xself[t] * (GIN ? 1.0f + gin_eps : di * di) : 0.0f;
                 }
                 if (l8 == 0) { // the row's scalars, computed once here instead of by every lane of P1's lane group
-                    REC[3 * i] = make_int4(jl[0] * ldh * 4, jl[1] * ldh * 4, jl[2] * ldh * 4, jl[3] * ldh * 4);
-                    REC[3 * i + 1] = make_int4(__float_as_int(c[0]), __float_as_int(c[1]), __float_as_int(c[2]), __float_as_int(c[3]));
-                    REC[3 * i + 2] = make_int4(__float_as_int(GIN ? 1.0f + gin_eps : di * di), r0.x, deg, __float_as_int(di));
+                    REC[STACK_ROW_REC_Q * i] = make_int4(jl[0] * ldh * 4, jl[1] * ldh * 4, jl[2] * ldh * 4, jl[3] * ldh * 4);
+                    REC[STACK_ROW_REC_Q * i + 1] = make_int4(__float_as_int(c[0]), __float_as_int(c[1]), __float_as_int(c[2]), __float_as_int(c[3]));
+                    REC[STACK_ROW_REC_Q * i + 2] = make_int4(__float_as_int(GIN ? 1.0f + gin_eps : di * di), r0.x, deg, __float_as_int(di));
                 }
             }
         }
@@ -737,9 +736,9 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
             const char *Hl = reinterpret_cast<const char *>(H) + gl * 16; // this lane's chunk of row 0
             int4 ra = make_int4(0, 0, 0, 0), rc = ra, rd = ra;
             if (grp < rows) {
-                ra = REC[3 * grp];
-                rc = REC[3 * grp + 1];
-                rd = REC[3 * grp + 2];
+                ra = REC[STACK_ROW_REC_Q * grp];
+                rc = REC[STACK_ROW_REC_Q * grp + 1];
+                rd = REC[STACK_ROW_REC_Q * grp + 2];
             }
             // (at most G2_UNITS passes: groups >= 16; fixed-count loop, no derived trip count)
 #pragma unroll 1
@@ -750,9 +749,9 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
                 const int rN = rA + groups;
                 const int4 ja = ra, ca = rc, da = rd;
                 if (rN < rows) {
-                    ra = REC[3 * rN];
-                    rc = REC[3 * rN + 1];
-                    rd = REC[3 * rN + 2];
+                    ra = REC[STACK_ROW_REC_Q * rN];
+                    rc = REC[STACK_ROW_REC_Q * rN + 1];
+                    rd = REC[STACK_ROW_REC_Q * rN + 2];
                 }
                 const V n0 = V::load(reinterpret_cast<const float *>(Hl + ja.x)); // unused slots alias the row itself (coefficient 0)
                 const V n1 = V::load(reinterpret_cast<const float *>(Hl + ja.y));
@@ -965,7 +964,7 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
                 };
                 // two loops, not one with a choice inside: a select between the LDS table and global
                 // memory is if-converted into flat loads (+ a full vmcnt/lgkmcnt drain per graph)
-                const int nlds = min(ngr, 64);
+                const int nlds = min(ngr, STACK_GRAPH_WIN);
                 for (int gi = 0; gi < nlds; gi++)
                     pool_graph(gi, sgp[gi], sgp[gi + 1]);
                 for (int gi = nlds; gi < ngr; gi++) // a pile of empty graphs
@@ -1013,24 +1012,15 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
 #endif
 }
 
+// what graph prep asks about the kernel (gnnb_stack_plan.h: the constants the launcher's plan and grid use)
 // node tiles the fused stack can walk in one launch: every resident workgroup keeps its run of the tile table in LDS
 // (graph prep coarsens the tiles of very large batches against this, so that they stay on the fused path)
-int gcn2_fused_tile_window() { return G2_TCAP - 1; }
-int gcn2_fused_grid(int num_tiles)
-{
-    const long long g = std::min<long long>(2LL * device_cu_count(), num_tiles);
-    return (int)std::max<long long>(g, 1);
-}
+long gcn2_fused_tile_capacity() { return g2_tile_capacity_of(device_cu_count()); }
+int gcn2_fused_grid(int num_tiles) { return g2_grid_of(num_tiles, device_cu_count()); }
+int gcn2_fused_tile_window() { return G2_RUN_TILES; }
 
-long gcn2_fused_tile_capacity()
-{
-    int devid = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&devid) == hipSuccess && hipGetDeviceProperties(&prop, devid) == hipSuccess)
-        cus = prop.multiProcessorCount;
-    return (long)(G2_TCAP - 2) * 2 * cus;
-}
-
+// read the options and the operands, plan (plan_gcn2_fused, gnnb_stack_plan.h: the decision table is there), pick the
+// instantiation, launch
 hipError_t launch_gcn2_fused(const BatchTables &t, const float *x, int f0, const float *w0, const float *b0,
                              int h0, const float *w1, const float *b1, int h1, int act,
                              const int32_t *pools, int num_pools, float *pooled, hipStream_t s, const G2Deep &deep)
@@ -1038,83 +1028,46 @@ hipError_t launch_gcn2_fused(const BatchTables &t, const float *x, int f0, const
     const Options &o = options();
     if (!o.fuse_gcn2 || t.num_nodes <= 0)
         return hipErrorNotSupported;
-    // more than two layers: fp32 mode only, middle weights 16-B aligned (float4 slice loads)
-    // (the opt-in bf16x6 math mode exists for the plain two-layer GCN form only: deeper GCN stacks and GIN stacks run their
-    // fp32 kernel in either mode -- the mode may never make a model slower by sending it down the layer-by-layer path)
-    if (deep.nl < 2 || (deep.nl > 2 && (!deep.wmid || (((uintptr_t)deep.wmid) & 15) || (deep.mid_stride & 3))))
+    const bool mid_ok = deep.wmid && !(((uintptr_t)deep.wmid) & 15) && !(deep.mid_stride & 3); // (float4 slice loads)
+    const G2Plan p = plan_gcn2_fused(G2PlanIn{f0, h0, h1, act, deep.nl, deep.gin, launch_math(), t.max_graph_nodes_hint, t.tile_rows,
+                                              mid_ok, deep.bmid != nullptr, stack_operands_aligned(x, w1, pooled, nullptr)});
+    if (!p.ok)
         return hipErrorNotSupported;
-    // GIN stacks: fp32 mode, out <= hidden (the wide matrices come hidden x hidden, zero-padded: gnnb_model_create), biases present
-    if (deep.gin && (h1 > h0 || !deep.wmid || !deep.bmid || (((uintptr_t)deep.wmid) & 15) || (deep.mid_stride & 3)))
-        return hipErrorNotSupported;
-    const int math = (launch_math() && deep.nl == 2 && !deep.gin) ? 1 : 0;
-    const int cap = 16 * g2_units(math);
-    if (t.max_graph_nodes_hint <= 0 || t.max_graph_nodes_hint + t.tile_rows - 1 > cap)
-        return hipErrorNotSupported; // no promise that whole graphs fit a stage
-    if (f0 < 1 || f0 > 32 || !(h0 == 32 || h0 == 64 || h0 == 128) || h1 < 4 || h1 > 128 || (h1 & 3))
-        return hipErrorNotSupported;
-    if ((((uintptr_t)w1) & 15) || (((uintptr_t)pooled) & 15) || (((uintptr_t)x) & 3))
-        return hipErrorNotSupported;
-    // every stage must hold at least one tile: workgroups need ceil(T / grid) + 1 <= G2_TCAP table entries
-    // (LDS carve: see the kernel)
-    const int xs_b = ((cap * f0 * 4) + 15) & ~15;
-    const int rows_b = xs_b + cap * 32, small_b = cap * 4 + 272;
-    const int ldh = (h0 > h1 ? h0 : h1) + 4;
-    const size_t a1_b = std::max((size_t)cap * (math ? 3 * (h0 * 2 + 16) : (h0 + 4) * 4), (size_t)cap * 16 * (f0 <= 16 ? 1 : 2) * 4);
-    const size_t lds = (size_t)rows_b + 2 * (size_t)small_b + (size_t)cap * ldh * 4 + a1_b + (size_t)cap * 48 +
-                       2 * (size_t)(G2_TCAP + 1) * 4;
-    const int kq0 = f0 <= 16 ? 1 : 2, kq1 = h0 / 16;
-    const int p0 = pools[0], p1 = num_pools > 1 ? pools[1] : 0, p2 = num_pools > 2 ? pools[2] : 0;
+    const StackPools pl(pools, num_pools);
     hipError_t rc = hipErrorNotSupported;
     auto go2 = [&](auto atag, auto q0tag, auto q1tag, auto mtag, auto dtag, auto h3tag) {
         constexpr int ACT = decltype(atag)::value, KQ0 = decltype(q0tag)::value, KQ1 = decltype(q1tag)::value;
         constexpr int MATH = decltype(mtag)::value;
         constexpr bool DEEP = decltype(dtag)::value != 0, GIN = decltype(dtag)::value == 2, H3 = decltype(h3tag)::value != 0;
         auto kern = k_gcn2_fused<ACT, KQ0, KQ1, MATH, DEEP, GIN, H3>;
-        if (ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds) != hipSuccess) {
-            rc = hipErrorNotSupported;
+        if (ensure_dynamic_lds(reinterpret_cast<const void *>(kern), p.lds) != hipSuccess)
             return;
-        }
-        static size_t lds_set = 0; // (occupancy of this instantiation at this LDS size: the same on every MI355X of a node)
-        static int blocks = 0, cus = 256;
-        if (lds_set != lds) {
-            int nb = 0, devid = 0;
-            hipDeviceProp_t prop;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, G2_WG, lds) != hipSuccess || nb < 1)
-                nb = 1;
-            if (hipGetDevice(&devid) == hipSuccess && hipGetDeviceProperties(&prop, devid) == hipSuccess)
-                cus = prop.multiProcessorCount;
-            blocks = nb > 2 ? 2 : nb;
-            lds_set = lds;
-        }
-        long long grid = (long long)cus * blocks;
-        if (grid > t.num_tiles)
-            grid = t.num_tiles;
-        const long long min_grid = ((long long)t.num_tiles + G2_TCAP - 2) / (G2_TCAP - 1);
-        if (grid < min_grid) {
-            rc = hipErrorNotSupported;
+        const Occupancy occ = kernel_occupancy(reinterpret_cast<const void *>(kern), G2_WG, p.lds, G2_WG_PER_CU);
+        // every stage must hold at least one tile: workgroups need ceil(T / grid) + 1 <= G2_TCAP table entries
+        const StackGrid g = stack_grid(t.num_tiles, G2_RUN_TILES, occ.cus, occ.blocks);
+        if (!g.ok)
             return;
-        }
         // (graph prep's stage cuts, when they were made for exactly this grid)
-        const int32_t *cut = (t.stage_cut && t.stage_cut_n == (int)grid) ? t.stage_cut : nullptr;
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G2_WG), lds, s, x, f0, t.node_rec, t.col, t.dinv,
-                           t.tile_first, t.tile_graph, t.graph_ptr, t.num_tiles, t.num_graphs, t.num_nodes, w0, b0, h0, w1, b1, h1, p0, p1, p2,
+        const int32_t *cut = (t.stage_cut && t.stage_cut_n == (int)g.grid) ? t.stage_cut : nullptr;
+        hipLaunchKernelGGL(kern, dim3((unsigned)g.grid), dim3(G2_WG), p.lds, s, x, f0, t.node_rec, t.col, t.dinv,
+                           t.tile_first, t.tile_graph, t.graph_ptr, t.num_tiles, t.num_graphs, t.num_nodes, w0, b0, h0, w1, b1, h1, pl.p0, pl.p1, pl.p2,
                            num_pools, pooled, deep.nl, deep.wmid, deep.bmid, deep.mid_stride, deep.bmid_stride, deep.skip, deep.eps, cut, t.err, t.err_host_dev);
         rc = hipGetLastError();
     };
-    auto go = [&](auto atag, auto q0tag, auto q1tag) {
-        const bool h3 = launch_math() == 3; // (opt-in f16x3, REDUCED precision: the GIN and deep variants)
-        if (deep.gin && h3)
+    [[maybe_unused]] auto go = [&](auto atag, auto q0tag, auto q1tag) {
+        if (p.variant == 2 && p.h3) // (opt-in f16x3, REDUCED precision: the GIN and deep variants)
             go2(atag, q0tag, q1tag, IntTag<0>{}, IntTag<2>{}, IntTag<1>{});
-        else if (deep.gin)
+        else if (p.variant == 2)
             go2(atag, q0tag, q1tag, IntTag<0>{}, IntTag<2>{}, IntTag<0>{});
-        else if (math)
+        else if (p.math)
             go2(atag, q0tag, q1tag, IntTag<1>{}, IntTag<0>{}, IntTag<0>{});
-        else if (deep.nl > 2) {
+        else if (p.variant == 1) {
             // (the deep variants have no register to spare -- GELU 125 of 128 in fp32, its f16x3 form spilled one; with the reduced
             // mode's overflow probe, round 6, the sigmoid / tanh forms at hidden 128 spill one too --: at hidden 128 only ReLU stacks
-            // take f16x3, the others keep fp32 in the mode, which is never less accurate; narrower stacks have registers to spare)
-            if constexpr (decltype(atag)::value == GNNB_ACT_RELU || (decltype(atag)::value != GNNB_ACT_GELU && decltype(q1tag)::value < 8)) {
-                if (h3) {
+            // take f16x3, the others keep fp32 in the mode, which is never less accurate; narrower stacks have registers to spare:
+            // g2_deep_takes_h3, which the plan's h3 went through as well)
+            if constexpr (g2_deep_takes_h3(decltype(atag)::value, decltype(q1tag)::value)) {
+                if (p.h3) {
                     go2(atag, q0tag, q1tag, IntTag<0>{}, IntTag<1>{}, IntTag<1>{});
                     return;
                 }
@@ -1124,23 +1077,15 @@ hipError_t launch_gcn2_fused(const BatchTables &t, const float *x, int f0, const
         else
             go2(atag, q0tag, q1tag, IntTag<0>{}, IntTag<0>{}, IntTag<0>{});
     };
-    auto go_q = [&](auto atag) {
-        if (kq0 == 1 && kq1 == 8) go(atag, IntTag<1>{}, IntTag<8>{});
-        else if (kq0 == 1 && kq1 == 4) go(atag, IntTag<1>{}, IntTag<4>{});
-        else if (kq0 == 1 && kq1 == 2) go(atag, IntTag<1>{}, IntTag<2>{});
-        else if (kq0 == 2 && kq1 == 8) go(atag, IntTag<2>{}, IntTag<8>{});
-        else if (kq0 == 2 && kq1 == 4) go(atag, IntTag<2>{}, IntTag<4>{});
-        else go(atag, IntTag<2>{}, IntTag<2>{});
-    };
 #ifdef GNNB_DEV_FAST // development builds: only the BASELINE config 2 / 3 instantiations (seconds instead of minutes to compile)
-    if (act == GNNB_ACT_RELU && kq0 == 1 && kq1 == 8 && !deep.gin && !math && deep.nl == 2)
+    if (act == GNNB_ACT_RELU && p.kq0 == 1 && p.kq1 == 8 && p.variant == 0 && !p.math)
         go2(IntTag<GNNB_ACT_RELU>{}, IntTag<1>{}, IntTag<8>{}, IntTag<0>{}, IntTag<0>{}, IntTag<0>{});
-    else if (act == GNNB_ACT_RELU && kq0 == 1 && kq1 == 8 && deep.gin && launch_math() == 3)
+    else if (act == GNNB_ACT_RELU && p.kq0 == 1 && p.kq1 == 8 && p.variant == 2 && p.h3)
         go2(IntTag<GNNB_ACT_RELU>{}, IntTag<1>{}, IntTag<8>{}, IntTag<0>{}, IntTag<2>{}, IntTag<1>{});
-    else if (act == GNNB_ACT_RELU && kq0 == 1 && kq1 == 8 && deep.gin)
+    else if (act == GNNB_ACT_RELU && p.kq0 == 1 && p.kq1 == 8 && p.variant == 2)
         go2(IntTag<GNNB_ACT_RELU>{}, IntTag<1>{}, IntTag<8>{}, IntTag<0>{}, IntTag<2>{}, IntTag<0>{});
 #else
-    GNNB_DISPATCH_ACT(act, go_q)
+    GNNB_DISPATCH_ACT(act, [&](auto atag) { stack_dispatch_kq(p.kq0, p.kq1, atag, go); })
 #endif
     return rc;
 }

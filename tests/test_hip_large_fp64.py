@@ -238,7 +238,7 @@ def _pool32(x, batch, p):
 
 # --------------------------------------------------------------------------- whole forwards past 2^23 nodes (controls)
 # (conv, hidden, layers, max_graph_nodes promise, route): the stack kernels keep a workgroup's run of the tile table on chip
-# (k_stack_zf.hip ZF_TCAP, gnnb_stack.h G2_TCAP: test_stack_at_its_tile_capacity); past that they decline
+# (gnnb_stack_plan.h ZF_TCAP, G2_TCAP: test_stack_at_its_tile_capacity); past that they decline
 # before anything is enqueued and the forward runs layer by layer -- which must then be right too
 FORWARDS = [("gcn", 128, 2, 29, "layerwise"), ("gin", 128, 3, 29, "layerwise"), ("gcn", 100, 2, 0, "layerwise"), ("sage", 100, 2, 0, "layerwise")]
 
@@ -254,8 +254,8 @@ def test_forward_past_2_23_nodes(conv, hidden, layers, promise, want, big_batch)
 
 
 def _stack_candidates(conv):
-    """Batch sizes at the stack kernels' tile capacity on this device, largest first (gnnb_runtime.hip graph prep; k_stack_zf.hip
-    ZF_TCAP; k_stack.hip G2_TCAP).  Promise 29, in_dim 11: k_gcn2_zf takes its 176-row stages and 128-row tiles, at most 62
+    """Batch sizes at the stack kernels' tile capacity on this device, largest first (gnnb_runtime.hip graph prep;
+    gnnb_stack_plan.h ZF_TCAP, G2_TCAP).  Promise 29, in_dim 11: k_gcn2_zf takes its 176-row stages and 128-row tiles, at most 62
     tiles per workgroup and one workgroup per CU; k_gcn2_fused 32-row tiles, at most 63 per workgroup, one or two workgroups
     per CU (its occupancy) -- both are tried, the larger first."""
     cus = torch.cuda.get_device_properties(0).multi_processor_count

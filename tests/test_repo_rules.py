@@ -62,9 +62,9 @@ def test_every_unit_is_built_and_the_probe_build_follows_the_unit_list():
 def test_kernel_sources_carry_no_build_switches_beyond_the_named_ones():
     """Measured-and-dropped alternatives are deleted, not kept behind -D switches (DESIGN 8 keeps their results): the only names
     that #if / #ifdef / #ifndef / #elif may test in csrc/ are the diagnostic and development builds' (the probe library, the ISA
-    table's marks, the phase-skip build of k_gcn2_zf, the one-instantiation build), the two that make k_stack_zf.hip a second
-    translation unit, and a header's own include guard (`#ifndef X` followed by `#define X` at its top)."""
-    allowed = {"GNNB_PROBE", "GNNB_ZF_MARK", "GNNB_ZF_ABLATE", "GNNB_DEV_FAST", "ZF_TU_HEAD", "GNNB_ZF_KERNEL_DEFINED"}
+    table's marks, the phase-skip build of k_gcn2_zf, the one-instantiation build) and a header's own include guard (`#ifndef X`
+    followed by `#define X` at its top)."""
+    allowed = {"GNNB_PROBE", "GNNB_ZF_MARK", "GNNB_ZF_ABLATE", "GNNB_DEV_FAST"}
     csrc = ROOT / "gnn-builder_amd" / "csrc"
     files = sorted(csrc.glob("*.hip")) + sorted(csrc.glob("*.h"))
     assert len(files) > 10

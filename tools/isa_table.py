@@ -2,7 +2,7 @@
 """Static instruction table of one kernel instantiation, per phase, read from the gfx950 ISA.
 
 Compiles a translation unit of gnn-builder_amd/csrc to device assembly (hipcc -S, --cuda-device-only) with
--DGNNB_ZF_MARK, which turns the kernel's phase stamps (ZF_PT(i) in k_stack_zf.hip) into `; ZFMARK i` comments, cuts the
+-DGNNB_ZF_MARK, which turns the kernel's phase stamps (ZF_PT(i) in k_stack_zf.h) into `; ZFMARK i` comments, cuts the
 kernel's text at those comments and at its labels, and counts per region and per basic block: MFMA, other VALU, SALU,
 LDS, VMEM, SMEM, waits / barriers, branches.  Loops are reported with their back edge so that a region's dynamic count
 can be formed as  sum(block count x trips).  No GPU needed.  ("build the per-phase static
