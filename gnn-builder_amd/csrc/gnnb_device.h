@@ -34,6 +34,15 @@ static hipError_t ensure_dynamic_lds(const void *kern, size_t lds)
     return e;
 }
 
+// lanes per row as a power of two: the smallest g >= lo with 2^g >= nvec, at most 6 (a wave)
+constexpr int lane_group_log2(int nvec, int lo = 0)
+{
+    int g = lo;
+    while ((1 << g) < nvec && g < 6)
+        g++;
+    return g;
+}
+
 // CUs of the CURRENT device (cached per device under a lock: a process may drive several GPUs; inline: one map for the library)
 inline int device_cu_count()
 {

@@ -1,6 +1,7 @@
 // k_aggregate.hip -- gather -> segmented reduce per destination row (HBM bound: the roofline kernel)
 // Part of libgnnb_hip.so (hand-written gfx950 / CDNA4 kernels of the GNNBuilder hot path); wavefront = 64 lanes.
 #include "gnnb_device.h"
+#include "gnnb_stage.h"
 
 namespace gnnb {
 
@@ -302,7 +303,29 @@ __device__ inline void agg_row_direct(int node, const float *__restrict__ x, con
 // flight from the first microsecond; bigger batches cycle the ring.  A tile that does not fit a stage (one very large
 // graph) is reduced straight from global memory.  Forms measured and dropped this round: a short-lived
 // workgroup per tile group (round 1's default), one ring per wave.
-static constexpr int RING_MAX_SLOTS = 4;
+// The slot's carve (RingCarve), RING_MAX_SLOTS and what the launcher decides (plan_aggregate_ring): gnnb_stage.h
+// The kernel keeps ITS spelling of the carve's offsets (taken from RingCarve they moved the machine code).  The lines are a macro
+// so that the check below expands the very same text: a drift on either side fails the build.
+#define RING_OWN_OFFSETS(cap, w, HASQ, HASGC)                      \
+    const int off_q = cap * w * 4;                                 \
+    const int off_rec = off_q + (HASQ ? cap * w * 4 : 0);          \
+    const int off_dinv = off_rec + cap * 32;                       \
+    const int off_gc = off_dinv + ((cap * 4 + 15) & ~15);          \
+    const int off_col = off_gc + (HASGC ? cap * 16 : 0); /* the stage's CSR slice (rows of degree > 4 read it): ecap entries */
+template <bool HASQ, bool HASGC>
+constexpr bool ring_own_offsets_match()
+{
+    for (int w = 1; w <= 512; w++)
+        for (int cap = 1; cap <= 4096; cap = cap * 3 + 1) {
+            RING_OWN_OFFSETS(cap, w, HASQ, HASGC)
+            const RingCarve cv{cap, w, HASQ, true, HASGC};
+            if (off_q != cv.off_q() || off_rec != cv.off_rec() || off_dinv != cv.off_dinv() || off_gc != cv.off_gc() || off_col != cv.off_col())
+                return false;
+        }
+    return true;
+}
+static_assert(ring_own_offsets_match<false, false>() && ring_own_offsets_match<false, true>() && ring_own_offsets_match<true, false>(),
+              "k_aggregate_ring's offsets are not RingCarve's");
 
 // Diagnostic build: wave 0 of every workgroup logs wall-clock stamps of its stage events (100 MHz ticks)
 #ifdef GNNB_PROBE
@@ -369,11 +392,7 @@ __global__ __launch_bounds__(1024) void k_aggregate_ring(
         g_probe[blockIdx.x * 64] = wall_clock64();
 #endif
     char *wbase = smem;
-    const int off_q = cap * w * 4;
-    const int off_rec = off_q + (HASQ ? cap * w * 4 : 0);
-    const int off_dinv = off_rec + cap * 32;
-    const int off_gc = off_dinv + ((cap * 4 + 15) & ~15);
-    const int off_col = off_gc + (HASGC ? cap * 16 : 0); // the stage's CSR slice (rows of degree > 4 read it): ecap entries
+    RING_OWN_OFFSETS(cap, w, HASQ, HASGC)
     const int nvec = w / VEC;
     const int G = 1 << glog2;       // lanes per destination row
     const int groups = 64 >> glog2; // rows a wave reduces at once
@@ -590,51 +609,24 @@ static hipError_t launch_aggregate_ring_t(const BatchTables &t, const float *x, 
                                           float *out, int w, float eps, hipStream_t s)
 {
     const Options &o = options();
-    const int tile_lo = std::min(std::max(t.tile_lo, 0), t.num_tiles);
-    if (t.num_tiles - tile_lo <= 0)
+    const RingPlan p = plan_aggregate_ring({MODE, VEC, w, t.num_tiles, t.tile_lo, t.tile_rows, device_cu_count(), (int)o.agg_ring_wg_per_cu,
+                                            (int)o.agg_lds_kb, (int)o.agg_ring_slots, (int)o.agg_ring_waves, (int)o.agg_balance,
+                                            (int)o.agg_nt_store, t.agg_cut != nullptr, t.agg_cut_n});
+    if (p.empty)
         return hipSuccess;
-    const int nvec = w / VEC;
-    int glog2 = 0;
-    while ((1 << glog2) < nvec && glog2 < 6)
-        glog2++;
-    const int num_cus = device_cu_count();
-    // per staged row: the row itself (PNA: p and q), its 32-B record, its normaliser, and 4 CSR entries (a stage
-    // whose CSR slice is longer than 4 per row -- multigraphs, hubs -- is cut shorter by the planner)
-    constexpr int ECAP_PER_ROW = 4;
-    const size_t per_row = (size_t)w * 4 * (MODE == GNNB_AGG_PNA ? 2 : 1) + (MODE != GNNB_AGG_COPY ? 32 + 4 + 4 * ECAP_PER_ROW : 0) +
-                           (MODE == GNNB_AGG_GCN && VEC == 4 ? 16 : 0);
-    const int wgs = std::max((int)o.agg_ring_wg_per_cu, 1);
-    const size_t budget = (size_t)(o.agg_lds_kb > 0 ? std::min(std::max((int)o.agg_lds_kb, 8), 158) : 158 / wgs) * 1024;
-    int ns = std::min(std::max((int)o.agg_ring_slots, 1), RING_MAX_SLOTS);
-    int nw = o.agg_ring_waves;
-    // one ring per workgroup: stages as large as the budget allows
-    if (nw <= 0)
-        nw = 16; // (measured: 16 waves issue a stage's DMA and drain its stores faster than 8)
-    nw = std::min(std::max(nw, 1), 16);
-    int cap = (int)((budget / ns) / per_row);
-    cap = std::min(std::max(cap, 1), 4096);
-    const int slot_bytes = (int)((((size_t)cap * per_row) + 31) & ~(size_t)15); // (+ 16: the normalisers are padded to 16 B)
-    const size_t lds = (size_t)ns * slot_bytes;
-    // persistent: `wgs` workgroups per CU; fewer when the batch has fewer tiles than rings
-    int grid = num_cus * wgs;
-    grid = std::min(grid, t.num_tiles - tile_lo);
-    if (grid < 1)
-        grid = 1;
-    // graph prep's row-balanced ranges, when they were made for exactly this grid
-    const int4 *cut = (o.agg_balance && tile_lo == 0 && t.agg_cut && t.agg_cut_n == grid) ? t.agg_cut : nullptr;
+    const int4 *cut = p.use_cut ? t.agg_cut : nullptr;
     auto launch = [&](auto kern) -> hipError_t {
         {
-            hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
+            hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), p.lds);
             if (e != hipSuccess)
                 return e;
         }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, s, x, selfq, out, t.node_rec, t.col, t.dinv,
-                           t.tile_first, t.tile_edge, t.num_tiles, t.num_nodes, t.num_edges, w, glog2, cap,
-                           cap * ECAP_PER_ROW, ns, slot_bytes, std::max(t.tile_rows / 2, 1) + 2, eps, tile_lo, t.gcoef, cut,
-                           std::max(t.tile_rows, 1));
+        hipLaunchKernelGGL(kern, dim3(p.grid), dim3(64 * p.nw), p.lds, s, x, selfq, out, t.node_rec, t.col, t.dinv,
+                           t.tile_first, t.tile_edge, t.num_tiles, t.num_nodes, t.num_edges, w, p.glog2, p.cap,
+                           p.ecap, p.ns, p.slot_bytes, p.slack, eps, p.tile_lo, t.gcoef, cut, p.tile_rows);
         return hipGetLastError();
     };
-    if (o.agg_nt_store)
+    if (p.nt)
         return launch(k_aggregate_ring<MODE, VEC, true>);
     return launch(k_aggregate_ring<MODE, VEC, false>);
 }
@@ -681,9 +673,7 @@ hipError_t launch_aggregate_edges(const BatchTables &t, const float *x, const fl
     const bool v4 = (width % 4 == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)out & 15) == 0) &&
                     (((uintptr_t)eterm & 15) == 0);
     const int nvec = v4 ? width / 4 : width;
-    int glog2 = 0;
-    while ((1 << glog2) < nvec && glog2 < 6)
-        glog2++;
+    const int glog2 = lane_group_log2(nvec);
     const int groups = WG >> glog2;
     const int grid = (t.num_nodes + groups - 1) / groups;
     if (v4)

@@ -2,6 +2,7 @@
 // whole graphs staged in LDS, aggregate there, all output columns from one staged stage
 // Part of libgnnb_hip.so (hand-written gfx950 / CDNA4 kernels of the GNNBuilder hot path); wavefront = 64 lanes.
 #include "gnnb_stack.h"
+#include "gnnb_stage.h"
 
 namespace gnnb {
 
@@ -25,9 +26,10 @@ namespace gnnb {
 // Graphs larger than a stage (no max_graph_nodes promise on this path) are taken in pieces whose sources are read from
 // global memory (L2) instead of LDS -- same arithmetic, same order.
 // Sums run in CSR order with the self term last, as k_aggregate_ring and the reference do.
-static constexpr int F1_NW = 8, F1_WG = F1_NW * 64, F1_CAP = 128, F1_ECAP = 8 * F1_CAP; // rows / CSR entries per stage
+// The tile-table window, the carve (F1Carve, F1_CAP rows / F1_ECAP CSR entries per stage) and the launch plan: gnnb_stage.h
+static constexpr int F1_NW = STAGE_NW, F1_WG = STAGE_WG;
 
-struct F1Stage {
+struct F1Stage { // (Stage of gnnb_stage.h + direct, next_row)
     int ok, nb, rows, e0, ne, direct, next_t, next_row; // direct: the piece's sources are read from global memory
 };
 
@@ -42,24 +44,21 @@ __global__ __launch_bounds__(F1_WG, 2) void k_conv_first(
     constexpr int LD0 = 16 * KQ + 4; // A0 row (floats), padded: conflict-free fragment reads
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
-    // ---- LDS carve: two input buffers {x rows | records | dinv | CSR slice}, one A0
-    const int xs_b = ((F1_CAP * F * 4) + 15) & ~15;
-    const int rec_o = xs_b, dinv_o = rec_o + F1_CAP * 32, col_o = dinv_o + F1_CAP * 4, in_b = col_o + F1_ECAP * 4;
+    // ---- LDS carve (F1Carve): two input buffers {x rows | records | dinv | CSR slice}, one A0
+    const F1Carve cv{F, KQ};
+    const int rec_o = cv.rec_o(), dinv_o = cv.dinv_o(), col_o = cv.col_o(), in_b = cv.in_b();
     float *A0 = reinterpret_cast<float *>(smem + 2 * (size_t)in_b);
     // per-wave scratch for the output transpose: 16 rows x 32 columns (+ 4 floats of padding per row)
     float *ST = A0 + F1_CAP * LD0 + wave * (16 * 36);
 
-    int t0, t1;
-
+    int t0, t1, tf, te;
     run_cuts(blockIdx.x, gridDim.x, (unsigned)num_tiles, t0, t1); // (32-bit: gnnb_device.h)
     if (t1 <= t0)
         return;
-    // window of the tile table in registers: lane l holds tile t0 + l (the launcher keeps runs below 64 tiles)
-    const int ti = min(t0 + min(lane, t1 - t0), num_tiles);
-    const int tf = min(max(tile_first[ti], 0), N), te = min(max(tile_edge[ti], 0), E);
+    stage_window(tile_first, tile_edge, num_tiles, N, E, lane, t0, t1, tf, te);
 
-    // ---- stage plan: the longest run of whole tiles from tile `ts` that fits the stage (rows and CSR slice); a tile that does
-    // not fit alone -- one graph beyond the stage -- goes in direct pieces of F1_CAP rows
+    // ---- stage plan, the general form of stage_plan<CAP> (gnnb_stage.h): the longest run of whole tiles from tile `ts` that fits the
+    // stage (rows AND CSR slice); a tile that does not fit alone -- one graph beyond the stage -- goes in direct pieces of F1_CAP rows
     auto plan = [&](int ts, int row_at) {
         F1Stage st;
         st.ok = ts < t1 ? 1 : 0;
@@ -104,6 +103,7 @@ __global__ __launch_bounds__(F1_WG, 2) void k_conv_first(
         return st;
     };
     int vm = 0; // vector-memory instructions this wave has issued (DMA + stores): counted waits (VM operations retire in order)
+    // (the DMA loops keep their own spelling in every staged kernel: as shared inline functions they moved the machine code)
     auto issue = [&](const F1Stage &st, int bb) {
         if (!st.ok || st.direct || st.rows <= 0)
             return;
@@ -142,6 +142,7 @@ __global__ __launch_bounds__(F1_WG, 2) void k_conv_first(
         cwl++;
     const int CW = 1 << cwl, RGN = F1_NW >> cwl;
     const int cw = wave & (CW - 1), rg = wave >> cwl;
+    // (own spelling, as k_sage_first_mean: as a shared inline function the loader moved the machine code)
     // weight slices -> registers: k step t of block q multiplies stage column 16 q + lg + 4 t (A0 is stored to match)
     float wr[2][KQ * 4];
 #pragma unroll
@@ -382,43 +383,32 @@ hipError_t launch_conv_first(const BatchTables &t, int agg_kind, float eps, cons
 {
     if (t.num_nodes <= 0)
         return hipSuccess;
-    if (!(agg_kind == GNNB_AGG_GCN || agg_kind == GNNB_AGG_SUM || agg_kind == GNNB_AGG_MEAN) || F < 1 || K > 32 || K < 1 ||
-        Nout < 1 || Nout > 256 || (cat > 0 && (cat != F || K != 2 * F || agg_kind != GNNB_AGG_MEAN)) || (cat == 0 && K != F) ||
-        t.tile_lo != 0 || (((uintptr_t)x) & 3))
+    const ConvFirstPlan p = plan_conv_first({agg_kind, F, K, Nout, cat, t.tile_lo, t.num_tiles, device_cu_count(), !(((uintptr_t)x) & 3)});
+    if (!p.ok)
         return hipErrorNotSupported;
-    const int kq = K <= 16 ? 1 : 2;
-    const int xs_b = ((F1_CAP * F * 4) + 15) & ~15;
-    const size_t in_b = (size_t)xs_b + F1_CAP * 32 + F1_CAP * 4 + F1_ECAP * 4;
-    const size_t lds = 2 * in_b + (size_t)F1_CAP * (16 * kq + 4) * 4 + (size_t)F1_NW * 16 * 36 * 4;
-    const int cus = device_cu_count();
-    long long grid = std::min<long long>(2LL * cus, t.num_tiles);
-    if (grid < 1)
-        grid = 1;
-    if ((t.num_tiles + grid - 1) / grid > 62) // a workgroup keeps its run of the tile table in one register per lane
-        grid = (t.num_tiles + 61) / 62;
     hipError_t rc = hipErrorNotSupported;
     auto go = [&](auto atag, auto qtag, auto mtag, auto ctag) {
         constexpr int ACT = decltype(atag)::value, KQ = decltype(qtag)::value, MODE = decltype(mtag)::value;
         constexpr bool CAT = decltype(ctag)::value != 0;
         auto kern = k_conv_first<ACT, KQ, MODE, CAT>;
-        if (ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds) != hipSuccess)
+        if (ensure_dynamic_lds(reinterpret_cast<const void *>(kern), p.lds) != hipSuccess)
             return;
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(F1_WG), lds, s, x, F, t.node_rec, t.col, t.dinv, t.tile_first, t.tile_edge,
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(F1_WG), p.lds, s, x, F, t.node_rec, t.col, t.dinv, t.tile_first, t.tile_edge,
                            t.num_tiles, t.num_nodes, t.num_edges, w, ldw, bias, K, Nout, eps, y);
         rc = hipGetLastError();
     };
     auto go_a = [&](auto atag) {
-        if (agg_kind == GNNB_AGG_GCN) {
-            if (kq == 1) go(atag, IntTag<1>{}, IntTag<GNNB_AGG_GCN>{}, IntTag<0>{});
+        if (p.mode == GNNB_AGG_GCN) {
+            if (p.kq == 1) go(atag, IntTag<1>{}, IntTag<GNNB_AGG_GCN>{}, IntTag<0>{});
             else go(atag, IntTag<2>{}, IntTag<GNNB_AGG_GCN>{}, IntTag<0>{});
-        } else if (agg_kind == GNNB_AGG_SUM) {
-            if (kq == 1) go(atag, IntTag<1>{}, IntTag<GNNB_AGG_SUM>{}, IntTag<0>{});
+        } else if (p.mode == GNNB_AGG_SUM) {
+            if (p.kq == 1) go(atag, IntTag<1>{}, IntTag<GNNB_AGG_SUM>{}, IntTag<0>{});
             else go(atag, IntTag<2>{}, IntTag<GNNB_AGG_SUM>{}, IntTag<0>{});
-        } else if (cat > 0) {
-            if (kq == 1) go(atag, IntTag<1>{}, IntTag<GNNB_AGG_MEAN>{}, IntTag<1>{});
+        } else if (p.cat) {
+            if (p.kq == 1) go(atag, IntTag<1>{}, IntTag<GNNB_AGG_MEAN>{}, IntTag<1>{});
             else go(atag, IntTag<2>{}, IntTag<GNNB_AGG_MEAN>{}, IntTag<1>{});
         } else {
-            if (kq == 1) go(atag, IntTag<1>{}, IntTag<GNNB_AGG_MEAN>{}, IntTag<0>{});
+            if (p.kq == 1) go(atag, IntTag<1>{}, IntTag<GNNB_AGG_MEAN>{}, IntTag<0>{});
             else go(atag, IntTag<2>{}, IntTag<GNNB_AGG_MEAN>{}, IntTag<0>{});
         }
     };

@@ -15,15 +15,13 @@
 //         16-B non-temporal stores, whole rows
 // Needs the max_graph_nodes promise (a graph must fit a stage: a source's output row exists only in LDS).  Same sums in the same
 // order as k_conv_first + k_aggregate_ring<MEAN> (bit-identical outputs).
+// The stage skeleton (tile-table window, stage planner), the carve and the launch plan: gnnb_stage.h
 #include "gnnb_stack.h"
+#include "gnnb_stage.h"
 
 namespace gnnb {
 
-static constexpr int FM_NW = 8, FM_WG = FM_NW * 64, FM_CAP = 56, FM_ECAP = 448;
-
-struct FmStage {
-    int ok, nb, rows, e0, ne, next_t;
-};
+static constexpr int FM_NW = STAGE_NW, FM_WG = STAGE_WG;
 
 template <int ACT, int KQ>
 __global__ __launch_bounds__(FM_WG, 2) void k_sage_first_mean(const float *__restrict__ x, int F, const int4 *__restrict__ node_rec,
@@ -37,46 +35,21 @@ __global__ __launch_bounds__(FM_WG, 2) void k_sage_first_mean(const float *__res
     const int LDY = Nout + 4;        // output-tile row (floats), padded
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
-    // ---- LDS carve: two input buffers {x rows | records | CSR slice}, A0, the output tile
-    const int xs_b = ((FM_CAP * F * 4) + 15) & ~15;
-    const int rec_o = xs_b, col_o = rec_o + FM_CAP * 32, in_b = col_o + FM_ECAP * 4;
+    // ---- LDS carve (FmCarve): two input buffers {x rows | records | CSR slice}, A0, the output tile
+    const FmCarve cv{F, KQ, Nout};
+    const int rec_o = cv.rec_o(), col_o = cv.col_o(), in_b = cv.in_b();
     float *A0 = reinterpret_cast<float *>(smem + 2 * (size_t)in_b);
     float *YT = A0 + FM_CAP * LD0;
 
-    int t0, t1;
-
+    int t0, t1, tf, te;
     run_cuts(blockIdx.x, gridDim.x, (unsigned)num_tiles, t0, t1); // (32-bit: gnnb_device.h)
     if (t1 <= t0)
         return;
-    // window of the tile table in registers: lane l holds tile t0 + l (the launcher keeps runs below 64 tiles); clamped: the
-    // tables of a malformed (flagged) batch may hold stale entries and must still stay in range
-    const int ti = min(t0 + min(lane, t1 - t0), num_tiles);
-    const int tf = min(max(tile_first[ti], 0), N), te = min(max(tile_edge[ti], 0), E);
-
-    auto plan = [&](int ts) {
-        FmStage st;
-        st.ok = ts < t1 ? 1 : 0;
-        st.nb = st.rows = st.e0 = st.ne = 0;
-        st.next_t = ts;
-        if (!st.ok)
-            return st;
-        const int rel = ts - t0;
-        const int nb = __builtin_amdgcn_readlane(tf, rel), e0 = __builtin_amdgcn_readlane(te, rel);
-        const unsigned long long fit = __ballot(lane > rel && lane <= t1 - t0 && tf - nb <= FM_CAP);
-        st.nb = nb;
-        st.e0 = e0;
-        int endl = rel + 1; // (nothing fits: the next tile alone, cut to the stage -- only if the max_graph_nodes promise is broken)
-        if (fit) {
-            const unsigned long long nofit = ~fit & (~0ull << (rel + 1));
-            endl = nofit ? __builtin_ctzll(nofit) - 1 : 63 - __builtin_clzll(fit);
-        }
-        st.rows = min(max(__builtin_amdgcn_readlane(tf, endl) - nb, 0), FM_CAP);
-        st.ne = max(__builtin_amdgcn_readlane(te, endl) - e0, 0);
-        st.next_t = t0 + endl;
-        return st;
-    };
+    stage_window(tile_first, tile_edge, num_tiles, N, E, lane, t0, t1, tf, te);
+    auto plan = [&](int ts) { return stage_plan<FM_CAP>(ts, t0, t1, lane, tf, te); };
     int vm = 0; // vector-memory instructions this wave has issued (DMA + stores): counted waits (VM operations retire in order)
-    auto issue = [&](const FmStage &st, int bb) {
+    // (the DMA loops keep their own spelling in every staged kernel: as shared inline functions they moved the machine code)
+    auto issue = [&](const Stage &st, int bb) {
         if (!st.ok || st.rows <= 0)
             return;
         char *base = smem + (size_t)bb * in_b;
@@ -95,10 +68,11 @@ __global__ __launch_bounds__(FM_WG, 2) void k_sage_first_mean(const float *__res
                     dma4_to_lds_u(col + st.e0 + c + lane, base + col_o + (size_t)c * 4);
     };
 
-    FmStage cur = plan(t0);
+    Stage cur = plan(t0);
     issue(cur, 0);
     int mark_cur = vm;
 
+    // (own spelling, as k_conv_first: as a shared inline function the loader moved the machine code)
     // ---- wave roles: NS slices of 16 output columns; a wave owns two ADJACENT slices (32 columns) for the units rg, rg + RGN, ...
     const int NS = (Nout + 15) >> 4;
     const int SPW = NS >= 2 ? 2 : 1;
@@ -153,11 +127,12 @@ __global__ __launch_bounds__(FM_WG, 2) void k_sage_first_mean(const float *__res
         // ---- the stage's inputs have landed (own share; then everybody's); everybody is done with A0, YT and the other buffer
         vmcnt_wait_n(min(vm - mark_cur, 63));
         g2_barrier();
-        const FmStage nxt = plan(cur.next_t);
+        const Stage nxt = plan(cur.next_t);
         issue(nxt, b ^ 1);
         const int mark_nxt = vm;
 
         // ---- P0: A0[i] = [mean_j x_j | x_i] in fragment order (k_conv_first's staged P0, MEAN + CAT)
+        // (not shared with it: here sources are clamped to the stage and a CSR slice past FM_ECAP is read from global memory)
         {
             constexpr int T0 = 2 * KQ; // columns per lane (16 KQ / 8)
             const float *xs = reinterpret_cast<const float *>(base);
@@ -311,41 +286,23 @@ hipError_t launch_sage_first_mean(const BatchTables &t, const float *x, int F, c
     if (t.num_nodes <= 0)
         return hipSuccess;
     const int K = 2 * F;
-    if (!options().sage_first_mean || F < 1 || K > 32 || !(Nout == 256 || Nout == 128 || Nout == 64) || t.tile_lo != 0 || (((uintptr_t)x) & 3))
+    const SageFirstMeanPlan p = plan_sage_first_mean({options().sage_first_mean != 0, F, Nout, t.tile_lo, t.num_tiles, device_cu_count(),
+                                                      !(((uintptr_t)x) & 3), !(((uintptr_t)y | (uintptr_t)mean_out) & 15),
+                                                      {t.max_graph_nodes_hint, t.tile_rows, t.promise_graphs, t.num_graphs, t.large_n}});
+    if (!p.ok)
         return hipErrorNotSupported;
-    if (t.max_graph_nodes_hint <= 0 || t.max_graph_nodes_hint + t.tile_rows - 1 > FM_CAP)
-        return hipErrorNotSupported; // whole graphs must fit a stage (validated on the device by graph prep: flag 8)
-    // a batch with a large segment: the promise covers graphs [0, promise_graphs) only and graph prep validates nothing about the
-    // rest -- those graphs need not fit a stage (round-5 advisor finding: they got clamped sources, unflagged): layer by layer
-    if (t.promise_graphs < t.num_graphs || t.large_n >= 0)
-        return hipErrorNotSupported;
-    if ((((uintptr_t)y | (uintptr_t)mean_out) & 15))
-        return hipErrorNotSupported;
-    const int kq = K <= 16 ? 1 : 2;
-    const int xs_b = ((FM_CAP * F * 4) + 15) & ~15;
-    const size_t in_b = (size_t)xs_b + FM_CAP * 32 + FM_ECAP * 4;
-    const size_t lds = 2 * in_b + (size_t)FM_CAP * (16 * kq + 4) * 4 + (size_t)FM_CAP * (Nout + 4) * 4;
-    int glog2 = 0;
-    while ((4 << glog2) < Nout)
-        glog2++;
-    const int cus = device_cu_count();
-    long long grid = std::min<long long>(2LL * cus, t.num_tiles);
-    if (grid < 1)
-        grid = 1;
-    if ((t.num_tiles + grid - 1) / grid > 62) // a workgroup keeps its run of the tile table in one register per lane
-        grid = (t.num_tiles + 61) / 62;
     hipError_t rc = hipErrorNotSupported;
     auto go = [&](auto atag, auto qtag) {
         constexpr int ACT = decltype(atag)::value, KQ = decltype(qtag)::value;
         auto kern = k_sage_first_mean<ACT, KQ>;
-        if (ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds) != hipSuccess)
+        if (ensure_dynamic_lds(reinterpret_cast<const void *>(kern), p.lds) != hipSuccess)
             return;
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(FM_WG), lds, s, x, F, t.node_rec, t.col, t.tile_first, t.tile_edge, t.num_tiles,
-                           t.num_nodes, t.num_edges, w, ldw, bias, K, Nout, glog2, y, mean_out);
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(FM_WG), p.lds, s, x, F, t.node_rec, t.col, t.tile_first, t.tile_edge, t.num_tiles,
+                           t.num_nodes, t.num_edges, w, ldw, bias, K, Nout, p.glog2, y, mean_out);
         rc = hipGetLastError();
     };
     auto go_a = [&](auto atag) {
-        if (kq == 1)
+        if (p.kq == 1)
             go(atag, IntTag<1>{});
         else
             go(atag, IntTag<2>{});

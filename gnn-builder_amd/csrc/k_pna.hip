@@ -22,15 +22,13 @@
 // Needs the max_graph_nodes promise (a graph must fit a stage: no
 // p row exists outside the chip) -- without it, and for the general form with its per-destination term, the layer keeps the
 // two-kernel route.  Same statistics in the same order as k_aggregate_ring<PNA>; the product's summation order is the MFMA's.
+// The stage skeleton (tile-table window, stage planner), the carve and the launch plan: gnnb_stage.h
 #include "gnnb_stack.h"
+#include "gnnb_stage.h"
 
 namespace gnnb {
 
-static constexpr int PA_NW = 8, PA_WG = PA_NW * 64, PA_CAP = 64, PA_ECAP = 512;
-
-struct PaStage {
-    int ok, nb, rows, e0, ne, next_t;
-};
+static constexpr int PA_NW = STAGE_NW, PA_WG = STAGE_WG;
 
 // MX = 2 ("f16x3", opt-in REDUCED precision: gnnb_set_option("math", 3)): the product on the fp16 matrix cores, hi + mid fp16
 // pieces of both operands, three products per 32-wide k block (k_stack_zf.h / gnnb_device.h).  The x rows arrive by DMA as
@@ -54,45 +52,23 @@ __global__ __launch_bounds__(PA_WG, 2) void k_pna_pagg(const float *__restrict__
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
-    // ---- LDS carve: two buffers {x rows, padded -> P | node records | CSR slice}
-    constexpr int xs_b = PA_CAP * LDX * 4, rec_o = xs_b, col_o = rec_o + PA_CAP * 32, in_b = col_o + PA_ECAP * 4;
+    // ---- LDS carve (PaCarve): two buffers {x rows, padded -> P | node records | CSR slice}
+    constexpr PaCarve cv{F};
+    constexpr int rec_o = cv.rec_o(), col_o = cv.col_o(), in_b = cv.in_b();
+    static_assert(cv.xs_b() == PA_CAP * LDX * 4, "the carve's rows are the kernel's padded rows");
 
-    int t0, t1;
-
+    int t0, t1, tf, te;
     run_cuts(blockIdx.x, gridDim.x, (unsigned)num_tiles, t0, t1); // (32-bit: gnnb_device.h)
     if (t1 <= t0)
         return;
-    // window of the tile table in registers: lane l holds tile t0 + l (the launcher keeps runs below 64 tiles)
-    // (clamped: the tables of a malformed batch may hold stale entries; a flagged batch must still stay in range)
-    const int ti = min(t0 + min(lane, t1 - t0), num_tiles);
-    const int tf = min(max(tile_first[ti], 0), N), te = min(max(tile_edge[ti], 0), E);
+    stage_window(tile_first, tile_edge, num_tiles, N, E, lane, t0, t1, tf, te);
 
     // the longest run of whole tiles from tile `ts` that fits a stage; its CSR slice is staged when it fits (else rows of
     // degree > 4 read `col` from global memory)
-    auto plan = [&](int ts) {
-        PaStage st;
-        st.ok = ts < t1 ? 1 : 0;
-        st.nb = st.rows = st.e0 = st.ne = 0;
-        st.next_t = ts;
-        if (!st.ok)
-            return st;
-        const int rel = ts - t0;
-        const int nb = __builtin_amdgcn_readlane(tf, rel), e0 = __builtin_amdgcn_readlane(te, rel);
-        const unsigned long long fit = __ballot(lane > rel && lane <= t1 - t0 && tf - nb <= PA_CAP);
-        st.nb = nb;
-        st.e0 = e0;
-        int endl = rel + 1; // (nothing fits: the next tile alone, cut to the stage -- only if the max_graph_nodes promise is broken)
-        if (fit) {
-            const unsigned long long nofit = ~fit & (~0ull << (rel + 1));
-            endl = nofit ? __builtin_ctzll(nofit) - 1 : 63 - __builtin_clzll(fit);
-        }
-        st.rows = min(max(__builtin_amdgcn_readlane(tf, endl) - nb, 0), PA_CAP);
-        st.ne = max(__builtin_amdgcn_readlane(te, endl) - e0, 0);
-        st.next_t = t0 + endl;
-        return st;
-    };
+    auto plan = [&](int ts) { return stage_plan<PA_CAP>(ts, t0, t1, lane, tf, te); };
     int vm = 0; // vector-memory instructions this wave has issued (DMA + stores): counted waits (VM operations retire in order)
-    auto issue = [&](const PaStage &st, int bb) {
+    // (the DMA loops keep their own spelling in every staged kernel: as shared inline functions they moved the machine code)
+    auto issue = [&](const Stage &st, int bb) {
         if (!st.ok || st.rows <= 0)
             return;
         char *base = smem + (size_t)bb * in_b;
@@ -111,7 +87,7 @@ __global__ __launch_bounds__(PA_WG, 2) void k_pna_pagg(const float *__restrict__
                     dma4_to_lds_u(col + st.e0 + c + lane, base + col_o + (size_t)c * 4);
     };
 
-    PaStage cur = plan(t0);
+    Stage cur = plan(t0);
     issue(cur, 0);
     int mark_cur = vm;
 
@@ -156,7 +132,7 @@ __global__ __launch_bounds__(PA_WG, 2) void k_pna_pagg(const float *__restrict__
         // ---- the stage's inputs have landed (own share; then everybody's), and everybody is done with the other buffer
         vmcnt_wait_n(min(vm - mark_cur, 63));
         g2_barrier();
-        const PaStage nxt = plan(cur.next_t);
+        const Stage nxt = plan(cur.next_t);
         issue(nxt, b ^ 1);
         const int mark_nxt = vm;
 
@@ -342,44 +318,29 @@ hipError_t launch_pna_pagg(const BatchTables &t, const float *x, int F, const fl
 {
     if (t.num_nodes <= 0)
         return hipSuccess;
-    if (!options().pna_pagg || !(F == 128 || F == 64 || F == 32) || t.tile_lo != 0)
+    const PnaPaggPlan p = plan_pna_pagg({options().pna_pagg != 0, F, ldw, t.tile_lo, launch_math(), t.num_tiles, device_cu_count(),
+                                         !(((uintptr_t)x | (uintptr_t)wb | (uintptr_t)out) & 15), {t.max_graph_nodes_hint, t.tile_rows, t.promise_graphs, t.num_graphs, t.large_n}});
+    if (!p.ok)
         return hipErrorNotSupported;
-    // a batch with a large segment: the max_graph_nodes promise covers graphs [0, promise_graphs) only and graph prep validates
-    // nothing about the rest -- those graphs need not fit a stage (round-5 advisor finding: they got clamped sources, unflagged)
-    if (t.promise_graphs < t.num_graphs || t.large_n >= 0)
-        return hipErrorNotSupported;
-    // whole graphs must fit a stage (validated on the device by graph prep: flag 8)
-    if (t.max_graph_nodes_hint <= 0 || t.max_graph_nodes_hint + t.tile_rows - 1 > PA_CAP)
-        return hipErrorNotSupported;
-    if ((((uintptr_t)x | (uintptr_t)wb | (uintptr_t)out) & 15) || (ldw & 3))
-        return hipErrorNotSupported;
-    const size_t lds = 2 * ((size_t)PA_CAP * (F + 4) * 4 + PA_CAP * 32 + PA_ECAP * 4);
-    const int cus = device_cu_count();
-    long long grid = std::min<long long>(2LL * cus, t.num_tiles);
-    if (grid < 1)
-        grid = 1;
-    if ((t.num_tiles + grid - 1) / grid > 62) // a workgroup keeps its run of the tile table in one register per lane
-        grid = (t.num_tiles + 61) / 62;
     hipError_t rc = hipErrorNotSupported;
-    const bool h3 = launch_math() == 3; // (opt-in f16x3, REDUCED precision)
     auto go1 = [&](auto qtag, auto mxtag) {
         constexpr int KQ = decltype(qtag)::value;
         auto kern = k_pna_pagg<KQ, decltype(mxtag)::value>;
-        if (ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds) != hipSuccess)
+        if (ensure_dynamic_lds(reinterpret_cast<const void *>(kern), p.lds) != hipSuccess)
             return;
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(PA_WG), lds, s, x, t.node_rec, t.col, t.tile_first, t.tile_edge, t.num_tiles,
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(PA_WG), p.lds, s, x, t.node_rec, t.col, t.tile_first, t.tile_edge, t.num_tiles,
                            t.num_nodes, t.num_edges, wb, ldw, out, t.err, t.err_host_dev);
         rc = hipGetLastError();
     };
     auto go = [&](auto qtag) {
-        if (h3)
+        if (p.mx == 2) // (opt-in f16x3, REDUCED precision)
             go1(qtag, IntTag<2>{});
         else
             go1(qtag, IntTag<0>{});
     };
-    if (F == 128)
+    if (p.kq == 8)
         go(IntTag<8>{});
-    else if (F == 64)
+    else if (p.kq == 4)
         go(IntTag<4>{});
     else
         go(IntTag<2>{});

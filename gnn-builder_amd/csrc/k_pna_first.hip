@@ -16,15 +16,28 @@
 //   OUT   whole rows -> HBM, 16-B non-temporal stores
 // Needs the max_graph_nodes promise (whole graphs in a stage); the general 13F mathematics (no degree classes: exact for any
 // degree), same statistics in the same order as k_aggregate_ring<PNA>.
+// The stage skeleton (tile-table window, stage planner), the carve and the launch plan: gnnb_stage.h
 #include "gnnb_stack.h"
+#include "gnnb_stage.h"
 
 namespace gnnb {
 
-static constexpr int PF_NW = 8, PF_WG = PF_NW * 64, PF_CAP = 64, PF_ECAP = 512;
+static constexpr int PF_NW = STAGE_NW, PF_WG = STAGE_WG;
 
-struct PfStage {
-    int ok, nb, rows, e0, ne, next_t;
-};
+// The kernel keeps ITS spelling of the carve's SW and PQ sizes (floats; taken from PfCarve they moved the machine code).  Macros, so
+// that the check expands the very same text: a drift on either side fails the build.
+#define PF_OWN_SW_F(F, F2) ((F * F2 + F + 3) & ~3)
+#define PF_OWN_PQ_F(LDP) ((PF_CAP * LDP + 3) & ~3)
+constexpr bool pf_own_sizes_match()
+{
+    for (int F = 1; F <= 12; F++) {
+        const int F2 = 2 * F, LDP = F2 + 1;
+        if (PF_OWN_SW_F(F, F2) != PfCarve{F, 1}.sw_f() || PF_OWN_PQ_F(LDP) != PfCarve{F, 1}.pq_f())
+            return false;
+    }
+    return true;
+}
+static_assert(pf_own_sizes_match(), "k_pna_first's SW / PQ sizes are not PfCarve's");
 
 template <int ACT, int KQ, int CSL>
 __global__ __launch_bounds__(PF_WG) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_pna_first(const float *__restrict__ x, int F, const int4 *__restrict__ node_rec,
@@ -42,46 +55,24 @@ __global__ __launch_bounds__(PF_WG) __attribute__((amdgpu_waves_per_eu(4, 4))) v
     const int F2 = 2 * F, LDP = F2 + 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
-    // ---- LDS carve: two input buffers {x rows | records | CSR slice | amp | att}, W_pre + b_pre, PQ, A0 (-> the output tile)
-    const int xs_b = ((PF_CAP * F * 4) + 15) & ~15;
-    const int rec_o = xs_b, col_o = rec_o + PF_CAP * 32, amp_o = col_o + PF_ECAP * 4, att_o = amp_o + PF_CAP * 4, in_b = att_o + PF_CAP * 4;
+    // ---- LDS carve (PfCarve): two input buffers {x rows | records | CSR slice | amp | att}, W_pre + b_pre, PQ, A0 (-> the output tile)
+    const PfCarve cv{F, KQ};
+    const int rec_o = cv.rec_o(), col_o = cv.col_o(), amp_o = cv.amp_o(), att_o = cv.att_o(), in_b = cv.in_b();
     float *SW = reinterpret_cast<float *>(smem + 2 * (size_t)in_b);        // W_pre [F][2F] then b_pre [F]
-    float *PQ = SW + ((F * F2 + F + 3) & ~3);                              // [CAP][LDP]: q (F) | p (F)
-    float *A0 = PQ + ((PF_CAP * LDP + 3) & ~3);
+    float *PQ = SW + PF_OWN_SW_F(F, F2);                                   // [CAP][LDP]: q (F) | p (F)
+    float *A0 = PQ + PF_OWN_PQ_F(LDP);
     float *YT = A0;
 
-    int t0, t1;
-
+    int t0, t1, tf, te;
     run_cuts(blockIdx.x, gridDim.x, (unsigned)num_tiles, t0, t1); // (32-bit: gnnb_device.h)
     if (t1 <= t0)
         return;
-    const int ti = min(t0 + min(lane, t1 - t0), num_tiles);
-    const int tf = min(max(tile_first[ti], 0), N), te = min(max(tile_edge[ti], 0), E);
+    stage_window(tile_first, tile_edge, num_tiles, N, E, lane, t0, t1, tf, te);
 
-    auto plan = [&](int ts) {
-        PfStage st;
-        st.ok = ts < t1 ? 1 : 0;
-        st.nb = st.rows = st.e0 = st.ne = 0;
-        st.next_t = ts;
-        if (!st.ok)
-            return st;
-        const int rel = ts - t0;
-        const int nb = __builtin_amdgcn_readlane(tf, rel), e0 = __builtin_amdgcn_readlane(te, rel);
-        const unsigned long long fit = __ballot(lane > rel && lane <= t1 - t0 && tf - nb <= PF_CAP);
-        st.nb = nb;
-        st.e0 = e0;
-        int endl = rel + 1; // (nothing fits: the next tile alone, cut to the stage -- only if the max_graph_nodes promise is broken)
-        if (fit) {
-            const unsigned long long nofit = ~fit & (~0ull << (rel + 1));
-            endl = nofit ? __builtin_ctzll(nofit) - 1 : 63 - __builtin_clzll(fit);
-        }
-        st.rows = min(max(__builtin_amdgcn_readlane(tf, endl) - nb, 0), PF_CAP);
-        st.ne = max(__builtin_amdgcn_readlane(te, endl) - e0, 0);
-        st.next_t = t0 + endl;
-        return st;
-    };
+    auto plan = [&](int ts) { return stage_plan<PF_CAP>(ts, t0, t1, lane, tf, te); };
     int vm = 0; // vector-memory instructions this wave has issued (DMA + stores): counted waits (VM operations retire in order)
-    auto issue = [&](const PfStage &st, int bb) {
+    // (the DMA loops keep their own spelling in every staged kernel: as shared inline functions they moved the machine code)
+    auto issue = [&](const Stage &st, int bb) {
         if (!st.ok || st.rows <= 0)
             return;
         char *base = smem + (size_t)bb * in_b;
@@ -110,7 +101,7 @@ __global__ __launch_bounds__(PF_WG) __attribute__((amdgpu_waves_per_eu(4, 4))) v
         }
     };
 
-    PfStage cur = plan(t0);
+    Stage cur = plan(t0);
     issue(cur, 0);
     int mark_cur = vm;
     // W_pre [F][2F] and b_pre -> LDS (tracked loads and LDS stores: complete behind the first barrier of the stage loop)
@@ -164,7 +155,7 @@ __global__ __launch_bounds__(PF_WG) __attribute__((amdgpu_waves_per_eu(4, 4))) v
         // ---- the stage's inputs have landed (own share; then everybody's); everybody is done with the output tile and the other buffer
         vmcnt_wait_n(min(vm - mark_cur, 63));
         g2_barrier();
-        const PfStage nxt = plan(cur.next_t);
+        const Stage nxt = plan(cur.next_t);
         issue(nxt, b ^ 1);
         const int mark_nxt = vm;
 
@@ -329,52 +320,32 @@ hipError_t launch_pna_first(const BatchTables &t, const float *x, int F, const f
 {
     if (t.num_nodes <= 0)
         return hipSuccess;
-    if (!options().pna_first || F < 1 || F > 12 || !(Nout == 128 || Nout == 64) || t.tile_lo != 0 || ldw < 13 * F || (((uintptr_t)x) & 3) ||
-        (((uintptr_t)y) & 15) || !t.amp || !t.att)
+    const PnaFirstPlan p = plan_pna_first({options().pna_first != 0, F, Nout, ldw, t.tile_lo, t.num_tiles, device_cu_count(),
+                                           !((((uintptr_t)x) & 3) || (((uintptr_t)y) & 15)), t.amp && t.att, {t.max_graph_nodes_hint, t.tile_rows, t.promise_graphs, t.num_graphs, t.large_n}});
+    if (!p.ok)
         return hipErrorNotSupported;
-    if (t.max_graph_nodes_hint <= 0 || t.max_graph_nodes_hint + t.tile_rows - 1 > PF_CAP)
-        return hipErrorNotSupported; // whole graphs must fit a stage (validated on the device by graph prep: flag 8)
-    // a batch with a large segment: the promise covers graphs [0, promise_graphs) only and graph prep validates nothing about the
-    // rest -- those graphs need not fit a stage (round-5 advisor finding: they got clamped sources, unflagged): layer by layer
-    if (t.promise_graphs < t.num_graphs || t.large_n >= 0)
-        return hipErrorNotSupported;
-    const int kq = (13 * F + 15) / 16;
-    if (Nout > 16 * kq) // (the output tile is written over A0)
-        return hipErrorNotSupported;
-    const int xs_b = ((PF_CAP * F * 4) + 15) & ~15;
-    const size_t in_b = (size_t)xs_b + PF_CAP * 32 + PF_ECAP * 4 + 2 * PF_CAP * 4;
-    const size_t lds = 2 * in_b + (size_t)((F * 2 * F + F + 3) & ~3) * 4 + (size_t)((PF_CAP * (2 * F + 1) + 3) & ~3) * 4 + (size_t)PF_CAP * (16 * kq + 4) * 4;
-    int glog2 = 0;
-    while ((4 << glog2) < Nout)
-        glog2++;
-    const int cus = device_cu_count();
-    long long grid = std::min<long long>(2LL * cus, t.num_tiles);
-    if (grid < 1)
-        grid = 1;
-    if ((t.num_tiles + grid - 1) / grid > 62) // a workgroup keeps its run of the tile table in one register per lane
-        grid = (t.num_tiles + 61) / 62;
     hipError_t rc = hipErrorNotSupported;
     auto go2 = [&](auto atag, auto qtag, auto ctag) {
         constexpr int ACT = decltype(atag)::value, KQ = decltype(qtag)::value, CSL = decltype(ctag)::value;
         auto kern = k_pna_first<ACT, KQ, CSL>;
-        if (ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds) != hipSuccess)
+        if (ensure_dynamic_lds(reinterpret_cast<const void *>(kern), p.lds) != hipSuccess)
             return;
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(PF_WG), lds, s, x, F, t.node_rec, t.col, t.amp, t.att, t.tile_first, t.tile_edge,
-                           t.num_tiles, t.num_nodes, t.num_edges, wpre, bpre, w, ldw, bias, Nout, glog2, y);
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(PF_WG), p.lds, s, x, F, t.node_rec, t.col, t.amp, t.att, t.tile_first, t.tile_edge,
+                           t.num_tiles, t.num_nodes, t.num_edges, wpre, bpre, w, ldw, bias, Nout, p.glog2, y);
         rc = hipGetLastError();
     };
     auto go = [&](auto atag, auto qtag) {
-        if (Nout == 128)
+        if (p.csl == 3)
             go2(atag, qtag, IntTag<3>{});
         else
             go2(atag, qtag, IntTag<2>{});
     };
     auto go_a = [&](auto atag) {
-        switch (kq) {
+        switch (p.kq) {
         case 8: go(atag, IntTag<8>{}); break;   // F = 9 (ogbg-molhiv) .. 9
         case 9: go(atag, IntTag<9>{}); break;   // F = 10, 11 (QM9)
         case 10: go(atag, IntTag<10>{}); break; // F = 12
-        default: break;                         // (narrower inputs: Nout > 16 kq was refused above for the usual widths)
+        default: break;                         // (the plan admits no other)
         }
     };
     GNNB_DISPATCH_ACT(act, go_a)

@@ -78,9 +78,7 @@ hipError_t launch_global_pool(const float *x, const int32_t *node_ptr, int num_g
         return hipSuccess;
     const bool v4 = (d % 4 == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)out & 15) == 0);
     const int nvec = v4 ? d / 4 : d;
-    int glog2 = 2;
-    while ((1 << glog2) < nvec && glog2 < 6)
-        glog2++;
+    const int glog2 = lane_group_log2(nvec, 2);
     const int per_wg = WG >> glog2;
     const int grid = (num_graphs + per_wg - 1) / per_wg;
     const int p0 = pools[0], p1 = num_pools > 1 ? pools[1] : 0, p2 = num_pools > 2 ? pools[2] : 0;
@@ -491,9 +489,7 @@ hipError_t launch_pool_mlp(const float *x, const int32_t *node_ptr, int num_grap
     const size_t lds = ((size_t)act0_floats + act1_floats + wfl) * 4;
     if (lds > 158 * 1024)
         return hipErrorNotSupported; // head too large for the fused kernel: caller uses pool + GEMMs
-    int glog2 = 2;
-    while ((1 << glog2) < (d >> 2) && glog2 < 6)
-        glog2++;
+    const int glog2 = lane_group_log2(d >> 2, 2);
     const int grid = (num_graphs + HEAD_GRAPHS - 1) / HEAD_GRAPHS;
     const int p0 = pools[0], p1 = num_pools > 1 ? pools[1] : 0, p2 = num_pools > 2 ? pools[2] : 0;
     auto go = [&](auto tag) {
