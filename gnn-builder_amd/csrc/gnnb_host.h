@@ -1,6 +1,7 @@
 // gnnb_host.h -- what the host translation units of libgnnb_hip.so share (gnnb_model.hip: description and weight upload;
-// gnnb_runtime.hip: workspace, graph prep, forward, C-ABI utilities): the two handle structs, the error helpers and the
-// dimension helpers of a model description.  Host only: no kernel unit includes it.
+// gnnb_runtime.hip: workspace, graph prep, stage entry points, C-ABI utilities; gnnb_forward.hip: the forward): the two handle
+// structs, the error helpers, the dimension helpers of a model description and what the forward takes from the runtime unit.
+// Host only: no kernel unit includes it.
 #pragma once
 
 #include <vector>
@@ -118,4 +119,48 @@ struct gnnb_workspace {
 namespace gnnb {
 // the model's MLP head as the readout kernels take it (gnnb_model.hip): the ONLY place that fills a HeadArgs
 HeadArgs model_head_args(const gnnb_model *model);
+
+// gnnb_runtime.hip, for the forward (gnnb_forward.hip) -- each is described where it is defined
+int ensure_gcoef(gnnb_workspace *ws, void *stream);
+int build_gemm(GemmArgs &g, const gnnb_gemm_seg *segs, int num_segs, const float *w, int ldw, int rows = 1);
+int linear_segs(const StreamK *sk_owned, const gnnb_gemm_seg *segs, int num_segs, const float *w_dev, int ldw, const float *bias_dev,
+                const float *skip_dev, float *y_dev, int M, int N, int act, void *stream);
+bool guest_prep_eligible(const gnnb_workspace *ws, int num_nodes);
+int graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev,
+                    int num_graphs, int num_nodes, int num_edges, float pna_delta, void *stream, PrepParams *defer);
+// gnnb_forward.hip, for graph prep
+BatchTables small_segment(const gnnb_workspace *ws);
+
+// The event-timed loop behind the *_timed entries: `warmup` launches, then `iters` launches between two events on `s`;
+// launch(i) -> GNNB_OK or an error (which ends the loop and is returned).  *out_us = microseconds per launch.
+template <typename F> static int timed_loop(hipStream_t s, int warmup, int iters, F launch, float *out_us)
+{
+    struct Events { // (destroyed on every return path)
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events()
+        {
+            if (e0)
+                (void)hipEventDestroy(e0);
+            if (e1)
+                (void)hipEventDestroy(e1);
+        }
+    } ev;
+    GNNB_HIP_TRY(hipEventCreate(&ev.e0));
+    GNNB_HIP_TRY(hipEventCreate(&ev.e1));
+    int rc = GNNB_OK;
+    for (int i = 0; i < warmup && rc == GNNB_OK; i++)
+        rc = launch(i);
+    if (rc != GNNB_OK)
+        return rc;
+    GNNB_HIP_TRY(hipStreamSynchronize(s));
+    GNNB_HIP_TRY(hipEventRecord(ev.e0, s));
+    for (int i = 0; i < iters && rc == GNNB_OK; i++)
+        rc = launch(i);
+    GNNB_HIP_TRY(hipEventRecord(ev.e1, s));
+    GNNB_HIP_TRY(hipEventSynchronize(ev.e1));
+    float ms = 0.f;
+    GNNB_HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *out_us = ms * 1000.0f / (float)iters;
+    return rc;
+}
 } // namespace gnnb

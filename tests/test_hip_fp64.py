@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 # the process-wide defaults of every option this file sets (gnnb_runtime.hip options())
 DEFAULTS = {"math": 0, "fuse_zf": 1, "zf_shape": 2, "zf_head": 0, "fuse_gcn2": 1, "stage_cut": 0, "large_fork": 2, "fuse_narrow": 1,
             "first_ring": 1, "pna_classes": 1, "pna_pagg": 1, "pna_first": 1, "pna_fold_lin": 1, "sage_first_mean": 1,
-            "head_small": 1, "head_pairs": 1}
+            "head_small": 1, "head_pairs": 1, "head_split": 0, "fuse_pool": 1, "fold_skip": 1}
 # math 2 (bf16x3: hi + mid bf16 pieces of both operands of k_gcn2_zf's wide update, ~16 significant bits per product): max error
 # relative to the output scale against float64.  README C2: 6.4e-7 absolute; measured here at C2 shape: 2.76e-6 relative; bound 3x that
 BF16X3_BOUND = 8.3e-6
@@ -63,10 +63,14 @@ def options(**kw):
             runtime.set_option(k, DEFAULTS[k])
 
 
-def check(route, got, model, batch, x, k=R.K):
+def references(model, batch, x):
+    """(float64 model output, fp32 oracle output) for ``check``: computed once where several cases share a model and a batch."""
+    return R.forward64(model, batch, x), O.forward_batched(model.spec(), canon(model), x, batch.coo, batch.node_ptr, batch.edge_ptr)
+
+
+def check(route, got, model, batch, x, k=R.K, refs=None):
     """``got`` against the float64 model within the fp32 budget; records e / e32 under ``route``."""
-    ref = R.forward64(model, batch, x)
-    base = O.forward_batched(model.spec(), canon(model), x, batch.coo, batch.node_ptr, batch.edge_ptr)
+    ref, base = refs if refs is not None else references(model, batch, x)
     e, e32 = R.budget(got, ref, base, k=k, what=route)
     WORST[route] = max(WORST.get(route, 0.0), R.ratio(e, e32))
     return ref

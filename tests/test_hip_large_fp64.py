@@ -147,7 +147,7 @@ def test_pna_degree_classes(hidden, nodes, math):
     promise = int(np.diff(batch.node_ptr).max())
     got, _ = check_forward(f"large pna F{hidden} math{math}", model, batch, x, promise=promise, maxdeg=maxdeg, math=math)
     general, _ = check_forward(None, model, batch, x, promise=promise, maxdeg=maxdeg, math=math, pna_classes=0)
-    below = batch.num_nodes * 16 * hidden + 512 < GIB4  # (gnnb_runtime.hip: the class form's condition)
+    below = batch.num_nodes * 16 * hidden + 512 < GIB4  # (gnnb_forward.hip pna_layer: the class form's condition)
     assert below == (nodes < t)
     if below:
         assert not np.array_equal(got, general), "the degree-class form did not run below its limit"
