@@ -174,7 +174,7 @@ struct MathScope { // entry points: `MathScope scope(ws->desc.math, ws->t.err, w
     MathScope &operator=(const MathScope &) = delete;
 };
 
-// Arguments of one graph prep (k_graph_prep; round 6: also of the prep the readout kernel runs for its stream's next batch, k_readout.hip)
+// Arguments of one graph prep (k_graph_prep; also of the prep the readout kernel runs for its stream's next batch, k_readout.hip)
 struct PrepParams {
     const int2 *coo;
     const int32_t *node_ptr, *edge_ptr;
@@ -197,12 +197,10 @@ struct GuestPrep {
     bool taken;
 };
 GuestPrep *&guest_prep_slot(); // thread-local; nullptr = nothing on offer
+// drop_self_loops: edges (v, v) are not entered into the tables (GCN: PyG's add_remaining_self_loops)
 PrepParams make_prep_params(const int32_t *coo, const int32_t *node_ptr, const int32_t *edge_ptr, const BatchTables &t, float pna_delta,
                             int drop_self_loops);
 hipError_t launch_graph_prep(const PrepParams &p, hipStream_t s);
-// drop_self_loops: edges (v, v) are not entered into the tables (GCN: PyG's add_remaining_self_loops)
-hipError_t launch_graph_prep(const int32_t *coo, const int32_t *node_ptr, const int32_t *edge_ptr,
-                             BatchTables &t, float pna_delta, int drop_self_loops, hipStream_t s);
 
 hipError_t launch_aggregate(const BatchTables &t, int kind, const float *x, const float *selfq,
                             float *out, int width, float eps, hipStream_t s);

@@ -437,8 +437,7 @@ int gnnb::graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int3
     else {
         if (defer)
             return fail(GNNB_ERR_INVALID, "graph prep deferred for a workspace that is not eligible");
-        GNNB_HIP_TRY(launch_graph_prep(coo_dev, node_ptr_dev, edge_ptr_dev, t, prep_delta, drop_self,
-                                       (hipStream_t)stream));
+        GNNB_HIP_TRY(launch_graph_prep(make_prep_params(coo_dev, node_ptr_dev, edge_ptr_dev, t, prep_delta, drop_self), (hipStream_t)stream));
     }
     ws->prepared = true;
     ws->prep_delta = prep_delta > 0.0f ? prep_delta : 0.0f;

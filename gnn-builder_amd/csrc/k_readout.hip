@@ -378,7 +378,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void k_pool_mlp(const float *__restri
 // One workgroup = 16 graphs; wave w takes the 16-column output slices w, w + 4, ...
 static constexpr int HS_THREADS = 256;
 
-// GUEST (round 6, gnnb_forward_prepared_prep_next): the graph prep of the stream's NEXT batch -- COO -> CSR, node records,
+// GUEST (gnnb_forward_prepared_prep_next): the graph prep of the stream's NEXT batch -- COO -> CSR, node records,
 // normalisers, tile tables of ANOTHER workspace (gnnb_prep.h: one wavefront per graph, <= 64 nodes each by that workspace's
 // promise) -- as EXTRA WORKGROUPS of this launch: blocks [0, prep_blocks) prepare four graphs each, the rest run the head.  The
 // prep is a chain of dependent fetches (its graph's table entries, its edges, then a few hundred instructions and the
@@ -386,10 +386,10 @@ static constexpr int HS_THREADS = 256;
 // of the other streams' batches it cost the three-stream pipeline ~4.5 us of a 42-us step.  Here it starts with the first
 // blocks of a kernel that runs ~11 us anyway.  (Tried first inside k_gcn2_zf, on the waves that idle through the last stage's
 // aggregation phase: that window is 2 us, the chain -- even with its fetches hoisted into the kernel's prologue -- outlasts
-// it by 4 us, and the stack kernel is the pipeline's critical resource: no gain, DESIGN 3.6.)
+// it by 4 us, and the stack kernel is the pipeline's critical resource: no gain, DESIGN 3.1.)
 // The parameter block is the kernel's FIRST argument and is never named: the prep blocks read it from the kernarg segment
 // (offset 0), the head blocks never fetch it.
-// REGISTER BUDGET (round 6): 72 (a launch bound of seven waves per SIMD; 67 used).  Beside k_gcn2_zf's four 96-register waves a
+// REGISTER BUDGET: 72 (a launch bound of seven waves per SIMD; 67 used).  Beside k_gcn2_zf's four 96-register waves a
 // SIMD has 128 registers left: this kernel's wave and a graph-prep wave (56) of the stream's next batch then run side by side
 // instead of one after the other -- BASELINE config 2, three batches in flight: 40.4-41.6 -> 37.6-37.7 us per step.
 static constexpr int HS_WAVES = 7; // waves per SIMD of the plain, paired-operand form (the register budget above)
@@ -403,10 +403,9 @@ __global__ __launch_bounds__(HS_THREADS, (GUEST || !PAIRS) ? 5 : HS_WAVES) /* (t
     __builtin_amdgcn_s_setprio(GNNB_GUEST_PRIO); // (co-runs with the next batch's conv-stack kernel: see k_graph_prep)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if constexpr (GUEST) {
-        static_assert(HS_THREADS / 64 == WG / 64, "the guest prep's blocks are k_graph_prep's");
         if ((int)blockIdx.x < prep_blocks) {
             const PrepParams gp = *kernarg_prep_params();
-            prep_graph_group<64, 4>(gp, (blockIdx.x * (HS_THREADS / 64) + wave) * 4, lane, reinterpret_cast<int32_t *>(smem) + wave * 256);
+            prep_graph_group<64, 4>(gp, (blockIdx.x * (HS_THREADS / 64) + wave) * 4, lane, reinterpret_cast<int32_t *>(smem) + wave * prep_wave_lds_ints(64));
             return;
         }
     }
@@ -434,9 +433,9 @@ static hipError_t launch_head_small(int num_graphs, const HeadArgs &head, int ac
     int prep_blocks = 0;
     if (guest) {
         gp = *gslot->params;
-        prep_blocks = ((gp.B + 1 + 3) / 4 + (HS_THREADS / 64) - 1) / (HS_THREADS / 64);
+        prep_blocks = prep_grid_blocks(gp.B + 1, 4, HS_THREADS);
     }
-    const size_t lds = std::max(head_small_lds_bytes(ldact), guest ? (size_t)(HS_THREADS / 64) * 1024 : (size_t)0);
+    const size_t lds = std::max(head_small_lds_bytes(ldact), guest ? (HS_THREADS / 64) * prep_wave_lds_ints(64) * sizeof(int32_t) : (size_t)0);
     auto go = [&](auto tag) {
         constexpr int ACT = decltype(tag)::value;
         if (guest)

@@ -163,3 +163,18 @@ def sample_graphs(batch, seed, count=256, nodes=()):
         k = int(np.searchsorted(batch.node_ptr, v, "right")) - 1
         g += [max(k - 1, 0), k, min(k + 1, B - 1)]
     return np.unique(np.asarray(g, np.int64))
+
+
+def oracle_tables_batched(batch: GraphBatch):
+    """(row_ptr, col) of the whole batch from the oracle's per-graph tables."""
+    from oracle import oracle as O
+
+    row_ptr, cols = [0], []
+    for g in range(batch.num_graphs):
+        xg, cg = batch.graph(g)
+        in_deg, _, offsets, nbrs = O.tables(cg, xg.shape[0])
+        n0 = int(batch.node_ptr[g])
+        for d in in_deg:
+            row_ptr.append(row_ptr[-1] + int(d))
+        cols.append(nbrs + n0)
+    return np.asarray(row_ptr, np.int32), (np.concatenate(cols) if cols else np.zeros(0, np.int32)).astype(np.int32)

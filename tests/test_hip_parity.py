@@ -11,7 +11,7 @@ import torch
 import golden_util as G
 from gnnbuilder_amd import runtime, synthetic
 from gnnbuilder_amd.batching import GraphBatch, pack_graphs
-from helpers import canon, make_model, to_dev
+from helpers import canon, make_model, oracle_tables_batched, to_dev
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -30,18 +30,6 @@ def fixture_batch():
     return pack_graphs([(x, coo)])
 
 
-def oracle_tables_batched(batch: GraphBatch):
-    row_ptr, cols = [0], []
-    for g in range(batch.num_graphs):
-        xg, cg = batch.graph(g)
-        in_deg, _, offsets, nbrs = O.tables(cg, xg.shape[0])
-        n0 = int(batch.node_ptr[g])
-        for d in in_deg:
-            row_ptr.append(row_ptr[-1] + int(d))
-        cols.append(nbrs + n0)
-    return np.asarray(row_ptr, np.int32), (np.concatenate(cols) if cols else np.zeros(0, np.int32)).astype(np.int32)
-
-
 def plain_model(conv, fin, fout):
     # one layer; identity-ish tail so stage tests can reuse CompiledModel's workspace
     return make_model(conv, in_dim=fin, hidden=fout, layers=1, out_dim=fout, task_out=3, mlp_layers=0)
@@ -55,7 +43,7 @@ def edge_case_batch():
     graphs.append((rng.uniform(-1, 1, (5, 8)), np.array([[0, 1], [1, 0], [2, 2], [3, 1], [3, 1]])))  # self loop, dup edge, isolated node 4
     graphs.append((rng.uniform(-1, 1, (0, 8)), np.zeros((0, 2), np.int32)))                    # empty graph
     n = 150                                                                                     # > 64 nodes: several lane chunks
-    e = np.stack([rng.integers(0, n, 700), rng.integers(0, n, 700)], 1)                         # > 512 edges: uncached path
+    e = np.stack([rng.integers(0, n, 700), rng.integers(0, n, 700)], 1)                         # > 256 edges (64 * PREP_REG_CHUNKS): the scan path re-reads its edges
     graphs.append((rng.uniform(-1, 1, (n, 8)), e))
     graphs.append((rng.uniform(-1, 1, (3, 8)), np.array([[0, 1], [1, 2], [2, 0]])))
     return pack_graphs([(np.asarray(x, np.float32), np.asarray(c, np.int32)) for x, c in graphs])
