@@ -125,7 +125,11 @@ def from_pyg_batch(x, edge_index, batch=None, ptr=None, num_graphs=None) -> Grap
     holds) or ``ptr`` [B+1] (``Batch.ptr``).  Edges may come in any order; they are grouped by graph
     with a STABLE sort, so the per-destination neighbour order -- hence the floating-point sum order
     of the aggregation -- is the one the reference's per-graph ``edge_index`` would give
-    (reference code_gen.py:262 writes ``edge_index.T`` per graph)."""
+    (reference code_gen.py:262 writes ``edge_index.T`` per graph).
+
+    This is the HOST form (numpy).  A mini-batch that already lives on the GPU goes through the device form instead, which
+    returns the same three index arrays without a copy to the host or a synchronisation:
+    ``runtime.CompiledModel.ingest_pyg`` / ``forward_pyg`` (``gnnb_ingest_pyg``, csrc/k_ingest.hip)."""
     x = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
     ei = np.asarray(edge_index)
     if ei.ndim != 2 or ei.shape[0] != 2:

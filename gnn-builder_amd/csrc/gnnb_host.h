@@ -91,6 +91,10 @@ struct gnnb_workspace {
     float *pooled = nullptr;            // [max_graphs, np*d]
     float *mlp[2] = {nullptr, nullptr}; // [max_graphs, max(mlp_hidden, mlp_out)]
     bool prepared = false;
+    char *ingest_blob = nullptr; // gnnb_workspace_enable_ingest: the outputs and the sort scratch of gnnb_ingest_pyg (ingest_layout), one allocation
+    bool flags_reported = false; // gnnb_forward_pyg: its ingest has made the lazy flag report of this call; the graph prep behind it skips its
+                                 // own, which could already see what THIS batch's ingest kernels flagged
+    bool ingested = false;       // an ingest has been enqueued: gnnb_workspace_check has something to report on
     float2 *pool_part = nullptr; // pieces of graphs that cross the 32-row blocks of the pooling GEMM epilogue (PoolEpilogue::part)
     bool gcoef_ready = false; // t.gcoef holds the prepared batch's GCN coefficients (ensure_gcoef)
     int max_graph_nodes = 0; // caller's promise (0 = none)

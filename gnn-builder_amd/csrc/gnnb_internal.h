@@ -202,6 +202,32 @@ PrepParams make_prep_params(const int32_t *coo, const int32_t *node_ptr, const i
                             int drop_self_loops);
 hipError_t launch_graph_prep(const PrepParams &p, hipStream_t s);
 
+// A PyG mini-batch on the device (k_ingest.hip): edge_index [2, E] + batch [N] or ptr [B+1], all int64 -> coo / node_ptr / edge_ptr
+constexpr int GNNB_FLAG_INGEST = 128;   // bit of BatchTables::err: the mini-batch was malformed (reported as GNNB_ERR_GRAPH)
+constexpr int INGEST_TILE = 1024;       // edges per workgroup of the edge kernels
+constexpr int INGEST_DIGIT_BITS = 8;    // bits of the graph id per radix pass of the general path
+constexpr int INGEST_STATE_UNSORTED = 0, INGEST_STATE_NODES_BROKEN = 1, INGEST_STATE_WORDS = 4; // IngestParams::state
+struct IngestParams {
+    const long long *src, *dst;   // the two rows of edge_index
+    const long long *batch, *ptr; // one of them, or neither (B == 1)
+    int B, N, E;
+    int32_t *node_ptr, *edge_ptr; // [B + 1]
+    int2 *coo;                    // [E]
+    int32_t *keys[2], *idx[2];    // [E] each: (graph id, input edge) pairs of the general path, two halves that alternate per pass
+    int32_t *hist;                // [2^INGEST_DIGIT_BITS x tiles] digit counts of one pass, scanned in place
+    int32_t *state;               // [INGEST_STATE_WORDS] "some edge's graph id is below its predecessor's", "batch / ptr is broken":
+                                  // zero between ingests (each word is cleared by a kernel that no reader of it runs beside)
+    int32_t *err, *err_host;      // the workspace's flag words (BatchTables::err / err_host_dev)
+};
+// byte offsets of the ingest allocation's arrays for a workspace's capacities, and its size: a pure function of the three
+struct IngestLayout {
+    size_t state, node_ptr, edge_ptr, coo, keys[2], idx[2], hist, bytes;
+};
+IngestLayout ingest_layout(int max_graphs, int max_nodes, int max_edges);
+int ingest_sort_passes(int num_graphs); // radix passes the general path launches for that many graphs
+// the whole launch sequence; depends on B, N, E and on which of batch / ptr is given, never on device data
+hipError_t launch_ingest(const IngestParams &p, hipStream_t s);
+
 hipError_t launch_aggregate(const BatchTables &t, int kind, const float *x, const float *selfq,
                             float *out, int width, float eps, hipStream_t s);
 // GraphSAGE's narrow first layer (k_conv_first's [mean | x] form) + the next layer's mean aggregate of its output rows, one kernel

@@ -248,6 +248,8 @@ void gnnb_workspace_destroy(gnnb_workspace *ws)
         return;
     if (ws->blob)
         (void)hipFree(ws->blob);
+    if (ws->ingest_blob)
+        (void)hipFree(ws->ingest_blob);
     if (ws->stage)
         (void)hipFree(ws->stage);
     if (ws->err_host)
@@ -361,6 +363,29 @@ bool gnnb::guest_prep_eligible(const gnnb_workspace *ws, int num_nodes)
     return !may_plan_stage_cuts(ws) && !wants_degree_classes(ws) && !wants_gcoef_at_prep(ws);
 }
 
+// Lazy detection: a batch prepared (or ingested) EARLIER on this workspace was flagged on the device (edge leaving its graph,
+// broken ptr arrays, broken max_graph_nodes promise, malformed PyG mini-batch) and nobody called gnnb_workspace_check since.  Read
+// from a host-mapped word without synchronising: it reports what has already run, never the batch being enqueued now.
+static int report_earlier_flags(gnnb_workspace *ws, void *stream)
+{
+    if (ws->flags_reported) { // (the same call has looked already: gnnb_forward_pyg)
+        ws->flags_reported = false;
+        return GNNB_OK;
+    }
+    if (!ws->err_host || *(volatile int32_t *)ws->err_host == 0)
+        return GNNB_OK;
+    const int32_t seen = *(volatile int32_t *)ws->err_host;
+    *(volatile int32_t *)ws->err_host = 0;
+    // reported now: the device word is cleared as well (in stream order), or a later gnnb_workspace_check would blame
+    // a good batch for it
+    (void)hipMemsetAsync(ws->t.err, 0, sizeof(int32_t), (hipStream_t)stream);
+    if (seen == GNNB_FLAG_RANGE)
+        return fail(GNNB_ERR_RANGE, "an earlier forward on this workspace met a non-finite value in a reduced-precision math mode "
+                                    "(fp16's range exceeded: its results were unspecified); run the model with math = 0");
+    return fail(GNNB_ERR_GRAPH, "an earlier batch on this workspace was flagged as malformed (its results were "
+                                "unspecified); gnnb_workspace_check reports and clears the flags");
+}
+
 // defer != nullptr (and guest_prep_eligible): everything gnnb_graph_prep does EXCEPT the launch -- *defer receives the kernel's arguments
 int gnnb::graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev,
                           int num_graphs, int num_nodes, int num_edges, float pna_delta, void *stream, PrepParams *defer)
@@ -374,21 +399,8 @@ int gnnb::graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int3
         return fail(GNNB_ERR_CAPACITY,
                     "batch (%d graphs, %d nodes, %d edges) exceeds workspace (%d, %d, %d)",
                     num_graphs, num_nodes, num_edges, ws->max_graphs, ws->max_nodes, ws->max_edges);
-    // lazy detection: a batch prepared EARLIER on this workspace was flagged on the device (edge leaving its graph,
-    // broken ptr arrays, broken max_graph_nodes promise) and nobody called gnnb_workspace_check since.  Read from a
-    // host-mapped word without synchronising: it reports what has already run, never the batch being enqueued now.
-    if (ws->err_host && *(volatile int32_t *)ws->err_host != 0) {
-        const int32_t seen = *(volatile int32_t *)ws->err_host;
-        *(volatile int32_t *)ws->err_host = 0;
-        // reported now: the device word is cleared as well (in stream order), or a later gnnb_workspace_check would blame
-        // a good batch for it
-        (void)hipMemsetAsync(ws->t.err, 0, sizeof(int32_t), (hipStream_t)stream);
-        if (seen == GNNB_FLAG_RANGE)
-            return fail(GNNB_ERR_RANGE, "an earlier forward on this workspace met a non-finite value in a reduced-precision math mode "
-                                        "(fp16's range exceeded: its results were unspecified); run the model with math = 0");
-        return fail(GNNB_ERR_GRAPH, "an earlier batch on this workspace was flagged as malformed (its results were "
-                                    "unspecified); gnnb_workspace_check reports and clears the flags");
-    }
+    if (const int rc = report_earlier_flags(ws, stream))
+        return rc;
     if (ws->large_g >= 0 && (ws->large_g > num_graphs || ws->large_n > num_nodes || ws->large_e > num_edges))
         return fail(GNNB_ERR_INVALID, "large segment (graph %d, node %d, edge %d) lies outside the batch (%d, %d, %d)",
                     ws->large_g, ws->large_n, ws->large_e, num_graphs, num_nodes, num_edges);
@@ -551,7 +563,7 @@ int gnnb_graph_prep(gnnb_workspace *ws, const int32_t *coo_dev, const int32_t *n
 
 int gnnb_workspace_check(gnnb_workspace *ws, void *stream)
 {
-    if (!ws || !ws->prepared)
+    if (!ws || (!ws->prepared && !ws->ingested))
         return fail(GNNB_ERR_INVALID, "workspace has no prepared batch");
     int32_t err = 0;
     GNNB_HIP_TRY(hipMemcpyAsync(&err, ws->t.err, sizeof(err), hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -566,12 +578,108 @@ int gnnb_workspace_check(gnnb_workspace *ws, void *stream)
         return fail(GNNB_ERR_GRAPH, "malformed batch (flags 0x%x): 1/2 ptr arrays not monotone/complete, 4 an edge leaves "
                                     "its graph, 8 a graph exceeds the max_graph_nodes promise, 16 the large-segment offsets "
                                     "disagree with node_ptr / edge_ptr, 32 a node exceeds the max_degree promise, 64 a reduced-precision "
-                                    "kernel produced a non-finite value", err);
+                                    "kernel produced a non-finite value, 128 gnnb_ingest_pyg: endpoint outside [0, N), edge between two "
+                                    "graphs, or broken batch / ptr", err);
     if (err & GNNB_FLAG_RANGE)
         return fail(GNNB_ERR_RANGE, "a reduced-precision math mode (bf16x3 / f16x3) produced a non-finite value since the last check: an "
                                     "activation or a weight beyond fp16's range (65504), or non-finite inputs; the results of that forward "
                                     "are unspecified -- run the model with math = 0 (flag 0x40)");
     return GNNB_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// PyG mini-batches (k_ingest.hip)
+size_t gnnb_ingest_bytes(int max_graphs, int max_nodes, int max_edges)
+{
+    if (max_graphs < 0 || max_nodes < 0 || max_edges < 0)
+        return 0;
+    return ingest_layout(max_graphs, max_nodes, max_edges).bytes;
+}
+
+int gnnb_workspace_enable_ingest(gnnb_workspace *ws)
+{
+    if (!ws)
+        return fail(GNNB_ERR_INVALID, "null workspace");
+    if (ws->ingest_blob)
+        return GNNB_OK; // (enabled already: the allocation is made once)
+    if (ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_workspace_enable_ingest: the workspace is in use (a batch has been prepared on it); "
+                                      "enable ingest right after gnnb_workspace_create");
+    const IngestLayout l = ingest_layout(ws->max_graphs, ws->max_nodes, ws->max_edges);
+    char *blob = nullptr;
+    hipError_t e = hipMalloc((void **)&blob, l.bytes);
+    if (e != hipSuccess)
+        return fail(GNNB_ERR_HIP, "ingest allocation of %zu bytes failed: %s", l.bytes, hipGetErrorString(e));
+    e = hipMemset(blob + l.state, 0, INGEST_STATE_WORDS * 4); // (synchronous, as the stream-K scratch's: joins no other stream)
+    if (e != hipSuccess) {
+        (void)hipFree(blob);
+        return fail(GNNB_ERR_HIP, "ingest state initialisation failed: %s", hipGetErrorString(e));
+    }
+    ws->ingest_blob = blob;
+    return GNNB_OK;
+}
+
+int gnnb_ingest_pyg(gnnb_workspace *ws, const int64_t *edge_index_dev, const int64_t *batch_dev, const int64_t *ptr_dev,
+                    int num_graphs, int num_nodes, int num_edges, const int32_t **coo_dev, const int32_t **node_ptr_dev,
+                    const int32_t **edge_ptr_dev, void *stream)
+{
+    if (!ws || !coo_dev || !node_ptr_dev || !edge_ptr_dev || (num_edges > 0 && !edge_index_dev))
+        return fail(GNNB_ERR_INVALID, "null argument to gnnb_ingest_pyg");
+    if (!ws->ingest_blob)
+        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg: call gnnb_workspace_enable_ingest on the workspace first");
+    if (num_graphs < 0 || num_nodes < 0 || num_edges < 0)
+        return fail(GNNB_ERR_INVALID, "negative batch size");
+    if (num_graphs > ws->max_graphs || num_nodes > ws->max_nodes || num_edges > ws->max_edges)
+        return fail(GNNB_ERR_CAPACITY, "batch (%d graphs, %d nodes, %d edges) exceeds workspace (%d, %d, %d)", num_graphs, num_nodes,
+                    num_edges, ws->max_graphs, ws->max_nodes, ws->max_edges);
+    if (batch_dev && ptr_dev)
+        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg takes batch or ptr, not both");
+    if (num_nodes == 0)
+        batch_dev = nullptr; // (no node: every node_ptr entry is 0; an empty `batch` may come without an address -- torch gives none)
+    else if (!batch_dev && !ptr_dev && num_graphs > 1)
+        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg needs batch or ptr for a batch of %d graphs", num_graphs);
+    if ((num_graphs == 0 && (num_nodes > 0 || num_edges > 0)) || (num_nodes == 0 && num_edges > 0))
+        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg: %d nodes and %d edges in %d graphs", num_nodes, num_edges, num_graphs);
+    if (const int rc = report_earlier_flags(ws, stream)) // (before anything is enqueued, as gnnb_graph_prep does)
+        return rc;
+    const IngestLayout l = ingest_layout(ws->max_graphs, ws->max_nodes, ws->max_edges);
+    char *b = ws->ingest_blob;
+    IngestParams p;
+    memset(&p, 0, sizeof(p));
+    p.src = (const long long *)edge_index_dev;
+    p.dst = p.src + num_edges;
+    p.batch = (const long long *)batch_dev;
+    p.ptr = (const long long *)ptr_dev;
+    p.B = num_graphs, p.N = num_nodes, p.E = num_edges;
+    p.node_ptr = (int32_t *)(b + l.node_ptr), p.edge_ptr = (int32_t *)(b + l.edge_ptr), p.coo = (int2 *)(b + l.coo);
+    for (int h = 0; h < 2; h++)
+        p.keys[h] = (int32_t *)(b + l.keys[h]), p.idx[h] = (int32_t *)(b + l.idx[h]);
+    p.hist = (int32_t *)(b + l.hist), p.state = (int32_t *)(b + l.state);
+    p.err = ws->t.err, p.err_host = ws->t.err_host_dev;
+    GNNB_HIP_TRY(launch_ingest(p, (hipStream_t)stream));
+    ws->ingested = true;
+    *coo_dev = (const int32_t *)p.coo;
+    *node_ptr_dev = p.node_ptr;
+    *edge_ptr_dev = p.edge_ptr;
+    return GNNB_OK;
+}
+
+int gnnb_forward_pyg(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev,
+                     const int64_t *batch_dev, const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges, float *out_dev,
+                     void *stream)
+{
+    if (!model || !ws)
+        return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg");
+    const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
+    const int rc = gnnb_ingest_pyg(ws, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &coo, &node_ptr, &edge_ptr, stream);
+    if (rc != GNNB_OK)
+        return rc;
+    // the ingest has reported what EARLIER batches left; its own kernels may have flagged this batch by now, which is for the
+    // next call (or gnnb_workspace_check) to report, not for the prep of this one
+    ws->flags_reported = true;
+    const int frc = gnnb_forward_batched(model, ws, x_dev, coo, node_ptr, edge_ptr, num_graphs, num_nodes, num_edges, out_dev, stream);
+    ws->flags_reported = false;
+    return frc;
 }
 
 // CSR slots no row owns (edges dropped by graph prep -- explicit self loops on a GCN workspace -- leave a gap at the end of

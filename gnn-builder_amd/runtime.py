@@ -90,7 +90,18 @@ EXPORTED_SYMBOLS = [
     "gnnb_malloc", "gnnb_free", "gnnb_memcpy_h2d", "gnnb_memcpy_d2h", "gnnb_set_option",
     "gnnb_aggregate_timed", "gnnb_linear_timed", "gnnb_gcn_stack_timed",
     "gnnb_aggregate_edges", "gnnb_edge_index_table_to_host", "gnnb_debug_stream_k_guard", "gnnb_pna_product_aggregate",
+    "gnnb_ingest_bytes", "gnnb_workspace_enable_ingest", "gnnb_ingest_pyg", "gnnb_forward_pyg",
 ]
+
+# k_ingest.hip (gnnb_internal.h INGEST_TILE / INGEST_DIGIT_BITS): edges per workgroup and bits of the graph id per radix pass
+INGEST_TILE = 1024
+INGEST_DIGIT_BITS = 8
+
+
+def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
+    """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
+    (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
+    return int(load_library(require_gpu=False).gnnb_ingest_bytes(int(max_graphs), int(max_nodes), int(max_edges)))
 
 
 def build_library(force: bool = False) -> Path:
@@ -163,6 +174,13 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
         lib.gnnb_pna_product_aggregate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         lib.gnnb_gcn_stack_timed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                              C.POINTER(C.c_float)]
+        lib.gnnb_ingest_bytes.restype = C.c_size_t
+        lib.gnnb_ingest_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.gnnb_workspace_enable_ingest.argtypes = [C.c_void_p]
+        lib.gnnb_ingest_pyg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
+        lib.gnnb_forward_pyg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib = lib
     if require_gpu and _lib.gnnb_device_count() <= 0:
         raise GnnbUnavailable("libgnnb_hip.so loaded but no MI355X (HIP device) is visible; "
@@ -232,6 +250,15 @@ def _require(t, name: str, dtype, ndim: int, last: Optional[int] = None):
                         (f" with last dimension {last}" if last is not None else ""))
     if not t.is_contiguous():
         raise GnnbError(f"{name} must be contiguous")
+
+
+class _Borrowed:
+    """Device memory of a workspace as ``__cuda_array_interface__``: ``torch.as_tensor`` makes a view of it (no copy) that
+    keeps this object -- and through it the owner of the memory -- alive."""
+
+    def __init__(self, ptr: int, shape, owner):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
+        self._owner = owner
 
 
 class CompiledModel:
@@ -316,6 +343,7 @@ class CompiledModel:
         return int(self.lib.gnnb_workspace_bytes(self._ws))
 
     def close(self) -> None:
+        self._ingest_views = (None,)  # (they borrow the workspace: dropped with it)
         if getattr(self, "_ws", None):
             self.lib.gnnb_workspace_destroy(self._ws)
             self._ws = C.c_void_p()
@@ -424,6 +452,93 @@ class CompiledModel:
             self._model, self._ws, x.ctypes.data_as(C.c_void_p), coo.ctypes.data_as(C.c_void_p),
             node_ptr.ctypes.data_as(C.c_void_p), edge_ptr.ctypes.data_as(C.c_void_p), B, x.shape[0],
             coo.shape[0], out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    # ------------------------------------------------------------------ PyG mini-batches
+    def enable_ingest(self) -> None:
+        """One more device allocation (``ingest_bytes`` of the workspace's capacities) for ``ingest_pyg`` / ``forward_pyg``.
+        Synchronous: call it once, right after construction, outside stream capture."""
+        _check(self.lib.gnnb_workspace_enable_ingest(self._ws))
+        self._ingest = True
+        self._ingest_views = (None,)
+
+    def _pyg_args(self, edge_index, batch, ptr, num_graphs, num_nodes):
+        """Checks of a PyG mini-batch's index tensors (raw pointers cross the C ABI); returns (batch or None, ptr or None, B, N, E)."""
+        import torch
+        if not getattr(self, "_ingest", False):
+            raise GnnbError("ingest is not enabled on this model's workspace: call enable_ingest() once after construction")
+        if isinstance(edge_index, torch.Tensor) and edge_index.dim() == 2 and edge_index.shape[0] != 2 and edge_index.shape[1] == 2:
+            raise GnnbError(f"edge_index has shape {tuple(edge_index.shape)}: this is the [E, 2] coo layout; pass the PyG layout "
+                            "[2, E] (edge_index.t().contiguous()), or give the [E, 2] int32 rows to forward()")
+        _require(edge_index, "edge_index", torch.int64, 2)
+        if edge_index.shape[0] != 2:
+            raise GnnbError(f"edge_index has shape {tuple(edge_index.shape)}; expected [2, E]")
+        E = int(edge_index.shape[1])
+        B = None if num_graphs is None else int(num_graphs)
+        N = None if num_nodes is None else int(num_nodes)
+        if ptr is not None:
+            _require(ptr, "ptr", torch.int64, 1)
+            if ptr.numel() < 1 or (B is not None and B != ptr.numel() - 1):
+                raise GnnbError(f"ptr has {ptr.numel()} entries; expected num_graphs + 1")
+            B = int(ptr.numel()) - 1
+        if batch is not None:
+            _require(batch, "batch", torch.int64, 1)
+            if N is not None and N != batch.numel():
+                raise GnnbError(f"batch has {batch.numel()} entries; expected one per node ({N})")
+            N = int(batch.numel())
+            if B is None:
+                raise GnnbError("num_graphs is required when only `batch` is given (Batch.num_graphs): reading batch[-1] would be "
+                                "a .item() synchronisation hidden in the call; or pass `ptr` as well")
+            ptr = None  # (both given: ptr named B; the kernels look graph ids up in batch)
+        elif ptr is None:
+            if B is None:
+                B = 1
+            if B != 1:
+                raise GnnbError("a batch of more than one graph needs `batch` or `ptr`")
+        if N is None:
+            raise GnnbError("num_nodes is required when `batch` is not given (x.shape[0])")
+        return batch, ptr, B, N, E
+
+    def ingest_pyg(self, edge_index, batch=None, ptr=None, num_graphs=None, stream=None, num_nodes=None):
+        """A PyG mini-batch's ``edge_index`` [2, E] int64 with ``batch`` [N] int64 (plus ``num_graphs``: a host integer,
+        ``Batch.num_graphs``) or ``ptr`` [B+1] int64 (plus ``num_nodes``) -> ``(coo [E, 2], node_ptr [B+1], edge_ptr [B+1])``,
+        int32, computed on the device with no synchronisation -- what ``batching.from_pyg_batch`` computes on the host.  The three
+        tensors are VIEWS of this model's workspace: valid until the next ``ingest_pyg`` / ``forward_pyg``.  Malformed input is
+        flagged, not refused: ``check()`` raises (flag 0x80), and the arrays of a flagged batch are in range but unspecified."""
+        import torch
+        batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, num_nodes)
+        coo_p, np_p, ep_p = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self.lib.gnnb_ingest_pyg(self._ws, _dptr(edge_index), _dptr(batch) if batch is not None else None,
+                                        _dptr(ptr) if ptr is not None else None, B, N, E, C.byref(coo_p), C.byref(np_p), C.byref(ep_p),
+                                        _stream_ptr(stream)))
+        # views of the whole arrays are made once (the allocation never moves), every call slices them: no HIP call per ingest,
+        # so a warmed-up ingest_pyg can be captured into a graph
+        ptrs = (coo_p.value, np_p.value, ep_p.value)
+        if getattr(self, "_ingest_views", (None,))[0] != ptrs:
+            dev = edge_index.device
+            view = lambda p, shape: torch.as_tensor(_Borrowed(p, shape, self), device=dev)  # noqa: E731
+            self._ingest_views = (ptrs, view(ptrs[0], (max(self.max_edges, 1), 2)), view(ptrs[1], (self.max_graphs + 1,)),
+                                  view(ptrs[2], (self.max_graphs + 1,)))
+        _, coo, nptr, eptr = self._ingest_views
+        return coo[:E], nptr[:B + 1], eptr[:B + 1]
+
+    def forward_pyg(self, x, edge_index, batch=None, ptr=None, num_graphs=None, out=None, stream=None):
+        """``forward`` on a PyG mini-batch as the loader holds it on the GPU (``x`` [N, in_dim] fp32, ``edge_index`` [2, E]
+        int64, ``batch`` [N] int64 + ``num_graphs``, or ``ptr`` [B+1] int64): ingest and forward on one stream, no host
+        synchronisation (``gnnb_forward_pyg``).  The stage-level entry points work afterwards as after ``forward``."""
+        import torch
+        _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
+        batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, int(x.shape[0]))
+        if out is None:
+            out = torch.empty((B, self.out_dim), dtype=torch.float32, device=x.device)
+        else:
+            _require(out, "out", torch.float32, 2, self.out_dim)
+            if out.shape[0] != B or out.device != x.device:
+                raise GnnbError(f"out must be [{B}, {self.out_dim}] on {x.device}, got {tuple(out.shape)} on {out.device}")
+        _check(self.lib.gnnb_forward_pyg(self._model, self._ws, _dptr(x), _dptr(edge_index), _dptr(batch) if batch is not None else None,
+                                         _dptr(ptr) if ptr is not None else None, B, N, E, _dptr(out), _stream_ptr(stream)))
+        self._keep = None  # (the batch's index arrays live in the workspace)
+        self._N, self._E, self._B = N, E, B
         return out
 
     # ------------------------------------------------------------------ stage-level entry points

@@ -43,7 +43,8 @@ typedef enum gnnb_status {
     GNNB_ERR_HIP = -3,       /* a HIP runtime call failed */
     GNNB_ERR_NO_DEVICE = -4, /* no gfx950 device visible */
     GNNB_ERR_GRAPH = -5,     /* malformed batch: an edge leaves its graph, ptr not monotone, a broken max_graph_nodes
-                              * promise, a large-segment triple that disagrees with the ptr arrays */
+                              * promise, a large-segment triple that disagrees with the ptr arrays, a malformed PyG
+                              * mini-batch (gnnb_ingest_pyg) */
     GNNB_ERR_RANGE = -6      /* a REDUCED-precision math mode (gnnb_model_desc::math 2 / 3) produced a non-finite value: fp16's
                               * range (65504) was exceeded by an activation or a weight, or the inputs were not finite.  The
                               * results of that forward are unspecified; run the model with math = 0 (gnnb_workspace_check) */
@@ -240,6 +241,44 @@ int gnnb_forward_batched_host(const gnnb_model *model, gnnb_workspace *ws, const
 /* Device-side validation result of the last prep on this workspace (synchronises the
  * stream): GNNB_OK or GNNB_ERR_GRAPH. */
 int gnnb_workspace_check(gnnb_workspace *ws, void *stream);
+
+/* ------------------------------------------------------------------ PyG mini-batches, ingested on the device
+ * (new entry points at version 104: gnnb_model_desc and GNNB_VERSION are unchanged.)
+ * The reference hands its kernel ONE graph per call: code_gen.py:262 writes every graph's edge_index.T to a file of its own
+ * and the testbench calls <name>_top once per graph (model_tb.cpp.jinja:189-201).  A PyTorch-Geometric loader holds a whole
+ * mini-batch on the GPU instead -- edge_index [2, E] int64 with batch-global ids, edges in any order, and batch [N] int64
+ * (graph id per node, non-decreasing) or ptr [B+1] int64.  These entries turn that into the layout of gnnb_forward_batched ON
+ * THE DEVICE: node_ptr / edge_ptr [B+1] int32 and coo [E, 2] int32, edges grouped by the graph of their destination with the
+ * input order kept inside a graph (stable: the floating-point sum order of every aggregate depends on it) -- exactly what the
+ * host adapter gnnbuilder_amd.batching.from_pyg_batch returns.  num_graphs / num_nodes / num_edges are host integers
+ * (Batch.num_graphs and tensor shapes); no device value is read back, nothing synchronises, and the launch sequence depends on
+ * those three integers only: a captured graph replays on grouped and on shuffled batches alike.
+ *
+ * Validation, on the device (flag 128 of gnnb_workspace_check -> GNNB_ERR_GRAPH; the lazy report of the next
+ * gnnb_graph_prep / gnnb_ingest_pyg fires as for the other flags): an endpoint outside [0, N) (negative, or a value that
+ * would alias after narrowing such as 2^32 + 3), an edge whose endpoints lie in different graphs, a batch entry that
+ * decreases or lies outside [0, B), a ptr that is not monotone, does not start at 0 or does not end at N.  A flagged batch is
+ * CONTAINED: every output is written, node_ptr / edge_ptr are monotone from 0 to N / E, every coo entry lies in [0, N);
+ * its results are unspecified.
+ *
+ * gnnb_workspace_enable_ingest makes ONE device allocation of gnnb_ingest_bytes(max_graphs, max_nodes, max_edges) bytes -- the
+ * three outputs and the sort scratch; a pure function of the workspace's capacities -- owned by the workspace and freed with
+ * it; the main allocation and gnnb_workspace_bytes do not change.  Synchronous; call it outside stream capture, before the
+ * workspace is used (GNNB_ERR_INVALID once a batch has been prepared on it; a second call is a no-op). */
+size_t gnnb_ingest_bytes(int max_graphs, int max_nodes, int max_edges);
+int gnnb_workspace_enable_ingest(gnnb_workspace *ws);
+/* Exactly one of batch_dev / ptr_dev (the other NULL), or neither when num_graphs == 1.  Capacity is checked as by
+ * gnnb_graph_prep (GNNB_ERR_CAPACITY); GNNB_ERR_INVALID without gnnb_workspace_enable_ingest.  Empty batches (no edges, no
+ * nodes, no graphs) are fine.  The three returned device pointers address the workspace's ingest allocation: valid until the
+ * next ingest on this workspace. */
+int gnnb_ingest_pyg(gnnb_workspace *ws, const int64_t *edge_index_dev, const int64_t *batch_dev,
+                    const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges,
+                    const int32_t **coo_dev, const int32_t **node_ptr_dev, const int32_t **edge_ptr_dev, void *stream);
+/* gnnb_ingest_pyg followed by gnnb_forward_batched on `stream`: from the loader's tensors to out_dev [num_graphs, mlp_out]
+ * without a host synchronisation, a copy to the host or an allocation (x_dev: [num_nodes, in_dim] fp32). */
+int gnnb_forward_pyg(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev,
+                     const int64_t *batch_dev, const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges,
+                     float *out_dev, void *stream);
 
 /* ------------------------------------------------------------------ stage entry points
  * The individual kernels, for parity tests, profiling and the roofline measurement. */

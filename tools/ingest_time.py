@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Time of the device ingest of a PyG mini-batch (``CompiledModel.ingest_pyg``, csrc/k_ingest.hip) at the BASELINE config 2
+batch shape, beside the host route it replaces and the graph prep that follows it.
+
+  grouped    edge_index as ``Batch.from_data_list`` gives it (the fast path)
+  shuffled   the same edges under a seeded permutation (the radix grouping)
+  graph_prep ``gnnb_graph_prep`` on the ingested arrays, for scale
+  host       ``batching.from_pyg_batch`` on tensors brought from the device + the three copies back (wall clock)
+
+Device figures: HIP events around ``--calls`` back-to-back calls on one stream, microseconds per call, median of ``--repeats``
+(``*_us``: eager calls, which the host's enqueue rate can bound; ``*_graph_us``: the same calls captured into one HIP graph and
+replayed, the device's own time).
+``--out FILE`` also writes the JSON line to a file; under ``rocprofv3 --kernel-trace --stats`` use small ``--repeats``."""
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from gnnbuilder_amd import runtime, synthetic  # noqa: E402
+from gnnbuilder_amd.batching import from_pyg_batch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--workload", default="c2")
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=9)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    w = bench.WORKLOADS[args.workload]
+    dev = torch.device("cuda:0")
+    b = synthetic.make_batch(w["shape"], w["batch"], seed=0)
+    B, N, E = b.num_graphs, b.num_nodes, b.num_edges
+    cm = runtime.CompiledModel.from_model(bench.build_model(w), B, N, E, max_graph_nodes=int(np.diff(b.node_ptr).max()))
+    cm.enable_ingest()
+    x = torch.from_numpy(b.x).to(dev)
+    ei = np.ascontiguousarray(b.coo.T.astype(np.int64))
+    batch = torch.from_numpy(np.repeat(np.arange(B), np.diff(b.node_ptr)).astype(np.int64)).to(dev)
+    grouped = torch.from_numpy(ei).to(dev)
+    shuffled = torch.from_numpy(np.ascontiguousarray(ei[:, np.random.default_rng(0).permutation(E)])).to(dev)
+
+    timer = runtime.HipTimer()
+
+    def device_us(call, calls=None):
+        calls = calls or args.calls
+        for _ in range(min(calls, 20)):
+            call()
+        torch.cuda.synchronize()
+        per_call = []
+        for _ in range(args.repeats):
+            timer.start()
+            for _ in range(calls):
+                call()
+            timer.stop()
+            per_call.append(timer.elapsed_ms() * 1000.0 / calls)
+        return per_call
+
+    def graph_us(call, per_graph=20):
+        """`per_graph` calls captured once, replayed; None where the capture is refused."""
+        try:
+            side, graph = torch.cuda.Stream(), torch.cuda.CUDAGraph()
+            torch.cuda.synchronize()
+            with torch.cuda.graph(graph, stream=side):
+                for _ in range(per_graph):
+                    call()
+        except Exception as exc:  # noqa: BLE001
+            print(f"capture refused: {exc}", file=sys.stderr)
+            return None
+        replays = max(args.calls // per_graph, 1)
+        t = [v / per_graph for v in device_us(graph.replay, replays)]
+        return round(statistics.median(t), 2)
+
+    def host_route(edges):
+        t0 = time.perf_counter()
+        r = from_pyg_batch(np.zeros((N, 0), np.float32), edges.cpu().numpy(), batch=batch.cpu().numpy(), num_graphs=B)
+        out = [torch.from_numpy(a).to(dev) for a in (r.coo, r.node_ptr, r.edge_ptr)]
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6, out
+
+    # both paths give what the host adapter gives (exact), before anything is timed
+    for edges in (grouped, shuffled):
+        got = cm.ingest_pyg(edges, batch=batch, num_graphs=B)
+        cm.check()
+        _, ref = host_route(edges)
+        assert all(torch.equal(g, r) for g, r in zip(got, ref))
+
+    res = {"workload": args.workload, "graphs": B, "nodes": N, "edges": E, "calls": args.calls, "repeats": args.repeats,
+           "sort_passes": -(-max(B - 1, 0).bit_length() // runtime.INGEST_DIGIT_BITS), "ingest_bytes": runtime.ingest_bytes(B, N, E)}
+    for name, edges in (("grouped", grouped), ("shuffled", shuffled)):
+        t = device_us(lambda: cm.ingest_pyg(edges, batch=batch, num_graphs=B))
+        res[f"ingest_{name}_us"] = round(statistics.median(t), 2)
+        res[f"ingest_{name}_us_min_max"] = [round(min(t), 2), round(max(t), 2)]
+        res[f"ingest_{name}_graph_us"] = graph_us(lambda: cm.ingest_pyg(edges, batch=batch, num_graphs=B))
+    coo, nptr, eptr = cm.ingest_pyg(grouped, batch=batch, num_graphs=B)
+    t = device_us(lambda: cm.graph_prep(coo, nptr, eptr, N))
+    res["graph_prep_us"] = round(statistics.median(t), 2)
+    res["graph_prep_graph_us"] = graph_us(lambda: cm.graph_prep(coo, nptr, eptr, N))
+    t = device_us(lambda: cm.forward(x, coo, nptr, eptr))
+    res["forward_us"] = round(statistics.median(t), 2)
+    t = device_us(lambda: cm.forward_pyg(x, grouped, batch=batch, num_graphs=B))
+    res["forward_pyg_grouped_us"] = round(statistics.median(t), 2)
+    cm.check()
+    for name, edges in (("grouped", grouped), ("shuffled", shuffled)):
+        t = [host_route(edges)[0] for _ in range(max(args.repeats, 3))]
+        res[f"host_route_{name}_us"] = round(statistics.median(t), 1)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
