@@ -458,17 +458,7 @@ static hipError_t launch_conv_stack(const gnnb_model *model, gnnb_workspace *ws,
     return he;
 }
 
-// The readout of graphs [g0, B) from the pooled matrix in one launch (k_head_small / k_pool_mlp's pre-pooled form);
-// hipErrorNotSupported (nothing launched) when the head does not fit it
-static hipError_t launch_readout_pooled(const gnnb_model *model, gnnb_workspace *ws, int g0, float *out_dev, hipStream_t s)
-{
-    const gnnb_model_desc &d = model->desc;
-    const int gw = gnn_out_width(d);
-    return launch_pool_mlp(nullptr, ws->t.graph_ptr + g0, ws->t.num_graphs - g0, gw, d.pools, d.num_pools, model_head_args(model), d.mlp_activation,
-                           out_dev + (size_t)g0 * d.mlp_out, s, ws->pooled + (size_t)g0 * d.num_pools * gw);
-}
-
-// ... and as a plain GEMM chain (a head too large for the readout kernels; the fixed-point emulation, each layer's output put
+// The head as a plain GEMM chain (a head too large for the readout kernels; the fixed-point emulation, each layer's output put
 // on the grid).  On the stand-alone GEMM scratch: the head's GEMMs never use the workspace's stream-K scratch.
 static int run_head_chain(const gnnb_model *model, gnnb_workspace *ws, int g0, float *out_dev, void *stream)
 {
@@ -494,7 +484,10 @@ static int run_head_chain(const gnnb_model *model, gnnb_workspace *ws, int g0, f
 // this route).  what: the error text's name of the launch.
 static int readout_from_pooled(const gnnb_model *model, gnnb_workspace *ws, int g0, float *out_dev, void *stream, const char *what = "readout")
 {
-    GNNB_RUNG(attempt(launch_readout_pooled(model, ws, g0, out_dev, (hipStream_t)stream), what));
+    const gnnb_model_desc &d = model->desc;
+    const int gw = gnn_out_width(d);
+    GNNB_RUNG(attempt(launch_readout_pooled(ws->pooled + (size_t)g0 * d.num_pools * gw, ws->t.num_graphs - g0, gw, model_head_args(model), d.mlp_activation,
+                                            out_dev + (size_t)g0 * d.mlp_out, (hipStream_t)stream), what));
     return run_head_chain(model, ws, g0, out_dev, stream);
 }
 
@@ -528,9 +521,9 @@ static int readout_layerwise(const gnnb_model *model, gnnb_workspace *ws, const 
             return readout_from_pooled(model, ws, 0, out_dev, stream, "fused readout");
         }
         // pooling + whole MLP head in one launch when the head fits LDS
-        GNNB_RUNG(attempt(launch_pool_mlp(cur, ws->t.graph_ptr, B, gw, d.pools, d.num_pools, model_head_args(model), d.mlp_activation, out_dev,
-                                          (hipStream_t)stream), "fused readout"));
-        if (options().head_small) {
+        GNNB_RUNG(attempt(launch_readout_fused(cur, ws->t.graph_ptr, B, gw, d.pools, d.num_pools, model_head_args(model), d.mlp_activation, out_dev,
+                                               (hipStream_t)stream), "fused readout"));
+        if (readout_small_enabled()) {
             // The head's weights do not fit LDS (SAGE d = 256 with three pools: 768 x 64 floats): pooling pass, then
             // the small readout that takes its weights from L2 as MFMA operands -- one launch over B / 16 workgroups
             // instead of a chain of GEMMs with M = B rows (64 workgroups of the 128-row tile at B = 8192: 51 us)

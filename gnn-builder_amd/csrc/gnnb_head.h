@@ -1,12 +1,107 @@
-// gnnb_head.h -- the MLP head on pooled rows as a device function: k_head_small (k_readout.hip) runs it as a kernel of its
-// own, k_gcn2_zf (k_stack_zf.h) runs it at the end of every workgroup's life on the graphs that workgroup pooled (round 5:
-// conv stack + pooling + head in ONE launch -- reference compute_gnn_head -> compute_global_graph_pooling ->
-// compute_mlp_head inside one top, templates/model.cpp.jinja:737-765).
+// gnnb_head.h -- the readout's one header: the pooling selection, k_pool_mlp's swizzle and LDS carve, the launch plans of k_pool_mlp
+// and k_head_small, and the MLP head on pooled rows as a device function: k_head_small (k_readout.hip) runs it as a kernel of its
+// own, k_gcn2_zf (k_stack_zf.h) runs it at the end of every workgroup's life on the graphs that workgroup pooled (round 5: conv
+// stack + pooling + head in ONE launch -- reference compute_gnn_head -> compute_global_graph_pooling -> compute_mlp_head inside
+// one top, templates/model.cpp.jinja:737-765).
 #pragma once
 #include "gnnb_device.h"
+#include "gnnb_stack_plan.h"
 
 namespace gnnb {
 
+// ---- pooling: the requested reductions in `aggrs` order, k_pool_mlp's kernel argument by value
+struct PoolSel {
+    int kind[3];
+    int np;
+};
+static inline PoolSel pool_sel(const int32_t *pools, int num_pools)
+{
+    return PoolSel{{pools[0], num_pools > 1 ? pools[1] : 0, num_pools > 2 ? pools[2] : 0}, num_pools};
+}
+
+// (The ordered row walk -- seed from the first row, blocks of four, tail -- stays spelled in both pool kernels: as one
+// pool_rows<VEC, DEEP8> / pool_pick, by reference or by value, with or without __restrict__, k_global_pool schedules its address
+// arithmetic differently, and as a by-value argument PoolSel changes how it fetches its kernarg: it keeps p0, p1, p2, np.)
+
+// ---- k_pool_mlp's LDS plan
+static constexpr int HEAD_GRAPHS = 16;   // graphs per workgroup (one MFMA tile of rows), every readout form
+static constexpr int HEAD_THREADS = 512; // k_pool_mlp: 8 waves, 16 graphs pooled in parallel (32 lanes each at d=128)
+static constexpr size_t POOL_MLP_LDS_MAX = 158 * 1024; // (2 KB short of the CU's LDS)
+static_assert(POOL_MLP_LDS_MAX <= (size_t)STACK_LDS_MAX, "k_pool_mlp's dynamic LDS is one CU's");
+
+// largest power of two <= 16 dividing the number of 16-B chunks per row (1 = no swizzle)
+__device__ inline int head_swz_p(int k)
+{
+    if (k & 3)
+        return 1;
+    const int c = k >> 2;
+    int p = 1;
+    while (p < 16 && (c % (2 * p)) == 0)
+        p *= 2;
+    return p;
+}
+// float offset of element (row, k) in a [rows][kdim] LDS image with 16-B chunks XOR-swizzled
+__device__ inline int head_off(int row, int k, int kdim, int P)
+{
+    return row * kdim + ((((k >> 2) ^ (row & (P - 1))) << 2) | (k & 3));
+}
+
+// Carve (floats): two activation buffers [16][widest layer they hold] -- layer l reads buffer l & 1 and writes buffer (l + 1) & 1,
+// buffer 0 holds the pooled tile -- then every layer's matrix with its bias right behind it.  Filled by pool_mlp_carve on the
+// host, read by the kernel as one by-value argument.
+struct PoolMlpCarve {
+    int act0, act1; // floats of the two activation buffers
+    int woff[8];    // layer l's matrix, in floats behind the activation buffers
+    size_t bytes;   // everything
+    __host__ __device__ static size_t bias_off(int n, int k) { return ((size_t)n * k + 3) & ~(size_t)3; } // behind the [n][k] matrix
+    size_t total() const { return bytes; }
+    bool fits() const { return bytes <= POOL_MLP_LDS_MAX; }
+};
+static inline PoolMlpCarve pool_mlp_carve(const HeadArgs &head)
+{
+    PoolMlpCarve c = {};
+    int maxw[2] = {4, 4};
+    for (int l = 0; l <= head.nlin; l++)
+        maxw[l & 1] = std::max(maxw[l & 1], (int)head.dims[l]);
+    c.act0 = (HEAD_GRAPHS * maxw[0] + 3) & ~3;
+    c.act1 = (HEAD_GRAPHS * maxw[1] + 3) & ~3;
+    size_t wfl = 0;
+    for (int l = 0; l < head.nlin; l++) {
+        c.woff[l] = (int)wfl;
+        wfl += PoolMlpCarve::bias_off(head.dims[l + 1], head.dims[l]) + (((size_t)head.dims[l + 1] + 3) & ~(size_t)3);
+    }
+    c.bytes = ((size_t)c.act0 + c.act1 + wfl) * 4;
+    return c;
+}
+
+// launch_pool_mlp (k_pool_mlp, from the node matrix x or from a pooled matrix).  The first row that applies:
+//   | condition                                                                  | result            |
+//   |----------------------------------------------------------------------------|-------------------|
+//   | option fuse_head off; nlin outside 1..8; d % 4 != 0                        | not supported     |
+//   | the source (x / pooled) or a weight matrix not 16-B aligned                | not supported     |
+//   | from a pooled matrix and dims[0] % 4 != 0                                  | not supported     |
+//   | the carve does not fit POOL_MLP_LDS_MAX                                    | not supported     |
+//   | otherwise                                                                  | carve, lds = carve.total() |
+struct PoolMlpPlan {
+    bool ok = false;
+    PoolMlpCarve carve = {};
+};
+static inline PoolMlpPlan plan_pool_mlp(bool fuse_head, const HeadArgs &head, int d, const float *src, bool from_pooled)
+{
+    PoolMlpPlan p;
+    if (!fuse_head || head.nlin < 1 || head.nlin > 8 || (d & 3) || (((uintptr_t)src & 15) != 0))
+        return p;
+    if (from_pooled && (head.dims[0] & 3))
+        return p;
+    for (int l = 0; l < head.nlin; l++)
+        if (((uintptr_t)head.w[l] & 15) != 0)
+            return p;
+    p.carve = pool_mlp_carve(head);
+    p.ok = p.carve.fits();
+    return p;
+}
+
+// ---- the small-footprint head (operands from L2): shape test and LDS
 static constexpr int HS_MAXW = 128; // widest hidden layer this form takes
 
 // Host side: does the head take this form?  (float4 operand fetches: widths % 4, 16-B aligned weights; hidden activations
@@ -27,7 +122,21 @@ static inline int head_small_ldact(const HeadArgs &head)
     return ((maxw + 3) & ~3) + 4;
 }
 static inline size_t head_small_lds_bytes(int ldact) { return (size_t)2 * 16 * ldact * 4; } // per group of four waves
+// launch_head_small (k_head_small on a pooled matrix).  The first row that applies:
+//   | condition                                                                  | result            |
+//   |----------------------------------------------------------------------------|-------------------|
+//   | no pooled matrix, or not 16-B aligned                                      | not supported     |
+//   | nlin outside 1..8; a width dims[0 .. nlin - 1] % 4 != 0; a weight matrix not 16-B aligned; a hidden width > HS_MAXW | not supported |
+//   | otherwise                                                                  | ldact = widest hidden layer + 4 |
+static inline int plan_head_small(const HeadArgs &head, const float *pooled)
+{
+    return (!pooled || (((uintptr_t)pooled) & 15)) ? 0 : head_small_ldact(head);
+}
 
+// ---- the head on pooled rows, operands from L2
+// (head_small_run keeps its own k loop and both run functions their own epilogue: as one head_tile_mma<UW> / one epilogue function --
+// tried with the row pointer or the operand fetch chosen by the caller, the offset as a functor, base and offset passed apart, the
+// chains by value -- k_head_small and k_gcn2_zf<HEAD> come out with other schedules or register assignments; they are budgeted)
 // One 16 x 16 output tile of one linear over the k range [k_lo, k_hi) (multiples of 16, or k): acc += A[16 graphs][k] . W[nn][k]^T,
 // v_mfma_f32_16x16x4_f32, four accumulator chains over interleaved 16-wide k blocks, every operand fetch of a 64-wide k step in
 // flight at once.  arow = this lane's A row (+ 4 lg), wrow = its W row (+ 4 lg); k = the row length (a float4 past it is zero).

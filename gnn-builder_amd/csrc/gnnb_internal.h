@@ -332,10 +332,13 @@ hipError_t launch_conv_first(const BatchTables &t, int agg_kind, float eps, cons
 // the pieces of graphs that cross 32-row blocks -> pooled (and zeros for empty graphs); after launch_linear(..., pe)
 hipError_t launch_pool_combine(const PoolEpilogue &pe, int M, int N, hipStream_t s);
 
-// returns hipErrorNotSupported when the head does not fit the fused kernel (caller falls back)
-hipError_t launch_pool_mlp(const float *x, const int32_t *node_ptr, int num_graphs, int d,
-                           const int32_t *pools, int num_pools, const HeadArgs &head, int act,
-                           float *out, hipStream_t s, const float *prepooled = nullptr);
+// The readout in one launch (k_readout.hip); hipErrorNotSupported (nothing launched) when the head does not fit (caller falls back).
+// fused: pooling of x [., d] + head (k_pool_mlp).  pooled: the head on a pooled matrix [B, dims[0]] of node width d -- the ladder
+// k_head_small (readout_small_enabled()), then k_pool_mlp's pre-pooled form.
+hipError_t launch_readout_fused(const float *x, const int32_t *node_ptr, int num_graphs, int d, const int32_t *pools, int num_pools,
+                                const HeadArgs &head, int act, float *out, hipStream_t s);
+hipError_t launch_readout_pooled(const float *pooled, int num_graphs, int d, const HeadArgs &head, int act, float *out, hipStream_t s);
+bool readout_small_enabled(); // options fuse_head and head_small, read here only
 
 // Whole 2-layer GCN conv stack + pooling in one persistent launch (graphs staged once in LDS):
 // x -> agg -> W0 -> act -> agg -> W1 -> act -> pooled [B, np*h1].  hipErrorNotSupported when the

@@ -81,13 +81,9 @@ hipError_t launch_global_pool(const float *x, const int32_t *node_ptr, int num_g
     const int glog2 = lane_group_log2(nvec, 2);
     const int per_wg = WG >> glog2;
     const int grid = (num_graphs + per_wg - 1) / per_wg;
-    const int p0 = pools[0], p1 = num_pools > 1 ? pools[1] : 0, p2 = num_pools > 2 ? pools[2] : 0;
-    if (v4)
-        hipLaunchKernelGGL(k_global_pool<4>, dim3(grid), dim3(WG), 0, s, x, node_ptr, num_graphs, d,
-                           glog2, p0, p1, p2, num_pools, out);
-    else
-        hipLaunchKernelGGL(k_global_pool<1>, dim3(grid), dim3(WG), 0, s, x, node_ptr, num_graphs, d,
-                           glog2, p0, p1, p2, num_pools, out);
+    const PoolSel sel = pool_sel(pools, num_pools);
+    hipLaunchKernelGGL((v4 ? k_global_pool<4> : k_global_pool<1>), dim3(grid), dim3(WG), 0, s, x, node_ptr, num_graphs, d, glog2,
+                       sel.kind[0], sel.kind[1], sel.kind[2], sel.np, out);
     return hipGetLastError();
 }
 
@@ -106,42 +102,19 @@ hipError_t launch_global_pool(const float *x, const int32_t *node_ptr, int num_g
 //      from LDS, XOR-swizzled rows), activations staying in LDS,
 //   3. writes [16, OUT].
 // The pooled tile and the hidden activations never touch HBM.
-static constexpr int HEAD_GRAPHS = 16;
-static constexpr int HEAD_THREADS = 512; // 8 waves: 16 graphs pooled in parallel (32 lanes each at d=128)
-
-__device__ inline int head_swz_p(int k)
-{
-    // largest power of two <= 16 dividing the number of 16-B chunks per row (1 = no swizzle)
-    if (k & 3)
-        return 1;
-    const int c = k >> 2;
-    int p = 1;
-    while (p < 16 && (c % (2 * p)) == 0)
-        p *= 2;
-    return p;
-}
-// float offset of element (row, k) in a [rows][kdim] LDS image with 16-B chunks XOR-swizzled
-__device__ inline int head_off(int row, int k, int kdim, int P)
-{
-    return row * kdim + ((((k >> 2) ^ (row & (P - 1))) << 2) | (k & 3));
-}
-
+// (tile and thread counts, the swizzle and the LDS carve: gnnb_head.h)
 template <int ACT>
 __global__ __launch_bounds__(HEAD_THREADS) void k_pool_mlp(const float *__restrict__ x,
                                                  const int32_t *__restrict__ node_ptr, int B, int d,
-                                                 int glog2, int p0, int p1, int p2, int np,
-                                                 HeadArgs head, float *__restrict__ out,
-                                                 const float *__restrict__ prepooled,
-                                                 int act0_floats, int act1_floats, int woff0, int woff1, int woff2, int woff3,
-                                                 int woff4, int woff5, int woff6, int woff7)
+                                                 int glog2, PoolSel sel, HeadArgs head, float *__restrict__ out,
+                                                 const float *__restrict__ prepooled, PoolMlpCarve carve)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // buffer 0 holds the pooled tile and every even layer's output, buffer 1 the odd ones
     // (LDS pointers derived arithmetically from smem: a runtime-indexed pointer array turns the
     // accesses into FLAT loads that wait on vmcnt)
     float *const act_lo = reinterpret_cast<float *>(smem);
-    float *wbase = reinterpret_cast<float *>(smem) + (size_t)act0_floats + act1_floats;
-    const int woff[8] = {woff0, woff1, woff2, woff3, woff4, woff5, woff6, woff7};
+    float *wbase = reinterpret_cast<float *>(smem) + (size_t)carve.act0 + carve.act1;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
     const int g0 = blockIdx.x * HEAD_GRAPHS;
@@ -152,7 +125,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void k_pool_mlp(const float *__restri
     for (int l = 0; l < head.nlin; l++) {
         const int k = head.dims[l], n = head.dims[l + 1];
         const float *W = head.w[l];
-        float *dstf = wbase + woff[l];
+        float *dstf = wbase + carve.woff[l];
         if ((k & 3) == 0) {
             const int C = k >> 2, P = head_swz_p(k), nch = n * C;
             for (int c0 = wave * 64; c0 < nch; c0 += (HEAD_THREADS / 64) * 64) {
@@ -170,7 +143,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void k_pool_mlp(const float *__restri
                     dma4_to_lds(W + c0 + lane, reinterpret_cast<char *>(dstf) + (size_t)c0 * 4);
         }
         // bias right behind its matrix (zeros when the layer has none)
-        float *dstb = dstf + (((size_t)n * k + 3) & ~(size_t)3);
+        float *dstb = dstf + PoolMlpCarve::bias_off(n, k);
         if (head.b[l] != nullptr) {
             for (int c0 = wave * 64; c0 < n; c0 += (HEAD_THREADS / 64) * 64)
                 if (c0 + lane < n)
@@ -200,7 +173,6 @@ __global__ __launch_bounds__(HEAD_THREADS) void k_pool_mlp(const float *__restri
         const int G = 1 << glog2, groups = HEAD_THREADS >> glog2;
         const int grp = tid >> glog2, gl = tid & (G - 1);
         const int k0 = head.dims[0], P0 = head_swz_p(k0);
-        const int pools[3] = {p0, p1, p2};
         const int nvec = d >> 2;
         for (int gi = grp; gi < HEAD_GRAPHS; gi += groups) {
             const int g = g0 + gi;
@@ -242,12 +214,12 @@ __global__ __launch_bounds__(HEAD_THREADS) void k_pool_mlp(const float *__restri
                 const int n = n1 - n0;
 #pragma unroll
                 for (int kk = 0; kk < 3; kk++) {
-                    if (kk >= np)
+                    if (kk >= sel.np)
                         break;
                     V r = sum;
-                    if (pools[kk] == GNNB_POOL_MEAN)
+                    if (sel.kind[kk] == GNNB_POOL_MEAN)
                         r = n > 0 ? vdiv(sum, V::splat((float)n)) : V::splat(0.0f);
-                    else if (pools[kk] == GNNB_POOL_MAX)
+                    else if (sel.kind[kk] == GNNB_POOL_MAX)
                         r = mx;
                     r.store(act_lo + head_off(gi, kk * d + fo, k0, P0));
                 }
@@ -266,10 +238,10 @@ __global__ __launch_bounds__(HEAD_THREADS) void k_pool_mlp(const float *__restri
         const int k = head.dims[l], n = head.dims[l + 1];
         const bool last = (l == head.nlin - 1);
         const int Pk = head_swz_p(k), Pn = head_swz_p(n);
-        const float *sA = reinterpret_cast<const float *>(smem) + (cur ? act0_floats : 0);
-        float *sY = reinterpret_cast<float *>(smem) + (cur ? 0 : act0_floats);
-        const float *sW = wbase + woff[l];
-        const float *sbias = sW + (((size_t)n * k + 3) & ~(size_t)3); // staged next to the matrix
+        const float *sA = reinterpret_cast<const float *>(smem) + (cur ? carve.act0 : 0);
+        float *sY = reinterpret_cast<float *>(smem) + (cur ? 0 : carve.act0);
+        const float *sW = wbase + carve.woff[l];
+        const float *sbias = sW + PoolMlpCarve::bias_off(n, k); // staged next to the matrix
         const bool vec = (k & 3) == 0;
         for (int sl = wave; sl * 16 < n; sl += HEAD_THREADS / 64) {
             const int nn = sl * 16 + li; // this lane's output column (B-fragment row of W)
@@ -389,14 +361,18 @@ static constexpr int HS_THREADS = 256;
 // it by 4 us, and the stack kernel is the pipeline's critical resource: no gain)
 // The parameter block is the kernel's FIRST argument and is never named: the prep blocks read it from the kernarg segment
 // (offset 0), the head blocks never fetch it.
-// REGISTER BUDGET: 72 (a launch bound of seven waves per SIMD; 67 used).  Beside k_gcn2_zf's four 96-register waves a
-// SIMD has 128 registers left: this kernel's wave and a graph-prep wave (56) of the stream's next batch then run side by side
-// instead of one after the other -- BASELINE config 2, three batches in flight: 40.4-41.6 -> 37.6-37.7 us per step.
-static constexpr int HS_WAVES = 7; // waves per SIMD of the plain, paired-operand form (the register budget above)
-// PAIRS = false (option head_pairs = 0): four operand slices in flight, 82 registers -- the faster form when NOTHING shares the chip (one
-// stream of forwards: 49.8 vs 51.9 us per forward at BASELINE config 2), the slower one in the pipeline.
+// The three forms and their register budgets (the launcher's table picks one):
+//   plain, PAIRS     72 (a launch bound of seven waves per SIMD; 67 used).  Beside k_gcn2_zf's four 96-register waves a SIMD has
+//                    128 registers left: this kernel's wave and a graph-prep wave (56) of the stream's next batch then run side by
+//                    side instead of one after the other -- BASELINE config 2, three batches in flight: 40.4-41.6 -> 37.6-37.7 us
+//                    per step.
+//   plain, !PAIRS    (option head_pairs = 0) four operand slices in flight, 82 registers, five waves per SIMD -- the faster form
+//                    when NOTHING shares the chip (one stream of forwards: 49.8 vs 51.9 us per forward at BASELINE config 2),
+//                    the slower one in the pipeline.
+//   GUEST (PAIRS)    carries the prep's code: five waves per SIMD.
+static constexpr int HS_WAVES = 7; // waves per SIMD of the plain, paired-operand form
 template <int ACT, bool GUEST, bool PAIRS = true>
-__global__ __launch_bounds__(HS_THREADS, (GUEST || !PAIRS) ? 5 : HS_WAVES) /* (the guest form carries the prep's code) */ void k_head_small(PrepParams guest_kernarg, int prep_blocks, const float *__restrict__ pooled, int B,
+__global__ __launch_bounds__(HS_THREADS, (GUEST || !PAIRS) ? 5 : HS_WAVES) void k_head_small(PrepParams guest_kernarg, int prep_blocks, const float *__restrict__ pooled, int B,
                                                              HeadArgs head, float *__restrict__ out, int ldact)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -415,16 +391,20 @@ __global__ __launch_bounds__(HS_THREADS, (GUEST || !PAIRS) ? 5 : HS_WAVES) /* (t
                                        [] { __syncthreads(); });
 }
 
-// hipErrorNotSupported when the head's shape does not suit the small form (caller takes k_pool_mlp)
-static hipError_t launch_head_small(int num_graphs, const HeadArgs &head, int act, float *out, hipStream_t s,
-                                    const float *prepooled)
+// the readout's three options, each read here only
+struct ReadoutOpts {
+    bool fuse_head, head_small, head_pairs;
+};
+static ReadoutOpts readout_opts() { return ReadoutOpts{options().fuse_head != 0, options().head_small != 0, options().head_pairs != 0}; }
+bool readout_small_enabled() { return readout_opts().fuse_head && readout_opts().head_small; }
+
+// hipErrorNotSupported when the head's shape does not suit the small form (plan_head_small; the ladder goes on to k_pool_mlp)
+static hipError_t launch_head_small(const float *pooled, int num_graphs, const HeadArgs &head, int act, float *out, hipStream_t s)
 {
-    if (!prepooled || (((uintptr_t)prepooled) & 15))
-        return hipErrorNotSupported;
-    const int ldact = head_small_ldact(head);
+    const int ldact = plan_head_small(head, pooled);
     if (ldact <= 0)
         return hipErrorNotSupported;
-    const int grid = (num_graphs + 15) / 16;
+    const int grid = (num_graphs + HEAD_GRAPHS - 1) / HEAD_GRAPHS;
     // a guest graph prep on offer (gnnb_forward_prepared_prep_next)?
     GuestPrep *const gslot = guest_prep_slot();
     const bool guest = gslot && gslot->params && !gslot->taken && gslot->params->max_graph_nodes_hint > 0 && gslot->params->max_graph_nodes_hint <= 64;
@@ -436,14 +416,12 @@ static hipError_t launch_head_small(int num_graphs, const HeadArgs &head, int ac
         prep_blocks = prep_grid_blocks(gp.B + 1, 4, HS_THREADS);
     }
     const size_t lds = std::max(head_small_lds_bytes(ldact), guest ? (HS_THREADS / 64) * prep_wave_lds_ints(64) * sizeof(int32_t) : (size_t)0);
+    const bool pairs = readout_opts().head_pairs;
     auto go = [&](auto tag) {
         constexpr int ACT = decltype(tag)::value;
-        if (guest)
-            hipLaunchKernelGGL((k_head_small<ACT, true>), dim3(grid + prep_blocks), dim3(HS_THREADS), lds, s, gp, prep_blocks, prepooled, num_graphs, head, out, ldact);
-        else if (options().head_pairs)
-            hipLaunchKernelGGL((k_head_small<ACT, false>), dim3(grid), dim3(HS_THREADS), lds, s, gp, 0, prepooled, num_graphs, head, out, ldact);
-        else
-            hipLaunchKernelGGL((k_head_small<ACT, false, false>), dim3(grid), dim3(HS_THREADS), lds, s, gp, 0, prepooled, num_graphs, head, out, ldact);
+        // (guest, pairs) -> form: the guest form is paired whatever the option says
+        auto kern = guest ? k_head_small<ACT, true, true> : pairs ? k_head_small<ACT, false, true> : k_head_small<ACT, false, false>;
+        hipLaunchKernelGGL(kern, dim3(grid + prep_blocks), dim3(HS_THREADS), lds, s, gp, prep_blocks, pooled, num_graphs, head, out, ldact);
     };
     GNNB_DISPATCH_ACT(act, go)
     const hipError_t rc = hipGetLastError();
@@ -452,57 +430,44 @@ static hipError_t launch_head_small(int num_graphs, const HeadArgs &head, int ac
     return rc;
 }
 
-hipError_t launch_pool_mlp(const float *x, const int32_t *node_ptr, int num_graphs, int d,
-                           const int32_t *pools, int num_pools, const HeadArgs &head, int act,
-                           float *out, hipStream_t s, const float *prepooled)
+// k_pool_mlp from the node matrix (pooled == nullptr) or from the pooled matrix (x, node_ptr == nullptr)
+static hipError_t launch_pool_mlp(const float *x, const int32_t *node_ptr, const float *pooled, int num_graphs, int d, PoolSel sel,
+                                  const HeadArgs &head, int act, float *out, hipStream_t s)
 {
-    if (num_graphs <= 0)
-        return hipSuccess;
-    if (prepooled && options().fuse_head && options().head_small) {
-        const hipError_t e = launch_head_small(num_graphs, head, act, out, s, prepooled);
-        if (e != hipErrorNotSupported)
-            return e;
-    }
-    const float *src = prepooled ? prepooled : x;
-    if (!options().fuse_head || head.nlin < 1 || head.nlin > 8 || (d & 3) || (((uintptr_t)src & 15) != 0))
-        return hipErrorNotSupported;
-    if (prepooled && (head.dims[0] & 3))
-        return hipErrorNotSupported;
-    // LDS plan: two activation buffers [16][max width] + every weight matrix
-    int maxw0 = 4, maxw1 = 4; // layer l reads buffer l&1 and writes buffer (l+1)&1
-    for (int l = 0; l <= head.nlin; l++) {
-        if (l & 1)
-            maxw1 = std::max(maxw1, head.dims[l]);
-        else
-            maxw0 = std::max(maxw0, head.dims[l]);
-    }
-    const int act0_floats = (HEAD_GRAPHS * maxw0 + 3) & ~3, act1_floats = (HEAD_GRAPHS * maxw1 + 3) & ~3;
-    int woff[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    size_t wfl = 0;
-    for (int l = 0; l < head.nlin; l++) {
-        woff[l] = (int)wfl;
-        wfl += (((size_t)head.dims[l] * head.dims[l + 1] + 3) & ~(size_t)3) + (((size_t)head.dims[l + 1] + 3) & ~(size_t)3);
-        if (((uintptr_t)head.w[l] & 15) != 0)
-            return hipErrorNotSupported;
-    }
-    const size_t lds = ((size_t)act0_floats + act1_floats + wfl) * 4;
-    if (lds > 158 * 1024)
-        return hipErrorNotSupported; // head too large for the fused kernel: caller uses pool + GEMMs
+    const PoolMlpPlan p = plan_pool_mlp(readout_opts().fuse_head, head, d, pooled ? pooled : x, pooled != nullptr);
+    if (!p.ok)
+        return hipErrorNotSupported; // (a head too large for LDS among the reasons: the caller uses pool + GEMMs)
+    const size_t lds = p.carve.total();
     const int glog2 = lane_group_log2(d >> 2, 2);
     const int grid = (num_graphs + HEAD_GRAPHS - 1) / HEAD_GRAPHS;
-    const int p0 = pools[0], p1 = num_pools > 1 ? pools[1] : 0, p2 = num_pools > 2 ? pools[2] : 0;
     auto go = [&](auto tag) {
         constexpr int ACT = decltype(tag)::value;
         auto kern = k_pool_mlp<ACT>;
         (void)ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(HEAD_THREADS), lds, s, x, node_ptr, num_graphs, d, glog2, p0, p1, p2,
-                           num_pools, head, out, prepooled, act0_floats, act1_floats, woff[0], woff[1], woff[2], woff[3], woff[4], woff[5],
-                           woff[6], woff[7]);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(HEAD_THREADS), lds, s, x, node_ptr, num_graphs, d, glog2, sel, head, out, pooled, p.carve);
     };
     GNNB_DISPATCH_ACT(act, go)
     return hipGetLastError();
 }
 
+hipError_t launch_readout_fused(const float *x, const int32_t *node_ptr, int num_graphs, int d, const int32_t *pools, int num_pools,
+                                const HeadArgs &head, int act, float *out, hipStream_t s)
+{
+    if (num_graphs <= 0)
+        return hipSuccess;
+    return launch_pool_mlp(x, node_ptr, nullptr, num_graphs, d, pool_sel(pools, num_pools), head, act, out, s);
+}
 
+hipError_t launch_readout_pooled(const float *pooled, int num_graphs, int d, const HeadArgs &head, int act, float *out, hipStream_t s)
+{
+    if (num_graphs <= 0)
+        return hipSuccess;
+    if (readout_small_enabled()) {
+        const hipError_t e = launch_head_small(pooled, num_graphs, head, act, out, s);
+        if (e != hipErrorNotSupported)
+            return e;
+    }
+    return launch_pool_mlp(nullptr, nullptr, pooled, num_graphs, d, PoolSel{}, head, act, out, s);
+}
 
 } // namespace gnnb

@@ -15,7 +15,7 @@ Where each form is reached (gnnb_runtime.hip ``build_gemm``, gemm_launch.hip ``l
   * scalar aggregate / pooling / GINE forms (``v4`` = 0): odd widths and the offset x / self_dev / out views;
   * the ring aggregate's ``big`` direct path (a node tile larger than a stage): widths 1024 and 2048 (PNA: 1024), where
     ``cap = 158 KB / slots / per_row`` is below a node tile's rows for most tiles, and the 300-node graph's hub tile;
-  * the ``launch_pool_mlp`` GEMM-chain fallback: every model of ``test_wide_and_odd_models`` (a head of > 158 KB of weights, or
+  * the GEMM-chain fallback behind ``launch_readout_fused``: every model of ``test_wide_and_odd_models`` (a head of > 158 KB of weights, or
     a pooled width ``d`` that is not a multiple of 4); ``fuse_head = 0`` forces the same chain and must agree.
 """
 import contextlib

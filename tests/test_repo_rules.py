@@ -86,3 +86,30 @@ def test_kernel_sources_carry_no_build_switches_beyond_the_named_ones():
                 if name != "defined" and name not in allowed and (i, name) != guard:
                     offenders.append(f"{p.name}:{i + 1}: {name}")
     assert not offenders, offenders
+
+
+def test_every_header_rebuilds_the_objects_that_include_it(tmp_path):
+    """A header missing from the Makefile's list left k_readout.o and the two k_stack_zf objects stale after an edit to
+    gnnb_head.h.  The list is derived now: for every csrc/*.h, ``make -n -W <header>`` names at least one object to rebuild, and
+    for gnnb_head.h exactly the units that include it, directly or through k_stack_zf.h.  Runs against stand-in objects in a
+    scratch directory (newer than every source), so that a tree that has not been built answers the same; -n -W neither
+    touches nor builds anything."""
+    import subprocess
+    csrc = ROOT / "gnn-builder_amd" / "csrc"
+    units = re.search(r"^UNITS := (.*)$", (csrc / "Makefile").read_text(), re.M).group(1).split()
+    (tmp_path / "flags.stamp").touch()
+    for u in units:
+        (tmp_path / f"{u}.o").touch()
+
+    def rebuilt(header):
+        out = subprocess.run(["make", "-C", str(csrc), "-n", "-W", header, "-o", str(tmp_path / "flags.stamp"), f"OBJDIR={tmp_path}",
+                              f"OUT={tmp_path / 'lib.so'}"], capture_output=True, text=True, check=True).stdout
+        return sorted(re.findall(r" -c -o \S*/(\w+)\.o ", out))
+
+    assert rebuilt("no_such_header.h") == []
+    headers = sorted(p.name for p in csrc.glob("*.h"))
+    assert "gnnb_head.h" in headers and len(headers) > 8
+    for h in headers:
+        assert rebuilt(h), h
+    assert rebuilt("gnnb_head.h") == ["k_readout", "k_stack_zf", "k_stack_zf_head"]
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(["flags.stamp"] + [f"{u}.o" for u in units])
