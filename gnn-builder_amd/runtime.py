@@ -21,13 +21,21 @@ PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("GNNB_HIP_LIB", PKG_DIR / "libgnnb_hip.so"))  # override: diagnostic builds only
 CSRC_DIR = PKG_DIR / "csrc"
 
-CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}
-ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}
-POOL = {"add": 0, "mean": 1, "max": 2}
-OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}
-AGG = {"gcn": 0, "sum": 1, "mean": 2, "pna": 3, "lg": 4, "simple": 5, "copy": 6}
-
-GNNB_OK = 0
+# ---------------------------------------------------------------------- values restated from the C headers
+# (tests/test_abi.py reads include/gnnb_hip.h and csrc/gnnb_internal.h and compares every one of them)
+GNNB_OK = 0                                                                      # gnnb_status
+GNNB_ERR_RANGE = -6                                                              # gnnb_status
+CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                 # gnnb_conv
+ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
+POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
+OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
+AGG = {"gcn": 0, "sum": 1, "mean": 2, "pna": 3, "lg": 4, "simple": 5, "copy": 6}  # gnnb_agg
+MATH_MODES = {"fp32": 0, "bf16x6": 1, "bf16x3": 2, "f16x3": 3}                   # gnnb_model_desc::math (no enum: its comment)
+PATH_NAMES = {0: "none", 1: "layerwise", 2: "stack", 3: "stack_zf"}              # GNNB_PATH_* (the anonymous enum), low bits
+PATH_LARGE_LAYERWISE = 16                                                        # GNNB_PATH_LARGE_LAYERWISE: a flag or-ed to them
+# k_ingest.hip (gnnb_internal.h INGEST_TILE / INGEST_DIGIT_BITS): edges per workgroup and bits of the graph id per radix pass
+INGEST_TILE = 1024
+INGEST_DIGIT_BITS = 8
 
 
 class GnnbError(RuntimeError):
@@ -36,6 +44,11 @@ class GnnbError(RuntimeError):
 
 class GnnbUnavailable(GnnbError):
     """The HIP extension or the GPU is missing: the product path cannot run (no fallback)."""
+
+
+class GnnbRangeError(GnnbError):
+    """A reduced-precision math mode (bf16x3 / f16x3) produced a non-finite value (``GNNB_ERR_RANGE``): fp16's range was
+    exceeded by an activation or a weight.  The flagged forward's results are unspecified; run the model with math="fp32"."""
 
 
 class ModelDesc(C.Structure):
@@ -63,39 +76,64 @@ class ModelDesc(C.Structure):
     ]
 
 
-MATH_MODES = {"fp32": 0, "bf16x6": 1, "bf16x3": 2, "f16x3": 3}  # gnnb_model_desc::math (include/gnnb_hip.h)
-GNNB_ERR_RANGE = -6
-
-
-class GnnbRangeError(GnnbError):
-    """A reduced-precision math mode (bf16x3 / f16x3) produced a non-finite value (``GNNB_ERR_RANGE``): fp16's range was
-    exceeded by an activation or a weight.  The flagged forward's results are unspecified; run the model with math="fp32"."""
-
-
 class GemmSeg(C.Structure):
     _fields_ = [("a_dev", C.c_void_p), ("rowscale_dev", C.c_void_p), ("lda", C.c_int32), ("k", C.c_int32)]
 
 
-# every symbol include/gnnb_hip.h declares (tests check the .so exports each one)
-PATH_NAMES = {0: "none", 1: "layerwise", 2: "stack", 3: "stack_zf"}  # gnnb_hip.h GNNB_PATH_*
-
-EXPORTED_SYMBOLS = [
-    "gnnb_version", "gnnb_last_error", "gnnb_device_count", "gnnb_stream_sync",
-    "gnnb_model_num_params", "gnnb_model_create", "gnnb_model_destroy", "gnnb_model_get_desc",
-    "gnnb_workspace_create", "gnnb_workspace_destroy", "gnnb_workspace_bytes", "gnnb_workspace_set_max_graph_nodes", "gnnb_workspace_set_max_degree",
-    "gnnb_workspace_last_path", "gnnb_workspace_set_large_segment",
-    "gnnb_forward_batched", "gnnb_forward_prepared", "gnnb_forward_prepared_prep_next", "gnnb_forward_batched_host", "gnnb_workspace_check",
-    "gnnb_graph_prep", "gnnb_graph_tables_to_host", "gnnb_aggregate", "gnnb_linear", "gnnb_global_pool",
-    "gnnb_event_create", "gnnb_event_record", "gnnb_event_elapsed_ms", "gnnb_event_destroy",
-    "gnnb_malloc", "gnnb_free", "gnnb_memcpy_h2d", "gnnb_memcpy_d2h", "gnnb_set_option",
-    "gnnb_aggregate_timed", "gnnb_linear_timed", "gnnb_gcn_stack_timed",
-    "gnnb_aggregate_edges", "gnnb_edge_index_table_to_host", "gnnb_debug_stream_k_guard", "gnnb_pna_product_aggregate",
-    "gnnb_ingest_bytes", "gnnb_workspace_enable_ingest", "gnnb_ingest_pyg", "gnnb_forward_pyg",
-]
-
-# k_ingest.hip (gnnb_internal.h INGEST_TILE / INGEST_DIGIT_BITS): edges per workgroup and bits of the graph id per radix pass
-INGEST_TILE = 1024
-INGEST_DIGIT_BITS = 8
+# ---------------------------------------------------------------------- the C ABI: every function of include/gnnb_hip.h
+# name -> (restype, argtypes), in the header's order; load_library applies it, tests/test_abi.py compares it with the header's
+# prototypes (no library needed).  A function left without argtypes takes a Python integer as a C int: a pointer or a size_t
+# from 2 GiB up would be truncated -- so none is left without.
+_P, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_PP, _PF, _DESC = C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.POINTER(ModelDesc)
+ABI = {
+    "gnnb_version": (_I, []),
+    "gnnb_last_error": (C.c_char_p, []),
+    "gnnb_device_count": (_I, []),
+    "gnnb_stream_sync": (_I, [_P]),
+    "gnnb_model_num_params": (_I, [_DESC]),
+    "gnnb_model_create": (_I, [_DESC, _PP, _I, _PP]),
+    "gnnb_model_destroy": (None, [_P]),
+    "gnnb_model_get_desc": (_I, [_P, _DESC]),
+    "gnnb_workspace_create": (_I, [_P, _I, _I, _I, _PP]),
+    "gnnb_workspace_destroy": (None, [_P]),
+    "gnnb_workspace_bytes": (_Z, [_P]),
+    "gnnb_workspace_set_max_graph_nodes": (_I, [_P, _I]),
+    "gnnb_workspace_set_max_degree": (_I, [_P, _I]),
+    "gnnb_workspace_last_path": (_I, [_P]),
+    "gnnb_workspace_set_large_segment": (_I, [_P, _I, _I, _I]),
+    "gnnb_forward_batched": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "gnnb_forward_prepared": (_I, [_P, _P, _P, _P, _P]),
+    "gnnb_forward_prepared_prep_next": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "gnnb_forward_batched_host": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "gnnb_workspace_check": (_I, [_P, _P]),
+    "gnnb_ingest_bytes": (_Z, [_I, _I, _I]),
+    "gnnb_workspace_enable_ingest": (_I, [_P]),
+    "gnnb_ingest_pyg": (_I, [_P, _P, _P, _P, _I, _I, _I, _PP, _PP, _PP, _P]),
+    "gnnb_forward_pyg": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "gnnb_graph_prep": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "gnnb_graph_tables_to_host": (_I, [_P, _P, _P, _P, _P]),
+    "gnnb_aggregate": (_I, [_P, _I, _P, _P, _P, _I, _F, _P]),
+    "gnnb_pna_product_aggregate": (_I, [_P, _P, _P, _I, _P, _I, _P]),
+    "gnnb_aggregate_edges": (_I, [_P, _P, _P, _P, _I, _F, _P]),
+    "gnnb_edge_index_table_to_host": (_I, [_P, _P, _P]),
+    "gnnb_linear": (_I, [C.POINTER(GemmSeg), _I, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "gnnb_debug_stream_k_guard": (_I, [_P, _P]),
+    "gnnb_global_pool": (_I, [_P, _P, _I, C.POINTER(C.c_int32), _I, _P, _P]),
+    "gnnb_event_create": (_I, [_PP]),
+    "gnnb_event_record": (_I, [_P, _P]),
+    "gnnb_event_elapsed_ms": (_I, [_P, _P, _PF]),
+    "gnnb_event_destroy": (None, [_P]),
+    "gnnb_aggregate_timed": (_I, [_P, _I, _P, _P, _P, _I, _I, _F, _I, _P, _PF]),
+    "gnnb_linear_timed": (_I, [_P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _PF]),
+    "gnnb_gcn_stack_timed": (_I, [_P, _P, _P, _I, _P, _PF]),
+    "gnnb_malloc": (_I, [_PP, _Z]),
+    "gnnb_free": (None, [_P]),
+    "gnnb_memcpy_h2d": (_I, [_P, _P, _Z, _P]),
+    "gnnb_memcpy_d2h": (_I, [_P, _P, _Z, _P]),
+    "gnnb_set_option": (_I, [C.c_char_p, _I]),
+}
+EXPORTED_SYMBOLS = list(ABI)  # (tests check the .so exports each one)
 
 
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
@@ -129,58 +167,9 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
                 "or `make -C gnn-builder_amd/csrc`.  There is no CPU fallback.")
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
-        lib.gnnb_last_error.restype = C.c_char_p
-        lib.gnnb_workspace_bytes.restype = C.c_size_t
-        lib.gnnb_workspace_bytes.argtypes = [C.c_void_p]
-        lib.gnnb_model_destroy.argtypes = [C.c_void_p]
-        lib.gnnb_model_destroy.restype = None
-        lib.gnnb_workspace_destroy.argtypes = [C.c_void_p]
-        lib.gnnb_workspace_destroy.restype = None
-        lib.gnnb_event_destroy.argtypes = [C.c_void_p]
-        lib.gnnb_event_destroy.restype = None
-        lib.gnnb_free.argtypes = [C.c_void_p]
-        lib.gnnb_free.restype = None
-        lib.gnnb_forward_batched.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        lib.gnnb_forward_prepared.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.gnnb_forward_prepared_prep_next.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                        C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        lib.gnnb_graph_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                        C.c_int, C.c_float, C.c_void_p]
-        lib.gnnb_aggregate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                       C.c_float, C.c_void_p]
-        lib.gnnb_linear.argtypes = [C.POINTER(GemmSeg), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        lib.gnnb_global_pool.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int,
-                                         C.c_void_p, C.c_void_p]
-        lib.gnnb_graph_tables_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.gnnb_workspace_check.argtypes = [C.c_void_p, C.c_void_p]
-        lib.gnnb_event_record.argtypes = [C.c_void_p, C.c_void_p]
-        lib.gnnb_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-        lib.gnnb_stream_sync.argtypes = [C.c_void_p]
-        lib.gnnb_set_option.argtypes = [C.c_char_p, C.c_int]
-        lib.gnnb_workspace_set_max_graph_nodes.argtypes = [C.c_void_p, C.c_int]
-        lib.gnnb_workspace_set_max_degree.argtypes = [C.c_void_p, C.c_int]
-        lib.gnnb_workspace_last_path.argtypes = [C.c_void_p]
-        lib.gnnb_workspace_set_large_segment.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        lib.gnnb_aggregate_timed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                             C.c_int, C.c_float, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
-        lib.gnnb_linear_timed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                          C.POINTER(C.c_float)]
-        lib.gnnb_aggregate_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
-        lib.gnnb_edge_index_table_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.gnnb_debug_stream_k_guard.argtypes = [C.c_void_p, C.c_void_p]
-        lib.gnnb_pna_product_aggregate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        lib.gnnb_gcn_stack_timed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                             C.POINTER(C.c_float)]
-        lib.gnnb_ingest_bytes.restype = C.c_size_t
-        lib.gnnb_ingest_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        lib.gnnb_workspace_enable_ingest.argtypes = [C.c_void_p]
-        lib.gnnb_ingest_pyg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
-        lib.gnnb_forward_pyg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        for name, (restype, argtypes) in ABI.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
     if require_gpu and _lib.gnnb_device_count() <= 0:
         raise GnnbUnavailable("libgnnb_hip.so loaded but no MI355X (HIP device) is visible; "
@@ -237,6 +226,11 @@ def _dptr(t) -> int:
     return int(t.data_ptr())
 
 
+def _optr(t) -> Optional[int]:
+    """Device pointer of an operand the header lets be NULL."""
+    return _dptr(t) if t is not None else None
+
+
 def _require(t, name: str, dtype, ndim: int, last: Optional[int] = None):
     """A raw pointer crosses the C ABI: a tensor of another dtype / layout / device would be silently reinterpreted
     (a PyG edge_index, int64 [2, E], read as int32 [E, 2] is garbage edges) -- refuse it here."""
@@ -250,6 +244,38 @@ def _require(t, name: str, dtype, ndim: int, last: Optional[int] = None):
                         (f" with last dimension {last}" if last is not None else ""))
     if not t.is_contiguous():
         raise GnnbError(f"{name} must be contiguous")
+
+
+def _require_rows(t, name: str, rows: int, width: int, like) -> None:
+    """``_require`` for a second input that the kernels read as exactly [rows, width] fp32 beside ``like``."""
+    import torch
+    _require(t, name, torch.float32, 2, width)
+    if t.shape[0] != rows or t.device != like.device:
+        raise GnnbError(f"{name} must be [{rows}, {width}] on {like.device}, got {tuple(t.shape)} on {t.device}")
+
+
+def _out(out, rows: int, width: int, x):
+    """The result tensor of an entry point: a new [rows, width] fp32 one on ``x``'s device, or the caller's, checked to be that
+    (on the forwards' issue path: no call deeper than ``_require``)."""
+    import torch
+    if out is None:
+        return torch.empty((rows, width), dtype=torch.float32, device=x.device)
+    _require(out, "out", torch.float32, 2, width)
+    if out.shape[0] != rows or out.device != x.device:
+        raise GnnbError(f"out must be [{rows}, {width}] on {x.device}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def _require_strided(t, name: str, rows: Optional[int] = None, min_cols: int = 0) -> None:
+    """A matrix whose row stride crosses the ABI beside its pointer (``lda`` / ``ldw``): fp32, CUDA, 2-D with unit column
+    stride -- a column slice of a wider buffer is legal, a transposed or column-strided view is not."""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or \
+            (t.shape[1] > 1 and t.stride(1) != 1):
+        raise GnnbError(f"{name} must be a 2-D float32 CUDA (HIP) tensor with unit column stride")
+    if (rows is not None and t.shape[0] != rows) or t.shape[1] < min_cols:
+        raise GnnbError(f"{name} has shape {tuple(t.shape)}; expected " +
+                        (f"at least {min_cols} columns" if rows is None else f"{rows} rows"))
 
 
 class _Borrowed:
@@ -267,9 +293,15 @@ class CompiledModel:
 
     def __init__(self, spec: dict, params: Sequence, max_graphs: int, max_nodes: int, max_edges: int,
                  max_graph_nodes: int = 0):
+        # every attribute first: close() / __del__ also run on an object whose construction raised part-way
+        self.lib = None
+        self._model, self._ws = C.c_void_p(), C.c_void_p()
+        self._B = self._N = self._E = 0  # sizes of the prepared batch (_prepared)
+        self._keep = None  # its index tensors, which the device still reads
+        self._ingest, self._ingest_views = False, (None,)
+        self.spec, self.desc = dict(spec), None
+        self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
-        self._N = self._E = self._B = 0  # sizes of the prepared batch (graph_prep / forward)
-        self.spec = dict(spec)
         self.desc = make_desc(spec)
         host = [np.ascontiguousarray(np.asarray(p.detach().cpu().numpy() if hasattr(p, "detach") else p,
                                                 dtype=np.float32)) for p in params]
@@ -279,16 +311,11 @@ class CompiledModel:
         if len(host) != n_expect:
             raise GnnbError(f"model needs {n_expect} parameter tensors, got {len(host)}")
         arr = (C.c_void_p * len(host))(*[h.ctypes.data for h in host])
-        self._model = C.c_void_p()
         _check(self.lib.gnnb_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
-        self._ws = C.c_void_p()
-        rc = self.lib.gnnb_workspace_create(self._model, int(max_graphs), int(max_nodes), int(max_edges),
-                                            C.byref(self._ws))
+        rc = self.lib.gnnb_workspace_create(self._model, self.max_graphs, self.max_nodes, self.max_edges, C.byref(self._ws))
         if rc != GNNB_OK:
-            self.lib.gnnb_model_destroy(self._model)
-            self._model = C.c_void_p()
+            self.close()
             _check(rc)
-        self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         if max_graph_nodes:
             self.set_max_graph_nodes(max_graph_nodes)
 
@@ -326,7 +353,7 @@ class CompiledModel:
         """Which kernels the last forward on this workspace ran: "layerwise", "stack" (k_gcn2_fused) or "stack_zf"
         (k_gcn2_zf); "none" before the first forward.  Diagnostics only."""
         v = int(self.lib.gnnb_workspace_last_path(self._ws))
-        return PATH_NAMES.get(v & 15, "?") + ("+large_layerwise" if v & 16 else "")
+        return PATH_NAMES.get(v & (PATH_LARGE_LAYERWISE - 1), "?") + ("+large_layerwise" if v & PATH_LARGE_LAYERWISE else "")
 
     def set_large_segment(self, first_graph: int = -1, first_node: int = -1, first_edge: int = -1) -> None:
         """Graphs [first_graph, B) of the following batches are exempt from the max_graph_nodes promise and run layer by
@@ -344,10 +371,10 @@ class CompiledModel:
 
     def close(self) -> None:
         self._ingest_views = (None,)  # (they borrow the workspace: dropped with it)
-        if getattr(self, "_ws", None):
+        if self._ws:
             self.lib.gnnb_workspace_destroy(self._ws)
             self._ws = C.c_void_p()
-        if getattr(self, "_model", None):
+        if self._model:
             self.lib.gnnb_model_destroy(self._model)
             self._model = C.c_void_p()
 
@@ -358,6 +385,18 @@ class CompiledModel:
             pass
 
     # ------------------------------------------------------------------ whole forward
+    def _prepared(self, B: int, N: int, E: int, keep) -> None:
+        """The workspace now holds the tables of a batch of these sizes: the stage-level entry points may follow, and check their
+        operands against them.  ``keep``: the batch's index tensors, which the device reads for as long as the batch is prepared."""
+        self._B, self._N, self._E, self._keep = B, N, E, keep
+
+    def _require_x(self, x, width: Optional[int] = None) -> None:
+        """``x`` of an entry point that runs on the prepared batch: the kernels read a row of it for every node of that batch."""
+        import torch
+        _require(x, "x", torch.float32, 2, width)
+        if int(x.shape[0]) != self._N:
+            raise GnnbError(f"x has {int(x.shape[0])} rows, the prepared batch has {self._N} nodes")
+
     def forward(self, x, coo, node_ptr, edge_ptr, out=None, stream=None):
         """All arguments are torch CUDA tensors (fp32 / int32, contiguous; ``coo`` is [E, 2] (src, dst) rows, NOT a PyG
         ``edge_index`` [2, E] -- transpose it); returns ``out`` [B, mlp_out].  Asynchronous on the current torch stream.
@@ -365,20 +404,13 @@ class CompiledModel:
         the results of a flagged batch are unspecified.  Without a ``check()`` the flag still surfaces: the next call
         on this workspace after a flagged batch has run raises ``GnnbError`` ("an earlier batch ...", no synchronisation,
         best effort)."""
-        import torch
         self._check_batch(x, coo, node_ptr, edge_ptr)
         B = int(node_ptr.numel()) - 1
         N, E = int(x.shape[0]), int(coo.shape[0])
-        if out is None:
-            out = torch.empty((B, self.out_dim), dtype=torch.float32, device=x.device)
-        else:
-            _require(out, "out", torch.float32, 2, self.out_dim)
-            if out.shape[0] != B or out.device != x.device:
-                raise GnnbError(f"out must be [{B}, {self.out_dim}] on {x.device}, got {tuple(out.shape)} on {out.device}")
+        out = _out(out, B, self.out_dim, x)
         _check(self.lib.gnnb_forward_batched(self._model, self._ws, _dptr(x), _dptr(coo), _dptr(node_ptr),
                                              _dptr(edge_ptr), B, N, E, _dptr(out), _stream_ptr(stream)))
-        self._keep = (coo, node_ptr, edge_ptr)
-        self._N, self._E, self._B = N, E, B  # (the batch is prepared now: the stage-level entry points may follow)
+        self._prepared(B, N, E, (coo, node_ptr, edge_ptr))
         return out
 
     def _check_batch(self, x, coo, node_ptr, edge_ptr) -> None:
@@ -393,24 +425,14 @@ class CompiledModel:
 
     def graph_prep(self, coo, node_ptr, edge_ptr, num_nodes: int, stream=None) -> None:
         self._check_batch(None, coo, node_ptr, edge_ptr)
-        B = int(node_ptr.numel()) - 1
-        self._keep = (coo, node_ptr, edge_ptr)
-        _check(self.lib.gnnb_graph_prep(self._ws, _dptr(coo), _dptr(node_ptr), _dptr(edge_ptr), B,
-                                        int(num_nodes), int(coo.shape[0]), float(self.desc.pna_delta),
-                                        _stream_ptr(stream)))
-        self._N, self._E, self._B = int(num_nodes), int(coo.shape[0]), B
+        B, N, E = int(node_ptr.numel()) - 1, int(num_nodes), int(coo.shape[0])
+        _check(self.lib.gnnb_graph_prep(self._ws, _dptr(coo), _dptr(node_ptr), _dptr(edge_ptr), B, N, E,
+                                        float(self.desc.pna_delta), _stream_ptr(stream)))
+        self._prepared(B, N, E, (coo, node_ptr, edge_ptr))
 
     def forward_prepared(self, x, out=None, stream=None):
-        import torch
-        _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
-        if int(x.shape[0]) != self._N:
-            raise GnnbError(f"x has {int(x.shape[0])} rows, the prepared batch has {self._N} nodes")
-        if out is None:
-            out = torch.empty((self._B, self.out_dim), dtype=torch.float32, device=x.device)
-        else:
-            _require(out, "out", torch.float32, 2, self.out_dim)
-            if out.shape[0] != self._B or out.device != x.device:
-                raise GnnbError(f"out must be [{self._B}, {self.out_dim}] on {x.device}, got {tuple(out.shape)} on {out.device}")
+        self._require_x(x, int(self.desc.in_dim))
+        out = _out(out, self._B, self.out_dim, x)
         _check(self.lib.gnnb_forward_prepared(self._model, self._ws, _dptr(x), _dptr(out), _stream_ptr(stream)))
         return out
 
@@ -419,22 +441,13 @@ class CompiledModel:
         ``nxt`` -- a second ``CompiledModel`` of the same design (two alternate along a stream of batches) -- in one call
         (``gnnb_forward_prepared_prep_next``): where the forward runs the 2-layer GCN stack kernel, the prep runs inside it.
         ``nxt.forward_prepared`` / ``nxt.forward_prepared_prep_next`` is then the next batch's forward."""
-        import torch
-        _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
-        if int(x.shape[0]) != self._N:
-            raise GnnbError(f"x has {int(x.shape[0])} rows, the prepared batch has {self._N} nodes")
+        self._require_x(x, int(self.desc.in_dim))
+        out = _out(out, self._B, self.out_dim, x)
         self._check_batch(None, coo, node_ptr, edge_ptr)
-        if out is None:
-            out = torch.empty((self._B, self.out_dim), dtype=torch.float32, device=x.device)
-        else:
-            _require(out, "out", torch.float32, 2, self.out_dim)
-            if out.shape[0] != self._B or out.device != x.device:
-                raise GnnbError(f"out must be [{self._B}, {self.out_dim}] on {x.device}, got {tuple(out.shape)} on {out.device}")
-        B = int(node_ptr.numel()) - 1
+        B, N, E = int(node_ptr.numel()) - 1, int(num_nodes), int(coo.shape[0])
         _check(self.lib.gnnb_forward_prepared_prep_next(self._model, self._ws, _dptr(x), _dptr(out), nxt._ws, _dptr(coo), _dptr(node_ptr),
-                                                        _dptr(edge_ptr), B, int(num_nodes), int(coo.shape[0]), _stream_ptr(stream)))
-        nxt._keep = (coo, node_ptr, edge_ptr)
-        nxt._N, nxt._E, nxt._B = int(num_nodes), int(coo.shape[0]), B
+                                                        _dptr(edge_ptr), B, N, E, _stream_ptr(stream)))
+        nxt._prepared(B, N, E, (coo, node_ptr, edge_ptr))
         return out
 
     def check(self, stream=None) -> None:
@@ -465,7 +478,7 @@ class CompiledModel:
     def _pyg_args(self, edge_index, batch, ptr, num_graphs, num_nodes):
         """Checks of a PyG mini-batch's index tensors (raw pointers cross the C ABI); returns (batch or None, ptr or None, B, N, E)."""
         import torch
-        if not getattr(self, "_ingest", False):
+        if not self._ingest:
             raise GnnbError("ingest is not enabled on this model's workspace: call enable_ingest() once after construction")
         if isinstance(edge_index, torch.Tensor) and edge_index.dim() == 2 and edge_index.shape[0] != 2 and edge_index.shape[1] == 2:
             raise GnnbError(f"edge_index has shape {tuple(edge_index.shape)}: this is the [E, 2] coo layout; pass the PyG layout "
@@ -508,13 +521,12 @@ class CompiledModel:
         import torch
         batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, num_nodes)
         coo_p, np_p, ep_p = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _check(self.lib.gnnb_ingest_pyg(self._ws, _dptr(edge_index), _dptr(batch) if batch is not None else None,
-                                        _dptr(ptr) if ptr is not None else None, B, N, E, C.byref(coo_p), C.byref(np_p), C.byref(ep_p),
-                                        _stream_ptr(stream)))
+        _check(self.lib.gnnb_ingest_pyg(self._ws, _dptr(edge_index), _optr(batch), _optr(ptr), B, N, E,
+                                        C.byref(coo_p), C.byref(np_p), C.byref(ep_p), _stream_ptr(stream)))
         # views of the whole arrays are made once (the allocation never moves), every call slices them: no HIP call per ingest,
         # so a warmed-up ingest_pyg can be captured into a graph
         ptrs = (coo_p.value, np_p.value, ep_p.value)
-        if getattr(self, "_ingest_views", (None,))[0] != ptrs:
+        if self._ingest_views[0] != ptrs:
             dev = edge_index.device
             view = lambda p, shape: torch.as_tensor(_Borrowed(p, shape, self), device=dev)  # noqa: E731
             self._ingest_views = (ptrs, view(ptrs[0], (max(self.max_edges, 1), 2)), view(ptrs[1], (self.max_graphs + 1,)),
@@ -529,19 +541,15 @@ class CompiledModel:
         import torch
         _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
         batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, int(x.shape[0]))
-        if out is None:
-            out = torch.empty((B, self.out_dim), dtype=torch.float32, device=x.device)
-        else:
-            _require(out, "out", torch.float32, 2, self.out_dim)
-            if out.shape[0] != B or out.device != x.device:
-                raise GnnbError(f"out must be [{B}, {self.out_dim}] on {x.device}, got {tuple(out.shape)} on {out.device}")
-        _check(self.lib.gnnb_forward_pyg(self._model, self._ws, _dptr(x), _dptr(edge_index), _dptr(batch) if batch is not None else None,
-                                         _dptr(ptr) if ptr is not None else None, B, N, E, _dptr(out), _stream_ptr(stream)))
-        self._keep = None  # (the batch's index arrays live in the workspace)
-        self._N, self._E, self._B = N, E, B
+        out = _out(out, B, self.out_dim, x)
+        _check(self.lib.gnnb_forward_pyg(self._model, self._ws, _dptr(x), _dptr(edge_index), _optr(batch), _optr(ptr),
+                                         B, N, E, _dptr(out), _stream_ptr(stream)))
+        self._prepared(B, N, E, None)  # (the batch's index arrays live in the workspace)
         return out
 
     # ------------------------------------------------------------------ stage-level entry points
+    # (raw pointers cross the C ABI: each checks every operand's dtype, layout, device and rows against the prepared batch, so
+    # that a short, narrower, int64, CPU or strided tensor is refused here instead of read out of bounds or reinterpreted)
     def tables_to_host(self, stream=None):
         row_ptr = np.zeros(self._N + 1, np.int32)
         col = np.zeros(max(self._E, 1), np.int32)
@@ -551,26 +559,18 @@ class CompiledModel:
                                                   in_deg.ctypes.data_as(C.c_void_p), _stream_ptr(stream)))
         return row_ptr, col[:self._E], in_deg[:self._N]
 
-    def aggregate(self, kind: str, x, self_term=None, eps: float = 0.0, out=None, stream=None):
-        import torch
-        _require(x, "x", torch.float32, 2)
+    def _aggregate_operands(self, kind: str, x, self_term, out, w: Optional[int] = None):
+        """Operands of ``gnnb_aggregate``: the kernel reads x[j * w] for every source j of the prepared batch, and the PNA
+        destination term beside it; returns (w, out)."""
+        self._require_x(x, w)
         w = int(x.shape[1])
-        # (raw pointers cross the C ABI: the kernel reads x[j * w] for every source j of the prepared batch)
-        if int(x.shape[0]) != self._N:
-            raise GnnbError(f"x has {int(x.shape[0])} rows, the prepared batch has {self._N} nodes")
-        ow = 4 * w if kind == "pna" else w
         if self_term is not None:
-            _require(self_term, "self_term", torch.float32, 2, w)
-            if int(self_term.shape[0]) != self._N or self_term.device != x.device:
-                raise GnnbError(f"self_term must be [{self._N}, {w}] on {x.device}")
-        if out is None:
-            out = torch.empty((x.shape[0], ow), dtype=torch.float32, device=x.device)
-        else:
-            _require(out, "out", torch.float32, 2, ow)
-            if out.shape[0] != x.shape[0] or out.device != x.device:
-                raise GnnbError(f"out must be [{int(x.shape[0])}, {ow}] on {x.device}")
-        _check(self.lib.gnnb_aggregate(self._ws, AGG[kind], _dptr(x),
-                                       _dptr(self_term) if self_term is not None else None, _dptr(out), w,
+            _require_rows(self_term, "self_term", self._N, w, x)
+        return w, _out(out, self._N, 4 * w if kind == "pna" else w, x)
+
+    def aggregate(self, kind: str, x, self_term=None, eps: float = 0.0, out=None, stream=None):
+        w, out = self._aggregate_operands(kind, x, self_term, out)
+        _check(self.lib.gnnb_aggregate(self._ws, AGG[kind], _dptr(x), _optr(self_term), _dptr(out), w,
                                        float(eps), _stream_ptr(stream)))
         return out
 
@@ -579,17 +579,12 @@ class CompiledModel:
         [width, ldw] view of the x_j half of the pre-NN weight (``W_pre[:, width:]``: a strided view is fine, the row stride is
         passed on).  Needs the workspace's ``max_graph_nodes`` promise (<= 57 with the default node tiles)."""
         import torch
-        _require(x, "x", torch.float32, 2)
+        self._require_x(x)
         w = int(x.shape[1])
-        if int(x.shape[0]) != self._N:
-            raise GnnbError(f"x has {int(x.shape[0])} rows, the prepared batch has {self._N} nodes")
         if wb.dtype != torch.float32 or wb.dim() != 2 or tuple(wb.shape) != (w, w) or wb.stride(1) != 1 or wb.device != x.device:
             raise GnnbError(f"wb must be a [{w}, {w}] float32 view with unit column stride on {x.device}")
-        if out is None:
-            out = torch.empty((x.shape[0], 4 * w), dtype=torch.float32, device=x.device)
-        else:
-            _require(out, "out", torch.float32, 2, 4 * w)
-        _check(self.lib.gnnb_pna_product_aggregate(self._ws, _dptr(x), wb.data_ptr(), int(wb.stride(0)), _dptr(out), w, _stream_ptr(stream)))
+        out = _out(out, self._N, 4 * w, x)
+        _check(self.lib.gnnb_pna_product_aggregate(self._ws, _dptr(x), _dptr(wb), int(wb.stride(0)), _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def edge_index_table_to_host(self, stream=None) -> np.ndarray:
@@ -600,24 +595,12 @@ class CompiledModel:
 
     def aggregate_edges(self, x, edge_term, eps: float = 0.0, out=None, stream=None):
         """GINE aggregate: ``(1 + eps) x_i + sum_j relu(x_j + edge_term[e])``; ``edge_term`` [E, width] in COO order."""
-        import torch
-        # raw pointers cross the C ABI: the kernel reads edge_term[eid * width] for every CSR slot and x[j * width] for
-        # every source -- a short, narrower, int64, CPU or strided tensor would be read out of bounds or reinterpreted
-        _require(x, "x", torch.float32, 2)
+        # (the kernel reads edge_term[eid * width] for every CSR slot: one row per COO edge of the prepared batch)
+        self._require_x(x)
         w = int(x.shape[1])
-        if int(x.shape[0]) != self._N:
-            raise GnnbError(f"x has {int(x.shape[0])} rows, the prepared batch has {self._N} nodes")
-        _require(edge_term, "edge_term", torch.float32, 2, w)
-        if int(edge_term.shape[0]) != self._E or edge_term.device != x.device:
-            raise GnnbError(f"edge_term must be [{self._E}, {w}] on {x.device} (one row per COO edge of the prepared batch), "
-                            f"got {tuple(edge_term.shape)} on {edge_term.device}")
-        if out is None:
-            out = torch.empty_like(x)
-        else:
-            _require(out, "out", torch.float32, 2, w)
-            if out.shape[0] != x.shape[0] or out.device != x.device:
-                raise GnnbError(f"out must be {tuple(x.shape)} on {x.device}")
-        _check(self.lib.gnnb_aggregate_edges(self._ws, _dptr(x), _dptr(edge_term), _dptr(out), int(x.shape[1]),
+        _require_rows(edge_term, "edge_term", self._E, w, x)
+        out = _out(out, self._N, w, x)
+        _check(self.lib.gnnb_aggregate_edges(self._ws, _dptr(x), _dptr(edge_term), _dptr(out), w,
                                              float(eps), _stream_ptr(stream)))
         return out
 
@@ -633,50 +616,69 @@ class CompiledModel:
         """Mean microseconds per launch over ``iters`` back-to-back launches issued from C,
         rotating over the (x, out) buffer pairs; HIP events on the launch stream."""
         n = len(xs)
+        if n < 1 or len(outs) != n or any(out is None for out in outs):
+            raise GnnbError(f"aggregate_timed takes as many outs as xs, at least one; got {n} xs and {len(outs)} outs")
+        w = None  # (of the first x, every other as wide)
+        for x, out in zip(xs, outs):
+            w, _ = self._aggregate_operands(kind, x, self_term, out, w)
         xa = (C.c_void_p * n)(*[_dptr(t) for t in xs])
         oa = (C.c_void_p * n)(*[_dptr(t) for t in outs])
         us = C.c_float()
-        _check(self.lib.gnnb_aggregate_timed(self._ws, AGG[kind], xa, _dptr(self_term) if self_term is not None else None,
-                                             oa, n, int(xs[0].shape[1]), float(eps), int(iters), _stream_ptr(stream),
-                                             C.byref(us)))
+        _check(self.lib.gnnb_aggregate_timed(self._ws, AGG[kind], xa, _optr(self_term), oa, n, w, float(eps), int(iters),
+                                             _stream_ptr(stream), C.byref(us)))
         return float(us.value)
 
     def gcn_stack_timed(self, x, iters: int, stream=None) -> float:
         """Mean microseconds per launch of the fused GCN stack + pooling kernel on the prepared
         batch (``graph_prep`` first); HIP events on the launch stream.  Raises if that path is not eligible."""
+        self._require_x(x, int(self.desc.in_dim))
         us = C.c_float()
         _check(self.lib.gnnb_gcn_stack_timed(self._model, self._ws, _dptr(x), int(iters), _stream_ptr(stream),
                                              C.byref(us)))
         return float(us.value)
 
     def global_pool(self, x, pools: Sequence[str], out=None, stream=None):
-        import torch
+        # (gnnb_global_pool reads x up to row node_ptr[B] of the prepared batch)
+        self._require_x(x)
         d = int(x.shape[1])
-        if out is None:
-            out = torch.empty((self._B, len(pools) * d), dtype=torch.float32, device=x.device)
+        out = _out(out, self._B, len(pools) * d, x)
         arr = (C.c_int32 * len(pools))(*[POOL[p] for p in pools])
         _check(self.lib.gnnb_global_pool(self._ws, _dptr(x), d, arr, len(pools), _dptr(out), _stream_ptr(stream)))
         return out
 
 
+def _linear_operands(segments, weight, bias, skip, out):
+    """Operands of ``gnnb_linear`` against what the header says it reads: every A_s [M, K_s] with its row stride passed as lda,
+    rowscale [M], weight [N, >= sum K_s] with its row stride passed as ldw, bias [N], skip and out [M, N] contiguous.  M = 0 is
+    legal (empty tensors).  Returns (M, N, out)."""
+    import torch
+    M = None  # (of the first segment; every other has as many rows)
+    for i, (a, rs) in enumerate(segments):
+        _require_strided(a, f"A of segment {i}", M)
+        M = int(a.shape[0])
+        if rs is not None:
+            _require(rs, f"rowscale of segment {i}", torch.float32, 1, M)
+    _require_strided(weight, "weight", None, sum(int(a.shape[1]) for a, _ in segments))
+    N = int(weight.shape[0])
+    if bias is not None:
+        _require(bias, "bias", torch.float32, 1, N)
+    if skip is not None:
+        _require_rows(skip, "skip", M, N, weight)
+    return M, N, _out(out, M, N, weight)
+
+
 def linear(segments, weight, bias=None, skip=None, act: str = "none", out=None, stream=None):
     """``segments``: list of (A [M, K_s] CUDA tensor, rowscale [M] or None).  weight [N, sum K_s]."""
-    import torch
     lib = load_library(require_gpu=True)
-    M = int(segments[0][0].shape[0])
-    N = int(weight.shape[0])
+    M, N, out = _linear_operands(segments, weight, bias, skip, out)
     segs = (GemmSeg * len(segments))()
     for i, (a, rs) in enumerate(segments):
         segs[i].a_dev = _dptr(a)
-        segs[i].rowscale_dev = _dptr(rs) if rs is not None else None
+        segs[i].rowscale_dev = _optr(rs)
         segs[i].lda = int(a.stride(0))
         segs[i].k = int(a.shape[1])
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=weight.device)
-    _check(lib.gnnb_linear(segs, len(segments), _dptr(weight), int(weight.stride(0)),
-                           _dptr(bias) if bias is not None else None,
-                           _dptr(skip) if skip is not None else None, _dptr(out), M, N, ACT[act],
-                           _stream_ptr(stream)))
+    _check(lib.gnnb_linear(segs, len(segments), _dptr(weight), int(weight.stride(0)), _optr(bias), _optr(skip), _dptr(out),
+                           M, N, ACT[act], _stream_ptr(stream)))
     return out
 
 
@@ -688,10 +690,10 @@ def stream_k_guard(stream=None) -> None:
 def linear_timed(a, weight, bias, out, act: str, iters: int, stream=None) -> float:
     """Mean microseconds per launch of one ``gnnb_linear`` configuration, launched from C."""
     lib = load_library(require_gpu=True)
+    M, N, out = _linear_operands([(a, None)], weight, bias, None, out)
     us = C.c_float()
     _check(lib.gnnb_linear_timed(_dptr(a), int(a.stride(0)), int(a.shape[1]), _dptr(weight), int(weight.stride(0)),
-                                 _dptr(bias) if bias is not None else None, _dptr(out), int(a.shape[0]),
-                                 int(weight.shape[0]), ACT[act], int(iters), _stream_ptr(stream), C.byref(us)))
+                                 _optr(bias), _dptr(out), M, N, ACT[act], int(iters), _stream_ptr(stream), C.byref(us)))
     return float(us.value)
 
 
@@ -699,8 +701,9 @@ class HipTimer:
     """hipEvent pair on an explicit stream (bench.py times kernels on the stream they run on)."""
 
     def __init__(self):
-        self.lib = load_library(require_gpu=True)
+        self.lib = None
         self.a, self.b = C.c_void_p(), C.c_void_p()
+        self.lib = load_library(require_gpu=True)
         _check(self.lib.gnnb_event_create(C.byref(self.a)))
         _check(self.lib.gnnb_event_create(C.byref(self.b)))
 

@@ -180,6 +180,59 @@ def test_stage_entry_points_refuse_mismatched_tensors(dev):
     with pytest.raises(runtime.GnnbError):
         cm.forward(xd, cood, nptr, eptr, out=torch.empty(1, cm.out_dim + 1, device=dev))
 
+    # the neighbours of those entry points: refused by the binding, before anything is launched
+    def refused(call, *args, **kw):
+        with pytest.raises(runtime.GnnbError) as e:
+            call(*args, **kw)
+        assert not str(e.value).startswith("libgnnb_hip error"), e.value
+
+    strided = torch.rand(G.N, 16, device=dev)[:, ::2]             # [N, 8] with column stride 2
+    pooled = cm.global_pool(xd, ["add", "max"])
+    for bad_x in (xd[:-1], xd.double(), xd.cpu(), strided):      # (gnnb_global_pool reads x up to row node_ptr[B])
+        refused(cm.global_pool, bad_x, ["add", "max"])
+    refused(cm.global_pool, xd, ["add", "max"], out=torch.empty(2, 16, device=dev))
+    w = torch.rand(5, 8, device=dev) - 0.5
+    b = torch.rand(5, device=dev)
+    y = runtime.linear([(xd, None)], w, b)
+    for bad_a in (xd.long(), xd.cpu(), strided):
+        refused(runtime.linear, [(bad_a, None)], w, b)
+    refused(runtime.linear, [(xd, None), (xd, None)], w, b)      # weight narrower than sum K_s
+    refused(runtime.linear, [(xd, None)], w, b[:-1])
+    refused(runtime.linear, [(xd, None)], w, b, out=torch.empty(G.N - 1, 5, device=dev))
+    refused(runtime.linear, [(xd, None)], w, b, out=torch.empty(G.N, 4, device=dev))
+    half = runtime.linear([(xd[:, :4], None)], w[:, :4].contiguous())   # a column-sliced view: its row stride 8 is passed as lda
+    assert xd[:, :4].stride(0) == 8
+    assert (half.cpu().double() - xd[:, :4].cpu().double() @ w[:, :4].cpu().double().T).abs().max().item() < 2e-5  # (as test_linear_matches_torch)
+    # the timed forms take the same operands as the entry points they launch
+    refused(runtime.linear_timed, strided, w, b, torch.empty(G.N, 5, device=dev), "none", 1)
+    refused(runtime.linear_timed, xd, w, b[:-1], torch.empty(G.N, 5, device=dev), "none", 1)
+    refused(runtime.linear_timed, xd, w, b, torch.empty(G.N - 1, 5, device=dev), "none", 1)
+    assert runtime.linear_timed(xd, w, b, torch.empty(G.N, 5, device=dev), "none", 1) > 0.0
+    outs = [torch.empty(G.N, 8, device=dev) for _ in range(2)]
+    refused(cm.aggregate_timed, "sum", [xd, xd[:-1]], outs, 1)
+    refused(cm.aggregate_timed, "sum", [xd, xd.double()], outs, 1)
+    refused(cm.aggregate_timed, "sum", [xd, xd], [outs[0], torch.empty(G.N - 1, 8, device=dev)], 1)
+    refused(cm.aggregate_timed, "sum", [xd, xd], outs[:1], 1)
+    assert cm.aggregate_timed("sum", [xd, xd], outs, 1) > 0.0 and torch.equal(outs[0], cm.aggregate("sum", xd))
+    for bad_x in (xd[:-1], xd.double(), xd.cpu(), strided):
+        refused(cm.gcn_stack_timed, bad_x, 1)
+    # k_pna_pagg on a workspace with a max_graph_nodes promise (promise + tile rows - 1 <= 64)
+    n, wd = 40, 32
+    ring = np.stack([np.arange(n), (np.arange(n) + 1) % n], 1).astype(np.int32)
+    pb = pack_graphs([(np.random.default_rng(3).uniform(-1, 1, (n, wd)).astype(np.float32), ring)])
+    pcm = runtime.CompiledModel.from_model(make_model("pna", in_dim=wd, hidden=wd, layers=1, out_dim=wd, task_out=2, mlp_layers=1),
+                                           1, n, n, max_graph_nodes=n)
+    px, pcoo, pnptr, peptr = to_dev(pb, dev)
+    pcm.graph_prep(pcoo, pnptr, peptr, n)
+    wb = (torch.rand(wd, 2 * wd, device=dev) - 0.5)[:, wd:]
+    stats = pcm.pna_product_aggregate(px, wb)
+    refused(pcm.pna_product_aggregate, px, wb, out=torch.empty(n - 1, 4 * wd, device=dev))
+    # after the refusals, the good calls still give the earlier results
+    assert torch.equal(cm.aggregate_edges(xd, et), good)
+    assert torch.equal(cm.global_pool(xd, ["add", "max"]), pooled)
+    assert torch.equal(runtime.linear([(xd, None)], w, b), y)
+    assert torch.equal(pcm.pna_product_aggregate(px, wb), stats)
+
 
 @pytest.mark.parametrize("kind,golden", [("simple", "tb_simple_output"), ("lg", "tb_lgconv_output")])
 def test_weight_free_convs_match_reference_golden(dev, kind, golden):
