@@ -129,7 +129,8 @@ def from_pyg_batch(x, edge_index, batch=None, ptr=None, num_graphs=None) -> Grap
 
     This is the HOST form (numpy).  A mini-batch that already lives on the GPU goes through the device form instead, which
     returns the same three index arrays without a copy to the host or a synchronisation:
-    ``runtime.CompiledModel.ingest_pyg`` / ``forward_pyg`` (``gnnb_ingest_pyg``, csrc/k_ingest.hip)."""
+    ``runtime.CompiledModel.ingest_pyg`` / ``forward_pyg`` (``gnnb_ingest_pyg``, csrc/k_ingest.hip); with the oversized graphs
+    ordered last as well (``order_large_last`` below): ``ingest_pyg_ordered`` / ``forward_pyg_ordered`` (csrc/k_order.hip)."""
     x = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
     ei = np.asarray(edge_index)
     if ei.ndim != 2 or ei.shape[0] != 2:
@@ -173,7 +174,11 @@ def order_large_last(batch: GraphBatch, max_graph_nodes: int):
     """Reorder a batch so that the graphs with more than ``max_graph_nodes`` nodes come last (stable inside both
     groups): the layout ``gnnb_workspace_set_large_segment`` asks for.  Returns ``(ordered batch, perm, (first_graph,
     first_node, first_edge))`` with ``ordered.graph(i) == batch.graph(perm[i])``; outputs of the ordered batch go back to the
-    caller's order with ``out[np.argsort(perm)]``.  ``first_graph == ordered.num_graphs`` when no graph is large."""
+    caller's order with ``out[np.argsort(perm)]``.  ``first_graph == ordered.num_graphs`` when no graph is large.
+
+    This is the HOST form (numpy).  A mini-batch that already lives on the GPU is ordered there instead, with the same arrays,
+    ``perm`` and triple as results and no copy of the batch to the host: ``runtime.CompiledModel.ingest_pyg_ordered`` /
+    ``forward_pyg_ordered`` (``gnnb_ingest_pyg_ordered``, csrc/k_order.hip)."""
     sizes = np.diff(batch.node_ptr)
     large = sizes > int(max_graph_nodes)
     perm = np.concatenate([np.flatnonzero(~large), np.flatnonzero(large)]).astype(np.int64)

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gnnb_internal.h"
+#include "gnnb_order.h"
 
 namespace gnnb {
 
@@ -95,6 +96,9 @@ struct gnnb_workspace {
     bool flags_reported = false; // gnnb_forward_pyg: its ingest has made the lazy flag report of this call; the graph prep behind it skips its
                                  // own, which could already see what THIS batch's ingest kernels flagged
     bool ingested = false;       // an ingest has been enqueued: gnnb_workspace_check has something to report on
+    char *order_blob = nullptr;  // gnnb_workspace_enable_ordered_ingest: the ordered batch and the staged outputs (order_layout), one allocation
+    int32_t *order_triple = nullptr, *order_triple_dev = nullptr; // host-mapped (first large graph, node row, edge row) of k_order_graphs, and
+                                                                  // its device-visible address
     float2 *pool_part = nullptr; // pieces of graphs that cross the 32-row blocks of the pooling GEMM epilogue (PoolEpilogue::part)
     bool gcoef_ready = false; // t.gcoef holds the prepared batch's GCN coefficients (ensure_gcoef)
     int max_graph_nodes = 0; // caller's promise (0 = none)

@@ -228,6 +228,31 @@ int ingest_sort_passes(int num_graphs); // radix passes the general path launche
 // the whole launch sequence; depends on B, N, E and on which of batch / ptr is given, never on device data
 hipError_t launch_ingest(const IngestParams &p, hipStream_t s);
 
+// The ingested batch with its oversized graphs last (k_order.hip): what batching.order_large_last does on the host.  A graph is
+// large when it has more than `limit` nodes (0: none is); small graphs first, large graphs last, both groups in input order.
+struct OrderParams {
+    const int32_t *node_ptr, *edge_ptr; // [B + 1] of the ingested batch (monotone from 0 to N / E, also for a flagged batch)
+    const int2 *coo;                    // [E] grouped by graph, every entry in [0, N)
+    const float *x;                     // [N, in_dim]
+    const long long *batch;             // [N] the caller's, or nullptr: the graph of a node is searched in node_ptr
+    int B, N, E, in_dim, limit;
+    int32_t *perm;                      // [B] position -> input graph
+    int32_t *node_ptr_ord, *edge_ptr_ord; // [B + 1] of the new order
+    int32_t *node_shift, *edge_shift;   // [B] per INPUT graph: new offset minus old
+    float *x_ord;                       // [N, in_dim]
+    int2 *coo_ord;                      // [E]
+    int32_t *triple;                    // [3] host-mapped: first large graph's position, node row and edge row ((B, N, E): none)
+};
+// byte offsets of the ordered form's arrays (its own allocation) and its size: a pure function of the five
+struct OrderLayout {
+    size_t x_ord, coo_ord, node_ptr, edge_ptr, perm, node_shift, edge_shift, out_ord, bytes;
+};
+OrderLayout order_layout(int max_graphs, int max_nodes, int max_edges, int in_dim, int mlp_out);
+// k_order_graphs, k_order_rows, k_order_edges on `s`; launch sizes from B, N, E, in_dim only
+hipError_t launch_order(const OrderParams &p, hipStream_t s);
+// out[perm[i], :] = out_ord[i, :]: the forward's rows back in the caller's graph order
+hipError_t launch_order_out(const float *out_ord, const int32_t *perm, float *out, int num_graphs, int width, hipStream_t s);
+
 hipError_t launch_aggregate(const BatchTables &t, int kind, const float *x, const float *selfq,
                             float *out, int width, float eps, hipStream_t s);
 // GraphSAGE's narrow first layer (k_conv_first's [mean | x] form) + the next layer's mean aggregate of its output rows, one kernel

@@ -250,6 +250,10 @@ void gnnb_workspace_destroy(gnnb_workspace *ws)
         (void)hipFree(ws->blob);
     if (ws->ingest_blob)
         (void)hipFree(ws->ingest_blob);
+    if (ws->order_blob)
+        (void)hipFree(ws->order_blob);
+    if (ws->order_triple)
+        (void)hipHostFree(ws->order_triple);
     if (ws->stage)
         (void)hipFree(ws->stage);
     if (ws->err_host)
@@ -680,6 +684,121 @@ int gnnb_forward_pyg(const gnnb_model *model, gnnb_workspace *ws, const float *x
     const int frc = gnnb_forward_batched(model, ws, x_dev, coo, node_ptr, edge_ptr, num_graphs, num_nodes, num_edges, out_dev, stream);
     ws->flags_reported = false;
     return frc;
+}
+
+// ---------------------------------------------------------------------------------------
+// PyG mini-batches with the oversized graphs ordered last (k_order.hip)
+size_t gnnb_order_bytes(int max_graphs, int max_nodes, int max_edges, int in_dim, int mlp_out)
+{
+    if (max_graphs < 0 || max_nodes < 0 || max_edges < 0 || in_dim < 0 || mlp_out < 0)
+        return 0;
+    return order_layout(max_graphs, max_nodes, max_edges, in_dim, mlp_out).bytes;
+}
+
+int gnnb_workspace_enable_ordered_ingest(gnnb_workspace *ws)
+{
+    if (!ws)
+        return fail(GNNB_ERR_INVALID, "null workspace");
+    if (ws->order_blob)
+        return GNNB_OK; // (enabled already: the allocation is made once)
+    if (ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_workspace_enable_ordered_ingest: the workspace is in use (a batch has been prepared on it); "
+                                      "enable the ordered ingest right after gnnb_workspace_create");
+    if (const int rc = gnnb_workspace_enable_ingest(ws))
+        return rc;
+    const OrderLayout l = order_layout(ws->max_graphs, ws->max_nodes, ws->max_edges, ws->desc.in_dim, ws->desc.mlp_out);
+    char *blob = nullptr;
+    hipError_t e = hipMalloc((void **)&blob, l.bytes);
+    if (e != hipSuccess)
+        return fail(GNNB_ERR_HIP, "ordered-ingest allocation of %zu bytes failed: %s", l.bytes, hipGetErrorString(e));
+    // the triple comes back through host-mapped memory (as the flag word does): required here, the launches behind it are sized by it
+    int32_t *triple = nullptr;
+    void *dp = nullptr;
+    e = hipHostMalloc((void **)&triple, 64, hipHostMallocMapped);
+    if (e == hipSuccess)
+        e = hipHostGetDevicePointer(&dp, triple, 0);
+    if (e != hipSuccess || !dp) {
+        if (triple)
+            (void)hipHostFree(triple);
+        (void)hipFree(blob);
+        (void)hipGetLastError();
+        return fail(GNNB_ERR_HIP, "host-mapped block of the ordered ingest failed: %s", hipGetErrorString(e));
+    }
+    triple[0] = triple[1] = triple[2] = 0;
+    ws->order_blob = blob;
+    ws->order_triple = triple;
+    ws->order_triple_dev = (int32_t *)dp;
+    return GNNB_OK;
+}
+
+int gnnb_ingest_pyg_ordered(gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev, const int64_t *batch_dev,
+                            const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges, const float **x_ord_dev,
+                            const int32_t **coo_dev, const int32_t **node_ptr_dev, const int32_t **edge_ptr_dev, const int32_t **perm_dev,
+                            int *first_graph, int *first_node, int *first_edge, void *stream)
+{
+    if (!ws || !x_ord_dev || !coo_dev || !node_ptr_dev || !edge_ptr_dev || !perm_dev || !first_graph || !first_node || !first_edge ||
+        (num_nodes > 0 && !x_dev))
+        return fail(GNNB_ERR_INVALID, "null argument to gnnb_ingest_pyg_ordered");
+    if (!ws->order_blob)
+        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg_ordered: call gnnb_workspace_enable_ordered_ingest on the workspace first");
+    // the triple is read on the host behind a wait: not under capture (nothing has been enqueued yet)
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg_ordered waits for its kernels and cannot be captured into a graph");
+    }
+    const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
+    if (const int rc = gnnb_ingest_pyg(ws, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &coo, &node_ptr, &edge_ptr, stream))
+        return rc;
+    const OrderLayout l = order_layout(ws->max_graphs, ws->max_nodes, ws->max_edges, ws->desc.in_dim, ws->desc.mlp_out);
+    char *b = ws->order_blob;
+    OrderParams p;
+    memset(&p, 0, sizeof(p));
+    p.node_ptr = node_ptr, p.edge_ptr = edge_ptr, p.coo = (const int2 *)coo;
+    p.x = x_dev;
+    p.batch = num_nodes > 0 ? (const long long *)batch_dev : nullptr;
+    p.B = num_graphs, p.N = num_nodes, p.E = num_edges, p.in_dim = ws->desc.in_dim;
+    p.limit = ws->max_graph_nodes; // the promise as it stands at this call
+    p.perm = (int32_t *)(b + l.perm), p.node_ptr_ord = (int32_t *)(b + l.node_ptr), p.edge_ptr_ord = (int32_t *)(b + l.edge_ptr);
+    p.node_shift = (int32_t *)(b + l.node_shift), p.edge_shift = (int32_t *)(b + l.edge_shift);
+    p.x_ord = (float *)(b + l.x_ord), p.coo_ord = (int2 *)(b + l.coo_ord);
+    p.triple = ws->order_triple_dev;
+    GNNB_HIP_TRY(launch_order(p, (hipStream_t)stream));
+    GNNB_HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); // the one synchronisation of the path
+    *first_graph = ((volatile int32_t *)ws->order_triple)[0];
+    *first_node = ((volatile int32_t *)ws->order_triple)[1];
+    *first_edge = ((volatile int32_t *)ws->order_triple)[2];
+    *x_ord_dev = p.x_ord;
+    *coo_dev = (const int32_t *)p.coo_ord;
+    *node_ptr_dev = p.node_ptr_ord;
+    *edge_ptr_dev = p.edge_ptr_ord;
+    *perm_dev = p.perm;
+    return GNNB_OK;
+}
+
+int gnnb_forward_pyg_ordered(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev,
+                             const int64_t *batch_dev, const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges,
+                             float *out_dev, void *stream)
+{
+    if (!model || !ws || (num_graphs > 0 && !out_dev))
+        return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg_ordered");
+    const float *x_ord = nullptr;
+    const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr, *perm = nullptr;
+    int g0 = 0, n0 = 0, e0 = 0;
+    if (const int rc = gnnb_ingest_pyg_ordered(ws, x_dev, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &x_ord, &coo,
+                                               &node_ptr, &edge_ptr, &perm, &g0, &n0, &e0, stream))
+        return rc;
+    // nothing large: no segment, the batch runs exactly as gnnb_forward_pyg would run it
+    if (const int rc = g0 == num_graphs ? gnnb_workspace_set_large_segment(ws, -1, -1, -1) : gnnb_workspace_set_large_segment(ws, g0, n0, e0))
+        return rc;
+    float *out_ord = (float *)(ws->order_blob + order_layout(ws->max_graphs, ws->max_nodes, ws->max_edges, ws->desc.in_dim, ws->desc.mlp_out).out_ord);
+    ws->flags_reported = true; // (the ingest has made this call's lazy report, as in gnnb_forward_pyg)
+    const int frc = gnnb_forward_batched(model, ws, x_ord, coo, node_ptr, edge_ptr, num_graphs, num_nodes, num_edges, out_ord, stream);
+    ws->flags_reported = false;
+    if (frc != GNNB_OK)
+        return frc;
+    GNNB_HIP_TRY(launch_order_out(out_ord, perm, out_dev, num_graphs, ws->desc.mlp_out, (hipStream_t)stream));
+    return GNNB_OK;
 }
 
 // CSR slots no row owns (edges dropped by graph prep -- explicit self loops on a GCN workspace -- leave a gap at the end of

@@ -1,0 +1,212 @@
+// k_order.hip -- the ingested batch (k_ingest.hip: coo grouped by graph, node_ptr / edge_ptr) with its oversized graphs LAST: the
+// layout gnnb_workspace_set_large_segment asks for, on the device (latency bound)
+// Part of libgnnb_hip.so (hand-written gfx950 / CDNA4 kernels of the GNNBuilder hot path); wavefront = 64 lanes.
+// What batching.order_large_last does on the host (flatnonzero, cumsum, two gathers).  A graph is large when it has more than
+// `limit` nodes; small graphs come first, large graphs last, both groups in input order.
+//   k_order_graphs   one workgroup, two carried scans over the B graphs (count, nodes, edges of the SMALL group; the large
+//                    group's running totals are the differences to i, node_ptr[i], edge_ptr[i]): perm, the new ptr arrays, per
+//                    input graph its node / edge shift, and the triple (first large graph, its node row, its edge row) into
+//                    a host-mapped block -- the three integers the large segment's launches are sized by
+//   k_order_rows     x_ord[v + node_shift[graph of v]] = x[v]: 16-byte pieces where width and pointers allow, floats otherwise
+//   k_order_edges    coo_ord[e + edge_shift[g]] = coo[e] + node_shift[g], g found in edge_ptr: the order inside a graph is kept
+//   k_order_out      out[perm[i]] = out_ord[i]: the forward's rows back in the caller's graph order
+// Containment: for a batch the ingest has flagged node_ptr / edge_ptr are still monotone from 0 to N / E and every coo entry is
+// in [0, N).  Under exactly that every index formed here stays inside its array: a new offset is a sum of sizes of other graphs
+// (<= N, <= E); the graph of a node taken from `batch` is used only if node_ptr agrees that the node lies in it; a renumbered
+// endpoint is clamped into [0, N) (an edge that leaves its graph -- flagged -- could otherwise leave the batch).
+#include <algorithm>
+#include <type_traits>
+
+#include "gnnb_device.h"
+
+namespace gnnb {
+
+constexpr int OG = 1024; // threads of k_order_graphs: one workgroup of 16 waves
+constexpr int OT = 256;  // threads per workgroup of the other three
+constexpr int ORDER_MAX_GRID = 4096; // workgroups of the copy kernels (grid-stride beyond)
+
+struct Tri { // graphs, nodes, edges
+    int c, n, e;
+};
+__device__ __forceinline__ Tri operator+(Tri a, Tri b) { return Tri{a.c + b.c, a.n + b.n, a.e + b.e}; }
+
+// exclusive prefix of `v` over the workgroup's OG threads, and the workgroup's total
+__device__ __forceinline__ Tri order_block_scan(Tri v, Tri &total, int (*s_wave)[OG / 64])
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const Tri incl = {wave_scan_incl(v.c), wave_scan_incl(v.n), wave_scan_incl(v.e)};
+    if (lane == 63) {
+        s_wave[0][wave] = incl.c;
+        s_wave[1][wave] = incl.n;
+        s_wave[2][wave] = incl.e;
+    }
+    __syncthreads();
+    Tri before = {0, 0, 0};
+    total = Tri{0, 0, 0};
+    for (int w = 0; w < OG / 64; w++) {
+        const Tri t = {s_wave[0][w], s_wave[1][w], s_wave[2][w]};
+        if (w < wave)
+            before = before + t;
+        total = total + t;
+    }
+    __syncthreads();
+    return Tri{before.c + incl.c - v.c, before.n + incl.n - v.n, before.e + incl.e - v.e};
+}
+
+// graph i < B as a term of the small group's sums ({0, 0, 0} for a large one)
+__device__ __forceinline__ Tri order_small_term(const OrderParams &p, int i, bool &small)
+{
+    const int n = p.node_ptr[i + 1] - p.node_ptr[i], e = p.edge_ptr[i + 1] - p.edge_ptr[i];
+    small = !(p.limit > 0 && n > p.limit);
+    return small ? Tri{1, n, e} : Tri{0, 0, 0};
+}
+
+__global__ __launch_bounds__(OG) void k_order_graphs(OrderParams p)
+{
+    __shared__ int s_wave[3][OG / 64];
+    Tri all_small = {0, 0, 0}; // the small group as a whole: where the large group starts
+    for (int base = 0; base < p.B; base += OG) {
+        const int i = base + threadIdx.x;
+        bool small = false;
+        const Tri v = i < p.B ? order_small_term(p, i, small) : Tri{0, 0, 0};
+        Tri total;
+        (void)order_block_scan(v, total, s_wave);
+        all_small = all_small + total;
+    }
+    Tri carry = {0, 0, 0};
+    for (int base = 0; base < p.B; base += OG) {
+        const int i = base + threadIdx.x;
+        bool small = false;
+        const Tri v = i < p.B ? order_small_term(p, i, small) : Tri{0, 0, 0};
+        Tri total;
+        const Tri excl = order_block_scan(v, total, s_wave);
+        if (i < p.B) {
+            const Tri sb = carry + excl; // the small graphs in front of graph i; the large ones in front of it are the rest
+            const int n0 = p.node_ptr[i], e0 = p.edge_ptr[i];
+            const int pos = small ? sb.c : all_small.c + (i - sb.c);
+            const int noff = small ? sb.n : all_small.n + (n0 - sb.n);
+            const int eoff = small ? sb.e : all_small.e + (e0 - sb.e);
+            p.perm[pos] = i;
+            p.node_ptr_ord[pos] = noff;
+            p.edge_ptr_ord[pos] = eoff;
+            p.node_shift[i] = noff - n0;
+            p.edge_shift[i] = eoff - e0;
+        }
+        carry = carry + total;
+    }
+    if (threadIdx.x == 0) {
+        p.node_ptr_ord[p.B] = p.N;
+        p.edge_ptr_ord[p.B] = p.E;
+        // (nothing large: all_small = (B, N, E), as order_large_last returns it)
+        __hip_atomic_store(&p.triple[0], all_small.c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&p.triple[1], all_small.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&p.triple[2], all_small.e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// the last g in [0, B) with ptr[g] <= i, for 0 <= i < ptr[B] and ptr[0] = 0: ptr[g] <= i < ptr[g + 1] on a monotone ptr
+// (searchsorted(ptr, i, "right") - 1; empty graphs are stepped over)
+__device__ __forceinline__ int order_search(const int32_t *ptr, int B, int i)
+{
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo + 1) >> 1);
+        if (ptr[mid] <= i)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// graph of node v in [0, N): batch[v] where node_ptr agrees (always, on a well-formed batch), otherwise the search
+__device__ __forceinline__ int order_graph_of_node(const OrderParams &p, int v)
+{
+    if (p.batch) {
+        const int g = (int)min(max(p.batch[v], 0ll), (long long)(p.B - 1));
+        if (p.node_ptr[g] <= v && v < p.node_ptr[g + 1])
+            return g;
+    }
+    return order_search(p.node_ptr, p.B, v);
+}
+
+// V floats per piece (4: a row is in_dim / 4 float4, both matrices 16-byte aligned); 64-bit indices: N * in_dim may pass 2^31
+template <int V> __global__ __launch_bounds__(OT) void k_order_rows(OrderParams p)
+{
+    using T = typename std::conditional<V == 4, float4, float>::type;
+    const long long q = p.in_dim / V, total = (long long)p.N * q;
+    const T *src = (const T *)p.x;
+    T *dst = (T *)p.x_ord;
+    for (long long i = (long long)blockIdx.x * OT + threadIdx.x; i < total; i += (long long)gridDim.x * OT) {
+        const int v = (int)(i / q);
+        dst[i + (long long)p.node_shift[order_graph_of_node(p, v)] * q] = src[i];
+    }
+}
+
+__global__ __launch_bounds__(OT) void k_order_edges(OrderParams p)
+{
+    for (long long e = (long long)blockIdx.x * OT + threadIdx.x; e < p.E; e += (long long)gridDim.x * OT) {
+        const int g = order_search(p.edge_ptr, p.B, (int)e);
+        const long long ns = p.node_shift[g], hi = p.N - 1;
+        const int2 c = p.coo[e];
+        p.coo_ord[e + p.edge_shift[g]] = make_int2((int)min(max(c.x + ns, 0ll), hi), (int)min(max(c.y + ns, 0ll), hi));
+    }
+}
+
+__global__ __launch_bounds__(OT) void k_order_out(const float *out_ord, const int32_t *perm, float *out, int B, int width)
+{
+    const long long total = (long long)B * width;
+    for (long long i = (long long)blockIdx.x * OT + threadIdx.x; i < total; i += (long long)gridDim.x * OT) {
+        const long long row = i / width;
+        out[(long long)perm[row] * width + (i - row * width)] = out_ord[i];
+    }
+}
+
+OrderLayout order_layout(int max_graphs, int max_nodes, int max_edges, int in_dim, int mlp_out)
+{
+    const size_t B = (size_t)std::max(max_graphs, 0), N = (size_t)std::max(max_nodes, 0), E = (size_t)std::max(max_edges, 1);
+    OrderLayout l;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    l.x_ord = carve(N * (size_t)std::max(in_dim, 0) * 4);
+    l.coo_ord = carve(E * 8);
+    l.node_ptr = carve((B + 1) * 4);
+    l.edge_ptr = carve((B + 1) * 4);
+    l.perm = carve(B * 4);
+    l.node_shift = carve(B * 4);
+    l.edge_shift = carve(B * 4);
+    l.out_ord = carve(B * (size_t)std::max(mlp_out, 0) * 4);
+    l.bytes = off;
+    return l;
+}
+
+static unsigned order_grid(long long items) { return (unsigned)std::min<long long>((items + OT - 1) / OT, ORDER_MAX_GRID); }
+
+hipError_t launch_order(const OrderParams &p, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_order_graphs, dim3(1), dim3(OG), 0, s, p);
+    const long long floats = (long long)p.N * p.in_dim;
+    if (floats > 0) {
+        if (p.in_dim % 4 == 0 && (((uintptr_t)p.x | (uintptr_t)p.x_ord) & 15) == 0)
+            hipLaunchKernelGGL(k_order_rows<4>, dim3(order_grid(floats / 4)), dim3(OT), 0, s, p);
+        else
+            hipLaunchKernelGGL(k_order_rows<1>, dim3(order_grid(floats)), dim3(OT), 0, s, p);
+    }
+    if (p.E > 0)
+        hipLaunchKernelGGL(k_order_edges, dim3(order_grid(p.E)), dim3(OT), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_order_out(const float *out_ord, const int32_t *perm, float *out, int num_graphs, int width, hipStream_t s)
+{
+    const long long total = (long long)num_graphs * width;
+    if (total > 0)
+        hipLaunchKernelGGL(k_order_out, dim3(order_grid(total)), dim3(OT), 0, s, out_ord, perm, out, num_graphs, width);
+    return hipGetLastError();
+}
+
+} // namespace gnnb

@@ -1,4 +1,4 @@
-"""Python binding of the C ABI in ``include/gnnb_hip.h`` (``libgnnb_hip.so``).
+"""Python binding of the C ABI in ``include/gnnb_hip.h`` and its extension ``include/gnnb_order.h`` (``libgnnb_hip.so``).
 
 This is the accelerated product path.  It has NO fallback: if the HIP library is not built, or no
 MI355X is visible, every entry point raises ``GnnbUnavailable`` -- it never routes to PyTorch or
@@ -85,7 +85,7 @@ class GemmSeg(C.Structure):
 # prototypes (no library needed).  A function left without argtypes takes a Python integer as a C int: a pointer or a size_t
 # from 2 GiB up would be truncated -- so none is left without.
 _P, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-_PP, _PF, _DESC = C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.POINTER(ModelDesc)
+_PP, _PF, _PI, _DESC = C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(ModelDesc)
 ABI = {
     "gnnb_version": (_I, []),
     "gnnb_last_error": (C.c_char_p, []),
@@ -134,12 +134,25 @@ ABI = {
     "gnnb_set_option": (_I, [C.c_char_p, _I]),
 }
 EXPORTED_SYMBOLS = list(ABI)  # (tests check the .so exports each one)
+# ... and every function of the extension header include/gnnb_order.h, in its order (tests/test_abi_order.py compares the two)
+ABI_ORDER = {
+    "gnnb_order_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "gnnb_workspace_enable_ordered_ingest": (_I, [_P]),
+    "gnnb_ingest_pyg_ordered": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _PP, _PP, _PP, _PP, _PP, _PI, _PI, _PI, _P]),
+    "gnnb_forward_pyg_ordered": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+}
 
 
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
     return int(load_library(require_gpu=False).gnnb_ingest_bytes(int(max_graphs), int(max_nodes), int(max_edges)))
+
+
+def order_bytes(max_graphs: int, max_nodes: int, max_edges: int, in_dim: int, mlp_out: int) -> int:
+    """Size of the allocation ``CompiledModel.enable_ordered_ingest`` makes beside the ingest's (``gnnb_order_bytes``): the
+    ordered ``x`` / ``coo`` / ptr arrays, ``perm``, the per-graph shifts and the staged outputs.  Pure host arithmetic, no GPU needed."""
+    return int(load_library(require_gpu=False).gnnb_order_bytes(int(max_graphs), int(max_nodes), int(max_edges), int(in_dim), int(mlp_out)))
 
 
 def build_library(force: bool = False) -> Path:
@@ -167,7 +180,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
                 "or `make -C gnn-builder_amd/csrc`.  There is no CPU fallback.")
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
-        for name, (restype, argtypes) in ABI.items():
+        for name, (restype, argtypes) in {**ABI, **ABI_ORDER}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -282,8 +295,8 @@ class _Borrowed:
     """Device memory of a workspace as ``__cuda_array_interface__``: ``torch.as_tensor`` makes a view of it (no copy) that
     keeps this object -- and through it the owner of the memory -- alive."""
 
-    def __init__(self, ptr: int, shape, owner):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
+    def __init__(self, ptr: int, shape, owner, typestr: str = "<i4"):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
         self._owner = owner
 
 
@@ -299,6 +312,7 @@ class CompiledModel:
         self._B = self._N = self._E = 0  # sizes of the prepared batch (_prepared)
         self._keep = None  # its index tensors, which the device still reads
         self._ingest, self._ingest_views = False, (None,)
+        self._ordered, self._order_views = False, (None,)
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
@@ -370,7 +384,7 @@ class CompiledModel:
         return int(self.lib.gnnb_workspace_bytes(self._ws))
 
     def close(self) -> None:
-        self._ingest_views = (None,)  # (they borrow the workspace: dropped with it)
+        self._ingest_views = self._order_views = (None,)  # (they borrow the workspace: dropped with it)
         if self._ws:
             self.lib.gnnb_workspace_destroy(self._ws)
             self._ws = C.c_void_p()
@@ -545,6 +559,60 @@ class CompiledModel:
         _check(self.lib.gnnb_forward_pyg(self._model, self._ws, _dptr(x), _dptr(edge_index), _optr(batch), _optr(ptr),
                                          B, N, E, _dptr(out), _stream_ptr(stream)))
         self._prepared(B, N, E, None)  # (the batch's index arrays live in the workspace)
+        return out
+
+    # ------------------------------------------------------------------ PyG mini-batches, oversized graphs ordered last
+    def enable_ordered_ingest(self) -> None:
+        """``enable_ingest`` (if that has not been done) and one more device allocation (``order_bytes``) for
+        ``ingest_pyg_ordered`` / ``forward_pyg_ordered``.  Synchronous: call it once, right after construction, outside stream
+        capture."""
+        _check(self.lib.gnnb_workspace_enable_ordered_ingest(self._ws))
+        if not self._ingest:
+            self._ingest, self._ingest_views = True, (None,)
+        self._ordered, self._order_views = True, (None,)
+
+    def _ordered_args(self, x, edge_index, batch, ptr, num_graphs):
+        import torch
+        if not self._ordered:
+            raise GnnbError("the ordered ingest is not enabled on this model's workspace: call enable_ordered_ingest() once after "
+                            "construction")
+        _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
+        return self._pyg_args(edge_index, batch, ptr, num_graphs, int(x.shape[0]))
+
+    def ingest_pyg_ordered(self, x, edge_index, batch=None, ptr=None, num_graphs=None, stream=None):
+        """``ingest_pyg`` and, on the device, ``batching.order_large_last`` at this workspace's ``max_graph_nodes`` promise: the
+        graphs with more nodes than the promise LAST (stable; promise 0: none is large).  Returns ``(x_ord [N, in_dim], coo
+        [E, 2], node_ptr [B+1], edge_ptr [B+1], perm [B], (first_graph, first_node, first_edge))`` -- what
+        ``order_large_last(from_pyg_batch(...), promise)`` returns, ``x_ord`` bit for bit; the triple as host integers, which is
+        the ONE synchronisation of this path (a wait on ``stream``; not capturable).  The tensors are VIEWS of this model's
+        workspace: valid until the next ``ingest_pyg_ordered`` / ``forward_pyg_ordered``."""
+        import torch
+        batch, ptr, B, N, E = self._ordered_args(x, edge_index, batch, ptr, num_graphs)
+        out_p = [C.c_void_p() for _ in range(5)]
+        seg = [C.c_int() for _ in range(3)]
+        _check(self.lib.gnnb_ingest_pyg_ordered(self._ws, _dptr(x), _dptr(edge_index), _optr(batch), _optr(ptr), B, N, E,
+                                                *[C.byref(p) for p in out_p], *[C.byref(v) for v in seg], _stream_ptr(stream)))
+        ptrs = tuple(p.value for p in out_p)
+        if self._order_views[0] != ptrs:  # (made once, sliced per call: as ingest_pyg's)
+            dev = edge_index.device
+            view = lambda p, shape, typestr="<i4": torch.as_tensor(_Borrowed(p, shape, self, typestr), device=dev)  # noqa: E731
+            G = self.max_graphs
+            self._order_views = (ptrs, view(ptrs[0], (self.max_nodes, max(int(self.desc.in_dim), 1)), "<f4"),
+                                 view(ptrs[1], (max(self.max_edges, 1), 2)), view(ptrs[2], (G + 1,)), view(ptrs[3], (G + 1,)),
+                                 view(ptrs[4], (G,)))
+        _, x_ord, coo, nptr, eptr, perm = self._order_views
+        return x_ord[:N], coo[:E], nptr[:B + 1], eptr[:B + 1], perm[:B], tuple(int(v.value) for v in seg)
+
+    def forward_pyg_ordered(self, x, edge_index, batch=None, ptr=None, num_graphs=None, out=None, stream=None):
+        """``forward_pyg`` for batches that hold a few graphs beyond the ``max_graph_nodes`` promise: ordered ingest, the large
+        segment set to its triple (removed when nothing is large), forward, rows put back (``gnnb_forward_pyg_ordered``).
+        Returns ``out`` [B, out_dim] in the CALLER's graph order.  Waits once on ``stream`` (three integers; not capturable).  The
+        large-segment setting is left on the workspace; the stage-level entry points work afterwards, on the ORDERED batch."""
+        batch, ptr, B, N, E = self._ordered_args(x, edge_index, batch, ptr, num_graphs)
+        out = _out(out, B, self.out_dim, x)
+        _check(self.lib.gnnb_forward_pyg_ordered(self._model, self._ws, _dptr(x), _dptr(edge_index), _optr(batch), _optr(ptr),
+                                                 B, N, E, _dptr(out), _stream_ptr(stream)))
+        self._prepared(B, N, E, None)  # (the ordered batch's index arrays live in the workspace)
         return out
 
     # ------------------------------------------------------------------ stage-level entry points

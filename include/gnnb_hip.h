@@ -252,7 +252,8 @@ int gnnb_workspace_check(gnnb_workspace *ws, void *stream);
  * input order kept inside a graph (stable: the floating-point sum order of every aggregate depends on it) -- exactly what the
  * host adapter gnnbuilder_amd.batching.from_pyg_batch returns.  num_graphs / num_nodes / num_edges are host integers
  * (Batch.num_graphs and tensor shapes); no device value is read back, nothing synchronises, and the launch sequence depends on
- * those three integers only: a captured graph replays on grouped and on shuffled batches alike.
+ * those three integers only: a captured graph replays on grouped and on shuffled batches alike.  (The ordered form in
+ * gnnb_order.h is the exception: it waits once, for three integers.)
  *
  * Validation, on the device (flag 128 of gnnb_workspace_check -> GNNB_ERR_GRAPH; the lazy report of the next
  * gnnb_graph_prep / gnnb_ingest_pyg fires as for the other flags): an endpoint outside [0, N) (negative, or a value that
@@ -279,6 +280,8 @@ int gnnb_ingest_pyg(gnnb_workspace *ws, const int64_t *edge_index_dev, const int
 int gnnb_forward_pyg(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev,
                      const int64_t *batch_dev, const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges,
                      float *out_dev, void *stream);
+
+/* (PyG mini-batches whose oversized graphs are ordered last on the device: the extension header gnnb_order.h, same library.) */
 
 /* ------------------------------------------------------------------ stage entry points
  * The individual kernels, for parity tests, profiling and the roofline measurement. */
