@@ -74,6 +74,8 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     G2Deep g;
     g.nl = 0;
     const int L = d.num_layers;
+    if (model->edge_dim) // a GINE model: no stack kernel forms the edge term
+        return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
         g.wmid = model->gin_w;
@@ -211,6 +213,14 @@ static int gin_hidden(const LayerCtx &c)
     const std::vector<const float *> &p = c.model->conv[c.l];
     const int fi = c.fi, fo = c.fo;
     int rc;
+    if (c.model->edge_dim) {
+        // GINE: the same layer with relu(x_j + W_e e_ij + b_e) as the message -- k_gine_aggregate forms the edge term on chip
+        // (slots 4, 5: W_e [fi, edge_dim], b_e); none of the fused rungs, everything behind the aggregate is GIN's
+        if (c.M > 0)
+            GNNB_HIP_TRY(launch_gine_aggregate(c.tv, c.cur, c.ws->edge_attr, c.model->edge_dim, p[4], c.model->edge_dim, p[5], c.ws->agg, fi,
+                                               d.gin_eps, c.hs()));
+        return c.linear1(c.rows(c.ws->agg, fi), fi, p[0], fi, p[1], nullptr, c.rows(c.ws->tmp0, fo), fo, GNNB_ACT_RELU);
+    }
     if (c.whole && options().fuse_narrow && fi <= 32)
         GNNB_RUNG(attempt(launch_conv_gather(c.ws->t, GNNB_AGG_SUM, d.gin_eps, c.cur, fi, fi, p[0], fi, p[1], nullptr, c.ws->tmp0, fo, GNNB_ACT_RELU, c.hs()),
                           "fused narrow conv"));
@@ -628,7 +638,7 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward");
     if (!ws->prepared)
         return fail(GNNB_ERR_INVALID, "workspace has no prepared batch");
-    if (memcmp(&model->desc, &ws->desc, sizeof(gnnb_model_desc)) != 0)
+    if (memcmp(&model->desc, &ws->desc, sizeof(gnnb_model_desc)) != 0 || model->edge_dim != ws->edge_dim)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;
@@ -652,10 +662,8 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
     return readout_layerwise(model, ws, cur, pooled, out_dev, stream);
 }
 
-extern "C" {
-
-int gnnb_forward_prepared(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev,
-                          float *out_dev, void *stream)
+// gnnb_forward_prepared and gnnb_forward_prepared_edges behind their checks
+static int forward_prepared(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, float *out_dev, void *stream)
 {
     // every launch below runs in the MODEL's math mode; the reduced modes' kernels flag this workspace
     MathScope math_scope(model ? model->desc.math : -1, ws ? ws->t.err : nullptr, ws ? ws->t.err_host_dev : nullptr);
@@ -669,6 +677,52 @@ int gnnb_forward_prepared(const gnnb_model *model, gnnb_workspace *ws, const flo
     return GNNB_OK;
 }
 
+// a GINE model, its own workspace, and edge attributes for a batch of num_edges edges
+static int check_edge_forward(const gnnb_model *model, const gnnb_workspace *ws, const float *edge_attr_dev, int num_edges, const char *entry)
+{
+    if (!model || !ws)
+        return fail(GNNB_ERR_INVALID, "null argument to %s", entry);
+    if (!model->edge_dim)
+        return fail(GNNB_ERR_INVALID, "%s takes a model of gnnb_edge_model_create; this one has no edge weights", entry);
+    if (model->edge_dim != ws->edge_dim)
+        return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
+    if (num_edges > 0 && !edge_attr_dev)
+        return fail(GNNB_ERR_INVALID, "%s: edge_attr_dev is NULL for a batch of %d edges", entry, num_edges);
+    return GNNB_OK;
+}
+
+extern "C" {
+
+int gnnb_forward_prepared(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev,
+                          float *out_dev, void *stream)
+{
+    if (const int rc = refuse_edge_model(model, ws, "gnnb_forward_prepared", "gnnb_forward_prepared_edges"))
+        return rc;
+    return forward_prepared(model, ws, x_dev, out_dev, stream);
+}
+
+int gnnb_forward_prepared_edges(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev,
+                                float *out_dev, void *stream)
+{
+    if (const int rc = check_edge_forward(model, ws, edge_attr_dev, ws && ws->prepared ? ws->t.num_edges : 0, "gnnb_forward_prepared_edges"))
+        return rc;
+    ws->edge_attr = edge_attr_dev;
+    const int rc = forward_prepared(model, ws, x_dev, out_dev, stream);
+    ws->edge_attr = nullptr;
+    return rc;
+}
+
+int gnnb_forward_batched_edges(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev,
+                               const int32_t *coo_dev, const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev, int num_graphs,
+                               int num_nodes, int num_edges, float *out_dev, void *stream)
+{
+    if (const int rc = check_edge_forward(model, ws, edge_attr_dev, num_edges, "gnnb_forward_batched_edges"))
+        return rc;
+    if (const int rc = gnnb_graph_prep(ws, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, model->desc.pna_delta, stream))
+        return rc;
+    return gnnb_forward_prepared_edges(model, ws, x_dev, edge_attr_dev, out_dev, stream);
+}
+
 int gnnb_forward_batched(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev,
                          const int32_t *coo_dev, const int32_t *node_ptr_dev,
                          const int32_t *edge_ptr_dev, int num_graphs, int num_nodes, int num_edges,
@@ -676,6 +730,8 @@ int gnnb_forward_batched(const gnnb_model *model, gnnb_workspace *ws, const floa
 {
     if (!model || !ws)
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_batched");
+    if (const int erc = refuse_edge_model(model, ws, "gnnb_forward_batched", "gnnb_forward_batched_edges"))
+        return erc;
     int rc = gnnb_graph_prep(ws, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes,
                              num_edges, model->desc.pna_delta, stream);
     if (rc != GNNB_OK)
@@ -692,6 +748,10 @@ int gnnb_forward_prepared_prep_next(const gnnb_model *model, gnnb_workspace *ws,
 {
     if (!model || !ws || !ws_next)
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_prepared_prep_next");
+    if (const int erc = refuse_edge_model(model, ws, "gnnb_forward_prepared_prep_next", "gnnb_forward_prepared_edges and gnnb_graph_prep"))
+        return erc;
+    if (const int erc = refuse_edge_model(nullptr, ws_next, "gnnb_forward_prepared_prep_next", "gnnb_forward_prepared_edges and gnnb_graph_prep"))
+        return erc;
     if (ws == ws_next)
         return fail(GNNB_ERR_INVALID, "gnnb_forward_prepared_prep_next: the next batch needs a workspace of its own (the forward reads "
                                       "the tables the prep writes)");
@@ -732,6 +792,8 @@ int gnnb_forward_batched_host(const gnnb_model *model, gnnb_workspace *ws, const
 {
     if (!model || !ws || !x || !node_ptr || !edge_ptr || !out || (num_edges > 0 && !coo))
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_batched_host");
+    if (const int erc = refuse_edge_model(model, ws, "gnnb_forward_batched_host", "gnnb_forward_batched_edges on device buffers"))
+        return erc;
     if (num_graphs > ws->max_graphs || num_nodes > ws->max_nodes || num_edges > ws->max_edges)
         return fail(GNNB_ERR_CAPACITY,
                     "batch (%d graphs, %d nodes, %d edges) exceeds workspace (%d, %d, %d)",
@@ -775,6 +837,8 @@ int gnnb_gcn_stack_timed(const gnnb_model *model, gnnb_workspace *ws, const floa
 {
     if (!model || !ws || !x_dev || iters < 1 || !out_us_per_launch)
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_gcn_stack_timed");
+    if (const int erc = refuse_edge_model(model, ws, "gnnb_gcn_stack_timed", "gnnb_forward_prepared_edges: it runs layer by layer"))
+        return erc;
     MathScope math_scope(model->desc.math, ws->t.err, ws->t.err_host_dev);
     if (!ws->prepared)
         return fail(GNNB_ERR_INVALID, "workspace has no prepared batch");

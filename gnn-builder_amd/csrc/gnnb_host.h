@@ -8,6 +8,7 @@
 
 #include "gnnb_internal.h"
 #include "gnnb_order.h"
+#include "gnnb_edge.h"
 
 namespace gnnb {
 
@@ -77,6 +78,7 @@ struct gnnb_model {
     const float *gin_w = nullptr, *gin_b = nullptr;
     gnnb::HeadArgs *head_dev = nullptr; // the MLP head's {weights, biases, widths} once more in device memory: k_gcn2_zf reads it at the
                                         // end of a workgroup's life (by value the 42 dwords stayed in scalar registers through its stage loop)
+    int edge_dim = 0; // > 0: a GINE model (gnnb_edge_model_create) -- conv slots 4, 5 of every layer hold W_e [in, edge_dim] and b_e [in]
     int device = 0;
 };
 
@@ -96,6 +98,9 @@ struct gnnb_workspace {
     bool flags_reported = false; // gnnb_forward_pyg: its ingest has made the lazy flag report of this call; the graph prep behind it skips its
                                  // own, which could already see what THIS batch's ingest kernels flagged
     bool ingested = false;       // an ingest has been enqueued: gnnb_workspace_check has something to report on
+    int edge_dim = 0;            // of the model the workspace was created for (0: no edge weights)
+    char *edge_blob = nullptr;   // gnnb_workspace_enable_edge_ingest: edge_attr in COO row order, [max_edges, edge_dim], one allocation
+    const float *edge_attr = nullptr; // the _edges forward in progress: its [E, edge_dim] edge attributes (nullptr outside one)
     char *order_blob = nullptr;  // gnnb_workspace_enable_ordered_ingest: the ordered batch and the staged outputs (order_layout), one allocation
     int32_t *order_triple = nullptr, *order_triple_dev = nullptr; // host-mapped (first large graph, node row, edge row) of k_order_graphs, and
                                                                   // its device-visible address
@@ -127,6 +132,9 @@ struct gnnb_workspace {
 namespace gnnb {
 // the model's MLP head as the readout kernels take it (gnnb_model.hip): the ONLY place that fills a HeadArgs
 HeadArgs model_head_args(const gnnb_model *model);
+
+// GNNB_OK, or GNNB_ERR_INVALID for a GINE model / its workspace at `entry`, which takes no edge attributes: says which entry does
+int refuse_edge_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
 
 // gnnb_runtime.hip, for the forward (gnnb_forward.hip) -- each is described where it is defined
 int ensure_gcoef(gnnb_workspace *ws, void *stream);

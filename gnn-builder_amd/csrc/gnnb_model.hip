@@ -236,7 +236,8 @@ WeightBias gin_execution_order(const gnnb_model_desc &d, const std::vector<float
 }
 
 // One conv layer's canonical tensors p[] and, behind them, the derived slots its conv type has -> their offsets in the image
-std::vector<size_t> push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p)
+// edge_dim > 0 (a GINE model: GIN's four tensors, then conv.lin): slots 4, 5 = W_e [in, edge_dim], b_e [in]
+std::vector<size_t> push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
@@ -252,6 +253,10 @@ std::vector<size_t> push_conv_layer(WeightImage &im, const gnnb_model_desc &d, i
         break;
     case GNNB_CONV_GIN: // hidden = out_channels (models.py:90)
         off = {im.push(p[0], fo * fi), im.push(p[1], fo), im.push(p[2], fo * fo), im.push(p[3], fo)};
+        if (edge_dim > 0) {
+            off.push_back(im.push(p[4], fi * (size_t)edge_dim));
+            off.push_back(im.push(p[5], fi));
+        }
         break;
     case GNNB_CONV_SAGE:
         off = {im.push(sage_cat_weights(p[0], p[2], fo, fi, false)), im.push(p[1], fo)};
@@ -276,25 +281,31 @@ std::vector<size_t> push_conv_layer(WeightImage &im, const gnnb_model_desc &d, i
     return off;
 }
 
-} // namespace
-
-extern "C" {
-
-int gnnb_model_num_params(const gnnb_model_desc *desc)
+// parameter tensors of a model; edge_dim > 0: a GINE model (two more per conv layer), which GIN descriptions without the
+// fixed-point emulation have
+int count_params(const gnnb_model_desc *desc, int edge_dim)
 {
     int rc = validate_desc(desc);
     if (rc != GNNB_OK)
         return rc;
-    return conv_slots(desc->conv_type) * desc->num_layers + 2 * desc->mlp_num_linear;
+    if (edge_dim != 0) {
+        if (edge_dim < 1 || edge_dim > 16)
+            return fail(GNNB_ERR_INVALID, "edge_dim %d: a GINE model takes 1 .. 16 edge attributes", edge_dim);
+        if (desc->conv_type != GNNB_CONV_GIN)
+            return fail(GNNB_ERR_INVALID, "a GINE model's description is a GIN description (conv_type %d given)", desc->conv_type);
+        if (desc->fpx_w != 0)
+            return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover GINE models (fpx_w must be 0)");
+    }
+    return (conv_slots(desc->conv_type) + (edge_dim ? 2 : 0)) * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
-int gnnb_model_create(const gnnb_model_desc *desc, const float *const *host_params, int num_params,
-                      gnnb_model **out_model)
+// gnnb_model_create and gnnb_edge_model_create (edge_dim > 0)
+int model_create(const gnnb_model_desc *desc, int edge_dim, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
         return fail(GNNB_ERR_INVALID, "null out_model");
     *out_model = nullptr;
-    int expect = gnnb_model_num_params(desc);
+    int expect = count_params(desc, edge_dim);
     if (expect < 0)
         return expect;
     if (num_params != expect || !host_params)
@@ -309,16 +320,17 @@ int gnnb_model_create(const gnnb_model_desc *desc, const float *const *host_para
     const gnnb_model_desc &d = *desc;
     WeightImage im(d);
     std::vector<std::vector<size_t>> conv_off(d.num_layers);
-    const int slots = conv_slots(d.conv_type);
+    const int slots = conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;
     for (int l = 0; l < d.num_layers; l++, pi += slots)
-        conv_off[l] = push_conv_layer(im, d, l, host_params + pi);
+        conv_off[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim);
     size_t w1f_off = 0;
     const bool have_w1f = d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         w1f_off = im.push(zf_fragment_order(&im.img[conv_off[1][0]], d.hidden_dim, d.out_dim));
     size_t gin_w_off = 0, gin_b_off = 0;
-    const bool have_gin = d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
+    // (a GINE model takes no stack kernel: no execution-order copy)
+    const bool have_gin = edge_dim == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
                           d.out_dim <= d.hidden_dim && d.out_dim % 4 == 0;
     if (have_gin) {
         const WeightBias g = gin_execution_order(d, im.img, conv_off);
@@ -336,6 +348,7 @@ int gnnb_model_create(const gnnb_model_desc *desc, const float *const *host_para
 
     gnnb_model *m = new gnnb_model();
     m->desc = d;
+    m->edge_dim = edge_dim;
     (void)hipGetDevice(&m->device);
     m->blob_floats = img.size();
     hipError_t e = hipMalloc((void **)&m->blob, std::max<size_t>(img.size(), 4) * sizeof(float));
@@ -374,6 +387,36 @@ int gnnb_model_create(const gnnb_model_desc *desc, const float *const *host_para
     *out_model = m;
     return GNNB_OK;
 }
+
+} // namespace
+
+extern "C" {
+
+int gnnb_model_num_params(const gnnb_model_desc *desc) { return count_params(desc, 0); }
+
+int gnnb_model_create(const gnnb_model_desc *desc, const float *const *host_params, int num_params, gnnb_model **out_model)
+{
+    return model_create(desc, 0, host_params, num_params, out_model);
+}
+
+int gnnb_edge_model_num_params(const gnnb_model_desc *desc, int edge_dim)
+{
+    if (edge_dim == 0)
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a GINE model takes 1 .. 16 edge attributes (gnnb_model_num_params: models without)");
+    return count_params(desc, edge_dim);
+}
+
+int gnnb_edge_model_create(const gnnb_model_desc *desc, int edge_dim, const float *const *host_params, int num_params,
+                           gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (edge_dim == 0)
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a GINE model takes 1 .. 16 edge attributes (gnnb_model_create: models without)");
+    return model_create(desc, edge_dim, host_params, num_params, out_model);
+}
+
+int gnnb_model_edge_dim(const gnnb_model *model) { return model ? model->edge_dim : 0; }
 
 void gnnb_model_destroy(gnnb_model *model)
 {

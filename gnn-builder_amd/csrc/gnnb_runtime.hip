@@ -52,6 +52,13 @@ Options &options()
     return o;
 }
 
+int refuse_edge_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use)
+{
+    if ((model && model->edge_dim) || (ws && ws->edge_dim))
+        return fail(GNNB_ERR_INVALID, "%s: a GINE model (gnnb_edge_model_create) needs its edge attributes: call %s (gnnb_edge.h)", entry, use);
+    return GNNB_OK;
+}
+
 static thread_local int tl_math = -1; // >= 0: the calling thread is inside an entry point of a model with its own math mode
 static thread_local FlagWord tl_flag = {nullptr, nullptr};
 int launch_math() { return tl_math >= 0 ? tl_math : (int)options().math; }
@@ -150,6 +157,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
 
     gnnb_workspace *ws = new gnnb_workspace();
     ws->desc = d;
+    ws->edge_dim = model->edge_dim;
     ws->max_graphs = max_graphs;
     ws->max_nodes = max_nodes;
     ws->max_edges = max_edges;
@@ -252,6 +260,8 @@ void gnnb_workspace_destroy(gnnb_workspace *ws)
         (void)hipFree(ws->ingest_blob);
     if (ws->order_blob)
         (void)hipFree(ws->order_blob);
+    if (ws->edge_blob)
+        (void)hipFree(ws->edge_blob);
     if (ws->order_triple)
         (void)hipHostFree(ws->order_triple);
     if (ws->stage)
@@ -315,7 +325,9 @@ int gnnb_workspace_set_max_degree(gnnb_workspace *ws, int d)
 static bool stack_promised(const gnnb_workspace *ws)
 {
     const gnnb_model_desc &d = ws->desc;
-    return options().fuse_gcn2 && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 && ws->max_graph_nodes > 0;
+    // (a GINE model's workspace: never -- its layers take no stack kernel, whatever the promise)
+    return options().fuse_gcn2 && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 && ws->max_graph_nodes > 0 &&
+           ws->edge_dim == 0;
 }
 
 // ... and the WHOLE batch is expected there: no large segment, no fixed-point emulation.  Such a batch needs neither the
@@ -674,6 +686,8 @@ int gnnb_forward_pyg(const gnnb_model *model, gnnb_workspace *ws, const float *x
 {
     if (!model || !ws)
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg");
+    if (const int rc = refuse_edge_model(model, ws, "gnnb_forward_pyg", "gnnb_forward_pyg_edges"))
+        return rc;
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
     const int rc = gnnb_ingest_pyg(ws, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &coo, &node_ptr, &edge_ptr, stream);
     if (rc != GNNB_OK)
@@ -782,6 +796,8 @@ int gnnb_forward_pyg_ordered(const gnnb_model *model, gnnb_workspace *ws, const 
 {
     if (!model || !ws || (num_graphs > 0 && !out_dev))
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg_ordered");
+    if (const int rc = refuse_edge_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg_edges"))
+        return rc;
     const float *x_ord = nullptr;
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr, *perm = nullptr;
     int g0 = 0, n0 = 0, e0 = 0;
@@ -798,6 +814,90 @@ int gnnb_forward_pyg_ordered(const gnnb_model *model, gnnb_workspace *ws, const 
     if (frc != GNNB_OK)
         return frc;
     GNNB_HIP_TRY(launch_order_out(out_ord, perm, out_dev, num_graphs, ws->desc.mlp_out, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// GINE models: PyG mini-batches with edge attributes (gnnb_edge.h; k_gine.hip)
+size_t gnnb_edge_ingest_bytes(int max_edges, int edge_dim)
+{
+    if (max_edges < 0 || edge_dim < 1 || edge_dim > 16)
+        return 0;
+    return ((size_t)std::max(max_edges, 1) * (size_t)edge_dim * sizeof(float) + 255) & ~(size_t)255;
+}
+
+int gnnb_workspace_enable_edge_ingest(gnnb_workspace *ws)
+{
+    if (!ws)
+        return fail(GNNB_ERR_INVALID, "null workspace");
+    if (ws->edge_blob)
+        return GNNB_OK; // (enabled already: the allocation is made once)
+    if (!ws->edge_dim)
+        return fail(GNNB_ERR_INVALID, "gnnb_workspace_enable_edge_ingest: the workspace belongs to a model without edge weights "
+                                      "(gnnb_edge_model_create makes one with)");
+    if (ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_workspace_enable_edge_ingest: the workspace is in use (a batch has been prepared on it); "
+                                      "enable the edge ingest right after gnnb_workspace_create");
+    if (const int rc = gnnb_workspace_enable_ingest(ws))
+        return rc;
+    const size_t bytes = gnnb_edge_ingest_bytes(ws->max_edges, ws->edge_dim);
+    char *blob = nullptr;
+    const hipError_t e = hipMalloc((void **)&blob, bytes);
+    if (e != hipSuccess)
+        return fail(GNNB_ERR_HIP, "edge-ingest allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    ws->edge_blob = blob;
+    return GNNB_OK;
+}
+
+int gnnb_ingest_pyg_edges(gnnb_workspace *ws, const int64_t *edge_index_dev, const float *edge_attr_dev, const int64_t *batch_dev,
+                          const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges, const int32_t **coo_dev,
+                          const int32_t **node_ptr_dev, const int32_t **edge_ptr_dev, const float **edge_attr_ord_dev, void *stream)
+{
+    if (!ws || !edge_attr_ord_dev || (num_edges > 0 && !edge_attr_dev))
+        return fail(GNNB_ERR_INVALID, "null argument to gnnb_ingest_pyg_edges");
+    if (!ws->edge_blob)
+        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg_edges: call gnnb_workspace_enable_edge_ingest on the workspace first");
+    if (const int rc = gnnb_ingest_pyg(ws, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, coo_dev, node_ptr_dev, edge_ptr_dev, stream))
+        return rc;
+    // the rows follow their edges: the general path's last pass left sorted position -> input edge in one half of idx (which half:
+    // launch_ingest's pass count); whether that path ran at all is the state word, read by the kernel
+    const IngestLayout l = ingest_layout(ws->max_graphs, ws->max_nodes, ws->max_edges);
+    const int passes = ingest_sort_passes(num_graphs);
+    const int32_t *idx = (passes == 0 || num_edges < 2) ? nullptr : (const int32_t *)(ws->ingest_blob + l.idx[passes & 1]);
+    GNNB_HIP_TRY(launch_edge_attr_order(edge_attr_dev, idx, (const int32_t *)(ws->ingest_blob + l.state), (float *)ws->edge_blob, num_edges,
+                                        ws->edge_dim, (hipStream_t)stream));
+    *edge_attr_ord_dev = (const float *)ws->edge_blob;
+    return GNNB_OK;
+}
+
+int gnnb_forward_pyg_edges(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev,
+                           const float *edge_attr_dev, const int64_t *batch_dev, const int64_t *ptr_dev, int num_graphs, int num_nodes,
+                           int num_edges, float *out_dev, void *stream)
+{
+    if (!model || !ws)
+        return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg_edges");
+    if (!model->edge_dim || model->edge_dim != ws->edge_dim)
+        return fail(GNNB_ERR_INVALID, "gnnb_forward_pyg_edges takes a model of gnnb_edge_model_create and its workspace");
+    const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
+    const float *edge_attr = nullptr;
+    if (const int rc = gnnb_ingest_pyg_edges(ws, edge_index_dev, edge_attr_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &coo, &node_ptr,
+                                             &edge_ptr, &edge_attr, stream))
+        return rc;
+    ws->flags_reported = true; // (the ingest has made this call's lazy report, as in gnnb_forward_pyg)
+    const int frc = gnnb_forward_batched_edges(model, ws, x_dev, edge_attr, coo, node_ptr, edge_ptr, num_graphs, num_nodes, num_edges, out_dev, stream);
+    ws->flags_reported = false;
+    return frc;
+}
+
+int gnnb_aggregate_edges_fused(gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev, int edge_dim, const float *we_dev, int ldwe,
+                               const float *be_dev, float *out_dev, int width, float eps, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_edges_fused needs a prepared batch (gnnb_graph_prep)");
+    if (!x_dev || !out_dev || !we_dev || !be_dev || width < 1 || edge_dim < 1 || edge_dim > 16 || ldwe < edge_dim ||
+        (ws->t.num_edges > 0 && !edge_attr_dev))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_edges_fused (edge_dim 1 .. 16, ldwe >= edge_dim)");
+    GNNB_HIP_TRY(launch_gine_aggregate(ws->t, x_dev, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, out_dev, width, eps, (hipStream_t)stream));
     return GNNB_OK;
 }
 

@@ -255,8 +255,12 @@ class _GINEConv(nn.Module):
 
 class GINEConv_GNNB(nn.Module):
     """Reference models.py:97-123.  Not in SUPPORTED_GNN_CONVS there (the emitter has a TODO for it,
-    templates/model.cpp.jinja:143-144), so ``GNNModel`` does not stack it; the native layer is reachable through
-    ``runtime.CompiledModel.gine_conv`` (C ABI ``gnnb_aggregate_edges`` + ``gnnb_linear``)."""
+    templates/model.cpp.jinja:143-144); here ``GNNModel`` stacks it: ``GNNModel(..., graph_input_edge_dim=d, gnn_conv=
+    GINEConv_GNNB, ...)`` builds every layer with ``edge_dim=d`` (1 .. 16) and ``forward(x, edge_index, batch, edge_attr)`` hands
+    the same ``edge_attr`` [E, d] to each.  The accelerated path is ``runtime.CompiledModel.from_model`` with
+    ``forward_edges`` / ``forward_pyg_edges`` (C ABI ``include/gnnb_edge.h``: the edge projection runs inside the aggregate kernel,
+    csrc/k_gine.hip).  One layer as separate stage calls stays reachable through ``runtime.CompiledModel.gine_conv``
+    (``gnnb_aggregate_edges`` + ``gnnb_linear``).  ``Project`` does not generate GINE designs."""
 
     def __init__(self, in_channels: int, out_channels: int, edge_dim: int, hidden_dim: Optional[int] = None,
                  eps: float = 0.0, p_in: int = 1, p_out: int = 1):
@@ -396,8 +400,9 @@ class MLP(nn.Module):
         return len(self.linear_layers)
 
 
-SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB]
-_CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna"}
+SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB]
+_CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine"}
+MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h)
 
 
 class GNNModel(nn.Module):
@@ -423,6 +428,12 @@ class GNNModel(nn.Module):
         if self.gnn_activation not in SUPPORTED_ACTIVATIONS:
             raise ValueError(f"gnn_activation {gnn_activation} has no native kernel; choose from {SUPPORTED_ACTIVATIONS}")
         self.gnn_skip_connection = gnn_skip_connection
+        conv_kwargs = {}
+        if self.gnn_conv is GINEConv_GNNB:
+            d = self.graph_input_edge_dim
+            if not isinstance(d, int) or isinstance(d, bool) or not 1 <= d <= MAX_EDGE_DIM:
+                raise ValueError(f"a GINE model needs graph_input_edge_dim, an int in 1 .. {MAX_EDGE_DIM} (got {d!r})")
+            conv_kwargs = {"edge_dim": d, "hidden_dim": None}  # (the MLP's hidden width = out_channels, as for GIN)
 
         self.global_pooling = global_pooling
         self.mlp_head = mlp_head  # registered before gnn_convs: parameter order mlp_head_*, gnn_convs_*
@@ -451,18 +462,23 @@ class GNNModel(nn.Module):
                 dims = (self.gnn_hidden_dim, self.gnn_output_dim, self.gnn_p_hidden, self.gnn_p_out)
             else:
                 dims = (self.gnn_hidden_dim, self.gnn_hidden_dim, self.gnn_p_hidden, self.gnn_p_hidden)
-            self.gnn_convs.append(self.gnn_conv(dims[0], dims[1], p_in=dims[2], p_out=dims[3]))
+            self.gnn_convs.append(self.gnn_conv(dims[0], dims[1], p_in=dims[2], p_out=dims[3], **conv_kwargs))
             self.gnn_activations.append(self.gnn_activation())
 
-    def forward(self, x: Tensor, edge_index: Tensor, batch: Optional[Tensor] = None) -> Tensor:
+    def forward(self, x: Tensor, edge_index: Tensor, batch: Optional[Tensor] = None, edge_attr: Optional[Tensor] = None) -> Tensor:
         """``batch=None``: one graph -> ``[1, out]``, exactly the reference.  With ``batch``
         (node -> graph index, PyG ``Batch`` convention) every graph is pooled separately ->
         ``[num_graphs, out]``; the reference ignores ``batch`` and pools all nodes into one row
-        (models.py:551-553,569; SURVEY finding 3), which has no meaning for independent graphs."""
+        (models.py:551-553,569; SURVEY finding 3), which has no meaning for independent graphs.
+        ``edge_attr`` [E, graph_input_edge_dim]: a GINE model's edge features, the same for every layer (required there;
+        the other convs ignore it)."""
+        gine = self.gnn_conv is GINEConv_GNNB
+        if gine and edge_attr is None:
+            raise ValueError("a GINE model needs edge_attr [E, graph_input_edge_dim]")
         h = x
         for i, (conv, act) in enumerate(zip(self.gnn_convs, self.gnn_activations)):
             h_in = h
-            h = conv(h, edge_index)
+            h = conv(h, edge_index, edge_attr) if gine else conv(h, edge_index)
             if self.gnn_skip_connection and i != 0 and i != self.gnn_num_layers - 1:
                 h = h + h_in
             h = act(h)
@@ -549,7 +565,8 @@ class GNNModel(nn.Module):
             "mlp_hidden": self.mlp_head.hidden_dim,
             "mlp_out": self.mlp_head.out_dim,
             "mlp_activation": _ACT_NAME[self.mlp_head.activation],
-            "gin_eps": float(conv0.eps) if isinstance(conv0, GINConv_GNNB) else 0.0,
+            "gin_eps": float(conv0.eps) if isinstance(conv0, (GINConv_GNNB, GINEConv_GNNB)) else 0.0,
+            "edge_dim": int(self.graph_input_edge_dim) if self.gnn_conv is GINEConv_GNNB else 0,
             "pna_delta": float(conv0.delta_scaler) if isinstance(conv0, PNAConv_GNNB) else 1.0,
             "output_activation": out_act,
         }
@@ -563,6 +580,8 @@ class GNNModel(nn.Module):
             "sage": ["conv_lin_l_weight", "conv_lin_l_bias", "conv_lin_r_weight"],
             "pna": ["conv_pre_nns_0_0_weight", "conv_pre_nns_0_0_bias", "conv_post_nns_0_0_weight",
                     "conv_post_nns_0_0_bias", "conv_lin_weight", "conv_lin_bias"],
+            "gine": ["mlp_linear_0_weight", "mlp_linear_0_bias", "mlp_linear_1_weight", "mlp_linear_1_bias",
+                     "conv_lin_weight", "conv_lin_bias"],  # (conv.lin: the edge projection [in, edge_dim], [in])
         }[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

@@ -1,4 +1,5 @@
-"""Python binding of the C ABI in ``include/gnnb_hip.h`` and its extension ``include/gnnb_order.h`` (``libgnnb_hip.so``).
+"""Python binding of the C ABI in ``include/gnnb_hip.h`` and its extensions ``include/gnnb_order.h`` and ``include/gnnb_edge.h``
+(``libgnnb_hip.so``).
 
 This is the accelerated product path.  It has NO fallback: if the HIP library is not built, or no
 MI355X is visible, every entry point raises ``GnnbUnavailable`` -- it never routes to PyTorch or
@@ -26,6 +27,7 @@ CSRC_DIR = PKG_DIR / "csrc"
 GNNB_OK = 0                                                                      # gnnb_status
 GNNB_ERR_RANGE = -6                                                              # gnnb_status
 CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                 # gnnb_conv
+MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -141,6 +143,19 @@ ABI_ORDER = {
     "gnnb_ingest_pyg_ordered": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _PP, _PP, _PP, _PP, _PP, _PI, _PI, _PI, _P]),
     "gnnb_forward_pyg_ordered": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
 }
+# ... and of include/gnnb_edge.h (GINE models), in its order (tests/test_abi_edge.py)
+ABI_EDGE = {
+    "gnnb_edge_model_num_params": (_I, [_DESC, _I]),
+    "gnnb_edge_model_create": (_I, [_DESC, _I, _PP, _I, _PP]),
+    "gnnb_model_edge_dim": (_I, [_P]),
+    "gnnb_forward_batched_edges": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "gnnb_forward_prepared_edges": (_I, [_P, _P, _P, _P, _P, _P]),
+    "gnnb_aggregate_edges_fused": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _F, _P]),
+    "gnnb_edge_ingest_bytes": (_Z, [_I, _I]),
+    "gnnb_workspace_enable_edge_ingest": (_I, [_P]),
+    "gnnb_ingest_pyg_edges": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _PP, _PP, _PP, _PP, _P]),
+    "gnnb_forward_pyg_edges": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+}
 
 
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
@@ -153,6 +168,12 @@ def order_bytes(max_graphs: int, max_nodes: int, max_edges: int, in_dim: int, ml
     """Size of the allocation ``CompiledModel.enable_ordered_ingest`` makes beside the ingest's (``gnnb_order_bytes``): the
     ordered ``x`` / ``coo`` / ptr arrays, ``perm``, the per-graph shifts and the staged outputs.  Pure host arithmetic, no GPU needed."""
     return int(load_library(require_gpu=False).gnnb_order_bytes(int(max_graphs), int(max_nodes), int(max_edges), int(in_dim), int(mlp_out)))
+
+
+def edge_ingest_bytes(max_edges: int, edge_dim: int) -> int:
+    """Size of the allocation ``CompiledModel.enable_edge_ingest`` makes beside the ingest's (``gnnb_edge_ingest_bytes``): the edge
+    attributes in COO row order.  Pure host arithmetic, no GPU needed; 0 for an ``edge_dim`` outside 1 .. 16."""
+    return int(load_library(require_gpu=False).gnnb_edge_ingest_bytes(int(max_edges), int(edge_dim)))
 
 
 def build_library(force: bool = False) -> Path:
@@ -180,7 +201,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
                 "or `make -C gnn-builder_amd/csrc`.  There is no CPU fallback.")
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
-        for name, (restype, argtypes) in {**ABI, **ABI_ORDER}.items():
+        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -202,7 +223,7 @@ def set_option(name: str, value: int) -> None:
 
 def make_desc(spec: dict) -> ModelDesc:
     d = ModelDesc()
-    d.conv_type = CONV[spec["conv"]]
+    d.conv_type = CONV["gin" if spec["conv"] == "gine" else spec["conv"]]  # (GINE: GIN's description, edge_dim beside it)
     d.num_layers = spec["num_layers"]
     d.in_dim = spec["in_dim"]
     d.hidden_dim = spec["hidden_dim"]
@@ -313,19 +334,27 @@ class CompiledModel:
         self._keep = None  # its index tensors, which the device still reads
         self._ingest, self._ingest_views = False, (None,)
         self._ordered, self._order_views = False, (None,)
+        self._edge_ingest, self._edge_views = False, (None,)
+        self.edge_dim = int(spec.get("edge_dim", 0) or 0) if spec.get("conv") == "gine" else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
         self.desc = make_desc(spec)
         host = [np.ascontiguousarray(np.asarray(p.detach().cpu().numpy() if hasattr(p, "detach") else p,
                                                 dtype=np.float32)) for p in params]
-        n_expect = self.lib.gnnb_model_num_params(C.byref(self.desc))
+        if spec.get("conv") == "gine" and not 1 <= self.edge_dim <= MAX_EDGE_DIM:
+            raise GnnbError(f"a GINE model needs spec['edge_dim'] in 1 .. {MAX_EDGE_DIM}, got {spec.get('edge_dim')!r}")
+        n_expect = (self.lib.gnnb_edge_model_num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
+                    self.lib.gnnb_model_num_params(C.byref(self.desc)))
         if n_expect < 0:
             _check(n_expect)
         if len(host) != n_expect:
             raise GnnbError(f"model needs {n_expect} parameter tensors, got {len(host)}")
         arr = (C.c_void_p * len(host))(*[h.ctypes.data for h in host])
-        _check(self.lib.gnnb_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
+        if self.edge_dim:
+            _check(self.lib.gnnb_edge_model_create(C.byref(self.desc), self.edge_dim, arr, len(host), C.byref(self._model)))
+        else:
+            _check(self.lib.gnnb_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
         rc = self.lib.gnnb_workspace_create(self._model, self.max_graphs, self.max_nodes, self.max_edges, C.byref(self._ws))
         if rc != GNNB_OK:
             self.close()
@@ -384,7 +413,7 @@ class CompiledModel:
         return int(self.lib.gnnb_workspace_bytes(self._ws))
 
     def close(self) -> None:
-        self._ingest_views = self._order_views = (None,)  # (they borrow the workspace: dropped with it)
+        self._ingest_views = self._order_views = self._edge_views = (None,)  # (they borrow the workspace: dropped with it)
         if self._ws:
             self.lib.gnnb_workspace_destroy(self._ws)
             self._ws = C.c_void_p()
@@ -615,6 +644,96 @@ class CompiledModel:
         self._prepared(B, N, E, None)  # (the ordered batch's index arrays live in the workspace)
         return out
 
+    # ------------------------------------------------------------------ GINE models: forwards with edge attributes
+    def _require_edge_attr(self, edge_attr, E: int, like, width: Optional[int] = None):
+        """``edge_attr`` of an entry point that reads one [edge_dim] row per edge: fp32 [E, edge_dim] on ``like``'s device; an
+        empty batch's may be None.  Returns its device pointer (None: NULL)."""
+        width = self.edge_dim if width is None else width
+        if edge_attr is None:
+            if E:
+                raise GnnbError(f"edge_attr is required: the batch has {E} edges")
+            return None
+        _require_rows(edge_attr, "edge_attr", E, width, like)
+        return _dptr(edge_attr) if E else None
+
+    def _require_edge_model(self, what: str) -> None:
+        if not self.edge_dim:
+            raise GnnbError(f"{what} takes a GINE model (a GNNModel of GINEConv_GNNB layers: edge weights); this model has none")
+
+    def forward_edges(self, x, edge_attr, coo, node_ptr, edge_ptr, out=None, stream=None):
+        """``forward`` of a GINE model: ``edge_attr`` [E, edge_dim] fp32, row ``i`` belongs to ``coo`` row ``i``
+        (``gnnb_forward_batched_edges``).  Everything else as ``forward``."""
+        self._require_edge_model("forward_edges")
+        self._check_batch(x, coo, node_ptr, edge_ptr)
+        B = int(node_ptr.numel()) - 1
+        N, E = int(x.shape[0]), int(coo.shape[0])
+        ea = self._require_edge_attr(edge_attr, E, x)
+        out = _out(out, B, self.out_dim, x)
+        _check(self.lib.gnnb_forward_batched_edges(self._model, self._ws, _dptr(x), ea, _dptr(coo), _dptr(node_ptr), _dptr(edge_ptr),
+                                                   B, N, E, _dptr(out), _stream_ptr(stream)))
+        self._prepared(B, N, E, (coo, node_ptr, edge_ptr))
+        return out
+
+    def forward_prepared_edges(self, x, edge_attr, out=None, stream=None):
+        """``forward_prepared`` of a GINE model on the batch ``graph_prep`` left in the workspace."""
+        self._require_edge_model("forward_prepared_edges")
+        self._require_x(x, int(self.desc.in_dim))
+        ea = self._require_edge_attr(edge_attr, self._E, x)
+        out = _out(out, self._B, self.out_dim, x)
+        _check(self.lib.gnnb_forward_prepared_edges(self._model, self._ws, _dptr(x), ea, _dptr(out), _stream_ptr(stream)))
+        return out
+
+    def enable_edge_ingest(self) -> None:
+        """``enable_ingest`` (if that has not been done) and one more device allocation (``edge_ingest_bytes``) for
+        ``ingest_pyg_edges`` / ``forward_pyg_edges``.  Synchronous: call it once, right after construction, outside stream
+        capture."""
+        self._require_edge_model("enable_edge_ingest")
+        _check(self.lib.gnnb_workspace_enable_edge_ingest(self._ws))
+        if not self._ingest:
+            self._ingest, self._ingest_views = True, (None,)
+        self._edge_ingest, self._edge_views = True, (None,)
+
+    def _edge_pyg_args(self, edge_index, edge_attr, batch, ptr, num_graphs, num_nodes, like):
+        if not self._edge_ingest:
+            raise GnnbError("the edge ingest is not enabled on this model's workspace: call enable_edge_ingest() once after "
+                            "construction")
+        batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, num_nodes)
+        return batch, ptr, B, N, E, self._require_edge_attr(edge_attr, E, like)
+
+    def ingest_pyg_edges(self, edge_index, edge_attr, batch=None, ptr=None, num_graphs=None, stream=None, num_nodes=None):
+        """``ingest_pyg`` with the mini-batch's ``edge_attr`` [E, edge_dim] fp32 (``Batch.edge_attr``, in ``edge_index``'s column
+        order): returns ``(coo, node_ptr, edge_ptr, edge_attr_ord)`` with ``edge_attr_ord[i]`` the attributes of ``coo`` row ``i`` --
+        what ``batching.from_pyg_batch(..., edge_attr=...)`` computes on the host, with no synchronisation
+        (``gnnb_ingest_pyg_edges``).  VIEWS of the workspace: valid until the next ingest on it."""
+        import torch
+        batch, ptr, B, N, E, ea = self._edge_pyg_args(edge_index, edge_attr, batch, ptr, num_graphs, num_nodes, edge_index)
+        out_p = [C.c_void_p() for _ in range(4)]
+        _check(self.lib.gnnb_ingest_pyg_edges(self._ws, _dptr(edge_index), ea, _optr(batch), _optr(ptr), B, N, E,
+                                              *[C.byref(p) for p in out_p], _stream_ptr(stream)))
+        ptrs = tuple(p.value for p in out_p)
+        if self._edge_views[0] != ptrs:  # (made once, sliced per call: as ingest_pyg's)
+            dev = edge_index.device
+            view = lambda p, shape, typestr="<i4": torch.as_tensor(_Borrowed(p, shape, self, typestr), device=dev)  # noqa: E731
+            G = self.max_graphs
+            self._edge_views = (ptrs, view(ptrs[0], (max(self.max_edges, 1), 2)), view(ptrs[1], (G + 1,)), view(ptrs[2], (G + 1,)),
+                                view(ptrs[3], (max(self.max_edges, 1), self.edge_dim), "<f4"))
+        _, coo, nptr, eptr, ea_ord = self._edge_views
+        return coo[:E], nptr[:B + 1], eptr[:B + 1], ea_ord[:E]
+
+    def forward_pyg_edges(self, x, edge_index, edge_attr, batch=None, ptr=None, num_graphs=None, out=None, stream=None):
+        """``forward_pyg`` of a GINE model: ``edge_attr`` [E, edge_dim] fp32 in ``edge_index``'s column order; ingest (the
+        attribute rows follow their edges) and forward on one stream, no host synchronisation, capturable
+        (``gnnb_forward_pyg_edges``)."""
+        import torch
+        self._require_edge_model("forward_pyg_edges")
+        _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
+        batch, ptr, B, N, E, ea = self._edge_pyg_args(edge_index, edge_attr, batch, ptr, num_graphs, int(x.shape[0]), x)
+        out = _out(out, B, self.out_dim, x)
+        _check(self.lib.gnnb_forward_pyg_edges(self._model, self._ws, _dptr(x), _dptr(edge_index), ea, _optr(batch), _optr(ptr),
+                                               B, N, E, _dptr(out), _stream_ptr(stream)))
+        self._prepared(B, N, E, None)  # (the batch's index arrays live in the workspace)
+        return out
+
     # ------------------------------------------------------------------ stage-level entry points
     # (raw pointers cross the C ABI: each checks every operand's dtype, layout, device and rows against the prepared batch, so
     # that a short, narrower, int64, CPU or strided tensor is refused here instead of read out of bounds or reinterpreted)
@@ -670,6 +789,26 @@ class CompiledModel:
         out = _out(out, self._N, w, x)
         _check(self.lib.gnnb_aggregate_edges(self._ws, _dptr(x), _dptr(edge_term), _dptr(out), w,
                                              float(eps), _stream_ptr(stream)))
+        return out
+
+    def aggregate_edges_fused(self, x, edge_attr, w_edge, b_edge, eps: float = 0.0, out=None, stream=None):
+        """GINE aggregate with the edge projection inside the kernel (``gnnb_aggregate_edges_fused``, csrc/k_gine.hip):
+        ``(1 + eps) x_i + sum_j relu(x_j + w_edge e_ij + b_edge)``; ``edge_attr`` [E, edge_dim <= 16] in COO order, ``w_edge``
+        [width, edge_dim] (a column slice of a wider matrix is fine: its row stride is passed on), ``b_edge`` [width]."""
+        import torch
+        self._require_x(x)
+        w = int(x.shape[1])
+        _require_strided(w_edge, "w_edge", w, 1)
+        ed = int(w_edge.shape[1])
+        if not 1 <= ed <= MAX_EDGE_DIM or w_edge.device != x.device:
+            raise GnnbError(f"w_edge must be [{w}, 1 .. {MAX_EDGE_DIM}] on {x.device}, got {tuple(w_edge.shape)} on {w_edge.device}")
+        _require(b_edge, "b_edge", torch.float32, 1, w)
+        if b_edge.device != x.device:
+            raise GnnbError(f"b_edge must be on {x.device}")
+        ea = self._require_edge_attr(edge_attr, self._E, x, ed)
+        out = _out(out, self._N, w, x)
+        _check(self.lib.gnnb_aggregate_edges_fused(self._ws, _dptr(x), ea, ed, _dptr(w_edge), int(w_edge.stride(0)) if w > 1 else ed,
+                                                   _dptr(b_edge), _dptr(out), w, float(eps), _stream_ptr(stream)))
         return out
 
     def gine_conv(self, x, edge_attr, w_edge, b_edge, w0, b0, w1, b1, eps: float = 0.0, stream=None):
