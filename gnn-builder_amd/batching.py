@@ -136,7 +136,7 @@ def from_pyg_batch(x, edge_index, batch=None, ptr=None, num_graphs=None, edge_at
     returns the same three index arrays without a copy to the host or a synchronisation:
     ``runtime.CompiledModel.ingest_pyg`` / ``forward_pyg`` (``gnnb_ingest_pyg``, csrc/k_ingest.hip); with the oversized graphs
     ordered last as well (``order_large_last`` below): ``ingest_pyg_ordered`` / ``forward_pyg_ordered`` (csrc/k_order.hip); with
-    edge attributes: ``ingest_pyg_edges`` / ``forward_pyg_edges`` (``gnnb_ingest_pyg_edges``, csrc/k_gine.hip)."""
+    edge attributes: ``ingest_pyg_edges`` / ``forward_pyg_edges`` (``gnnb_ingest_pyg_edges``, csrc/k_ingest.hip)."""
     x = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
     ei = np.asarray(edge_index)
     if ei.ndim != 2 or ei.shape[0] != 2:

@@ -1,5 +1,6 @@
 // gnnb_forward.hip -- the forward of libgnnb_hip.so: WHICH kernels of k_*.hip a forward runs, in which order and on which
-// stream.  Host only, no kernels.  (gnnb_runtime.hip: errors, options, workspace, graph prep, the stage entry points.)
+// stream.  Host only, no kernels.  (gnnb_runtime.hip: errors, options, workspace, graph prep, the stage entry points;
+// gnnb_ingest.hip: the PyG mini-batch entries, which end in forward_batched_tail.)
 //
 // Sequencing follows the reference's generated top (gnnbuilder/templates/model.cpp.jinja):
 //   compute_gnn_head (:151-359)                -> the stack kernels, or per layer: k_aggregate + k_linear (+skip +act fused)
@@ -135,6 +136,7 @@ struct LayerCtx {
     bool fpx;
     bool *pooled;      // non-null: the caller accepts ws->pooled in place of the last layer's output; set by try_pooling_gemm
     bool *mean_ready;  // GraphSAGE: ws->agg already holds mean_j of this layer's input rows (k_sage_first_mean, the layer before)
+    const float *edge_attr; // GINE: the batch's [E, edge_dim] edge attributes in COO row order (nullptr: a model without)
     int l, fi, fo;
     bool last;
     const float *cur;  // the layer's input [N, fi] ...
@@ -217,7 +219,7 @@ static int gin_hidden(const LayerCtx &c)
         // GINE: the same layer with relu(x_j + W_e e_ij + b_e) as the message -- k_gine_aggregate forms the edge term on chip
         // (slots 4, 5: W_e [fi, edge_dim], b_e); none of the fused rungs, everything behind the aggregate is GIN's
         if (c.M > 0)
-            GNNB_HIP_TRY(launch_gine_aggregate(c.tv, c.cur, c.ws->edge_attr, c.model->edge_dim, p[4], c.model->edge_dim, p[5], c.ws->agg, fi,
+            GNNB_HIP_TRY(launch_gine_aggregate(c.tv, c.cur, c.edge_attr, c.model->edge_dim, p[4], c.model->edge_dim, p[5], c.ws->agg, fi,
                                                d.gin_eps, c.hs()));
         return c.linear1(c.rows(c.ws->agg, fi), fi, p[0], fi, p[1], nullptr, c.rows(c.ws->tmp0, fo), fo, GNNB_ACT_RELU);
     }
@@ -347,7 +349,8 @@ static int pna_layer(const LayerCtx &c)
 // row_lo = 0 is the whole batch; row_lo > 0 the caller's large segment (gnnb_workspace_set_large_segment), whose first
 // node tile is tile_lo.  *out_cur = the last layer's output matrix ([N, width], rows below row_lo untouched) -- unless
 // pooled_in_epilogue is given and comes back true: the last layer's GEMM pooled into ws->pooled and wrote no node matrix.
-static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, int row_lo, int tile_lo,
+// edge_attr: a GINE model's edge attributes (nullptr: a model without).
+static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const float *edge_attr, int row_lo, int tile_lo,
                            const float **out_cur, void *stream, bool *pooled_in_epilogue = nullptr)
 {
     if (pooled_in_epilogue)
@@ -355,7 +358,7 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
     const gnnb_model_desc &d = model->desc;
     bool mean_ready = false;
     LayerCtx c = {model, ws, stream, row_lo, ws->t.num_nodes - row_lo, row_lo == 0, ws->t, ws->sk.part ? &ws->sk : nullptr, d.fpx_w > 0,
-                  pooled_in_epilogue, &mean_ready};
+                  pooled_in_epilogue, &mean_ready, edge_attr};
     c.tv.tile_lo = tile_lo;
     c.cur = x_dev;
     int which = 0;
@@ -618,7 +621,8 @@ static int forward_stack(const gnnb_model *model, gnnb_workspace *ws, const floa
     }
     if (seg && !forked) { // the general layer-by-layer kernels on the large segment's rows
         const float *lcur = nullptr;
-        if ((rc = run_conv_layers(model, ws, x_dev, ws->large_n, ws->large_n / ws->t.tile_rows, &lcur, stream)))
+        // (no edge attributes: a GINE model never comes here -- gcn_stack_middle_layers)
+        if ((rc = run_conv_layers(model, ws, x_dev, nullptr, ws->large_n, ws->large_n / ws->t.tile_rows, &lcur, stream)))
             return rc;
         GNNB_HIP_TRY(pool_large_segment(model, ws, lcur, (hipStream_t)stream));
     }
@@ -631,7 +635,7 @@ static int forward_stack(const gnnb_model *model, gnnb_workspace *ws, const floa
     return readout_from_pooled(model, ws, hg0, out_dev, stream);
 }
 
-static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, float *out_dev,
+static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const float *edge_attr, float *out_dev,
                                  void *stream)
 {
     if (!model || !ws || !x_dev || !out_dev)
@@ -657,17 +661,17 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
     ws->last_path = GNNB_PATH_LAYERWISE;
     const float *cur = nullptr;
     bool pooled = false;
-    if ((rc = run_conv_layers(model, ws, x_dev, 0, 0, &cur, stream, &pooled)))
+    if ((rc = run_conv_layers(model, ws, x_dev, edge_attr, 0, 0, &cur, stream, &pooled)))
         return rc;
     return readout_layerwise(model, ws, cur, pooled, out_dev, stream);
 }
 
-// gnnb_forward_prepared and gnnb_forward_prepared_edges behind their checks
-static int forward_prepared(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, float *out_dev, void *stream)
+// gnnb_forward_prepared and gnnb_forward_prepared_edges behind their checks; edge_attr: the latter's (nullptr: a model without)
+static int forward_prepared(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const float *edge_attr, float *out_dev, void *stream)
 {
     // every launch below runs in the MODEL's math mode; the reduced modes' kernels flag this workspace
     MathScope math_scope(model ? model->desc.math : -1, ws ? ws->t.err : nullptr, ws ? ws->t.err_host_dev : nullptr);
-    int rc = forward_prepared_body(model, ws, x_dev, out_dev, stream);
+    int rc = forward_prepared_body(model, ws, x_dev, edge_attr, out_dev, stream);
     if (rc != GNNB_OK)
         return rc;
     // output_activation(dim=-1) over every graph's output row (models.py:572-573)
@@ -691,6 +695,18 @@ static int check_edge_forward(const gnnb_model *model, const gnnb_workspace *ws,
     return GNNB_OK;
 }
 
+// The one tail of gnnb_forward_batched, gnnb_forward_batched_edges and the three gnnb_forward_pyg* (gnnb_ingest.hip), each behind its
+// own checks: graph prep -- without the lazy flag report where the entry's ingest has made it -- then the prepared forward.
+int gnnb::forward_batched_tail(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev, const int32_t *coo_dev,
+                               const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev, int num_graphs, int num_nodes, int num_edges,
+                               float *out_dev, void *stream, bool ingest_reported)
+{
+    if (const int rc = graph_prep_impl(ws, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, model->desc.pna_delta, stream,
+                                       nullptr, ingest_reported))
+        return rc;
+    return forward_prepared(model, ws, x_dev, edge_attr_dev, out_dev, stream);
+}
+
 extern "C" {
 
 int gnnb_forward_prepared(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev,
@@ -698,7 +714,7 @@ int gnnb_forward_prepared(const gnnb_model *model, gnnb_workspace *ws, const flo
 {
     if (const int rc = refuse_edge_model(model, ws, "gnnb_forward_prepared", "gnnb_forward_prepared_edges"))
         return rc;
-    return forward_prepared(model, ws, x_dev, out_dev, stream);
+    return forward_prepared(model, ws, x_dev, nullptr, out_dev, stream);
 }
 
 int gnnb_forward_prepared_edges(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev,
@@ -706,10 +722,7 @@ int gnnb_forward_prepared_edges(const gnnb_model *model, gnnb_workspace *ws, con
 {
     if (const int rc = check_edge_forward(model, ws, edge_attr_dev, ws && ws->prepared ? ws->t.num_edges : 0, "gnnb_forward_prepared_edges"))
         return rc;
-    ws->edge_attr = edge_attr_dev;
-    const int rc = forward_prepared(model, ws, x_dev, out_dev, stream);
-    ws->edge_attr = nullptr;
-    return rc;
+    return forward_prepared(model, ws, x_dev, edge_attr_dev, out_dev, stream);
 }
 
 int gnnb_forward_batched_edges(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev,
@@ -718,9 +731,8 @@ int gnnb_forward_batched_edges(const gnnb_model *model, gnnb_workspace *ws, cons
 {
     if (const int rc = check_edge_forward(model, ws, edge_attr_dev, num_edges, "gnnb_forward_batched_edges"))
         return rc;
-    if (const int rc = gnnb_graph_prep(ws, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, model->desc.pna_delta, stream))
-        return rc;
-    return gnnb_forward_prepared_edges(model, ws, x_dev, edge_attr_dev, out_dev, stream);
+    return forward_batched_tail(model, ws, x_dev, edge_attr_dev, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, out_dev, stream,
+                                false);
 }
 
 int gnnb_forward_batched(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev,
@@ -732,11 +744,7 @@ int gnnb_forward_batched(const gnnb_model *model, gnnb_workspace *ws, const floa
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_batched");
     if (const int erc = refuse_edge_model(model, ws, "gnnb_forward_batched", "gnnb_forward_batched_edges"))
         return erc;
-    int rc = gnnb_graph_prep(ws, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes,
-                             num_edges, model->desc.pna_delta, stream);
-    if (rc != GNNB_OK)
-        return rc;
-    return gnnb_forward_prepared(model, ws, x_dev, out_dev, stream);
+    return forward_batched_tail(model, ws, x_dev, nullptr, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, out_dev, stream, false);
 }
 
 // gnnb_forward_prepared(model, ws, ...) followed by gnnb_graph_prep(ws_next, ...) on the same stream -- with the prep of ws_next
@@ -764,7 +772,7 @@ int gnnb_forward_prepared_prep_next(const gnnb_model *model, gnnb_workspace *ws,
         return gnnb_graph_prep(ws_next, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, model->desc.pna_delta, stream);
     }
     PrepParams pp;
-    int rc = graph_prep_impl(ws_next, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, model->desc.pna_delta, stream, &pp);
+    int rc = graph_prep_impl(ws_next, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, model->desc.pna_delta, stream, &pp, false);
     if (rc != GNNB_OK)
         return rc; // (nothing was enqueued)
     ws_next->prepared = false; // (until its prep is enqueued)
@@ -794,10 +802,8 @@ int gnnb_forward_batched_host(const gnnb_model *model, gnnb_workspace *ws, const
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_batched_host");
     if (const int erc = refuse_edge_model(model, ws, "gnnb_forward_batched_host", "gnnb_forward_batched_edges on device buffers"))
         return erc;
-    if (num_graphs > ws->max_graphs || num_nodes > ws->max_nodes || num_edges > ws->max_edges)
-        return fail(GNNB_ERR_CAPACITY,
-                    "batch (%d graphs, %d nodes, %d edges) exceeds workspace (%d, %d, %d)",
-                    num_graphs, num_nodes, num_edges, ws->max_graphs, ws->max_nodes, ws->max_edges);
+    if (const int crc = check_batch_sizes(ws, num_graphs, num_nodes, num_edges))
+        return crc;
     const gnnb_model_desc &d = model->desc;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // staging buffers live in the workspace, sized once for its capacities: the reference's <name>_top is called once

@@ -1,7 +1,7 @@
 // gnnb_host.h -- what the host translation units of libgnnb_hip.so share (gnnb_model.hip: description and weight upload;
-// gnnb_runtime.hip: workspace, graph prep, stage entry points, C-ABI utilities; gnnb_forward.hip: the forward): the two handle
-// structs, the error helpers, the dimension helpers of a model description and what the forward takes from the runtime unit.
-// Host only: no kernel unit includes it.
+// gnnb_runtime.hip: workspace, graph prep, stage entry points, C-ABI utilities; gnnb_ingest.hip: the PyG mini-batch entries;
+// gnnb_forward.hip: the forward): the two handle structs, the error helpers, the dimension helpers of a model description and
+// what the units take from each other.  Host only: no kernel unit includes it.
 #pragma once
 
 #include <vector>
@@ -95,12 +95,9 @@ struct gnnb_workspace {
     float *mlp[2] = {nullptr, nullptr}; // [max_graphs, max(mlp_hidden, mlp_out)]
     bool prepared = false;
     char *ingest_blob = nullptr; // gnnb_workspace_enable_ingest: the outputs and the sort scratch of gnnb_ingest_pyg (ingest_layout), one allocation
-    bool flags_reported = false; // gnnb_forward_pyg: its ingest has made the lazy flag report of this call; the graph prep behind it skips its
-                                 // own, which could already see what THIS batch's ingest kernels flagged
     bool ingested = false;       // an ingest has been enqueued: gnnb_workspace_check has something to report on
     int edge_dim = 0;            // of the model the workspace was created for (0: no edge weights)
     char *edge_blob = nullptr;   // gnnb_workspace_enable_edge_ingest: edge_attr in COO row order, [max_edges, edge_dim], one allocation
-    const float *edge_attr = nullptr; // the _edges forward in progress: its [E, edge_dim] edge attributes (nullptr outside one)
     char *order_blob = nullptr;  // gnnb_workspace_enable_ordered_ingest: the ordered batch and the staged outputs (order_layout), one allocation
     int32_t *order_triple = nullptr, *order_triple_dev = nullptr; // host-mapped (first large graph, node row, edge row) of k_order_graphs, and
                                                                   // its device-visible address
@@ -142,10 +139,24 @@ int build_gemm(GemmArgs &g, const gnnb_gemm_seg *segs, int num_segs, const float
 int linear_segs(const StreamK *sk_owned, const gnnb_gemm_seg *segs, int num_segs, const float *w_dev, int ldw, const float *bias_dev,
                 const float *skip_dev, float *y_dev, int M, int N, int act, void *stream);
 bool guest_prep_eligible(const gnnb_workspace *ws, int num_nodes);
+// ingest_reported: this call's ingest has made the lazy flag report already; graph prep skips its own, which could already see
+// what THIS batch's ingest kernels flagged -- that is for the next call (or gnnb_workspace_check) to report
 int graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev,
-                    int num_graphs, int num_nodes, int num_edges, float pna_delta, void *stream, PrepParams *defer);
+                    int num_graphs, int num_nodes, int num_edges, float pna_delta, void *stream, PrepParams *defer, bool ingest_reported);
+// ... and for the PyG entries (gnnb_ingest.hip) as well
+int report_earlier_flags(gnnb_workspace *ws, void *stream);
+int check_batch_sizes(const gnnb_workspace *ws, int num_graphs, int num_nodes, int num_edges);
 // gnnb_forward.hip, for graph prep
 BatchTables small_segment(const gnnb_workspace *ws);
+// gnnb_forward.hip: the tail of every gnnb_forward_batched* / gnnb_forward_pyg* entry behind its own checks -- graph prep, then
+// the prepared forward; edge_attr_dev: a GINE model's [E, edge_dim] attributes in COO row order (nullptr: a model without)
+int forward_batched_tail(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev, const int32_t *coo_dev,
+                         const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev, int num_graphs, int num_nodes, int num_edges,
+                         float *out_dev, void *stream, bool ingest_reported);
+
+// the add-on allocations' layouts at a workspace's capacities
+inline IngestLayout ingest_layout(const gnnb_workspace *ws) { return ingest_layout(ws->max_graphs, ws->max_nodes, ws->max_edges); }
+inline OrderLayout order_layout(const gnnb_workspace *ws) { return order_layout(ws->max_graphs, ws->max_nodes, ws->max_edges, ws->desc.in_dim, ws->desc.mlp_out); }
 
 // The event-timed loop behind the *_timed entries: `warmup` launches, then `iters` launches between two events on `s`;
 // launch(i) -> GNNB_OK or an error (which ends the loop and is returned).  *out_us = microseconds per launch.

@@ -283,7 +283,7 @@ hipError_t launch_aggregate_edges(const BatchTables &t, const float *x, const fl
 // [E, edge_dim] in COO order (edge_dim 1 .. 16), we [width, ldwe >= edge_dim], be [width].  hipErrorInvalidValue: nothing launched
 hipError_t launch_gine_aggregate(const BatchTables &t, const float *x, const float *edge_attr, int edge_dim, const float *we, int ldwe,
                                  const float *be, float *out, int width, float eps, hipStream_t s);
-// the ingest's edge attributes in COO row order (k_gine.hip): out[i] = edge_attr[state[INGEST_STATE_UNSORTED] ? idx[i] : i]; idx:
+// the ingest's edge attributes in COO row order (k_ingest.hip): out[i] = edge_attr[state[INGEST_STATE_UNSORTED] ? idx[i] : i]; idx:
 // the general path's sorted-position -> input-edge array (nullptr: that path was not launched), state: IngestParams::state
 hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,
                                   hipStream_t s);

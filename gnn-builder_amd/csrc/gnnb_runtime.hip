@@ -1,6 +1,7 @@
 // gnnb_runtime.hip -- host side of libgnnb_hip.so: errors and options, the workspace handle, graph prep and its plan, the
-// stage entry points of the C ABI declared in include/gnnb_hip.h (gnnb_aggregate, gnnb_linear, gnnb_global_pool ...), the
-// timed loops and the utilities.  The forward -- which kernels run, in which order -- is gnnb_forward.hip.
+// stage entry points of the C ABI declared in include/gnnb_hip.h and gnnb_edge.h (gnnb_aggregate, gnnb_linear, gnnb_global_pool
+// ...), the timed loops and the utilities.  The forward -- which kernels run, in which order -- is gnnb_forward.hip; the PyG
+// mini-batch entries (ingest, ordered ingest, edge attributes) and the workspace's add-on allocations are gnnb_ingest.hip.
 //
 // graph prep follows the reference's generated top (gnnbuilder/templates/model.cpp.jinja):
 //   compute_degree/neighbor_tables (:737-758)  -> k_graph_prep, once per batch, shared by all layers
@@ -316,7 +317,8 @@ int gnnb_workspace_set_max_degree(gnnb_workspace *ws, int d)
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------
-// (C++ linkage from here to gnnb_graph_prep: the gnnb:: functions below are what gnnb_forward.hip takes from this unit, gnnb_host.h)
+// (C++ linkage from here to gnnb_graph_prep: the gnnb:: functions below are what gnnb_forward.hip and gnnb_ingest.hip take from this
+// unit, gnnb_host.h)
 // The prep plan: what graph prep has to know about a workspace, each question answered in ONE place.  All of it is a handful
 // of integer tests on the workspace and the options: nothing here allocates or looks anything up.
 
@@ -382,12 +384,8 @@ bool gnnb::guest_prep_eligible(const gnnb_workspace *ws, int num_nodes)
 // Lazy detection: a batch prepared (or ingested) EARLIER on this workspace was flagged on the device (edge leaving its graph,
 // broken ptr arrays, broken max_graph_nodes promise, malformed PyG mini-batch) and nobody called gnnb_workspace_check since.  Read
 // from a host-mapped word without synchronising: it reports what has already run, never the batch being enqueued now.
-static int report_earlier_flags(gnnb_workspace *ws, void *stream)
+int gnnb::report_earlier_flags(gnnb_workspace *ws, void *stream)
 {
-    if (ws->flags_reported) { // (the same call has looked already: gnnb_forward_pyg)
-        ws->flags_reported = false;
-        return GNNB_OK;
-    }
     if (!ws->err_host || *(volatile int32_t *)ws->err_host == 0)
         return GNNB_OK;
     const int32_t seen = *(volatile int32_t *)ws->err_host;
@@ -402,21 +400,29 @@ static int report_earlier_flags(gnnb_workspace *ws, void *stream)
                                 "unspecified); gnnb_workspace_check reports and clears the flags");
 }
 
+// a batch of these sizes against the workspace's capacities
+int gnnb::check_batch_sizes(const gnnb_workspace *ws, int num_graphs, int num_nodes, int num_edges)
+{
+    if (num_graphs < 0 || num_nodes < 0 || num_edges < 0)
+        return fail(GNNB_ERR_INVALID, "negative batch size");
+    if (num_graphs > ws->max_graphs || num_nodes > ws->max_nodes || num_edges > ws->max_edges)
+        return fail(GNNB_ERR_CAPACITY, "batch (%d graphs, %d nodes, %d edges) exceeds workspace (%d, %d, %d)", num_graphs, num_nodes,
+                    num_edges, ws->max_graphs, ws->max_nodes, ws->max_edges);
+    return GNNB_OK;
+}
+
 // defer != nullptr (and guest_prep_eligible): everything gnnb_graph_prep does EXCEPT the launch -- *defer receives the kernel's arguments
 int gnnb::graph_prep_impl(gnnb_workspace *ws, const int32_t *coo_dev, const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev,
-                          int num_graphs, int num_nodes, int num_edges, float pna_delta, void *stream, PrepParams *defer)
+                          int num_graphs, int num_nodes, int num_edges, float pna_delta, void *stream, PrepParams *defer, bool ingest_reported)
 {
     if (!ws || !node_ptr_dev || !edge_ptr_dev || (num_edges > 0 && !coo_dev))
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_graph_prep");
     MathScope math_scope(ws->desc.math); // (the tile granularity depends on which stack kernel the mode selects)
-    if (num_graphs < 0 || num_nodes < 0 || num_edges < 0)
-        return fail(GNNB_ERR_INVALID, "negative batch size");
-    if (num_graphs > ws->max_graphs || num_nodes > ws->max_nodes || num_edges > ws->max_edges)
-        return fail(GNNB_ERR_CAPACITY,
-                    "batch (%d graphs, %d nodes, %d edges) exceeds workspace (%d, %d, %d)",
-                    num_graphs, num_nodes, num_edges, ws->max_graphs, ws->max_nodes, ws->max_edges);
-    if (const int rc = report_earlier_flags(ws, stream))
+    if (const int rc = check_batch_sizes(ws, num_graphs, num_nodes, num_edges))
         return rc;
+    if (!ingest_reported) // (else: the same call has looked already, in front of its ingest -- gnnb_host.h)
+        if (const int rc = report_earlier_flags(ws, stream))
+            return rc;
     if (ws->large_g >= 0 && (ws->large_g > num_graphs || ws->large_n > num_nodes || ws->large_e > num_edges))
         return fail(GNNB_ERR_INVALID, "large segment (graph %d, node %d, edge %d) lies outside the batch (%d, %d, %d)",
                     ws->large_g, ws->large_n, ws->large_e, num_graphs, num_nodes, num_edges);
@@ -574,7 +580,7 @@ int gnnb_graph_prep(gnnb_workspace *ws, const int32_t *coo_dev, const int32_t *n
                     const int32_t *edge_ptr_dev, int num_graphs, int num_nodes, int num_edges,
                     float pna_delta, void *stream)
 {
-    return graph_prep_impl(ws, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, pna_delta, stream, nullptr);
+    return graph_prep_impl(ws, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, pna_delta, stream, nullptr, false);
 }
 
 int gnnb_workspace_check(gnnb_workspace *ws, void *stream)
@@ -600,304 +606,6 @@ int gnnb_workspace_check(gnnb_workspace *ws, void *stream)
         return fail(GNNB_ERR_RANGE, "a reduced-precision math mode (bf16x3 / f16x3) produced a non-finite value since the last check: an "
                                     "activation or a weight beyond fp16's range (65504), or non-finite inputs; the results of that forward "
                                     "are unspecified -- run the model with math = 0 (flag 0x40)");
-    return GNNB_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// PyG mini-batches (k_ingest.hip)
-size_t gnnb_ingest_bytes(int max_graphs, int max_nodes, int max_edges)
-{
-    if (max_graphs < 0 || max_nodes < 0 || max_edges < 0)
-        return 0;
-    return ingest_layout(max_graphs, max_nodes, max_edges).bytes;
-}
-
-int gnnb_workspace_enable_ingest(gnnb_workspace *ws)
-{
-    if (!ws)
-        return fail(GNNB_ERR_INVALID, "null workspace");
-    if (ws->ingest_blob)
-        return GNNB_OK; // (enabled already: the allocation is made once)
-    if (ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_workspace_enable_ingest: the workspace is in use (a batch has been prepared on it); "
-                                      "enable ingest right after gnnb_workspace_create");
-    const IngestLayout l = ingest_layout(ws->max_graphs, ws->max_nodes, ws->max_edges);
-    char *blob = nullptr;
-    hipError_t e = hipMalloc((void **)&blob, l.bytes);
-    if (e != hipSuccess)
-        return fail(GNNB_ERR_HIP, "ingest allocation of %zu bytes failed: %s", l.bytes, hipGetErrorString(e));
-    e = hipMemset(blob + l.state, 0, INGEST_STATE_WORDS * 4); // (synchronous, as the stream-K scratch's: joins no other stream)
-    if (e != hipSuccess) {
-        (void)hipFree(blob);
-        return fail(GNNB_ERR_HIP, "ingest state initialisation failed: %s", hipGetErrorString(e));
-    }
-    ws->ingest_blob = blob;
-    return GNNB_OK;
-}
-
-int gnnb_ingest_pyg(gnnb_workspace *ws, const int64_t *edge_index_dev, const int64_t *batch_dev, const int64_t *ptr_dev,
-                    int num_graphs, int num_nodes, int num_edges, const int32_t **coo_dev, const int32_t **node_ptr_dev,
-                    const int32_t **edge_ptr_dev, void *stream)
-{
-    if (!ws || !coo_dev || !node_ptr_dev || !edge_ptr_dev || (num_edges > 0 && !edge_index_dev))
-        return fail(GNNB_ERR_INVALID, "null argument to gnnb_ingest_pyg");
-    if (!ws->ingest_blob)
-        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg: call gnnb_workspace_enable_ingest on the workspace first");
-    if (num_graphs < 0 || num_nodes < 0 || num_edges < 0)
-        return fail(GNNB_ERR_INVALID, "negative batch size");
-    if (num_graphs > ws->max_graphs || num_nodes > ws->max_nodes || num_edges > ws->max_edges)
-        return fail(GNNB_ERR_CAPACITY, "batch (%d graphs, %d nodes, %d edges) exceeds workspace (%d, %d, %d)", num_graphs, num_nodes,
-                    num_edges, ws->max_graphs, ws->max_nodes, ws->max_edges);
-    if (batch_dev && ptr_dev)
-        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg takes batch or ptr, not both");
-    if (num_nodes == 0)
-        batch_dev = nullptr; // (no node: every node_ptr entry is 0; an empty `batch` may come without an address -- torch gives none)
-    else if (!batch_dev && !ptr_dev && num_graphs > 1)
-        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg needs batch or ptr for a batch of %d graphs", num_graphs);
-    if ((num_graphs == 0 && (num_nodes > 0 || num_edges > 0)) || (num_nodes == 0 && num_edges > 0))
-        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg: %d nodes and %d edges in %d graphs", num_nodes, num_edges, num_graphs);
-    if (const int rc = report_earlier_flags(ws, stream)) // (before anything is enqueued, as gnnb_graph_prep does)
-        return rc;
-    const IngestLayout l = ingest_layout(ws->max_graphs, ws->max_nodes, ws->max_edges);
-    char *b = ws->ingest_blob;
-    IngestParams p;
-    memset(&p, 0, sizeof(p));
-    p.src = (const long long *)edge_index_dev;
-    p.dst = p.src + num_edges;
-    p.batch = (const long long *)batch_dev;
-    p.ptr = (const long long *)ptr_dev;
-    p.B = num_graphs, p.N = num_nodes, p.E = num_edges;
-    p.node_ptr = (int32_t *)(b + l.node_ptr), p.edge_ptr = (int32_t *)(b + l.edge_ptr), p.coo = (int2 *)(b + l.coo);
-    for (int h = 0; h < 2; h++)
-        p.keys[h] = (int32_t *)(b + l.keys[h]), p.idx[h] = (int32_t *)(b + l.idx[h]);
-    p.hist = (int32_t *)(b + l.hist), p.state = (int32_t *)(b + l.state);
-    p.err = ws->t.err, p.err_host = ws->t.err_host_dev;
-    GNNB_HIP_TRY(launch_ingest(p, (hipStream_t)stream));
-    ws->ingested = true;
-    *coo_dev = (const int32_t *)p.coo;
-    *node_ptr_dev = p.node_ptr;
-    *edge_ptr_dev = p.edge_ptr;
-    return GNNB_OK;
-}
-
-int gnnb_forward_pyg(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev,
-                     const int64_t *batch_dev, const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges, float *out_dev,
-                     void *stream)
-{
-    if (!model || !ws)
-        return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg");
-    if (const int rc = refuse_edge_model(model, ws, "gnnb_forward_pyg", "gnnb_forward_pyg_edges"))
-        return rc;
-    const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
-    const int rc = gnnb_ingest_pyg(ws, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &coo, &node_ptr, &edge_ptr, stream);
-    if (rc != GNNB_OK)
-        return rc;
-    // the ingest has reported what EARLIER batches left; its own kernels may have flagged this batch by now, which is for the
-    // next call (or gnnb_workspace_check) to report, not for the prep of this one
-    ws->flags_reported = true;
-    const int frc = gnnb_forward_batched(model, ws, x_dev, coo, node_ptr, edge_ptr, num_graphs, num_nodes, num_edges, out_dev, stream);
-    ws->flags_reported = false;
-    return frc;
-}
-
-// ---------------------------------------------------------------------------------------
-// PyG mini-batches with the oversized graphs ordered last (k_order.hip)
-size_t gnnb_order_bytes(int max_graphs, int max_nodes, int max_edges, int in_dim, int mlp_out)
-{
-    if (max_graphs < 0 || max_nodes < 0 || max_edges < 0 || in_dim < 0 || mlp_out < 0)
-        return 0;
-    return order_layout(max_graphs, max_nodes, max_edges, in_dim, mlp_out).bytes;
-}
-
-int gnnb_workspace_enable_ordered_ingest(gnnb_workspace *ws)
-{
-    if (!ws)
-        return fail(GNNB_ERR_INVALID, "null workspace");
-    if (ws->order_blob)
-        return GNNB_OK; // (enabled already: the allocation is made once)
-    if (ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_workspace_enable_ordered_ingest: the workspace is in use (a batch has been prepared on it); "
-                                      "enable the ordered ingest right after gnnb_workspace_create");
-    if (const int rc = gnnb_workspace_enable_ingest(ws))
-        return rc;
-    const OrderLayout l = order_layout(ws->max_graphs, ws->max_nodes, ws->max_edges, ws->desc.in_dim, ws->desc.mlp_out);
-    char *blob = nullptr;
-    hipError_t e = hipMalloc((void **)&blob, l.bytes);
-    if (e != hipSuccess)
-        return fail(GNNB_ERR_HIP, "ordered-ingest allocation of %zu bytes failed: %s", l.bytes, hipGetErrorString(e));
-    // the triple comes back through host-mapped memory (as the flag word does): required here, the launches behind it are sized by it
-    int32_t *triple = nullptr;
-    void *dp = nullptr;
-    e = hipHostMalloc((void **)&triple, 64, hipHostMallocMapped);
-    if (e == hipSuccess)
-        e = hipHostGetDevicePointer(&dp, triple, 0);
-    if (e != hipSuccess || !dp) {
-        if (triple)
-            (void)hipHostFree(triple);
-        (void)hipFree(blob);
-        (void)hipGetLastError();
-        return fail(GNNB_ERR_HIP, "host-mapped block of the ordered ingest failed: %s", hipGetErrorString(e));
-    }
-    triple[0] = triple[1] = triple[2] = 0;
-    ws->order_blob = blob;
-    ws->order_triple = triple;
-    ws->order_triple_dev = (int32_t *)dp;
-    return GNNB_OK;
-}
-
-int gnnb_ingest_pyg_ordered(gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev, const int64_t *batch_dev,
-                            const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges, const float **x_ord_dev,
-                            const int32_t **coo_dev, const int32_t **node_ptr_dev, const int32_t **edge_ptr_dev, const int32_t **perm_dev,
-                            int *first_graph, int *first_node, int *first_edge, void *stream)
-{
-    if (!ws || !x_ord_dev || !coo_dev || !node_ptr_dev || !edge_ptr_dev || !perm_dev || !first_graph || !first_node || !first_edge ||
-        (num_nodes > 0 && !x_dev))
-        return fail(GNNB_ERR_INVALID, "null argument to gnnb_ingest_pyg_ordered");
-    if (!ws->order_blob)
-        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg_ordered: call gnnb_workspace_enable_ordered_ingest on the workspace first");
-    // the triple is read on the host behind a wait: not under capture (nothing has been enqueued yet)
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
-        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg_ordered waits for its kernels and cannot be captured into a graph");
-    }
-    const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
-    if (const int rc = gnnb_ingest_pyg(ws, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &coo, &node_ptr, &edge_ptr, stream))
-        return rc;
-    const OrderLayout l = order_layout(ws->max_graphs, ws->max_nodes, ws->max_edges, ws->desc.in_dim, ws->desc.mlp_out);
-    char *b = ws->order_blob;
-    OrderParams p;
-    memset(&p, 0, sizeof(p));
-    p.node_ptr = node_ptr, p.edge_ptr = edge_ptr, p.coo = (const int2 *)coo;
-    p.x = x_dev;
-    p.batch = num_nodes > 0 ? (const long long *)batch_dev : nullptr;
-    p.B = num_graphs, p.N = num_nodes, p.E = num_edges, p.in_dim = ws->desc.in_dim;
-    p.limit = ws->max_graph_nodes; // the promise as it stands at this call
-    p.perm = (int32_t *)(b + l.perm), p.node_ptr_ord = (int32_t *)(b + l.node_ptr), p.edge_ptr_ord = (int32_t *)(b + l.edge_ptr);
-    p.node_shift = (int32_t *)(b + l.node_shift), p.edge_shift = (int32_t *)(b + l.edge_shift);
-    p.x_ord = (float *)(b + l.x_ord), p.coo_ord = (int2 *)(b + l.coo_ord);
-    p.triple = ws->order_triple_dev;
-    GNNB_HIP_TRY(launch_order(p, (hipStream_t)stream));
-    GNNB_HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); // the one synchronisation of the path
-    *first_graph = ((volatile int32_t *)ws->order_triple)[0];
-    *first_node = ((volatile int32_t *)ws->order_triple)[1];
-    *first_edge = ((volatile int32_t *)ws->order_triple)[2];
-    *x_ord_dev = p.x_ord;
-    *coo_dev = (const int32_t *)p.coo_ord;
-    *node_ptr_dev = p.node_ptr_ord;
-    *edge_ptr_dev = p.edge_ptr_ord;
-    *perm_dev = p.perm;
-    return GNNB_OK;
-}
-
-int gnnb_forward_pyg_ordered(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev,
-                             const int64_t *batch_dev, const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges,
-                             float *out_dev, void *stream)
-{
-    if (!model || !ws || (num_graphs > 0 && !out_dev))
-        return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg_ordered");
-    if (const int rc = refuse_edge_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg_edges"))
-        return rc;
-    const float *x_ord = nullptr;
-    const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr, *perm = nullptr;
-    int g0 = 0, n0 = 0, e0 = 0;
-    if (const int rc = gnnb_ingest_pyg_ordered(ws, x_dev, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &x_ord, &coo,
-                                               &node_ptr, &edge_ptr, &perm, &g0, &n0, &e0, stream))
-        return rc;
-    // nothing large: no segment, the batch runs exactly as gnnb_forward_pyg would run it
-    if (const int rc = g0 == num_graphs ? gnnb_workspace_set_large_segment(ws, -1, -1, -1) : gnnb_workspace_set_large_segment(ws, g0, n0, e0))
-        return rc;
-    float *out_ord = (float *)(ws->order_blob + order_layout(ws->max_graphs, ws->max_nodes, ws->max_edges, ws->desc.in_dim, ws->desc.mlp_out).out_ord);
-    ws->flags_reported = true; // (the ingest has made this call's lazy report, as in gnnb_forward_pyg)
-    const int frc = gnnb_forward_batched(model, ws, x_ord, coo, node_ptr, edge_ptr, num_graphs, num_nodes, num_edges, out_ord, stream);
-    ws->flags_reported = false;
-    if (frc != GNNB_OK)
-        return frc;
-    GNNB_HIP_TRY(launch_order_out(out_ord, perm, out_dev, num_graphs, ws->desc.mlp_out, (hipStream_t)stream));
-    return GNNB_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// GINE models: PyG mini-batches with edge attributes (gnnb_edge.h; k_gine.hip)
-size_t gnnb_edge_ingest_bytes(int max_edges, int edge_dim)
-{
-    if (max_edges < 0 || edge_dim < 1 || edge_dim > 16)
-        return 0;
-    return ((size_t)std::max(max_edges, 1) * (size_t)edge_dim * sizeof(float) + 255) & ~(size_t)255;
-}
-
-int gnnb_workspace_enable_edge_ingest(gnnb_workspace *ws)
-{
-    if (!ws)
-        return fail(GNNB_ERR_INVALID, "null workspace");
-    if (ws->edge_blob)
-        return GNNB_OK; // (enabled already: the allocation is made once)
-    if (!ws->edge_dim)
-        return fail(GNNB_ERR_INVALID, "gnnb_workspace_enable_edge_ingest: the workspace belongs to a model without edge weights "
-                                      "(gnnb_edge_model_create makes one with)");
-    if (ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_workspace_enable_edge_ingest: the workspace is in use (a batch has been prepared on it); "
-                                      "enable the edge ingest right after gnnb_workspace_create");
-    if (const int rc = gnnb_workspace_enable_ingest(ws))
-        return rc;
-    const size_t bytes = gnnb_edge_ingest_bytes(ws->max_edges, ws->edge_dim);
-    char *blob = nullptr;
-    const hipError_t e = hipMalloc((void **)&blob, bytes);
-    if (e != hipSuccess)
-        return fail(GNNB_ERR_HIP, "edge-ingest allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-    ws->edge_blob = blob;
-    return GNNB_OK;
-}
-
-int gnnb_ingest_pyg_edges(gnnb_workspace *ws, const int64_t *edge_index_dev, const float *edge_attr_dev, const int64_t *batch_dev,
-                          const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges, const int32_t **coo_dev,
-                          const int32_t **node_ptr_dev, const int32_t **edge_ptr_dev, const float **edge_attr_ord_dev, void *stream)
-{
-    if (!ws || !edge_attr_ord_dev || (num_edges > 0 && !edge_attr_dev))
-        return fail(GNNB_ERR_INVALID, "null argument to gnnb_ingest_pyg_edges");
-    if (!ws->edge_blob)
-        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg_edges: call gnnb_workspace_enable_edge_ingest on the workspace first");
-    if (const int rc = gnnb_ingest_pyg(ws, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, coo_dev, node_ptr_dev, edge_ptr_dev, stream))
-        return rc;
-    // the rows follow their edges: the general path's last pass left sorted position -> input edge in one half of idx (which half:
-    // launch_ingest's pass count); whether that path ran at all is the state word, read by the kernel
-    const IngestLayout l = ingest_layout(ws->max_graphs, ws->max_nodes, ws->max_edges);
-    const int passes = ingest_sort_passes(num_graphs);
-    const int32_t *idx = (passes == 0 || num_edges < 2) ? nullptr : (const int32_t *)(ws->ingest_blob + l.idx[passes & 1]);
-    GNNB_HIP_TRY(launch_edge_attr_order(edge_attr_dev, idx, (const int32_t *)(ws->ingest_blob + l.state), (float *)ws->edge_blob, num_edges,
-                                        ws->edge_dim, (hipStream_t)stream));
-    *edge_attr_ord_dev = (const float *)ws->edge_blob;
-    return GNNB_OK;
-}
-
-int gnnb_forward_pyg_edges(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev,
-                           const float *edge_attr_dev, const int64_t *batch_dev, const int64_t *ptr_dev, int num_graphs, int num_nodes,
-                           int num_edges, float *out_dev, void *stream)
-{
-    if (!model || !ws)
-        return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg_edges");
-    if (!model->edge_dim || model->edge_dim != ws->edge_dim)
-        return fail(GNNB_ERR_INVALID, "gnnb_forward_pyg_edges takes a model of gnnb_edge_model_create and its workspace");
-    const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
-    const float *edge_attr = nullptr;
-    if (const int rc = gnnb_ingest_pyg_edges(ws, edge_index_dev, edge_attr_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &coo, &node_ptr,
-                                             &edge_ptr, &edge_attr, stream))
-        return rc;
-    ws->flags_reported = true; // (the ingest has made this call's lazy report, as in gnnb_forward_pyg)
-    const int frc = gnnb_forward_batched_edges(model, ws, x_dev, edge_attr, coo, node_ptr, edge_ptr, num_graphs, num_nodes, num_edges, out_dev, stream);
-    ws->flags_reported = false;
-    return frc;
-}
-
-int gnnb_aggregate_edges_fused(gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev, int edge_dim, const float *we_dev, int ldwe,
-                               const float *be_dev, float *out_dev, int width, float eps, void *stream)
-{
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_edges_fused needs a prepared batch (gnnb_graph_prep)");
-    if (!x_dev || !out_dev || !we_dev || !be_dev || width < 1 || edge_dim < 1 || edge_dim > 16 || ldwe < edge_dim ||
-        (ws->t.num_edges > 0 && !edge_attr_dev))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_edges_fused (edge_dim 1 .. 16, ldwe >= edge_dim)");
-    GNNB_HIP_TRY(launch_gine_aggregate(ws->t, x_dev, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, out_dev, width, eps, (hipStream_t)stream));
     return GNNB_OK;
 }
 
@@ -964,6 +672,18 @@ int gnnb_aggregate_edges(gnnb_workspace *ws, const float *x_dev, const float *ed
     if (!x_dev || !out_dev || width < 1 || (ws->t.num_edges > 0 && !edge_term_dev))
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_edges");
     GNNB_HIP_TRY(launch_aggregate_edges(ws->t, x_dev, edge_term_dev, out_dev, width, eps, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_edges_fused(gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev, int edge_dim, const float *we_dev, int ldwe,
+                               const float *be_dev, float *out_dev, int width, float eps, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_edges_fused needs a prepared batch (gnnb_graph_prep)");
+    if (!x_dev || !out_dev || !we_dev || !be_dev || width < 1 || edge_dim < 1 || edge_dim > 16 || ldwe < edge_dim ||
+        (ws->t.num_edges > 0 && !edge_attr_dev))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_edges_fused (edge_dim 1 .. 16, ldwe >= edge_dim)");
+    GNNB_HIP_TRY(launch_gine_aggregate(ws->t, x_dev, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, out_dev, width, eps, (hipStream_t)stream));
     return GNNB_OK;
 }
 

@@ -1,4 +1,4 @@
-// k_gine.hip -- GINE with the edge projection inside the aggregate (gnnb_edge.h), and the edge-attribute pass of the PyG ingest.
+// k_gine.hip -- GINE with the edge projection inside the aggregate (gnnb_edge.h).
 // Part of libgnnb_hip.so (hand-written gfx950 / CDNA4 kernels of the GNNBuilder hot path); wavefront = 64 lanes.
 //
 // k_gine_aggregate (reference gine_conv_agg + the self term of gine_conv, gnn_builder_lib.h:1555-1742):
@@ -28,10 +28,6 @@
 // its pieces round-robin, park the piece sums in LDS and the owner adds them in piece order -- the rule above, so a hub of in-degree
 // 1200 costs its workgroup 19 pieces over 4 .. 256 lane groups instead of 1200 dependent steps of one.  Long rows are taken in a
 // second walk behind the short ones: a workgroup without one pays ONE barrier per column pass.
-//
-// k_edge_attr_order: edge_attr_ord[i] = edge_attr[src(i)], src(i) = i on the ingest's grouped path and idx[i] on its general
-// path (the sorted-position -> input-edge array k_ingest_finish consumes); the path is read from the ingest's state word, as
-// the ingest's own kernels do: no read-back, the same launch for grouped and shuffled input.
 #include "gnnb_device.h"
 
 namespace gnnb {
@@ -324,29 +320,6 @@ hipError_t launch_gine_aggregate(const BatchTables &t, const float *x, const flo
     GNNB_GINE_ED(9) GNNB_GINE_ED(10) GNNB_GINE_ED(11) GNNB_GINE_ED(12) GNNB_GINE_ED(13) GNNB_GINE_ED(14) GNNB_GINE_ED(15) GNNB_GINE_ED(16)
 #undef GNNB_GINE_ED
     }
-    return hipGetLastError();
-}
-
-// ---- the PyG ingest's edge attributes in COO row order ---------------------------------------------------------------------------
-__global__ __launch_bounds__(WG) void k_edge_attr_order(const float *__restrict__ edge_attr, const int32_t *__restrict__ idx,
-                                                        const int32_t *__restrict__ state, float *__restrict__ out, int E, int ED)
-{
-    const long long i = (long long)blockIdx.x * WG + threadIdx.x; // one attribute value per thread
-    if (i >= (long long)E * ED)
-        return;
-    const int row = (int)(i / ED), d = (int)(i - (long long)row * ED);
-    // (idx is a permutation of the input edges by construction; clamped all the same, as k_ingest_finish clamps it)
-    const int src = (idx && state[INGEST_STATE_UNSORTED]) ? min(max(idx[row], 0), E - 1) : row;
-    out[i] = edge_attr[(size_t)src * ED + d];
-}
-
-hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,
-                                  hipStream_t s)
-{
-    if (num_edges <= 0 || edge_dim <= 0)
-        return hipSuccess;
-    const long long n = (long long)num_edges * edge_dim;
-    hipLaunchKernelGGL(k_edge_attr_order, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, s, edge_attr, idx, state, out, num_edges, edge_dim);
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // k_ingest.hip -- a PyG mini-batch on the device: edge_index [2, E] int64 + batch [N] int64 (or ptr [B+1] int64) -> the
-// project's batch layout coo [E, 2] int32 grouped by graph (stable), node_ptr / edge_ptr [B+1] int32 (latency bound)
+// project's batch layout coo [E, 2] int32 grouped by graph (stable), node_ptr / edge_ptr [B+1] int32 (latency bound); and a
+// GINE model's edge attributes carried along (k_edge_attr_order)
 // Part of libgnnb_hip.so (hand-written gfx950 / CDNA4 kernels of the GNNBuilder hot path); wavefront = 64 lanes.
 // What batching.from_pyg_batch does on the host (searchsorted, stable argsort, cumsum) without a device value ever being read
 // back: the launch sequence depends on the host integers B, N, E only, so a captured graph replays on any batch of that shape.
@@ -16,6 +17,10 @@
 // Containment of malformed input (flag GNNB_FLAG_INGEST): endpoints are clamped into [0, N), graph ids into [0, B); the keys
 // that are sorted are the clamped ones, so edge_ptr is monotone by construction; a broken `batch` / `ptr` gives node_ptr =
 // {0, N, ..., N} (every node in graph 0): in range and monotone, the results of a flagged batch are unspecified.
+//
+// k_edge_attr_order: edge_attr_ord[i] = edge_attr[src(i)], src(i) = i on the ingest's grouped path and idx[i] on its general
+// path (the sorted-position -> input-edge array k_ingest_finish consumes); the path is read from the ingest's state word, as
+// the ingest's own kernels do: no read-back, the same launch for grouped and shuffled input.
 #include <algorithm>
 
 #include "gnnb_device.h"
@@ -330,6 +335,29 @@ hipError_t launch_ingest(const IngestParams &p, hipStream_t s)
                            pass == 0 ? (const int32_t *)nullptr : (const int32_t *)p.idx[from], p.keys[from ^ 1], p.idx[from ^ 1], shift, nb);
     }
     hipLaunchKernelGGL(k_ingest_finish, dim3(tiles_incl), dim3(IT), 0, s, p, (const int32_t *)p.keys[from], (const int32_t *)p.idx[from]);
+    return hipGetLastError();
+}
+
+// ---- the PyG ingest's edge attributes in COO row order ---------------------------------------------------------------------------
+__global__ __launch_bounds__(WG) void k_edge_attr_order(const float *__restrict__ edge_attr, const int32_t *__restrict__ idx,
+                                                        const int32_t *__restrict__ state, float *__restrict__ out, int E, int ED)
+{
+    const long long i = (long long)blockIdx.x * WG + threadIdx.x; // one attribute value per thread
+    if (i >= (long long)E * ED)
+        return;
+    const int row = (int)(i / ED), d = (int)(i - (long long)row * ED);
+    // (idx is a permutation of the input edges by construction; clamped all the same, as k_ingest_finish clamps it)
+    const int src = (idx && state[INGEST_STATE_UNSORTED]) ? min(max(idx[row], 0), E - 1) : row;
+    out[i] = edge_attr[(size_t)src * ED + d];
+}
+
+hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,
+                                  hipStream_t s)
+{
+    if (num_edges <= 0 || edge_dim <= 0)
+        return hipSuccess;
+    const long long n = (long long)num_edges * edge_dim;
+    hipLaunchKernelGGL(k_edge_attr_order, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, s, edge_attr, idx, state, out, num_edges, edge_dim);
     return hipGetLastError();
 }
 

@@ -312,6 +312,15 @@ def _require_strided(t, name: str, rows: Optional[int] = None, min_cols: int = 0
                         (f"at least {min_cols} columns" if rows is None else f"{rows} rows"))
 
 
+# the add-ons of a workspace (CompiledModel.enable_*): the refusal of a call made before its enable
+_NOT_ENABLED = {
+    "ingest": "ingest is not enabled on this model's workspace: call enable_ingest() once after construction",
+    "ordered": "the ordered ingest is not enabled on this model's workspace: call enable_ordered_ingest() once after construction",
+    "edges": "the edge ingest is not enabled on this model's workspace: call enable_edge_ingest() once after construction",
+}
+_INGEST_OUTS = {"ingest": 3, "ordered": 5, "edges": 4}  # arrays its ingest returns (CompiledModel._view_specs)
+
+
 class _Borrowed:
     """Device memory of a workspace as ``__cuda_array_interface__``: ``torch.as_tensor`` makes a view of it (no copy) that
     keeps this object -- and through it the owner of the memory -- alive."""
@@ -332,9 +341,8 @@ class CompiledModel:
         self._model, self._ws = C.c_void_p(), C.c_void_p()
         self._B = self._N = self._E = 0  # sizes of the prepared batch (_prepared)
         self._keep = None  # its index tensors, which the device still reads
-        self._ingest, self._ingest_views = False, (None,)
-        self._ordered, self._order_views = False, (None,)
-        self._edge_ingest, self._edge_views = False, (None,)
+        self._addons = set()  # what the enable_* calls have allocated beside the workspace: "ingest", "ordered", "edges"
+        self._views = {}  # add-on -> (device pointers, views of its whole arrays): _borrowed_views
         self.edge_dim = int(spec.get("edge_dim", 0) or 0) if spec.get("conv") == "gine" else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
@@ -413,7 +421,7 @@ class CompiledModel:
         return int(self.lib.gnnb_workspace_bytes(self._ws))
 
     def close(self) -> None:
-        self._ingest_views = self._order_views = self._edge_views = (None,)  # (they borrow the workspace: dropped with it)
+        self._views = {}  # (they borrow the workspace: dropped with it)
         if self._ws:
             self.lib.gnnb_workspace_destroy(self._ws)
             self._ws = C.c_void_p()
@@ -447,16 +455,21 @@ class CompiledModel:
         the results of a flagged batch are unspecified.  Without a ``check()`` the flag still surfaces: the next call
         on this workspace after a flagged batch has run raises ``GnnbError`` ("an earlier batch ...", no synchronisation,
         best effort)."""
-        self._check_batch(x, coo, node_ptr, edge_ptr)
-        B = int(node_ptr.numel()) - 1
-        N, E = int(x.shape[0]), int(coo.shape[0])
+        return self._forward_batched(False, x, None, coo, node_ptr, edge_ptr, out, stream)
+
+    def _forward_batched(self, edges: bool, x, edge_attr, coo, node_ptr, edge_ptr, out, stream):
+        """``forward`` and, with ``edges``, ``forward_edges`` (``gnnb_forward_batched_edges``: ``edge_attr`` behind ``x``)."""
+        B, N, E = self._check_batch(x, coo, node_ptr, edge_ptr)
+        ea = self._require_edge_attr(edge_attr, E, x) if edges else None
         out = _out(out, B, self.out_dim, x)
-        _check(self.lib.gnnb_forward_batched(self._model, self._ws, _dptr(x), _dptr(coo), _dptr(node_ptr),
-                                             _dptr(edge_ptr), B, N, E, _dptr(out), _stream_ptr(stream)))
+        tail = (_dptr(coo), _dptr(node_ptr), _dptr(edge_ptr), B, N, E, _dptr(out), _stream_ptr(stream))
+        _check(self.lib.gnnb_forward_batched_edges(self._model, self._ws, _dptr(x), ea, *tail) if edges else
+               self.lib.gnnb_forward_batched(self._model, self._ws, _dptr(x), *tail))
         self._prepared(B, N, E, (coo, node_ptr, edge_ptr))
         return out
 
-    def _check_batch(self, x, coo, node_ptr, edge_ptr) -> None:
+    def _check_batch(self, x, coo, node_ptr, edge_ptr, num_nodes=None):
+        """Checks of a batch's tensors (raw pointers cross the C ABI); returns (B, N, E) -- N from ``x``, or ``num_nodes`` without one."""
         import torch
         if x is not None:
             _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
@@ -465,10 +478,10 @@ class CompiledModel:
         _require(edge_ptr, "edge_ptr", torch.int32, 1)
         if node_ptr.numel() != edge_ptr.numel() or node_ptr.numel() < 1:
             raise GnnbError("node_ptr and edge_ptr must both have num_graphs + 1 entries")
+        return int(node_ptr.numel()) - 1, int(num_nodes if x is None else x.shape[0]), int(coo.shape[0])
 
     def graph_prep(self, coo, node_ptr, edge_ptr, num_nodes: int, stream=None) -> None:
-        self._check_batch(None, coo, node_ptr, edge_ptr)
-        B, N, E = int(node_ptr.numel()) - 1, int(num_nodes), int(coo.shape[0])
+        B, N, E = self._check_batch(None, coo, node_ptr, edge_ptr, num_nodes)
         _check(self.lib.gnnb_graph_prep(self._ws, _dptr(coo), _dptr(node_ptr), _dptr(edge_ptr), B, N, E,
                                         float(self.desc.pna_delta), _stream_ptr(stream)))
         self._prepared(B, N, E, (coo, node_ptr, edge_ptr))
@@ -486,8 +499,7 @@ class CompiledModel:
         ``nxt.forward_prepared`` / ``nxt.forward_prepared_prep_next`` is then the next batch's forward."""
         self._require_x(x, int(self.desc.in_dim))
         out = _out(out, self._B, self.out_dim, x)
-        self._check_batch(None, coo, node_ptr, edge_ptr)
-        B, N, E = int(node_ptr.numel()) - 1, int(num_nodes), int(coo.shape[0])
+        B, N, E = self._check_batch(None, coo, node_ptr, edge_ptr, num_nodes)
         _check(self.lib.gnnb_forward_prepared_prep_next(self._model, self._ws, _dptr(x), _dptr(out), nxt._ws, _dptr(coo), _dptr(node_ptr),
                                                         _dptr(edge_ptr), B, N, E, _stream_ptr(stream)))
         nxt._prepared(B, N, E, (coo, node_ptr, edge_ptr))
@@ -515,14 +527,40 @@ class CompiledModel:
         """One more device allocation (``ingest_bytes`` of the workspace's capacities) for ``ingest_pyg`` / ``forward_pyg``.
         Synchronous: call it once, right after construction, outside stream capture."""
         _check(self.lib.gnnb_workspace_enable_ingest(self._ws))
-        self._ingest = True
-        self._ingest_views = (None,)
+        self._addons.add("ingest")
+
+    def _view_specs(self, addon: str):
+        """(shape, typestr) of the whole arrays an add-on's ingest returns, in the order of its out-pointers."""
+        G, cap_e = self.max_graphs, max(self.max_edges, 1)
+        coo = [((cap_e, 2), "<i4"), ((G + 1,), "<i4"), ((G + 1,), "<i4")]  # coo, node_ptr, edge_ptr
+        return {"ingest": coo,
+                "ordered": [((self.max_nodes, max(int(self.desc.in_dim), 1)), "<f4")] + coo + [((G,), "<i4")],  # x_ord ..., perm
+                "edges": coo + [((cap_e, self.edge_dim), "<f4")]}[addon]  # ..., edge_attr_ord
+
+    def _ingest(self, addon: str, fn, lead, batch, ptr, sizes, dev, stream, ints: int = 0):
+        """What the three ingests share: ``fn(ws, *lead, batch, ptr, *sizes, <the add-on's out-pointers>, <ints int*>, stream)``;
+        returns views of the whole output arrays and the integers.  The views are made the first time the pointers are seen (the
+        allocation never moves) and every call slices them: no HIP call per ingest after the first, so a warmed-up ingest can be
+        captured into a graph."""
+        out_p = [C.c_void_p() for _ in range(_INGEST_OUTS[addon])]
+        seg = [C.c_int() for _ in range(ints)]
+        _check(fn(self._ws, *lead, _optr(batch), _optr(ptr), *sizes, *[C.byref(p) for p in out_p], *[C.byref(v) for v in seg],
+                  _stream_ptr(stream)))
+        ptrs = tuple(p.value for p in out_p)
+        cached = self._views.get(addon)
+        if cached is None or cached[0] != ptrs:
+            import torch
+            specs = self._view_specs(addon)
+            assert len(specs) == len(ptrs), (addon, "_INGEST_OUTS and _view_specs disagree")
+            cached = self._views[addon] = (ptrs, [torch.as_tensor(_Borrowed(p, shape, self, typestr), device=dev)
+                                                  for p, (shape, typestr) in zip(ptrs, specs)])
+        return cached[1], tuple(int(v.value) for v in seg)
 
     def _pyg_args(self, edge_index, batch, ptr, num_graphs, num_nodes):
         """Checks of a PyG mini-batch's index tensors (raw pointers cross the C ABI); returns (batch or None, ptr or None, B, N, E)."""
         import torch
-        if not self._ingest:
-            raise GnnbError("ingest is not enabled on this model's workspace: call enable_ingest() once after construction")
+        if "ingest" not in self._addons:
+            raise GnnbError(_NOT_ENABLED["ingest"])
         if isinstance(edge_index, torch.Tensor) and edge_index.dim() == 2 and edge_index.shape[0] != 2 and edge_index.shape[1] == 2:
             raise GnnbError(f"edge_index has shape {tuple(edge_index.shape)}: this is the [E, 2] coo layout; pass the PyG layout "
                             "[2, E] (edge_index.t().contiguous()), or give the [E, 2] int32 rows to forward()")
@@ -561,33 +599,33 @@ class CompiledModel:
         int32, computed on the device with no synchronisation -- what ``batching.from_pyg_batch`` computes on the host.  The three
         tensors are VIEWS of this model's workspace: valid until the next ``ingest_pyg`` / ``forward_pyg``.  Malformed input is
         flagged, not refused: ``check()`` raises (flag 0x80), and the arrays of a flagged batch are in range but unspecified."""
-        import torch
         batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, num_nodes)
-        coo_p, np_p, ep_p = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _check(self.lib.gnnb_ingest_pyg(self._ws, _dptr(edge_index), _optr(batch), _optr(ptr), B, N, E,
-                                        C.byref(coo_p), C.byref(np_p), C.byref(ep_p), _stream_ptr(stream)))
-        # views of the whole arrays are made once (the allocation never moves), every call slices them: no HIP call per ingest,
-        # so a warmed-up ingest_pyg can be captured into a graph
-        ptrs = (coo_p.value, np_p.value, ep_p.value)
-        if self._ingest_views[0] != ptrs:
-            dev = edge_index.device
-            view = lambda p, shape: torch.as_tensor(_Borrowed(p, shape, self), device=dev)  # noqa: E731
-            self._ingest_views = (ptrs, view(ptrs[0], (max(self.max_edges, 1), 2)), view(ptrs[1], (self.max_graphs + 1,)),
-                                  view(ptrs[2], (self.max_graphs + 1,)))
-        _, coo, nptr, eptr = self._ingest_views
+        (coo, nptr, eptr), _ = self._ingest("ingest", self.lib.gnnb_ingest_pyg, (_dptr(edge_index),), batch, ptr, (B, N, E), edge_index.device, stream)
         return coo[:E], nptr[:B + 1], eptr[:B + 1]
 
     def forward_pyg(self, x, edge_index, batch=None, ptr=None, num_graphs=None, out=None, stream=None):
         """``forward`` on a PyG mini-batch as the loader holds it on the GPU (``x`` [N, in_dim] fp32, ``edge_index`` [2, E]
         int64, ``batch`` [N] int64 + ``num_graphs``, or ``ptr`` [B+1] int64): ingest and forward on one stream, no host
         synchronisation (``gnnb_forward_pyg``).  The stage-level entry points work afterwards as after ``forward``."""
+        return self._forward_pyg(self.lib.gnnb_forward_pyg, "ingest", x, edge_index, None, batch, ptr, num_graphs, out, stream)
+
+    def _forward_pyg(self, fn, addon: str, x, edge_index, edge_attr, batch, ptr, num_graphs, out, stream):
+        """``forward_pyg`` ("ingest"), ``forward_pyg_ordered`` ("ordered") and ``forward_pyg_edges`` ("edges": ``edge_attr`` behind
+        ``edge_index``) on their C entry ``fn``.  Each refuses in the order it always has: the ordered form names its missing
+        add-on before it looks at ``x``, the edge form behind ``x``, the plain form inside ``_pyg_args``."""
         import torch
+        if addon == "ordered" and addon not in self._addons:
+            raise GnnbError(_NOT_ENABLED[addon])
         _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
+        if addon == "edges" and addon not in self._addons:
+            raise GnnbError(_NOT_ENABLED[addon])
         batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, int(x.shape[0]))
+        ea = self._require_edge_attr(edge_attr, E, x) if addon == "edges" else None
         out = _out(out, B, self.out_dim, x)
-        _check(self.lib.gnnb_forward_pyg(self._model, self._ws, _dptr(x), _dptr(edge_index), _optr(batch), _optr(ptr),
-                                         B, N, E, _dptr(out), _stream_ptr(stream)))
-        self._prepared(B, N, E, None)  # (the batch's index arrays live in the workspace)
+        tail = (_optr(batch), _optr(ptr), B, N, E, _dptr(out), _stream_ptr(stream))
+        _check(fn(self._model, self._ws, _dptr(x), _dptr(edge_index), ea, *tail) if addon == "edges" else
+               fn(self._model, self._ws, _dptr(x), _dptr(edge_index), *tail))
+        self._prepared(B, N, E, None)  # (the batch's index arrays, ordered or not, live in the workspace)
         return out
 
     # ------------------------------------------------------------------ PyG mini-batches, oversized graphs ordered last
@@ -596,17 +634,7 @@ class CompiledModel:
         ``ingest_pyg_ordered`` / ``forward_pyg_ordered``.  Synchronous: call it once, right after construction, outside stream
         capture."""
         _check(self.lib.gnnb_workspace_enable_ordered_ingest(self._ws))
-        if not self._ingest:
-            self._ingest, self._ingest_views = True, (None,)
-        self._ordered, self._order_views = True, (None,)
-
-    def _ordered_args(self, x, edge_index, batch, ptr, num_graphs):
-        import torch
-        if not self._ordered:
-            raise GnnbError("the ordered ingest is not enabled on this model's workspace: call enable_ordered_ingest() once after "
-                            "construction")
-        _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
-        return self._pyg_args(edge_index, batch, ptr, num_graphs, int(x.shape[0]))
+        self._addons |= {"ingest", "ordered"}
 
     def ingest_pyg_ordered(self, x, edge_index, batch=None, ptr=None, num_graphs=None, stream=None):
         """``ingest_pyg`` and, on the device, ``batching.order_large_last`` at this workspace's ``max_graph_nodes`` promise: the
@@ -616,33 +644,20 @@ class CompiledModel:
         the ONE synchronisation of this path (a wait on ``stream``; not capturable).  The tensors are VIEWS of this model's
         workspace: valid until the next ``ingest_pyg_ordered`` / ``forward_pyg_ordered``."""
         import torch
-        batch, ptr, B, N, E = self._ordered_args(x, edge_index, batch, ptr, num_graphs)
-        out_p = [C.c_void_p() for _ in range(5)]
-        seg = [C.c_int() for _ in range(3)]
-        _check(self.lib.gnnb_ingest_pyg_ordered(self._ws, _dptr(x), _dptr(edge_index), _optr(batch), _optr(ptr), B, N, E,
-                                                *[C.byref(p) for p in out_p], *[C.byref(v) for v in seg], _stream_ptr(stream)))
-        ptrs = tuple(p.value for p in out_p)
-        if self._order_views[0] != ptrs:  # (made once, sliced per call: as ingest_pyg's)
-            dev = edge_index.device
-            view = lambda p, shape, typestr="<i4": torch.as_tensor(_Borrowed(p, shape, self, typestr), device=dev)  # noqa: E731
-            G = self.max_graphs
-            self._order_views = (ptrs, view(ptrs[0], (self.max_nodes, max(int(self.desc.in_dim), 1)), "<f4"),
-                                 view(ptrs[1], (max(self.max_edges, 1), 2)), view(ptrs[2], (G + 1,)), view(ptrs[3], (G + 1,)),
-                                 view(ptrs[4], (G,)))
-        _, x_ord, coo, nptr, eptr, perm = self._order_views
-        return x_ord[:N], coo[:E], nptr[:B + 1], eptr[:B + 1], perm[:B], tuple(int(v.value) for v in seg)
+        if "ordered" not in self._addons:
+            raise GnnbError(_NOT_ENABLED["ordered"])
+        _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
+        batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, int(x.shape[0]))
+        (x_ord, coo, nptr, eptr, perm), seg = self._ingest("ordered", self.lib.gnnb_ingest_pyg_ordered, (_dptr(x), _dptr(edge_index)), batch, ptr,
+                                                           (B, N, E), edge_index.device, stream, ints=3)
+        return x_ord[:N], coo[:E], nptr[:B + 1], eptr[:B + 1], perm[:B], seg
 
     def forward_pyg_ordered(self, x, edge_index, batch=None, ptr=None, num_graphs=None, out=None, stream=None):
         """``forward_pyg`` for batches that hold a few graphs beyond the ``max_graph_nodes`` promise: ordered ingest, the large
         segment set to its triple (removed when nothing is large), forward, rows put back (``gnnb_forward_pyg_ordered``).
         Returns ``out`` [B, out_dim] in the CALLER's graph order.  Waits once on ``stream`` (three integers; not capturable).  The
         large-segment setting is left on the workspace; the stage-level entry points work afterwards, on the ORDERED batch."""
-        batch, ptr, B, N, E = self._ordered_args(x, edge_index, batch, ptr, num_graphs)
-        out = _out(out, B, self.out_dim, x)
-        _check(self.lib.gnnb_forward_pyg_ordered(self._model, self._ws, _dptr(x), _dptr(edge_index), _optr(batch), _optr(ptr),
-                                                 B, N, E, _dptr(out), _stream_ptr(stream)))
-        self._prepared(B, N, E, None)  # (the ordered batch's index arrays live in the workspace)
-        return out
+        return self._forward_pyg(self.lib.gnnb_forward_pyg_ordered, "ordered", x, edge_index, None, batch, ptr, num_graphs, out, stream)
 
     # ------------------------------------------------------------------ GINE models: forwards with edge attributes
     def _require_edge_attr(self, edge_attr, E: int, like, width: Optional[int] = None):
@@ -664,15 +679,7 @@ class CompiledModel:
         """``forward`` of a GINE model: ``edge_attr`` [E, edge_dim] fp32, row ``i`` belongs to ``coo`` row ``i``
         (``gnnb_forward_batched_edges``).  Everything else as ``forward``."""
         self._require_edge_model("forward_edges")
-        self._check_batch(x, coo, node_ptr, edge_ptr)
-        B = int(node_ptr.numel()) - 1
-        N, E = int(x.shape[0]), int(coo.shape[0])
-        ea = self._require_edge_attr(edge_attr, E, x)
-        out = _out(out, B, self.out_dim, x)
-        _check(self.lib.gnnb_forward_batched_edges(self._model, self._ws, _dptr(x), ea, _dptr(coo), _dptr(node_ptr), _dptr(edge_ptr),
-                                                   B, N, E, _dptr(out), _stream_ptr(stream)))
-        self._prepared(B, N, E, (coo, node_ptr, edge_ptr))
-        return out
+        return self._forward_batched(True, x, edge_attr, coo, node_ptr, edge_ptr, out, stream)
 
     def forward_prepared_edges(self, x, edge_attr, out=None, stream=None):
         """``forward_prepared`` of a GINE model on the batch ``graph_prep`` left in the workspace."""
@@ -689,50 +696,27 @@ class CompiledModel:
         capture."""
         self._require_edge_model("enable_edge_ingest")
         _check(self.lib.gnnb_workspace_enable_edge_ingest(self._ws))
-        if not self._ingest:
-            self._ingest, self._ingest_views = True, (None,)
-        self._edge_ingest, self._edge_views = True, (None,)
-
-    def _edge_pyg_args(self, edge_index, edge_attr, batch, ptr, num_graphs, num_nodes, like):
-        if not self._edge_ingest:
-            raise GnnbError("the edge ingest is not enabled on this model's workspace: call enable_edge_ingest() once after "
-                            "construction")
-        batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, num_nodes)
-        return batch, ptr, B, N, E, self._require_edge_attr(edge_attr, E, like)
+        self._addons |= {"ingest", "edges"}
 
     def ingest_pyg_edges(self, edge_index, edge_attr, batch=None, ptr=None, num_graphs=None, stream=None, num_nodes=None):
         """``ingest_pyg`` with the mini-batch's ``edge_attr`` [E, edge_dim] fp32 (``Batch.edge_attr``, in ``edge_index``'s column
         order): returns ``(coo, node_ptr, edge_ptr, edge_attr_ord)`` with ``edge_attr_ord[i]`` the attributes of ``coo`` row ``i`` --
         what ``batching.from_pyg_batch(..., edge_attr=...)`` computes on the host, with no synchronisation
         (``gnnb_ingest_pyg_edges``).  VIEWS of the workspace: valid until the next ingest on it."""
-        import torch
-        batch, ptr, B, N, E, ea = self._edge_pyg_args(edge_index, edge_attr, batch, ptr, num_graphs, num_nodes, edge_index)
-        out_p = [C.c_void_p() for _ in range(4)]
-        _check(self.lib.gnnb_ingest_pyg_edges(self._ws, _dptr(edge_index), ea, _optr(batch), _optr(ptr), B, N, E,
-                                              *[C.byref(p) for p in out_p], _stream_ptr(stream)))
-        ptrs = tuple(p.value for p in out_p)
-        if self._edge_views[0] != ptrs:  # (made once, sliced per call: as ingest_pyg's)
-            dev = edge_index.device
-            view = lambda p, shape, typestr="<i4": torch.as_tensor(_Borrowed(p, shape, self, typestr), device=dev)  # noqa: E731
-            G = self.max_graphs
-            self._edge_views = (ptrs, view(ptrs[0], (max(self.max_edges, 1), 2)), view(ptrs[1], (G + 1,)), view(ptrs[2], (G + 1,)),
-                                view(ptrs[3], (max(self.max_edges, 1), self.edge_dim), "<f4"))
-        _, coo, nptr, eptr, ea_ord = self._edge_views
+        if "edges" not in self._addons:
+            raise GnnbError(_NOT_ENABLED["edges"])
+        batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, num_nodes)
+        ea = self._require_edge_attr(edge_attr, E, edge_index)
+        (coo, nptr, eptr, ea_ord), _ = self._ingest("edges", self.lib.gnnb_ingest_pyg_edges, (_dptr(edge_index), ea), batch, ptr, (B, N, E),
+                                                    edge_index.device, stream)
         return coo[:E], nptr[:B + 1], eptr[:B + 1], ea_ord[:E]
 
     def forward_pyg_edges(self, x, edge_index, edge_attr, batch=None, ptr=None, num_graphs=None, out=None, stream=None):
         """``forward_pyg`` of a GINE model: ``edge_attr`` [E, edge_dim] fp32 in ``edge_index``'s column order; ingest (the
         attribute rows follow their edges) and forward on one stream, no host synchronisation, capturable
         (``gnnb_forward_pyg_edges``)."""
-        import torch
         self._require_edge_model("forward_pyg_edges")
-        _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
-        batch, ptr, B, N, E, ea = self._edge_pyg_args(edge_index, edge_attr, batch, ptr, num_graphs, int(x.shape[0]), x)
-        out = _out(out, B, self.out_dim, x)
-        _check(self.lib.gnnb_forward_pyg_edges(self._model, self._ws, _dptr(x), _dptr(edge_index), ea, _optr(batch), _optr(ptr),
-                                               B, N, E, _dptr(out), _stream_ptr(stream)))
-        self._prepared(B, N, E, None)  # (the batch's index arrays live in the workspace)
-        return out
+        return self._forward_pyg(self.lib.gnnb_forward_pyg_edges, "edges", x, edge_index, edge_attr, batch, ptr, num_graphs, out, stream)
 
     # ------------------------------------------------------------------ stage-level entry points
     # (raw pointers cross the C ABI: each checks every operand's dtype, layout, device and rows against the prepared batch, so

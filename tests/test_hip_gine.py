@@ -273,6 +273,26 @@ def test_one_captured_forward_replays_on_grouped_and_on_shuffled_edges(pyg, dev)
     cm.check()
 
 
+def test_flagged_batch_is_reported_by_the_next_forward(dev):
+    """tests/test_hip_ingest.py's test of this name for ``forward_pyg_edges``: what the ingest kernels of a call flag (an
+    endpoint = N, contained by design) is reported by the NEXT call on the workspace -- not by the call's own graph prep --
+    and once."""
+    b = synthetic.make_batch("qm9", 12, seed=9)
+    ei = np.ascontiguousarray(b.coo.T.astype(np.int64)).reshape(2, -1)
+    N = b.num_nodes
+    bad = ei.copy()
+    bad[1, int(b.edge_ptr[4]) + 1] = N
+    m = runtime.CompiledModel.from_model(make_gine_model(in_dim=4, edge_dim=4, hidden=16, layers=2, seed=5), 16, 512, 1024)
+    m.enable_edge_ingest()
+    x, ea, batch_dev = torch.zeros((N, 4), device=dev), _t(edge_attrs(b.num_edges, 4, seed=44), dev), _t(batch_vector(b), dev)
+    m.forward_pyg_edges(x, _t(bad, dev), ea, batch=batch_dev, num_graphs=12)  # flagged on the device; no check()
+    torch.cuda.synchronize()
+    with pytest.raises(runtime.GnnbError, match="earlier batch"):
+        m.forward_pyg_edges(x, _t(ei, dev), ea, batch=batch_dev, num_graphs=12)
+    m.forward_pyg_edges(x, _t(ei, dev), ea, batch=batch_dev, num_graphs=12)  # reported once
+    m.check()
+
+
 # ---------------------------------------------------------------------------------------------------- 6. refusals
 def test_refusals(pyg, dev):
     cm, b = pyg["cm"], pyg["b"]

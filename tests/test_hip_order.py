@@ -319,6 +319,26 @@ def test_flagged_batch_stays_contained(dev):
     _check_arrays(m, dev, b.x, ei, 20, batch=batch, B=B)  # a well-formed batch on the same workspace is not blamed for it
 
 
+def test_flagged_batch_is_reported_by_the_next_forward(dev):
+    """tests/test_hip_ingest.py's test of this name for ``forward_pyg_ordered``: what the ingest kernels of a call flag is
+    reported by the NEXT call on the workspace -- not by the call's own graph prep -- and once."""
+    b = synthetic.make_batch("qm9", 12, seed=9)
+    ei, batch = _pyg(b)
+    N = b.num_nodes
+    bad = ei.copy()
+    bad[1, int(b.edge_ptr[4]) + 1] = N
+    model = make_model("gcn", in_dim=4, hidden=16, layers=2, out_dim=16, task_out=3, mlp_layers=0)
+    m = runtime.CompiledModel.from_model(model, 16, 512, 1024)
+    m.enable_ordered_ingest()
+    x, batch_dev = torch.zeros((N, 4), device=dev), _t(batch, dev)
+    m.forward_pyg_ordered(x, _t(bad, dev), batch=batch_dev, num_graphs=12)  # flagged on the device; no check()
+    torch.cuda.synchronize()
+    with pytest.raises(runtime.GnnbError, match="earlier batch"):
+        m.forward_pyg_ordered(x, _t(ei, dev), batch=batch_dev, num_graphs=12)
+    m.forward_pyg_ordered(x, _t(ei, dev), batch=batch_dev, num_graphs=12)  # reported once
+    m.check()
+
+
 # ---------------------------------------------------------------------------------------------------- 8. API errors, no device work
 def test_api_errors(dev):
     b = synthetic.make_batch("qm9", 12, seed=9)
