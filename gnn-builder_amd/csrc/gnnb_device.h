@@ -1,5 +1,6 @@
 // gnnb_device.h -- device-side helpers shared by the kernel translation units of libgnnb_hip.so (gfx950 only):
-// dynamic-LDS attribute cache, LDS-DMA issue / counted-wait helpers, vector-of-floats helpers, activations.
+// dynamic-LDS attribute cache, LDS-DMA issue / counted-wait helpers, vector-of-floats helpers, activations, the validation-flag
+// report, wave / workgroup scans, the ptr-array search, the wave match.
 // Everything here is static / inline: each translation unit gets its own copy (the library is built without -fgpu-rdc).
 #pragma once
 #include <algorithm>
@@ -190,6 +191,20 @@ __device__ inline Vf<1> pyg_std(const Vf<1> &m2, const Vf<1> &m)
     return r;
 }
 
+// THE report of a validation flag (the GNNB_FLAG_* bits of BatchTables::err, gnnb_internal.h), by one lane: the authoritative word
+// lives in device memory (read and reset by gnnb_workspace_check); a copy of "something was flagged" is also dropped into a
+// host-mapped word, which the NEXT entry call on the workspace reads without synchronising (lazy detection for callers that never
+// call the check).  The copy is a plain store, not an or: the host asks the mapped word two things only -- "is it zero" and "is it
+// exactly GNNB_FLAG_RANGE" (report_earlier_flags) -- and a store of any other bit answers both as an or with it would, whatever
+// the word held.  The mapped word therefore holds the LAST reporter's bits: a RANGE report that lands behind a malformed-batch
+// report makes the lazy path say RANGE where gnnb_workspace_check, which reads the device word, says GRAPH.
+__device__ __forceinline__ void report_flag(int32_t *err, int32_t *err_host, int bits)
+{
+    atomicOr(err, bits);
+    if (err_host)
+        *reinterpret_cast<volatile int32_t *>(err_host) = bits;
+}
+
 // -------------------------------------------------------------------------------------
 // ---- Overflow contract of the REDUCED-precision math modes (gnnb_model_desc::math 2 "bf16x3" / 3 "f16x3"; VERDICT round 5,
 // item 3).  The reference's fixed-point build has DEFINED overflow (ap_fixed<W, I, AP_TRN, AP_WRAP>, code_gen.py:39-52,
@@ -214,18 +229,15 @@ struct RangeProbe {
             see(a[i], in_range);
     }
     __device__ __forceinline__ bool any() const { return bad != 0ull; } // wave-uniform
-    // one atomic per wave that saw something (rare), and the host-mapped copy graph prep's flag_batch writes too
+    // one report_flag per wave that saw something (rare)
     // returns the number of vector-memory instructions the WAVE issued (wave-uniform: 0, or the atomic + the host-mapped store):
     // the kernels that count their own vmcnt add it to their books
     __device__ __forceinline__ int report(int32_t *err, int32_t *err_host) const
     {
         if (!err || bad == 0ull)
             return 0;
-        if ((threadIdx.x & 63) == 0) {
-            atomicOr(err, GNNB_FLAG_RANGE);
-            if (err_host)
-                *reinterpret_cast<volatile int32_t *>(err_host) = GNNB_FLAG_RANGE;
-        }
+        if ((threadIdx.x & 63) == 0)
+            report_flag(err, err_host, GNNB_FLAG_RANGE);
         return err_host ? 2 : 1;
     }
 };
@@ -314,6 +326,76 @@ __device__ __forceinline__ int wave_scan_incl(int x)
     x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
     return x;
 }
+// Exclusive prefix sum over the workgroup's WAVES * 64 threads of C int components at once, and the workgroup's totals:
+// wave_scan_incl per component, then the waves' totals through s_wave (C x WAVES ints of the caller's LDS) -- one pair of
+// barriers for all C.  Every thread of the workgroup calls it; s_wave is free again behind the call.  A caller with more
+// elements than threads walks them in chunks and carries the totals itself.
+template <int WAVES, int C>
+__device__ __forceinline__ void block_scan_excl(const int (&v)[C], int (&excl)[C], int (&total)[C], int (*s_wave)[WAVES])
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl[C];
+#pragma unroll
+    for (int c = 0; c < C; c++)
+        incl[c] = wave_scan_incl(v[c]);
+    if (lane == 63) {
+#pragma unroll
+        for (int c = 0; c < C; c++)
+            s_wave[c][wave] = incl[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        int before = 0;
+        total[c] = 0;
+        for (int w = 0; w < WAVES; w++) {
+            const int t = s_wave[c][w];
+            before += w < wave ? t : 0;
+            total[c] += t;
+        }
+        excl[c] = before + incl[c] - v[c];
+    }
+    __syncthreads();
+}
+
+// The last g in [0, B) with ptr[g] <= i, for B >= 1: ptr[g] <= i < ptr[g + 1] on a monotone ptr with ptr[0] = 0 and i < ptr[B]
+// (searchsorted(ptr, i, "right") - 1; empty graphs are stepped over).  Stays inside ptr[1 .. B - 1] whatever the array holds.
+template <typename T>
+__device__ __forceinline__ int ptr_search(const T *ptr, int B, int i)
+{
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo + 1) >> 1);
+        if (ptr[mid] <= (T)i)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// Wave match on a small key: the mask of the lanes with `keep` whose key has the same low `nbits` bits as this lane's, by one
+// ballot per bit (without meaning for a lane without `keep`).  A lane's rank among its matches is the mask's popcount below the
+// lane -- stable, lanes being in input order -- and their number the popcount.  (The molecule-path graph prep, gnnb_prep.h, forms
+// the same mask and from the same ballots a second one, matched on the lane index: it keeps its own loop.)
+__device__ __forceinline__ unsigned long long wave_match(bool keep, int key, int nbits)
+{
+    unsigned long long same = __ballot(keep);
+#pragma unroll
+    for (int b = 0; b < nbits; b++) {
+        const unsigned long long mb = __ballot(keep && ((key >> b) & 1));
+        same &= ((key >> b) & 1) ? mb : ~mb;
+    }
+    return same;
+}
+
+// workgroups of a grid-stride copy kernel over `items` elements: one thread each up to `cap` workgroups, strides beyond
+static constexpr int COPY_GRID_CAP = 4096;
+inline unsigned capped_grid(unsigned long long items, int threads, int cap = COPY_GRID_CAP)
+{
+    return (unsigned)std::min<unsigned long long>((items + threads - 1) / threads, cap);
+}
+
 __device__ inline void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // s_waitcnt vmcnt(n) for a run-time (wave-uniform) n: the instruction takes an immediate
 __device__ __forceinline__ void vmcnt_wait_upto(int n)

@@ -805,11 +805,10 @@ int gnnb_forward_batched_host(const gnnb_model *model, gnnb_workspace *ws, const
     if (const int crc = check_batch_sizes(ws, num_graphs, num_nodes, num_edges))
         return crc;
     const gnnb_model_desc &d = model->desc;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // staging buffers live in the workspace, sized once for its capacities: the reference's <name>_top is called once
     // per graph (model_tb.cpp.jinja:189-205), and a hipMalloc / hipFree pair per call would dominate it
-    const size_t cx = up((size_t)ws->max_nodes * d.in_dim * 4), cc = up((size_t)std::max(ws->max_edges, 1) * 8),
-                 cp = up(((size_t)ws->max_graphs + 1) * 4), co = up((size_t)ws->max_graphs * d.mlp_out * 4);
+    const size_t cx = arena_up((size_t)ws->max_nodes * d.in_dim * 4), cc = arena_up((size_t)std::max(ws->max_edges, 1) * 8),
+                 cp = arena_up(((size_t)ws->max_graphs + 1) * 4), co = arena_up((size_t)ws->max_graphs * d.mlp_out * 4);
     if (!ws->stage) {
         GNNB_HIP_TRY(hipMalloc((void **)&ws->stage, cx + cc + 2 * cp + co));
         ws->stage_bytes = cx + cc + 2 * cp + co;

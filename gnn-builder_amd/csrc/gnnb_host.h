@@ -94,11 +94,11 @@ struct gnnb_workspace {
     float *pooled = nullptr;            // [max_graphs, np*d]
     float *mlp[2] = {nullptr, nullptr}; // [max_graphs, max(mlp_hidden, mlp_out)]
     bool prepared = false;
-    char *ingest_blob = nullptr; // gnnb_workspace_enable_ingest: the outputs and the sort scratch of gnnb_ingest_pyg (ingest_layout), one allocation
+    char *ingest_blob = nullptr; // gnnb_workspace_enable_ingest: the outputs and the sort scratch of gnnb_ingest_pyg (ingest_place), one allocation
     bool ingested = false;       // an ingest has been enqueued: gnnb_workspace_check has something to report on
     int edge_dim = 0;            // of the model the workspace was created for (0: no edge weights)
     char *edge_blob = nullptr;   // gnnb_workspace_enable_edge_ingest: edge_attr in COO row order, [max_edges, edge_dim], one allocation
-    char *order_blob = nullptr;  // gnnb_workspace_enable_ordered_ingest: the ordered batch and the staged outputs (order_layout), one allocation
+    char *order_blob = nullptr;  // gnnb_workspace_enable_ordered_ingest: the ordered batch and the staged outputs (order_place), one allocation
     int32_t *order_triple = nullptr, *order_triple_dev = nullptr; // host-mapped (first large graph, node row, edge row) of k_order_graphs, and
                                                                   // its device-visible address
     float2 *pool_part = nullptr; // pieces of graphs that cross the 32-row blocks of the pooling GEMM epilogue (PoolEpilogue::part)
@@ -154,9 +154,10 @@ int forward_batched_tail(const gnnb_model *model, gnnb_workspace *ws, const floa
                          const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev, int num_graphs, int num_nodes, int num_edges,
                          float *out_dev, void *stream, bool ingest_reported);
 
-// the add-on allocations' layouts at a workspace's capacities
-inline IngestLayout ingest_layout(const gnnb_workspace *ws) { return ingest_layout(ws->max_graphs, ws->max_nodes, ws->max_edges); }
-inline OrderLayout order_layout(const gnnb_workspace *ws) { return order_layout(ws->max_graphs, ws->max_nodes, ws->max_edges, ws->desc.in_dim, ws->desc.mlp_out); }
+// the add-on allocations at a workspace's capacities: their arrays placed in the workspace's blob, and their size (the size alone
+// while the blob is not allocated)
+inline size_t ingest_place(const gnnb_workspace *ws, IngestParams &p) { return ingest_place(ws->ingest_blob, ws->max_graphs, ws->max_nodes, ws->max_edges, p); }
+inline size_t order_place(const gnnb_workspace *ws, OrderParams &p) { return order_place(ws->order_blob, ws->max_graphs, ws->max_nodes, ws->max_edges, ws->desc.in_dim, ws->desc.mlp_out, p); }
 
 // The event-timed loop behind the *_timed entries: `warmup` launches, then `iters` launches between two events on `s`;
 // launch(i) -> GNNB_OK or an error (which ends the loop and is returned).  *out_us = microseconds per launch.

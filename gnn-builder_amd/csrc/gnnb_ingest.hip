@@ -40,17 +40,20 @@ size_t gnnb_ingest_bytes(int max_graphs, int max_nodes, int max_edges)
 {
     if (max_graphs < 0 || max_nodes < 0 || max_edges < 0)
         return 0;
-    return ingest_layout(max_graphs, max_nodes, max_edges).bytes;
+    IngestParams p;
+    return ingest_place(nullptr, max_graphs, max_nodes, max_edges, p);
 }
 
 int gnnb_workspace_enable_ingest(gnnb_workspace *ws)
 {
     const bool pending = addon_pending(ws, &gnnb_workspace::ingest_blob);
-    const int rc = enable_addon(ws, &gnnb_workspace::ingest_blob, ws ? ingest_layout(ws).bytes : 0, "gnnb_workspace_enable_ingest", "ingest", "ingest");
+    IngestParams p;
+    const int rc = enable_addon(ws, &gnnb_workspace::ingest_blob, pending ? ingest_place(ws, p) : 0, "gnnb_workspace_enable_ingest", "ingest", "ingest");
     if (rc != GNNB_OK || !pending)
         return rc;
+    (void)ingest_place(ws, p);
     // (synchronous, as the stream-K scratch's: joins no other stream)
-    const hipError_t e = hipMemset(ws->ingest_blob + ingest_layout(ws).state, 0, INGEST_STATE_WORDS * 4);
+    const hipError_t e = hipMemset(p.state, 0, INGEST_STATE_WORDS * 4);
     if (e != hipSuccess) {
         (void)hipFree(ws->ingest_blob);
         ws->ingest_blob = nullptr;
@@ -79,19 +82,14 @@ int gnnb_ingest_pyg(gnnb_workspace *ws, const int64_t *edge_index_dev, const int
         return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg: %d nodes and %d edges in %d graphs", num_nodes, num_edges, num_graphs);
     if (const int rc = report_earlier_flags(ws, stream)) // (before anything is enqueued, as gnnb_graph_prep does)
         return rc;
-    const IngestLayout l = ingest_layout(ws);
-    char *b = ws->ingest_blob;
     IngestParams p;
     memset(&p, 0, sizeof(p));
+    (void)ingest_place(ws, p);
     p.src = (const long long *)edge_index_dev;
     p.dst = p.src + num_edges;
     p.batch = (const long long *)batch_dev;
     p.ptr = (const long long *)ptr_dev;
     p.B = num_graphs, p.N = num_nodes, p.E = num_edges;
-    p.node_ptr = (int32_t *)(b + l.node_ptr), p.edge_ptr = (int32_t *)(b + l.edge_ptr), p.coo = (int2 *)(b + l.coo);
-    for (int h = 0; h < 2; h++)
-        p.keys[h] = (int32_t *)(b + l.keys[h]), p.idx[h] = (int32_t *)(b + l.idx[h]);
-    p.hist = (int32_t *)(b + l.hist), p.state = (int32_t *)(b + l.state);
     p.err = ws->t.err, p.err_host = ws->t.err_host_dev;
     GNNB_HIP_TRY(launch_ingest(p, (hipStream_t)stream));
     ws->ingested = true;
@@ -123,7 +121,8 @@ size_t gnnb_order_bytes(int max_graphs, int max_nodes, int max_edges, int in_dim
 {
     if (max_graphs < 0 || max_nodes < 0 || max_edges < 0 || in_dim < 0 || mlp_out < 0)
         return 0;
-    return order_layout(max_graphs, max_nodes, max_edges, in_dim, mlp_out).bytes;
+    OrderParams p;
+    return order_place(nullptr, max_graphs, max_nodes, max_edges, in_dim, mlp_out, p);
 }
 
 int gnnb_workspace_enable_ordered_ingest(gnnb_workspace *ws)
@@ -150,8 +149,9 @@ int gnnb_workspace_enable_ordered_ingest(gnnb_workspace *ws)
             ws->order_triple_dev = (int32_t *)dp;
         }
     }
-    return enable_addon(ws, &gnnb_workspace::order_blob, ws ? order_layout(ws).bytes : 0, "gnnb_workspace_enable_ordered_ingest", "the ordered ingest",
-                        "ordered-ingest");
+    OrderParams p;
+    return enable_addon(ws, &gnnb_workspace::order_blob, ws && !ws->order_blob ? order_place(ws, p) : 0, "gnnb_workspace_enable_ordered_ingest",
+                        "the ordered ingest", "ordered-ingest");
 }
 
 int gnnb_ingest_pyg_ordered(gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev, const int64_t *batch_dev,
@@ -173,18 +173,14 @@ int gnnb_ingest_pyg_ordered(gnnb_workspace *ws, const float *x_dev, const int64_
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
     if (const int rc = gnnb_ingest_pyg(ws, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &coo, &node_ptr, &edge_ptr, stream))
         return rc;
-    const OrderLayout l = order_layout(ws);
-    char *b = ws->order_blob;
     OrderParams p;
     memset(&p, 0, sizeof(p));
+    (void)order_place(ws, p);
     p.node_ptr = node_ptr, p.edge_ptr = edge_ptr, p.coo = (const int2 *)coo;
     p.x = x_dev;
     p.batch = num_nodes > 0 ? (const long long *)batch_dev : nullptr;
     p.B = num_graphs, p.N = num_nodes, p.E = num_edges, p.in_dim = ws->desc.in_dim;
     p.limit = ws->max_graph_nodes; // the promise as it stands at this call
-    p.perm = (int32_t *)(b + l.perm), p.node_ptr_ord = (int32_t *)(b + l.node_ptr), p.edge_ptr_ord = (int32_t *)(b + l.edge_ptr);
-    p.node_shift = (int32_t *)(b + l.node_shift), p.edge_shift = (int32_t *)(b + l.edge_shift);
-    p.x_ord = (float *)(b + l.x_ord), p.coo_ord = (int2 *)(b + l.coo_ord);
     p.triple = ws->order_triple_dev;
     GNNB_HIP_TRY(launch_order(p, (hipStream_t)stream));
     GNNB_HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); // the one synchronisation of the path
@@ -216,7 +212,9 @@ int gnnb_forward_pyg_ordered(const gnnb_model *model, gnnb_workspace *ws, const 
     // nothing large: no segment, the batch runs exactly as gnnb_forward_pyg would run it
     if (const int rc = g0 == num_graphs ? gnnb_workspace_set_large_segment(ws, -1, -1, -1) : gnnb_workspace_set_large_segment(ws, g0, n0, e0))
         return rc;
-    float *out_ord = (float *)(ws->order_blob + order_layout(ws).out_ord);
+    OrderParams placed;
+    (void)order_place(ws, placed);
+    float *out_ord = placed.out_ord;
     if (const int rc = forward_batched_tail(model, ws, x_ord, nullptr, coo, node_ptr, edge_ptr, num_graphs, num_nodes, num_edges, out_ord, stream, true))
         return rc;
     GNNB_HIP_TRY(launch_order_out(out_ord, perm, out_dev, num_graphs, ws->desc.mlp_out, (hipStream_t)stream));
@@ -229,7 +227,7 @@ size_t gnnb_edge_ingest_bytes(int max_edges, int edge_dim)
 {
     if (max_edges < 0 || edge_dim < 1 || edge_dim > 16)
         return 0;
-    return ((size_t)std::max(max_edges, 1) * (size_t)edge_dim * sizeof(float) + 255) & ~(size_t)255;
+    return arena_up((size_t)std::max(max_edges, 1) * (size_t)edge_dim * sizeof(float));
 }
 
 int gnnb_workspace_enable_edge_ingest(gnnb_workspace *ws)
@@ -256,11 +254,11 @@ int gnnb_ingest_pyg_edges(gnnb_workspace *ws, const int64_t *edge_index_dev, con
         return rc;
     // the rows follow their edges: the general path's last pass left sorted position -> input edge in one half of idx (which half:
     // launch_ingest's pass count); whether that path ran at all is the state word, read by the kernel
-    const IngestLayout l = ingest_layout(ws);
+    IngestParams p;
+    (void)ingest_place(ws, p);
     const int passes = ingest_sort_passes(num_graphs);
-    const int32_t *idx = (passes == 0 || num_edges < 2) ? nullptr : (const int32_t *)(ws->ingest_blob + l.idx[passes & 1]);
-    GNNB_HIP_TRY(launch_edge_attr_order(edge_attr_dev, idx, (const int32_t *)(ws->ingest_blob + l.state), (float *)ws->edge_blob, num_edges,
-                                        ws->edge_dim, (hipStream_t)stream));
+    const int32_t *idx = (passes == 0 || num_edges < 2) ? nullptr : p.idx[passes & 1];
+    GNNB_HIP_TRY(launch_edge_attr_order(edge_attr_dev, idx, p.state, (float *)ws->edge_blob, num_edges, ws->edge_dim, (hipStream_t)stream));
     *edge_attr_ord_dev = (const float *)ws->edge_blob;
     return GNNB_OK;
 }

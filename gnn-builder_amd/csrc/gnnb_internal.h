@@ -52,9 +52,34 @@ struct BatchTables {
     int32_t num_tiles;
 };
 
-// bit of BatchTables::err set by a kernel that multiplies on 16-bit pieces (math modes 2 / 3) when it produced a non-finite
-// value: the overflow contract of the reduced modes (gnnb_device.h: RangeProbe), reported as GNNB_ERR_RANGE
+// The bits of BatchTables::err (and of its host-mapped copy), each set by the kernels that validate what it names; the one
+// device-side report is report_flag (gnnb_device.h), the host decode gnnb_workspace_check / report_earlier_flags
+// (gnnb_runtime.hip).  All but GNNB_FLAG_RANGE are reported as GNNB_ERR_GRAPH.
+constexpr int GNNB_FLAG_PTR_ENDS = 1;      // graph prep: node_ptr / edge_ptr do not run from 0 to N / E (not complete)
+constexpr int GNNB_FLAG_PTR_ORDER = 2;     // graph prep: a graph's node or edge range is reversed or leaves the batch (not monotone)
+constexpr int GNNB_FLAG_EDGE = 4;          // graph prep: an edge leaves its graph
+constexpr int GNNB_FLAG_GRAPH_NODES = 8;   // graph prep: a graph exceeds the max_graph_nodes promise
+constexpr int GNNB_FLAG_LARGE_SEGMENT = 16; // graph prep: the large-segment offsets disagree with node_ptr / edge_ptr
+constexpr int GNNB_FLAG_DEGREE = 32;       // k_deg_count: a node exceeds the max_degree promise
+// a kernel that multiplies on 16-bit pieces (math modes 2 / 3) produced a non-finite value: the overflow contract of the reduced
+// modes (gnnb_device.h: RangeProbe), reported as GNNB_ERR_RANGE
 constexpr int GNNB_FLAG_RANGE = 64;
+constexpr int GNNB_FLAG_INGEST = 128;      // k_ingest.hip: the PyG mini-batch was malformed
+
+// The 256-byte arena of every device allocation that holds several arrays: each array starts on a 256-byte boundary, in the order
+// it is taken.  ONE statement per array names it, its element type and its length, and answers both "how many bytes" (off, after
+// the last take) and "where" -- base == nullptr: sizes only, every take gives nullptr and no pointer is formed from null.
+constexpr size_t arena_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+struct Arena {
+    char *base;
+    size_t off = 0;
+    template <typename T> T *take(size_t count)
+    {
+        const size_t o = off;
+        off += arena_up(count * sizeof(T));
+        return base ? reinterpret_cast<T *>(base + o) : nullptr;
+    }
+};
 constexpr int GNNB_G2_STAGE_ROWS = 64;     // rows per stage of the fused 2-layer GCN kernel (4 MFMA units)
 constexpr int GNNB_G2_STAGE_ROWS_BF6 = 48; // ... in the opt-in bf16x6 math mode (3 units)
 // what graph prep asks about k_gcn2_zf, the transform-first 2-layer GCN kernel (k_stack_zf.hip; the values are the launch plan's
@@ -203,7 +228,6 @@ PrepParams make_prep_params(const int32_t *coo, const int32_t *node_ptr, const i
 hipError_t launch_graph_prep(const PrepParams &p, hipStream_t s);
 
 // A PyG mini-batch on the device (k_ingest.hip): edge_index [2, E] + batch [N] or ptr [B+1], all int64 -> coo / node_ptr / edge_ptr
-constexpr int GNNB_FLAG_INGEST = 128;   // bit of BatchTables::err: the mini-batch was malformed (reported as GNNB_ERR_GRAPH)
 constexpr int INGEST_TILE = 1024;       // edges per workgroup of the edge kernels
 constexpr int INGEST_DIGIT_BITS = 8;    // bits of the graph id per radix pass of the general path
 constexpr int INGEST_STATE_UNSORTED = 0, INGEST_STATE_NODES_BROKEN = 1, INGEST_STATE_WORDS = 4; // IngestParams::state
@@ -219,11 +243,9 @@ struct IngestParams {
                                   // zero between ingests (each word is cleared by a kernel that no reader of it runs beside)
     int32_t *err, *err_host;      // the workspace's flag words (BatchTables::err / err_host_dev)
 };
-// byte offsets of the ingest allocation's arrays for a workspace's capacities, and its size: a pure function of the three
-struct IngestLayout {
-    size_t state, node_ptr, edge_ptr, coo, keys[2], idx[2], hist, bytes;
-};
-IngestLayout ingest_layout(int max_graphs, int max_nodes, int max_edges);
+// The ingest allocation at a workspace's capacities: p's arrays (node_ptr .. state) placed in `blob`, and the allocation's size -- a
+// pure function of the three.  blob == nullptr: the size alone (the arrays read nullptr).
+size_t ingest_place(char *blob, int max_graphs, int max_nodes, int max_edges, IngestParams &p);
 int ingest_sort_passes(int num_graphs); // radix passes the general path launches for that many graphs
 // the whole launch sequence; depends on B, N, E and on which of batch / ptr is given, never on device data
 hipError_t launch_ingest(const IngestParams &p, hipStream_t s);
@@ -242,12 +264,11 @@ struct OrderParams {
     float *x_ord;                       // [N, in_dim]
     int2 *coo_ord;                      // [E]
     int32_t *triple;                    // [3] host-mapped: first large graph's position, node row and edge row ((B, N, E): none)
+    float *out_ord;                     // [B, mlp_out] the forward's rows in the new order (launch_order_out's input; no kernel of launch_order reads it)
 };
-// byte offsets of the ordered form's arrays (its own allocation) and its size: a pure function of the five
-struct OrderLayout {
-    size_t x_ord, coo_ord, node_ptr, edge_ptr, perm, node_shift, edge_shift, out_ord, bytes;
-};
-OrderLayout order_layout(int max_graphs, int max_nodes, int max_edges, int in_dim, int mlp_out);
+// The ordered form's own allocation: p's output arrays (perm .. coo_ord, out_ord) placed in `blob`, and the allocation's size -- a
+// pure function of the five.  blob == nullptr: the size alone (the arrays read nullptr).
+size_t order_place(char *blob, int max_graphs, int max_nodes, int max_edges, int in_dim, int mlp_out, OrderParams &p);
 // k_order_graphs, k_order_rows, k_order_edges on `s`; launch sizes from B, N, E, in_dim only
 hipError_t launch_order(const OrderParams &p, hipStream_t s);
 // out[perm[i], :] = out_ord[i, :]: the forward's rows back in the caller's graph order

@@ -23,15 +23,8 @@ struct GraphRange {
     int n0, n1, e0, e1;
 };
 
-// Batch-validation flag: the authoritative word lives in device memory (read and reset by gnnb_workspace_check); a
-// copy of "something was flagged" is also dropped into a host-mapped word, which the NEXT entry call on the workspace
-// reads without synchronising (lazy detection for callers that never call the check).
-__device__ __forceinline__ void flag_batch(const PrepParams &p, int bits)
-{
-    atomicOr(p.err, bits);
-    if (p.err_host)
-        *reinterpret_cast<volatile int32_t *>(p.err_host) = bits;
-}
+// batch-validation flag of graph prep (report_flag, gnnb_device.h)
+__device__ __forceinline__ void flag_batch(const PrepParams &p, int bits) { report_flag(p.err, p.err_host, bits); }
 
 // ---- the steps the three paths share ------------------------------------------------------------------------------------
 // Does edge e enter the tables?  An edge that leaves its graph is an error (`bad`) and is dropped, so that later gathers stay
@@ -203,7 +196,7 @@ __device__ void prep_graph_scan(const PrepParams &p, const GraphRange r, int lan
         base += __shfl(incl, 63, 64);
     }
     if (bad)
-        flag_batch(p, 4);
+        flag_batch(p, GNNB_FLAG_EDGE);
 }
 
 // 1 / sqrt(1 + d) for the in-degrees the molecule path can meet (<= 64 edges), as correctly rounded fp32 divisions of
@@ -290,7 +283,7 @@ __device__ __forceinline__ void prep_graph_small(const PrepParams &p, const Grap
     if (lane < n)
         store_node_record(p, n0 + lane, start, deg, *reinterpret_cast<const int4 *>(s_first_w + lane * 4));
     if (bad)
-        flag_batch(p, 4);
+        flag_batch(p, GNNB_FLAG_EDGE);
 }
 
 // ---- register path: n <= PREP_FAST_NODES and ne <= PREP_FAST_EDGES, but not both <= 64 ------------------------------------
@@ -396,7 +389,7 @@ __device__ __forceinline__ void prep_graph_ballot(const PrepParams &p, const Gra
             store_node_record(p, n0 + vl, start[q], deg[q], *reinterpret_cast<const int4 *>(s_first_w + vl * 4));
     }
     if (bad)
-        flag_batch(p, 4);
+        flag_batch(p, GNNB_FLAG_EDGE);
 }
 
 // One graph (g < B), or the batch's tail (g == B: the end entries of the tables, the rows no graph owns), by one wavefront.
@@ -433,7 +426,7 @@ __device__ __forceinline__ void prep_one_graph(const PrepParams &p, int g, int l
     // with the ptr arrays of THIS batch (stale workspace state from the batch before) would leave the rows between the two
     // boundaries to neither half: flagged here, where both arrays are read anyway.
     if (p.large_n >= 0 && g == p.promise_graphs && lane == 0 && (np_at(g) != p.large_n || ep_at(g) != p.large_e))
-        flag_batch(p, 16);
+        flag_batch(p, GNNB_FLAG_LARGE_SEGMENT);
     // Containment of malformed batches: whatever node_ptr / edge_ptr hold, every row in [0, N) leaves this
     // kernel with a record that later kernels can follow without leaving the buffers -- start and start + deg
     // inside [0, E], sources inside [0, N).  A graph's ranges are CLAMPED instead of rejected (any row r < N lies
@@ -447,7 +440,7 @@ __device__ __forceinline__ void prep_one_graph(const PrepParams &p, int g, int l
                 p.agg_cut[1 << p.cut_log2] = make_int4(N, N, E, B); // (the end of the last range)
             p.row_ptr[N] = E;
             if (last != N || p.edge_ptr[B] != E || first != 0 || p.edge_ptr[0] != 0)
-                flag_batch(p, 1);
+                flag_batch(p, GNNB_FLAG_PTR_ENDS);
         }
         if (first > 0)
             prep_empty_rows(p, 0, min(first, N), lane);
@@ -460,7 +453,7 @@ __device__ __forceinline__ void prep_one_graph(const PrepParams &p, int g, int l
     GraphRange r{np_at(g), np_at(g + 1), ep_at(g), ep_at(g + 1)};
     if (r.n0 > r.n1 || r.e0 > r.e1 || r.n1 > N || r.e1 > E || r.n0 < 0 || r.e0 < 0) {
         if (lane == 0)
-            flag_batch(p, 2);
+            flag_batch(p, GNNB_FLAG_PTR_ORDER);
         r.n0 = min(max(r.n0, 0), N);
         r.n1 = min(max(r.n1, 0), N);
         r.e0 = min(max(r.e0, 0), E);
@@ -491,7 +484,7 @@ __device__ __forceinline__ void prep_one_graph(const PrepParams &p, int g, int l
         } while (bb < (1 << p.cut_log2) && (int)(((long long)max(bb, 0) * N) >> p.cut_log2) < r.n1);
     }
     if (p.max_graph_nodes_hint > 0 && n > p.max_graph_nodes_hint && g < p.promise_graphs && lane == 0)
-        flag_batch(p, 8); // the caller's max_graph_nodes promise does not hold for this batch
+        flag_batch(p, GNNB_FLAG_GRAPH_NODES); // the caller's max_graph_nodes promise does not hold for this batch
     // (all three conditions are wave-uniform)
     if (n > PREP_FAST_NODES || ne > PREP_FAST_EDGES)
         prep_graph_scan(p, r, lane);

@@ -164,77 +164,68 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     ws->max_edges = max_edges;
     (void)hipGetDevice(&ws->device);
 
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
     const size_t N = max_nodes, E = std::max(max_edges, 1), B = max_graphs;
     // (models whose last conv layer ends in the large-K segmented GEMM -- GraphSAGE -- pool in that GEMM's epilogue: a
     // node -> graph table and the buffer for the pieces of graphs that cross 32-row blocks)
     const bool pool_epi = (d.conv_type == GNNB_CONV_SAGE || d.conv_type == GNNB_CONV_PNA) && d.num_layers >= 1 && d.fpx_w <= 0;
-    const size_t o_rp = carve((N + 1) * 4), o_col = carve(E * 4), o_eid = carve(E * 4), o_rec = carve(N * 32), o_dinv = carve(N * 4), o_amp = carve(N * 4),
-                 o_att = carve(N * 4), o_gcoef = carve(N * 16), o_tile = carve((max_tiles + 1) * 4), o_tedge = carve((max_tiles + 1) * 4), o_gptr = carve((B + 1) * 4),
-                 o_tgraph = carve((max_tiles + 1) * 4), o_err = carve(4), o_cut = carve((4096 + 1) * 16), o_scut = carve((1024 + 2) * 4),
-                 o_plan = carve(want_plan ? (size_t)stage_cut_levels((int)max_tiles) * (max_tiles + 1) * 4 : 0),
-                 o_dwork = carve(d.conv_type == GNNB_CONV_PNA ? 1024 * 16 * 4 : 0),
-                 o_dperm = carve(d.conv_type == GNNB_CONV_PNA ? ((N + 127) / 128 + GNNB_DEG_CLASSES + 1) * 128 * 4 : 0),
-                 o_dcls = carve(d.conv_type == GNNB_CONV_PNA ? ((N + 127) / 128 + GNNB_DEG_CLASSES + 1) * 4 : 0),
-                 o_ngraph = carve(pool_epi ? N * 4 : 0), o_part = carve(pool_epi ? ((N + 31) / 32) * 2 * (size_t)gnn_out_width(d) * 8 : 0),
-                 o_a0 = carve(N * maxw * 4), o_a1 = carve(N * maxw * 4), o_agg = carve(N * aggw * 4),
-                 o_t0 = carve(N * tmpw * 4), o_t1 = carve(N * tmpw * 4),
-                 o_pool = carve(B * pooledw * 4), o_m0 = carve(B * mlpw * 4),
-                 o_m1 = carve(B * mlpw * 4), o_sk = carve(want_sk ? stream_k_scratch_bytes() : 0);
-    ws->bytes = off;
+    const bool pna = d.conv_type == GNNB_CONV_PNA;
+    const size_t deg_tiles = (N + 127) / 128 + GNNB_DEG_CLASSES + 1;
+    // THE list of the blob's arrays, in their order in it: run once without a base for the size, once on the blob (an array the
+    // workspace does not want takes nothing and reads nullptr)
+    char *sk_base = nullptr;
+    auto place = [&](Arena a) {
+        BatchTables &t = ws->t;
+        t.row_ptr = a.take<int32_t>(N + 1);
+        t.col = a.take<int32_t>(E);
+        t.eid = a.take<int32_t>(E);
+        t.node_rec = a.take<int4>(2 * N);
+        t.dinv = a.take<float>(N);
+        t.amp = a.take<float>(N);
+        t.att = a.take<float>(N);
+        t.gcoef = a.take<float4>(N);
+        t.tile_first = a.take<int32_t>(max_tiles + 1);
+        t.tile_edge = a.take<int32_t>(max_tiles + 1);
+        t.graph_ptr = a.take<int32_t>(B + 1);
+        t.tile_graph = a.take<int32_t>(max_tiles + 1);
+        t.err = a.take<int32_t>(1);
+        t.agg_cut = a.take<int4>(4096 + 1);
+        t.stage_cut = a.take<int32_t>(1024 + 2);
+        ws->plan_scratch = want_plan ? a.take<int32_t>((size_t)stage_cut_levels((int)max_tiles) * (max_tiles + 1)) : nullptr;
+        ws->deg_work = pna ? a.take<int32_t>(1024 * 16) : nullptr;
+        ws->deg_perm = pna ? a.take<int32_t>(deg_tiles * 128) : nullptr;
+        ws->deg_tile_cls = pna ? a.take<int32_t>(deg_tiles) : nullptr;
+        t.node_graph = pool_epi ? a.take<int32_t>(N) : nullptr;
+        ws->pool_part = pool_epi ? a.take<float2>(((N + 31) / 32) * 2 * (size_t)gnn_out_width(d)) : nullptr;
+        ws->act[0] = a.take<float>(N * maxw);
+        ws->act[1] = a.take<float>(N * maxw);
+        ws->agg = a.take<float>(N * aggw);
+        ws->tmp0 = a.take<float>(N * tmpw);
+        ws->tmp1 = a.take<float>(N * tmpw);
+        ws->pooled = a.take<float>(B * pooledw);
+        ws->mlp[0] = a.take<float>(B * mlpw);
+        ws->mlp[1] = a.take<float>(B * mlpw);
+        sk_base = want_sk ? a.take<char>(stream_k_scratch_bytes()) : nullptr;
+        return a.off;
+    };
+    ws->bytes = place(Arena{nullptr});
     hipError_t e = hipMalloc((void **)&ws->blob, ws->bytes);
     if (e != hipSuccess) {
+        const size_t bytes = ws->bytes;
         delete ws;
-        return fail(GNNB_ERR_HIP, "workspace allocation of %zu bytes failed: %s", off,
+        return fail(GNNB_ERR_HIP, "workspace allocation of %zu bytes failed: %s", bytes,
                     hipGetErrorString(e));
     }
-    char *b = ws->blob;
-    ws->t.row_ptr = (int32_t *)(b + o_rp);
-    ws->t.col = (int32_t *)(b + o_col);
-    ws->t.eid = (int32_t *)(b + o_eid);
-    ws->t.node_rec = (int4 *)(b + o_rec);
-    ws->t.dinv = (float *)(b + o_dinv);
-    ws->t.amp = (float *)(b + o_amp);
-    ws->t.att = (float *)(b + o_att);
-    ws->t.gcoef = (float4 *)(b + o_gcoef);
-    ws->t.tile_first = (int32_t *)(b + o_tile);
-    ws->t.graph_ptr = (int32_t *)(b + o_gptr);
-    ws->t.tile_edge = (int32_t *)(b + o_tedge);
-    ws->t.tile_graph = (int32_t *)(b + o_tgraph);
-    ws->t.err = (int32_t *)(b + o_err);
-    ws->t.agg_cut = (int4 *)(b + o_cut);
+    (void)place(Arena{ws->blob});
     ws->t.agg_cut_n = 0;
-    ws->t.stage_cut = (int32_t *)(b + o_scut);
     ws->t.stage_cut_n = 0;
     ws->t.stage_cut_cap = 1024;
-    ws->plan_scratch = want_plan ? (int32_t *)(b + o_plan) : nullptr;
-    ws->t.node_graph = pool_epi ? (int32_t *)(b + o_ngraph) : nullptr;
-    if (d.conv_type == GNNB_CONV_PNA) {
-        ws->deg_work = (int32_t *)(b + o_dwork);
-        ws->deg_perm = (int32_t *)(b + o_dperm);
-        ws->deg_tile_cls = (int32_t *)(b + o_dcls);
-    }
-    ws->pool_part = pool_epi ? (float2 *)(b + o_part) : nullptr;
-    ws->act[0] = (float *)(b + o_a0);
-    ws->act[1] = (float *)(b + o_a1);
-    ws->agg = (float *)(b + o_agg);
-    ws->tmp0 = (float *)(b + o_t0);
-    ws->tmp1 = (float *)(b + o_t1);
-    ws->pooled = (float *)(b + o_pool);
-    ws->mlp[0] = (float *)(b + o_m0);
-    ws->mlp[1] = (float *)(b + o_m1);
     (void)hipMemset(ws->t.err, 0, sizeof(int32_t));
     if (want_sk) {
-        ws->sk = stream_k_scratch_at(b + o_sk);
+        ws->sk = stream_k_scratch_at(sk_base);
         // arrival counters zero (as every launch leaves them), guard pattern behind them.  Synchronous memsets, not the null
         // stream + a synchronise: that would join -- and could disturb a capture in progress on -- every blocking stream of the
         // process (round-5 advisor finding)
-        (void)stream_k_scratch_init_sync(b + o_sk);
+        (void)stream_k_scratch_init_sync(sk_base);
     }
     // best effort: without the mapped word only gnnb_workspace_check reports a malformed batch
     ws->t.err_host_dev = nullptr;
@@ -596,6 +587,9 @@ int gnnb_workspace_check(gnnb_workspace *ws, void *stream)
     }
     if (ws->err_host)
         *(volatile int32_t *)ws->err_host = 0;
+    static_assert(GNNB_FLAG_PTR_ENDS == 1 && GNNB_FLAG_PTR_ORDER == 2 && GNNB_FLAG_EDGE == 4 && GNNB_FLAG_GRAPH_NODES == 8 &&
+                      GNNB_FLAG_LARGE_SEGMENT == 16 && GNNB_FLAG_DEGREE == 32 && GNNB_FLAG_RANGE == 64 && GNNB_FLAG_INGEST == 128,
+                  "the message below names the bits by value");
     if (err & ~GNNB_FLAG_RANGE)
         return fail(GNNB_ERR_GRAPH, "malformed batch (flags 0x%x): 1/2 ptr arrays not monotone/complete, 4 an edge leaves "
                                     "its graph, 8 a graph exceeds the max_graph_nodes promise, 16 the large-segment offsets "

@@ -36,28 +36,17 @@ static_assert(INGEST_TILE % IT == 0, "whole rounds");
 // the validation flag of the workspace (what flag_batch is to graph prep): one lane per wave with something to report
 __device__ __forceinline__ void ingest_flag(const IngestParams &p, bool bad)
 {
-    if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) {
-        atomicOr(p.err, GNNB_FLAG_INGEST);
-        if (p.err_host)
-            (void)__hip_atomic_fetch_or(p.err_host, GNNB_FLAG_INGEST, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0)
+        report_flag(p.err, p.err_host, GNNB_FLAG_INGEST);
 }
 
-// graph of node v in [0, N), always inside [0, B): batch[v] clamped, or the last g with ptr[g] <= v -- a search that stays
-// inside ptr[1 .. B - 1] whatever the array holds (searchsorted(ptr, v, "right") - 1 on a well-formed one)
+// graph of node v in [0, N), always inside [0, B): batch[v] clamped, or the last g with ptr[g] <= v (ptr_search: inside
+// ptr[1 .. B - 1] whatever the array holds), or 0 (neither: B == 1)
 __device__ __forceinline__ int ingest_graph_of(const IngestParams &p, int v)
 {
     if (p.batch)
         return (int)min(max(p.batch[v], 0ll), (long long)(p.B - 1));
-    int lo = 0, hi = p.ptr ? p.B - 1 : 0;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo + 1) >> 1);
-        if (p.ptr[mid] <= (long long)v)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
+    return p.ptr ? ptr_search(p.ptr, p.B, v) : 0;
 }
 
 // endpoints of input edge e narrowed into [0, N); true = one of them lay outside (negative, >= N, or beyond 32 bits)
@@ -178,32 +167,22 @@ __global__ __launch_bounds__(1024) void k_ingest_scan(IngestParams p, int n)
 {
     if (!p.state[INGEST_STATE_UNSORTED])
         return;
-    __shared__ int s_wave[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int s_wave[1][16];
     int carry = 0;
     for (int base = 0; base < n; base += 1024) {
         const int i = base + threadIdx.x;
-        const int v = i < n ? p.hist[i] : 0;
-        const int incl = wave_scan_incl(v);
-        if (lane == 63)
-            s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < 16; w++) {
-            const int t = s_wave[w];
-            before += w < wave ? t : 0;
-            total += t;
-        }
+        const int v[1] = {i < n ? p.hist[i] : 0};
+        int excl[1], total[1];
+        block_scan_excl<16, 1>(v, excl, total, s_wave);
         if (i < n)
-            p.hist[i] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();
+            p.hist[i] = carry + excl[0];
+        carry += total[0];
     }
 }
 
 // Tile b moves its (key, edge index) pairs to hist[digit * nb + b] + rank among the tile's pairs of that digit.  The rank of
 // a pair counts the pairs in front of it in tile order (round, wave, lane): inside a wave by matching the lanes on the eight
-// bits of the digit (as prep_graph_small does for destinations), across waves and rounds by a prefix over the 16 (round,
+// bits of the digit (wave_match; as prep_graph_small does for destinations), across waves and rounds by a prefix over the 16 (round,
 // wave) counts of each digit.  idx_in == nullptr: the first pass, a pair's edge index is its position.
 __global__ __launch_bounds__(IT) void k_ingest_scatter(IngestParams p, const int32_t *keys_in, const int32_t *idx_in, int32_t *keys_out,
                                                        int32_t *idx_out, int shift, int nb)
@@ -223,12 +202,7 @@ __global__ __launch_bounds__(IT) void k_ingest_scatter(IngestParams p, const int
         const bool keep = e < p.E;
         key[k] = keep ? keys_in[e] : 0;
         const int dig = (key[k] >> shift) & (DIGITS - 1);
-        unsigned long long same = __ballot(keep);
-#pragma unroll
-        for (int b = 0; b < INGEST_DIGIT_BITS; b++) {
-            const unsigned long long mb = __ballot(keep && ((dig >> b) & 1));
-            same &= ((dig >> b) & 1) ? mb : ~mb;
-        }
+        const unsigned long long same = wave_match(keep, dig, INGEST_DIGIT_BITS);
         rank[k] = __builtin_amdgcn_mbcnt_hi((unsigned)(same >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)same, 0));
         if (keep && rank[k] == 0)
             s_cnt[k * (IT / 64) + wave][dig] = __popcll(same);
@@ -286,28 +260,21 @@ int ingest_sort_passes(int num_graphs)
     return passes;
 }
 
-IngestLayout ingest_layout(int max_graphs, int max_nodes, int max_edges)
+size_t ingest_place(char *blob, int max_graphs, int max_nodes, int max_edges, IngestParams &p)
 {
     (void)max_nodes; // (no array of the ingest has one entry per node)
     const size_t B = (size_t)std::max(max_graphs, 0), E = (size_t)std::max(max_edges, 1), nb = (E + INGEST_TILE - 1) / INGEST_TILE;
-    IngestLayout l;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    l.state = carve(INGEST_STATE_WORDS * 4); // (first: the words enable_ingest zeroes)
-    l.node_ptr = carve((B + 1) * 4);
-    l.edge_ptr = carve((B + 1) * 4);
-    l.coo = carve(E * 8);
+    Arena a{blob};
+    p.state = a.take<int32_t>(INGEST_STATE_WORDS); // (first: the words enable_ingest zeroes)
+    p.node_ptr = a.take<int32_t>(B + 1);
+    p.edge_ptr = a.take<int32_t>(B + 1);
+    p.coo = a.take<int2>(E);
     for (int h = 0; h < 2; h++) {
-        l.keys[h] = carve(E * 4);
-        l.idx[h] = carve(E * 4);
+        p.keys[h] = a.take<int32_t>(E);
+        p.idx[h] = a.take<int32_t>(E);
     }
-    l.hist = carve(nb * DIGITS * 4);
-    l.bytes = off;
-    return l;
+    p.hist = a.take<int32_t>(nb * DIGITS);
+    return a.off;
 }
 
 hipError_t launch_ingest(const IngestParams &p, hipStream_t s)

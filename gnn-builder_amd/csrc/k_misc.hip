@@ -64,11 +64,8 @@ __global__ __launch_bounds__(WG) void k_deg_count(const int32_t *__restrict__ ro
     }
     if (lane < 16)
         work[run * 16 + lane] = lane < GNNB_DEG_CLASSES ? cnt : 0;
-    if (__ballot(bad) && lane == 0) { // the caller's max_degree promise is broken: flagged, results unspecified
-        atomicOr(err, 32);
-        if (err_host)
-            *reinterpret_cast<volatile int32_t *>(err_host) = 32;
-    }
+    if (__ballot(bad) && lane == 0) // the caller's max_degree promise is broken: flagged, results unspecified
+        report_flag(err, err_host, GNNB_FLAG_DEGREE);
 }
 
 __global__ __launch_bounds__(GNNB_DEG_RUNS) void k_deg_offsets(int32_t *__restrict__ work, int32_t *__restrict__ tile_cls, int max_tiles)
@@ -182,8 +179,7 @@ hipError_t launch_quantize(const float *src, float *dst, size_t n, int W, int I,
         return hipSuccess;
     const float inv_step = ldexpf(1.0f, W - I), step = ldexpf(1.0f, -(W - I));
     const float span = ldexpf(1.0f, I), half = ldexpf(1.0f, I - 1);
-    const unsigned grid = (unsigned)std::min<size_t>((n + WG - 1) / WG, 4096);
-    hipLaunchKernelGGL(k_quantize, dim3(grid), dim3(WG), 0, s, src, dst, n, inv_step, step, half, span);
+    hipLaunchKernelGGL(k_quantize, dim3(capped_grid(n, WG)), dim3(WG), 0, s, src, dst, n, inv_step, step, half, span);
     return hipGetLastError();
 }
 

@@ -22,35 +22,21 @@
 namespace gnnb {
 
 constexpr int OG = 1024; // threads of k_order_graphs: one workgroup of 16 waves
-constexpr int OT = 256;  // threads per workgroup of the other three
-constexpr int ORDER_MAX_GRID = 4096; // workgroups of the copy kernels (grid-stride beyond)
+constexpr int OT = 256;  // threads per workgroup of the other three (grid-stride copies: capped_grid)
 
 struct Tri { // graphs, nodes, edges
     int c, n, e;
 };
 __device__ __forceinline__ Tri operator+(Tri a, Tri b) { return Tri{a.c + b.c, a.n + b.n, a.e + b.e}; }
 
-// exclusive prefix of `v` over the workgroup's OG threads, and the workgroup's total
+// exclusive prefix of `v` over the workgroup's OG threads, and the workgroup's total: the three components in one block_scan_excl
 __device__ __forceinline__ Tri order_block_scan(Tri v, Tri &total, int (*s_wave)[OG / 64])
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const Tri incl = {wave_scan_incl(v.c), wave_scan_incl(v.n), wave_scan_incl(v.e)};
-    if (lane == 63) {
-        s_wave[0][wave] = incl.c;
-        s_wave[1][wave] = incl.n;
-        s_wave[2][wave] = incl.e;
-    }
-    __syncthreads();
-    Tri before = {0, 0, 0};
-    total = Tri{0, 0, 0};
-    for (int w = 0; w < OG / 64; w++) {
-        const Tri t = {s_wave[0][w], s_wave[1][w], s_wave[2][w]};
-        if (w < wave)
-            before = before + t;
-        total = total + t;
-    }
-    __syncthreads();
-    return Tri{before.c + incl.c - v.c, before.n + incl.n - v.n, before.e + incl.e - v.e};
+    const int in[3] = {v.c, v.n, v.e};
+    int excl[3], tot[3];
+    block_scan_excl<OG / 64, 3>(in, excl, tot, s_wave);
+    total = Tri{tot[0], tot[1], tot[2]};
+    return Tri{excl[0], excl[1], excl[2]};
 }
 
 // graph i < B as a term of the small group's sums ({0, 0, 0} for a large one)
@@ -104,22 +90,7 @@ __global__ __launch_bounds__(OG) void k_order_graphs(OrderParams p)
     }
 }
 
-// the last g in [0, B) with ptr[g] <= i, for 0 <= i < ptr[B] and ptr[0] = 0: ptr[g] <= i < ptr[g + 1] on a monotone ptr
-// (searchsorted(ptr, i, "right") - 1; empty graphs are stepped over)
-__device__ __forceinline__ int order_search(const int32_t *ptr, int B, int i)
-{
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo + 1) >> 1);
-        if (ptr[mid] <= i)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
-// graph of node v in [0, N): batch[v] where node_ptr agrees (always, on a well-formed batch), otherwise the search
+// graph of node v in [0, N): batch[v] where node_ptr agrees (always, on a well-formed batch), otherwise the search (ptr_search)
 __device__ __forceinline__ int order_graph_of_node(const OrderParams &p, int v)
 {
     if (p.batch) {
@@ -127,7 +98,7 @@ __device__ __forceinline__ int order_graph_of_node(const OrderParams &p, int v)
         if (p.node_ptr[g] <= v && v < p.node_ptr[g + 1])
             return g;
     }
-    return order_search(p.node_ptr, p.B, v);
+    return ptr_search(p.node_ptr, p.B, v);
 }
 
 // V floats per piece (4: a row is in_dim / 4 float4, both matrices 16-byte aligned); 64-bit indices: N * in_dim may pass 2^31
@@ -146,7 +117,7 @@ template <int V> __global__ __launch_bounds__(OT) void k_order_rows(OrderParams 
 __global__ __launch_bounds__(OT) void k_order_edges(OrderParams p)
 {
     for (long long e = (long long)blockIdx.x * OT + threadIdx.x; e < p.E; e += (long long)gridDim.x * OT) {
-        const int g = order_search(p.edge_ptr, p.B, (int)e);
+        const int g = ptr_search(p.edge_ptr, p.B, (int)e);
         const long long ns = p.node_shift[g], hi = p.N - 1;
         const int2 c = p.coo[e];
         p.coo_ord[e + p.edge_shift[g]] = make_int2((int)min(max(c.x + ns, 0ll), hi), (int)min(max(c.y + ns, 0ll), hi));
@@ -162,29 +133,20 @@ __global__ __launch_bounds__(OT) void k_order_out(const float *out_ord, const in
     }
 }
 
-OrderLayout order_layout(int max_graphs, int max_nodes, int max_edges, int in_dim, int mlp_out)
+size_t order_place(char *blob, int max_graphs, int max_nodes, int max_edges, int in_dim, int mlp_out, OrderParams &p)
 {
     const size_t B = (size_t)std::max(max_graphs, 0), N = (size_t)std::max(max_nodes, 0), E = (size_t)std::max(max_edges, 1);
-    OrderLayout l;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    l.x_ord = carve(N * (size_t)std::max(in_dim, 0) * 4);
-    l.coo_ord = carve(E * 8);
-    l.node_ptr = carve((B + 1) * 4);
-    l.edge_ptr = carve((B + 1) * 4);
-    l.perm = carve(B * 4);
-    l.node_shift = carve(B * 4);
-    l.edge_shift = carve(B * 4);
-    l.out_ord = carve(B * (size_t)std::max(mlp_out, 0) * 4);
-    l.bytes = off;
-    return l;
+    Arena a{blob};
+    p.x_ord = a.take<float>(N * (size_t)std::max(in_dim, 0));
+    p.coo_ord = a.take<int2>(E);
+    p.node_ptr_ord = a.take<int32_t>(B + 1);
+    p.edge_ptr_ord = a.take<int32_t>(B + 1);
+    p.perm = a.take<int32_t>(B);
+    p.node_shift = a.take<int32_t>(B);
+    p.edge_shift = a.take<int32_t>(B);
+    p.out_ord = a.take<float>(B * (size_t)std::max(mlp_out, 0));
+    return a.off;
 }
-
-static unsigned order_grid(long long items) { return (unsigned)std::min<long long>((items + OT - 1) / OT, ORDER_MAX_GRID); }
 
 hipError_t launch_order(const OrderParams &p, hipStream_t s)
 {
@@ -192,12 +154,12 @@ hipError_t launch_order(const OrderParams &p, hipStream_t s)
     const long long floats = (long long)p.N * p.in_dim;
     if (floats > 0) {
         if (p.in_dim % 4 == 0 && (((uintptr_t)p.x | (uintptr_t)p.x_ord) & 15) == 0)
-            hipLaunchKernelGGL(k_order_rows<4>, dim3(order_grid(floats / 4)), dim3(OT), 0, s, p);
+            hipLaunchKernelGGL(k_order_rows<4>, dim3(capped_grid(floats / 4, OT)), dim3(OT), 0, s, p);
         else
-            hipLaunchKernelGGL(k_order_rows<1>, dim3(order_grid(floats)), dim3(OT), 0, s, p);
+            hipLaunchKernelGGL(k_order_rows<1>, dim3(capped_grid(floats, OT)), dim3(OT), 0, s, p);
     }
     if (p.E > 0)
-        hipLaunchKernelGGL(k_order_edges, dim3(order_grid(p.E)), dim3(OT), 0, s, p);
+        hipLaunchKernelGGL(k_order_edges, dim3(capped_grid(p.E, OT)), dim3(OT), 0, s, p);
     return hipGetLastError();
 }
 
@@ -205,7 +167,7 @@ hipError_t launch_order_out(const float *out_ord, const int32_t *perm, float *ou
 {
     const long long total = (long long)num_graphs * width;
     if (total > 0)
-        hipLaunchKernelGGL(k_order_out, dim3(order_grid(total)), dim3(OT), 0, s, out_ord, perm, out, num_graphs, width);
+        hipLaunchKernelGGL(k_order_out, dim3(capped_grid(total, OT)), dim3(OT), 0, s, out_ord, perm, out, num_graphs, width);
     return hipGetLastError();
 }
 

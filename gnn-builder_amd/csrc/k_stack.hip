@@ -993,11 +993,8 @@ __global__ __launch_bounds__(G2_WG, 4) void k_gcn2_fused(
     }
     if constexpr (H3) { // the reduced mode's overflow contract: GNNB_FLAG_RANGE into the workspace's flag word (gnnb_device.h)
         __syncthreads();
-        if (tid == 0 && *SFLAG != 0 && err) {
-            atomicOr(err, GNNB_FLAG_RANGE);
-            if (err_host)
-                *reinterpret_cast<volatile int32_t *>(err_host) = GNNB_FLAG_RANGE;
-        }
+        if (tid == 0 && *SFLAG != 0 && err)
+            report_flag(err, err_host, GNNB_FLAG_RANGE);
     }
 #ifdef GNNB_PROBE
     if (lane == 0 && blockIdx.x < 512) {

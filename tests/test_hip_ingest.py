@@ -121,9 +121,11 @@ def test_more_graph_ids_than_two_digit_passes_cover(dev):
 
 # ---------------------------------------------------------------------------------------------------- 4. block edges
 @pytest.mark.parametrize("shuffled", [False, True])
-@pytest.mark.parametrize("E", [0, 1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2049])
+@pytest.mark.parametrize("E", [0, 1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2049, 4096, 4097])
 def test_edge_counts_around_wave_workgroup_and_tile(cm, dev, E, shuffled):
-    """64 lanes, 256 threads, tiles of 1024 edges (one more element closes the ptr arrays: E = 1023 fills a tile exactly)."""
+    """64 lanes, 256 threads, tiles of 1024 edges (one more element closes the ptr arrays: E = 1023 fills a tile exactly).  The
+    general path's digit table has 256 entries per tile and is scanned in chunks of 1024: E = 4096 (4 tiles) fills one chunk
+    exactly, E = 4097 (5 tiles) carries into a second."""
     assert runtime.INGEST_TILE == 1024
     rng = np.random.default_rng(E)
     sizes = np.array([7, 9, 8, 3, 13])

@@ -21,6 +21,15 @@ def needed(B, N, E):
     return 4 * (2 * (B + 1) + 2 * E + 4 * E + (1 << runtime.INGEST_DIGIT_BITS) * tiles + 4)
 
 
+def exact(B, N, E):
+    """The allocation's closed form: every array's bytes rounded up to 256 -- the state words, the two ptr arrays, coo, two
+    halves of keys and edge indices, the digit counts; sized for at least one edge."""
+    up = lambda b: -(-b // 256) * 256
+    E = max(E, 1)
+    tiles = -(-E // runtime.INGEST_TILE)
+    return up(16) + 2 * up(4 * (B + 1)) + up(8 * E) + 4 * up(4 * E) + up(4 * (1 << runtime.INGEST_DIGIT_BITS) * tiles)
+
+
 def test_size_is_a_monotone_function_of_the_capacities(size):
     grid = [1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2048, 2049, 65536, 70_000, 140_000, 1 << 20]
     for axis in range(3):
@@ -31,6 +40,7 @@ def test_size_is_a_monotone_function_of_the_capacities(size):
                 caps.insert(axis, v)
                 sizes.append(size(*caps))
                 assert sizes[-1] == size(*caps) > 0  # (a function of the three numbers alone)
+                assert sizes[-1] == exact(*caps), caps
             assert sizes == sorted(sizes), (axis, other, sizes)
 
 
@@ -42,3 +52,4 @@ def test_size_covers_what_the_kernels_index(size):
     for B, N, E in shapes:
         assert size(B, N, E) >= needed(B, N, E), (B, N, E)
         assert size(B, N, E) <= needed(B, N, max(E, 1)) + 16 * 256  # (no more than the arrays and their 256-byte alignment)
+        assert size(B, N, E) == exact(B, N, E), (B, N, E)

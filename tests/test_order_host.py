@@ -19,6 +19,13 @@ def needed(B, N, E, in_dim, mlp_out):
     return 4 * (N * in_dim + B * mlp_out + 2 * E + 2 * (B + 1) + 3 * B)
 
 
+def exact(B, N, E, in_dim, mlp_out):
+    """The allocation's closed form: every array's bytes rounded up to 256 -- x_ord, coo (sized for at least one edge), the two
+    ptr arrays, perm and the two shifts, the staged outputs."""
+    up = lambda b: -(-b // 256) * 256
+    return up(4 * N * in_dim) + up(8 * max(E, 1)) + 2 * up(4 * (B + 1)) + 3 * up(4 * B) + up(4 * B * mlp_out)
+
+
 def test_size_is_positive_and_monotone_in_every_argument(lib):
     assert lib.order_bytes(0, 0, 0, 0, 0) > 0
     grid = [0, 1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2049, 70_000, 1 << 20]
@@ -30,6 +37,7 @@ def test_size_is_positive_and_monotone_in_every_argument(lib):
                 args.insert(axis, v)
                 sizes.append(lib.order_bytes(*args))
                 assert sizes[-1] == lib.order_bytes(*args) > 0  # (a function of the five numbers alone)
+                assert sizes[-1] == exact(*args), args
             assert sizes == sorted(sizes), (axis, other, sizes)
 
 
@@ -39,6 +47,7 @@ def test_size_covers_what_the_kernels_index(lib):
                  (4096, 110_000, 240_000, 9, 1), (1 << 20, 1 << 24, 1 << 25, 256, 64)]:
         assert lib.order_bytes(*args) >= needed(*args), args
         assert lib.order_bytes(*args) <= needed(*args) + 8 + 8 * 256, args  # (no more than the arrays and their 256-byte alignment)
+        assert lib.order_bytes(*args) == exact(*args), args
 
 
 def test_size_does_not_depend_on_another_model(lib):
