@@ -92,14 +92,14 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     if (d.conv_type != GNNB_CONV_GCN || L < 2 || L > GNNB_MAX_LAYERS)
         return g;
     if (L > 2) {
-        g.wmid = model->conv[1][0];
-        g.bmid = model->conv[1][1];
+        g.wmid = model->conv[1].w0;
+        g.bmid = model->conv[1].b0;
         if (L > 3) {
-            g.mid_stride = (long)(model->conv[2][0] - model->conv[1][0]);
-            g.bmid_stride = (long)(model->conv[2][1] - model->conv[1][1]);
+            g.mid_stride = (long)(model->conv[2].w0 - model->conv[1].w0);
+            g.bmid_stride = (long)(model->conv[2].b0 - model->conv[1].b0);
         }
         for (int l = 1; l + 1 < L; l++)
-            if (model->conv[l][0] != g.wmid + (long)(l - 1) * g.mid_stride || model->conv[l][1] != g.bmid + (long)(l - 1) * g.bmid_stride)
+            if (model->conv[l].w0 != g.wmid + (long)(l - 1) * g.mid_stride || model->conv[l].b0 != g.bmid + (long)(l - 1) * g.bmid_stride)
                 return g;
     }
     g.skip = d.skip ? 1 : 0;
@@ -142,7 +142,7 @@ struct LayerCtx {
     const float *cur;  // the layer's input [N, fi] ...
     float *nxt;        // ... and output [N, fo]
     const float *skip; // cur on a middle layer of a model with skip connections
-    bool skip_fold;    // (GraphSAGE / PNA: derived weight slots of such a layer carry the skip connection as + I on x's own weights: gnnb_model_create)
+    bool skip_fold;    // (GraphSAGE / PNA: the derived weights of such a layer (w_cat_skip, w_fold, w_class) carry the skip connection as + I on x's own weights: gnnb_model_create)
 
     hipStream_t hs() const { return (hipStream_t)stream; }
     // the row range of a [N, width] matrix
@@ -196,90 +196,90 @@ static int try_pooling_gemm(const LayerCtx &c, const gnnb_gemm_seg *segs, int nu
 static int gcn_layer(const LayerCtx &c)
 {
     const gnnb_model_desc &d = c.model->desc;
-    const std::vector<const float *> &p = c.model->conv[c.l];
+    const LayerWeights &p = c.model->conv[c.l];
     const int fi = c.fi, fo = c.fo;
     int rc;
     // aggregate at the input width, then transform (the reference's order, lib:1346-1379)
     if (c.whole && options().fuse_narrow && fi <= 32)
-        GNNB_RUNG(attempt(launch_conv_gather(c.ws->t, GNNB_AGG_GCN, 0.f, c.cur, fi, fi, p[0], fi, p[1], c.skip, c.nxt, fo, d.activation, c.hs()),
+        GNNB_RUNG(attempt(launch_conv_gather(c.ws->t, GNNB_AGG_GCN, 0.f, c.cur, fi, fi, p.w0, fi, p.b0, c.skip, c.nxt, fo, d.activation, c.hs()),
                           "fused narrow conv"));
     if ((rc = c.aggregate(GNNB_AGG_GCN, c.cur, nullptr, c.ws->agg, fi, 0.f)))
         return rc;
-    return c.linear1(c.rows(c.ws->agg, fi), fi, p[0], fi, p[1], c.rows(c.skip, fi), c.rows(c.nxt, fo), fo, d.activation);
+    return c.linear1(c.rows(c.ws->agg, fi), fi, p.w0, fi, p.b0, c.rows(c.skip, fi), c.rows(c.nxt, fo), fo, d.activation);
 }
 
 // GIN's first linear + ReLU on the eps-weighted sum -> ws->tmp0
 static int gin_hidden(const LayerCtx &c)
 {
     const gnnb_model_desc &d = c.model->desc;
-    const std::vector<const float *> &p = c.model->conv[c.l];
+    const LayerWeights &p = c.model->conv[c.l];
     const int fi = c.fi, fo = c.fo;
     int rc;
     if (c.model->edge_dim) {
         // GINE: the same layer with relu(x_j + W_e e_ij + b_e) as the message -- k_gine_aggregate forms the edge term on chip
-        // (slots 4, 5: W_e [fi, edge_dim], b_e); none of the fused rungs, everything behind the aggregate is GIN's
+        // (edge_w [fi, edge_dim], edge_b); none of the fused rungs, everything behind the aggregate is GIN's
         if (c.M > 0)
-            GNNB_HIP_TRY(launch_gine_aggregate(c.tv, c.cur, c.edge_attr, c.model->edge_dim, p[4], c.model->edge_dim, p[5], c.ws->agg, fi,
+            GNNB_HIP_TRY(launch_gine_aggregate(c.tv, c.cur, c.edge_attr, c.model->edge_dim, p.edge_w, c.model->edge_dim, p.edge_b, c.ws->agg, fi,
                                                d.gin_eps, c.hs()));
-        return c.linear1(c.rows(c.ws->agg, fi), fi, p[0], fi, p[1], nullptr, c.rows(c.ws->tmp0, fo), fo, GNNB_ACT_RELU);
+        return c.linear1(c.rows(c.ws->agg, fi), fi, p.w0, fi, p.b0, nullptr, c.rows(c.ws->tmp0, fo), fo, GNNB_ACT_RELU);
     }
     if (c.whole && options().fuse_narrow && fi <= 32)
-        GNNB_RUNG(attempt(launch_conv_gather(c.ws->t, GNNB_AGG_SUM, d.gin_eps, c.cur, fi, fi, p[0], fi, p[1], nullptr, c.ws->tmp0, fo, GNNB_ACT_RELU, c.hs()),
+        GNNB_RUNG(attempt(launch_conv_gather(c.ws->t, GNNB_AGG_SUM, d.gin_eps, c.cur, fi, fi, p.w0, fi, p.b0, nullptr, c.ws->tmp0, fo, GNNB_ACT_RELU, c.hs()),
                           "fused narrow conv"));
     if ((rc = c.aggregate(GNNB_AGG_SUM, c.cur, nullptr, c.ws->agg, fi, d.gin_eps)))
         return rc;
-    return c.linear1(c.rows(c.ws->agg, fi), fi, p[0], fi, p[1], nullptr, c.rows(c.ws->tmp0, fo), fo, GNNB_ACT_RELU);
+    return c.linear1(c.rows(c.ws->agg, fi), fi, p.w0, fi, p.b0, nullptr, c.rows(c.ws->tmp0, fo), fo, GNNB_ACT_RELU);
 }
 
 static int gin_layer(const LayerCtx &c)
 {
-    const std::vector<const float *> &p = c.model->conv[c.l];
+    const LayerWeights &p = c.model->conv[c.l];
     const int fo = c.fo;
     int rc;
     if ((rc = gin_hidden(c)))
         return rc;
-    return c.linear1(c.rows(c.ws->tmp0, fo), fo, p[2], fo, p[3], c.rows(c.skip, fo), c.rows(c.nxt, fo), fo, c.model->desc.activation);
+    return c.linear1(c.rows(c.ws->tmp0, fo), fo, p.w1, fo, p.b1, c.rows(c.skip, fo), c.rows(c.nxt, fo), fo, c.model->desc.activation);
 }
 
 static int sage_layer(const LayerCtx &c)
 {
     const gnnb_model_desc &d = c.model->desc;
-    const std::vector<const float *> &p = c.model->conv[c.l];
+    const LayerWeights &p = c.model->conv[c.l];
     const int fi = c.fi, fo = c.fo;
     int rc;
     const bool narrow = c.whole && options().fuse_narrow && 2 * fi <= 32;
     if (narrow && !c.last && c.skip == nullptr && !c.fpx) {
         // narrow input AND a layer behind it: the stage's output rows stay in LDS and the next layer's mean aggregate is
         // taken from there -- its aggregate kernel (a full read and write of [N, fo]) is not run
-        rc = attempt(launch_sage_first_mean(c.ws->t, c.cur, fi, p[0], 2 * fi, p[1], c.nxt, c.ws->agg, fo, d.activation, c.hs()), "first-layer + mean");
+        rc = attempt(launch_sage_first_mean(c.ws->t, c.cur, fi, p.w_cat, 2 * fi, p.b_cat, c.nxt, c.ws->agg, fo, d.activation, c.hs()), "first-layer + mean");
         if (rc == GNNB_OK)
             *c.mean_ready = true;
         GNNB_RUNG(rc);
     }
     if (narrow) // narrow input: [mean_j x_j | x_i] is produced inside the GEMM's A stage (K = 2 F_in)
-        GNNB_RUNG(attempt(launch_conv_gather(c.ws->t, GNNB_AGG_MEAN, 0.f, c.cur, fi, 2 * fi, p[0], 2 * fi, p[1], c.skip, c.nxt, fo, d.activation, c.hs(), fi),
+        GNNB_RUNG(attempt(launch_conv_gather(c.ws->t, GNNB_AGG_MEAN, 0.f, c.cur, fi, 2 * fi, p.w_cat, 2 * fi, p.b_cat, c.skip, c.nxt, fo, d.activation, c.hs(), fi),
                           "fused narrow conv"));
     if (!*c.mean_ready && (rc = c.aggregate(GNNB_AGG_MEAN, c.cur, nullptr, c.ws->agg, fi, 0.f)))
         return rc;
     *c.mean_ready = false;
     gnnb_gemm_seg segs[2] = {{c.rows(c.ws->agg, fi), nullptr, fi, fi}, {c.rows(c.cur, fi), nullptr, fi, fi}};
-    GNNB_RUNG(try_pooling_gemm(c, segs, 2, p[0], 2 * fi, p[1]));
-    if (c.skip_fold && p.size() >= 3 && options().fold_skip) // (slot 2: [Wl | Wr + I])
-        return c.linear(segs, 2, p[2], 2 * fi, p[1], nullptr, c.rows(c.nxt, fo), fo, d.activation);
-    return c.linear(segs, 2, p[0], 2 * fi, p[1], c.rows(c.skip, fi), c.rows(c.nxt, fo), fo, d.activation);
+    GNNB_RUNG(try_pooling_gemm(c, segs, 2, p.w_cat, 2 * fi, p.b_cat));
+    if (c.skip_fold && p.w_cat_skip && options().fold_skip) // ([Wl | Wr + I])
+        return c.linear(segs, 2, p.w_cat_skip, 2 * fi, p.b_cat, nullptr, c.rows(c.nxt, fo), fo, d.activation);
+    return c.linear(segs, 2, p.w_cat, 2 * fi, p.b_cat, c.rows(c.skip, fi), c.rows(c.nxt, fo), fo, d.activation);
 }
 
 // PNA: the source half p = x . Wb^T and its aggregate -> ws->agg: in one kernel, p on chip, where the degree-class form (no
 // destination term) and the max_graph_nodes promise (whole graphs in a stage) allow; else GEMM -> [N, F] -> aggregate
 static int pna_source_aggregate(const LayerCtx &c, bool classes)
 {
-    const std::vector<const float *> &p = c.model->conv[c.l];
+    const LayerWeights &p = c.model->conv[c.l];
     const int fi = c.fi;
     float *q = c.ws->tmp0, *pp = c.ws->tmp1;
     int rc;
     if (classes)
-        GNNB_RUNG(attempt(launch_pna_pagg(c.ws->t, c.cur, fi, p[0] + fi, 2 * fi, c.ws->agg, c.hs()), "PNA product + aggregate"));
-    if ((rc = c.linear1(c.rows(c.cur, fi), fi, p[0] + fi, 2 * fi, nullptr, nullptr, c.rows(pp, fi), fi, GNNB_ACT_NONE)))
+        GNNB_RUNG(attempt(launch_pna_pagg(c.ws->t, c.cur, fi, p.w_pre + fi, 2 * fi, c.ws->agg, c.hs()), "PNA product + aggregate"));
+    if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_pre + fi, 2 * fi, nullptr, nullptr, c.rows(pp, fi), fi, GNNB_ACT_NONE)))
         return rc;
     return c.aggregate(GNNB_AGG_PNA, pp, classes ? nullptr : q, c.ws->agg, fi, 0.f);
 }
@@ -288,12 +288,12 @@ static int pna_layer(const LayerCtx &c)
 {
     const gnnb_model_desc &d = c.model->desc;
     gnnb_workspace *const ws = c.ws;
-    const std::vector<const float *> &p = c.model->conv[c.l];
+    const LayerWeights &p = c.model->conv[c.l];
     const int fi = c.fi, fo = c.fo;
     int rc;
     // a narrow input (the first layer): the whole layer in one kernel, whole graphs staged in LDS (k_pna_first.hip)
-    if (c.whole && fi <= 12 && c.skip == nullptr && !c.fpx && p.size() >= 8 && options().pna_fold_lin && ws->prep_delta == d.pna_delta)
-        GNNB_RUNG(attempt(launch_pna_first(ws->t, c.cur, fi, p[0], p[1], p[6], 13 * fi, p[7], c.nxt, fo, d.activation, c.hs()), "narrow PNA layer"));
+    if (c.whole && fi <= 12 && c.skip == nullptr && !c.fpx && p.w_fold && options().pna_fold_lin && ws->prep_delta == d.pna_delta)
+        GNNB_RUNG(attempt(launch_pna_first(ws->t, c.cur, fi, p.w_pre, p.b_pre, p.w_fold, 13 * fi, p.b_fold, c.nxt, fo, d.activation, c.hs()), "narrow PNA layer"));
     // h_ij = Wpre [x_i || x_j] + b  ==  (Wpre[:, :F] x_i + b) + Wpre[:, F:] x_j
     float *q = ws->tmp0;
     // degree-class form (gnnb_workspace_set_max_degree; decided here: it folds the destination's pre-NN term into x's
@@ -301,9 +301,9 @@ static int pna_layer(const LayerCtx &c)
     // (the row-class GEMM addresses a row of its operands as a 32-bit byte offset on the operand's base, row * 16 fi
     // for the aggregate: the form applies while that stays below 2^32 -- 2^21 rows at fi = 128, 2^20 at fi = 256; larger
     // batches take the general form below, decided here, before anything of the layer is enqueued)
-    const bool classes = p.size() >= 10 && options().pna_fold_lin && options().pna_classes && c.whole && ws->deg_ready && c.M > 0 && !c.fpx &&
+    const bool classes = p.w_class && options().pna_fold_lin && options().pna_classes && c.whole && ws->deg_ready && c.M > 0 && !c.fpx &&
                          ws->deg_delta == d.pna_delta && fo > 32 && (uint64_t)c.M * 16 * fi + 512 <= 0xffffffffull;
-    if (!classes && (rc = c.linear1(c.rows(c.cur, fi), fi, p[0], 2 * fi, p[1], nullptr, c.rows(q, fi), fi, GNNB_ACT_NONE)))
+    if (!classes && (rc = c.linear1(c.rows(c.cur, fi), fi, p.w_pre, 2 * fi, p.b_pre, nullptr, c.rows(q, fi), fi, GNNB_ACT_NONE)))
         return rc;
     if ((rc = pna_source_aggregate(c, classes)))
         return rc;
@@ -312,14 +312,14 @@ static int pna_layer(const LayerCtx &c)
         // the rows' own places; skip + activation in the epilogue (the last layer pools in the pass behind)
         gnnb_gemm_seg s2[2] = {{c.cur, nullptr, fi, fi}, {ws->agg, nullptr, 4 * fi, 4 * fi}};
         GemmArgs g;
-        if ((rc = build_gemm(g, s2, 2, p[8], 5 * fi)))
+        if ((rc = build_gemm(g, s2, 2, p.w_class, 5 * fi)))
             return rc;
         RowClasses rcl;
         rcl.perm = ws->deg_perm;
         rcl.tile_cls = ws->deg_tile_cls;
         rcl.w_stride = (long)fo * 5 * fi;
         rcl.bias_stride = fo;
-        hipError_t he = launch_linear(g, p[8], 5 * fi, p[9], c.skip_fold ? nullptr : c.skip, c.nxt, ws->deg_max_tiles * 128, fo, d.activation,
+        hipError_t he = launch_linear(g, p.w_class, 5 * fi, p.b_class, c.skip_fold ? nullptr : c.skip, c.nxt, ws->deg_max_tiles * 128, fo, d.activation,
                                       c.hs(), nullptr, &rcl, c.sk);
         if (he == hipSuccess)
             return GNNB_OK;
@@ -331,18 +331,18 @@ static int pna_layer(const LayerCtx &c)
                              {c.rows(ws->agg, 4 * fi), nullptr, 4 * fi, 4 * fi},
                              {c.rows(ws->agg, 4 * fi), ws->t.amp + c.row_lo, 4 * fi, 4 * fi},
                              {c.rows(ws->agg, 4 * fi), ws->t.att + c.row_lo, 4 * fi, 4 * fi}};
-    if (p.size() >= 8 && options().pna_fold_lin) {
+    if (p.w_fold && options().pna_fold_lin) {
         // `lin` folded into the post-NN at upload (gnnb_model_create): one GEMM, skip + activation in its epilogue;
         // the last layer of a whole-batch run pools there too (as GraphSAGE's; PNA's own condition: the pooling epilogue
         // takes no skip operand, and this GEMM would carry one)
         if (c.skip == nullptr)
-            GNNB_RUNG(try_pooling_gemm(c, segs, 4, p[6], 13 * fi, p[7]));
-        return c.linear(segs, 4, p[6], 13 * fi, p[7], c.skip_fold ? nullptr : c.rows(c.skip, fo), c.rows(c.nxt, fo), fo, d.activation);
+            GNNB_RUNG(try_pooling_gemm(c, segs, 4, p.w_fold, 13 * fi, p.b_fold));
+        return c.linear(segs, 4, p.w_fold, 13 * fi, p.b_fold, c.skip_fold ? nullptr : c.rows(c.skip, fo), c.rows(c.nxt, fo), fo, d.activation);
     }
     float *hid = ws->tmp0; // q is dead after the aggregate
-    if ((rc = c.linear(segs, 4, p[2], 13 * fi, p[3], nullptr, c.rows(hid, fo), fo, GNNB_ACT_NONE)))
+    if ((rc = c.linear(segs, 4, p.w_post, 13 * fi, p.b_post, nullptr, c.rows(hid, fo), fo, GNNB_ACT_NONE)))
         return rc;
-    return c.linear1(c.rows(hid, fo), fo, p[4], fo, p[5], c.rows(c.skip, fo), c.rows(c.nxt, fo), fo, d.activation);
+    return c.linear1(c.rows(hid, fo), fo, p.w_lin, fo, p.b_lin, c.rows(c.skip, fo), c.rows(c.nxt, fo), fo, d.activation);
 }
 
 // The conv layers one by one (gather-aggregate + GEMM kernels) on the node rows [row_lo, N) of the prepared batch:
@@ -415,10 +415,9 @@ static hipError_t large_segment_small(const gnnb_model *model, gnnb_workspace *w
     int which = 0;
     for (int l = 0; l < d.num_layers; l++) {
         const LayerDims ld = layer_dims(d, l);
-        const std::vector<const float *> &p = model->conv[l];
+        const LayerWeights &p = model->conv[l];
         const LayerIO io = layer_io(d, ws, l, cur, which);
-        const bool gin = d.conv_type == GNNB_CONV_GIN;
-        hipError_t he = launch_conv_rows(ws->t, d.conv_type, cur, ld.fin, p[0], p[1], gin ? p[2] : nullptr, gin ? p[3] : nullptr,
+        hipError_t he = launch_conv_rows(ws->t, d.conv_type, cur, ld.fin, p.w0, p.b0, p.w1, p.b1, // (GCN: no second linear)
                                          ld.fout, io.skip, io.nxt, ws->large_n, d.activation, d.gin_eps, s);
         if (he != hipSuccess)
             return he; // (NotSupported can only come from the first layer's checks above: nothing is half done)
@@ -457,15 +456,15 @@ static hipError_t launch_conv_stack(const gnnb_model *model, gnnb_workspace *ws,
     if (!deep.gin && L == 2) { // two GCN layers, fp32: the transform-first form with 96-row stages (k_stack_zf.h)
         const bool offer = head_out != nullptr && model->head_dev != nullptr && d.mlp_num_linear <= 8 && d.mlp_activation == d.activation;
         const HeadArgs head = model_head_args(model);
-        he = launch_gcn2_zf(t, x_dev, d.in_dim, model->conv[0][0], model->conv[0][1], d.hidden_dim, model->conv[1][0],
-                            model->conv[1][1], d.out_dim, d.activation, d.pools, d.num_pools, ws->pooled, s, model->zf_w1f,
+        he = launch_gcn2_zf(t, x_dev, d.in_dim, model->conv[0].w0, model->conv[0].b0, d.hidden_dim, model->conv[1].w0,
+                            model->conv[1].b0, d.out_dim, d.activation, d.pools, d.num_pools, ws->pooled, s, model->zf_w1f,
                             offer ? &head : nullptr, offer ? model->head_dev : nullptr, offer ? head_out : nullptr, head_fused);
     }
     *path = GNNB_PATH_STACK_ZF;
     if (he == hipErrorNotSupported) {
         *path = GNNB_PATH_STACK;
-        he = launch_gcn2_fused(t, x_dev, d.in_dim, model->conv[0][0], model->conv[0][1], d.hidden_dim,
-                               model->conv[L - 1][0], model->conv[L - 1][1], d.out_dim, d.activation, d.pools,
+        he = launch_gcn2_fused(t, x_dev, d.in_dim, model->conv[0].w0, model->conv[0].b0, d.hidden_dim,
+                               model->conv[L - 1].w0, model->conv[L - 1].b0, d.out_dim, d.activation, d.pools,
                                d.num_pools, ws->pooled, s, deep);
     }
     return he;

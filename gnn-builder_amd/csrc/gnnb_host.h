@@ -1,12 +1,14 @@
 // gnnb_host.h -- what the host translation units of libgnnb_hip.so share (gnnb_model.hip: description and weight upload;
 // gnnb_runtime.hip: workspace, graph prep, stage entry points, C-ABI utilities; gnnb_ingest.hip: the PyG mini-batch entries;
 // gnnb_forward.hip: the forward): the two handle structs, the error helpers, the dimension helpers of a model description and
-// what the units take from each other.  Host only: no kernel unit includes it.
+// what the units take from each other.  Host only: no kernel unit includes it.  (The dimension helpers and the weights' named slots:
+// gnnb_weights.h, which needs no HIP header.)
 #pragma once
 
 #include <vector>
 
 #include "gnnb_internal.h"
+#include "gnnb_weights.h"
 #include "gnnb_order.h"
 #include "gnnb_edge.h"
 
@@ -23,52 +25,13 @@ int fail(int code, const char *fmt, ...);
                         __FILE__, __LINE__);                                                      \
     } while (0)
 
-struct LayerDims {
-    int fin, fout;
-};
-
-// canonical parameter tensors per conv layer (-1: unknown conv type)
-inline int conv_slots(int conv)
-{
-    switch (conv) {
-    case GNNB_CONV_GCN: return 2;
-    case GNNB_CONV_GIN: return 4;
-    case GNNB_CONV_SAGE: return 3;
-    case GNNB_CONV_PNA: return 6;
-    default: return -1;
-    }
-}
-
-// gnnbuilder/models.py:519-549
-inline LayerDims layer_dims(const gnnb_model_desc &d, int l)
-{
-    if (d.num_layers == 1)
-        return {d.in_dim, d.out_dim};
-    if (l == 0)
-        return {d.in_dim, d.hidden_dim};
-    if (l == d.num_layers - 1)
-        return {d.hidden_dim, d.out_dim};
-    return {d.hidden_dim, d.hidden_dim};
-}
-
-inline int gnn_out_width(const gnnb_model_desc &d) { return d.num_layers == 0 ? d.in_dim : d.out_dim; }
-
-// gnnbuilder/models.py:398-415
-inline void mlp_dims(const gnnb_model_desc &d, int i, int *din, int *dout)
-{
-    const int pooled = d.num_pools * gnn_out_width(d);
-    *din = (i == 0) ? pooled : d.mlp_hidden;
-    *dout = (i == d.mlp_num_linear - 1) ? d.mlp_out : d.mlp_hidden;
-}
-
 } // namespace gnnb
 
 struct gnnb_model {
     gnnb_model_desc desc;
     float *blob = nullptr; // all weights, device
     size_t blob_floats = 0;
-    // per conv layer device pointers (canonical slots; SAGE slot 0 is the fused [Wl|Wr])
-    std::vector<std::vector<const float *>> conv;
+    std::vector<gnnb::LayerWeights> conv; // per conv layer, device pointers by name (gnnb_weights.h: LayerSlots)
     std::vector<const float *> head_w, head_b;
     const float *zf_w1f = nullptr; // 2-layer GCN: layer 1's weight once more, in MFMA-fragment order (see k_gcn2_zf)
     // GIN stacks (k_gcn2_fused<GIN>): every wide matrix once more in EXECUTION order, each hidden x hidden at one stride --
@@ -78,8 +41,9 @@ struct gnnb_model {
     const float *gin_w = nullptr, *gin_b = nullptr;
     gnnb::HeadArgs *head_dev = nullptr; // the MLP head's {weights, biases, widths} once more in device memory: k_gcn2_zf reads it at the
                                         // end of a workgroup's life (by value the 42 dwords stayed in scalar registers through its stage loop)
-    int edge_dim = 0; // > 0: a GINE model (gnnb_edge_model_create) -- conv slots 4, 5 of every layer hold W_e [in, edge_dim] and b_e [in]
+    int edge_dim = 0; // > 0: a GINE model (gnnb_edge_model_create) -- every layer has edge_w [in, edge_dim] and edge_b [in]
     int device = 0;
+    ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };
 
 struct gnnb_workspace {

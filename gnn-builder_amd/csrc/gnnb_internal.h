@@ -361,8 +361,7 @@ hipError_t stream_k_scratch_init_sync(void *base);           // the same with sy
 // diagnostics: 1 = the scratch's counters are all zero and the guard region behind them is whole, 0 = not, -1 = read-back failed.
 // owned == nullptr: the standalone scratch of (current device, s), 1 when there is none yet.  Synchronises s.
 int stream_k_guard_intact(const StreamK *owned, hipStream_t s);
-constexpr int GNNB_DEG_CLASSES = 16; // in-degrees 0 .. 15 get a class each (0: PNA's scalers of degree 1, but no messages); a larger promise keeps the general form
-constexpr int GNNB_DEG_MAX = GNNB_DEG_CLASSES - 1;
+constexpr int GNNB_DEG_MAX = GNNB_DEG_CLASSES - 1; // (GNNB_DEG_CLASSES: gnnb_hip.h, beside the promise it bounds)
 // the batch's rows sorted into degree classes (k_misc.hip); work = 256 x 16 ints, perm = max_tiles * 128, tile_cls = max_tiles
 hipError_t launch_degree_classes(const BatchTables &t, int promise, int32_t *work, int32_t *perm, int32_t *tile_cls, int max_tiles,
                                  hipStream_t s);

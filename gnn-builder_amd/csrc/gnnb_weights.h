@@ -1,0 +1,371 @@
+// gnnb_weights.h -- a model's weights as the forward reads them: the named slots of a conv layer (LayerSlots), the derived forms
+// the kernels take (one helper each below) and build_weight_image, the ONE function that lays canonical and derived tensors out
+// in the blob gnnb_model_create uploads.  Pure host arithmetic on the standard library and the C ABI's description: no HIP
+// header in here, so that a plain C++ compiler builds it and tests/test_weights_host.py checks the layout, the permutations and
+// the folded sums without a GPU.
+// Reference: load_parameters once (gnnbuilder/templates/model.cpp.jinja:724-730).
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "gnnb_hip.h"
+
+namespace gnnb {
+
+struct LayerDims {
+    int fin, fout;
+};
+
+// canonical parameter tensors per conv layer (-1: unknown conv type)
+inline int conv_slots(int conv)
+{
+    switch (conv) {
+    case GNNB_CONV_GCN: return 2;
+    case GNNB_CONV_GIN: return 4;
+    case GNNB_CONV_SAGE: return 3;
+    case GNNB_CONV_PNA: return 6;
+    default: return -1;
+    }
+}
+
+// gnnbuilder/models.py:519-549
+inline LayerDims layer_dims(const gnnb_model_desc &d, int l)
+{
+    if (d.num_layers == 1)
+        return {d.in_dim, d.out_dim};
+    if (l == 0)
+        return {d.in_dim, d.hidden_dim};
+    if (l == d.num_layers - 1)
+        return {d.hidden_dim, d.out_dim};
+    return {d.hidden_dim, d.hidden_dim};
+}
+
+inline int gnn_out_width(const gnnb_model_desc &d) { return d.num_layers == 0 ? d.in_dim : d.out_dim; }
+
+// gnnbuilder/models.py:398-415
+inline void mlp_dims(const gnnb_model_desc &d, int i, int *din, int *dout)
+{
+    const int pooled = d.num_pools * gnn_out_width(d);
+    *din = (i == 0) ? pooled : d.mlp_hidden;
+    *dout = (i == d.mlp_num_linear - 1) ? d.mlp_out : d.mlp_hidden;
+}
+
+constexpr size_t NO_OFFSET = ~(size_t)0;
+// what a slot holds when the layer has no such tensor: nullptr, or NO_OFFSET in the layout
+template <typename T> constexpr T absent_slot() { return T(); }
+template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
+
+// One conv layer's tensors in the blob, by name: T = const float * in a model (LayerWeights: device pointers), size_t in the
+// layout build_weight_image returns (LayerOffsets: floats from the image's start).  A layer holds its conv type's members and
+// leaves the others absent.  The C side's one statement of what follows the canonical order of include/gnnb_hip.h
+// (gnnb_model_num_params) and models.py (canonical_param_names); in = the layer's input width, out = its output width; all
+// row-major [out][in] as torch.nn.Linear.weight.  "canonical" = tensor k of the layer as the caller passed it.
+//   GCN        w0 [out, in], b0 [out]               canonical 0, 1
+//   GIN, GINE  w0 [out, in], b0 [out]               canonical 0, 1: the first linear (ReLU behind it; hidden = out, models.py:90)
+//              w1 [out, out], b1 [out]              canonical 2, 3: the second linear
+//              edge_w [in, edge_dim], edge_b [in]   canonical 4, 5 of a GINE model (gnnb_model::edge_dim > 0): conv.lin
+//   GraphSAGE  w_cat [out, 2 in]                    derived: [Wl | Wr], canonical 0 and 2 side by side (sage_cat_weights)
+//              b_cat [out]                          canonical 1: lin_l's bias (lin_r has none); goes with either w_cat form
+//              w_cat_skip [out, 2 in]               derived: [Wl | Wr + I]; a skip middle layer with in == out, not under fpx
+//   PNA        w_pre [in, 2 in], b_pre [in]         canonical 0, 1: the pre-NN; columns [0, in) act on the destination x_i
+//              w_post [out, 13 in], b_post [out]    canonical 2, 3: the post-NN
+//              w_lin [out, out], b_lin [out]        canonical 4, 5
+//              w_fold [out, 13 in], b_fold [out]    derived: `lin` folded into the post-NN, + I on a skip middle layer with
+//                                                   in == out (pna_fold_lin); not under fpx
+//              w_class [16][out, 5 in], b_class [16][out]   derived: the degree-class form of w_fold (pna_degree_class_weights);
+//                                                   where w_fold exists and out > 32
+// (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
+template <typename T> struct LayerSlots {
+    T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
+    T edge_w = absent_slot<T>(), edge_b = absent_slot<T>();
+    T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
+    T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
+    T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
+    T w_fold = absent_slot<T>(), b_fold = absent_slot<T>(), w_class = absent_slot<T>(), b_class = absent_slot<T>();
+
+    // the same slots with f applied to each (offsets -> pointers)
+    template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
+    {
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_cat),  f(b_cat),   f(w_cat_skip), f(w_pre),
+                f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin),  f(w_fold), f(b_fold), f(w_class), f(b_class)};
+    }
+};
+using LayerWeights = LayerSlots<const float *>;
+using LayerOffsets = LayerSlots<size_t>;
+
+// where everything sits in the image (floats from its start; NO_OFFSET: the model has no such tensor)
+struct WeightLayout {
+    std::vector<LayerOffsets> conv;
+    size_t zf_w1f = NO_OFFSET;                    // gnnb_model::zf_w1f
+    size_t gin_w = NO_OFFSET, gin_b = NO_OFFSET; // gnnb_model::gin_w, gin_b
+    std::vector<size_t> head_w, head_b;
+};
+
+// host staging image of the blob: every tensor padded to a 16-byte boundary
+struct WeightImage {
+    std::vector<float> img;
+    bool fpx;
+    float q_inv, q_step, q_span, q_half;
+    explicit WeightImage(const gnnb_model_desc &d)
+        : fpx(d.fpx_w > 0), q_inv(fpx ? ldexpf(1.0f, d.fpx_w - d.fpx_i) : 1.0f), q_step(fpx ? ldexpf(1.0f, -(d.fpx_w - d.fpx_i)) : 1.0f),
+          q_span(fpx ? ldexpf(1.0f, d.fpx_i) : 1.0f), q_half(fpx ? ldexpf(1.0f, d.fpx_i - 1) : 1.0f)
+    {
+    }
+    size_t push(const float *src, size_t n) // -> offset of the tensor in the image
+    {
+        size_t off = img.size();
+        img.insert(img.end(), src, src + n);
+        if (fpx) // W_TYPE = ap_fixed<W, I>: the weights live on the grid (model.h.jinja:41-45)
+            for (size_t i = off; i < off + n; i++) {
+                float v = floorf(img[i] * q_inv) * q_step;
+                img[i] = v - q_span * floorf((v + q_half) / q_span);
+            }
+        while (img.size() % 4)
+            img.push_back(0.0f);
+        return off;
+    }
+    size_t push(const std::vector<float> &v) { return push(v.data(), v.size()); }
+};
+
+struct WeightBias { // a derived matrix and the bias that goes with it
+    std::vector<float> w, b;
+};
+
+// GraphSAGE: lin_l and lin_r fused into one [out, 2*in] matrix [Wl | Wr]; plus_identity: [Wl | Wr + I], the layer's skip
+// connection folded into the root weights
+inline std::vector<float> sage_cat_weights(const float *wl, const float *wr, size_t fo, size_t fi, bool plus_identity)
+{
+    std::vector<float> cat(fo * 2 * fi);
+    for (size_t o = 0; o < fo; o++) {
+        memcpy(&cat[o * 2 * fi], wl + o * fi, fi * sizeof(float));
+        memcpy(&cat[o * 2 * fi + fi], wr + o * fi, fi * sizeof(float));
+    }
+    if (plus_identity)
+        for (size_t o = 0; o < fo; o++)
+            cat[o * 2 * fi + fi + o] += 1.0f;
+    return cat;
+}
+
+// PNA: `lin` folded into the post-NN.  PNAConv applies them back to back with nothing in between
+// (out = W_lin (W_post [x | S] + b_post) + b_lin, gnn_builder_lib.h:2081-2157), so
+// W' = W_lin W_post [out, 13 F] and b' = W_lin b_post + b_lin (formed in double, rounded once) give the layer
+// in ONE 13F-wide GEMM whose epilogue carries the skip operand and the activation: the out x out GEMM and the
+// [N, out] hand-over between the two are gone (3 x ~55 us of a BASELINE config 4 step).  Not under the
+// fixed-point emulation: the folded matrix is not on the weight grid.
+inline WeightBias pna_fold_lin(const float *w_post, const float *b_post, const float *w_lin, const float *b_lin, size_t fi, size_t fo,
+                               bool skip_fold)
+{
+    const size_t K13 = 13 * fi;
+    std::vector<double> acc(K13);
+    WeightBias f{std::vector<float>(fo * K13), std::vector<float>(fo)};
+    for (size_t o = 0; o < fo; o++) {
+        std::fill(acc.begin(), acc.end(), 0.0);
+        double ab = (double)b_lin[o];
+        for (size_t h = 0; h < fo; h++) {
+            const double wl = (double)w_lin[o * fo + h];
+            const float *wp = w_post + h * K13;
+            for (size_t k = 0; k < K13; k++)
+                acc[k] += wl * (double)wp[k];
+            ab += wl * (double)b_post[h];
+        }
+        if (skip_fold)
+            acc[o] += 1.0; // (+ I on the x segment: the skip connection)
+        for (size_t k = 0; k < K13; k++)
+            f.w[o * K13 + k] = (float)acc[k];
+        f.b[o] = (float)ab;
+    }
+    return f;
+}
+
+// PNA, the degree-class form (gnnb_workspace_set_max_degree): for every in-degree c = 0 .. 15 the matrix
+//   ( W'_x + S_c Wq | W'_1 + amp W'_2 + att W'_3 ),  [out, 5 F],   and the bias  b' + S_c bq,
+// of the folded W' above (`folded`); amp / att as graph prep computes them (k_prep.hip: logf(d + 1) / delta and its
+// reciprocal, d = max(c, 1)).  S_c = the max + min + mean column blocks of the class's A matrix: the
+// destination's own pre-NN term q_i = Wq x_i + bq shifts max, min and mean of its messages by q_i and
+// leaves std alone (gnn_builder_lib.h:1801-1850), so it is folded into x's weights too and the q GEMM is
+// not run at all.  Class 0 (no messages: the four aggregates are 0, not q) carries no S term.
+// wq = W_pre [F, 2F]: columns [0, F) act on the destination x_i (lib:1801-1802), bias bq
+inline WeightBias pna_degree_class_weights(const WeightBias &folded, const float *wq, const float *bq, size_t fi, size_t fo, float pna_delta)
+{
+    const size_t K13 = 13 * fi, K5 = 5 * fi;
+    WeightBias c5{std::vector<float>((size_t)GNNB_DEG_CLASSES * fo * K5), std::vector<float>((size_t)GNNB_DEG_CLASSES * fo)};
+    std::vector<double> wa(4 * fi), sq(fi), sqw(fi);
+    for (int c = 0; c < GNNB_DEG_CLASSES; c++) {
+        const float lg = logf((float)std::max(c, 1) + 1.0f);
+        const double amp = (double)(lg / pna_delta), att = (double)(pna_delta / lg);
+        float *dst = &c5.w[(size_t)c * fo * K5];
+        for (size_t o = 0; o < fo; o++) {
+            const float *src = &folded.w[o * K13];
+            for (size_t k = 0; k < 4 * fi; k++)
+                wa[k] = (double)src[fi + k] + amp * (double)src[5 * fi + k] + att * (double)src[9 * fi + k];
+            for (size_t k = 0; k < 4 * fi; k++)
+                dst[o * K5 + fi + k] = (float)wa[k];
+            double bsum = (double)folded.b[o];
+            if (c > 0) {
+                for (size_t k = 0; k < fi; k++)
+                    sq[k] = wa[k] + wa[fi + k] + wa[2 * fi + k]; // S_c[o][k]: max + min + mean
+                // (S_c Wq)[o][j] = sum_k S_c[o][k] Wq[k][j], k ascending from src[j] as before, but walked
+                // along Wq's rows: the column walk (stride 2F) made a 1024-wide PNA layer's upload ~80 s
+                for (size_t j = 0; j < fi; j++)
+                    sqw[j] = (double)src[j];
+                for (size_t k = 0; k < fi; k++) {
+                    const double s = sq[k];
+                    const float *wr = wq + k * 2 * fi;
+                    for (size_t j = 0; j < fi; j++)
+                        sqw[j] += s * (double)wr[j];
+                }
+                for (size_t j = 0; j < fi; j++)
+                    dst[o * K5 + j] = (float)sqw[j];
+                for (size_t k = 0; k < fi; k++)
+                    bsum += sq[k] * (double)bq[k];
+            } else {
+                for (size_t j = 0; j < fi; j++)
+                    dst[o * K5 + j] = src[j];
+            }
+            c5.b[(size_t)c * fo + o] = (float)bsum;
+        }
+    }
+    return c5;
+}
+
+// k_gcn2_zf reads its 16-column slice of the last GCN layer's weight as MFMA B fragments: lane (li, lg) of the wave that
+// owns slice s takes W[16 s + li][16 q + 4 lg .. + 3] for q = 0 .. K/16 - 1.  Straight from the [out][in] matrix that is
+// 16 rows x 64 B per load instruction (half of every 128-B line unused, 32 MB of L2 traffic per launch over the chip);
+// a second copy in fragment order -- float4 index ((s K/16 + q) 4 + lg) 16 + li -- makes every load instruction one
+// contiguous KiB.  Rows past `out` are zero.  w1 [out_dim, K]
+inline std::vector<float> zf_fragment_order(const float *w1, int K, int out_dim)
+{
+    const int KQ = K / 16, NS = (out_dim + 15) / 16;
+    std::vector<float> frag((size_t)NS * 16 * K, 0.0f);
+    for (int s = 0; s < NS; s++)
+        for (int q = 0; q < KQ; q++)
+            for (int lg = 0; lg < 4; lg++)
+                for (int li = 0; li < 16; li++) {
+                    const int n = 16 * s + li;
+                    if (n >= out_dim)
+                        continue;
+                    for (int e = 0; e < 4; e++)
+                        frag[((((size_t)s * KQ + q) * 4 + lg) * 16 + li) * 4 + e] = w1[(size_t)n * K + 16 * q + 4 * lg + e];
+                }
+    return frag;
+}
+
+// GIN stacks: every wide matrix once more in EXECUTION order at one hidden x hidden stride, zero-padded (gnnb_model::gin_w):
+// index 0 = layer 0's second linear, 2l - 1 / 2l = layer l's first / second linear; the biases likewise.  Read from the
+// image (conv_off: the layers' canonical tensors in it), so the copies are on the fixed-point grid when the originals are.
+inline WeightBias gin_execution_order(const gnnb_model_desc &d, const std::vector<float> &img, const std::vector<LayerOffsets> &conv_off)
+{
+    const size_t h = d.hidden_dim, ho = d.out_dim;
+    const int L = d.num_layers, nm = 2 * L - 1;
+    WeightBias g{std::vector<float>((size_t)nm * h * h, 0.0f), std::vector<float>((size_t)nm * h, 0.0f)};
+    auto put = [&](int idx, size_t off_w, size_t off_b, size_t rows, size_t cols) { // [rows, cols] -> top-left of slot idx
+        for (size_t r = 0; r < rows; r++)
+            memcpy(&g.w[(size_t)idx * h * h + r * h], &img[off_w + r * cols], cols * sizeof(float));
+        memcpy(&g.b[(size_t)idx * h], &img[off_b], rows * sizeof(float));
+    };
+    put(0, conv_off[0].w1, conv_off[0].b1, L == 1 ? ho : h, L == 1 ? ho : h); // (layer 0's second linear)
+    for (int l = 1; l < L; l++) {
+        const size_t fo = l == L - 1 ? ho : h;
+        put(2 * l - 1, conv_off[l].w0, conv_off[l].b0, fo, h); // Wa [fo, h]
+        put(2 * l, conv_off[l].w1, conv_off[l].b1, fo, fo);     // Wb [fo, fo]
+    }
+    return g;
+}
+
+// One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; a GINE model's two behind GIN's four) and the
+// derived forms its conv type has, pushed in the order of LayerSlots' comment -> their offsets in the image
+inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim)
+{
+    const LayerDims ld = layer_dims(d, l);
+    const size_t fi = ld.fin, fo = ld.fout;
+    // the layer's skip connection (middle layers: y = conv(x) + x, models.py:562-564) where x itself is an operand of
+    // the layer's GEMM (GraphSAGE's root term, PNA's x segment): folded into that operand's weights as + I, so that the
+    // [N, out] skip operand is not read again in the epilogue (45 of 293 us of a 128-wide PNA layer's GEMM went there:
+    // 32-byte pieces of 128-byte lines)
+    const bool skip_fold = d.skip && l != 0 && l != d.num_layers - 1 && fi == fo && !im.fpx;
+    LayerOffsets off;
+    switch (d.conv_type) {
+    case GNNB_CONV_GCN:
+        off.w0 = im.push(p[0], fo * fi);
+        off.b0 = im.push(p[1], fo);
+        break;
+    case GNNB_CONV_GIN: // hidden = out_channels (models.py:90)
+        off.w0 = im.push(p[0], fo * fi);
+        off.b0 = im.push(p[1], fo);
+        off.w1 = im.push(p[2], fo * fo);
+        off.b1 = im.push(p[3], fo);
+        if (edge_dim > 0) {
+            off.edge_w = im.push(p[4], fi * (size_t)edge_dim);
+            off.edge_b = im.push(p[5], fi);
+        }
+        break;
+    case GNNB_CONV_SAGE: // {Wl, bl, Wr}
+        off.w_cat = im.push(sage_cat_weights(p[0], p[2], fo, fi, false));
+        off.b_cat = im.push(p[1], fo);
+        if (skip_fold)
+            off.w_cat_skip = im.push(sage_cat_weights(p[0], p[2], fo, fi, true));
+        break;
+    case GNNB_CONV_PNA:
+        off.w_pre = im.push(p[0], fi * 2 * fi);
+        off.b_pre = im.push(p[1], fi);
+        off.w_post = im.push(p[2], fo * 13 * fi);
+        off.b_post = im.push(p[3], fo);
+        off.w_lin = im.push(p[4], fo * fo);
+        off.b_lin = im.push(p[5], fo);
+        if (!im.fpx) {
+            const WeightBias folded = pna_fold_lin(p[2], p[3], p[4], p[5], fi, fo, skip_fold);
+            off.w_fold = im.push(folded.w);
+            off.b_fold = im.push(folded.b);
+            if (fo > 32) { // (any input width: whole 32-wide chunks take k_linear_dma's row-class mode, others the generic kernel's)
+                const WeightBias classes = pna_degree_class_weights(folded, p[0], p[1], fi, fo, d.pna_delta);
+                off.w_class = im.push(classes.w);
+                off.b_class = im.push(classes.b);
+            }
+        }
+        break;
+    }
+    return off;
+}
+
+struct BuiltWeights {
+    std::vector<float> img;
+    WeightLayout layout;
+};
+
+// The blob of a validated description (gnnb_model_create's checks have passed; edge_dim > 0: a GINE model) from the caller's
+// tensors in canonical order, and where everything is in it.  Blob order: conv layers (canonical + derived tensors), k_gcn2_zf's
+// fragment copy, the GIN stack's copies, the head.
+inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params)
+{
+    WeightImage im(d);
+    WeightLayout lo;
+    lo.conv.resize(d.num_layers);
+    const int slots = conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
+    int pi = 0;
+    for (int l = 0; l < d.num_layers; l++, pi += slots)
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim);
+    const bool have_w1f = d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
+    if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
+        lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));
+    // (a GINE model takes no stack kernel: no execution-order copy)
+    const bool have_gin = edge_dim == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
+                          d.out_dim <= d.hidden_dim && d.out_dim % 4 == 0;
+    if (have_gin) {
+        const WeightBias g = gin_execution_order(d, im.img, lo.conv);
+        lo.gin_w = im.push(g.w);
+        lo.gin_b = im.push(g.b);
+    }
+    for (int i = 0; i < d.mlp_num_linear; i++, pi += 2) {
+        int din, dout;
+        mlp_dims(d, i, &din, &dout);
+        lo.head_w.push_back(im.push(host_params[pi], (size_t)din * dout));
+        lo.head_b.push_back(im.push(host_params[pi + 1], (size_t)dout));
+    }
+    return {std::move(im.img), std::move(lo)};
+}
+
+} // namespace gnnb

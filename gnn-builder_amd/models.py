@@ -573,7 +573,8 @@ class GNNModel(nn.Module):
 
     def canonical_param_names(self) -> List[str]:
         """Flat parameter names (``layer_parameter_names_flat`` style) in the order the C ABI's
-        ``gnnb_model_create`` expects: conv layers first, then the head."""
+        ``gnnb_model_create`` expects: conv layers first, then the head.  (The C side's statement of the same order, and of
+        the member each tensor is read under: ``LayerSlots`` in csrc/gnnb_weights.h.)"""
         per_conv = {
             "gcn": ["conv_lin_weight", "conv_bias"],
             "gin": ["mlp_linear_0_weight", "mlp_linear_0_bias", "mlp_linear_1_weight", "mlp_linear_1_bias"],

@@ -130,7 +130,9 @@ int gnnb_stream_sync(void *stream);
  *                   SAGE {Wl[out,in], bl[out], Wr[out,in]}
  *                   PNA  {Wpre[in,2in], bpre[in], Wpost[out,13in], bpost[out], Wlin[out,out], blin[out]}
  *   then per head linear {W[out,in], b[out]}.
- * All row-major [out][in] fp32 = torch.nn.Linear.weight (gnn_builder_lib.h:40-45). */
+ * All row-major [out][in] fp32 = torch.nn.Linear.weight (gnn_builder_lib.h:40-45).
+ * (The library's own statement of which tensor is which, and of the forms it derives from them: LayerSlots in
+ * csrc/gnnb_weights.h.) */
 int gnnb_model_num_params(const gnnb_model_desc *desc);
 /* Copies the weights to the device once (the reference's copy_parameters_flag=1 call,
  * model.cpp.jinja:724-730).  host_params[i] points at tensor i (host memory). */
@@ -166,6 +168,8 @@ int gnnb_workspace_set_max_graph_nodes(gnnb_workspace *ws, int n);
  * stay below 2^32 (the class GEMM's 32-bit row offsets: up to 2^21 - 1 rows at width 128, 2^20 - 1 at 256); larger
  * batches run the general form, with the same results.  VALIDATED on the device by every graph prep like the node
  * promise (flag 32 of gnnb_workspace_check).  Other conv types ignore it. */
+#define GNNB_DEG_CLASSES 16 /* in-degrees 0 .. 15 get a class each (0: PNA's scalers of degree 1, but no messages); a larger
+                             * promise keeps the general form */
 int gnnb_workspace_set_max_degree(gnnb_workspace *ws, int d);
 
 /* Which kernels the LAST forward on this workspace ran (diagnostics / benchmarks: the answer does not change any
