@@ -73,6 +73,41 @@ def edge_batch(graphs, fin, seed, hub=True):
     return pack_graphs(gs[:graphs // 2] + extra + gs[graphs // 2:])
 
 
+STAR_IN_DEGREES = (0, 1, 3, 4, 5, 8, 9, 63, 64, 65, 66, 127, 128, 129, 257, 300, 1200)
+
+
+def star_graph(n, fin, in_degrees, seed):
+    """``n`` nodes; node ``i`` has exactly ``in_degrees[i]`` in-edges (none behind the list), sources drawn from the whole
+    graph (duplicates and self loops occur), the edges shuffled."""
+    rng = np.random.default_rng(seed)
+    dst = np.repeat(np.arange(len(in_degrees)), in_degrees)
+    coo = np.stack([rng.integers(0, n, len(dst)), dst], 1)
+    return rng.uniform(-1, 1, (n, fin)).astype(np.float32), coo[rng.permutation(len(coo))].astype(np.int32)
+
+
+def sweep_batch(graphs, fin, seed):
+    """``graphs`` QM9-shaped molecules and three 400-node ``star_graph``s of ``STAR_IN_DEGREES`` -- the first graph, one near
+    the middle (its list reversed: the long rows land in other lane groups) and the last graph -- with an empty and a
+    one-node graph between the others; features uniform(-1, 1) of width ``fin``.  Returns (batch, the stars' graph ids)."""
+    from gnnbuilder_amd.batching import pack_graphs
+    b = synthetic.make_batch("qm9", graphs, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    gs = [(rng.uniform(-1, 1, (b.graph(g)[0].shape[0], fin)).astype(np.float32), b.graph(g)[1]) for g in range(b.num_graphs)]
+    stars = [star_graph(400, fin, STAR_IN_DEGREES[::-1] if k == 1 else STAR_IN_DEGREES, seed + 10 + k) for k in range(3)]
+    third, half = graphs // 3, graphs // 2
+    parts = [stars[0]] + gs[:third] + [EMPTY(fin)] + gs[third:half] + [stars[1]] + gs[half:2 * third] + [ONE(fin)] + gs[2 * third:] \
+        + [stars[2]]
+    return pack_graphs(parts), np.array([0, half + 2, len(parts) - 1])
+
+
+def sub_edge_rows(batch, graph_ids):
+    """The edges of graphs ``graph_ids`` (increasing) as rows of ``batch.coo``, in ``sub_batch``'s order: what selects the
+    sub-batch's rows of a per-edge array."""
+    gids = np.asarray(graph_ids, np.int64)
+    e0, esz = batch.edge_ptr[gids].astype(np.int64), np.diff(batch.edge_ptr).astype(np.int64)[gids]
+    return np.repeat(e0 - np.concatenate([[0], np.cumsum(esz)[:-1]]), esz) + np.arange(esz.sum())
+
+
 def grid_features(n, w, seed):
     """uniform(-1, 1) rounded to multiples of 1/4, plus noise below 1e-3: two messages of a column differ by < 2e-3 or by
     > 0.24, so no PNA variance lies near PyG's 1e-5 threshold (the std jumps there; float64 and fp32 could legitimately
