@@ -550,9 +550,10 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
     // ---- P0: A0[i][f] = sum_j x_j[f] dinv_i dinv_j + x_i[f] dinv_i^2   (CSR order, self last) and the per-row record
     // for P1: {byte offsets of the 4 inline neighbour rows in H}{coefficients dinv_i dinv_j, 0 past the degree}
     // {dinv_i^2, rp0, deg, dinv_i}.  Eight lanes per row, lane l8 takes features l8, l8 + 8, ...; a wave pass = 8 rows;
-    // wave-pass p of the stage is done by wave (pstart + p) mod 8.  Every LDS load is unconditional (unused neighbour
-    // slots alias the row itself, inactive lanes read row 0) and the degree only selects.
-    auto phase_p0 = [&](const ZfStage &st, int bb, int tv, int pstart) {
+    // wave-pass p of the stage is done by wave (pstart + p) mod 8; a wave's next pass is `pstep` further (the number of
+    // waves the passes are dealt over: all of them, or the stage's idle ones -- see the call in the stage loop).  Every LDS
+    // load is unconditional (unused neighbour slots alias the row itself, inactive lanes read row 0) and the degree only selects.
+    auto phase_p0 = [&](const ZfStage &st, int bb, int tv, int pstart, int pstep) {
         constexpr int T0 = LD0 / 8;
         const float *xs = reinterpret_cast<const float *>(smem);
         const int4 *srec = reinterpret_cast<const int4 *>(smem + xs_b);
@@ -564,7 +565,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
         const int wv = __builtin_amdgcn_readfirstlane(tv >> 6), l8 = tv & 7, r8 = (tv >> 3) & 7;
         const int rows = st.rows, nb = st.nb;
         const int npass = (rows + 7) >> 3;
-        for (int p = (wv - pstart) & (G2_NW - 1); p < npass; p += G2_NW) {
+        for (int p = (wv - pstart) & (G2_NW - 1); p < npass; p += pstep) {
             const int i = p * 8 + r8;
             const bool active = i < rows;
             const int ic = active ? i : 0;
@@ -646,7 +647,7 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
     if (dbg & 64)
         return; // (launch + tables + weights + first DMA landed)
 #endif
-    phase_p0(cur, 0, tid, 0);
+    phase_p0(cur, 0, tid, 0, G2_NW);
     // (the W1 slice, first needed by M1: its loads had the whole prologue to land; pinned HERE so that no wait for it
     // is left inside the stage loop -- see the note on w0r above)
 #pragma unroll
@@ -846,10 +847,14 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
         {
             const int nv = h1p >> 2; // float4 chunks per row
             const bool pow2 = (nv & (nv - 1)) == 0;
-            // (column parts only while the tasks fill at most HALF of the waves: the phase is bound by the instructions the
-            // SIMDs have to issue -- shared with the MFMA stream of the co-resident workgroup --, not by the longest wave,
-            // and every task pays ~150 instructions of set-up, combine and stores: one part per graph for the four or
-            // five graphs of a BASELINE config 2 stage, 42.4 instead of 43.3 us)
+            // (column parts only while the tasks fill at most HALF of the waves: every task pays ~150 instructions of set-up,
+            // combine and stores, and the phase is bound by the instructions the SIMDs have to issue.  On the 96-row shape
+            // they are shared with the MFMA stream of the co-resident workgroup: one part per graph for the four or five
+            // graphs of a BASELINE config 2 stage, 42.4 instead of 43.3 us.  On the wide shape nothing co-resides and the
+            // round-7 probe shows both sides of it: a graph wave's P1 is 5.9-6.6 k cycles of which the row walk
+            // is 4.2-4.6 k, the end barrier still waits 1.6-2.3 k for the stage's largest graph -- yet shortening one wave's
+            // chain by hiding an LDS round trip per pass bought nothing, while taking P0' off the graph waves --
+            // fewer instructions on the SIMDs that carry them -- took 0.6 k cycles off the stage)
             // (round 4, wide shape: letting the parts fill ALL sixteen waves -- eight graphs x two parts -- is 0.25 us SLOWER,
             // 40.15 vs 39.9 us: the row walk of a task shortens from 4.1 k to 2.9 k cycles, but every task pays its ~1.9 k
             // cycles of set-up, combine and stores, and the next stage's P0 loses its idle waves)
@@ -898,7 +903,9 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
                 // Row loop, written for instruction count (in this phase every instruction of the wave is on the
                 // workgroup's critical path, and VALU issue is what the phase is bound by): running pointers instead of
                 // per-row address arithmetic, no software prefetch (its register rotation cost ten moves per row; the other
-                // waves of the SIMD cover the two LDS round trips), full passes without predication and one predicated
+                // waves of the SIMD cover the two LDS round trips -- round 7 measured that again with the next pass's
+                // neighbour offsets requested into the dead `ja` registers behind the third neighbour term, the earliest
+                // place 96 registers allow: 37.78 vs 37.66 us per step), full passes without predication and one predicated
                 // tail pass, maxima through v_max_f32 directly (fmaxf adds a canonicalising v_max per operand).
                 const char *prec = reinterpret_cast<const char *>(REC) + (r0g + sr) * STACK_ROW_REC_B;
                 const char *pself = Hl + (r0g + sr) * ldhb;
@@ -1057,9 +1064,23 @@ __global__ __launch_bounds__(NW * 64, (zf_waves_per_simd<ACT, KQ0, KQ1, MX, HEAD
         ZF_PT(7);
 
         // ---- P0 of the NEXT stage (its rows landed before the last barrier but one), starting on the first wave that
-        // had no graph to reduce
-        if (nxt.ok && ZF_ON(1))
-            phase_p0(nxt, b ^ 1, tv, (ngr << csl) & (G2_NW - 1));
+        // had no graph to reduce.  When at least a quarter of the waves have no P1 task, the passes are dealt over THOSE waves
+        // only and a wave that walked a graph goes straight to the end barrier: the graph waves are the stage's critical
+        // chain (the end barrier waits for the largest graph), the idle ones wait thousands of cycles for them, and the SIMDs
+        // that carry fewer tasks are the ones with more idle waves.  Round robin over all waves put one pass (of ~22) behind
+        // every row walk.  Otherwise -- more tasks than that, or tasks that wrap -- the passes go round robin over all waves
+        // as before.  Measured at BASELINE config 2 (8-10 tasks per stage, so "from 8 idle waves on" covers the 8-task stages
+        // only and "from 4 on" every stage; us per step of bench.py, medians of five rotated runs, the 8 / 4 comparison on
+        // builds that also carried the dropped offset prefetch of DESIGN 8): all waves 37.66; from 8 on 37.55; from 4 on
+        // 37.32 -- the rule pays on every stage it reaches, so the lower condition stays; without the prefetch 37.69 -> 37.25
+        // (profiles/r07_c2_zf_p1_bench.json).  Fewer than 4 idle waves do not occur at config 2: not measured, old dealing.
+        // The 96-row shape (8 waves) gets the same rule: 49.05 -> 48.54 us per step at config 2.
+        {
+            const int ntask = ngr << csl;
+            const bool idle_only = ntask <= G2_NW - G2_NW / 4;
+            if (nxt.ok && ZF_ON(1) && (!idle_only || wv >= ntask))
+                phase_p0(nxt, b ^ 1, tv, ntask & (G2_NW - 1), idle_only ? G2_NW - ntask : G2_NW);
+        }
         ZF_PT(8);
         // the stage after next: planned by ONE wave (executed by all sixteen the plan was a tenth of the kernel's vector
         // instructions), handed over through LDS
