@@ -28,7 +28,7 @@ import jinja2
 import numpy as np
 import torch
 
-from .models import GINEConv_GNNB, GNNModel
+from .models import GINEConv_GNNB, GNNModel, PNAEConv_GNNB
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
 CURRENT_DIR = Path(__file__).resolve().parent
@@ -93,6 +93,11 @@ class Project:
                 "Project does not generate GINE designs: the generated shim, the templates and the tb_data format carry no edge "
                 "attributes (the reference's emitter has a TODO there, model.cpp.jinja:143-144); run the model through "
                 "runtime.CompiledModel.from_model(model, ...).forward_edges / forward_pyg_edges")
+        if getattr(model, "gnn_conv", None) is PNAEConv_GNNB:
+            raise NotImplementedError(
+                "Project does not generate PNAE designs (PNA with edge features): the generated shim, the templates and the tb_data "
+                "format carry no edge attributes; run the model through runtime.CompiledModel.from_model(model, ...).forward_edges / "
+                "forward_pyg_edges")
         self.model = model
         self.dataset = dataset
         self.name = name

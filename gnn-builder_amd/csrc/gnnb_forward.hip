@@ -290,9 +290,11 @@ static int pna_layer(const LayerCtx &c)
     gnnb_workspace *const ws = c.ws;
     const LayerWeights &p = c.model->conv[c.l];
     const int fi = c.fi, fo = c.fo;
+    const int edge_dim = c.model->edge_dim;
+    const int ldpre = (edge_dim ? 3 : 2) * fi; // w_pre's row stride: [Wa | Wb], and | Wc of a model with edge features behind them
     int rc;
     // a narrow input (the first layer): the whole layer in one kernel, whole graphs staged in LDS (k_pna_first.hip)
-    if (c.whole && fi <= 12 && c.skip == nullptr && !c.fpx && p.w_fold && options().pna_fold_lin && ws->prep_delta == d.pna_delta)
+    if (!edge_dim && c.whole && fi <= 12 && c.skip == nullptr && !c.fpx && p.w_fold && options().pna_fold_lin && ws->prep_delta == d.pna_delta)
         GNNB_RUNG(attempt(launch_pna_first(ws->t, c.cur, fi, p.w_pre, p.b_pre, p.w_fold, 13 * fi, p.b_fold, c.nxt, fo, d.activation, c.hs()), "narrow PNA layer"));
     // h_ij = Wpre [x_i || x_j] + b  ==  (Wpre[:, :F] x_i + b) + Wpre[:, F:] x_j
     float *q = ws->tmp0;
@@ -301,11 +303,20 @@ static int pna_layer(const LayerCtx &c)
     // (the row-class GEMM addresses a row of its operands as a 32-bit byte offset on the operand's base, row * 16 fi
     // for the aggregate: the form applies while that stays below 2^32 -- 2^21 rows at fi = 128, 2^20 at fi = 256; larger
     // batches take the general form below, decided here, before anything of the layer is enqueued)
-    const bool classes = p.w_class && options().pna_fold_lin && options().pna_classes && c.whole && ws->deg_ready && c.M > 0 && !c.fpx &&
+    const bool classes = !edge_dim && p.w_class && options().pna_fold_lin && options().pna_classes && c.whole && ws->deg_ready && c.M > 0 && !c.fpx &&
                          ws->deg_delta == d.pna_delta && fo > 32 && (uint64_t)c.M * 16 * fi + 512 <= 0xffffffffull;
-    if (!classes && (rc = c.linear1(c.rows(c.cur, fi), fi, p.w_pre, 2 * fi, p.b_pre, nullptr, c.rows(q, fi), fi, GNNB_ACT_NONE)))
+    if (!classes && (rc = c.linear1(c.rows(c.cur, fi), fi, p.w_pre, ldpre, p.b_pre, nullptr, c.rows(q, fi), fi, GNNB_ACT_NONE)))
         return rc;
-    if ((rc = pna_source_aggregate(c, classes)))
+    if (edge_dim) {
+        // PNA with edge features: h_ij = q_i + p_j + (W_e e_ij + b_e) -- the p GEMM, then k_pna_edge_aggregate forms the edge term on
+        // chip (edge_w = Wc W_enc [fi, edge_dim], edge_b = Wc b_enc: gnnb_weights.h); none of the fused rungs, no class form;
+        // everything behind the aggregate is PNA's
+        float *pp = ws->tmp1;
+        if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_pre + fi, ldpre, nullptr, nullptr, c.rows(pp, fi), fi, GNNB_ACT_NONE)))
+            return rc;
+        if (c.M > 0)
+            GNNB_HIP_TRY(launch_pna_edge_aggregate(c.tv, pp, q, c.edge_attr, edge_dim, p.edge_w, edge_dim, p.edge_b, ws->agg, fi, c.hs()));
+    } else if ((rc = pna_source_aggregate(c, classes)))
         return rc;
     if (classes) {
         // degree-class form (gnnb_workspace_set_max_degree): [x | A] . W_class^T over the class-sorted rows, written to

@@ -11,6 +11,7 @@
 #include "gnnb_weights.h"
 #include "gnnb_order.h"
 #include "gnnb_edge.h"
+#include "gnnb_pna_edge.h"
 
 namespace gnnb {
 
@@ -41,7 +42,7 @@ struct gnnb_model {
     const float *gin_w = nullptr, *gin_b = nullptr;
     gnnb::HeadArgs *head_dev = nullptr; // the MLP head's {weights, biases, widths} once more in device memory: k_gcn2_zf reads it at the
                                         // end of a workgroup's life (by value the 42 dwords stayed in scalar registers through its stage loop)
-    int edge_dim = 0; // > 0: a GINE model (gnnb_edge_model_create) -- every layer has edge_w [in, edge_dim] and edge_b [in]
+    int edge_dim = 0; // > 0: a GINE model (gnnb_edge_model_create) or PNA with edge features (gnnb_pna_edge_model_create: desc.conv_type says which) -- every layer has edge_w [in, edge_dim] and edge_b [in]
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };

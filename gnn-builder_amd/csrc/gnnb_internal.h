@@ -304,6 +304,10 @@ hipError_t launch_aggregate_edges(const BatchTables &t, const float *x, const fl
 // [E, edge_dim] in COO order (edge_dim 1 .. 16), we [width, ldwe >= edge_dim], be [width].  hipErrorInvalidValue: nothing launched
 hipError_t launch_gine_aggregate(const BatchTables &t, const float *x, const float *edge_attr, int edge_dim, const float *we, int ldwe,
                                  const float *be, float *out, int width, float eps, hipStream_t s);
+// PNA with edge features (k_pna_edge.hip): out [N, 4 width] = max | min | mean | std over a row's in-edges of q_i + p_j + we . edge_attr[edge] + be,
+// in launch_aggregate(GNNB_AGG_PNA)'s layout; p [N, width], q [N, width] or nullptr (no destination term), the rest as above
+hipError_t launch_pna_edge_aggregate(const BatchTables &t, const float *p, const float *q, const float *edge_attr, int edge_dim, const float *we,
+                                     int ldwe, const float *be, float *out, int width, hipStream_t s);
 // the ingest's edge attributes in COO row order (k_ingest.hip): out[i] = edge_attr[state[INGEST_STATE_UNSORTED] ? idx[i] : i]; idx:
 // the general path's sorted-position -> input-edge array (nullptr: that path was not launched), state: IngestParams::state
 hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,

@@ -73,31 +73,34 @@ HeadArgs gnnb::model_head_args(const gnnb_model *model)
 
 namespace {
 
-// parameter tensors of a model; edge_dim > 0: a GINE model (two more per conv layer), which GIN descriptions without the
-// fixed-point emulation have
-int count_params(const gnnb_model_desc *desc, int edge_dim)
+// parameter tensors of a model; edge_dim > 0: an edge model (two more per conv layer), which descriptions of conv type `base` --
+// GIN: a GINE model (gnnb_edge.h), PNA: PNA with edge features (gnnb_pna_edge.h) -- without the fixed-point emulation have
+int count_params(const gnnb_model_desc *desc, int edge_dim, int base = GNNB_CONV_GIN)
 {
     int rc = validate_desc(desc);
     if (rc != GNNB_OK)
         return rc;
     if (edge_dim != 0) {
+        const char *const kind = base == GNNB_CONV_PNA ? "PNA edge" : "GINE";
         if (edge_dim < 1 || edge_dim > 16)
-            return fail(GNNB_ERR_INVALID, "edge_dim %d: a GINE model takes 1 .. 16 edge attributes", edge_dim);
-        if (desc->conv_type != GNNB_CONV_GIN)
-            return fail(GNNB_ERR_INVALID, "a GINE model's description is a GIN description (conv_type %d given)", desc->conv_type);
+            return fail(GNNB_ERR_INVALID, "edge_dim %d: a %s model takes 1 .. 16 edge attributes", edge_dim, kind);
+        if (desc->conv_type != base)
+            return fail(GNNB_ERR_INVALID, "a %s model's description is a %s description (conv_type %d given)", kind,
+                        base == GNNB_CONV_PNA ? "PNA" : "GIN", desc->conv_type);
         if (desc->fpx_w != 0)
-            return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover GINE models (fpx_w must be 0)");
+            return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover %s models (fpx_w must be 0)", kind);
     }
     return (conv_slots(desc->conv_type) + (edge_dim ? 2 : 0)) * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
-// gnnb_model_create and gnnb_edge_model_create (edge_dim > 0)
-int model_create(const gnnb_model_desc *desc, int edge_dim, const float *const *host_params, int num_params, gnnb_model **out_model)
+// gnnb_model_create, and gnnb_edge_model_create / gnnb_pna_edge_model_create (edge_dim > 0, base = GIN / PNA)
+int model_create(const gnnb_model_desc *desc, int edge_dim, const float *const *host_params, int num_params, gnnb_model **out_model,
+                 int base = GNNB_CONV_GIN)
 {
     if (!out_model)
         return fail(GNNB_ERR_INVALID, "null out_model");
     *out_model = nullptr;
-    int expect = count_params(desc, edge_dim);
+    int expect = count_params(desc, edge_dim, base);
     if (expect < 0)
         return expect;
     if (num_params != expect || !host_params)
@@ -176,6 +179,23 @@ int gnnb_edge_model_create(const gnnb_model_desc *desc, int edge_dim, const floa
     if (edge_dim == 0)
         return fail(GNNB_ERR_INVALID, "edge_dim 0: a GINE model takes 1 .. 16 edge attributes (gnnb_model_create: models without)");
     return model_create(desc, edge_dim, host_params, num_params, out_model);
+}
+
+int gnnb_pna_edge_model_num_params(const gnnb_model_desc *desc, int edge_dim)
+{
+    if (edge_dim == 0)
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a PNA edge model takes 1 .. 16 edge attributes (gnnb_model_num_params: models without)");
+    return count_params(desc, edge_dim, GNNB_CONV_PNA);
+}
+
+int gnnb_pna_edge_model_create(const gnnb_model_desc *desc, int edge_dim, const float *const *host_params, int num_params,
+                               gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (edge_dim == 0)
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a PNA edge model takes 1 .. 16 edge attributes (gnnb_model_create: models without)");
+    return model_create(desc, edge_dim, host_params, num_params, out_model, GNNB_CONV_PNA);
 }
 
 int gnnb_model_edge_dim(const gnnb_model *model) { return model ? model->edge_dim : 0; }

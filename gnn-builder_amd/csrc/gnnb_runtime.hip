@@ -1,5 +1,5 @@
 // gnnb_runtime.hip -- host side of libgnnb_hip.so: errors and options, the workspace handle, graph prep and its plan, the
-// stage entry points of the C ABI declared in include/gnnb_hip.h and gnnb_edge.h (gnnb_aggregate, gnnb_linear, gnnb_global_pool
+// stage entry points of the C ABI declared in include/gnnb_hip.h, gnnb_edge.h and gnnb_pna_edge.h (gnnb_aggregate, gnnb_linear, gnnb_global_pool
 // ...), the timed loops and the utilities.  The forward -- which kernels run, in which order -- is gnnb_forward.hip; the PyG
 // mini-batch entries (ingest, ordered ingest, edge attributes) and the workspace's add-on allocations are gnnb_ingest.hip.
 //
@@ -351,7 +351,7 @@ static StackKernel promised_stack_kernel(const gnnb_workspace *ws)
 static bool wants_degree_classes(const gnnb_workspace *ws)
 {
     return ws->desc.conv_type == GNNB_CONV_PNA && ws->max_degree > 0 && ws->max_degree <= GNNB_DEG_MAX && options().pna_classes && ws->deg_perm &&
-           ws->large_g < 0 && ws->desc.fpx_w <= 0;
+           ws->large_g < 0 && ws->desc.fpx_w <= 0 && ws->edge_dim == 0; // (PNA with edge features takes no class form)
 }
 
 // The stage-cut planner MAY run behind the tables: the option is on and the workspace was created with its scratch.  (Coarse on
@@ -678,6 +678,18 @@ int gnnb_aggregate_edges_fused(gnnb_workspace *ws, const float *x_dev, const flo
         (ws->t.num_edges > 0 && !edge_attr_dev))
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_edges_fused (edge_dim 1 .. 16, ldwe >= edge_dim)");
     GNNB_HIP_TRY(launch_gine_aggregate(ws->t, x_dev, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, out_dev, width, eps, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_pna_edges(gnnb_workspace *ws, const float *p_dev, const float *q_dev, const float *edge_attr_dev, int edge_dim,
+                             const float *we_dev, int ldwe, const float *be_dev, float *out_dev, int width, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_pna_edges needs a prepared batch (gnnb_graph_prep)");
+    if (!p_dev || !out_dev || !we_dev || !be_dev || width < 1 || edge_dim < 1 || edge_dim > 16 || ldwe < edge_dim ||
+        (ws->t.num_edges > 0 && !edge_attr_dev))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_pna_edges (edge_dim 1 .. 16, ldwe >= edge_dim)");
+    GNNB_HIP_TRY(launch_pna_edge_aggregate(ws->t, p_dev, q_dev, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, out_dev, width, (hipStream_t)stream));
     return GNNB_OK;
 }
 

@@ -78,6 +78,11 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //                                                   in == out (pna_fold_lin); not under fpx
 //              w_class [16][out, 5 in], b_class [16][out]   derived: the degree-class form of w_fold (pna_degree_class_weights);
 //                                                   where w_fold exists and out > 32
+//   PNA + edges  (gnnb_model::edge_dim > 0, gnnb_pna_edge_model_create) PNA's slots with a three-block pre-NN, and
+//              w_pre [in, 3 in]                     canonical 0: columns [2 in, 3 in) = W_c act on the encoded edge attributes
+//              edge_w [in, edge_dim], edge_b [in]   derived from canonical 6, 7 (conv.edge_encoder): W_c W_enc and W_c b_enc
+//                                                   (pna_edge_projection) -- what k_pna_edge_aggregate adds to q_i + p_j
+//              no w_class / b_class: such a model does not take the degree-class form
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
@@ -232,6 +237,31 @@ inline WeightBias pna_degree_class_weights(const WeightBias &folded, const float
     return c5;
 }
 
+// PNA with edge features: the pre-NN is linear, so its third column block W_c = W_pre[:, 2F:3F] and the edge encoder collapse into
+// ONE projection of the raw attributes, pre_nn([x_i | x_j | W_enc e + b_enc]) = (Wa x_i + b) + Wb x_j + (W_c W_enc) e + W_c b_enc:
+//   w [F, edge_dim] = W_c W_enc,   b [F] = W_c b_enc      (formed in double, rounded once)
+// w_pre [F, 3F], w_enc [F, edge_dim], b_enc [F]
+inline WeightBias pna_edge_projection(const float *w_pre, const float *w_enc, const float *b_enc, size_t fi, size_t edge_dim)
+{
+    WeightBias e{std::vector<float>(fi * edge_dim), std::vector<float>(fi)};
+    std::vector<double> acc(edge_dim);
+    for (size_t o = 0; o < fi; o++) {
+        const float *wc = w_pre + o * 3 * fi + 2 * fi;
+        std::fill(acc.begin(), acc.end(), 0.0);
+        double ab = 0.0;
+        for (size_t h = 0; h < fi; h++) {
+            const double c = (double)wc[h];
+            for (size_t k = 0; k < edge_dim; k++)
+                acc[k] += c * (double)w_enc[h * edge_dim + k];
+            ab += c * (double)b_enc[h];
+        }
+        for (size_t k = 0; k < edge_dim; k++)
+            e.w[o * edge_dim + k] = (float)acc[k];
+        e.b[o] = (float)ab;
+    }
+    return e;
+}
+
 // k_gcn2_zf reads its 16-column slice of the last GCN layer's weight as MFMA B fragments: lane (li, lg) of the wave that
 // owns slice s takes W[16 s + li][16 q + 4 lg .. + 3] for q = 0 .. K/16 - 1.  Straight from the [out][in] matrix that is
 // 16 rows x 64 B per load instruction (half of every 128-B line unused, 32 MB of L2 traffic per launch over the chip);
@@ -276,7 +306,7 @@ inline WeightBias gin_execution_order(const gnnb_model_desc &d, const std::vecto
     return g;
 }
 
-// One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; a GINE model's two behind GIN's four) and the
+// One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six) and the
 // derived forms its conv type has, pushed in the order of LayerSlots' comment -> their offsets in the image
 inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim)
 {
@@ -310,7 +340,7 @@ inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, i
             off.w_cat_skip = im.push(sage_cat_weights(p[0], p[2], fo, fi, true));
         break;
     case GNNB_CONV_PNA:
-        off.w_pre = im.push(p[0], fi * 2 * fi);
+        off.w_pre = im.push(p[0], fi * (edge_dim > 0 ? 3 : 2) * fi);
         off.b_pre = im.push(p[1], fi);
         off.w_post = im.push(p[2], fo * 13 * fi);
         off.b_post = im.push(p[3], fo);
@@ -320,7 +350,11 @@ inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, i
             const WeightBias folded = pna_fold_lin(p[2], p[3], p[4], p[5], fi, fo, skip_fold);
             off.w_fold = im.push(folded.w);
             off.b_fold = im.push(folded.b);
-            if (fo > 32) { // (any input width: whole 32-wide chunks take k_linear_dma's row-class mode, others the generic kernel's)
+            if (edge_dim > 0) { // (behind a three-block pre-NN: p[6], p[7] = conv.edge_encoder; no degree-class form)
+                const WeightBias proj = pna_edge_projection(p[0], p[6], p[7], fi, (size_t)edge_dim);
+                off.edge_w = im.push(proj.w);
+                off.edge_b = im.push(proj.b);
+            } else if (fo > 32) { // (any input width: whole 32-wide chunks take k_linear_dma's row-class mode, others the generic kernel's)
                 const WeightBias classes = pna_degree_class_weights(folded, p[0], p[1], fi, fo, d.pna_delta);
                 off.w_class = im.push(classes.w);
                 off.b_class = im.push(classes.b);
@@ -336,7 +370,7 @@ struct BuiltWeights {
     WeightLayout layout;
 };
 
-// The blob of a validated description (gnnb_model_create's checks have passed; edge_dim > 0: a GINE model) from the caller's
+// The blob of a validated description (gnnb_model_create's checks have passed; edge_dim > 0: a GINE or PNA edge model) from the caller's
 // tensors in canonical order, and where everything is in it.  Blob order: conv layers (canonical + derived tensors), k_gcn2_zf's
 // fragment copy, the GIN stack's copies, the head.
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params)

@@ -180,17 +180,22 @@ class _PNAConv(nn.Module):
     ``std`` is PyG's: ``sqrt(clamp(E[h^2]-E[h]^2, 1e-5))`` zeroed where ``<= sqrt(1e-5)``
     (SURVEY finding 5, pinned by ``tb_pna_output.bin``)."""
 
-    def __init__(self, in_channels: int, out_channels: int, avg_deg_log: float):
+    def __init__(self, in_channels: int, out_channels: int, avg_deg_log: float, pre_blocks: int = 2):
         super().__init__()
         self.aggr_module = _DegreeScalerAggregation(avg_deg_log)
-        self.pre_nns = nn.ModuleList([nn.Sequential(nn.Linear(2 * in_channels, in_channels))])
+        self.pre_nns = nn.ModuleList([nn.Sequential(nn.Linear(pre_blocks * in_channels, in_channels))])
         self.post_nns = nn.ModuleList([nn.Sequential(nn.Linear(13 * in_channels, out_channels))])
         self.lin = nn.Linear(out_channels, out_channels)
 
     def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
-        n, f = x.size(0), x.size(1)
         src, dst = edge_index[0], edge_index[1]
         h = self.pre_nns[0](torch.cat([x[dst], x[src]], dim=-1))  # destination first
+        return self.reduce(x, edge_index, h)
+
+    def reduce(self, x: Tensor, edge_index: Tensor, h: Tensor) -> Tensor:
+        """Everything behind the messages ``h`` [E, in]: the four aggregators, the scalers, post-NN and ``lin``."""
+        n, f = x.size(0), x.size(1)
+        src, dst = edge_index[0], edge_index[1]
         idx = dst.unsqueeze(-1).expand(-1, f)
         zeros = x.new_zeros(n, f)
         deg = _in_degree(edge_index, n)
@@ -232,6 +237,50 @@ class PNAConv_GNNB(nn.Module):
 
     def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
         return self.conv(x, edge_index)
+
+
+class _PNAEConv(_PNAConv):
+    """``_PNAConv`` with edge features: PyG's ``PNAConv(..., edge_dim=d, towers=1, pre_layers=1, post_layers=1,
+    divide_input=False)``.  The message is ``pre_nn(cat[x_i, x_j, edge_encoder(e_ij)])``, destination first; aggregators, the
+    std clamp and mask, the scalers and ``delta`` are ``_PNAConv``'s.  Parameters: ``edge_encoder.weight`` [in, edge_dim],
+    ``edge_encoder.bias`` [in], ``pre_nns.0.0.weight`` [in, 3 in], and the rest as ``_PNAConv``."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, avg_deg_log: float):
+        super().__init__(in_channels, out_channels, avg_deg_log, pre_blocks=3)
+        self.edge_encoder = nn.Linear(edge_dim, in_channels)
+
+    def message(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        src, dst = edge_index[0], edge_index[1]
+        return self.pre_nns[0](torch.cat([x[dst], x[src], self.edge_encoder(edge_attr)], dim=-1))  # destination first
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        return self.reduce(x, edge_index, self.message(x, edge_index, edge_attr))
+
+
+class PNAEConv_GNNB(nn.Module):
+    """PNA with edge features (no class of the reference: its ``PNAConv_GNNB`` stores ``graph_input_edge_dim`` and drops it).
+    ``GNNModel(..., graph_input_edge_dim=d, gnn_conv=PNAEConv_GNNB, ...)`` builds every layer with ``edge_dim=d`` (1 .. 16) and
+    ``forward(x, edge_index, batch, edge_attr)`` hands the same ``edge_attr`` [E, d] to each.  The accelerated path is
+    ``runtime.CompiledModel.from_model`` with ``forward_edges`` / ``forward_pyg_edges`` (C ABI ``include/gnnb_pna_edge.h``: the
+    pre-NN is linear, so the edge term ``(W_c W_enc) e_ij + W_c b_enc`` is formed inside the aggregate kernel,
+    csrc/k_pna_edge.hip).  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, delta: float = 1.0, p_in: int = 1,
+                 p_out: int = 1):
+        super().__init__()
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.edge_dim = edge_dim
+        self.delta = delta
+        self.p_in = p_in
+        self.p_out = p_out
+        self.aggregators = ["max", "min", "mean", "std"]
+        self.scalers = ["identity", "amplification", "attenuation"]
+        self.conv = _PNAEConv(in_channels, out_channels, edge_dim, float(delta))
+        self.delta_scaler = self.conv.aggr_module.avg_deg_log.item()
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        return self.conv(x, edge_index, edge_attr)
 
 
 # --------------------------------------------------------------------------------------- GINE
@@ -400,9 +449,11 @@ class MLP(nn.Module):
         return len(self.linear_layers)
 
 
-SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB]
-_CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine"}
-MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h)
+SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB]
+_CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
+              PNAEConv_GNNB: "pnae"}
+_EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE"}  # convs that take edge_attr, and what the messages call them
+MAX_EDGE_DIM = 16  # of a GINE or PNAE model (include/gnnb_edge.h, gnnb_pna_edge.h)
 
 
 class GNNModel(nn.Module):
@@ -429,11 +480,13 @@ class GNNModel(nn.Module):
             raise ValueError(f"gnn_activation {gnn_activation} has no native kernel; choose from {SUPPORTED_ACTIVATIONS}")
         self.gnn_skip_connection = gnn_skip_connection
         conv_kwargs = {}
-        if self.gnn_conv is GINEConv_GNNB:
+        if self.gnn_conv in _EDGE_CONVS:
             d = self.graph_input_edge_dim
             if not isinstance(d, int) or isinstance(d, bool) or not 1 <= d <= MAX_EDGE_DIM:
-                raise ValueError(f"a GINE model needs graph_input_edge_dim, an int in 1 .. {MAX_EDGE_DIM} (got {d!r})")
-            conv_kwargs = {"edge_dim": d, "hidden_dim": None}  # (the MLP's hidden width = out_channels, as for GIN)
+                raise ValueError(f"a {_EDGE_CONVS[self.gnn_conv]} model needs graph_input_edge_dim, an int in 1 .. {MAX_EDGE_DIM} (got {d!r})")
+            conv_kwargs = {"edge_dim": d}
+            if self.gnn_conv is GINEConv_GNNB:
+                conv_kwargs["hidden_dim"] = None  # (the MLP's hidden width = out_channels, as for GIN)
 
         self.global_pooling = global_pooling
         self.mlp_head = mlp_head  # registered before gnn_convs: parameter order mlp_head_*, gnn_convs_*
@@ -470,11 +523,11 @@ class GNNModel(nn.Module):
         (node -> graph index, PyG ``Batch`` convention) every graph is pooled separately ->
         ``[num_graphs, out]``; the reference ignores ``batch`` and pools all nodes into one row
         (models.py:551-553,569; SURVEY finding 3), which has no meaning for independent graphs.
-        ``edge_attr`` [E, graph_input_edge_dim]: a GINE model's edge features, the same for every layer (required there;
-        the other convs ignore it)."""
-        gine = self.gnn_conv is GINEConv_GNNB
+        ``edge_attr`` [E, graph_input_edge_dim]: a GINE or PNAE model's edge features, the same for every layer (required
+        there; the other convs ignore it)."""
+        gine = self.gnn_conv in _EDGE_CONVS
         if gine and edge_attr is None:
-            raise ValueError("a GINE model needs edge_attr [E, graph_input_edge_dim]")
+            raise ValueError(f"a {_EDGE_CONVS[self.gnn_conv]} model needs edge_attr [E, graph_input_edge_dim]")
         h = x
         for i, (conv, act) in enumerate(zip(self.gnn_convs, self.gnn_activations)):
             h_in = h
@@ -566,8 +619,8 @@ class GNNModel(nn.Module):
             "mlp_out": self.mlp_head.out_dim,
             "mlp_activation": _ACT_NAME[self.mlp_head.activation],
             "gin_eps": float(conv0.eps) if isinstance(conv0, (GINConv_GNNB, GINEConv_GNNB)) else 0.0,
-            "edge_dim": int(self.graph_input_edge_dim) if self.gnn_conv is GINEConv_GNNB else 0,
-            "pna_delta": float(conv0.delta_scaler) if isinstance(conv0, PNAConv_GNNB) else 1.0,
+            "edge_dim": int(self.graph_input_edge_dim) if self.gnn_conv in _EDGE_CONVS else 0,
+            "pna_delta": float(conv0.delta_scaler) if isinstance(conv0, (PNAConv_GNNB, PNAEConv_GNNB)) else 1.0,
             "output_activation": out_act,
         }
 
@@ -583,7 +636,10 @@ class GNNModel(nn.Module):
                     "conv_post_nns_0_0_bias", "conv_lin_weight", "conv_lin_bias"],
             "gine": ["mlp_linear_0_weight", "mlp_linear_0_bias", "mlp_linear_1_weight", "mlp_linear_1_bias",
                      "conv_lin_weight", "conv_lin_bias"],  # (conv.lin: the edge projection [in, edge_dim], [in])
-        }[self.spec()["conv"]]
+        }
+        # (PNA's six, then the edge encoder [in, edge_dim], [in]: the base conv's tensors first, the edge tensors behind)
+        per_conv["pnae"] = per_conv["pna"] + ["conv_edge_encoder_weight", "conv_edge_encoder_bias"]
+        per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):
             names += [f"mlp_head_linear_layers_{i}_weight", f"mlp_head_linear_layers_{i}_bias"]

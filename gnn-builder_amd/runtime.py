@@ -27,7 +27,8 @@ CSRC_DIR = PKG_DIR / "csrc"
 GNNB_OK = 0                                                                      # gnnb_status
 GNNB_ERR_RANGE = -6                                                              # gnnb_status
 CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                 # gnnb_conv
-MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it
+MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
+_EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -158,6 +159,14 @@ ABI_EDGE = {
 }
 
 
+# ... and of include/gnnb_pna_edge.h (PNA models with edge features), in its order (tests/test_abi_pna_edge.py)
+ABI_PNA_EDGE = {
+    "gnnb_pna_edge_model_num_params": (_I, [_DESC, _I]),
+    "gnnb_pna_edge_model_create": (_I, [_DESC, _I, _PP, _I, _PP]),
+    "gnnb_aggregate_pna_edges": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -201,7 +210,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
                 "or `make -C gnn-builder_amd/csrc`.  There is no CPU fallback.")
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
-        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE}.items():
+        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -223,7 +232,7 @@ def set_option(name: str, value: int) -> None:
 
 def make_desc(spec: dict) -> ModelDesc:
     d = ModelDesc()
-    d.conv_type = CONV["gin" if spec["conv"] == "gine" else spec["conv"]]  # (GINE: GIN's description, edge_dim beside it)
+    d.conv_type = CONV[_EDGE_BASE.get(spec["conv"], spec["conv"])]  # (GINE: GIN's description, "pnae": PNA's; edge_dim beside it)
     d.num_layers = spec["num_layers"]
     d.in_dim = spec["in_dim"]
     d.hidden_dim = spec["hidden_dim"]
@@ -343,16 +352,19 @@ class CompiledModel:
         self._keep = None  # its index tensors, which the device still reads
         self._addons = set()  # what the enable_* calls have allocated beside the workspace: "ingest", "ordered", "edges"
         self._views = {}  # add-on -> (device pointers, views of its whole arrays): _borrowed_views
-        self.edge_dim = int(spec.get("edge_dim", 0) or 0) if spec.get("conv") == "gine" else 0
+        self.edge_dim = int(spec.get("edge_dim", 0) or 0) if spec.get("conv") in _EDGE_BASE else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
         self.desc = make_desc(spec)
         host = [np.ascontiguousarray(np.asarray(p.detach().cpu().numpy() if hasattr(p, "detach") else p,
                                                 dtype=np.float32)) for p in params]
-        if spec.get("conv") == "gine" and not 1 <= self.edge_dim <= MAX_EDGE_DIM:
-            raise GnnbError(f"a GINE model needs spec['edge_dim'] in 1 .. {MAX_EDGE_DIM}, got {spec.get('edge_dim')!r}")
-        n_expect = (self.lib.gnnb_edge_model_num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
+        if spec.get("conv") in _EDGE_BASE and not 1 <= self.edge_dim <= MAX_EDGE_DIM:
+            raise GnnbError(f"a {spec['conv'].upper()} model needs spec['edge_dim'] in 1 .. {MAX_EDGE_DIM}, got {spec.get('edge_dim')!r}")
+        # (an edge model's own pair of entries: gnnb_edge.h for GINE, gnnb_pna_edge.h for PNA with edge features)
+        num_params, create = ((self.lib.gnnb_pna_edge_model_num_params, self.lib.gnnb_pna_edge_model_create) if spec.get("conv") == "pnae" else
+                              (self.lib.gnnb_edge_model_num_params, self.lib.gnnb_edge_model_create))
+        n_expect = (num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
                     self.lib.gnnb_model_num_params(C.byref(self.desc)))
         if n_expect < 0:
             _check(n_expect)
@@ -360,7 +372,7 @@ class CompiledModel:
             raise GnnbError(f"model needs {n_expect} parameter tensors, got {len(host)}")
         arr = (C.c_void_p * len(host))(*[h.ctypes.data for h in host])
         if self.edge_dim:
-            _check(self.lib.gnnb_edge_model_create(C.byref(self.desc), self.edge_dim, arr, len(host), C.byref(self._model)))
+            _check(create(C.byref(self.desc), self.edge_dim, arr, len(host), C.byref(self._model)))
         else:
             _check(self.lib.gnnb_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
         rc = self.lib.gnnb_workspace_create(self._model, self.max_graphs, self.max_nodes, self.max_edges, C.byref(self._ws))
@@ -659,7 +671,7 @@ class CompiledModel:
         large-segment setting is left on the workspace; the stage-level entry points work afterwards, on the ORDERED batch."""
         return self._forward_pyg(self.lib.gnnb_forward_pyg_ordered, "ordered", x, edge_index, None, batch, ptr, num_graphs, out, stream)
 
-    # ------------------------------------------------------------------ GINE models: forwards with edge attributes
+    # ------------------------------------------------------------------ GINE and PNAE models: forwards with edge attributes
     def _require_edge_attr(self, edge_attr, E: int, like, width: Optional[int] = None):
         """``edge_attr`` of an entry point that reads one [edge_dim] row per edge: fp32 [E, edge_dim] on ``like``'s device; an
         empty batch's may be None.  Returns its device pointer (None: NULL)."""
@@ -673,7 +685,8 @@ class CompiledModel:
 
     def _require_edge_model(self, what: str) -> None:
         if not self.edge_dim:
-            raise GnnbError(f"{what} takes a GINE model (a GNNModel of GINEConv_GNNB layers: edge weights); this model has none")
+            raise GnnbError(f"{what} takes a GINE or PNAE model (a GNNModel of GINEConv_GNNB or PNAEConv_GNNB layers: edge weights); "
+                            "this model has none")
 
     def forward_edges(self, x, edge_attr, coo, node_ptr, edge_ptr, out=None, stream=None):
         """``forward`` of a GINE model: ``edge_attr`` [E, edge_dim] fp32, row ``i`` belongs to ``coo`` row ``i``
@@ -793,6 +806,30 @@ class CompiledModel:
         out = _out(out, self._N, w, x)
         _check(self.lib.gnnb_aggregate_edges_fused(self._ws, _dptr(x), ea, ed, _dptr(w_edge), int(w_edge.stride(0)) if w > 1 else ed,
                                                    _dptr(b_edge), _dptr(out), w, float(eps), _stream_ptr(stream)))
+        return out
+
+    def aggregate_pna_edges(self, p, q, edge_attr, w_edge, b_edge, out=None, stream=None):
+        """PNA's aggregate with the edge projection inside the kernel (``gnnb_aggregate_pna_edges``, csrc/k_pna_edge.hip):
+        ``max | min | mean | std`` over a row's in-edges of ``q_i + p_j + w_edge e_ij + b_edge`` -> [N, 4 width] as
+        ``aggregate("pna", ...)``; ``p`` [N, width], ``q`` [N, width] or None (no destination term), ``edge_attr``
+        [E, edge_dim <= 16] in COO order, ``w_edge`` [width, edge_dim] (a column slice of a wider matrix is fine: its row stride is
+        passed on), ``b_edge`` [width]."""
+        import torch
+        self._require_x(p)
+        w = int(p.shape[1])
+        if q is not None:
+            _require_rows(q, "q", self._N, w, p)
+        _require_strided(w_edge, "w_edge", w, 1)
+        ed = int(w_edge.shape[1])
+        if not 1 <= ed <= MAX_EDGE_DIM or w_edge.device != p.device:
+            raise GnnbError(f"w_edge must be [{w}, 1 .. {MAX_EDGE_DIM}] on {p.device}, got {tuple(w_edge.shape)} on {w_edge.device}")
+        _require(b_edge, "b_edge", torch.float32, 1, w)
+        if b_edge.device != p.device:
+            raise GnnbError(f"b_edge must be on {p.device}")
+        ea = self._require_edge_attr(edge_attr, self._E, p, ed)
+        out = _out(out, self._N, 4 * w, p)
+        _check(self.lib.gnnb_aggregate_pna_edges(self._ws, _dptr(p), _optr(q), ea, ed, _dptr(w_edge), int(w_edge.stride(0)) if w > 1 else ed,
+                                                 _dptr(b_edge), _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def gine_conv(self, x, edge_attr, w_edge, b_edge, w0, b0, w1, b1, eps: float = 0.0, stream=None):

@@ -21,6 +21,11 @@
  * message names the _edges entry); the _edges entries return GNNB_ERR_INVALID for a model without edge weights.
  * gnnb_workspace_set_max_graph_nodes / _set_max_degree / _set_large_segment, gnnb_graph_prep, gnnb_workspace_check and the
  * stage entry points work on such a workspace as on any other.
+ *
+ * A PNA model with edge features (gnnb_pna_edge.h: gnnb_pna_edge_model_create, a PNA description with edge_dim beside it) is the
+ * other kind of model with edge weights: the forwards and the ingest entries below run it as they run a GINE model ("a model of
+ * gnnb_edge_model_create" below reads "... or of gnnb_pna_edge_model_create"), gnnb_model_edge_dim reports its edge_dim, and the
+ * entries that refuse a GINE model refuse it in the same way.
  */
 #ifndef GNNB_EDGE_H
 #define GNNB_EDGE_H
