@@ -75,7 +75,7 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     G2Deep g;
     g.nl = 0;
     const int L = d.num_layers;
-    if (model->edge_dim) // a GINE model: no stack kernel forms the edge term
+    if (model->edge_dim || model->gat_heads) // a GINE model: no stack kernel forms the edge term; a GATv2 model: none forms attention
         return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
@@ -206,6 +206,24 @@ static int gcn_layer(const LayerCtx &c)
     if ((rc = c.aggregate(GNNB_AGG_GCN, c.cur, nullptr, c.ws->agg, fi, 0.f)))
         return rc;
     return c.linear1(c.rows(c.ws->agg, fi), fi, p.w0, fi, p.b0, c.rows(c.skip, fi), c.rows(c.nxt, fo), fo, d.activation);
+}
+
+// GATv2 (gnnb_gat.h; a GCN description with heads beside it): ONE GEMM x -> [xl | xr] [N, 2 fo] on the stacked weight [W_l ; W_r] in
+// the model's math mode, then ONE k_gatv2_aggregate launch -- scores, softmax and weighted sum in one pass over the edges, with
+// the bias, the skip term and the activation in its epilogue (no GEMM follows the aggregate here).  None of the fused rungs
+static int gat_layer(const LayerCtx &c)
+{
+    const gnnb_model_desc &d = c.model->desc;
+    const LayerWeights &p = c.model->conv[c.l];
+    const int fi = c.fi, fo = c.fo;
+    float *lr = c.ws->tmp0;
+    int rc;
+    if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_lr, fi, p.b_lr, nullptr, c.rows(lr, 2 * fo), 2 * fo, GNNB_ACT_NONE)))
+        return rc;
+    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+        GNNB_HIP_TRY(launch_gatv2_aggregate(c.tv, lr, 2 * fo, lr + fo, 2 * fo, p.att, p.gat_bias, c.skip, d.activation, c.model->gat_heads,
+                                            c.model->gat_slope, c.nxt, fo, c.hs()));
+    return GNNB_OK;
 }
 
 // GIN's first linear + ReLU on the eps-weighted sum -> ws->tmp0
@@ -384,7 +402,7 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
         c.skip_fold = c.skip != nullptr && c.fi == c.fo && !c.fpx;
         int rc = GNNB_OK;
         switch (d.conv_type) {
-        case GNNB_CONV_GCN: rc = gcn_layer(c); break;
+        case GNNB_CONV_GCN: rc = model->gat_heads ? gat_layer(c) : gcn_layer(c); break;
         case GNNB_CONV_GIN: rc = gin_layer(c); break;
         case GNNB_CONV_SAGE: rc = sage_layer(c); break;
         case GNNB_CONV_PNA: rc = pna_layer(c); break;
@@ -652,7 +670,8 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward");
     if (!ws->prepared)
         return fail(GNNB_ERR_INVALID, "workspace has no prepared batch");
-    if (memcmp(&model->desc, &ws->desc, sizeof(gnnb_model_desc)) != 0 || model->edge_dim != ws->edge_dim)
+    if (memcmp(&model->desc, &ws->desc, sizeof(gnnb_model_desc)) != 0 || model->edge_dim != ws->edge_dim ||
+        model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;

@@ -12,6 +12,7 @@
 #include "gnnb_order.h"
 #include "gnnb_edge.h"
 #include "gnnb_pna_edge.h"
+#include "gnnb_gat.h"
 
 namespace gnnb {
 
@@ -43,6 +44,8 @@ struct gnnb_model {
     gnnb::HeadArgs *head_dev = nullptr; // the MLP head's {weights, biases, widths} once more in device memory: k_gcn2_zf reads it at the
                                         // end of a workgroup's life (by value the 42 dwords stayed in scalar registers through its stage loop)
     int edge_dim = 0; // > 0: a GINE model (gnnb_edge_model_create) or PNA with edge features (gnnb_pna_edge_model_create: desc.conv_type says which) -- every layer has edge_w [in, edge_dim] and edge_b [in]
+    int gat_heads = 0;      // > 0: a GATv2 model (gnnb_gat_model_create; desc is a GCN description) -- every layer has w_lr, b_lr, att, gat_bias
+    float gat_slope = 0.0f; // ... and its leaky_relu slope
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };
@@ -62,6 +65,8 @@ struct gnnb_workspace {
     char *ingest_blob = nullptr; // gnnb_workspace_enable_ingest: the outputs and the sort scratch of gnnb_ingest_pyg (ingest_place), one allocation
     bool ingested = false;       // an ingest has been enqueued: gnnb_workspace_check has something to report on
     int edge_dim = 0;            // of the model the workspace was created for (0: no edge weights)
+    int gat_heads = 0;           // ... and its heads and slope when it is a GATv2 model (0: it is not)
+    float gat_slope = 0.0f;
     char *edge_blob = nullptr;   // gnnb_workspace_enable_edge_ingest: edge_attr in COO row order, [max_edges, edge_dim], one allocation
     char *order_blob = nullptr;  // gnnb_workspace_enable_ordered_ingest: the ordered batch and the staged outputs (order_place), one allocation
     int32_t *order_triple = nullptr, *order_triple_dev = nullptr; // host-mapped (first large graph, node row, edge row) of k_order_graphs, and
@@ -97,6 +102,9 @@ HeadArgs model_head_args(const gnnb_model *model);
 
 // GNNB_OK, or GNNB_ERR_INVALID for a GINE model / its workspace at `entry`, which takes no edge attributes: says which entry does
 int refuse_edge_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
+
+// GNNB_OK, or GNNB_ERR_INVALID for a GATv2 model / its workspace at `entry`, which serves the stack kernels' promise only: says which entry runs it
+int refuse_gat_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
 
 // gnnb_runtime.hip, for the forward (gnnb_forward.hip) -- each is described where it is defined
 int ensure_gcoef(gnnb_workspace *ws, void *stream);

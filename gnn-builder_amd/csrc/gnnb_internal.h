@@ -308,6 +308,13 @@ hipError_t launch_gine_aggregate(const BatchTables &t, const float *x, const flo
 // in launch_aggregate(GNNB_AGG_PNA)'s layout; p [N, width], q [N, width] or nullptr (no destination term), the rest as above
 hipError_t launch_pna_edge_aggregate(const BatchTables &t, const float *p, const float *q, const float *edge_attr, int edge_dim, const float *we,
                                      int ldwe, const float *be, float *out, int width, hipStream_t s);
+// GATv2 (k_gatv2.hip): out [N, width] = act(sum_j softmax_j(s_ij) xl_j + bias + skip_i) over j in N(i) u {i}, per head of width / heads
+// columns, s_ij = sum_c att_c leaky_relu(xl_j[c] + xr_i[c]); xl / xr: rows of stride ldl / ldr >= width (the halves of one GEMM
+// output), att [width], bias [width] or nullptr, skip [N, width] or nullptr; the tables of a GCN workspace (no (v, v) edges: the
+// kernel adds the self term).  hipErrorInvalidValue: nothing launched
+constexpr int GAT_MAX_HEADS = 8, GAT_MAX_WIDTH = 256;
+hipError_t launch_gatv2_aggregate(const BatchTables &t, const float *xl, int ldl, const float *xr, int ldr, const float *att, const float *bias,
+                                  const float *skip, int act, int heads, float slope, float *out, int width, hipStream_t s);
 // the ingest's edge attributes in COO row order (k_ingest.hip): out[i] = edge_attr[state[INGEST_STATE_UNSORTED] ? idx[i] : i]; idx:
 // the general path's sorted-position -> input-edge array (nullptr: that path was not launched), state: IngestParams::state
 hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,

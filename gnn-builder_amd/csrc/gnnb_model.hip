@@ -3,6 +3,7 @@
 // device blob, its offsets turned into the model's pointers.
 // Reference: load_parameters once (gnnbuilder/templates/model.cpp.jinja:724-730).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "gnnb_host.h"
@@ -93,16 +94,63 @@ int count_params(const gnnb_model_desc *desc, int edge_dim, int base = GNNB_CONV
     return (conv_slots(desc->conv_type) + (edge_dim ? 2 : 0)) * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
-// gnnb_model_create, and gnnb_edge_model_create / gnnb_pna_edge_model_create (edge_dim > 0, base = GIN / PNA)
-int model_create(const gnnb_model_desc *desc, int edge_dim, const float *const *host_params, int num_params, gnnb_model **out_model,
-                 int base = GNNB_CONV_GIN)
+// parameter tensors of a GATv2 model (gnnb_gat.h): a GCN description without the fixed-point emulation, heads 1 .. 8 dividing every
+// layer's output width, which is at most 256
+int count_gat_params(const gnnb_model_desc *desc, int heads)
+{
+    int rc = validate_desc(desc);
+    if (rc != GNNB_OK)
+        return rc;
+    if (heads < 1 || heads > GAT_MAX_HEADS)
+        return fail(GNNB_ERR_INVALID, "heads %d: a GATv2 model takes 1 .. %d heads", heads, GAT_MAX_HEADS);
+    if (desc->conv_type != GNNB_CONV_GCN)
+        return fail(GNNB_ERR_INVALID, "a GATv2 model's description is a GCN description (conv_type %d given)", desc->conv_type);
+    if (desc->fpx_w != 0)
+        return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover GATv2 models (fpx_w must be 0)");
+    for (int l = 0; l < desc->num_layers; l++) {
+        const int fo = layer_dims(*desc, l).fout;
+        if (fo % heads != 0)
+            return fail(GNNB_ERR_INVALID, "layer %d's output width %d is not divisible by heads %d", l, fo, heads);
+        if (fo > GAT_MAX_WIDTH)
+            return fail(GNNB_ERR_INVALID, "layer %d's output width %d: a GATv2 layer is at most %d wide", l, fo, GAT_MAX_WIDTH);
+    }
+    return GAT_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+}
+
+// What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
+// type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
+// (gnnb_gat_model_create: a GCN description)
+struct ModelKind {
+    int edge_dim = 0, base = GNNB_CONV_GIN;
+    int gat_heads = 0;
+    float gat_slope = 0.0f;
+    static ModelKind plain() { return {}; }
+    static ModelKind edges(int edge_dim, int base)
+    {
+        ModelKind k;
+        k.edge_dim = edge_dim, k.base = base;
+        return k;
+    }
+    static ModelKind gatv2(int heads, float slope)
+    {
+        ModelKind k;
+        k.gat_heads = heads, k.gat_slope = slope;
+        return k;
+    }
+};
+
+// the body of the four *_model_create entries
+int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
         return fail(GNNB_ERR_INVALID, "null out_model");
     *out_model = nullptr;
-    int expect = count_params(desc, edge_dim, base);
+    const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads;
+    int expect = gat_heads != 0 ? count_gat_params(desc, gat_heads) : count_params(desc, edge_dim, kind.base);
     if (expect < 0)
         return expect;
+    if (gat_heads != 0 && !std::isfinite(kind.gat_slope))
+        return fail(GNNB_ERR_INVALID, "negative_slope must be finite");
     if (num_params != expect || !host_params)
         return fail(GNNB_ERR_INVALID, "expected %d parameter tensors, got %d", expect, num_params);
     for (int i = 0; i < num_params; i++)
@@ -112,13 +160,15 @@ int model_create(const gnnb_model_desc *desc, int edge_dim, const float *const *
         return fail(GNNB_ERR_NO_DEVICE, "no HIP device visible: the MI355X path cannot run");
 
     const gnnb_model_desc &d = *desc;
-    const BuiltWeights built = build_weight_image(d, edge_dim, host_params);
+    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads);
     const std::vector<float> &img = built.img;
     const WeightLayout &lo = built.layout;
 
     gnnb_model *m = new gnnb_model();
     m->desc = d;
     m->edge_dim = edge_dim;
+    m->gat_heads = gat_heads;
+    m->gat_slope = gat_heads ? kind.gat_slope : 0.0f;
     (void)hipGetDevice(&m->device);
     m->blob_floats = img.size();
     hipError_t e = hipMalloc((void **)&m->blob, std::max<size_t>(img.size(), 4) * sizeof(float));
@@ -161,7 +211,7 @@ int gnnb_model_num_params(const gnnb_model_desc *desc) { return count_params(des
 
 int gnnb_model_create(const gnnb_model_desc *desc, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
-    return model_create(desc, 0, host_params, num_params, out_model);
+    return model_create(desc, ModelKind::plain(), host_params, num_params, out_model);
 }
 
 int gnnb_edge_model_num_params(const gnnb_model_desc *desc, int edge_dim)
@@ -178,7 +228,7 @@ int gnnb_edge_model_create(const gnnb_model_desc *desc, int edge_dim, const floa
         *out_model = nullptr;
     if (edge_dim == 0)
         return fail(GNNB_ERR_INVALID, "edge_dim 0: a GINE model takes 1 .. 16 edge attributes (gnnb_model_create: models without)");
-    return model_create(desc, edge_dim, host_params, num_params, out_model);
+    return model_create(desc, ModelKind::edges(edge_dim, GNNB_CONV_GIN), host_params, num_params, out_model);
 }
 
 int gnnb_pna_edge_model_num_params(const gnnb_model_desc *desc, int edge_dim)
@@ -195,10 +245,24 @@ int gnnb_pna_edge_model_create(const gnnb_model_desc *desc, int edge_dim, const 
         *out_model = nullptr;
     if (edge_dim == 0)
         return fail(GNNB_ERR_INVALID, "edge_dim 0: a PNA edge model takes 1 .. 16 edge attributes (gnnb_model_create: models without)");
-    return model_create(desc, edge_dim, host_params, num_params, out_model, GNNB_CONV_PNA);
+    return model_create(desc, ModelKind::edges(edge_dim, GNNB_CONV_PNA), host_params, num_params, out_model);
 }
 
 int gnnb_model_edge_dim(const gnnb_model *model) { return model ? model->edge_dim : 0; }
+
+int gnnb_gat_model_num_params(const gnnb_model_desc *desc, int heads) { return count_gat_params(desc, heads); }
+
+int gnnb_gat_model_create(const gnnb_model_desc *desc, int heads, float negative_slope, const float *const *host_params, int num_params,
+                          gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (heads == 0) // (ModelKind reads 0 as "no GATv2 model")
+        return fail(GNNB_ERR_INVALID, "heads 0: a GATv2 model takes 1 .. %d heads", GAT_MAX_HEADS);
+    return model_create(desc, ModelKind::gatv2(heads, negative_slope), host_params, num_params, out_model);
+}
+
+int gnnb_model_gat_heads(const gnnb_model *model) { return model ? model->gat_heads : 0; }
 
 void gnnb_model_destroy(gnnb_model *model)
 {

@@ -60,6 +60,14 @@ int refuse_edge_model(const gnnb_model *model, const gnnb_workspace *ws, const c
     return GNNB_OK;
 }
 
+int refuse_gat_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use)
+{
+    if ((model && model->gat_heads) || (ws && ws->gat_heads))
+        return fail(GNNB_ERR_INVALID, "%s: a GATv2 model (gnnb_gat_model_create) runs layer by layer and is not served here: call %s (gnnb_gat.h)",
+                    entry, use);
+    return GNNB_OK;
+}
+
 static thread_local int tl_math = -1; // >= 0: the calling thread is inside an entry point of a model with its own math mode
 static thread_local FlagWord tl_flag = {nullptr, nullptr};
 int launch_math() { return tl_math >= 0 ? tl_math : (int)options().math; }
@@ -140,6 +148,9 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
         aggw = std::max(aggw, d.conv_type == GNNB_CONV_PNA ? 4 * ld.fin : ld.fin);
     }
     tmpw = std::max(tmpw, maxw);
+    if (model->gat_heads) // a GATv2 layer's GEMM writes [xl | xr] [N, 2 out] into tmp0
+        for (int l = 0; l < d.num_layers; l++)
+            tmpw = std::max(tmpw, 2 * layer_dims(d, l).fout);
     // the widest GEMM K of the conv layers: from 1024 on k_linear_dma may cut its tiles along K (stream-K) and needs a scratch,
     // which belongs to the workspace -- forwards of different workspaces never share one, whatever streams or graphs run them
     int max_k = 0;
@@ -150,7 +161,8 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     const bool want_sk = max_k >= 1024;
     // (the stage-cut planner's tables: opt-in -- carved only for workspaces created while the option is on; a workspace created
     // without them keeps equal tile counts whatever the option says later: round-5 advisor finding)
-    const bool want_plan = options().stage_cut && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2;
+    const bool want_plan = options().stage_cut && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 &&
+                           model->gat_heads == 0; // (a GATv2 model takes no stack kernel: no stage plan)
     const int pooledw = d.num_pools * gnn_out_width(d);
     const int mlpw = std::max(d.mlp_hidden, d.mlp_out);
     const int min_tile_rows = 4;
@@ -159,6 +171,8 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     gnnb_workspace *ws = new gnnb_workspace();
     ws->desc = d;
     ws->edge_dim = model->edge_dim;
+    ws->gat_heads = model->gat_heads;
+    ws->gat_slope = model->gat_slope;
     ws->max_graphs = max_graphs;
     ws->max_nodes = max_nodes;
     ws->max_edges = max_edges;
@@ -318,9 +332,9 @@ int gnnb_workspace_set_max_degree(gnnb_workspace *ws, int d)
 static bool stack_promised(const gnnb_workspace *ws)
 {
     const gnnb_model_desc &d = ws->desc;
-    // (a GINE model's workspace: never -- its layers take no stack kernel, whatever the promise)
+    // (a GINE model's workspace, a GATv2 model's: never -- their layers take no stack kernel, whatever the promise)
     return options().fuse_gcn2 && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 && ws->max_graph_nodes > 0 &&
-           ws->edge_dim == 0;
+           ws->edge_dim == 0 && ws->gat_heads == 0;
 }
 
 // ... and the WHOLE batch is expected there: no large segment, no fixed-point emulation.  Such a batch needs neither the
@@ -359,7 +373,12 @@ static bool wants_degree_classes(const gnnb_workspace *ws)
 static bool may_plan_stage_cuts(const gnnb_workspace *ws) { return options().stage_cut && ws->plan_scratch; }
 
 // GCN: the coefficient table is produced behind the tables unless the whole batch is expected on the stack kernels
-static bool wants_gcoef_at_prep(const gnnb_workspace *ws) { return ws->desc.conv_type == GNNB_CONV_GCN && !stack_expected(ws); }
+// (a GATv2 workspace is a GCN description whose layers never read the table: not produced there; gnnb_aggregate(GNNB_AGG_GCN) as a
+// stage entry on such a workspace produces it lazily, ensure_gcoef)
+static bool wants_gcoef_at_prep(const gnnb_workspace *ws)
+{
+    return ws->desc.conv_type == GNNB_CONV_GCN && ws->gat_heads == 0 && !stack_expected(ws);
+}
 
 // Can this workspace's graph prep run as a guest of the forward's readout kernel (k_head_small's extra workgroups)?  The molecule
 // path (promise <= 64 nodes) of a batch that needs NOTHING launched behind its tables: no stage cuts, no degree classes, no
@@ -690,6 +709,24 @@ int gnnb_aggregate_pna_edges(gnnb_workspace *ws, const float *p_dev, const float
         (ws->t.num_edges > 0 && !edge_attr_dev))
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_pna_edges (edge_dim 1 .. 16, ldwe >= edge_dim)");
     GNNB_HIP_TRY(launch_pna_edge_aggregate(ws->t, p_dev, q_dev, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, out_dev, width, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_gatv2(gnnb_workspace *ws, const float *xl_dev, int ldl, const float *xr_dev, int ldr, const float *att_dev,
+                         const float *bias_dev, const float *skip_dev, int act, int heads, float negative_slope, float *out_dev, int width,
+                         void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gatv2 needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type != GNNB_CONV_GCN) // (only there are the tables free of (v, v) edges: the kernel adds the self term)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gatv2 takes the prepared batch of a GCN workspace (or a GATv2 model's): graph prep drops "
+                                      "explicit self loops there, the kernel adds the one self term");
+    if (!xl_dev || !xr_dev || !att_dev || !out_dev || heads < 1 || heads > GAT_MAX_HEADS || width < 1 || width > GAT_MAX_WIDTH ||
+        width % heads != 0 || ldl < width || ldr < width || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE || !std::isfinite(negative_slope))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gatv2 (heads 1 .. %d dividing width 1 .. %d, ldl and ldr >= width, a "
+                                      "gnnb_act, a finite negative_slope)", GAT_MAX_HEADS, GAT_MAX_WIDTH);
+    GNNB_HIP_TRY(launch_gatv2_aggregate(ws->t, xl_dev, ldl, xr_dev, ldr, att_dev, bias_dev, skip_dev, act, heads, negative_slope, out_dev, width,
+                                        (hipStream_t)stream));
     return GNNB_OK;
 }
 

@@ -83,10 +83,17 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //              edge_w [in, edge_dim], edge_b [in]   derived from canonical 6, 7 (conv.edge_encoder): W_c W_enc and W_c b_enc
 //                                                   (pna_edge_projection) -- what k_pna_edge_aggregate adds to q_i + p_j
 //              no w_class / b_class: such a model does not take the degree-class form
+//   GATv2      (gnnb_model::gat_heads > 0, gnnb_gat_model_create: a GCN description) none of GCN's slots, but
+//              w_lr [2 out, in]                     derived: [W_l ; W_r], canonical 0 (conv.lin_l.weight) on top of canonical 2
+//                                                   (conv.lin_r.weight) -- ONE GEMM gives [xl | xr] [N, 2 out] (gat_stack_rows)
+//              b_lr [2 out]                         derived: [b_l ; b_r], canonical 1 and 3
+//              att [out]                            canonical 4: conv.att [1, heads, out / heads], head-major
+//              gat_bias [out]                       canonical 5: conv.bias, added behind the aggregate
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
     T edge_w = absent_slot<T>(), edge_b = absent_slot<T>();
+    T w_lr = absent_slot<T>(), b_lr = absent_slot<T>(), att = absent_slot<T>(), gat_bias = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -95,8 +102,9 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_cat),  f(b_cat),   f(w_cat_skip), f(w_pre),
-                f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin),  f(w_fold), f(b_fold), f(w_class), f(b_class)};
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_cat),
+                f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
+                f(b_class)};
     }
 };
 using LayerWeights = LayerSlots<const float *>;
@@ -306,12 +314,32 @@ inline WeightBias gin_execution_order(const gnnb_model_desc &d, const std::vecto
     return g;
 }
 
-// One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six) and the
-// derived forms its conv type has, pushed in the order of LayerSlots' comment -> their offsets in the image
-inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim)
+// GATv2: two tensors of `rows_each` rows of `cols` floats, the first on top of the second ([W_l ; W_r], and with cols = 1 [b_l ; b_r])
+inline std::vector<float> gat_stack_rows(const float *top, const float *bottom, size_t rows_each, size_t cols)
+{
+    std::vector<float> s(2 * rows_each * cols);
+    memcpy(s.data(), top, rows_each * cols * sizeof(float));
+    memcpy(s.data() + rows_each * cols, bottom, rows_each * cols * sizeof(float));
+    return s;
+}
+
+constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_gat.h)
+
+// One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
+// GATv2 model's six in gnnb_gat.h's order) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
+// their offsets in the image
+inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (gat_heads > 0) { // (a GCN description whose layers are GATv2's)
+        LayerOffsets g;
+        g.w_lr = im.push(gat_stack_rows(p[0], p[2], fo, fi));
+        g.b_lr = im.push(gat_stack_rows(p[1], p[3], fo, 1));
+        g.att = im.push(p[4], fo);
+        g.gat_bias = im.push(p[5], fo);
+        return g;
+    }
     // the layer's skip connection (middle layers: y = conv(x) + x, models.py:562-564) where x itself is an operand of
     // the layer's GEMM (GraphSAGE's root term, PNA's x segment): folded into that operand's weights as + I, so that the
     // [N, out] skip operand is not read again in the epilogue (45 of 293 us of a 128-wide PNA layer's GEMM went there:
@@ -372,17 +400,18 @@ struct BuiltWeights {
 
 // The blob of a validated description (gnnb_model_create's checks have passed; edge_dim > 0: a GINE or PNA edge model) from the caller's
 // tensors in canonical order, and where everything is in it.  Blob order: conv layers (canonical + derived tensors), k_gcn2_zf's
-// fragment copy, the GIN stack's copies, the head.
-inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params)
+// fragment copy, the GIN stack's copies, the head.  gat_heads > 0: a GATv2 model (a GCN description, six tensors per layer; no
+// fragment copy -- it takes no stack kernel).
+inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
+    const int slots = gat_heads > 0 ? GAT_PARAM_SLOTS : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;
     for (int l = 0; l < d.num_layers; l++, pi += slots)
-        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim);
-    const bool have_w1f = d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads);
+    const bool have_w1f = gat_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));
     // (a GINE model takes no stack kernel: no execution-order copy)

@@ -331,12 +331,90 @@ class GINEConv_GNNB(nn.Module):
 class GATConv_GNNB(nn.Module):
     """Listed by the reference's SUPPORTED_GNN_CONVS but it has no native kernel for it
     (gnn_builder_lib.h:2343 ``// TODO: GAT layer``; template TODO model.cpp.jinja:141-142);
-    out of scope here as well."""
+    out of scope here as well.  Attention models run as ``GATv2Conv_GNNB`` below."""
 
     def __init__(self, *args, **kwargs):
         super().__init__()
         raise NotImplementedError(
             "GATConv_GNNB has no native path in the reference (gnn_builder_lib.h:2343) and none here")
+
+
+# --------------------------------------------------------------------------------------- GATv2
+MAX_GAT_HEADS = 8  # of a GATv2 model (include/gnnb_gat.h)
+
+
+class _GATv2Conv(nn.Module):
+    """PyG's ``GATv2Conv(in_channels, out_channels, heads, concat=True, negative_slope, add_self_loops=True, bias=True,
+    share_weights=False, edge_dim=None, dropout=0)`` with ``out_channels`` PER HEAD, as PyG counts it::
+
+        xl = lin_l(x) [N, H, C]      xr = lin_r(x) [N, H, C]
+        s_ij[h] = sum_c att[h, c] * leaky_relu(xl_j[h, c] + xr_i[h, c])     for j in N(i) u {i}
+        a_ij[h] = exp(s_ij[h] - max_j s_ij[h]) / (sum_j exp(s_ij[h] - max_j s_ij[h]) + 1e-16)
+        out_i[h, :] = sum_j a_ij[h] * xl_j[h, :]  + bias
+
+    Self loops are PyG's (``remove_self_loops`` + ``add_self_loops``): explicit ``(v, v)`` edges of the input are removed and
+    exactly one is added per node -- the rule ``_GCNConv`` applies.  Parameters: ``lin_l.weight`` [H C, in], ``lin_l.bias``,
+    ``lin_r.weight``, ``lin_r.bias``, ``att`` [1, H, C], ``bias`` [H C]; weights and ``att`` glorot, biases zero."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, negative_slope: float = 0.2):
+        super().__init__()
+        self.heads = heads
+        self.out_channels = out_channels
+        self.negative_slope = negative_slope
+        self.lin_l = nn.Linear(in_channels, heads * out_channels)
+        self.lin_r = nn.Linear(in_channels, heads * out_channels)
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.bias = nn.Parameter(torch.zeros(heads * out_channels))
+        _glorot(self.lin_l.weight)
+        _glorot(self.lin_r.weight)
+        _glorot(self.att)
+        with torch.no_grad():
+            self.lin_l.bias.zero_()
+            self.lin_r.bias.zero_()
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        n, H, C = x.size(0), self.heads, self.out_channels
+        if edge_index.numel():
+            edge_index = edge_index[:, edge_index[0] != edge_index[1]]
+        loops = torch.arange(n, dtype=torch.long, device=x.device)
+        src = torch.cat([edge_index[0].long(), loops]) if edge_index.numel() else loops
+        dst = torch.cat([edge_index[1].long(), loops]) if edge_index.numel() else loops
+        xl = self.lin_l(x).view(n, H, C)
+        xr = self.lin_r(x).view(n, H, C)
+        s = (nn.functional.leaky_relu(xl[src] + xr[dst], self.negative_slope) * self.att).sum(dim=-1)  # [E + N, H]
+        idx = dst.unsqueeze(-1).expand(-1, H)
+        smax = s.new_full((n, H), float("-inf")).scatter_reduce(0, idx, s, reduce="amax", include_self=True)
+        e = (s - smax[dst]).exp()
+        a = e / (s.new_zeros(n, H).index_add(0, dst, e)[dst] + 1e-16)
+        out = x.new_zeros(n, H, C).index_add(0, dst, a.unsqueeze(-1) * xl[src])
+        return out.reshape(n, H * C) + self.bias
+
+
+class GATv2Conv_GNNB(nn.Module):
+    """GATv2 (no class of the reference, whose ``GATConv_GNNB`` is a stub): ``out_channels`` is the layer's WHOLE output width,
+    split over ``heads`` (1 .. 8, dividing it) and concatenated -- PyG's ``GATv2Conv(in_channels, out_channels // heads,
+    heads=heads)``.  ``GNNModel(..., gnn_conv=GATv2Conv_GNNB, gnn_heads=H)`` stacks it; ``forward(x, edge_index)``.  The
+    accelerated path is ``runtime.CompiledModel.from_model`` with the ordinary ``forward`` / ``forward_pyg`` (C ABI
+    ``include/gnnb_gat.h``: one GEMM and one launch of csrc/k_gatv2.hip per layer, the softmax online inside the aggregate).
+    ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, negative_slope: float = 0.2, p_in: int = 1,
+                 p_out: int = 1):
+        super().__init__()
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
+            raise ValueError(f"heads must be an int in 1 .. {MAX_GAT_HEADS} (got {heads!r})")
+        if out_channels % heads != 0:
+            raise ValueError(f"out_channels ({out_channels}) must be divisible by heads ({heads})")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.heads = heads
+        self.negative_slope = float(negative_slope)
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _GATv2Conv(in_channels, out_channels // heads, heads, self.negative_slope)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        return self.conv(x, edge_index)
 
 
 # --------------------------------------------------------------------------------------- pooling / MLP
@@ -449,9 +527,10 @@ class MLP(nn.Module):
         return len(self.linear_layers)
 
 
-SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB]
+SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
+                       GATv2Conv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
-              PNAEConv_GNNB: "pnae"}
+              PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2"}
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE"}  # convs that take edge_attr, and what the messages call them
 MAX_EDGE_DIM = 16  # of a GINE or PNAE model (include/gnnb_edge.h, gnnb_pna_edge.h)
 
@@ -465,7 +544,7 @@ class GNNModel(nn.Module):
                  gnn_conv: TorchModuleArg, gnn_activation: TorchModuleArg, gnn_skip_connection: bool,
                  global_pooling: GlobalPooling, mlp_head: MLP,
                  output_activation: TorchModuleArgOptional, gnn_p_in: int = 1, gnn_p_hidden: int = 1,
-                 gnn_p_out: int = 1) -> None:
+                 gnn_p_out: int = 1, gnn_heads: int = 1) -> None:
         super().__init__()
         self.graph_input_feature_dim = graph_input_feature_dim
         self.graph_input_edge_dim = graph_input_edge_dim
@@ -487,6 +566,18 @@ class GNNModel(nn.Module):
             conv_kwargs = {"edge_dim": d}
             if self.gnn_conv is GINEConv_GNNB:
                 conv_kwargs["hidden_dim"] = None  # (the MLP's hidden width = out_channels, as for GIN)
+
+        self.gnn_heads = gnn_heads
+        if self.gnn_conv is GATv2Conv_GNNB:
+            if not isinstance(gnn_heads, int) or isinstance(gnn_heads, bool) or not 1 <= gnn_heads <= MAX_GAT_HEADS:
+                raise ValueError(f"a GATv2 model needs gnn_heads, an int in 1 .. {MAX_GAT_HEADS} (got {gnn_heads!r})")
+            widths = [gnn_output_dim] if gnn_num_layers <= 1 else [gnn_hidden_dim, gnn_output_dim]
+            if gnn_num_layers >= 1 and any(w % gnn_heads for w in widths):
+                raise ValueError(f"gnn_hidden_dim and gnn_output_dim ({gnn_hidden_dim}, {gnn_output_dim}) must be divisible by "
+                                 f"gnn_heads ({gnn_heads})")
+            conv_kwargs = {"heads": gnn_heads}
+        elif gnn_heads != 1:
+            raise ValueError(f"gnn_heads={gnn_heads!r}: only a GATv2 model (gnn_conv=GATv2Conv_GNNB) has attention heads")
 
         self.global_pooling = global_pooling
         self.mlp_head = mlp_head  # registered before gnn_convs: parameter order mlp_head_*, gnn_convs_*
@@ -605,6 +696,9 @@ class GNNModel(nn.Module):
                 raise NotImplementedError(f"output_activation {self.output_activation} has no native path "
                                           "(nn.Softmax and nn.LogSoftmax do)")
         conv0 = self.gnn_convs[0] if len(self.gnn_convs) else None
+        gat = {}
+        if self.gnn_conv is GATv2Conv_GNNB:  # (a GCN description on the C side; these two travel beside it: include/gnnb_gat.h)
+            gat = {"heads": int(self.gnn_heads), "negative_slope": float(conv0.negative_slope) if conv0 is not None else 0.2}
         return {
             "conv": _CONV_NAME[self.gnn_conv],
             "num_layers": self.gnn_num_layers,
@@ -622,6 +716,7 @@ class GNNModel(nn.Module):
             "edge_dim": int(self.graph_input_edge_dim) if self.gnn_conv in _EDGE_CONVS else 0,
             "pna_delta": float(conv0.delta_scaler) if isinstance(conv0, (PNAConv_GNNB, PNAEConv_GNNB)) else 1.0,
             "output_activation": out_act,
+            **gat,
         }
 
     def canonical_param_names(self) -> List[str]:
@@ -639,6 +734,7 @@ class GNNModel(nn.Module):
         }
         # (PNA's six, then the edge encoder [in, edge_dim], [in]: the base conv's tensors first, the edge tensors behind)
         per_conv["pnae"] = per_conv["pna"] + ["conv_edge_encoder_weight", "conv_edge_encoder_bias"]
+        per_conv["gatv2"] = ["conv_lin_l_weight", "conv_lin_l_bias", "conv_lin_r_weight", "conv_lin_r_bias", "conv_att", "conv_bias"]
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

@@ -29,6 +29,8 @@ GNNB_ERR_RANGE = -6                                                             
 CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                 # gnnb_conv
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
+MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn"}  # spec["conv"] -> the conv its description carries, where that is another
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -167,6 +169,15 @@ ABI_PNA_EDGE = {
 }
 
 
+# ... and of include/gnnb_gat.h (GATv2 models), in its order (tests/test_abi_gat.py)
+ABI_GAT = {
+    "gnnb_gat_model_num_params": (_I, [_DESC, _I]),
+    "gnnb_gat_model_create": (_I, [_DESC, _I, _F, _PP, _I, _PP]),
+    "gnnb_model_gat_heads": (_I, [_P]),
+    "gnnb_aggregate_gatv2": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -210,7 +221,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
                 "or `make -C gnn-builder_amd/csrc`.  There is no CPU fallback.")
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
-        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE}.items():
+        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -232,7 +243,8 @@ def set_option(name: str, value: int) -> None:
 
 def make_desc(spec: dict) -> ModelDesc:
     d = ModelDesc()
-    d.conv_type = CONV[_EDGE_BASE.get(spec["conv"], spec["conv"])]  # (GINE: GIN's description, "pnae": PNA's; edge_dim beside it)
+    # (GINE: GIN's description, "pnae": PNA's, edge_dim beside it; "gatv2": GCN's, heads and negative_slope beside it)
+    d.conv_type = CONV[_DESC_BASE.get(spec["conv"], spec["conv"])]
     d.num_layers = spec["num_layers"]
     d.in_dim = spec["in_dim"]
     d.hidden_dim = spec["hidden_dim"]
@@ -353,6 +365,7 @@ class CompiledModel:
         self._addons = set()  # what the enable_* calls have allocated beside the workspace: "ingest", "ordered", "edges"
         self._views = {}  # add-on -> (device pointers, views of its whole arrays): _borrowed_views
         self.edge_dim = int(spec.get("edge_dim", 0) or 0) if spec.get("conv") in _EDGE_BASE else 0
+        self.gat_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") == "gatv2" else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
@@ -365,6 +378,7 @@ class CompiledModel:
         num_params, create = ((self.lib.gnnb_pna_edge_model_num_params, self.lib.gnnb_pna_edge_model_create) if spec.get("conv") == "pnae" else
                               (self.lib.gnnb_edge_model_num_params, self.lib.gnnb_edge_model_create))
         n_expect = (num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
+                    self.lib.gnnb_gat_model_num_params(C.byref(self.desc), self.gat_heads) if spec.get("conv") == "gatv2" else
                     self.lib.gnnb_model_num_params(C.byref(self.desc)))
         if n_expect < 0:
             _check(n_expect)
@@ -373,6 +387,9 @@ class CompiledModel:
         arr = (C.c_void_p * len(host))(*[h.ctypes.data for h in host])
         if self.edge_dim:
             _check(create(C.byref(self.desc), self.edge_dim, arr, len(host), C.byref(self._model)))
+        elif spec.get("conv") == "gatv2":  # (gnnb_gat.h: a GCN description, heads and negative_slope beside it)
+            _check(self.lib.gnnb_gat_model_create(C.byref(self.desc), self.gat_heads, float(spec.get("negative_slope", 0.2)), arr, len(host),
+                                                  C.byref(self._model)))
         else:
             _check(self.lib.gnnb_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
         rc = self.lib.gnnb_workspace_create(self._model, self.max_graphs, self.max_nodes, self.max_edges, C.byref(self._ws))
@@ -830,6 +847,41 @@ class CompiledModel:
         out = _out(out, self._N, 4 * w, p)
         _check(self.lib.gnnb_aggregate_pna_edges(self._ws, _dptr(p), _optr(q), ea, ed, _dptr(w_edge), int(w_edge.stride(0)) if w > 1 else ed,
                                                  _dptr(b_edge), _dptr(out), w, _stream_ptr(stream)))
+        return out
+
+    def aggregate_gatv2(self, xl, xr, att, bias=None, skip=None, act: str = "none", heads: int = 1, negative_slope: float = 0.2, out=None,
+                        stream=None):
+        """One GATv2 layer behind its GEMM (``gnnb_aggregate_gatv2``, csrc/k_gatv2.hip) on the prepared batch of a GCN or GATv2
+        model's workspace: ``act(sum_j softmax_j(s_ij) xl_j + bias + skip_i)`` over ``j`` in ``N(i)`` and ``i`` itself, per head,
+        ``s_ij = att_h . leaky_relu(xl_j + xr_i)`` -> [N, width].  ``xl``, ``xr`` [N, width] (column slices of a wider matrix are
+        fine -- the two halves of one [N, 2 width] GEMM output: their row strides are passed on), ``att`` [width] (or PyG's
+        [1, heads, width / heads]), ``bias`` [width] or None, ``skip`` [N, width] or None; ``heads`` 1 .. 8 dividing ``width`` <= 256."""
+        import torch
+        _require_strided(xl, "xl", self._N, 1)
+        w = int(xl.shape[1])
+        _require_strided(xr, "xr", self._N, w)
+        if int(xr.shape[1]) != w or xr.device != xl.device:
+            raise GnnbError(f"xr must be [{self._N}, {w}] on {xl.device}, got {tuple(xr.shape)} on {xr.device}")
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
+            raise GnnbError(f"heads must be an int in 1 .. {MAX_GAT_HEADS}, got {heads!r}")
+        if w > MAX_GAT_WIDTH or w % heads:
+            raise GnnbError(f"width {w}: a GATv2 layer is at most {MAX_GAT_WIDTH} wide and divisible by heads ({heads})")
+        if act not in ACT:
+            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        if not isinstance(att, torch.Tensor) or att.numel() != w:
+            raise GnnbError(f"att must hold {w} values ([{w}] or [1, {heads}, {w // heads}])")
+        att = att.reshape(w)
+        _require(att, "att", torch.float32, 1, w)
+        if bias is not None:
+            _require(bias, "bias", torch.float32, 1, w)
+        if att.device != xl.device or (bias is not None and bias.device != xl.device):
+            raise GnnbError(f"att and bias must be on {xl.device}")
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, xl)
+        out = _out(out, self._N, w, xl)
+        _check(self.lib.gnnb_aggregate_gatv2(self._ws, _dptr(xl), int(xl.stride(0)) if self._N > 1 else w, _dptr(xr),
+                                             int(xr.stride(0)) if self._N > 1 else w, _dptr(att), _optr(bias), _optr(skip), ACT[act], heads,
+                                             float(negative_slope), _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def gine_conv(self, x, edge_attr, w_edge, b_edge, w0, b0, w1, b1, eps: float = 0.0, stream=None):
