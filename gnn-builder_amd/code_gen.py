@@ -28,7 +28,7 @@ import jinja2
 import numpy as np
 import torch
 
-from .models import GATv2Conv_GNNB, GINEConv_GNNB, GNNModel, PNAEConv_GNNB
+from .models import GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, PNAEConv_GNNB
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
 CURRENT_DIR = Path(__file__).resolve().parent
@@ -103,6 +103,11 @@ class Project:
                 "Project does not generate GATv2 designs: the generated shim and the templates have no attention layer (the reference's "
                 "library has a TODO there, gnn_builder_lib.h:2343); run the model through runtime.CompiledModel.from_model(model, ...)"
                 ".forward / forward_pyg")
+        if getattr(model, "gnn_conv", None) is GATv2EConv_GNNB:
+            raise NotImplementedError(
+                "Project does not generate GATv2 designs with edge features: the generated shim and the templates have no attention layer "
+                "and carry no edge attributes; run the model through runtime.CompiledModel.from_model(model, ...).forward_edges / "
+                "forward_pyg_edges")
         self.model = model
         self.dataset = dataset
         self.name = name

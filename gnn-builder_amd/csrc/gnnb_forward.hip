@@ -220,7 +220,12 @@ static int gat_layer(const LayerCtx &c)
     int rc;
     if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_lr, fi, p.b_lr, nullptr, c.rows(lr, 2 * fo), 2 * fo, GNNB_ACT_NONE)))
         return rc;
-    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+    // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+    if (c.M > 0 && c.model->edge_dim) // with edge features (gnnb_gat_edge.h): lin_edge's projection of the batch's edge attributes, inside the score
+        GNNB_HIP_TRY(launch_gatv2_edge_aggregate(c.tv, lr, 2 * fo, lr + fo, 2 * fo, p.att, p.gat_bias, c.skip, d.activation, c.model->gat_heads,
+                                                 c.model->gat_slope, c.edge_attr, c.model->edge_dim, p.w_edge, c.model->edge_dim, c.nxt, fo,
+                                                 c.hs()));
+    else if (c.M > 0)
         GNNB_HIP_TRY(launch_gatv2_aggregate(c.tv, lr, 2 * fo, lr + fo, 2 * fo, p.att, p.gat_bias, c.skip, d.activation, c.model->gat_heads,
                                             c.model->gat_slope, c.nxt, fo, c.hs()));
     return GNNB_OK;

@@ -13,6 +13,7 @@
 #include "gnnb_edge.h"
 #include "gnnb_pna_edge.h"
 #include "gnnb_gat.h"
+#include "gnnb_gat_edge.h"
 
 namespace gnnb {
 
@@ -44,7 +45,8 @@ struct gnnb_model {
     gnnb::HeadArgs *head_dev = nullptr; // the MLP head's {weights, biases, widths} once more in device memory: k_gcn2_zf reads it at the
                                         // end of a workgroup's life (by value the 42 dwords stayed in scalar registers through its stage loop)
     int edge_dim = 0; // > 0: a GINE model (gnnb_edge_model_create) or PNA with edge features (gnnb_pna_edge_model_create: desc.conv_type says which) -- every layer has edge_w [in, edge_dim] and edge_b [in]
-    int gat_heads = 0;      // > 0: a GATv2 model (gnnb_gat_model_create; desc is a GCN description) -- every layer has w_lr, b_lr, att, gat_bias
+    int gat_heads = 0;      // > 0: a GATv2 model (gnnb_gat_model_create; desc is a GCN description) -- every layer has w_lr, b_lr, att, gat_bias;
+                            // with edge_dim > 0 besides: GATv2 with edge features (gnnb_gat_edge_model_create) -- and w_edge [out, edge_dim]
     float gat_slope = 0.0f; // ... and its leaky_relu slope
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)

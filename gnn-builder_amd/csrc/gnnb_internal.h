@@ -315,6 +315,13 @@ hipError_t launch_pna_edge_aggregate(const BatchTables &t, const float *p, const
 constexpr int GAT_MAX_HEADS = 8, GAT_MAX_WIDTH = 256;
 hipError_t launch_gatv2_aggregate(const BatchTables &t, const float *xl, int ldl, const float *xr, int ldr, const float *att, const float *bias,
                                   const float *skip, int act, int heads, float slope, float *out, int width, hipStream_t s);
+// GATv2 with edge features (k_gatv2_edge.hip): the same with s_ij = sum_c att_c leaky_relu(xl_j[c] + xr_i[c] + (W_e e_ij)[c]); edge_attr
+// [E, edge_dim] in COO row order (t.eid maps the CSR slots; nullptr only with num_edges == 0), we [width, edge_dim] at row stride
+// ldwe >= edge_dim, edge_dim 1 .. 16; the self term's attribute is the mean of the row's, and it is taken last.
+// hipErrorInvalidValue: nothing launched
+hipError_t launch_gatv2_edge_aggregate(const BatchTables &t, const float *xl, int ldl, const float *xr, int ldr, const float *att,
+                                       const float *bias, const float *skip, int act, int heads, float slope, const float *edge_attr, int edge_dim,
+                                       const float *we, int ldwe, float *out, int width, hipStream_t s);
 // the ingest's edge attributes in COO row order (k_ingest.hip): out[i] = edge_attr[state[INGEST_STATE_UNSORTED] ? idx[i] : i]; idx:
 // the general path's sorted-position -> input-edge array (nullptr: that path was not launched), state: IngestParams::state
 hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,

@@ -95,14 +95,16 @@ int count_params(const gnnb_model_desc *desc, int edge_dim, int base = GNNB_CONV
 }
 
 // parameter tensors of a GATv2 model (gnnb_gat.h): a GCN description without the fixed-point emulation, heads 1 .. 8 dividing every
-// layer's output width, which is at most 256
-int count_gat_params(const gnnb_model_desc *desc, int heads)
+// layer's output width, which is at most 256; edge_dim != 0: with edge features (gnnb_gat_edge.h), 1 .. 16, one more tensor per layer
+int count_gat_params(const gnnb_model_desc *desc, int heads, int edge_dim = 0)
 {
     int rc = validate_desc(desc);
     if (rc != GNNB_OK)
         return rc;
     if (heads < 1 || heads > GAT_MAX_HEADS)
         return fail(GNNB_ERR_INVALID, "heads %d: a GATv2 model takes 1 .. %d heads", heads, GAT_MAX_HEADS);
+    if (edge_dim != 0 && (edge_dim < 1 || edge_dim > 16))
+        return fail(GNNB_ERR_INVALID, "edge_dim %d: a GATv2 model with edge features takes 1 .. 16 edge attributes", edge_dim);
     if (desc->conv_type != GNNB_CONV_GCN)
         return fail(GNNB_ERR_INVALID, "a GATv2 model's description is a GCN description (conv_type %d given)", desc->conv_type);
     if (desc->fpx_w != 0)
@@ -114,12 +116,12 @@ int count_gat_params(const gnnb_model_desc *desc, int heads)
         if (fo > GAT_MAX_WIDTH)
             return fail(GNNB_ERR_INVALID, "layer %d's output width %d: a GATv2 layer is at most %d wide", l, fo, GAT_MAX_WIDTH);
     }
-    return GAT_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+    return (GAT_PARAM_SLOTS + (edge_dim ? 1 : 0)) * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
 // What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
 // type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
-// (gnnb_gat_model_create: a GCN description)
+// (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features)
 struct ModelKind {
     int edge_dim = 0, base = GNNB_CONV_GIN;
     int gat_heads = 0;
@@ -137,16 +139,22 @@ struct ModelKind {
         k.gat_heads = heads, k.gat_slope = slope;
         return k;
     }
+    static ModelKind gatv2_edges(int heads, float slope, int edge_dim)
+    {
+        ModelKind k = gatv2(heads, slope);
+        k.edge_dim = edge_dim, k.base = GNNB_CONV_GCN;
+        return k;
+    }
 };
 
-// the body of the four *_model_create entries
+// the body of the five *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
         return fail(GNNB_ERR_INVALID, "null out_model");
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads;
-    int expect = gat_heads != 0 ? count_gat_params(desc, gat_heads) : count_params(desc, edge_dim, kind.base);
+    int expect = gat_heads != 0 ? count_gat_params(desc, gat_heads, edge_dim) : count_params(desc, edge_dim, kind.base);
     if (expect < 0)
         return expect;
     if (gat_heads != 0 && !std::isfinite(kind.gat_slope))
@@ -263,6 +271,27 @@ int gnnb_gat_model_create(const gnnb_model_desc *desc, int heads, float negative
 }
 
 int gnnb_model_gat_heads(const gnnb_model *model) { return model ? model->gat_heads : 0; }
+
+int gnnb_gat_edge_model_num_params(const gnnb_model_desc *desc, int heads, int edge_dim)
+{
+    if (edge_dim == 0)
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a GATv2 model with edge features takes 1 .. 16 edge attributes (gnnb_gat_model_num_params: "
+                                      "models without)");
+    return count_gat_params(desc, heads, edge_dim);
+}
+
+int gnnb_gat_edge_model_create(const gnnb_model_desc *desc, int heads, float negative_slope, int edge_dim, const float *const *host_params,
+                               int num_params, gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (heads == 0) // (ModelKind reads 0 as "no GATv2 model")
+        return fail(GNNB_ERR_INVALID, "heads 0: a GATv2 model takes 1 .. %d heads", GAT_MAX_HEADS);
+    if (edge_dim == 0)
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a GATv2 model with edge features takes 1 .. 16 edge attributes (gnnb_gat_model_create: models "
+                                      "without)");
+    return model_create(desc, ModelKind::gatv2_edges(heads, negative_slope, edge_dim), host_params, num_params, out_model);
+}
 
 void gnnb_model_destroy(gnnb_model *model)
 {

@@ -730,6 +730,27 @@ int gnnb_aggregate_gatv2(gnnb_workspace *ws, const float *xl_dev, int ldl, const
     return GNNB_OK;
 }
 
+int gnnb_aggregate_gatv2_edges(gnnb_workspace *ws, const float *xl_dev, int ldl, const float *xr_dev, int ldr, const float *att_dev,
+                               const float *bias_dev, const float *skip_dev, int act, int heads, float negative_slope, const float *edge_attr_dev,
+                               int edge_dim, const float *we_dev, int ldwe, float *out_dev, int width, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gatv2_edges needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type != GNNB_CONV_GCN) // (only there are the tables free of (v, v) edges: the kernel adds the self term)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gatv2_edges takes the prepared batch of a GCN workspace (or a GATv2 model's): graph prep "
+                                      "drops explicit self loops there, the kernel adds the one self term");
+    if (!xl_dev || !xr_dev || !att_dev || !out_dev || heads < 1 || heads > GAT_MAX_HEADS || width < 1 || width > GAT_MAX_WIDTH ||
+        width % heads != 0 || ldl < width || ldr < width || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE || !std::isfinite(negative_slope))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gatv2_edges (heads 1 .. %d dividing width 1 .. %d, ldl and ldr >= width, a "
+                                      "gnnb_act, a finite negative_slope)", GAT_MAX_HEADS, GAT_MAX_WIDTH);
+    if (!we_dev || edge_dim < 1 || edge_dim > 16 || ldwe < edge_dim || (ws->t.num_edges > 0 && !edge_attr_dev))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gatv2_edges (edge_dim 1 .. 16, ldwe >= edge_dim, edge_attr for a batch "
+                                      "with edges)");
+    GNNB_HIP_TRY(launch_gatv2_edge_aggregate(ws->t, xl_dev, ldl, xr_dev, ldr, att_dev, bias_dev, skip_dev, act, heads, negative_slope, edge_attr_dev,
+                                             edge_dim, we_dev, ldwe, out_dev, width, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
 int gnnb_pna_product_aggregate(gnnb_workspace *ws, const float *x_dev, const float *wb_dev, int ldw, float *out_dev, int width,
                                void *stream)
 {

@@ -89,11 +89,14 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //              b_lr [2 out]                         derived: [b_l ; b_r], canonical 1 and 3
 //              att [out]                            canonical 4: conv.att [1, heads, out / heads], head-major
 //              gat_bias [out]                       canonical 5: conv.bias, added behind the aggregate
+//   GATv2 + edges  (gat_heads > 0 and edge_dim > 0, gnnb_gat_edge_model_create) GATv2's slots, and
+//              w_edge [out, edge_dim]               canonical 6: conv.lin_edge.weight (no bias), raw -- what k_gatv2_edge_aggregate
+//                                                   projects the edge attributes with, inside the score
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
     T edge_w = absent_slot<T>(), edge_b = absent_slot<T>();
-    T w_lr = absent_slot<T>(), b_lr = absent_slot<T>(), att = absent_slot<T>(), gat_bias = absent_slot<T>();
+    T w_lr = absent_slot<T>(), b_lr = absent_slot<T>(), att = absent_slot<T>(), gat_bias = absent_slot<T>(), w_edge = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -102,7 +105,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -323,10 +326,10 @@ inline std::vector<float> gat_stack_rows(const float *top, const float *bottom, 
     return s;
 }
 
-constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_gat.h)
+constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_gat.h); one more with edge features (gnnb_gat_edge.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
-// GATv2 model's six in gnnb_gat.h's order) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
+// GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
 // their offsets in the image
 inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0)
 {
@@ -338,6 +341,8 @@ inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, i
         g.b_lr = im.push(gat_stack_rows(p[1], p[3], fo, 1));
         g.att = im.push(p[4], fo);
         g.gat_bias = im.push(p[5], fo);
+        if (edge_dim > 0)
+            g.w_edge = im.push(p[6], fo * (size_t)edge_dim);
         return g;
     }
     // the layer's skip connection (middle layers: y = conv(x) + x, models.py:562-564) where x itself is an operand of
@@ -401,13 +406,13 @@ struct BuiltWeights {
 // The blob of a validated description (gnnb_model_create's checks have passed; edge_dim > 0: a GINE or PNA edge model) from the caller's
 // tensors in canonical order, and where everything is in it.  Blob order: conv layers (canonical + derived tensors), k_gcn2_zf's
 // fragment copy, the GIN stack's copies, the head.  gat_heads > 0: a GATv2 model (a GCN description, six tensors per layer; no
-// fragment copy -- it takes no stack kernel).
+// fragment copy -- it takes no stack kernel); with edge_dim > 0 besides, GATv2 with edge features (seven tensors per layer).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = gat_heads > 0 ? GAT_PARAM_SLOTS : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
+    const int slots = gat_heads > 0 ? GAT_PARAM_SLOTS + (edge_dim ? 1 : 0) : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;
     for (int l = 0; l < d.num_layers; l++, pi += slots)
         lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads);

@@ -331,7 +331,7 @@ class GINEConv_GNNB(nn.Module):
 class GATConv_GNNB(nn.Module):
     """Listed by the reference's SUPPORTED_GNN_CONVS but it has no native kernel for it
     (gnn_builder_lib.h:2343 ``// TODO: GAT layer``; template TODO model.cpp.jinja:141-142);
-    out of scope here as well.  Attention models run as ``GATv2Conv_GNNB`` below."""
+    out of scope here as well.  Attention models run as ``GATv2Conv_GNNB`` below (``GATv2EConv_GNNB`` with edge features)."""
 
     def __init__(self, *args, **kwargs):
         super().__init__()
@@ -354,7 +354,8 @@ class _GATv2Conv(nn.Module):
 
     Self loops are PyG's (``remove_self_loops`` + ``add_self_loops``): explicit ``(v, v)`` edges of the input are removed and
     exactly one is added per node -- the rule ``_GCNConv`` applies.  Parameters: ``lin_l.weight`` [H C, in], ``lin_l.bias``,
-    ``lin_r.weight``, ``lin_r.bias``, ``att`` [1, H, C], ``bias`` [H C]; weights and ``att`` glorot, biases zero."""
+    ``lin_r.weight``, ``lin_r.bias``, ``att`` [1, H, C], ``bias`` [H C]; weights and ``att`` glorot, biases zero.  ``edge_dim=d``
+    is ``_GATv2EConv`` below."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, negative_slope: float = 0.2):
         super().__init__()
@@ -396,6 +397,7 @@ class GATv2Conv_GNNB(nn.Module):
     heads=heads)``.  ``GNNModel(..., gnn_conv=GATv2Conv_GNNB, gnn_heads=H)`` stacks it; ``forward(x, edge_index)``.  The
     accelerated path is ``runtime.CompiledModel.from_model`` with the ordinary ``forward`` / ``forward_pyg`` (C ABI
     ``include/gnnb_gat.h``: one GEMM and one launch of csrc/k_gatv2.hip per layer, the softmax online inside the aggregate).
+    This class ignores ``graph_input_edge_dim`` and ``edge_attr``; scores that see the bond features are ``GATv2EConv_GNNB``'s.
     ``Project`` does not generate such designs."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, negative_slope: float = 0.2, p_in: int = 1,
@@ -415,6 +417,77 @@ class GATv2Conv_GNNB(nn.Module):
 
     def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
         return self.conv(x, edge_index)
+
+class _GATv2EConv(_GATv2Conv):
+    """``_GATv2Conv`` with edge features: PyG's ``GATv2Conv(..., edge_dim=d, fill_value='mean')``.  The edge term enters the score
+    only, the message stays ``xl_j``::
+
+        p_ij = lin_edge(e_ij) [H, C]                     lin_edge: Linear(d, H C, bias=False)
+        s_ij[h] = sum_c att[h, c] * leaky_relu(xl_j[h, c] + xr_i[h, c] + p_ij[h, c])     for j in N(i) u {i}
+
+    Self loops: explicit ``(v, v)`` rows of the input are removed TOGETHER WITH their attribute rows, one self loop is added per
+    node and its attribute is the mean of the attributes of the node's remaining in-edges (taken after the removal; 0 for a node
+    without in-edges).  Parameters: ``_GATv2Conv``'s, then ``lin_edge.weight`` [H C, d], glorot."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, heads: int = 1, negative_slope: float = 0.2):
+        super().__init__(in_channels, out_channels, heads, negative_slope)
+        self.lin_edge = nn.Linear(edge_dim, heads * out_channels, bias=False)
+        _glorot(self.lin_edge.weight)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        n, H, C = x.size(0), self.heads, self.out_channels
+        d = self.lin_edge.in_features
+        edge_attr = edge_attr.reshape(-1, d)
+        if edge_index.numel():
+            keep = edge_index[0] != edge_index[1]
+            edge_index, edge_attr = edge_index[:, keep], edge_attr[keep]
+        loops = torch.arange(n, dtype=torch.long, device=x.device)
+        esrc = edge_index[0].long() if edge_index.numel() else loops[:0]
+        edst = edge_index[1].long() if edge_index.numel() else loops[:0]
+        # fill_value='mean': the self loop's attribute is the mean over the remaining in-edges (count clamped to 1: 0 without any)
+        deg = x.new_zeros(n).index_add(0, edst, x.new_ones(edst.numel()))
+        loop_attr = x.new_zeros(n, d).index_add(0, edst, edge_attr) / deg.clamp(min=1).unsqueeze(-1)
+        src, dst = torch.cat([esrc, loops]), torch.cat([edst, loops])
+        p = self.lin_edge(torch.cat([edge_attr, loop_attr])).view(-1, H, C)
+        xl = self.lin_l(x).view(n, H, C)
+        xr = self.lin_r(x).view(n, H, C)
+        s = (nn.functional.leaky_relu(xl[src] + xr[dst] + p, self.negative_slope) * self.att).sum(dim=-1)  # [E + N, H]
+        idx = dst.unsqueeze(-1).expand(-1, H)
+        smax = s.new_full((n, H), float("-inf")).scatter_reduce(0, idx, s, reduce="amax", include_self=True)
+        e = (s - smax[dst]).exp()
+        a = e / (s.new_zeros(n, H).index_add(0, dst, e)[dst] + 1e-16)
+        out = x.new_zeros(n, H, C).index_add(0, dst, a.unsqueeze(-1) * xl[src])
+        return out.reshape(n, H * C) + self.bias
+
+
+class GATv2EConv_GNNB(nn.Module):
+    """GATv2 with edge features: ``GATv2Conv_GNNB`` whose scores see ``edge_attr`` -- PyG's ``GATv2Conv(in_channels,
+    out_channels // heads, heads=heads, edge_dim=d)``.  ``GNNModel(..., graph_input_edge_dim=d, gnn_conv=GATv2EConv_GNNB,
+    gnn_heads=H)`` builds every layer with ``edge_dim=d`` (1 .. 16) and ``forward(x, edge_index, batch, edge_attr)`` hands the same
+    ``edge_attr`` [E, d] to each.  The accelerated path is ``runtime.CompiledModel.from_model`` with ``forward_edges`` /
+    ``forward_pyg_edges`` (C ABI ``include/gnnb_gat_edge.h``: the edge projection and the scores are formed inside the aggregate
+    kernel, csrc/k_gatv2_edge.hip).  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, heads: int = 1, negative_slope: float = 0.2,
+                 p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
+            raise ValueError(f"heads must be an int in 1 .. {MAX_GAT_HEADS} (got {heads!r})")
+        if out_channels % heads != 0:
+            raise ValueError(f"out_channels ({out_channels}) must be divisible by heads ({heads})")
+        if not isinstance(edge_dim, int) or isinstance(edge_dim, bool) or not 1 <= edge_dim <= 16:
+            raise ValueError(f"edge_dim must be an int in 1 .. 16 (got {edge_dim!r})")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.edge_dim = edge_dim
+        self.heads = heads
+        self.negative_slope = float(negative_slope)
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _GATv2EConv(in_channels, out_channels // heads, edge_dim, heads, self.negative_slope)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        return self.conv(x, edge_index, edge_attr)
 
 
 # --------------------------------------------------------------------------------------- pooling / MLP
@@ -528,11 +601,12 @@ class MLP(nn.Module):
 
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
-                       GATv2Conv_GNNB]
+                       GATv2Conv_GNNB, GATv2EConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
-              PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2"}
-_EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE"}  # convs that take edge_attr, and what the messages call them
-MAX_EDGE_DIM = 16  # of a GINE or PNAE model (include/gnnb_edge.h, gnnb_pna_edge.h)
+              PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e"}
+_EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E"}  # convs that take edge_attr, and what the messages call them
+MAX_EDGE_DIM = 16  # of a GINE, PNAE or GATv2E model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h)
+_GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # convs with attention heads
 
 
 class GNNModel(nn.Module):
@@ -568,14 +642,14 @@ class GNNModel(nn.Module):
                 conv_kwargs["hidden_dim"] = None  # (the MLP's hidden width = out_channels, as for GIN)
 
         self.gnn_heads = gnn_heads
-        if self.gnn_conv is GATv2Conv_GNNB:
+        if self.gnn_conv in _GAT_CONVS:
             if not isinstance(gnn_heads, int) or isinstance(gnn_heads, bool) or not 1 <= gnn_heads <= MAX_GAT_HEADS:
                 raise ValueError(f"a GATv2 model needs gnn_heads, an int in 1 .. {MAX_GAT_HEADS} (got {gnn_heads!r})")
             widths = [gnn_output_dim] if gnn_num_layers <= 1 else [gnn_hidden_dim, gnn_output_dim]
             if gnn_num_layers >= 1 and any(w % gnn_heads for w in widths):
                 raise ValueError(f"gnn_hidden_dim and gnn_output_dim ({gnn_hidden_dim}, {gnn_output_dim}) must be divisible by "
                                  f"gnn_heads ({gnn_heads})")
-            conv_kwargs = {"heads": gnn_heads}
+            conv_kwargs = {**conv_kwargs, "heads": gnn_heads}  # (GATv2E: edge_dim from above stays)
         elif gnn_heads != 1:
             raise ValueError(f"gnn_heads={gnn_heads!r}: only a GATv2 model (gnn_conv=GATv2Conv_GNNB) has attention heads")
 
@@ -614,7 +688,7 @@ class GNNModel(nn.Module):
         (node -> graph index, PyG ``Batch`` convention) every graph is pooled separately ->
         ``[num_graphs, out]``; the reference ignores ``batch`` and pools all nodes into one row
         (models.py:551-553,569; SURVEY finding 3), which has no meaning for independent graphs.
-        ``edge_attr`` [E, graph_input_edge_dim]: a GINE or PNAE model's edge features, the same for every layer (required
+        ``edge_attr`` [E, graph_input_edge_dim]: a GINE, PNAE or GATv2E model's edge features, the same for every layer (required
         there; the other convs ignore it)."""
         gine = self.gnn_conv in _EDGE_CONVS
         if gine and edge_attr is None:
@@ -697,7 +771,7 @@ class GNNModel(nn.Module):
                                           "(nn.Softmax and nn.LogSoftmax do)")
         conv0 = self.gnn_convs[0] if len(self.gnn_convs) else None
         gat = {}
-        if self.gnn_conv is GATv2Conv_GNNB:  # (a GCN description on the C side; these two travel beside it: include/gnnb_gat.h)
+        if self.gnn_conv in _GAT_CONVS:  # (a GCN description on the C side; these two travel beside it: include/gnnb_gat.h)
             gat = {"heads": int(self.gnn_heads), "negative_slope": float(conv0.negative_slope) if conv0 is not None else 0.2}
         return {
             "conv": _CONV_NAME[self.gnn_conv],
@@ -735,6 +809,7 @@ class GNNModel(nn.Module):
         # (PNA's six, then the edge encoder [in, edge_dim], [in]: the base conv's tensors first, the edge tensors behind)
         per_conv["pnae"] = per_conv["pna"] + ["conv_edge_encoder_weight", "conv_edge_encoder_bias"]
         per_conv["gatv2"] = ["conv_lin_l_weight", "conv_lin_l_bias", "conv_lin_r_weight", "conv_lin_r_bias", "conv_att", "conv_bias"]
+        per_conv["gatv2e"] = per_conv["gatv2"] + ["conv_lin_edge_weight"]  # (GATv2's six, then lin_edge [out, edge_dim])
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

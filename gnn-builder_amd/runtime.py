@@ -30,7 +30,9 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn"}  # spec["conv"] -> the conv its description carries, where that is another
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn"}  # spec["conv"] -> the conv its description carries, where that is another
+_EDGE_CONVS = (*_EDGE_BASE, "gatv2e")  # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h)
+_GAT_CONVS = ("gatv2", "gatv2e")       # ... and of those with heads and negative_slope beside it
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -178,6 +180,14 @@ ABI_GAT = {
 }
 
 
+# ... and of include/gnnb_gat_edge.h (GATv2 models with edge features), in its order (tests/test_abi_gat_edge.py)
+ABI_GAT_EDGE = {
+    "gnnb_gat_edge_model_num_params": (_I, [_DESC, _I, _I]),
+    "gnnb_gat_edge_model_create": (_I, [_DESC, _I, _F, _I, _PP, _I, _PP]),
+    "gnnb_aggregate_gatv2_edges": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _P, _I, _P, _I, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -221,7 +231,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
                 "or `make -C gnn-builder_amd/csrc`.  There is no CPU fallback.")
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
-        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT}.items():
+        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -243,7 +253,8 @@ def set_option(name: str, value: int) -> None:
 
 def make_desc(spec: dict) -> ModelDesc:
     d = ModelDesc()
-    # (GINE: GIN's description, "pnae": PNA's, edge_dim beside it; "gatv2": GCN's, heads and negative_slope beside it)
+    # (GINE: GIN's description, "pnae": PNA's, edge_dim beside it; "gatv2": GCN's, heads and negative_slope beside it; "gatv2e": GCN's,
+    # all three beside it)
     d.conv_type = CONV[_DESC_BASE.get(spec["conv"], spec["conv"])]
     d.num_layers = spec["num_layers"]
     d.in_dim = spec["in_dim"]
@@ -364,20 +375,21 @@ class CompiledModel:
         self._keep = None  # its index tensors, which the device still reads
         self._addons = set()  # what the enable_* calls have allocated beside the workspace: "ingest", "ordered", "edges"
         self._views = {}  # add-on -> (device pointers, views of its whole arrays): _borrowed_views
-        self.edge_dim = int(spec.get("edge_dim", 0) or 0) if spec.get("conv") in _EDGE_BASE else 0
-        self.gat_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") == "gatv2" else 0
+        self.edge_dim = int(spec.get("edge_dim", 0) or 0) if spec.get("conv") in _EDGE_CONVS else 0
+        self.gat_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _GAT_CONVS else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
         self.desc = make_desc(spec)
         host = [np.ascontiguousarray(np.asarray(p.detach().cpu().numpy() if hasattr(p, "detach") else p,
                                                 dtype=np.float32)) for p in params]
-        if spec.get("conv") in _EDGE_BASE and not 1 <= self.edge_dim <= MAX_EDGE_DIM:
+        if spec.get("conv") in _EDGE_CONVS and not 1 <= self.edge_dim <= MAX_EDGE_DIM:
             raise GnnbError(f"a {spec['conv'].upper()} model needs spec['edge_dim'] in 1 .. {MAX_EDGE_DIM}, got {spec.get('edge_dim')!r}")
         # (an edge model's own pair of entries: gnnb_edge.h for GINE, gnnb_pna_edge.h for PNA with edge features)
         num_params, create = ((self.lib.gnnb_pna_edge_model_num_params, self.lib.gnnb_pna_edge_model_create) if spec.get("conv") == "pnae" else
                               (self.lib.gnnb_edge_model_num_params, self.lib.gnnb_edge_model_create))
-        n_expect = (num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
+        n_expect = (self.lib.gnnb_gat_edge_model_num_params(C.byref(self.desc), self.gat_heads, self.edge_dim) if spec.get("conv") == "gatv2e" else
+                    num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
                     self.lib.gnnb_gat_model_num_params(C.byref(self.desc), self.gat_heads) if spec.get("conv") == "gatv2" else
                     self.lib.gnnb_model_num_params(C.byref(self.desc)))
         if n_expect < 0:
@@ -385,7 +397,10 @@ class CompiledModel:
         if len(host) != n_expect:
             raise GnnbError(f"model needs {n_expect} parameter tensors, got {len(host)}")
         arr = (C.c_void_p * len(host))(*[h.ctypes.data for h in host])
-        if self.edge_dim:
+        if spec.get("conv") == "gatv2e":  # (gnnb_gat_edge.h: a GCN description, heads, negative_slope and edge_dim beside it)
+            _check(self.lib.gnnb_gat_edge_model_create(C.byref(self.desc), self.gat_heads, float(spec.get("negative_slope", 0.2)), self.edge_dim,
+                                                       arr, len(host), C.byref(self._model)))
+        elif self.edge_dim:
             _check(create(C.byref(self.desc), self.edge_dim, arr, len(host), C.byref(self._model)))
         elif spec.get("conv") == "gatv2":  # (gnnb_gat.h: a GCN description, heads and negative_slope beside it)
             _check(self.lib.gnnb_gat_model_create(C.byref(self.desc), self.gat_heads, float(spec.get("negative_slope", 0.2)), arr, len(host),
@@ -688,7 +703,7 @@ class CompiledModel:
         large-segment setting is left on the workspace; the stage-level entry points work afterwards, on the ORDERED batch."""
         return self._forward_pyg(self.lib.gnnb_forward_pyg_ordered, "ordered", x, edge_index, None, batch, ptr, num_graphs, out, stream)
 
-    # ------------------------------------------------------------------ GINE and PNAE models: forwards with edge attributes
+    # ------------------------------------------------------------------ GINE, PNAE and GATv2E models: forwards with edge attributes
     def _require_edge_attr(self, edge_attr, E: int, like, width: Optional[int] = None):
         """``edge_attr`` of an entry point that reads one [edge_dim] row per edge: fp32 [E, edge_dim] on ``like``'s device; an
         empty batch's may be None.  Returns its device pointer (None: NULL)."""
@@ -702,8 +717,8 @@ class CompiledModel:
 
     def _require_edge_model(self, what: str) -> None:
         if not self.edge_dim:
-            raise GnnbError(f"{what} takes a GINE or PNAE model (a GNNModel of GINEConv_GNNB or PNAEConv_GNNB layers: edge weights); "
-                            "this model has none")
+            raise GnnbError(f"{what} takes a GINE or PNAE model, or GATv2 with edge features (a GNNModel of GINEConv_GNNB, PNAEConv_GNNB or "
+                            "GATv2EConv_GNNB layers: edge weights); this model has none")
 
     def forward_edges(self, x, edge_attr, coo, node_ptr, edge_ptr, out=None, stream=None):
         """``forward`` of a GINE model: ``edge_attr`` [E, edge_dim] fp32, row ``i`` belongs to ``coo`` row ``i``
@@ -882,6 +897,47 @@ class CompiledModel:
         _check(self.lib.gnnb_aggregate_gatv2(self._ws, _dptr(xl), int(xl.stride(0)) if self._N > 1 else w, _dptr(xr),
                                              int(xr.stride(0)) if self._N > 1 else w, _dptr(att), _optr(bias), _optr(skip), ACT[act], heads,
                                              float(negative_slope), _dptr(out), w, _stream_ptr(stream)))
+        return out
+
+    def aggregate_gatv2_edges(self, xl, xr, att, edge_attr, w_edge, bias=None, skip=None, act: str = "none", heads: int = 1,
+                              negative_slope: float = 0.2, out=None, stream=None):
+        """One GATv2 layer with edge features behind its GEMM (``gnnb_aggregate_gatv2_edges``, csrc/k_gatv2_edge.hip) on the prepared
+        batch of a GCN, GATv2 or GATv2E model's workspace: ``aggregate_gatv2`` with ``s_ij = att_h . leaky_relu(xl_j + xr_i +
+        w_edge e_ij)``; the self term's ``e_ii`` is the mean of the row's attribute rows.  ``xl``, ``xr``, ``att``, ``bias``, ``skip``,
+        ``heads`` as there; ``edge_attr`` [E, edge_dim <= 16] in COO order, ``w_edge`` [width, edge_dim] (a column slice of a wider
+        matrix is fine: its row stride is passed on)."""
+        import torch
+        _require_strided(xl, "xl", self._N, 1)
+        w = int(xl.shape[1])
+        _require_strided(xr, "xr", self._N, w)
+        if int(xr.shape[1]) != w or xr.device != xl.device:
+            raise GnnbError(f"xr must be [{self._N}, {w}] on {xl.device}, got {tuple(xr.shape)} on {xr.device}")
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
+            raise GnnbError(f"heads must be an int in 1 .. {MAX_GAT_HEADS}, got {heads!r}")
+        if w > MAX_GAT_WIDTH or w % heads:
+            raise GnnbError(f"width {w}: a GATv2 layer is at most {MAX_GAT_WIDTH} wide and divisible by heads ({heads})")
+        if act not in ACT:
+            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        if not isinstance(att, torch.Tensor) or att.numel() != w:
+            raise GnnbError(f"att must hold {w} values ([{w}] or [1, {heads}, {w // heads}])")
+        att = att.reshape(w)
+        _require(att, "att", torch.float32, 1, w)
+        if bias is not None:
+            _require(bias, "bias", torch.float32, 1, w)
+        if att.device != xl.device or (bias is not None and bias.device != xl.device):
+            raise GnnbError(f"att and bias must be on {xl.device}")
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, xl)
+        _require_strided(w_edge, "w_edge", w, 1)
+        ed = int(w_edge.shape[1])
+        if not 1 <= ed <= MAX_EDGE_DIM or w_edge.device != xl.device:
+            raise GnnbError(f"w_edge must be [{w}, 1 .. {MAX_EDGE_DIM}] on {xl.device}, got {tuple(w_edge.shape)} on {w_edge.device}")
+        ea = self._require_edge_attr(edge_attr, self._E, xl, ed)
+        out = _out(out, self._N, w, xl)
+        _check(self.lib.gnnb_aggregate_gatv2_edges(self._ws, _dptr(xl), int(xl.stride(0)) if self._N > 1 else w, _dptr(xr),
+                                                   int(xr.stride(0)) if self._N > 1 else w, _dptr(att), _optr(bias), _optr(skip), ACT[act],
+                                                   heads, float(negative_slope), ea, ed, _dptr(w_edge), int(w_edge.stride(0)) if w > 1 else ed,
+                                                   _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def gine_conv(self, x, edge_attr, w_edge, b_edge, w0, b0, w1, b1, eps: float = 0.0, stream=None):
