@@ -28,7 +28,7 @@ import jinja2
 import numpy as np
 import torch
 
-from .models import GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, PNAEConv_GNNB
+from .models import GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, PNAEConv_GNNB, TransformerConv_GNNB
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
 CURRENT_DIR = Path(__file__).resolve().parent
@@ -108,6 +108,10 @@ class Project:
                 "Project does not generate GATv2 designs with edge features: the generated shim and the templates have no attention layer "
                 "and carry no edge attributes; run the model through runtime.CompiledModel.from_model(model, ...).forward_edges / "
                 "forward_pyg_edges")
+        if getattr(model, "gnn_conv", None) is TransformerConv_GNNB:
+            raise NotImplementedError(
+                "Project does not generate TransformerConv designs: the generated shim and the templates have no attention layer; run "
+                "the model through runtime.CompiledModel.from_model(model, ...).forward / forward_pyg")
         self.model = model
         self.dataset = dataset
         self.name = name

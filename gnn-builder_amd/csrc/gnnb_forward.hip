@@ -75,7 +75,8 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     G2Deep g;
     g.nl = 0;
     const int L = d.num_layers;
-    if (model->edge_dim || model->gat_heads) // a GINE model: no stack kernel forms the edge term; a GATv2 model: none forms attention
+    // a GINE model: no stack kernel forms the edge term; a GATv2 model, a TransformerConv model: none forms attention
+    if (model->edge_dim || model->gat_heads || model->tf_heads)
         return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
@@ -228,6 +229,27 @@ static int gat_layer(const LayerCtx &c)
     else if (c.M > 0)
         GNNB_HIP_TRY(launch_gatv2_aggregate(c.tv, lr, 2 * fo, lr + fo, 2 * fo, p.att, p.gat_bias, c.skip, d.activation, c.model->gat_heads,
                                             c.model->gat_slope, c.nxt, fo, c.hs()));
+    return GNNB_OK;
+}
+
+// TransformerConv (gnnb_transformer.h; a GIN description with heads beside it, so the tables keep explicit (v, v) edges): ONE GEMM
+// x -> [q | k | v | r] [N, 4 fo] on the stacked weight [W_q ; W_k ; W_v ; W_skip] in the model's math mode (the GEMM launch plan
+// tiles N: 4 fo up to 1024 is one launch), then ONE k_transformer_aggregate launch -- dot-product scores, softmax and the weighted
+// sum of the value rows in one pass over the edges, with the root term, the skip term and the activation in its epilogue.  None of
+// the fused rungs
+static int transformer_layer(const LayerCtx &c)
+{
+    const gnnb_model_desc &d = c.model->desc;
+    const LayerWeights &p = c.model->conv[c.l];
+    const int fi = c.fi, fo = c.fo, heads = c.model->tf_heads;
+    float *qkvr = c.ws->tmp0;
+    int rc;
+    if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_qkvr, fi, p.b_qkvr, nullptr, c.rows(qkvr, 4 * fo), 4 * fo, GNNB_ACT_NONE)))
+        return rc;
+    const float scale = 1.0f / std::sqrt((float)(fo / heads)); // (once on the host: the kernel multiplies each score by it)
+    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+        GNNB_HIP_TRY(launch_transformer_aggregate(c.tv, qkvr, 4 * fo, qkvr + fo, 4 * fo, qkvr + 2 * fo, 4 * fo, qkvr + 3 * fo, 4 * fo, c.skip,
+                                                  d.activation, heads, scale, c.nxt, fo, c.hs()));
     return GNNB_OK;
 }
 
@@ -408,7 +430,7 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
         int rc = GNNB_OK;
         switch (d.conv_type) {
         case GNNB_CONV_GCN: rc = model->gat_heads ? gat_layer(c) : gcn_layer(c); break;
-        case GNNB_CONV_GIN: rc = gin_layer(c); break;
+        case GNNB_CONV_GIN: rc = model->tf_heads ? transformer_layer(c) : gin_layer(c); break;
         case GNNB_CONV_SAGE: rc = sage_layer(c); break;
         case GNNB_CONV_PNA: rc = pna_layer(c); break;
         }
@@ -676,7 +698,7 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
     if (!ws->prepared)
         return fail(GNNB_ERR_INVALID, "workspace has no prepared batch");
     if (memcmp(&model->desc, &ws->desc, sizeof(gnnb_model_desc)) != 0 || model->edge_dim != ws->edge_dim ||
-        model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope)
+        model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope || model->tf_heads != ws->tf_heads)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;

@@ -14,6 +14,7 @@
 #include "gnnb_pna_edge.h"
 #include "gnnb_gat.h"
 #include "gnnb_gat_edge.h"
+#include "gnnb_transformer.h"
 
 namespace gnnb {
 
@@ -48,6 +49,8 @@ struct gnnb_model {
     int gat_heads = 0;      // > 0: a GATv2 model (gnnb_gat_model_create; desc is a GCN description) -- every layer has w_lr, b_lr, att, gat_bias;
                             // with edge_dim > 0 besides: GATv2 with edge features (gnnb_gat_edge_model_create) -- and w_edge [out, edge_dim]
     float gat_slope = 0.0f; // ... and its leaky_relu slope
+    int tf_heads = 0;       // > 0: a TransformerConv model (gnnb_transformer_model_create; desc is a GIN description) -- every layer has
+                            // w_qkvr, b_qkvr and none of GIN's slots.  Its own field: gnnb_model_gat_heads stays 0 for such a model
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };
@@ -69,6 +72,7 @@ struct gnnb_workspace {
     int edge_dim = 0;            // of the model the workspace was created for (0: no edge weights)
     int gat_heads = 0;           // ... and its heads and slope when it is a GATv2 model (0: it is not)
     float gat_slope = 0.0f;
+    int tf_heads = 0;            // ... and its heads when it is a TransformerConv model (0: it is not)
     char *edge_blob = nullptr;   // gnnb_workspace_enable_edge_ingest: edge_attr in COO row order, [max_edges, edge_dim], one allocation
     char *order_blob = nullptr;  // gnnb_workspace_enable_ordered_ingest: the ordered batch and the staged outputs (order_place), one allocation
     int32_t *order_triple = nullptr, *order_triple_dev = nullptr; // host-mapped (first large graph, node row, edge row) of k_order_graphs, and
@@ -107,6 +111,9 @@ int refuse_edge_model(const gnnb_model *model, const gnnb_workspace *ws, const c
 
 // GNNB_OK, or GNNB_ERR_INVALID for a GATv2 model / its workspace at `entry`, which serves the stack kernels' promise only: says which entry runs it
 int refuse_gat_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
+
+// ... and for a TransformerConv model / its workspace (gnnb_transformer.h)
+int refuse_transformer_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
 
 // gnnb_runtime.hip, for the forward (gnnb_forward.hip) -- each is described where it is defined
 int ensure_gcoef(gnnb_workspace *ws, void *stream);

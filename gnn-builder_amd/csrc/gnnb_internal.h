@@ -322,6 +322,14 @@ hipError_t launch_gatv2_aggregate(const BatchTables &t, const float *xl, int ldl
 hipError_t launch_gatv2_edge_aggregate(const BatchTables &t, const float *xl, int ldl, const float *xr, int ldr, const float *att,
                                        const float *bias, const float *skip, int act, int heads, float slope, const float *edge_attr, int edge_dim,
                                        const float *we, int ldwe, float *out, int width, hipStream_t s);
+// TransformerConv (k_transformer.hip): out [N, width] = act((sum_j softmax_j(s_ij) v_j + root_i) + skip_i) over j in N(i) as the tables
+// hold it, per head of width / heads columns, s_ij = (q_i . k_j) * scale; q / k / v / root: rows of stride ldq / ldk / ldv / ldr >=
+// width (the column blocks of one GEMM output), root [N, width] or nullptr (ldr ignored), skip [N, width] or nullptr; tables that
+// keep explicit (v, v) edges (any but a GCN description's): no self term is added.  hipErrorInvalidValue: nothing launched
+constexpr int TF_MAX_HEADS = 8, TF_MAX_WIDTH = 256;
+hipError_t launch_transformer_aggregate(const BatchTables &t, const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
+                                        const float *root, int ldr, const float *skip, int act, int heads, float scale, float *out, int width,
+                                        hipStream_t s);
 // the ingest's edge attributes in COO row order (k_ingest.hip): out[i] = edge_attr[state[INGEST_STATE_UNSORTED] ? idx[i] : i]; idx:
 // the general path's sorted-position -> input-edge array (nullptr: that path was not launched), state: IngestParams::state
 hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,

@@ -119,13 +119,38 @@ int count_gat_params(const gnnb_model_desc *desc, int heads, int edge_dim = 0)
     return (GAT_PARAM_SLOTS + (edge_dim ? 1 : 0)) * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
+// parameter tensors of a TransformerConv model (gnnb_transformer.h): a GIN description (its tables keep explicit (v, v) edges) without
+// the fixed-point emulation, heads 1 .. 8 dividing every layer's output width, which is at most 256
+int count_transformer_params(const gnnb_model_desc *desc, int heads)
+{
+    int rc = validate_desc(desc);
+    if (rc != GNNB_OK)
+        return rc;
+    if (heads < 1 || heads > TF_MAX_HEADS)
+        return fail(GNNB_ERR_INVALID, "heads %d: a TransformerConv model takes 1 .. %d heads", heads, TF_MAX_HEADS);
+    if (desc->conv_type != GNNB_CONV_GIN)
+        return fail(GNNB_ERR_INVALID, "a TransformerConv model's description is a GIN description (conv_type %d given)", desc->conv_type);
+    if (desc->fpx_w != 0)
+        return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover TransformerConv models (fpx_w must be 0)");
+    for (int l = 0; l < desc->num_layers; l++) {
+        const int fo = layer_dims(*desc, l).fout;
+        if (fo % heads != 0)
+            return fail(GNNB_ERR_INVALID, "layer %d's output width %d is not divisible by heads %d", l, fo, heads);
+        if (fo > TF_MAX_WIDTH)
+            return fail(GNNB_ERR_INVALID, "layer %d's output width %d: a TransformerConv layer is at most %d wide", l, fo, TF_MAX_WIDTH);
+    }
+    return TF_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+}
+
 // What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
 // type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
-// (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features)
+// (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features), or heads of a
+// TransformerConv model (gnnb_transformer_model_create: a GIN description)
 struct ModelKind {
     int edge_dim = 0, base = GNNB_CONV_GIN;
     int gat_heads = 0;
     float gat_slope = 0.0f;
+    int tf_heads = 0;
     static ModelKind plain() { return {}; }
     static ModelKind edges(int edge_dim, int base)
     {
@@ -145,16 +170,24 @@ struct ModelKind {
         k.edge_dim = edge_dim, k.base = GNNB_CONV_GCN;
         return k;
     }
+    static ModelKind transformer(int heads)
+    {
+        ModelKind k;
+        k.tf_heads = heads;
+        return k;
+    }
 };
 
-// the body of the five *_model_create entries
+// the body of the six *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
         return fail(GNNB_ERR_INVALID, "null out_model");
     *out_model = nullptr;
-    const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads;
-    int expect = gat_heads != 0 ? count_gat_params(desc, gat_heads, edge_dim) : count_params(desc, edge_dim, kind.base);
+    const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
+    int expect = tf_heads != 0    ? count_transformer_params(desc, tf_heads)
+                 : gat_heads != 0 ? count_gat_params(desc, gat_heads, edge_dim)
+                                  : count_params(desc, edge_dim, kind.base);
     if (expect < 0)
         return expect;
     if (gat_heads != 0 && !std::isfinite(kind.gat_slope))
@@ -168,7 +201,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
         return fail(GNNB_ERR_NO_DEVICE, "no HIP device visible: the MI355X path cannot run");
 
     const gnnb_model_desc &d = *desc;
-    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads);
+    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads);
     const std::vector<float> &img = built.img;
     const WeightLayout &lo = built.layout;
 
@@ -177,6 +210,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     m->edge_dim = edge_dim;
     m->gat_heads = gat_heads;
     m->gat_slope = gat_heads ? kind.gat_slope : 0.0f;
+    m->tf_heads = tf_heads;
     (void)hipGetDevice(&m->device);
     m->blob_floats = img.size();
     hipError_t e = hipMalloc((void **)&m->blob, std::max<size_t>(img.size(), 4) * sizeof(float));
@@ -292,6 +326,20 @@ int gnnb_gat_edge_model_create(const gnnb_model_desc *desc, int heads, float neg
                                       "without)");
     return model_create(desc, ModelKind::gatv2_edges(heads, negative_slope, edge_dim), host_params, num_params, out_model);
 }
+
+int gnnb_transformer_model_num_params(const gnnb_model_desc *desc, int heads) { return count_transformer_params(desc, heads); }
+
+int gnnb_transformer_model_create(const gnnb_model_desc *desc, int heads, const float *const *host_params, int num_params,
+                                  gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (heads == 0) // (ModelKind reads 0 as "no TransformerConv model")
+        return fail(GNNB_ERR_INVALID, "heads 0: a TransformerConv model takes 1 .. %d heads", TF_MAX_HEADS);
+    return model_create(desc, ModelKind::transformer(heads), host_params, num_params, out_model);
+}
+
+int gnnb_model_transformer_heads(const gnnb_model *model) { return model ? model->tf_heads : 0; }
 
 void gnnb_model_destroy(gnnb_model *model)
 {

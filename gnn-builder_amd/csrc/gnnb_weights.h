@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <utility>
 #include <vector>
 
@@ -92,11 +93,17 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //   GATv2 + edges  (gat_heads > 0 and edge_dim > 0, gnnb_gat_edge_model_create) GATv2's slots, and
 //              w_edge [out, edge_dim]               canonical 6: conv.lin_edge.weight (no bias), raw -- what k_gatv2_edge_aggregate
 //                                                   projects the edge attributes with, inside the score
+//   TransformerConv  (gnnb_model::tf_heads > 0, gnnb_transformer_model_create: a GIN description) none of GIN's slots, but
+//              w_qkvr [4 out, in]                   derived: [W_q ; W_k ; W_v ; W_skip], canonical 2 (conv.lin_query.weight), 0
+//                                                   (conv.lin_key.weight), 4 (conv.lin_value.weight), 6 (conv.lin_skip.weight) on top
+//                                                   of each other -- ONE GEMM gives [q | k | v | r] [N, 4 out] (stack_rows)
+//              b_qkvr [4 out]                       derived: [b_q ; b_k ; b_v ; b_skip], canonical 3, 1, 5, 7
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
     T edge_w = absent_slot<T>(), edge_b = absent_slot<T>();
     T w_lr = absent_slot<T>(), b_lr = absent_slot<T>(), att = absent_slot<T>(), gat_bias = absent_slot<T>(), w_edge = absent_slot<T>();
+    T w_qkvr = absent_slot<T>(), b_qkvr = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -105,7 +112,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_qkvr), f(b_qkvr), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -326,15 +333,35 @@ inline std::vector<float> gat_stack_rows(const float *top, const float *bottom, 
     return s;
 }
 
+// TransformerConv: gat_stack_rows for n tensors, the first on top ([W_q ; W_k ; W_v ; W_skip], and with cols = 1 the biases)
+inline std::vector<float> stack_rows(std::initializer_list<const float *> parts, size_t rows_each, size_t cols)
+{
+    std::vector<float> s(parts.size() * rows_each * cols);
+    size_t at = 0;
+    for (const float *p : parts) {
+        memcpy(s.data() + at, p, rows_each * cols * sizeof(float));
+        at += rows_each * cols;
+    }
+    return s;
+}
+
 constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_gat.h); one more with edge features (gnnb_gat_edge.h)
+constexpr int TF_PARAM_SLOTS = 8;  // a TransformerConv layer's canonical tensors (gnnb_transformer.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
 // their offsets in the image
-inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0)
+inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0,
+                                    int tf_heads = 0)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (tf_heads > 0) { // (a GIN description whose layers are TransformerConv's; canonical order: key, query, value, skip)
+        LayerOffsets g;
+        g.w_qkvr = im.push(stack_rows({p[2], p[0], p[4], p[6]}, fo, fi));
+        g.b_qkvr = im.push(stack_rows({p[3], p[1], p[5], p[7]}, fo, 1));
+        return g;
+    }
     if (gat_heads > 0) { // (a GCN description whose layers are GATv2's)
         LayerOffsets g;
         g.w_lr = im.push(gat_stack_rows(p[0], p[2], fo, fi));
@@ -407,20 +434,24 @@ struct BuiltWeights {
 // tensors in canonical order, and where everything is in it.  Blob order: conv layers (canonical + derived tensors), k_gcn2_zf's
 // fragment copy, the GIN stack's copies, the head.  gat_heads > 0: a GATv2 model (a GCN description, six tensors per layer; no
 // fragment copy -- it takes no stack kernel); with edge_dim > 0 besides, GATv2 with edge features (seven tensors per layer).
-inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0)
+// tf_heads > 0: a TransformerConv model (a GIN description, eight tensors per layer; no execution-order copy -- no stack kernel).
+inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
+                                       int tf_heads = 0)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = gat_heads > 0 ? GAT_PARAM_SLOTS + (edge_dim ? 1 : 0) : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
+    const int slots = tf_heads > 0    ? TF_PARAM_SLOTS
+                      : gat_heads > 0 ? GAT_PARAM_SLOTS + (edge_dim ? 1 : 0)
+                                      : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;
     for (int l = 0; l < d.num_layers; l++, pi += slots)
-        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads);
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads);
     const bool have_w1f = gat_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));
-    // (a GINE model takes no stack kernel: no execution-order copy)
-    const bool have_gin = edge_dim == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
+    // (a GINE model, a TransformerConv model take no stack kernel: no execution-order copy)
+    const bool have_gin = edge_dim == 0 && tf_heads == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
                           d.out_dim <= d.hidden_dim && d.out_dim % 4 == 0;
     if (have_gin) {
         const WeightBias g = gin_execution_order(d, im.img, lo.conv);

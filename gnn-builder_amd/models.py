@@ -490,6 +490,72 @@ class GATv2EConv_GNNB(nn.Module):
         return self.conv(x, edge_index, edge_attr)
 
 
+# --------------------------------------------------------------------------------------- TransformerConv
+class _TransformerConv(nn.Module):
+    """PyG's ``TransformerConv(in_channels, out_channels, heads, concat=True, beta=False, dropout=0, edge_dim=None, bias=True,
+    root_weight=True)`` -- the Graph Transformer layer -- with ``out_channels`` PER HEAD, as PyG counts it::
+
+        q = lin_query(x) [N, H, C]   k = lin_key(x) [N, H, C]   v = lin_value(x) [N, H, C]   r = lin_skip(x) [N, H C]
+        s_ij[h] = (q_i[h, :] . k_j[h, :]) / sqrt(C)                        for j in N(i) -- the input's edges as they are
+        a_ij[h] = exp(s_ij[h] - max_j s_ij[h]) / (sum_j exp(s_ij[h] - max_j s_ij[h]) + 1e-16)
+        out_i   = concat_h( sum_j a_ij[h] * v_j[h, :] ) + r_i
+
+    No self loop is added and none is removed: an explicit ``(v, v)`` edge is an ordinary edge, a node without in-edges gets
+    ``lin_skip(x)`` alone.  Modules in PyG's order ``lin_key``, ``lin_query``, ``lin_value``, ``lin_skip``, each
+    ``nn.Linear(in, H C, bias=True)`` with torch's default initialisation (what PyG's ``Linear`` uses); the conv has no
+    parameter of its own.  Out of scope: ``edge_dim``, ``beta=True``, ``concat=False``, ``root_weight=False``, dropout."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1):
+        super().__init__()
+        self.heads = heads
+        self.out_channels = out_channels
+        self.lin_key = nn.Linear(in_channels, heads * out_channels)
+        self.lin_query = nn.Linear(in_channels, heads * out_channels)
+        self.lin_value = nn.Linear(in_channels, heads * out_channels)
+        self.lin_skip = nn.Linear(in_channels, heads * out_channels)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        n, H, C = x.size(0), self.heads, self.out_channels
+        src, dst = edge_index[0].long(), edge_index[1].long()
+        q = self.lin_query(x).view(n, H, C)
+        k = self.lin_key(x).view(n, H, C)
+        v = self.lin_value(x).view(n, H, C)
+        s = (q[dst] * k[src]).sum(dim=-1) / math.sqrt(C)  # [E, H]
+        idx = dst.unsqueeze(-1).expand(-1, H)
+        smax = s.new_full((n, H), float("-inf")).scatter_reduce(0, idx, s, reduce="amax", include_self=True)
+        e = (s - smax[dst]).exp()
+        a = e / (s.new_zeros(n, H).index_add(0, dst, e)[dst] + 1e-16)
+        out = x.new_zeros(n, H, C).index_add(0, dst, a.unsqueeze(-1) * v[src])
+        return out.reshape(n, H * C) + self.lin_skip(x)
+
+
+class TransformerConv_GNNB(nn.Module):
+    """The Graph Transformer layer (no class of the reference): ``out_channels`` is the layer's WHOLE output width, split over
+    ``heads`` (1 .. 8, dividing it) and concatenated, as ``GATv2Conv_GNNB`` counts it -- PyG's ``TransformerConv(in_channels,
+    out_channels // heads, heads=heads)``.  ``GNNModel(..., gnn_conv=TransformerConv_GNNB, gnn_heads=H)`` stacks it;
+    ``forward(x, edge_index)``.  The accelerated path is ``runtime.CompiledModel.from_model`` with the ordinary ``forward`` /
+    ``forward_pyg`` (C ABI ``include/gnnb_transformer.h``: one GEMM ``x -> [q | k | v | r]`` and one launch of
+    csrc/k_transformer.hip per layer, the softmax online inside the aggregate).  This class ignores ``graph_input_edge_dim`` and
+    ``edge_attr``.  Out of scope: ``edge_dim`` (the natural follow-up), ``beta=True``, ``concat=False``, ``root_weight=False``
+    and dropout.  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
+            raise ValueError(f"heads must be an int in 1 .. {MAX_GAT_HEADS} (got {heads!r})")
+        if out_channels % heads != 0:
+            raise ValueError(f"out_channels ({out_channels}) must be divisible by heads ({heads})")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.heads = heads
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _TransformerConv(in_channels, out_channels // heads, heads)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        return self.conv(x, edge_index)
+
+
 # --------------------------------------------------------------------------------------- pooling / MLP
 SUPPORTED_GLOBAL_POOLING_AGGRS = {"add": "SumAggregation", "max": "MaxAggregation", "mean": "MeanAggregation"}
 SUPPORTED_GLOBAL_POOLING_MODE = ["cat"]
@@ -601,12 +667,13 @@ class MLP(nn.Module):
 
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
-                       GATv2Conv_GNNB, GATv2EConv_GNNB]
+                       GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
-              PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e"}
+              PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer"}
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E"}  # convs that take edge_attr, and what the messages call them
 MAX_EDGE_DIM = 16  # of a GINE, PNAE or GATv2E model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h)
-_GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # convs with attention heads
+_GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # the GATv2 convs (heads and negative_slope travel beside a GCN description)
+_HEAD_CONVS = _GAT_CONVS + (TransformerConv_GNNB,)  # convs with attention heads: the ones that take gnn_heads
 
 
 class GNNModel(nn.Module):
@@ -642,9 +709,10 @@ class GNNModel(nn.Module):
                 conv_kwargs["hidden_dim"] = None  # (the MLP's hidden width = out_channels, as for GIN)
 
         self.gnn_heads = gnn_heads
-        if self.gnn_conv in _GAT_CONVS:
+        if self.gnn_conv in _HEAD_CONVS:
             if not isinstance(gnn_heads, int) or isinstance(gnn_heads, bool) or not 1 <= gnn_heads <= MAX_GAT_HEADS:
-                raise ValueError(f"a GATv2 model needs gnn_heads, an int in 1 .. {MAX_GAT_HEADS} (got {gnn_heads!r})")
+                kind = "TransformerConv" if self.gnn_conv is TransformerConv_GNNB else "GATv2"
+                raise ValueError(f"a {kind} model needs gnn_heads, an int in 1 .. {MAX_GAT_HEADS} (got {gnn_heads!r})")
             widths = [gnn_output_dim] if gnn_num_layers <= 1 else [gnn_hidden_dim, gnn_output_dim]
             if gnn_num_layers >= 1 and any(w % gnn_heads for w in widths):
                 raise ValueError(f"gnn_hidden_dim and gnn_output_dim ({gnn_hidden_dim}, {gnn_output_dim}) must be divisible by "
@@ -773,6 +841,8 @@ class GNNModel(nn.Module):
         gat = {}
         if self.gnn_conv in _GAT_CONVS:  # (a GCN description on the C side; these two travel beside it: include/gnnb_gat.h)
             gat = {"heads": int(self.gnn_heads), "negative_slope": float(conv0.negative_slope) if conv0 is not None else 0.2}
+        elif self.gnn_conv is TransformerConv_GNNB:  # (a GIN description on the C side, heads beside it: include/gnnb_transformer.h)
+            gat = {"heads": int(self.gnn_heads)}
         return {
             "conv": _CONV_NAME[self.gnn_conv],
             "num_layers": self.gnn_num_layers,
@@ -810,6 +880,8 @@ class GNNModel(nn.Module):
         per_conv["pnae"] = per_conv["pna"] + ["conv_edge_encoder_weight", "conv_edge_encoder_bias"]
         per_conv["gatv2"] = ["conv_lin_l_weight", "conv_lin_l_bias", "conv_lin_r_weight", "conv_lin_r_bias", "conv_att", "conv_bias"]
         per_conv["gatv2e"] = per_conv["gatv2"] + ["conv_lin_edge_weight"]  # (GATv2's six, then lin_edge [out, edge_dim])
+        # (PyG's registration order: key, query, value, skip -- the C side stacks them as [W_q ; W_k ; W_v ; W_skip])
+        per_conv["transformer"] = [f"conv_lin_{n}_{t}" for n in ("key", "query", "value", "skip") for t in ("weight", "bias")]
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

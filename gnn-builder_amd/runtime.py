@@ -30,9 +30,12 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn"}  # spec["conv"] -> the conv its description carries, where that is another
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
 _EDGE_CONVS = (*_EDGE_BASE, "gatv2e")  # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h)
 _GAT_CONVS = ("gatv2", "gatv2e")       # ... and of those with heads and negative_slope beside it
+# a TransformerConv model (include/gnnb_transformer.h, spec["conv"] == "transformer"): its description is GIN's -- the tables keep
+# explicit (v, v) edges --, heads travels beside it
+MAX_TRANSFORMER_HEADS, MAX_TRANSFORMER_WIDTH = 8, 256
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -188,6 +191,15 @@ ABI_GAT_EDGE = {
 }
 
 
+# ... and of include/gnnb_transformer.h (TransformerConv models), in its order (tests/test_abi_transformer.py)
+ABI_TRANSFORMER = {
+    "gnnb_transformer_model_num_params": (_I, [_DESC, _I]),
+    "gnnb_transformer_model_create": (_I, [_DESC, _I, _PP, _I, _PP]),
+    "gnnb_model_transformer_heads": (_I, [_P]),
+    "gnnb_aggregate_transformer": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _F, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -231,7 +243,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
                 "or `make -C gnn-builder_amd/csrc`.  There is no CPU fallback.")
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
-        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE}.items():
+        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -377,6 +389,7 @@ class CompiledModel:
         self._views = {}  # add-on -> (device pointers, views of its whole arrays): _borrowed_views
         self.edge_dim = int(spec.get("edge_dim", 0) or 0) if spec.get("conv") in _EDGE_CONVS else 0
         self.gat_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _GAT_CONVS else 0
+        self.transformer_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") == "transformer" else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
@@ -391,6 +404,7 @@ class CompiledModel:
         n_expect = (self.lib.gnnb_gat_edge_model_num_params(C.byref(self.desc), self.gat_heads, self.edge_dim) if spec.get("conv") == "gatv2e" else
                     num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
                     self.lib.gnnb_gat_model_num_params(C.byref(self.desc), self.gat_heads) if spec.get("conv") == "gatv2" else
+                    self.lib.gnnb_transformer_model_num_params(C.byref(self.desc), self.transformer_heads) if spec.get("conv") == "transformer" else
                     self.lib.gnnb_model_num_params(C.byref(self.desc)))
         if n_expect < 0:
             _check(n_expect)
@@ -405,6 +419,8 @@ class CompiledModel:
         elif spec.get("conv") == "gatv2":  # (gnnb_gat.h: a GCN description, heads and negative_slope beside it)
             _check(self.lib.gnnb_gat_model_create(C.byref(self.desc), self.gat_heads, float(spec.get("negative_slope", 0.2)), arr, len(host),
                                                   C.byref(self._model)))
+        elif spec.get("conv") == "transformer":  # (gnnb_transformer.h: a GIN description, heads beside it)
+            _check(self.lib.gnnb_transformer_model_create(C.byref(self.desc), self.transformer_heads, arr, len(host), C.byref(self._model)))
         else:
             _check(self.lib.gnnb_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
         rc = self.lib.gnnb_workspace_create(self._model, self.max_graphs, self.max_nodes, self.max_edges, C.byref(self._ws))
@@ -897,6 +913,42 @@ class CompiledModel:
         _check(self.lib.gnnb_aggregate_gatv2(self._ws, _dptr(xl), int(xl.stride(0)) if self._N > 1 else w, _dptr(xr),
                                              int(xr.stride(0)) if self._N > 1 else w, _dptr(att), _optr(bias), _optr(skip), ACT[act], heads,
                                              float(negative_slope), _dptr(out), w, _stream_ptr(stream)))
+        return out
+
+    def aggregate_transformer(self, q, k, v, root=None, skip=None, act: str = "none", heads: int = 1, scale: Optional[float] = None,
+                              out=None, stream=None):
+        """One TransformerConv layer behind its GEMM (``gnnb_aggregate_transformer``, csrc/k_transformer.hip) on the prepared batch
+        of a workspace whose tables keep explicit self loops (any but a GCN or GATv2 model's, which is refused):
+        ``act((sum_j softmax_j(s_ij) v_j + root_i) + skip_i)`` over ``j`` in ``N(i)`` as the batch holds it, per head,
+        ``s_ij = (q_i . k_j) * scale`` -> [N, width].  ``q``, ``k``, ``v`` [N, width] and ``root`` [N, width] or None (column
+        slices of a wider matrix are fine -- the four blocks of one [N, 4 width] GEMM output: their row strides are passed on),
+        ``skip`` [N, width] contiguous or None; ``heads`` 1 .. 8 dividing ``width`` <= 256; ``scale=None``: ``1 / sqrt(width /
+        heads)``."""
+        _require_strided(q, "q", self._N, 1)
+        w = int(q.shape[1])
+        for name, t in (("k", k), ("v", v), ("root", root)):
+            if t is None and name == "root":
+                continue
+            _require_strided(t, name, self._N, w)
+            if int(t.shape[1]) != w or t.device != q.device:
+                raise GnnbError(f"{name} must be [{self._N}, {w}] on {q.device}, got {tuple(t.shape)} on {t.device}")
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_TRANSFORMER_HEADS:
+            raise GnnbError(f"heads must be an int in 1 .. {MAX_TRANSFORMER_HEADS}, got {heads!r}")
+        if w > MAX_TRANSFORMER_WIDTH or w % heads:
+            raise GnnbError(f"width {w}: a TransformerConv layer is at most {MAX_TRANSFORMER_WIDTH} wide and divisible by heads ({heads})")
+        if act not in ACT:
+            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        if scale is None:
+            scale = float(np.float32(1.0) / np.sqrt(np.float32(w // heads)))  # (in fp32, as the layer's own)
+        if not np.isfinite(scale):
+            raise GnnbError(f"scale must be finite, got {scale!r}")
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, q)
+        out = _out(out, self._N, w, q)
+        ld = lambda t: int(t.stride(0)) if self._N > 1 else w  # noqa: E731  (one row: any stride describes it)
+        _check(self.lib.gnnb_aggregate_transformer(self._ws, _dptr(q), ld(q), _dptr(k), ld(k), _dptr(v), ld(v), _optr(root),
+                                                   ld(root) if root is not None else w, _optr(skip), ACT[act], heads, float(scale),
+                                                   _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def aggregate_gatv2_edges(self, xl, xr, att, edge_attr, w_edge, bias=None, skip=None, act: str = "none", heads: int = 1,

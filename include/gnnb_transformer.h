@@ -1,0 +1,88 @@
+/*
+ * gnnb_transformer.h -- extension of the C ABI in gnnb_hip.h (same library, libgnnb_hip.so): TransformerConv models (the Graph
+ * Transformer layer: scaled dot-product attention with a root weight), end to end.  gnnb_hip.h, gnnb_order.h, gnnb_edge.h,
+ * gnnb_pna_edge.h, gnnb_gat.h and gnnb_gat_edge.h are unchanged by these entries (no new version: the library stays at 104).
+ *
+ * Reference: none in gnnbuilder.  The model is TransformerConv_GNNB (gnn-builder_amd/models.py, class _TransformerConv): PyG's
+ * TransformerConv(in, out / heads, heads = H, concat = True, beta = False, dropout = 0, edge_dim = None, bias = True,
+ * root_weight = True),
+ *   q = lin_query(x) [N, H, C],  k = lin_key(x) [N, H, C],  v = lin_value(x) [N, H, C],  r = lin_skip(x) [N, H C],  C = out / H
+ *   s_ij[h]   = (q_i[h, :] . k_j[h, :]) / sqrt(C)                              j in N(i) -- the input's edges as they are
+ *   a_ij[h]   = exp(s_ij[h] - max_j s_ij[h]) / (sum_j exp(s_ij[h] - max_j s_ij[h]) + 1e-16)
+ *   out_i     = concat_h( sum_j a_ij[h] v_j[h, :] ) + r_i
+ * Self loops: none is added and none is removed.  An explicit (v, v) edge of the input is an ordinary edge; a node without
+ * in-edges gets the root term r_i alone.
+ *
+ * Such a model is an ordinary gnnb_model: its description is a GIN description (conv_type = GNNB_CONV_GIN, gin_eps ignored, every
+ * other field as for GIN) and heads (1 .. 8) travels BESIDE it, as it does beside a GATv2 model's GCN description.  The choice
+ * has substance: the tables of a GCN workspace drop explicit (v, v) edges in graph prep (gnnb_hip.h, "Explicit self loops"),
+ * the tables of a GIN workspace keep them -- which is what this layer needs.  gnnb_model_gat_heads is 0 for such a model, as
+ * gnnb_gat.h promises; gnnb_model_transformer_heads reports its heads.
+ *
+ * What such a model runs: layer by layer (gnnb_workspace_last_path: GNNB_PATH_LAYERWISE, whatever the max_graph_nodes and
+ * max_degree promises, which change no bit).  A layer is ONE GEMM, x -> [q | k | v | r] [N, 4 out] on the stacked weight
+ * [W_q ; W_k ; W_v ; W_skip] in the model's math mode, and ONE launch of k_transformer_aggregate (csrc/k_transformer.hip: scores,
+ * softmax and weighted sum in one pass over the edges with an online softmax, nothing per edge in HBM; the root term, the middle
+ * layers' skip term and the activation in its epilogue; plain fp32 in every math mode; scale = 1 / sqrt(C), computed once on the
+ * host).  Then the readout and the output activation as for every model.  No stack kernel, no stage plan, no fixed-point
+ * emulation (fpx_w must be 0), no capture restrictions: nothing in the forward allocates, waits or reads back.
+ *
+ * It has no edge attributes, so the ordinary entries run it: gnnb_forward_batched, gnnb_forward_prepared, gnnb_forward_pyg,
+ * gnnb_forward_batched_host and gnnb_forward_prepared_prep_next.  The _edges entries of gnnb_edge.h refuse it as a model without
+ * edge weights; gnnb_forward_pyg_ordered refuses it and names gnnb_forward_pyg.  A model matches a workspace only if both are
+ * TransformerConv's and heads are equal.
+ *
+ * Out of scope: edge_dim (the natural follow-up: q_i . (k_j + W_e e_ij) = q_i . k_j + (W_e^T q_i) . e_ij and
+ * sum_j a_ij W_e e_ij = W_e sum_j a_ij e_ij, so the edge term can cost edge_dim FMAs per edge and head), beta = True,
+ * concat = False, root_weight = False at model level (the stage entry's root = NULL covers the kernel side), dropout.
+ */
+#ifndef GNNB_TRANSFORMER_H
+#define GNNB_TRANSFORMER_H
+
+#include "gnnb_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Parameter tensors of a TransformerConv model, in gnnb_transformer_model_create's order: per conv layer conv.lin_key.weight
+ * [out, in], conv.lin_key.bias [out], conv.lin_query.weight, .bias, conv.lin_value.weight, .bias, conv.lin_skip.weight, .bias
+ * (models.py _TransformerConv, PyG's registration order; GNNModel.canonical_param_names), then the head's as in
+ * gnnb_model_create: 8 per layer + 2 per head linear.  Negative: a gnnb_status (GNNB_ERR_INVALID: heads outside 1 .. 8, a layer
+ * output width not divisible by heads or above 256, conv_type != GNNB_CONV_GIN, fpx_w != 0, or a description
+ * gnnb_model_num_params refuses). */
+int gnnb_transformer_model_num_params(const gnnb_model_desc *desc, int heads);
+/* gnnb_model_create (load_parameters, model.cpp.jinja:724-730) for such a model (models.py GNNModel with gnn_conv =
+ * TransformerConv_GNNB).  Destroy with gnnb_model_destroy, make its workspace with gnnb_workspace_create. */
+int gnnb_transformer_model_create(const gnnb_model_desc *desc, int heads, const float *const *host_params, int num_params,
+                                  gnnb_model **out_model);
+/* heads of a model of gnnb_transformer_model_create; 0 for every other model (and for NULL) */
+int gnnb_model_transformer_heads(const gnnb_model *model);
+
+/* Stage entry: one TransformerConv layer behind its GEMM,
+ *   out_i = act( (sum_{j in N(i)} a_ij v_j + root_i) + skip_i ),   s_ij[h] = (q_i[h, :] . k_j[h, :]) * scale
+ * on the prepared batch of any workspace whose tables keep explicit self loops (a GIN, GINE, GraphSAGE, PNA or TransformerConv
+ * model's); a GCN, GATv2 or GATv2-with-edges workspace is refused (GNNB_ERR_INVALID: its tables have dropped the (v, v) edges).
+ * q_dev / k_dev / v_dev: rows of `width` floats at row strides ldq / ldk / ldv >= width; root_dev rows at stride ldr >= width, or
+ * NULL (ldr ignored) -- the four column blocks of one [N, 4 width] GEMM output are fine; skip_dev [N, width] or NULL, act a
+ * gnnb_act, heads 1 .. 8 dividing width, width 1 .. 256, a finite scale (the layer passes 1 / sqrt(width / heads)), out_dev
+ * [N, width].  16-byte accesses when (width / heads) % 4 == 0 and q / k / v / root / skip / out and the strides are 16-byte
+ * aligned, scalar accesses otherwise.  fp32 in every math mode.  A row without in-edges gives act(root_i + skip_i), bit for bit;
+ * with root NULL as well act(skip_i), or act(0).  GNNB_ERR_INVALID (nothing launched): an unprepared workspace, a GCN
+ * description's workspace, a NULL operand, heads or width out of range, a stride below width.
+ * Summation order -- fixed by the batch and by the form (16-byte or scalar), never by the grid or by which workgroup took a row;
+ * a repeat launch gives the same bits.  Per (row, head): a score's products per lane over its columns (fma, column increasing),
+ * the lanes' partials in a butterfly, the sum times scale (dot, then scale); the state (m, l, acc) starts at (-inf, 0, 0); the
+ * in-edges in CSR slot order in batches of 4: m' = max(m, s_0 .. s_3), l = l exp(m - m') + (((e_0 + e_1) + e_2) + e_3),
+ * acc = acc exp(m - m') + e_0 v_0 + .. + e_3 v_3 with e_r = exp(s_r - m'); a row of more than 64 in-edges in pieces of 64 slots,
+ * each from (-inf, 0, 0), merged in piece order; out = act((acc / (l + 1e-16) + root) + skip).  exp is the hardware's exp2 of the
+ * argument scaled by log2(e). */
+int gnnb_aggregate_transformer(gnnb_workspace *ws, const float *q_dev, int ldq, const float *k_dev, int ldk,
+                               const float *v_dev, int ldv, const float *root_dev /*[N, width] rows at ldr, or NULL*/, int ldr,
+                               const float *skip_dev /*[N, width] or NULL*/, int act /*gnnb_act*/, int heads, float scale,
+                               float *out_dev /*[N, width]*/, int width, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* GNNB_TRANSFORMER_H */
