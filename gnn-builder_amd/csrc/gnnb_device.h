@@ -1,6 +1,6 @@
 // gnnb_device.h -- device-side helpers shared by the kernel translation units of libgnnb_hip.so (gfx950 only):
 // dynamic-LDS attribute cache, LDS-DMA issue / counted-wait helpers, vector-of-floats helpers, activations, the validation-flag
-// report, wave / workgroup scans, the ptr-array search, the wave match.
+// report, wave / workgroup scans, the ptr-array search, the wave match, the row-walk primitives of the edge and attention aggregates.
 // Everything here is static / inline: each translation unit gets its own copy (the library is built without -fgpu-rdc).
 #pragma once
 #include <algorithm>
@@ -451,6 +451,87 @@ __device__ __forceinline__ void agg_store(const Vf<1> &v, float *p)
         __builtin_nontemporal_store(v.v, p);
     else
         v.store(p);
+}
+
+// ---- row-walk primitives of the aggregates that deal destination rows to lane groups (k_gine, k_pna_edge, the attention
+// aggregates of gnnb_attn.h): a lane's VEC consecutive columns of a row, an edge's attributes, a batch's slot records, a row's record
+template <int VEC>
+__device__ __forceinline__ void row_load_vec(const float *p, float *v)
+{
+    if constexpr (VEC == 4) {
+        const float4 t = *reinterpret_cast<const float4 *>(p);
+        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    } else {
+        v[0] = *p;
+    }
+}
+
+// non-temporal (a vector store with the nt bit): the output is not read again by the kernel and, stored plainly, evicts the rows
+// the gathers hit in L2 (k_pna_edge_aggregate's [N, 4 width] output: 112.8 us against 78.3 at the shape of DESIGN 3.2b)
+template <int VEC>
+__device__ __forceinline__ void row_store_nt(float *p, const float (&v)[VEC])
+{
+    if constexpr (VEC == 4) {
+        const agg_f32x4 t = {v[0], v[1], v[2], v[3]};
+        __builtin_nontemporal_store(t, reinterpret_cast<agg_f32x4 *>(p));
+    } else {
+        __builtin_nontemporal_store(v[0], p);
+    }
+}
+
+// one edge's attributes; avec (wave-uniform): rows of 16-byte pieces at 16-byte aligned addresses
+template <int ED>
+__device__ __forceinline__ void row_load_attr(const float *p, bool avec, float (&e)[ED])
+{
+    if constexpr (ED % 4 == 0) {
+        if (avec) {
+#pragma unroll
+            for (int q = 0; q < ED / 4; q++) {
+                const float4 t = *reinterpret_cast<const float4 *>(p + 4 * q);
+                e[4 * q] = t.x, e[4 * q + 1] = t.y, e[4 * q + 2] = t.z, e[4 * q + 3] = t.w;
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < ED; d++)
+        e[d] = p[d];
+}
+
+// the CSR slots [k, k + R) below k1: source rows clamped into [0, N) -- a malformed table cannot send a load outside; nothing is
+// read for a slot at or past k1
+template <int R>
+__device__ __forceinline__ void row_load_slots(const int32_t *__restrict__ col, int k, int k1, int N, int (&j)[R])
+{
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        j[r] = 0;
+        if (k + r < k1)
+            j[r] = min(max(col[k + r], 0), N - 1);
+    }
+}
+
+// ... and their COO rows, clamped into [0, E)
+template <int R>
+__device__ __forceinline__ void row_load_slots(const int32_t *__restrict__ col, const int32_t *__restrict__ eid, int k, int k1, int N, int E,
+                                               int (&j)[R], int (&ei)[R])
+{
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        j[r] = 0, ei[r] = 0;
+        if (k + r < k1) {
+            j[r] = min(max(col[k + r], 0), N - 1);
+            ei[r] = min(max(eid[k + r], 0), E - 1);
+        }
+    }
+}
+
+// row's start and in-degree from its node record, clamped into the E slots of col / eid
+__device__ __forceinline__ void row_record(const int4 *__restrict__ node_rec, int node, int E, int &rp0, int &deg)
+{
+    const int4 r0 = node_rec[2 * (size_t)node];
+    rp0 = min(max(r0.x, 0), E);
+    deg = min(max(r0.y, 0), E - rp0);
 }
 
 // LGConv normaliser (gnn_builder_lib.h:2383-2386): 1/sqrt(d_i d_j) on IN-degrees, 0 when the product is 0

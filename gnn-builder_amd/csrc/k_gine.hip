@@ -38,42 +38,12 @@ constexpr int GINE_WG_PER_CU = 8;   // workgroups per CU the grid is cut for at 
 constexpr int GINE_MAX_EDGE_DIM = 16;
 
 template <int VEC>
-__device__ __forceinline__ void gine_load_vec(const float *p, float (&v)[VEC])
-{
-    if constexpr (VEC == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
-template <int VEC>
 __device__ __forceinline__ void gine_store_vec(float *p, const float (&v)[VEC])
 {
     if constexpr (VEC == 4)
         *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
     else
         *p = v[0];
-}
-
-// one edge's attributes; avec (wave-uniform): rows of 16-byte pieces at 16-byte aligned addresses
-template <int ED>
-__device__ __forceinline__ void gine_load_attr(const float *p, bool avec, float (&e)[ED])
-{
-    if constexpr (ED % 4 == 0) {
-        if (avec) {
-#pragma unroll
-            for (int q = 0; q < ED / 4; q++) {
-                const float4 t = *reinterpret_cast<const float4 *>(p + 4 * q);
-                e[4 * q] = t.x, e[4 * q + 1] = t.y, e[4 * q + 2] = t.z, e[4 * q + 3] = t.w;
-            }
-            return;
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < ED; d++)
-        e[d] = p[d];
 }
 
 // relu(x_j + W_e e + b_e) of the first n of GINE_R loaded neighbours, added to acc in their order
@@ -95,21 +65,6 @@ __device__ __forceinline__ void gine_add_messages(const float (&xj)[GINE_R][VEC]
         }
 }
 
-// the CSR slots [k, k + GINE_R) below k1: source rows and COO rows, clamped into the buffers (col into [0, N), eid into [0, E)) --
-// a malformed table cannot send a load outside; nothing is read for a slot at or past k1
-__device__ __forceinline__ void gine_load_slots(const int32_t *__restrict__ col, const int32_t *__restrict__ eid, int k, int k1, int N, int E,
-                                                int (&j)[GINE_R], int (&ei)[GINE_R])
-{
-#pragma unroll
-    for (int r = 0; r < GINE_R; r++) {
-        j[r] = 0, ei[r] = 0;
-        if (k + r < k1) {
-            j[r] = min(max(col[k + r], 0), N - 1);
-            ei[r] = min(max(eid[k + r], 0), E - 1);
-        }
-    }
-}
-
 // ... and the first n of those neighbours' x_j (the lane's VEC columns from column fo) and attribute rows
 template <int VEC, int ED>
 __device__ __forceinline__ void gine_load_messages(const float *__restrict__ x, const float *__restrict__ ea, const int (&j)[GINE_R],
@@ -125,8 +80,8 @@ __device__ __forceinline__ void gine_load_messages(const float *__restrict__ x, 
         for (int d = 0; d < ED; d++)
             e[r][d] = 0.0f;
         if (r < n) {
-            gine_load_vec<VEC>(x + (size_t)j[r] * w + fo, xj[r]);
-            gine_load_attr<ED>(ea + (size_t)ei[r] * ED, avec, e[r]);
+            row_load_vec<VEC>(x + (size_t)j[r] * w + fo, xj[r]);
+            row_load_attr<ED>(ea + (size_t)ei[r] * ED, avec, e[r]);
         }
     }
 }
@@ -140,18 +95,10 @@ __device__ __forceinline__ void gine_piece_sum(const float *__restrict__ x, cons
     for (int k = k0; k < k1; k += GINE_R) {
         int j[GINE_R], ei[GINE_R];
         float xj[GINE_R][VEC], e[GINE_R][ED];
-        gine_load_slots(col, eid, k, k1, N, E, j, ei);
+        row_load_slots(col, eid, k, k1, N, E, j, ei);
         gine_load_messages<VEC, ED>(x, ea, j, ei, k1 - k, w, fo, avec, xj, e);
         gine_add_messages<VEC, ED>(xj, e, k1 - k, wgt, bias, acc);
     }
-}
-
-// row's start and in-degree from its node record, clamped into the E slots of col / eid
-__device__ __forceinline__ void gine_row(const int4 *__restrict__ node_rec, int node, int E, int &rp0, int &deg)
-{
-    const int4 r0 = node_rec[2 * (size_t)node];
-    rp0 = min(max(r0.x, 0), E);
-    deg = min(max(r0.y, 0), E - rp0);
 }
 
 template <int VEC, int ED>
@@ -172,7 +119,7 @@ __global__ __launch_bounds__(WG) void k_gine_aggregate(const float *__restrict__
         node = it < iters ? (it * (int)gridDim.x + (int)blockIdx.x) * groups + grp : N;
         rp0 = 0, deg = 0;
         if (node < N)
-            gine_row(node_rec, node, E, rp0, deg);
+            row_record(node_rec, node, E, rp0, deg);
         else
             node = N;
     };
@@ -200,17 +147,17 @@ __global__ __launch_bounds__(WG) void k_gine_aggregate(const float *__restrict__
         int n0, rp_0, dg_0, n1, rp_1, dg_1;
         int j0[GINE_R], e0[GINE_R];
         row_of(0, n0, rp_0, dg_0);
-        gine_load_slots(col, eid, rp_0, rp_0 + (dg_0 <= GINE_CHUNK ? dg_0 : 0), N, E, j0, e0);
+        row_load_slots(col, eid, rp_0, rp_0 + (dg_0 <= GINE_CHUNK ? dg_0 : 0), N, E, j0, e0);
         row_of(1, n1, rp_1, dg_1);
         bool any_long = false;
         for (int it = 0; it < iters; it++) {
             int n2, rp_2, dg_2, j1[GINE_R], e1[GINE_R];
             row_of(it + 2, n2, rp_2, dg_2);
-            gine_load_slots(col, eid, rp_1, rp_1 + (dg_1 <= GINE_CHUNK ? dg_1 : 0), N, E, j1, e1);
+            row_load_slots(col, eid, rp_1, rp_1 + (dg_1 <= GINE_CHUNK ? dg_1 : 0), N, E, j1, e1);
             any_long |= dg_0 > GINE_CHUNK;
             if (n0 < N && dg_0 <= GINE_CHUNK && active) {
                 float xi[VEC], xj[GINE_R][VEC], e[GINE_R][ED], acc[VEC];
-                gine_load_vec<VEC>(x + (size_t)n0 * w + fo, xi);
+                row_load_vec<VEC>(x + (size_t)n0 * w + fo, xi);
                 gine_load_messages<VEC, ED>(x, ea, j0, e0, dg_0, w, fo, avec != 0, xj, e);
 #pragma unroll
                 for (int v = 0; v < VEC; v++)
@@ -245,7 +192,7 @@ __global__ __launch_bounds__(WG) void k_gine_aggregate(const float *__restrict__
                 if (ln < 0)
                     continue;
                 int lrp, ldeg;
-                gine_row(node_rec, ln, E, lrp, ldeg);
+                row_record(node_rec, ln, E, lrp, ldeg);
                 const int npieces = (ldeg + GINE_CHUNK - 1) / GINE_CHUNK;
                 float acc[VEC];
 #pragma unroll
@@ -275,7 +222,7 @@ __global__ __launch_bounds__(WG) void k_gine_aggregate(const float *__restrict__
                 }
                 if (grp == g && active) {
                     float xi[VEC];
-                    gine_load_vec<VEC>(x + (size_t)ln * w + fo, xi);
+                    row_load_vec<VEC>(x + (size_t)ln * w + fo, xi);
                     finish(ln, acc, xi);
                 }
             }

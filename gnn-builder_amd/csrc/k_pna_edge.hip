@@ -50,49 +50,6 @@ struct PnaeStats {
     }
 };
 
-template <int VEC>
-__device__ __forceinline__ void pnae_load_vec(const float *p, float (&v)[VEC])
-{
-    if constexpr (VEC == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
-// non-temporal (a vector store with the nt bit): the [N, 4 width] output is four times the gathered matrix and is not read again by
-// this kernel -- stored plainly it evicts the p rows the gathers hit in L2 (112.8 us against 78.3 at the shape of DESIGN 3.2b)
-template <int VEC>
-__device__ __forceinline__ void pnae_store_vec(float *p, const float (&v)[VEC])
-{
-    if constexpr (VEC == 4) {
-        const agg_f32x4 t = {v[0], v[1], v[2], v[3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<agg_f32x4 *>(p));
-    } else {
-        __builtin_nontemporal_store(v[0], p);
-    }
-}
-
-// one edge's attributes; avec (wave-uniform): rows of 16-byte pieces at 16-byte aligned addresses
-template <int ED>
-__device__ __forceinline__ void pnae_load_attr(const float *p, bool avec, float (&e)[ED])
-{
-    if constexpr (ED % 4 == 0) {
-        if (avec) {
-#pragma unroll
-            for (int q = 0; q < ED / 4; q++) {
-                const float4 t = *reinterpret_cast<const float4 *>(p + 4 * q);
-                e[4 * q] = t.x, e[4 * q + 1] = t.y, e[4 * q + 2] = t.z, e[4 * q + 3] = t.w;
-            }
-            return;
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < ED; d++)
-        e[d] = p[d];
-}
-
 // h = (W_e e + b_e + p_j) + q_i of the first n of PNAE_R loaded neighbours, taken into the statistics in their order
 template <int VEC, int ED>
 __device__ __forceinline__ void pnae_take_messages(const float (&pj)[PNAE_R][VEC], const float (&e)[PNAE_R][ED], int n,
@@ -117,21 +74,6 @@ __device__ __forceinline__ void pnae_take_messages(const float (&pj)[PNAE_R][VEC
         }
 }
 
-// the CSR slots [k, k + PNAE_R) below k1: source rows and COO rows, clamped into the buffers (col into [0, N), eid into [0, E)) --
-// a malformed table cannot send a load outside; nothing is read for a slot at or past k1
-__device__ __forceinline__ void pnae_load_slots(const int32_t *__restrict__ col, const int32_t *__restrict__ eid, int k, int k1, int N, int E,
-                                                int (&j)[PNAE_R], int (&ei)[PNAE_R])
-{
-#pragma unroll
-    for (int r = 0; r < PNAE_R; r++) {
-        j[r] = 0, ei[r] = 0;
-        if (k + r < k1) {
-            j[r] = min(max(col[k + r], 0), N - 1);
-            ei[r] = min(max(eid[k + r], 0), E - 1);
-        }
-    }
-}
-
 // ... and the first n of those neighbours' p_j (the lane's VEC columns from column fo) and attribute rows
 template <int VEC, int ED>
 __device__ __forceinline__ void pnae_load_messages(const float *__restrict__ p, const float *__restrict__ ea, const int (&j)[PNAE_R],
@@ -147,8 +89,8 @@ __device__ __forceinline__ void pnae_load_messages(const float *__restrict__ p, 
         for (int d = 0; d < ED; d++)
             e[r][d] = 0.0f;
         if (r < n) {
-            pnae_load_vec<VEC>(p + (size_t)j[r] * w + fo, pj[r]);
-            pnae_load_attr<ED>(ea + (size_t)ei[r] * ED, avec, e[r]);
+            row_load_vec<VEC>(p + (size_t)j[r] * w + fo, pj[r]);
+            row_load_attr<ED>(ea + (size_t)ei[r] * ED, avec, e[r]);
         }
     }
 }
@@ -162,18 +104,10 @@ __device__ __forceinline__ void pnae_piece(const float *__restrict__ p, const fl
     for (int k = k0; k < k1; k += PNAE_R) {
         int j[PNAE_R], ei[PNAE_R];
         float pj[PNAE_R][VEC], e[PNAE_R][ED];
-        pnae_load_slots(col, eid, k, k1, N, E, j, ei);
+        row_load_slots(col, eid, k, k1, N, E, j, ei);
         pnae_load_messages<VEC, ED>(p, ea, j, ei, k1 - k, w, fo, avec, pj, e);
         pnae_take_messages<VEC, ED>(pj, e, k1 - k, wgt, bias, qi, a);
     }
-}
-
-// row's start and in-degree from its node record, clamped into the E slots of col / eid
-__device__ __forceinline__ void pnae_row(const int4 *__restrict__ node_rec, int node, int E, int &rp0, int &deg)
-{
-    const int4 r0 = node_rec[2 * (size_t)node];
-    rp0 = min(max(r0.x, 0), E);
-    deg = min(max(r0.y, 0), E - rp0);
 }
 
 // (<4, 4> -- 16-byte form, edge_dim 4: bond features -- is asked to fit four waves per SIMD: 127 registers, no scratch, where the
@@ -196,7 +130,7 @@ __global__ __launch_bounds__(WG, (VEC == 4 && ED == 4) ? 4 : 1) void k_pna_edge_
         node = it < iters ? (it * (int)gridDim.x + (int)blockIdx.x) * groups + grp : N;
         rp0 = 0, deg = 0;
         if (node < N)
-            pnae_row(node_rec, node, E, rp0, deg);
+            row_record(node_rec, node, E, rp0, deg);
         else
             node = N;
     };
@@ -216,7 +150,7 @@ __global__ __launch_bounds__(WG, (VEC == 4 && ED == 4) ? 4 : 1) void k_pna_edge_
             for (int v = 0; v < VEC; v++)
                 qi[v] = 0.0f;
             if (q != nullptr)
-                pnae_load_vec<VEC>(q + (size_t)node * w + fo, qi);
+                row_load_vec<VEC>(q + (size_t)node * w + fo, qi);
         };
         auto finish = [&](int node, int deg, const PnaeStats<VEC> &a) { // AggAcc<GNNB_AGG_PNA>::done
             float mx[VEC], mn[VEC], mean[VEC], sd[VEC];
@@ -231,10 +165,10 @@ __global__ __launch_bounds__(WG, (VEC == 4 && ED == 4) ? 4 : 1) void k_pna_edge_
                 }
             }
             float *o = out + (size_t)node * 4 * w + fo;
-            pnae_store_vec<VEC>(o, mx);
-            pnae_store_vec<VEC>(o + w, mn);
-            pnae_store_vec<VEC>(o + 2 * (size_t)w, mean);
-            pnae_store_vec<VEC>(o + 3 * (size_t)w, sd);
+            row_store_nt<VEC>(o, mx);
+            row_store_nt<VEC>(o + w, mn);
+            row_store_nt<VEC>(o + 2 * (size_t)w, mean);
+            row_store_nt<VEC>(o + 3 * (size_t)w, sd);
         };
         // ---- rows of at most PNAE_CHUNK in-edges, no barrier.  Three steps are in flight per lane group, so that a step exposes ONE
         // memory latency, not the chain record -> slots -> rows: the record of step it + 2 and the first PNAE_R slots of step it + 1
@@ -242,13 +176,13 @@ __global__ __launch_bounds__(WG, (VEC == 4 && ED == 4) ? 4 : 1) void k_pna_edge_
         int n0, rp_0, dg_0, n1, rp_1, dg_1;
         int j0[PNAE_R], e0[PNAE_R];
         row_of(0, n0, rp_0, dg_0);
-        pnae_load_slots(col, eid, rp_0, rp_0 + (dg_0 <= PNAE_CHUNK ? dg_0 : 0), N, E, j0, e0);
+        row_load_slots(col, eid, rp_0, rp_0 + (dg_0 <= PNAE_CHUNK ? dg_0 : 0), N, E, j0, e0);
         row_of(1, n1, rp_1, dg_1);
         bool any_long = false;
         for (int it = 0; it < iters; it++) {
             int n2, rp_2, dg_2, j1[PNAE_R], e1[PNAE_R];
             row_of(it + 2, n2, rp_2, dg_2);
-            pnae_load_slots(col, eid, rp_1, rp_1 + (dg_1 <= PNAE_CHUNK ? dg_1 : 0), N, E, j1, e1);
+            row_load_slots(col, eid, rp_1, rp_1 + (dg_1 <= PNAE_CHUNK ? dg_1 : 0), N, E, j1, e1);
             any_long |= dg_0 > PNAE_CHUNK;
             if (n0 < N && dg_0 <= PNAE_CHUNK && active) {
                 float qi[VEC], pj[PNAE_R][VEC], e[PNAE_R][ED];
@@ -286,7 +220,7 @@ __global__ __launch_bounds__(WG, (VEC == 4 && ED == 4) ? 4 : 1) void k_pna_edge_
                 if (ln < 0)
                     continue;
                 int lrp, ldeg;
-                pnae_row(node_rec, ln, E, lrp, ldeg);
+                row_record(node_rec, ln, E, lrp, ldeg);
                 const int npieces = (ldeg + PNAE_CHUNK - 1) / PNAE_CHUNK;
                 float qi[VEC];
                 load_q(ln, qi); // (every piece's messages carry the row's destination term)
