@@ -28,7 +28,8 @@ import jinja2
 import numpy as np
 import torch
 
-from .models import GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, PNAEConv_GNNB, TransformerConv_GNNB
+from .models import (GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, PNAEConv_GNNB, TransformerConv_GNNB,
+                     TransformerEConv_GNNB)
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
 CURRENT_DIR = Path(__file__).resolve().parent
@@ -112,6 +113,11 @@ class Project:
             raise NotImplementedError(
                 "Project does not generate TransformerConv designs: the generated shim and the templates have no attention layer; run "
                 "the model through runtime.CompiledModel.from_model(model, ...).forward / forward_pyg")
+        if getattr(model, "gnn_conv", None) is TransformerEConv_GNNB:
+            raise NotImplementedError(
+                "Project does not generate TransformerConv designs with edge features: the generated shim and the templates have no "
+                "attention layer and carry no edge attributes; run the model through runtime.CompiledModel.from_model(model, ...)"
+                ".forward_edges / forward_pyg_edges")
         self.model = model
         self.dataset = dataset
         self.name = name

@@ -236,7 +236,11 @@ static int gat_layer(const LayerCtx &c)
 // x -> [q | k | v | r] [N, 4 fo] on the stacked weight [W_q ; W_k ; W_v ; W_skip] in the model's math mode (the GEMM launch plan
 // tiles N: 4 fo up to 1024 is one launch), then ONE k_transformer_aggregate launch -- dot-product scores, softmax and the weighted
 // sum of the value rows in one pass over the edges, with the root term, the skip term and the activation in its epilogue.  None of
-// the fused rungs
+// the fused rungs.
+// With edge features (gnnb_transformer_edge.h): the GEMM's weight carries the folded block W_qe behind the four, so the ONE GEMM
+// gives x -> [q | k | v | r | qe] [N, ld], ld = 4 fo + roundup4(heads edge_dim) (at most 1024 + 128 columns: still one launch,
+// the plan tiles N and walks the column tiles of any width), and the ONE launch is k_transformer_edge_aggregate, which takes qe
+// beside q and lin_edge's raw weight for its epilogue
 static int transformer_layer(const LayerCtx &c)
 {
     const gnnb_model_desc &d = c.model->desc;
@@ -244,6 +248,16 @@ static int transformer_layer(const LayerCtx &c)
     const int fi = c.fi, fo = c.fo, heads = c.model->tf_heads;
     float *qkvr = c.ws->tmp0;
     int rc;
+    if (const int ed = c.model->edge_dim) {
+        const int ld = 4 * fo + (int)transformer_edge_qe_rows(heads, ed);
+        if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_qkvre, fi, p.b_qkvre, nullptr, c.rows(qkvr, ld), ld, GNNB_ACT_NONE)))
+            return rc;
+        const float scale = 1.0f / std::sqrt((float)(fo / heads));
+        if (c.M > 0)
+            GNNB_HIP_TRY(launch_transformer_edge_aggregate(c.tv, qkvr, ld, qkvr + fo, ld, qkvr + 2 * fo, ld, qkvr + 4 * fo, ld, qkvr + 3 * fo, ld,
+                                                           c.skip, d.activation, heads, scale, c.edge_attr, ed, p.w_edge, ed, c.nxt, fo, c.hs()));
+        return GNNB_OK;
+    }
     if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_qkvr, fi, p.b_qkvr, nullptr, c.rows(qkvr, 4 * fo), 4 * fo, GNNB_ACT_NONE)))
         return rc;
     const float scale = 1.0f / std::sqrt((float)(fo / heads)); // (once on the host: the kernel multiplies each score by it)

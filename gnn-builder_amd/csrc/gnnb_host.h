@@ -15,6 +15,7 @@
 #include "gnnb_gat.h"
 #include "gnnb_gat_edge.h"
 #include "gnnb_transformer.h"
+#include "gnnb_transformer_edge.h"
 
 namespace gnnb {
 
@@ -50,7 +51,9 @@ struct gnnb_model {
                             // with edge_dim > 0 besides: GATv2 with edge features (gnnb_gat_edge_model_create) -- and w_edge [out, edge_dim]
     float gat_slope = 0.0f; // ... and its leaky_relu slope
     int tf_heads = 0;       // > 0: a TransformerConv model (gnnb_transformer_model_create; desc is a GIN description) -- every layer has
-                            // w_qkvr, b_qkvr and none of GIN's slots.  Its own field: gnnb_model_gat_heads stays 0 for such a model
+                            // w_qkvr, b_qkvr and none of GIN's slots.  Its own field: gnnb_model_gat_heads stays 0 for such a model;
+                            // with edge_dim > 0 besides: TransformerConv with edge features (gnnb_transformer_edge_model_create) --
+                            // w_qkvre, b_qkvre and w_edge [out, edge_dim] instead
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };

@@ -330,6 +330,16 @@ constexpr int TF_MAX_HEADS = 8, TF_MAX_WIDTH = 256;
 hipError_t launch_transformer_aggregate(const BatchTables &t, const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
                                         const float *root, int ldr, const float *skip, int act, int heads, float scale, float *out, int width,
                                         hipStream_t s);
+// TransformerConv with edge features (k_transformer_edge.hip): the same with s_ij = (q_i . k_j + qe_i . e_ij) * scale and
+// out = act(((acc + we aacc) / (l + 1e-16) + root_i) + skip_i), aacc = the softmax-weighted sum of the attribute rows, per head;
+// qe: rows of heads * edge_dim floats at stride ldqe, edge_attr [E, edge_dim] in COO row order (t.eid maps the CSR slots; nullptr
+// only with num_edges == 0), we [width, edge_dim] at row stride ldwe >= edge_dim, edge_dim 1 .. 16.  The kernel computes what it is
+// given: qe = W_e^T q is the caller's business.  hipErrorInvalidValue: nothing launched
+constexpr int TFE_MAX_EDGE_DIM = 16;
+hipError_t launch_transformer_edge_aggregate(const BatchTables &t, const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
+                                             const float *qe, int ldqe, const float *root, int ldr, const float *skip, int act, int heads,
+                                             float scale, const float *edge_attr, int edge_dim, const float *we, int ldwe, float *out, int width,
+                                             hipStream_t s);
 // the ingest's edge attributes in COO row order (k_ingest.hip): out[i] = edge_attr[state[INGEST_STATE_UNSORTED] ? idx[i] : i]; idx:
 // the general path's sorted-position -> input-edge array (nullptr: that path was not launched), state: IngestParams::state
 hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,

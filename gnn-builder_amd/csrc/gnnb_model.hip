@@ -121,7 +121,8 @@ int count_gat_params(const gnnb_model_desc *desc, int heads, int edge_dim = 0)
 
 // parameter tensors of a TransformerConv model (gnnb_transformer.h): a GIN description (its tables keep explicit (v, v) edges) without
 // the fixed-point emulation, heads 1 .. 8 dividing every layer's output width, which is at most 256
-int count_transformer_params(const gnnb_model_desc *desc, int heads)
+// (edge_dim != 0: with edge features, gnnb_transformer_edge.h -- lin_edge's weight is a ninth tensor per layer)
+int count_transformer_params(const gnnb_model_desc *desc, int heads, int edge_dim = 0)
 {
     int rc = validate_desc(desc);
     if (rc != GNNB_OK)
@@ -139,13 +140,17 @@ int count_transformer_params(const gnnb_model_desc *desc, int heads)
         if (fo > TF_MAX_WIDTH)
             return fail(GNNB_ERR_INVALID, "layer %d's output width %d: a TransformerConv layer is at most %d wide", l, fo, TF_MAX_WIDTH);
     }
-    return TF_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+    if (edge_dim != 0 && (edge_dim < 1 || edge_dim > TFE_MAX_EDGE_DIM))
+        return fail(GNNB_ERR_INVALID, "edge_dim %d: a TransformerConv model with edge features takes edge_dim 1 .. %d", edge_dim,
+                    TFE_MAX_EDGE_DIM);
+    return (TF_PARAM_SLOTS + (edge_dim ? 1 : 0)) * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
 // What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
 // type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
 // (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features), or heads of a
-// TransformerConv model (gnnb_transformer_model_create: a GIN description)
+// TransformerConv model (gnnb_transformer_model_create: a GIN description), or heads and edge_dim
+// (gnnb_transformer_edge_model_create: TransformerConv with edge features)
 struct ModelKind {
     int edge_dim = 0, base = GNNB_CONV_GIN;
     int gat_heads = 0;
@@ -176,16 +181,22 @@ struct ModelKind {
         k.tf_heads = heads;
         return k;
     }
+    static ModelKind transformer_edges(int heads, int edge_dim)
+    {
+        ModelKind k = transformer(heads);
+        k.edge_dim = edge_dim;
+        return k;
+    }
 };
 
-// the body of the six *_model_create entries
+// the body of the seven *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
         return fail(GNNB_ERR_INVALID, "null out_model");
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
-    int expect = tf_heads != 0    ? count_transformer_params(desc, tf_heads)
+    int expect = tf_heads != 0    ? count_transformer_params(desc, tf_heads, edge_dim)
                  : gat_heads != 0 ? count_gat_params(desc, gat_heads, edge_dim)
                                   : count_params(desc, edge_dim, kind.base);
     if (expect < 0)
@@ -340,6 +351,25 @@ int gnnb_transformer_model_create(const gnnb_model_desc *desc, int heads, const 
 }
 
 int gnnb_model_transformer_heads(const gnnb_model *model) { return model ? model->tf_heads : 0; }
+
+int gnnb_transformer_edge_model_num_params(const gnnb_model_desc *desc, int heads, int edge_dim)
+{
+    if (edge_dim == 0) // (count_transformer_params reads 0 as "no edge features")
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a TransformerConv model with edge features takes edge_dim 1 .. %d", TFE_MAX_EDGE_DIM);
+    return count_transformer_params(desc, heads, edge_dim);
+}
+
+int gnnb_transformer_edge_model_create(const gnnb_model_desc *desc, int heads, int edge_dim, const float *const *host_params, int num_params,
+                                       gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (heads == 0) // (ModelKind reads 0 as "no TransformerConv model" ...)
+        return fail(GNNB_ERR_INVALID, "heads 0: a TransformerConv model takes 1 .. %d heads", TF_MAX_HEADS);
+    if (edge_dim == 0) // (... and as "no edge features")
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a TransformerConv model with edge features takes edge_dim 1 .. %d", TFE_MAX_EDGE_DIM);
+    return model_create(desc, ModelKind::transformer_edges(heads, edge_dim), host_params, num_params, out_model);
+}
 
 void gnnb_model_destroy(gnnb_model *model)
 {

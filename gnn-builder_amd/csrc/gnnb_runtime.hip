@@ -161,7 +161,8 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
             tmpw = std::max(tmpw, 2 * layer_dims(d, l).fout);
     if (model->tf_heads) // a TransformerConv layer's GEMM writes [q | k | v | r] [N, 4 out] into tmp0
         for (int l = 0; l < d.num_layers; l++)
-            tmpw = std::max(tmpw, 4 * layer_dims(d, l).fout);
+            tmpw = std::max(tmpw, 4 * layer_dims(d, l).fout + // (with edge features: [.. | qe], padded to whole 16-byte pieces)
+                                      (model->edge_dim ? (int)transformer_edge_qe_rows(model->tf_heads, model->edge_dim) : 0));
     // the widest GEMM K of the conv layers: from 1024 on k_linear_dma may cut its tiles along K (stream-K) and needs a scratch,
     // which belongs to the workspace -- forwards of different workspaces never share one, whatever streams or graphs run them
     int max_k = 0;
@@ -782,6 +783,31 @@ int gnnb_aggregate_transformer(gnnb_workspace *ws, const float *q_dev, int ldq, 
                                       "root's ldr >= width, a gnnb_act, a finite scale)", TF_MAX_HEADS, TF_MAX_WIDTH);
     GNNB_HIP_TRY(launch_transformer_aggregate(ws->t, q_dev, ldq, k_dev, ldk, v_dev, ldv, root_dev, ldr, skip_dev, act, heads, scale, out_dev,
                                               width, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_transformer_edges(gnnb_workspace *ws, const float *q_dev, int ldq, const float *k_dev, int ldk, const float *v_dev, int ldv,
+                                     const float *qe_dev, int ldqe, const float *root_dev, int ldr, const float *skip_dev, int act, int heads,
+                                     float scale, const float *edge_attr_dev, int edge_dim, const float *we_dev, int ldwe, float *out_dev,
+                                     int width, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_transformer_edges needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's with or without edge features)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_transformer_edges takes a prepared batch whose tables keep explicit self loops: graph prep "
+                                      "drops the (v, v) edges on a workspace of a GCN description (a GCN or GATv2 model's), and this layer "
+                                      "counts them as ordinary edges, with their attribute rows");
+    if (!q_dev || !k_dev || !v_dev || !out_dev || heads < 1 || heads > TF_MAX_HEADS || width < 1 || width > TF_MAX_WIDTH || width % heads != 0 ||
+        ldq < width || ldk < width || ldv < width || (root_dev && ldr < width) || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE ||
+        !std::isfinite(scale))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_transformer_edges (heads 1 .. %d dividing width 1 .. %d, ldq, ldk, ldv and "
+                                      "root's ldr >= width, a gnnb_act, a finite scale)", TF_MAX_HEADS, TF_MAX_WIDTH);
+    if (!qe_dev || !we_dev || edge_dim < 1 || edge_dim > TFE_MAX_EDGE_DIM || ldqe < heads * edge_dim || ldwe < edge_dim ||
+        (ws->t.num_edges > 0 && !edge_attr_dev))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_transformer_edges (qe and we, edge_dim 1 .. %d, ldqe >= heads * edge_dim, "
+                                      "ldwe >= edge_dim, edge_attr for a batch with edges)", TFE_MAX_EDGE_DIM);
+    GNNB_HIP_TRY(launch_transformer_edge_aggregate(ws->t, q_dev, ldq, k_dev, ldk, v_dev, ldv, qe_dev, ldqe, root_dev, ldr, skip_dev, act, heads,
+                                                   scale, edge_attr_dev, edge_dim, we_dev, ldwe, out_dev, width, (hipStream_t)stream));
     return GNNB_OK;
 }
 

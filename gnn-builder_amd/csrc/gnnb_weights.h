@@ -98,12 +98,20 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //                                                   (conv.lin_key.weight), 4 (conv.lin_value.weight), 6 (conv.lin_skip.weight) on top
 //                                                   of each other -- ONE GEMM gives [q | k | v | r] [N, 4 out] (stack_rows)
 //              b_qkvr [4 out]                       derived: [b_q ; b_k ; b_v ; b_skip], canonical 3, 1, 5, 7
+//   TransformerConv + edges  (tf_heads > 0 and edge_dim > 0, gnnb_transformer_edge_model_create) neither of TransformerConv's slots, but
+//              w_qkvre [4 out + roundup4(heads edge_dim), in]   derived: [W_q ; W_k ; W_v ; W_skip ; W_qe ; 0], W_qe [heads edge_dim, in] =
+//                                                   per head W_e[h]^T W_q[h] (transformer_edge_fold) -- ONE GEMM gives
+//                                                   [q | k | v | r | qe] with qe_i[h] = W_e[h]^T q_i[h]; zero rows up to a multiple of 4
+//              b_qkvre [4 out + roundup4(heads edge_dim)]       derived: [b_q ; b_k ; b_v ; b_skip ; W_e[h]^T b_q[h] ; 0]
+//              w_edge [out, edge_dim]               canonical 8: conv.lin_edge.weight (no bias), raw -- what
+//                                                   k_transformer_edge_aggregate applies to the weighted attribute sum in its epilogue
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
     T edge_w = absent_slot<T>(), edge_b = absent_slot<T>();
     T w_lr = absent_slot<T>(), b_lr = absent_slot<T>(), att = absent_slot<T>(), gat_bias = absent_slot<T>(), w_edge = absent_slot<T>();
     T w_qkvr = absent_slot<T>(), b_qkvr = absent_slot<T>();
+    T w_qkvre = absent_slot<T>(), b_qkvre = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -112,7 +120,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_qkvr), f(b_qkvr), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -345,8 +353,38 @@ inline std::vector<float> stack_rows(std::initializer_list<const float *> parts,
     return s;
 }
 
+// TransformerConv with edge features: the query's edge term as a linear function of x.  q_i[h] . (W_e[h] e) = (W_e[h]^T q_i[h]) . e,
+// and q = W_q x + b_q, so qe_i[h * edge_dim + t] = (W_qe x_i + b_qe)[h * edge_dim + t] with
+//   W_qe[h * edge_dim + t][:] = sum_c W_e[h C + c][t] * W_q[h C + c][:],   b_qe[h * edge_dim + t] = sum_c W_e[h C + c][t] * b_q[h C + c]
+// (C = fo / heads; accumulated in double, c increasing, rounded once -- as pna_edge_projection), padded with zero rows to a multiple
+// of 4 rows: w [roundup4(heads edge_dim), fi], b [roundup4(heads edge_dim)].  w_q [fo, fi], b_q [fo], w_e [fo, edge_dim]
+inline size_t transformer_edge_qe_rows(size_t heads, size_t edge_dim) { return (heads * edge_dim + 3) / 4 * 4; }
+inline WeightBias transformer_edge_fold(const float *w_q, const float *b_q, const float *w_e, size_t fi, size_t fo, size_t heads, size_t edge_dim)
+{
+    const size_t C = fo / heads, rows = transformer_edge_qe_rows(heads, edge_dim);
+    WeightBias f{std::vector<float>(rows * fi, 0.0f), std::vector<float>(rows, 0.0f)};
+    std::vector<double> acc(fi);
+    for (size_t h = 0; h < heads; h++)
+        for (size_t t = 0; t < edge_dim; t++) {
+            std::fill(acc.begin(), acc.end(), 0.0);
+            double ab = 0.0;
+            for (size_t c = 0; c < C; c++) {
+                const double e = (double)w_e[(h * C + c) * edge_dim + t];
+                const float *wq = w_q + (h * C + c) * fi;
+                for (size_t k = 0; k < fi; k++)
+                    acc[k] += e * (double)wq[k];
+                ab += e * (double)b_q[h * C + c];
+            }
+            for (size_t k = 0; k < fi; k++)
+                f.w[(h * edge_dim + t) * fi + k] = (float)acc[k];
+            f.b[h * edge_dim + t] = (float)ab;
+        }
+    return f;
+}
+
 constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_gat.h); one more with edge features (gnnb_gat_edge.h)
-constexpr int TF_PARAM_SLOTS = 8;  // a TransformerConv layer's canonical tensors (gnnb_transformer.h)
+constexpr int TF_PARAM_SLOTS = 8;  // a TransformerConv layer's canonical tensors (gnnb_transformer.h); one more with edge features
+                                   // (gnnb_transformer_edge.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
@@ -356,6 +394,17 @@ inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, i
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (tf_heads > 0 && edge_dim > 0) { // (... with edge features: lin_edge's weight behind the eight; the folded query block)
+        LayerOffsets g;
+        const WeightBias qe = transformer_edge_fold(p[2], p[3], p[8], fi, fo, (size_t)tf_heads, (size_t)edge_dim);
+        std::vector<float> w = stack_rows({p[2], p[0], p[4], p[6]}, fo, fi), b = stack_rows({p[3], p[1], p[5], p[7]}, fo, 1);
+        w.insert(w.end(), qe.w.begin(), qe.w.end());
+        b.insert(b.end(), qe.b.begin(), qe.b.end());
+        g.w_qkvre = im.push(w);
+        g.b_qkvre = im.push(b);
+        g.w_edge = im.push(p[8], fo * (size_t)edge_dim);
+        return g;
+    }
     if (tf_heads > 0) { // (a GIN description whose layers are TransformerConv's; canonical order: key, query, value, skip)
         LayerOffsets g;
         g.w_qkvr = im.push(stack_rows({p[2], p[0], p[4], p[6]}, fo, fi));
@@ -434,14 +483,15 @@ struct BuiltWeights {
 // tensors in canonical order, and where everything is in it.  Blob order: conv layers (canonical + derived tensors), k_gcn2_zf's
 // fragment copy, the GIN stack's copies, the head.  gat_heads > 0: a GATv2 model (a GCN description, six tensors per layer; no
 // fragment copy -- it takes no stack kernel); with edge_dim > 0 besides, GATv2 with edge features (seven tensors per layer).
-// tf_heads > 0: a TransformerConv model (a GIN description, eight tensors per layer; no execution-order copy -- no stack kernel).
+// tf_heads > 0: a TransformerConv model (a GIN description, eight tensors per layer; no execution-order copy -- no stack kernel);
+// with edge_dim > 0 besides, TransformerConv with edge features (nine tensors per layer).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
                                        int tf_heads = 0)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = tf_heads > 0    ? TF_PARAM_SLOTS
+    const int slots = tf_heads > 0    ? TF_PARAM_SLOTS + (edge_dim ? 1 : 0)
                       : gat_heads > 0 ? GAT_PARAM_SLOTS + (edge_dim ? 1 : 0)
                                       : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;

@@ -503,7 +503,8 @@ class _TransformerConv(nn.Module):
     No self loop is added and none is removed: an explicit ``(v, v)`` edge is an ordinary edge, a node without in-edges gets
     ``lin_skip(x)`` alone.  Modules in PyG's order ``lin_key``, ``lin_query``, ``lin_value``, ``lin_skip``, each
     ``nn.Linear(in, H C, bias=True)`` with torch's default initialisation (what PyG's ``Linear`` uses); the conv has no
-    parameter of its own.  Out of scope: ``edge_dim``, ``beta=True``, ``concat=False``, ``root_weight=False``, dropout."""
+    parameter of its own.  ``edge_dim`` is ``_TransformerEConv``'s.  Out of scope: ``beta=True``, ``concat=False``,
+    ``root_weight=False``, dropout."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1):
         super().__init__()
@@ -536,8 +537,8 @@ class TransformerConv_GNNB(nn.Module):
     ``forward(x, edge_index)``.  The accelerated path is ``runtime.CompiledModel.from_model`` with the ordinary ``forward`` /
     ``forward_pyg`` (C ABI ``include/gnnb_transformer.h``: one GEMM ``x -> [q | k | v | r]`` and one launch of
     csrc/k_transformer.hip per layer, the softmax online inside the aggregate).  This class ignores ``graph_input_edge_dim`` and
-    ``edge_attr``.  Out of scope: ``edge_dim`` (the natural follow-up), ``beta=True``, ``concat=False``, ``root_weight=False``
-    and dropout.  ``Project`` does not generate such designs."""
+    ``edge_attr``; attention that sees the bond features is ``TransformerEConv_GNNB``'s.  Out of scope: ``beta=True``,
+    ``concat=False``, ``root_weight=False`` and dropout.  ``Project`` does not generate such designs."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, p_in: int = 1, p_out: int = 1):
         super().__init__()
@@ -554,6 +555,71 @@ class TransformerConv_GNNB(nn.Module):
 
     def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
         return self.conv(x, edge_index)
+
+
+class _TransformerEConv(_TransformerConv):
+    """``_TransformerConv`` with edge features: PyG's ``TransformerConv(..., edge_dim=d)``.  The projected edge attributes are added
+    to the key AND to the value::
+
+        p_ij    = lin_edge(e_ij) [H, C]                                    lin_edge: Linear(d, H C, bias=False)
+        s_ij[h] = (q_i[h, :] . (k_j[h, :] + p_ij[h, :])) / sqrt(C)         for j in N(i) -- the input's edges as they are
+        a_ij[h] = exp(s_ij[h] - max_j s_ij[h]) / (sum_j exp(s_ij[h] - max_j s_ij[h]) + 1e-16)
+        out_i   = concat_h( sum_j a_ij[h] * (v_j[h, :] + p_ij[h, :]) ) + r_i
+
+    No self loop is added and none is removed: an explicit ``(v, v)`` edge is an ordinary edge and so is its attribute row; a node
+    without in-edges gets ``lin_skip(x)`` alone.  Parameters: ``_TransformerConv``'s, then ``lin_edge.weight`` [H C, d] with
+    torch's default ``Linear`` initialisation (what PyG uses there).  This is the layer as it is defined: project, add to key and
+    value.  (The accelerated path evaluates the same sums with the projection moved out of the per-edge work; that is its
+    business, include/gnnb_transformer_edge.h.)"""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, heads: int = 1):
+        super().__init__(in_channels, out_channels, heads)
+        self.lin_edge = nn.Linear(edge_dim, heads * out_channels, bias=False)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        n, H, C = x.size(0), self.heads, self.out_channels
+        src, dst = edge_index[0].long(), edge_index[1].long()
+        p = self.lin_edge(edge_attr.reshape(-1, self.lin_edge.in_features)).view(-1, H, C)
+        q = self.lin_query(x).view(n, H, C)
+        k = self.lin_key(x).view(n, H, C)[src] + p
+        v = self.lin_value(x).view(n, H, C)[src] + p
+        s = (q[dst] * k).sum(dim=-1) / math.sqrt(C)  # [E, H]
+        idx = dst.unsqueeze(-1).expand(-1, H)
+        smax = s.new_full((n, H), float("-inf")).scatter_reduce(0, idx, s, reduce="amax", include_self=True)
+        e = (s - smax[dst]).exp()
+        a = e / (s.new_zeros(n, H).index_add(0, dst, e)[dst] + 1e-16)
+        out = x.new_zeros(n, H, C).index_add(0, dst, a.unsqueeze(-1) * v)
+        return out.reshape(n, H * C) + self.lin_skip(x)
+
+
+class TransformerEConv_GNNB(nn.Module):
+    """The Graph Transformer layer with edge features: ``TransformerConv_GNNB`` whose keys and values see ``edge_attr`` -- PyG's
+    ``TransformerConv(in_channels, out_channels // heads, heads=heads, edge_dim=d)``.  ``GNNModel(..., graph_input_edge_dim=d,
+    gnn_conv=TransformerEConv_GNNB, gnn_heads=H)`` builds every layer with ``edge_dim=d`` (1 .. 16) and
+    ``forward(x, edge_index, batch, edge_attr)`` hands the same ``edge_attr`` [E, d] to each.  The accelerated path is
+    ``runtime.CompiledModel.from_model`` with ``forward_edges`` / ``forward_pyg_edges`` (C ABI
+    ``include/gnnb_transformer_edge.h``: one GEMM ``x -> [q | k | v | r | qe]`` and one launch of csrc/k_transformer_edge.hip per
+    layer).  Out of scope: ``beta=True``, ``concat=False``, ``root_weight=False`` and dropout.  ``Project`` does not generate such
+    designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, heads: int = 1, p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
+            raise ValueError(f"heads must be an int in 1 .. {MAX_GAT_HEADS} (got {heads!r})")
+        if out_channels % heads != 0:
+            raise ValueError(f"out_channels ({out_channels}) must be divisible by heads ({heads})")
+        if not isinstance(edge_dim, int) or isinstance(edge_dim, bool) or not 1 <= edge_dim <= 16:
+            raise ValueError(f"edge_dim must be an int in 1 .. 16 (got {edge_dim!r})")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.edge_dim = edge_dim
+        self.heads = heads
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _TransformerEConv(in_channels, out_channels // heads, edge_dim, heads)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        return self.conv(x, edge_index, edge_attr)
 
 
 # --------------------------------------------------------------------------------------- pooling / MLP
@@ -667,13 +733,16 @@ class MLP(nn.Module):
 
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
-                       GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB]
+                       GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
-              PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer"}
-_EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E"}  # convs that take edge_attr, and what the messages call them
-MAX_EDGE_DIM = 16  # of a GINE, PNAE or GATv2E model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h)
+              PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
+              TransformerEConv_GNNB: "transformere"}
+# convs that take edge_attr, and what the messages call them
+_EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE"}
+MAX_EDGE_DIM = 16  # of a GINE, PNAE, GATv2E or TransformerE model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h, gnnb_transformer_edge.h)
 _GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # the GATv2 convs (heads and negative_slope travel beside a GCN description)
-_HEAD_CONVS = _GAT_CONVS + (TransformerConv_GNNB,)  # convs with attention heads: the ones that take gnn_heads
+_TF_CONVS = (TransformerConv_GNNB, TransformerEConv_GNNB)  # the TransformerConv convs (heads travel beside a GIN description)
+_HEAD_CONVS = _GAT_CONVS + _TF_CONVS  # convs with attention heads: the ones that take gnn_heads
 
 
 class GNNModel(nn.Module):
@@ -711,13 +780,13 @@ class GNNModel(nn.Module):
         self.gnn_heads = gnn_heads
         if self.gnn_conv in _HEAD_CONVS:
             if not isinstance(gnn_heads, int) or isinstance(gnn_heads, bool) or not 1 <= gnn_heads <= MAX_GAT_HEADS:
-                kind = "TransformerConv" if self.gnn_conv is TransformerConv_GNNB else "GATv2"
+                kind = "TransformerConv" if self.gnn_conv in _TF_CONVS else "GATv2"
                 raise ValueError(f"a {kind} model needs gnn_heads, an int in 1 .. {MAX_GAT_HEADS} (got {gnn_heads!r})")
             widths = [gnn_output_dim] if gnn_num_layers <= 1 else [gnn_hidden_dim, gnn_output_dim]
             if gnn_num_layers >= 1 and any(w % gnn_heads for w in widths):
                 raise ValueError(f"gnn_hidden_dim and gnn_output_dim ({gnn_hidden_dim}, {gnn_output_dim}) must be divisible by "
                                  f"gnn_heads ({gnn_heads})")
-            conv_kwargs = {**conv_kwargs, "heads": gnn_heads}  # (GATv2E: edge_dim from above stays)
+            conv_kwargs = {**conv_kwargs, "heads": gnn_heads}  # (GATv2E, TransformerE: edge_dim from above stays)
         elif gnn_heads != 1:
             raise ValueError(f"gnn_heads={gnn_heads!r}: only a GATv2 model (gnn_conv=GATv2Conv_GNNB) has attention heads")
 
@@ -756,7 +825,7 @@ class GNNModel(nn.Module):
         (node -> graph index, PyG ``Batch`` convention) every graph is pooled separately ->
         ``[num_graphs, out]``; the reference ignores ``batch`` and pools all nodes into one row
         (models.py:551-553,569; SURVEY finding 3), which has no meaning for independent graphs.
-        ``edge_attr`` [E, graph_input_edge_dim]: a GINE, PNAE or GATv2E model's edge features, the same for every layer (required
+        ``edge_attr`` [E, graph_input_edge_dim]: a GINE, PNAE, GATv2E or TransformerE model's edge features, the same for every layer (required
         there; the other convs ignore it)."""
         gine = self.gnn_conv in _EDGE_CONVS
         if gine and edge_attr is None:
@@ -841,7 +910,7 @@ class GNNModel(nn.Module):
         gat = {}
         if self.gnn_conv in _GAT_CONVS:  # (a GCN description on the C side; these two travel beside it: include/gnnb_gat.h)
             gat = {"heads": int(self.gnn_heads), "negative_slope": float(conv0.negative_slope) if conv0 is not None else 0.2}
-        elif self.gnn_conv is TransformerConv_GNNB:  # (a GIN description on the C side, heads beside it: include/gnnb_transformer.h)
+        elif self.gnn_conv in _TF_CONVS:  # (a GIN description on the C side, heads beside it: include/gnnb_transformer.h, _edge.h)
             gat = {"heads": int(self.gnn_heads)}
         return {
             "conv": _CONV_NAME[self.gnn_conv],
@@ -882,6 +951,7 @@ class GNNModel(nn.Module):
         per_conv["gatv2e"] = per_conv["gatv2"] + ["conv_lin_edge_weight"]  # (GATv2's six, then lin_edge [out, edge_dim])
         # (PyG's registration order: key, query, value, skip -- the C side stacks them as [W_q ; W_k ; W_v ; W_skip])
         per_conv["transformer"] = [f"conv_lin_{n}_{t}" for n in ("key", "query", "value", "skip") for t in ("weight", "bias")]
+        per_conv["transformere"] = per_conv["transformer"] + ["conv_lin_edge_weight"]  # (the eight, then lin_edge [out, edge_dim])
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

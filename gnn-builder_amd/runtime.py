@@ -30,11 +30,13 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
-_EDGE_CONVS = (*_EDGE_BASE, "gatv2e")  # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h)
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
+# spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h)
+_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere")
 _GAT_CONVS = ("gatv2", "gatv2e")       # ... and of those with heads and negative_slope beside it
 # a TransformerConv model (include/gnnb_transformer.h, spec["conv"] == "transformer"): its description is GIN's -- the tables keep
-# explicit (v, v) edges --, heads travels beside it
+# explicit (v, v) edges --, heads travels beside it; with edge features ("transformere", include/gnnb_transformer_edge.h) edge_dim too
+_TRANSFORMER_CONVS = ("transformer", "transformere")
 MAX_TRANSFORMER_HEADS, MAX_TRANSFORMER_WIDTH = 8, 256
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
@@ -200,6 +202,15 @@ ABI_TRANSFORMER = {
 }
 
 
+# ... and of include/gnnb_transformer_edge.h (TransformerConv models with edge features), in its order
+# (tests/test_abi_transformer_edge.py)
+ABI_TRANSFORMER_EDGE = {
+    "gnnb_transformer_edge_model_num_params": (_I, [_DESC, _I, _I]),
+    "gnnb_transformer_edge_model_create": (_I, [_DESC, _I, _I, _PP, _I, _PP]),
+    "gnnb_aggregate_transformer_edges": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _F, _P, _I, _P, _I, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -243,7 +254,8 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
                 "or `make -C gnn-builder_amd/csrc`.  There is no CPU fallback.")
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
-        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER}.items():
+        for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER,
+                                           **ABI_TRANSFORMER_EDGE}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -389,7 +401,7 @@ class CompiledModel:
         self._views = {}  # add-on -> (device pointers, views of its whole arrays): _borrowed_views
         self.edge_dim = int(spec.get("edge_dim", 0) or 0) if spec.get("conv") in _EDGE_CONVS else 0
         self.gat_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _GAT_CONVS else 0
-        self.transformer_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") == "transformer" else 0
+        self.transformer_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _TRANSFORMER_CONVS else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
@@ -402,6 +414,8 @@ class CompiledModel:
         num_params, create = ((self.lib.gnnb_pna_edge_model_num_params, self.lib.gnnb_pna_edge_model_create) if spec.get("conv") == "pnae" else
                               (self.lib.gnnb_edge_model_num_params, self.lib.gnnb_edge_model_create))
         n_expect = (self.lib.gnnb_gat_edge_model_num_params(C.byref(self.desc), self.gat_heads, self.edge_dim) if spec.get("conv") == "gatv2e" else
+                    self.lib.gnnb_transformer_edge_model_num_params(C.byref(self.desc), self.transformer_heads, self.edge_dim)
+                    if spec.get("conv") == "transformere" else
                     num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
                     self.lib.gnnb_gat_model_num_params(C.byref(self.desc), self.gat_heads) if spec.get("conv") == "gatv2" else
                     self.lib.gnnb_transformer_model_num_params(C.byref(self.desc), self.transformer_heads) if spec.get("conv") == "transformer" else
@@ -414,6 +428,9 @@ class CompiledModel:
         if spec.get("conv") == "gatv2e":  # (gnnb_gat_edge.h: a GCN description, heads, negative_slope and edge_dim beside it)
             _check(self.lib.gnnb_gat_edge_model_create(C.byref(self.desc), self.gat_heads, float(spec.get("negative_slope", 0.2)), self.edge_dim,
                                                        arr, len(host), C.byref(self._model)))
+        elif spec.get("conv") == "transformere":  # (gnnb_transformer_edge.h: a GIN description, heads and edge_dim beside it)
+            _check(self.lib.gnnb_transformer_edge_model_create(C.byref(self.desc), self.transformer_heads, self.edge_dim, arr, len(host),
+                                                               C.byref(self._model)))
         elif self.edge_dim:
             _check(create(C.byref(self.desc), self.edge_dim, arr, len(host), C.byref(self._model)))
         elif spec.get("conv") == "gatv2":  # (gnnb_gat.h: a GCN description, heads and negative_slope beside it)
@@ -719,7 +736,7 @@ class CompiledModel:
         large-segment setting is left on the workspace; the stage-level entry points work afterwards, on the ORDERED batch."""
         return self._forward_pyg(self.lib.gnnb_forward_pyg_ordered, "ordered", x, edge_index, None, batch, ptr, num_graphs, out, stream)
 
-    # ------------------------------------------------------------------ GINE, PNAE and GATv2E models: forwards with edge attributes
+    # ------------------------------------------------------------------ GINE, PNAE, GATv2E and TransformerE models: forwards with edge attributes
     def _require_edge_attr(self, edge_attr, E: int, like, width: Optional[int] = None):
         """``edge_attr`` of an entry point that reads one [edge_dim] row per edge: fp32 [E, edge_dim] on ``like``'s device; an
         empty batch's may be None.  Returns its device pointer (None: NULL)."""
@@ -949,6 +966,51 @@ class CompiledModel:
         _check(self.lib.gnnb_aggregate_transformer(self._ws, _dptr(q), ld(q), _dptr(k), ld(k), _dptr(v), ld(v), _optr(root),
                                                    ld(root) if root is not None else w, _optr(skip), ACT[act], heads, float(scale),
                                                    _dptr(out), w, _stream_ptr(stream)))
+        return out
+
+    def aggregate_transformer_edges(self, q, k, v, qe, edge_attr, w_edge, root=None, skip=None, act: str = "none", heads: int = 1,
+                                    scale: Optional[float] = None, out=None, stream=None):
+        """One TransformerConv layer with edge features behind its GEMM (``gnnb_aggregate_transformer_edges``,
+        csrc/k_transformer_edge.hip) on the prepared batch of a workspace whose tables keep explicit self loops:
+        ``aggregate_transformer`` with ``s_ij = (q_i . k_j + qe_i[h] . e_ij) * scale`` and ``w_edge (sum_j softmax_j e_ij)`` added to
+        the weighted sum of the value rows, per head.  ``q``, ``k``, ``v``, ``root``, ``skip``, ``heads``, ``scale`` as there;
+        ``qe`` [N, heads * edge_dim] (the layer passes ``W_e[h]^T q_i[h]``; the entry computes what it is given), ``edge_attr``
+        [E, edge_dim <= 16] in COO order, ``w_edge`` [width, edge_dim]; column slices of wider matrices are fine for ``qe`` and
+        ``w_edge`` too: their row strides are passed on."""
+        _require_strided(q, "q", self._N, 1)
+        w = int(q.shape[1])
+        for name, t in (("k", k), ("v", v), ("root", root)):
+            if t is None and name == "root":
+                continue
+            _require_strided(t, name, self._N, w)
+            if int(t.shape[1]) != w or t.device != q.device:
+                raise GnnbError(f"{name} must be [{self._N}, {w}] on {q.device}, got {tuple(t.shape)} on {t.device}")
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_TRANSFORMER_HEADS:
+            raise GnnbError(f"heads must be an int in 1 .. {MAX_TRANSFORMER_HEADS}, got {heads!r}")
+        if w > MAX_TRANSFORMER_WIDTH or w % heads:
+            raise GnnbError(f"width {w}: a TransformerConv layer is at most {MAX_TRANSFORMER_WIDTH} wide and divisible by heads ({heads})")
+        if act not in ACT:
+            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        if scale is None:
+            scale = float(np.float32(1.0) / np.sqrt(np.float32(w // heads)))  # (in fp32, as the layer's own)
+        if not np.isfinite(scale):
+            raise GnnbError(f"scale must be finite, got {scale!r}")
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, q)
+        _require_strided(w_edge, "w_edge", w, 1)
+        ed = int(w_edge.shape[1])
+        if not 1 <= ed <= MAX_EDGE_DIM or w_edge.device != q.device:
+            raise GnnbError(f"w_edge must be [{w}, 1 .. {MAX_EDGE_DIM}] on {q.device}, got {tuple(w_edge.shape)} on {w_edge.device}")
+        _require_strided(qe, "qe", self._N, heads * ed)
+        if int(qe.shape[1]) != heads * ed or qe.device != q.device:
+            raise GnnbError(f"qe must be [{self._N}, heads * edge_dim = {heads * ed}] on {q.device}, got {tuple(qe.shape)} on {qe.device}")
+        ea = self._require_edge_attr(edge_attr, self._E, q, ed)
+        out = _out(out, self._N, w, q)
+        ld = lambda t, cols: int(t.stride(0)) if self._N > 1 else cols  # noqa: E731  (one row: any stride describes it)
+        _check(self.lib.gnnb_aggregate_transformer_edges(self._ws, _dptr(q), ld(q, w), _dptr(k), ld(k, w), _dptr(v), ld(v, w), _dptr(qe),
+                                                         ld(qe, heads * ed), _optr(root), ld(root, w) if root is not None else w, _optr(skip),
+                                                         ACT[act], heads, float(scale), ea, ed, _dptr(w_edge),
+                                                         int(w_edge.stride(0)) if w > 1 else ed, _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def aggregate_gatv2_edges(self, xl, xr, att, edge_attr, w_edge, bias=None, skip=None, act: str = "none", heads: int = 1,

@@ -32,8 +32,7 @@
  * edge weights; gnnb_forward_pyg_ordered refuses it and names gnnb_forward_pyg.  A model matches a workspace only if both are
  * TransformerConv's and heads are equal.
  *
- * Out of scope: edge_dim (the natural follow-up: q_i . (k_j + W_e e_ij) = q_i . k_j + (W_e^T q_i) . e_ij and
- * sum_j a_ij W_e e_ij = W_e sum_j a_ij e_ij, so the edge term can cost edge_dim FMAs per edge and head), beta = True,
+ * edge_dim = d is gnnb_transformer_edge.h's (a model kind of its own, run by the _edges entries).  Out of scope: beta = True,
  * concat = False, root_weight = False at model level (the stage entry's root = NULL covers the kernel side), dropout.
  */
 #ifndef GNNB_TRANSFORMER_H
