@@ -28,8 +28,8 @@ import jinja2
 import numpy as np
 import torch
 
-from .models import (GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, PNAEConv_GNNB, TransformerConv_GNNB,
-                     TransformerEConv_GNNB)
+from .models import (GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, PNAEConv_GNNB, ResGatedGraphConv_GNNB,
+                     TransformerConv_GNNB, TransformerEConv_GNNB)
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
 CURRENT_DIR = Path(__file__).resolve().parent
@@ -118,6 +118,10 @@ class Project:
                 "Project does not generate TransformerConv designs with edge features: the generated shim and the templates have no "
                 "attention layer and carry no edge attributes; run the model through runtime.CompiledModel.from_model(model, ...)"
                 ".forward_edges / forward_pyg_edges")
+        if getattr(model, "gnn_conv", None) is ResGatedGraphConv_GNNB:
+            raise NotImplementedError(
+                "Project does not generate ResGatedGraphConv designs: the generated shim and the templates have no gated layer; run "
+                "the model through runtime.CompiledModel.from_model(model, ...).forward / forward_pyg")
         self.model = model
         self.dataset = dataset
         self.name = name

@@ -75,8 +75,9 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     G2Deep g;
     g.nl = 0;
     const int L = d.num_layers;
-    // a GINE model: no stack kernel forms the edge term; a GATv2 model, a TransformerConv model: none forms attention
-    if (model->edge_dim || model->gat_heads || model->tf_heads)
+    // a GINE model: no stack kernel forms the edge term; a GATv2 model, a TransformerConv model: none forms attention; a
+    // ResGatedGraphConv model: none forms the gate
+    if (model->edge_dim || model->gat_heads || model->tf_heads || model->gated)
         return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
@@ -267,6 +268,26 @@ static int transformer_layer(const LayerCtx &c)
     return GNNB_OK;
 }
 
+// ResGatedGraphConv (gnnb_resgated.h; a GIN description with the "gated" mark beside it, so the tables keep explicit (v, v) edges):
+// ONE GEMM x -> [k | q | v | r] [N, 4 fo] on the stacked weight [W_k ; W_q ; W_v ; W_skip] in the model's math mode (conv.bias
+// rides as the skip block's GEMM bias), then ONE k_resgated_aggregate launch -- the per-column sigmoid gate and the gated sum of
+// the value rows in one pass over the edges, with the root term, the skip term and the activation in its epilogue.  None of the
+// fused rungs
+static int resgated_layer(const LayerCtx &c)
+{
+    const gnnb_model_desc &d = c.model->desc;
+    const LayerWeights &p = c.model->conv[c.l];
+    const int fi = c.fi, fo = c.fo;
+    float *kqvr = c.ws->tmp0;
+    int rc;
+    if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_kqvr, fi, p.b_kqvr, nullptr, c.rows(kqvr, 4 * fo), 4 * fo, GNNB_ACT_NONE)))
+        return rc;
+    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+        GNNB_HIP_TRY(launch_resgated_aggregate(c.tv, kqvr, 4 * fo, kqvr + fo, 4 * fo, kqvr + 2 * fo, 4 * fo, kqvr + 3 * fo, 4 * fo, c.skip,
+                                               d.activation, c.nxt, fo, c.hs()));
+    return GNNB_OK;
+}
+
 // GIN's first linear + ReLU on the eps-weighted sum -> ws->tmp0
 static int gin_hidden(const LayerCtx &c)
 {
@@ -444,7 +465,7 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
         int rc = GNNB_OK;
         switch (d.conv_type) {
         case GNNB_CONV_GCN: rc = model->gat_heads ? gat_layer(c) : gcn_layer(c); break;
-        case GNNB_CONV_GIN: rc = model->tf_heads ? transformer_layer(c) : gin_layer(c); break;
+        case GNNB_CONV_GIN: rc = model->tf_heads ? transformer_layer(c) : model->gated ? resgated_layer(c) : gin_layer(c); break;
         case GNNB_CONV_SAGE: rc = sage_layer(c); break;
         case GNNB_CONV_PNA: rc = pna_layer(c); break;
         }
@@ -712,7 +733,7 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
     if (!ws->prepared)
         return fail(GNNB_ERR_INVALID, "workspace has no prepared batch");
     if (memcmp(&model->desc, &ws->desc, sizeof(gnnb_model_desc)) != 0 || model->edge_dim != ws->edge_dim ||
-        model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope || model->tf_heads != ws->tf_heads)
+        model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope || model->tf_heads != ws->tf_heads || model->gated != ws->gated)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;

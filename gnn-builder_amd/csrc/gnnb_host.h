@@ -16,6 +16,7 @@
 #include "gnnb_gat_edge.h"
 #include "gnnb_transformer.h"
 #include "gnnb_transformer_edge.h"
+#include "gnnb_resgated.h"
 
 namespace gnnb {
 
@@ -54,6 +55,8 @@ struct gnnb_model {
                             // w_qkvr, b_qkvr and none of GIN's slots.  Its own field: gnnb_model_gat_heads stays 0 for such a model;
                             // with edge_dim > 0 besides: TransformerConv with edge features (gnnb_transformer_edge_model_create) --
                             // w_qkvre, b_qkvre and w_edge [out, edge_dim] instead
+    int gated = 0;          // 1: a ResGatedGraphConv model (gnnb_resgated_model_create; desc is a GIN description) -- every layer has
+                            // w_kqvr, b_kqvr and none of GIN's slots
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };
@@ -76,6 +79,7 @@ struct gnnb_workspace {
     int gat_heads = 0;           // ... and its heads and slope when it is a GATv2 model (0: it is not)
     float gat_slope = 0.0f;
     int tf_heads = 0;            // ... and its heads when it is a TransformerConv model (0: it is not)
+    int gated = 0;               // ... and 1 when it is a ResGatedGraphConv model
     char *edge_blob = nullptr;   // gnnb_workspace_enable_edge_ingest: edge_attr in COO row order, [max_edges, edge_dim], one allocation
     char *order_blob = nullptr;  // gnnb_workspace_enable_ordered_ingest: the ordered batch and the staged outputs (order_place), one allocation
     int32_t *order_triple = nullptr, *order_triple_dev = nullptr; // host-mapped (first large graph, node row, edge row) of k_order_graphs, and
@@ -117,6 +121,9 @@ int refuse_gat_model(const gnnb_model *model, const gnnb_workspace *ws, const ch
 
 // ... and for a TransformerConv model / its workspace (gnnb_transformer.h)
 int refuse_transformer_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
+
+// ... and for a ResGatedGraphConv model / its workspace (gnnb_resgated.h)
+int refuse_resgated_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
 
 // gnnb_runtime.hip, for the forward (gnnb_forward.hip) -- each is described where it is defined
 int ensure_gcoef(gnnb_workspace *ws, void *stream);

@@ -340,6 +340,13 @@ hipError_t launch_transformer_edge_aggregate(const BatchTables &t, const float *
                                              const float *qe, int ldqe, const float *root, int ldr, const float *skip, int act, int heads,
                                              float scale, const float *edge_attr, int edge_dim, const float *we, int ldwe, float *out, int width,
                                              hipStream_t s);
+// ResGatedGraphConv (k_resgated.hip): out [N, width] = act((sum_j sigmoid(k_i + q_j) * v_j + root_i) + skip_i) over j in N(i) as the
+// tables hold it, the gate per column; k / q / v / root: rows of stride ldk / ldq / ldv / ldr >= width (the column blocks of one GEMM
+// output), root [N, width] or nullptr (ldr ignored), skip [N, width] or nullptr; tables that keep explicit (v, v) edges (any but a
+// GCN description's): no self term is added.  hipErrorInvalidValue: nothing launched
+constexpr int RG_MAX_WIDTH = 256;
+hipError_t launch_resgated_aggregate(const BatchTables &t, const float *k, int ldk, const float *q, int ldq, const float *v, int ldv,
+                                     const float *root, int ldr, const float *skip, int act, float *out, int width, hipStream_t s);
 // the ingest's edge attributes in COO row order (k_ingest.hip): out[i] = edge_attr[state[INGEST_STATE_UNSORTED] ? idx[i] : i]; idx:
 // the general path's sorted-position -> input-edge array (nullptr: that path was not launched), state: IngestParams::state
 hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,

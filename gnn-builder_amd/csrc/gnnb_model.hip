@@ -146,16 +146,37 @@ int count_transformer_params(const gnnb_model_desc *desc, int heads, int edge_di
     return (TF_PARAM_SLOTS + (edge_dim ? 1 : 0)) * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
+// parameter tensors of a ResGatedGraphConv model (gnnb_resgated.h): a GIN description (its tables keep explicit (v, v) edges) without
+// the fixed-point emulation, every layer's output width at most 256
+int count_resgated_params(const gnnb_model_desc *desc)
+{
+    int rc = validate_desc(desc);
+    if (rc != GNNB_OK)
+        return rc;
+    if (desc->conv_type != GNNB_CONV_GIN)
+        return fail(GNNB_ERR_INVALID, "a ResGatedGraphConv model's description is a GIN description (conv_type %d given)", desc->conv_type);
+    if (desc->fpx_w != 0)
+        return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover ResGatedGraphConv models (fpx_w must be 0)");
+    for (int l = 0; l < desc->num_layers; l++) {
+        const int fo = layer_dims(*desc, l).fout;
+        if (fo > RG_MAX_WIDTH)
+            return fail(GNNB_ERR_INVALID, "layer %d's output width %d: a ResGatedGraphConv layer is at most %d wide", l, fo, RG_MAX_WIDTH);
+    }
+    return RG_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+}
+
 // What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
 // type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
 // (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features), or heads of a
 // TransformerConv model (gnnb_transformer_model_create: a GIN description), or heads and edge_dim
-// (gnnb_transformer_edge_model_create: TransformerConv with edge features)
+// (gnnb_transformer_edge_model_create: TransformerConv with edge features), or the "gated" mark of a ResGatedGraphConv model
+// (gnnb_resgated_model_create: a GIN description)
 struct ModelKind {
     int edge_dim = 0, base = GNNB_CONV_GIN;
     int gat_heads = 0;
     float gat_slope = 0.0f;
     int tf_heads = 0;
+    bool gated = false;
     static ModelKind plain() { return {}; }
     static ModelKind edges(int edge_dim, int base)
     {
@@ -187,16 +208,23 @@ struct ModelKind {
         k.edge_dim = edge_dim;
         return k;
     }
+    static ModelKind resgated()
+    {
+        ModelKind k;
+        k.gated = true;
+        return k;
+    }
 };
 
-// the body of the seven *_model_create entries
+// the body of the eight *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
         return fail(GNNB_ERR_INVALID, "null out_model");
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
-    int expect = tf_heads != 0    ? count_transformer_params(desc, tf_heads, edge_dim)
+    int expect = kind.gated       ? count_resgated_params(desc)
+                 : tf_heads != 0  ? count_transformer_params(desc, tf_heads, edge_dim)
                  : gat_heads != 0 ? count_gat_params(desc, gat_heads, edge_dim)
                                   : count_params(desc, edge_dim, kind.base);
     if (expect < 0)
@@ -212,7 +240,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
         return fail(GNNB_ERR_NO_DEVICE, "no HIP device visible: the MI355X path cannot run");
 
     const gnnb_model_desc &d = *desc;
-    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads);
+    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated);
     const std::vector<float> &img = built.img;
     const WeightLayout &lo = built.layout;
 
@@ -222,6 +250,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     m->gat_heads = gat_heads;
     m->gat_slope = gat_heads ? kind.gat_slope : 0.0f;
     m->tf_heads = tf_heads;
+    m->gated = kind.gated ? 1 : 0;
     (void)hipGetDevice(&m->device);
     m->blob_floats = img.size();
     hipError_t e = hipMalloc((void **)&m->blob, std::max<size_t>(img.size(), 4) * sizeof(float));
@@ -370,6 +399,17 @@ int gnnb_transformer_edge_model_create(const gnnb_model_desc *desc, int heads, i
         return fail(GNNB_ERR_INVALID, "edge_dim 0: a TransformerConv model with edge features takes edge_dim 1 .. %d", TFE_MAX_EDGE_DIM);
     return model_create(desc, ModelKind::transformer_edges(heads, edge_dim), host_params, num_params, out_model);
 }
+
+int gnnb_resgated_model_num_params(const gnnb_model_desc *desc) { return count_resgated_params(desc); }
+
+int gnnb_resgated_model_create(const gnnb_model_desc *desc, const float *const *host_params, int num_params, gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    return model_create(desc, ModelKind::resgated(), host_params, num_params, out_model);
+}
+
+int gnnb_model_is_resgated(const gnnb_model *model) { return model ? model->gated : 0; }
 
 void gnnb_model_destroy(gnnb_model *model)
 {

@@ -76,6 +76,14 @@ int refuse_transformer_model(const gnnb_model *model, const gnnb_workspace *ws, 
     return GNNB_OK;
 }
 
+int refuse_resgated_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use)
+{
+    if ((model && model->gated) || (ws && ws->gated))
+        return fail(GNNB_ERR_INVALID, "%s: a ResGatedGraphConv model (gnnb_resgated_model_create) runs layer by layer and is not served here: "
+                                      "call %s (gnnb_resgated.h)", entry, use);
+    return GNNB_OK;
+}
+
 static thread_local int tl_math = -1; // >= 0: the calling thread is inside an entry point of a model with its own math mode
 static thread_local FlagWord tl_flag = {nullptr, nullptr};
 int launch_math() { return tl_math >= 0 ? tl_math : (int)options().math; }
@@ -163,6 +171,9 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
         for (int l = 0; l < d.num_layers; l++)
             tmpw = std::max(tmpw, 4 * layer_dims(d, l).fout + // (with edge features: [.. | qe], padded to whole 16-byte pieces)
                                       (model->edge_dim ? (int)transformer_edge_qe_rows(model->tf_heads, model->edge_dim) : 0));
+    if (model->gated) // a ResGatedGraphConv layer's GEMM writes [k | q | v | r] [N, 4 out] into tmp0
+        for (int l = 0; l < d.num_layers; l++)
+            tmpw = std::max(tmpw, 4 * layer_dims(d, l).fout);
     // the widest GEMM K of the conv layers: from 1024 on k_linear_dma may cut its tiles along K (stream-K) and needs a scratch,
     // which belongs to the workspace -- forwards of different workspaces never share one, whatever streams or graphs run them
     int max_k = 0;
@@ -174,8 +185,8 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     // (the stage-cut planner's tables: opt-in -- carved only for workspaces created while the option is on; a workspace created
     // without them keeps equal tile counts whatever the option says later: round-5 advisor finding)
     const bool want_plan = options().stage_cut && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 &&
-                           model->gat_heads == 0 && model->tf_heads == 0; // (a GATv2 model, a TransformerConv model take no stack
-                                                                          // kernel: no stage plan)
+                           model->gat_heads == 0 && model->tf_heads == 0 && model->gated == 0; // (a GATv2 model, a TransformerConv model,
+                                                                          // a ResGatedGraphConv model take no stack kernel: no stage plan)
     const int pooledw = d.num_pools * gnn_out_width(d);
     const int mlpw = std::max(d.mlp_hidden, d.mlp_out);
     const int min_tile_rows = 4;
@@ -187,6 +198,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     ws->gat_heads = model->gat_heads;
     ws->gat_slope = model->gat_slope;
     ws->tf_heads = model->tf_heads;
+    ws->gated = model->gated;
     ws->max_graphs = max_graphs;
     ws->max_nodes = max_nodes;
     ws->max_edges = max_edges;
@@ -346,10 +358,10 @@ int gnnb_workspace_set_max_degree(gnnb_workspace *ws, int d)
 static bool stack_promised(const gnnb_workspace *ws)
 {
     const gnnb_model_desc &d = ws->desc;
-    // (a GINE model's workspace, a GATv2 model's, a TransformerConv model's: never -- their layers take no stack kernel, whatever
-    // the promise)
+    // (a GINE model's workspace, a GATv2 model's, a TransformerConv model's, a ResGatedGraphConv model's: never -- their layers take
+    // no stack kernel, whatever the promise)
     return options().fuse_gcn2 && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 && ws->max_graph_nodes > 0 &&
-           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->tf_heads == 0;
+           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->tf_heads == 0 && ws->gated == 0;
 }
 
 // ... and the WHOLE batch is expected there: no large segment, no fixed-point emulation.  Such a batch needs neither the
@@ -783,6 +795,24 @@ int gnnb_aggregate_transformer(gnnb_workspace *ws, const float *q_dev, int ldq, 
                                       "root's ldr >= width, a gnnb_act, a finite scale)", TF_MAX_HEADS, TF_MAX_WIDTH);
     GNNB_HIP_TRY(launch_transformer_aggregate(ws->t, q_dev, ldq, k_dev, ldk, v_dev, ldv, root_dev, ldr, skip_dev, act, heads, scale, out_dev,
                                               width, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_resgated(gnnb_workspace *ws, const float *k_dev, int ldk, const float *q_dev, int ldq, const float *v_dev, int ldv,
+                            const float *root_dev, int ldr, const float *skip_dev, int act, float *out_dev, int width, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_resgated needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's with or without edge features)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_resgated takes a prepared batch whose tables keep explicit self loops: graph prep "
+                                      "drops the (v, v) edges on a workspace of a GCN description (a GCN or GATv2 model's), and this layer "
+                                      "counts them as ordinary edges");
+    if (!k_dev || !q_dev || !v_dev || !out_dev || width < 1 || width > RG_MAX_WIDTH || ldk < width || ldq < width || ldv < width ||
+        (root_dev && ldr < width) || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE)
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_resgated (k, q, v and out not NULL, width 1 .. %d, ldk, ldq, ldv and "
+                                      "root's ldr >= width, a gnnb_act)", RG_MAX_WIDTH);
+    GNNB_HIP_TRY(launch_resgated_aggregate(ws->t, k_dev, ldk, q_dev, ldq, v_dev, ldv, root_dev, ldr, skip_dev, act, out_dev, width,
+                                           (hipStream_t)stream));
     return GNNB_OK;
 }
 

@@ -105,6 +105,14 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //              b_qkvre [4 out + roundup4(heads edge_dim)]       derived: [b_q ; b_k ; b_v ; b_skip ; W_e[h]^T b_q[h] ; 0]
 //              w_edge [out, edge_dim]               canonical 8: conv.lin_edge.weight (no bias), raw -- what
 //                                                   k_transformer_edge_aggregate applies to the weighted attribute sum in its epilogue
+//   ResGatedGraphConv  (gnnb_model::gated, gnnb_resgated_model_create: a GIN description) none of GIN's slots, but
+//              w_kqvr [4 out, in]                   derived: [W_k ; W_q ; W_v ; W_skip], canonical 0 (conv.lin_key.weight), 2
+//                                                   (conv.lin_query.weight), 4 (conv.lin_value.weight), 6 (conv.lin_skip.weight) on top
+//                                                   of each other -- ONE GEMM gives [k | q | v | r] [N, 4 out]; q and v are adjacent
+//                                                   blocks, so a neighbour's q_j | v_j is ONE span of 2 out floats of its row
+//              b_kqvr [4 out]                       derived: [b_k ; b_q ; b_v ; bias], canonical 1, 3, 5 and 7 (conv.bias): lin_skip has
+//                                                   no bias, so the conv's own rides as the skip block's GEMM bias.  b_q is NOT
+//                                                   folded into b_k: every block keeps the rounding of its own linear
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
@@ -112,6 +120,7 @@ template <typename T> struct LayerSlots {
     T w_lr = absent_slot<T>(), b_lr = absent_slot<T>(), att = absent_slot<T>(), gat_bias = absent_slot<T>(), w_edge = absent_slot<T>();
     T w_qkvr = absent_slot<T>(), b_qkvr = absent_slot<T>();
     T w_qkvre = absent_slot<T>(), b_qkvre = absent_slot<T>();
+    T w_kqvr = absent_slot<T>(), b_kqvr = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -120,7 +129,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -385,15 +394,22 @@ inline WeightBias transformer_edge_fold(const float *w_q, const float *b_q, cons
 constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_gat.h); one more with edge features (gnnb_gat_edge.h)
 constexpr int TF_PARAM_SLOTS = 8;  // a TransformerConv layer's canonical tensors (gnnb_transformer.h); one more with edge features
                                    // (gnnb_transformer_edge.h)
+constexpr int RG_PARAM_SLOTS = 8;  // a ResGatedGraphConv layer's canonical tensors (gnnb_resgated.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
 // their offsets in the image
 inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0,
-                                    int tf_heads = 0)
+                                    int tf_heads = 0, bool gated = false)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (gated) { // (a GIN description whose layers are ResGatedGraphConv's; canonical order: key, query, value, skip weight, conv.bias)
+        LayerOffsets g;
+        g.w_kqvr = im.push(stack_rows({p[0], p[2], p[4], p[6]}, fo, fi));
+        g.b_kqvr = im.push(stack_rows({p[1], p[3], p[5], p[7]}, fo, 1));
+        return g;
+    }
     if (tf_heads > 0 && edge_dim > 0) { // (... with edge features: lin_edge's weight behind the eight; the folded query block)
         LayerOffsets g;
         const WeightBias qe = transformer_edge_fold(p[2], p[3], p[8], fi, fo, (size_t)tf_heads, (size_t)edge_dim);
@@ -484,24 +500,26 @@ struct BuiltWeights {
 // fragment copy, the GIN stack's copies, the head.  gat_heads > 0: a GATv2 model (a GCN description, six tensors per layer; no
 // fragment copy -- it takes no stack kernel); with edge_dim > 0 besides, GATv2 with edge features (seven tensors per layer).
 // tf_heads > 0: a TransformerConv model (a GIN description, eight tensors per layer; no execution-order copy -- no stack kernel);
-// with edge_dim > 0 besides, TransformerConv with edge features (nine tensors per layer).
+// with edge_dim > 0 besides, TransformerConv with edge features (nine tensors per layer).  gated: a ResGatedGraphConv model (a GIN
+// description, eight tensors per layer; no execution-order copy either).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
-                                       int tf_heads = 0)
+                                       int tf_heads = 0, bool gated = false)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = tf_heads > 0    ? TF_PARAM_SLOTS + (edge_dim ? 1 : 0)
+    const int slots = gated           ? RG_PARAM_SLOTS
+                      : tf_heads > 0  ? TF_PARAM_SLOTS + (edge_dim ? 1 : 0)
                       : gat_heads > 0 ? GAT_PARAM_SLOTS + (edge_dim ? 1 : 0)
                                       : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;
     for (int l = 0; l < d.num_layers; l++, pi += slots)
-        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads);
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated);
     const bool have_w1f = gat_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));
-    // (a GINE model, a TransformerConv model take no stack kernel: no execution-order copy)
-    const bool have_gin = edge_dim == 0 && tf_heads == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
+    // (a GINE model, a TransformerConv model, a ResGatedGraphConv model take no stack kernel: no execution-order copy)
+    const bool have_gin = edge_dim == 0 && tf_heads == 0 && !gated && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
                           d.out_dim <= d.hidden_dim && d.out_dim % 4 == 0;
     if (have_gin) {
         const WeightBias g = gin_execution_order(d, im.img, lo.conv);

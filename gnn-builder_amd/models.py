@@ -622,6 +622,59 @@ class TransformerEConv_GNNB(nn.Module):
         return self.conv(x, edge_index, edge_attr)
 
 
+# --------------------------------------------------------------------------------------- ResGatedGraphConv
+class _ResGatedGraphConv(nn.Module):
+    """PyG's ``ResGatedGraphConv(in_channels, out_channels, act=Sigmoid(), edge_dim=None, root_weight=True, bias=True)`` -- the
+    Residual Gated Graph ConvNet of Bresson & Laurent, the "GatedGCN" of *Benchmarking GNNs* without its edge stream::
+
+        k = lin_key(x) [N, out]   q = lin_query(x) [N, out]   v = lin_value(x) [N, out]   r = lin_skip(x) [N, out]
+        g_ij  = sigmoid(k_i + q_j)                     [out] -- a gate per column; for j in N(i), the input's edges as they are
+        out_i = sum_j g_ij * v_j + r_i + bias          elementwise
+
+    The DESTINATION's key meets the SOURCE's query (PyG's ``message(k_i, q_j, v_j)``).  No self loop is added and none is
+    removed: an explicit ``(v, v)`` edge is an ordinary edge, duplicate edges count as often as they occur, a node without
+    in-edges gets ``lin_skip(x_i) + bias`` alone.  Modules in PyG's order ``lin_key``, ``lin_query``, ``lin_value`` -- each
+    ``nn.Linear(in, out, bias=True)`` --, ``lin_skip`` -- ``nn.Linear(in, out, bias=False)`` --, all with torch's default
+    initialisation (what PyG's ``Linear`` uses), and the conv's own ``bias`` [out], zero-initialised.  Out of scope:
+    ``edge_dim``, ``root_weight=False``, ``bias=False``, gates other than the sigmoid."""
+
+    def __init__(self, in_channels: int, out_channels: int):
+        super().__init__()
+        self.out_channels = out_channels
+        self.lin_key = nn.Linear(in_channels, out_channels)
+        self.lin_query = nn.Linear(in_channels, out_channels)
+        self.lin_value = nn.Linear(in_channels, out_channels)
+        self.lin_skip = nn.Linear(in_channels, out_channels, bias=False)
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        src, dst = edge_index[0].long(), edge_index[1].long()
+        k, q, v = self.lin_key(x), self.lin_query(x), self.lin_value(x)
+        out = torch.zeros_like(v).index_add(0, dst, torch.sigmoid(k[dst] + q[src]) * v[src])
+        return out + self.lin_skip(x) + self.bias
+
+
+class ResGatedGraphConv_GNNB(nn.Module):
+    """The residual gated graph conv (no class of the reference): PyG's ``ResGatedGraphConv(in_channels, out_channels)``.
+    ``GNNModel(..., gnn_conv=ResGatedGraphConv_GNNB)`` stacks it (``gnn_heads`` stays 1); ``forward(x, edge_index)``.  The
+    accelerated path is ``runtime.CompiledModel.from_model`` with the ordinary ``forward`` / ``forward_pyg`` (C ABI
+    ``include/gnnb_resgated.h``: one GEMM ``x -> [k | q | v | r]`` and one launch of csrc/k_resgated.hip per layer, the gate formed
+    inside the aggregate).  This class ignores ``graph_input_edge_dim`` and ``edge_attr``: PyG's ``edge_dim`` form, which
+    concatenates ``e_ij`` to the inputs of key, query and value, is a model kind of its own and out of scope, as are
+    ``root_weight=False``, ``bias=False`` and other gates.  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _ResGatedGraphConv(in_channels, out_channels)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        return self.conv(x, edge_index)
+
+
 # --------------------------------------------------------------------------------------- pooling / MLP
 SUPPORTED_GLOBAL_POOLING_AGGRS = {"add": "SumAggregation", "max": "MaxAggregation", "mean": "MeanAggregation"}
 SUPPORTED_GLOBAL_POOLING_MODE = ["cat"]
@@ -733,10 +786,10 @@ class MLP(nn.Module):
 
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
-                       GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB]
+                       GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
               PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
-              TransformerEConv_GNNB: "transformere"}
+              TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated"}
 # convs that take edge_attr, and what the messages call them
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE"}
 MAX_EDGE_DIM = 16  # of a GINE, PNAE, GATv2E or TransformerE model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h, gnnb_transformer_edge.h)
@@ -952,6 +1005,9 @@ class GNNModel(nn.Module):
         # (PyG's registration order: key, query, value, skip -- the C side stacks them as [W_q ; W_k ; W_v ; W_skip])
         per_conv["transformer"] = [f"conv_lin_{n}_{t}" for n in ("key", "query", "value", "skip") for t in ("weight", "bias")]
         per_conv["transformere"] = per_conv["transformer"] + ["conv_lin_edge_weight"]  # (the eight, then lin_edge [out, edge_dim])
+        # (key, query, value with their biases, lin_skip's weight -- it has no bias --, then the conv's own bias: include/gnnb_resgated.h)
+        per_conv["resgated"] = [f"conv_lin_{n}_{t}" for n in ("key", "query", "value") for t in ("weight", "bias")] + [
+            "conv_lin_skip_weight", "conv_bias"]
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

@@ -30,7 +30,7 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
 # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h)
 _EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere")
 _GAT_CONVS = ("gatv2", "gatv2e")       # ... and of those with heads and negative_slope beside it
@@ -38,6 +38,8 @@ _GAT_CONVS = ("gatv2", "gatv2e")       # ... and of those with heads and negativ
 # explicit (v, v) edges --, heads travels beside it; with edge features ("transformere", include/gnnb_transformer_edge.h) edge_dim too
 _TRANSFORMER_CONVS = ("transformer", "transformere")
 MAX_TRANSFORMER_HEADS, MAX_TRANSFORMER_WIDTH = 8, 256
+# a ResGatedGraphConv model (include/gnnb_resgated.h, spec["conv"] == "resgated"): its description is GIN's too, a "gated" mark beside it
+MAX_RESGATED_WIDTH = 256
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -211,6 +213,15 @@ ABI_TRANSFORMER_EDGE = {
 }
 
 
+# ... and of include/gnnb_resgated.h (ResGatedGraphConv models), in its order (tests/test_abi_resgated.py)
+ABI_RESGATED = {
+    "gnnb_resgated_model_num_params": (_I, [_DESC]),
+    "gnnb_resgated_model_create": (_I, [_DESC, _PP, _I, _PP]),
+    "gnnb_model_is_resgated": (_I, [_P]),
+    "gnnb_aggregate_resgated": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -255,7 +266,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
         for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER,
-                                           **ABI_TRANSFORMER_EDGE}.items():
+                                           **ABI_TRANSFORMER_EDGE, **ABI_RESGATED}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -419,6 +430,7 @@ class CompiledModel:
                     num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
                     self.lib.gnnb_gat_model_num_params(C.byref(self.desc), self.gat_heads) if spec.get("conv") == "gatv2" else
                     self.lib.gnnb_transformer_model_num_params(C.byref(self.desc), self.transformer_heads) if spec.get("conv") == "transformer" else
+                    self.lib.gnnb_resgated_model_num_params(C.byref(self.desc)) if spec.get("conv") == "resgated" else
                     self.lib.gnnb_model_num_params(C.byref(self.desc)))
         if n_expect < 0:
             _check(n_expect)
@@ -438,6 +450,8 @@ class CompiledModel:
                                                   C.byref(self._model)))
         elif spec.get("conv") == "transformer":  # (gnnb_transformer.h: a GIN description, heads beside it)
             _check(self.lib.gnnb_transformer_model_create(C.byref(self.desc), self.transformer_heads, arr, len(host), C.byref(self._model)))
+        elif spec.get("conv") == "resgated":  # (gnnb_resgated.h: a GIN description, the "gated" mark beside it)
+            _check(self.lib.gnnb_resgated_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
         else:
             _check(self.lib.gnnb_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
         rc = self.lib.gnnb_workspace_create(self._model, self.max_graphs, self.max_nodes, self.max_edges, C.byref(self._ws))
@@ -966,6 +980,34 @@ class CompiledModel:
         _check(self.lib.gnnb_aggregate_transformer(self._ws, _dptr(q), ld(q), _dptr(k), ld(k), _dptr(v), ld(v), _optr(root),
                                                    ld(root) if root is not None else w, _optr(skip), ACT[act], heads, float(scale),
                                                    _dptr(out), w, _stream_ptr(stream)))
+        return out
+
+    def aggregate_resgated(self, k, q, v, root=None, skip=None, act: str = "none", out=None, stream=None):
+        """One ResGatedGraphConv layer behind its GEMM (``gnnb_aggregate_resgated``, csrc/k_resgated.hip) on the prepared batch of a
+        workspace whose tables keep explicit self loops (any but a GCN or GATv2 model's, which is refused):
+        ``act((sum_j sigmoid(k_i + q_j) * v_j + root_i) + skip_i)`` over ``j`` in ``N(i)`` as the batch holds it, the gate per
+        column -> [N, width].  ``k``, ``q``, ``v`` [N, width] and ``root`` [N, width] or None (column slices of a wider matrix are
+        fine -- the four blocks of one [N, 4 width] GEMM output: their row strides are passed on), ``skip`` [N, width] contiguous
+        or None; ``width`` <= 256."""
+        _require_strided(k, "k", self._N, 1)
+        w = int(k.shape[1])
+        for name, t in (("q", q), ("v", v), ("root", root)):
+            if t is None and name == "root":
+                continue
+            _require_strided(t, name, self._N, w)
+            if int(t.shape[1]) != w or t.device != k.device:
+                raise GnnbError(f"{name} must be [{self._N}, {w}] on {k.device}, got {tuple(t.shape)} on {t.device}")
+        if w > MAX_RESGATED_WIDTH:
+            raise GnnbError(f"width {w}: a ResGatedGraphConv layer is at most {MAX_RESGATED_WIDTH} wide")
+        if act not in ACT:
+            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, k)
+        out = _out(out, self._N, w, k)
+        ld = lambda t: int(t.stride(0)) if self._N > 1 else w  # noqa: E731  (one row: any stride describes it)
+        _check(self.lib.gnnb_aggregate_resgated(self._ws, _dptr(k), ld(k), _dptr(q), ld(q), _dptr(v), ld(v), _optr(root),
+                                                ld(root) if root is not None else w, _optr(skip), ACT[act], _dptr(out), w,
+                                                _stream_ptr(stream)))
         return out
 
     def aggregate_transformer_edges(self, q, k, v, qe, edge_attr, w_edge, root=None, skip=None, act: str = "none", heads: int = 1,

@@ -1,0 +1,86 @@
+/*
+ * gnnb_resgated.h -- extension of the C ABI in gnnb_hip.h (same library, libgnnb_hip.so): ResGatedGraphConv models (the Residual
+ * Gated Graph ConvNet of Bresson & Laurent, the "GatedGCN" of Benchmarking GNNs), end to end.  gnnb_hip.h, gnnb_order.h,
+ * gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat.h, gnnb_gat_edge.h, gnnb_transformer.h and gnnb_transformer_edge.h are unchanged by these
+ * entries (no new version: the library stays at 104).
+ *
+ * Reference: none in gnnbuilder.  The model is ResGatedGraphConv_GNNB (gnn-builder_amd/models.py, class _ResGatedGraphConv): PyG's
+ * ResGatedGraphConv(in, out, act = Sigmoid(), edge_dim = None, root_weight = True, bias = True),
+ *   k = lin_key(x) [N, out],  q = lin_query(x) [N, out],  v = lin_value(x) [N, out],  r = lin_skip(x) [N, out] (no bias of its own)
+ *   out_i = r_i + bias + sum_{j in N(i)} sigmoid(k_i + q_j) * v_j          elementwise; j in N(i) -- the input's edges as they are
+ * Self loops: none is added and none is removed.  An explicit (v, v) edge of the input is an ordinary edge; a node without
+ * in-edges gets r_i + bias alone.
+ *
+ * Such a model is an ordinary gnnb_model: its description is a GIN description (conv_type = GNNB_CONV_GIN, gin_eps ignored, every
+ * other field as for GIN) with a "gated" mark BESIDE it.  The reason is gnnb_transformer.h's: the tables of a GCN workspace drop
+ * explicit (v, v) edges in graph prep (gnnb_hip.h, "Explicit self loops"), the tables of a GIN workspace keep them -- which is what
+ * this layer needs.  gnnb_model_is_resgated reports the mark; gnnb_model_gat_heads, gnnb_model_transformer_heads and
+ * gnnb_model_edge_dim are 0 for such a model.
+ *
+ * What such a model runs: layer by layer (gnnb_workspace_last_path: GNNB_PATH_LAYERWISE, whatever the max_graph_nodes and
+ * max_degree promises, which change no bit).  A layer is ONE GEMM, x -> [k | q | v | r] [N, 4 out] on the stacked weight
+ * [W_k ; W_q ; W_v ; W_skip] with the bias vector [b_k | b_q | b_v | bias] in the model's math mode -- conv.bias rides as the skip
+ * block's GEMM bias, because lin_skip has none; b_q is NOT folded into b_k, every block keeps its own linear's rounding --, and ONE
+ * launch of k_resgated_aggregate (csrc/k_resgated.hip: the gate and the gated sum in one pass over the edges, nothing per edge in
+ * HBM; the root term, the middle layers' skip term and the activation in its epilogue; plain fp32 in every math mode).  Then the
+ * readout and the output activation as for every model.  No stack kernel, no stage plan, no fixed-point emulation (fpx_w must be
+ * 0), no capture restrictions: nothing in the forward allocates, waits or reads back.
+ *
+ * It has no edge attributes, so the ordinary entries run it: gnnb_forward_batched, gnnb_forward_prepared, gnnb_forward_pyg,
+ * gnnb_forward_batched_host and gnnb_forward_prepared_prep_next.  The _edges entries of gnnb_edge.h refuse it as a model without
+ * edge weights; gnnb_forward_pyg_ordered refuses it and names gnnb_forward_pyg.  A model matches a workspace only if both are
+ * gated.
+ *
+ * Out of scope: edge_dim (PyG concatenates e_ij to the inputs of key, query and value: a model kind of its own), root_weight =
+ * False and bias = False at model level (the stage entry's root = NULL covers the kernel side), gates other than sigmoid, widths
+ * above 256.
+ */
+#ifndef GNNB_RESGATED_H
+#define GNNB_RESGATED_H
+
+#include "gnnb_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Parameter tensors of a ResGatedGraphConv model, in gnnb_resgated_model_create's order: per conv layer conv.lin_key.weight
+ * [out, in], conv.lin_key.bias [out], conv.lin_query.weight, .bias, conv.lin_value.weight, .bias, conv.lin_skip.weight [out, in],
+ * conv.bias [out] (models.py _ResGatedGraphConv; GNNModel.canonical_param_names), then the head's as in gnnb_model_create: 8 per
+ * layer + 2 per head linear.  Negative: a gnnb_status (GNNB_ERR_INVALID: a layer output width above 256, conv_type !=
+ * GNNB_CONV_GIN, fpx_w != 0, or a description gnnb_model_num_params refuses). */
+int gnnb_resgated_model_num_params(const gnnb_model_desc *desc);
+/* gnnb_model_create (load_parameters, model.cpp.jinja:724-730) for such a model (models.py GNNModel with gnn_conv =
+ * ResGatedGraphConv_GNNB).  Destroy with gnnb_model_destroy, make its workspace with gnnb_workspace_create. */
+int gnnb_resgated_model_create(const gnnb_model_desc *desc, const float *const *host_params, int num_params, gnnb_model **out_model);
+/* 1 for a model of gnnb_resgated_model_create; 0 for every other model (and for NULL) */
+int gnnb_model_is_resgated(const gnnb_model *model);
+
+/* Stage entry: one ResGatedGraphConv layer behind its GEMM,
+ *   out_i = act( (sum_{j in N(i)} sigmoid(k_i + q_j) * v_j + root_i) + skip_i )                  the gate per column
+ * on the prepared batch of any workspace whose tables keep explicit self loops (a GIN, GINE, GraphSAGE, PNA, TransformerConv or
+ * ResGatedGraphConv model's); a GCN, GATv2 or GATv2-with-edges workspace is refused (GNNB_ERR_INVALID: its tables have dropped the
+ * (v, v) edges).  k_dev / q_dev / v_dev: rows of `width` floats at row strides ldk / ldq / ldv >= width; root_dev rows at stride
+ * ldr >= width, or NULL (ldr ignored) -- the four column blocks of one [N, 4 width] GEMM output are fine; skip_dev [N, width] or
+ * NULL, act a gnnb_act, width 1 .. 256, out_dev [N, width].  16-byte accesses when width % 4 == 0 and k / q / v / root / skip /
+ * out and the strides are 16-byte aligned, scalar accesses otherwise.  fp32 in every math mode.  A row without in-edges gives
+ * act(root_i + skip_i) with root's own bits; with root NULL as well act(skip_i), or act(0).  An absent term adds nothing: it does
+ * not add 0.  GNNB_ERR_INVALID (nothing launched): an unprepared workspace, a GCN description's workspace, a NULL operand, width
+ * out of range, a stride below width.
+ * The gate: s = k_ic + q_jc forms first, in fp32; g = 1 / (1 + exp(-s)) with the hardware's exp2 of the argument scaled by
+ * -log2(e) and the hardware's reciprocal (1 ulp each).  It saturates cleanly: s = -200 gives a gate of exactly 0, s = +200 exactly
+ * 1, and no finite input gives a NaN.
+ * Summation order -- fixed by the batch and by the form (16-byte or scalar), never by the grid or by which workgroup took a row;
+ * a repeat launch gives the same bits.  Per (row, column): the in-edges in CSR slot order in batches of 4,
+ * acc = fma(g_3, v_3, fma(g_2, v_2, fma(g_1, v_1, fma(g_0, v_0, acc)))), slots past the row's end taking no part; a row of more than
+ * 64 in-edges in pieces of 64 slots, each summed from 0, the pieces added in piece order onto 0 -- a plain sum;
+ * out = act((acc + root) + skip). */
+int gnnb_aggregate_resgated(gnnb_workspace *ws, const float *k_dev, int ldk, const float *q_dev, int ldq, const float *v_dev,
+                            int ldv, const float *root_dev /*[N, width] rows at ldr, or NULL*/, int ldr,
+                            const float *skip_dev /*[N, width] or NULL*/, int act /*gnnb_act*/, float *out_dev /*[N, width]*/,
+                            int width, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* GNNB_RESGATED_H */
