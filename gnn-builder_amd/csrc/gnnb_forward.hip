@@ -479,13 +479,19 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
     return GNNB_OK;
 }
 
+// The large segment of the PREPARED batch: what graph prep validated against the batch and baked into its tables (t.promise_graphs,
+// t.large_n, t.large_e; the device check behind flag 16), NOT the workspace's current setting -- gnnb_workspace_set_large_segment
+// between a graph prep and its prepared forward names the segment of the NEXT prep, and everything below this line reads the
+// split from here.  -1: the batch was prepared without one.
+static int prepared_large_g(const gnnb_workspace *ws) { return ws->t.large_n >= 0 ? ws->t.promise_graphs : -1; }
+
 // global pooling of the large segment's graphs [large_g, B) from the node matrix `cur` into their rows of ws->pooled
 static hipError_t pool_large_segment(const gnnb_model *model, gnnb_workspace *ws, const float *cur, hipStream_t s)
 {
     const gnnb_model_desc &d = model->desc;
-    const int gw = gnn_out_width(d);
-    return launch_global_pool(cur, ws->t.graph_ptr + ws->large_g, ws->t.num_graphs - ws->large_g, gw, d.pools, d.num_pools,
-                              ws->pooled + (size_t)ws->large_g * d.num_pools * gw, s);
+    const int gw = gnn_out_width(d), large_g = prepared_large_g(ws);
+    return launch_global_pool(cur, ws->t.graph_ptr + large_g, ws->t.num_graphs - large_g, gw, d.pools, d.num_pools,
+                              ws->pooled + (size_t)large_g * d.num_pools * gw, s);
 }
 
 // The large segment through the small-footprint per-layer kernel (k_conv_rows) + pooling, all on stream `s`; fills
@@ -509,7 +515,7 @@ static hipError_t large_segment_small(const gnnb_model *model, gnnb_workspace *w
         const LayerWeights &p = model->conv[l];
         const LayerIO io = layer_io(d, ws, l, cur, which);
         hipError_t he = launch_conv_rows(ws->t, d.conv_type, cur, ld.fin, p.w0, p.b0, p.w1, p.b1, // (GCN: no second linear)
-                                         ld.fout, io.skip, io.nxt, ws->large_n, d.activation, d.gin_eps, s);
+                                         ld.fout, io.skip, io.nxt, ws->t.large_n, d.activation, d.gin_eps, s);
         if (he != hipSuccess)
             return he; // (NotSupported can only come from the first layer's checks above: nothing is half done)
         cur = io.nxt;
@@ -519,14 +525,16 @@ static hipError_t large_segment_small(const gnnb_model *model, gnnb_workspace *w
 
 // The batch tables restricted to the graphs the max_graph_nodes promise covers: everything, or -- with a large segment --
 // graphs [0, large_g) = nodes [0, large_n) = edges [0, large_e).  The stack kernels clamp every table entry to these
-// counts, so a tile that begins in the small segment ends at its last node.
+// counts, so a tile that begins in the small segment ends at its last node.  (The prepared batch's segment: graph prep calls this
+// behind the lines that bake it, where it is the workspace's setting.)
 BatchTables gnnb::small_segment(const gnnb_workspace *ws)
 {
     BatchTables t = ws->t;
-    if (ws->large_g >= 0 && ws->large_g < t.num_graphs) {
-        t.num_graphs = ws->large_g;
-        t.num_nodes = ws->large_n;
-        t.num_edges = ws->large_e;
+    const int large_g = prepared_large_g(ws);
+    if (large_g >= 0 && large_g < t.num_graphs) {
+        t.num_graphs = large_g;
+        t.num_nodes = ws->t.large_n;
+        t.num_edges = ws->t.large_e;
         t.num_tiles = (t.num_nodes + t.tile_rows - 1) / t.tile_rows;
     }
     return t;
@@ -675,8 +683,8 @@ static bool ensure_side_stream(gnnb_workspace *ws)
 // whole batch down the layer-by-layer path.  DECLINED: no stack kernel takes the model / batch.
 static int forward_stack(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, float *out_dev, const G2Deep &deep, void *stream)
 {
-    const int B = ws->t.num_graphs;
-    const bool seg = ws->large_g >= 0 && ws->large_g < B;
+    const int B = ws->t.num_graphs, large_g = prepared_large_g(ws), large_n = ws->t.large_n;
+    const bool seg = large_g >= 0 && large_g < B;
     int rc;
     // The large segment first, FORKED: its kernels are built to run beside the stack kernel (k_conv_rows.hip), so they
     // go on the workspace's side stream behind an event on the caller's stream and are joined in front of the readout.
@@ -712,14 +720,14 @@ static int forward_stack(const gnnb_model *model, gnnb_workspace *ws, const floa
     if (seg && !forked) { // the general layer-by-layer kernels on the large segment's rows
         const float *lcur = nullptr;
         // (no edge attributes: a GINE model never comes here -- gcn_stack_middle_layers)
-        if ((rc = run_conv_layers(model, ws, x_dev, nullptr, ws->large_n, ws->large_n / ws->t.tile_rows, &lcur, stream)))
+        if ((rc = run_conv_layers(model, ws, x_dev, nullptr, large_n, large_n / ws->t.tile_rows, &lcur, stream)))
             return rc;
         GNNB_HIP_TRY(pool_large_segment(model, ws, lcur, (hipStream_t)stream));
     }
     if (seg)
         ws->last_path |= GNNB_PATH_LARGE_LAYERWISE;
     // (the stack kernel ran the head on its own graphs: what is left are the graphs of the large segment, if any)
-    const int hg0 = head_fused ? (seg ? ws->large_g : B) : 0;
+    const int hg0 = head_fused ? (seg ? large_g : B) : 0;
     if (hg0 >= B)
         return GNNB_OK;
     return readout_from_pooled(model, ws, hg0, out_dev, stream);
@@ -746,7 +754,7 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
 
     // (large_g = 0: every graph is large -> layer by layer)
     const G2Deep deep = gcn_stack_middle_layers(model);
-    if (!fpx && deep.nl >= 2 && d.mlp_num_linear <= 8 && !(ws->large_g == 0 && B > 0))
+    if (!fpx && deep.nl >= 2 && d.mlp_num_linear <= 8 && !(prepared_large_g(ws) == 0 && B > 0))
         GNNB_RUNG(forward_stack(model, ws, x_dev, out_dev, deep, stream));
 
     ws->last_path = GNNB_PATH_LAYERWISE;

@@ -86,6 +86,8 @@ struct gnnb_workspace {
                                                                   // its device-visible address
     float2 *pool_part = nullptr; // pieces of graphs that cross the 32-row blocks of the pooling GEMM epilogue (PoolEpilogue::part)
     bool gcoef_ready = false; // t.gcoef holds the prepared batch's GCN coefficients (ensure_gcoef)
+    // (both promises are read by graph prep alone: the prepared forward goes by what the prep left -- t.max_graph_nodes_hint,
+    // t.tile_rows, gcoef_ready, deg_ready -- so a setter between a prep and its forward speaks of the NEXT prep)
     int max_graph_nodes = 0; // caller's promise (0 = none)
     int max_degree = 0;      // caller's promise on the in-degree (0 = none): gnnb_workspace_set_max_degree
     // PNA degree classes of the prepared batch (launch_degree_classes): valid when deg_ready; deg_delta = the delta it was prepared with
@@ -97,7 +99,9 @@ struct gnnb_workspace {
     float prep_delta = 0.0f; // the delta the prepared batch's amp / att tables were computed with (PNA workspaces; 0: none)
     int last_path = GNNB_PATH_NONE; // which kernels the last forward on this workspace ran (gnnb_workspace_last_path)
     // "large segment" of the NEXT batches (gnnb_workspace_set_large_segment): graphs [large_g, B) -- nodes from large_n,
-    // edges from large_e -- are exempt from the max_graph_nodes promise and run layer by layer; -1 = no such segment
+    // edges from large_e -- are exempt from the max_graph_nodes promise and run layer by layer; -1 = no such segment.  Read by
+    // graph prep alone, which checks the triple against the batch and bakes it into t (promise_graphs, large_n, large_e): the
+    // prepared forward takes the PREPARED batch's segment from there (gnnb_forward.hip, prepared_large_g)
     int large_g = -1, large_n = -1, large_e = -1;
     // fork / join for the large segment: its small kernels run on `side` beside the stack kernel on the caller's stream
     hipStream_t side = nullptr;

@@ -479,11 +479,17 @@ class CompiledModel:
         return cls(spec, model.canonical_params(), max_graphs, max_nodes, max_edges, max_graph_nodes)
 
     def set_max_graph_nodes(self, n: int) -> None:
+        """Promise on the largest graph of the following batches (0 = none).  Like ``set_max_degree`` and ``set_large_segment`` it
+        takes effect at the NEXT graph prep (``graph_prep``, or the one inside ``forward`` / ``forward_edges`` / ``forward_pyg*`` /
+        ``forward_prepared_prep_next``'s ``nxt``): a batch that is already prepared runs ``forward_prepared`` /
+        ``forward_prepared_edges`` / ``forward_prepared_prep_next`` by what its own prep validated and baked into the tables,
+        whatever has been set since -- the same route and the same bits as without the call."""
         _check(self.lib.gnnb_workspace_set_max_graph_nodes(self._ws, int(n)))
 
     def set_max_degree(self, d: int) -> None:
         """Promise on the largest in-degree of the following batches (0 = none; a bound, where the reference's ``degree_guess`` is a hint): PNA models
-        then run their post-NN products in the degree-class form (d <= 15).  Validated on the device (``check()``)."""
+        then run their post-NN products in the degree-class form (d <= 15).  Validated on the device (``check()``).  Takes effect at
+        the next graph prep (``set_max_graph_nodes``): the class tables belong to the prepared batch."""
         _check(self.lib.gnnb_workspace_set_max_degree(self._ws, int(d)))
 
     def stream_k_guard(self, stream=None) -> None:
@@ -500,7 +506,9 @@ class CompiledModel:
     def set_large_segment(self, first_graph: int = -1, first_node: int = -1, first_edge: int = -1) -> None:
         """Graphs [first_graph, B) of the following batches are exempt from the max_graph_nodes promise and run layer by
         layer while the rest takes the LDS-resident stack (``gnnb_workspace_set_large_segment``); the caller orders the
-        batch so that they come last (``batching.order_large_last``).  No arguments: no large segment."""
+        batch so that they come last (``batching.order_large_last``).  No arguments: no large segment.  Takes effect at the next
+        graph prep (``set_max_graph_nodes``): a prepared batch keeps the segment it was prepared with, the one that was checked
+        against it."""
         _check(self.lib.gnnb_workspace_set_large_segment(self._ws, int(first_graph), int(first_node), int(first_edge)))
 
     @property
@@ -611,6 +619,9 @@ class CompiledModel:
             self._model, self._ws, x.ctypes.data_as(C.c_void_p), coo.ctypes.data_as(C.c_void_p),
             node_ptr.ctypes.data_as(C.c_void_p), edge_ptr.ctypes.data_as(C.c_void_p), B, x.shape[0],
             coo.shape[0], out.ctypes.data_as(C.c_void_p)))
+        # (the workspace now holds THIS batch's tables -- its index arrays live in the workspace's staging buffer: without this
+        # tables_to_host and the stage entries would size and check their buffers by the batch prepared before)
+        self._prepared(B, int(x.shape[0]), int(coo.shape[0]), None)
         return out
 
     # ------------------------------------------------------------------ PyG mini-batches

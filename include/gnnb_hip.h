@@ -155,7 +155,13 @@ size_t gnnb_workspace_bytes(const gnnb_workspace *ws);
  * larger graph makes gnnb_workspace_check() return GNNB_ERR_GRAPH (the reference's MAX_NODES, by
  * contrast, is never checked: model.cpp.jinja:5-22).  Callers that never call the check still find out: the NEXT
  * gnnb_graph_prep / gnnb_forward_batched on the workspace after a flagged batch has run returns GNNB_ERR_GRAPH
- * (read from a host-mapped word, no synchronisation; best effort -- the check is the authoritative answer). */
+ * (read from a host-mapped word, no synchronisation; best effort -- the check is the authoritative answer).
+ * WHEN IT TAKES EFFECT (this setter, gnnb_workspace_set_max_degree and gnnb_workspace_set_large_segment alike): at the next
+ * graph prep -- gnnb_graph_prep, or the prep inside gnnb_forward_batched* / gnnb_forward_pyg* / gnnb_forward_prepared_prep_next's
+ * ws_next.  Graph prep validates the three settings against its batch and bakes them into the tables; gnnb_forward_prepared,
+ * gnnb_forward_prepared_edges and gnnb_forward_prepared_prep_next run the PREPARED batch by what its prep baked, whatever has
+ * been set since.  A setter called between a graph prep and its prepared forward therefore changes nothing about that forward
+ * (same route, same bits as without the call) and applies from the next prep on. */
 int gnnb_workspace_set_max_graph_nodes(gnnb_workspace *ws, int n);
 /* Promise that no node of the batches run on this workspace has an in-degree above `d` (0 = no promise, the default).  The
  * reference knows a per-design degree figure only as a hint (Project(..., degree_guess, ...), code_gen.py:63-82: HLS loop trip
@@ -167,7 +173,9 @@ int gnnb_workspace_set_max_graph_nodes(gnnb_workspace *ws, int n);
  * the batch is prepared with the model's own pna_delta, and while the batch's rows x 16 x (layer input width) bytes + 512
  * stay below 2^32 (the class GEMM's 32-bit row offsets: up to 2^21 - 1 rows at width 128, 2^20 - 1 at 256); larger
  * batches run the general form, with the same results.  VALIDATED on the device by every graph prep like the node
- * promise (flag 32 of gnnb_workspace_check).  Other conv types ignore it. */
+ * promise (flag 32 of gnnb_workspace_check).  Other conv types ignore it.  Takes effect at the next graph prep (see
+ * gnnb_workspace_set_max_graph_nodes): the class tables belong to the prepared batch, and a prepared forward uses them if and
+ * only if its prep made them. */
 #define GNNB_DEG_CLASSES 16 /* in-degrees 0 .. 15 get a class each (0: PNA's scalers of degree 1, but no messages); a larger
                              * promise keeps the general form */
 int gnnb_workspace_set_max_degree(gnnb_workspace *ws, int d);
@@ -191,7 +199,9 @@ int gnnb_workspace_last_path(const gnnb_workspace *ws);
  * row and its first edge row (host integers: launch sizes depend on them).  Graphs [0, first_graph) keep the promise
  * (still validated on the device) and run in the stack kernel; graphs [first_graph, num_graphs) are unrestricted and run
  * through the layer-by-layer kernels; both halves fill one pooled matrix and share the readout.  The setting applies to
- * every following gnnb_graph_prep / forward on the workspace until it is changed; first_graph < 0 removes it.  The
+ * every following gnnb_graph_prep (and the forwards on what it prepared) until it is changed; first_graph < 0 removes it.  A
+ * batch that is ALREADY prepared keeps the segment it was prepared with -- the one that was checked against it: setting or
+ * removing the segment between gnnb_graph_prep and gnnb_forward_prepared* does not move the split of that forward.  The
  * triple must describe the batch it is used with: every graph prep checks ON THE DEVICE that first_node ==
  * node_ptr[first_graph] and first_edge == edge_ptr[first_graph] and flags the batch otherwise (GNNB_ERR_GRAPH from
  * gnnb_workspace_check, flag bit 16) -- a triple left over from the batch before would otherwise leave the rows between the
