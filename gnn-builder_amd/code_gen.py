@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from .models import (GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, PNAEConv_GNNB, ResGatedGraphConv_GNNB,
-                     TransformerConv_GNNB, TransformerEConv_GNNB)
+                     ResGatedGraphEConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB)
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
 CURRENT_DIR = Path(__file__).resolve().parent
@@ -122,6 +122,11 @@ class Project:
             raise NotImplementedError(
                 "Project does not generate ResGatedGraphConv designs: the generated shim and the templates have no gated layer; run "
                 "the model through runtime.CompiledModel.from_model(model, ...).forward / forward_pyg")
+        if getattr(model, "gnn_conv", None) is ResGatedGraphEConv_GNNB:
+            raise NotImplementedError(
+                "Project does not generate ResGatedGraphConv designs with edge features: the generated shim and the templates have "
+                "no gated layer and carry no edge attributes; run the model through runtime.CompiledModel.from_model(model, ...)"
+                ".forward_edges / forward_pyg_edges")
         self.model = model
         self.dataset = dataset
         self.name = name

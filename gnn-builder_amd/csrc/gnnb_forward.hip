@@ -272,7 +272,8 @@ static int transformer_layer(const LayerCtx &c)
 // ONE GEMM x -> [k | q | v | r] [N, 4 fo] on the stacked weight [W_k ; W_q ; W_v ; W_skip] in the model's math mode (conv.bias
 // rides as the skip block's GEMM bias), then ONE k_resgated_aggregate launch -- the per-column sigmoid gate and the gated sum of
 // the value rows in one pass over the edges, with the root term, the skip term and the activation in its epilogue.  None of the
-// fused rungs
+// fused rungs.  With edge features (gnnb_resgated_edge.h): the same GEMM on the x column blocks, then ONE
+// k_resgated_edge_aggregate launch, which forms both edge terms from the batch's edge attributes and w_gv_edge = [W_g ; W_v]
 static int resgated_layer(const LayerCtx &c)
 {
     const gnnb_model_desc &d = c.model->desc;
@@ -282,6 +283,13 @@ static int resgated_layer(const LayerCtx &c)
     int rc;
     if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_kqvr, fi, p.b_kqvr, nullptr, c.rows(kqvr, 4 * fo), 4 * fo, GNNB_ACT_NONE)))
         return rc;
+    if (const int ed = c.model->edge_dim) {
+        if (c.M > 0)
+            GNNB_HIP_TRY(launch_resgated_edge_aggregate(c.tv, kqvr, 4 * fo, kqvr + fo, 4 * fo, kqvr + 2 * fo, 4 * fo, kqvr + 3 * fo, 4 * fo, c.skip,
+                                                        d.activation, c.edge_attr, ed, p.w_gv_edge, ed, p.w_gv_edge + (size_t)fo * ed, ed, c.nxt,
+                                                        fo, c.hs()));
+        return GNNB_OK;
+    }
     if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
         GNNB_HIP_TRY(launch_resgated_aggregate(c.tv, kqvr, 4 * fo, kqvr + fo, 4 * fo, kqvr + 2 * fo, 4 * fo, kqvr + 3 * fo, 4 * fo, c.skip,
                                                d.activation, c.nxt, fo, c.hs()));

@@ -17,6 +17,7 @@
 #include "gnnb_transformer.h"
 #include "gnnb_transformer_edge.h"
 #include "gnnb_resgated.h"
+#include "gnnb_resgated_edge.h"
 
 namespace gnnb {
 
@@ -56,7 +57,8 @@ struct gnnb_model {
                             // with edge_dim > 0 besides: TransformerConv with edge features (gnnb_transformer_edge_model_create) --
                             // w_qkvre, b_qkvre and w_edge [out, edge_dim] instead
     int gated = 0;          // 1: a ResGatedGraphConv model (gnnb_resgated_model_create; desc is a GIN description) -- every layer has
-                            // w_kqvr, b_kqvr and none of GIN's slots
+                            // w_kqvr, b_kqvr and none of GIN's slots; with edge_dim > 0 besides: ResGatedGraphConv with edge features
+                            // (gnnb_resgated_edge_model_create) -- w_kqvr of the x column blocks, b_kqvr and w_gv_edge [2 out, edge_dim]
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };

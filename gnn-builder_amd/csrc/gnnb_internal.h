@@ -347,6 +347,14 @@ hipError_t launch_transformer_edge_aggregate(const BatchTables &t, const float *
 constexpr int RG_MAX_WIDTH = 256;
 hipError_t launch_resgated_aggregate(const BatchTables &t, const float *k, int ldk, const float *q, int ldq, const float *v, int ldv,
                                      const float *root, int ldr, const float *skip, int act, float *out, int width, hipStream_t s);
+// ResGatedGraphConv with edge features (k_resgated_edge.hip): the same with the gate's argument (k_i + q_j) + wg . e_ij and the value
+// v_j + wv . e_ij, per column; edge_attr [E, edge_dim] in COO row order (t.eid maps the CSR slots; nullptr only with num_edges == 0),
+// wg / wv [width, edge_dim] at row strides ldwg / ldwv >= edge_dim, edge_dim 1 .. 16.  The kernel computes what it is given:
+// wg = W_ke + W_qe is the caller's business.  hipErrorInvalidValue: nothing launched
+constexpr int RGE_MAX_EDGE_DIM = 16;
+hipError_t launch_resgated_edge_aggregate(const BatchTables &t, const float *k, int ldk, const float *q, int ldq, const float *v, int ldv,
+                                          const float *root, int ldr, const float *skip, int act, const float *edge_attr, int edge_dim,
+                                          const float *wg, int ldwg, const float *wv, int ldwv, float *out, int width, hipStream_t s);
 // the ingest's edge attributes in COO row order (k_ingest.hip): out[i] = edge_attr[state[INGEST_STATE_UNSORTED] ? idx[i] : i]; idx:
 // the general path's sorted-position -> input-edge array (nullptr: that path was not launched), state: IngestParams::state
 hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,

@@ -147,12 +147,16 @@ int count_transformer_params(const gnnb_model_desc *desc, int heads, int edge_di
 }
 
 // parameter tensors of a ResGatedGraphConv model (gnnb_resgated.h): a GIN description (its tables keep explicit (v, v) edges) without
-// the fixed-point emulation, every layer's output width at most 256
-int count_resgated_params(const gnnb_model_desc *desc)
+// the fixed-point emulation, every layer's output width at most 256 (edge_dim != 0: with edge features, gnnb_resgated_edge.h -- the
+// same eight tensors per layer, lin_key / lin_query / lin_value [out, in + edge_dim])
+int count_resgated_params(const gnnb_model_desc *desc, int edge_dim = 0)
 {
     int rc = validate_desc(desc);
     if (rc != GNNB_OK)
         return rc;
+    if (edge_dim != 0 && (edge_dim < 1 || edge_dim > RGE_MAX_EDGE_DIM))
+        return fail(GNNB_ERR_INVALID, "edge_dim %d: a ResGatedGraphConv model with edge features takes edge_dim 1 .. %d", edge_dim,
+                    RGE_MAX_EDGE_DIM);
     if (desc->conv_type != GNNB_CONV_GIN)
         return fail(GNNB_ERR_INVALID, "a ResGatedGraphConv model's description is a GIN description (conv_type %d given)", desc->conv_type);
     if (desc->fpx_w != 0)
@@ -170,7 +174,8 @@ int count_resgated_params(const gnnb_model_desc *desc)
 // (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features), or heads of a
 // TransformerConv model (gnnb_transformer_model_create: a GIN description), or heads and edge_dim
 // (gnnb_transformer_edge_model_create: TransformerConv with edge features), or the "gated" mark of a ResGatedGraphConv model
-// (gnnb_resgated_model_create: a GIN description)
+// (gnnb_resgated_model_create: a GIN description), or that mark and edge_dim (gnnb_resgated_edge_model_create: ResGatedGraphConv with
+// edge features)
 struct ModelKind {
     int edge_dim = 0, base = GNNB_CONV_GIN;
     int gat_heads = 0;
@@ -214,16 +219,22 @@ struct ModelKind {
         k.gated = true;
         return k;
     }
+    static ModelKind resgated_edges(int edge_dim)
+    {
+        ModelKind k = resgated();
+        k.edge_dim = edge_dim;
+        return k;
+    }
 };
 
-// the body of the eight *_model_create entries
+// the body of the nine *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
         return fail(GNNB_ERR_INVALID, "null out_model");
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
-    int expect = kind.gated       ? count_resgated_params(desc)
+    int expect = kind.gated       ? count_resgated_params(desc, edge_dim)
                  : tf_heads != 0  ? count_transformer_params(desc, tf_heads, edge_dim)
                  : gat_heads != 0 ? count_gat_params(desc, gat_heads, edge_dim)
                                   : count_params(desc, edge_dim, kind.base);
@@ -410,6 +421,23 @@ int gnnb_resgated_model_create(const gnnb_model_desc *desc, const float *const *
 }
 
 int gnnb_model_is_resgated(const gnnb_model *model) { return model ? model->gated : 0; }
+
+int gnnb_resgated_edge_model_num_params(const gnnb_model_desc *desc, int edge_dim)
+{
+    if (edge_dim == 0) // (count_resgated_params reads 0 as "no edge features")
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a ResGatedGraphConv model with edge features takes edge_dim 1 .. %d", RGE_MAX_EDGE_DIM);
+    return count_resgated_params(desc, edge_dim);
+}
+
+int gnnb_resgated_edge_model_create(const gnnb_model_desc *desc, int edge_dim, const float *const *host_params, int num_params,
+                                    gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (edge_dim == 0) // (... and as "no edge features")
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a ResGatedGraphConv model with edge features takes edge_dim 1 .. %d", RGE_MAX_EDGE_DIM);
+    return model_create(desc, ModelKind::resgated_edges(edge_dim), host_params, num_params, out_model);
+}
 
 void gnnb_model_destroy(gnnb_model *model)
 {

@@ -816,6 +816,29 @@ int gnnb_aggregate_resgated(gnnb_workspace *ws, const float *k_dev, int ldk, con
     return GNNB_OK;
 }
 
+int gnnb_aggregate_resgated_edges(gnnb_workspace *ws, const float *k_dev, int ldk, const float *q_dev, int ldq, const float *v_dev, int ldv,
+                                  const float *root_dev, int ldr, const float *skip_dev, int act, const float *edge_attr_dev, int edge_dim,
+                                  const float *wg_dev, int ldwg, const float *wv_dev, int ldwv, float *out_dev, int width, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_resgated_edges needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's with or without edge features)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_resgated_edges takes a prepared batch whose tables keep explicit self loops: graph prep "
+                                      "drops the (v, v) edges on a workspace of a GCN description (a GCN or GATv2 model's), and this layer "
+                                      "counts them as ordinary edges");
+    if (!k_dev || !q_dev || !v_dev || !out_dev || width < 1 || width > RG_MAX_WIDTH || ldk < width || ldq < width || ldv < width ||
+        (root_dev && ldr < width) || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE)
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_resgated_edges (k, q, v and out not NULL, width 1 .. %d, ldk, ldq, ldv "
+                                      "and root's ldr >= width, a gnnb_act)", RG_MAX_WIDTH);
+    if (!wg_dev || !wv_dev || edge_dim < 1 || edge_dim > RGE_MAX_EDGE_DIM || ldwg < edge_dim || ldwv < edge_dim ||
+        (ws->t.num_edges > 0 && !edge_attr_dev))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_resgated_edges (wg and wv, edge_dim 1 .. %d, ldwg and ldwv >= edge_dim, "
+                                      "edge_attr for a batch with edges)", RGE_MAX_EDGE_DIM);
+    GNNB_HIP_TRY(launch_resgated_edge_aggregate(ws->t, k_dev, ldk, q_dev, ldq, v_dev, ldv, root_dev, ldr, skip_dev, act, edge_attr_dev, edge_dim,
+                                                wg_dev, ldwg, wv_dev, ldwv, out_dev, width, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
 int gnnb_aggregate_transformer_edges(gnnb_workspace *ws, const float *q_dev, int ldq, const float *k_dev, int ldk, const float *v_dev, int ldv,
                                      const float *qe_dev, int ldqe, const float *root_dev, int ldr, const float *skip_dev, int act, int heads,
                                      float scale, const float *edge_attr_dev, int edge_dim, const float *we_dev, int ldwe, float *out_dev,

@@ -113,6 +113,14 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //              b_kqvr [4 out]                       derived: [b_k ; b_q ; b_v ; bias], canonical 1, 3, 5 and 7 (conv.bias): lin_skip has
 //                                                   no bias, so the conv's own rides as the skip block's GEMM bias.  b_q is NOT
 //                                                   folded into b_k: every block keeps the rounding of its own linear
+//   ResGatedGraphConv + edges  (gated and edge_dim > 0, gnnb_resgated_edge_model_create) lin_key / lin_query / lin_value are
+//              [out, in + edge_dim], the x columns first
+//              w_kqvr [4 out, in]                   derived: [W_kx ; W_qx ; W_vx ; W_skip] -- the x column blocks, copied
+//              b_kqvr [4 out]                       as above
+//              w_gv_edge [2 out, edge_dim]          derived: [W_g ; W_v], W_g = W_ke + W_qe (the e column blocks of lin_key and
+//                                                   lin_query: both enter the gate's argument; added in double, rounded once --
+//                                                   resgated_edge_blocks), W_v = W_ve, copied -- what k_resgated_edge_aggregate adds
+//                                                   per edge to the gate's argument and to the value
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
@@ -120,7 +128,7 @@ template <typename T> struct LayerSlots {
     T w_lr = absent_slot<T>(), b_lr = absent_slot<T>(), att = absent_slot<T>(), gat_bias = absent_slot<T>(), w_edge = absent_slot<T>();
     T w_qkvr = absent_slot<T>(), b_qkvr = absent_slot<T>();
     T w_qkvre = absent_slot<T>(), b_qkvre = absent_slot<T>();
-    T w_kqvr = absent_slot<T>(), b_kqvr = absent_slot<T>();
+    T w_kqvr = absent_slot<T>(), b_kqvr = absent_slot<T>(), w_gv_edge = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -129,7 +137,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -391,6 +399,28 @@ inline WeightBias transformer_edge_fold(const float *w_q, const float *b_q, cons
     return f;
 }
 
+// ResGatedGraphConv with edge features: a linear's [fo, fi + edge_dim] weight (x columns first) split.  x_cols: its [fo, fi] block
+inline std::vector<float> resgated_x_cols(const float *w, size_t fi, size_t fo, size_t edge_dim)
+{
+    std::vector<float> x(fo * fi);
+    for (size_t c = 0; c < fo; c++)
+        memcpy(&x[c * fi], w + c * (fi + edge_dim), fi * sizeof(float));
+    return x;
+}
+// ... and [W_g ; W_v] [2 fo, edge_dim]: W_g[c][t] = W_ke[c][t] + W_qe[c][t] in double, rounded once (the gate's argument takes
+// lin_key's and lin_query's edge terms, both of the same e_ij); W_v = W_ve, copied
+inline std::vector<float> resgated_edge_blocks(const float *w_key, const float *w_query, const float *w_value, size_t fi, size_t fo, size_t edge_dim)
+{
+    std::vector<float> gv(2 * fo * edge_dim);
+    const size_t ld = fi + edge_dim;
+    for (size_t c = 0; c < fo; c++)
+        for (size_t t = 0; t < edge_dim; t++) {
+            gv[c * edge_dim + t] = (float)((double)w_key[c * ld + fi + t] + (double)w_query[c * ld + fi + t]);
+            gv[(fo + c) * edge_dim + t] = w_value[c * ld + fi + t];
+        }
+    return gv;
+}
+
 constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_gat.h); one more with edge features (gnnb_gat_edge.h)
 constexpr int TF_PARAM_SLOTS = 8;  // a TransformerConv layer's canonical tensors (gnnb_transformer.h); one more with edge features
                                    // (gnnb_transformer_edge.h)
@@ -406,6 +436,15 @@ inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, i
     const size_t fi = ld.fin, fo = ld.fout;
     if (gated) { // (a GIN description whose layers are ResGatedGraphConv's; canonical order: key, query, value, skip weight, conv.bias)
         LayerOffsets g;
+        if (edge_dim > 0) { // (... with edge features, gnnb_resgated_edge.h: the same eight, key / query / value [fo, fi + edge_dim])
+            const size_t ed = (size_t)edge_dim;
+            const std::vector<float> kx = resgated_x_cols(p[0], fi, fo, ed), qx = resgated_x_cols(p[2], fi, fo, ed),
+                                     vx = resgated_x_cols(p[4], fi, fo, ed);
+            g.w_kqvr = im.push(stack_rows({kx.data(), qx.data(), vx.data(), p[6]}, fo, fi));
+            g.b_kqvr = im.push(stack_rows({p[1], p[3], p[5], p[7]}, fo, 1));
+            g.w_gv_edge = im.push(resgated_edge_blocks(p[0], p[2], p[4], fi, fo, ed));
+            return g;
+        }
         g.w_kqvr = im.push(stack_rows({p[0], p[2], p[4], p[6]}, fo, fi));
         g.b_kqvr = im.push(stack_rows({p[1], p[3], p[5], p[7]}, fo, 1));
         return g;
@@ -501,7 +540,8 @@ struct BuiltWeights {
 // fragment copy -- it takes no stack kernel); with edge_dim > 0 besides, GATv2 with edge features (seven tensors per layer).
 // tf_heads > 0: a TransformerConv model (a GIN description, eight tensors per layer; no execution-order copy -- no stack kernel);
 // with edge_dim > 0 besides, TransformerConv with edge features (nine tensors per layer).  gated: a ResGatedGraphConv model (a GIN
-// description, eight tensors per layer; no execution-order copy either).
+// description, eight tensors per layer; no execution-order copy either); with edge_dim > 0 besides, ResGatedGraphConv with edge
+// features (the same eight, three of them [out, in + edge_dim]).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
                                        int tf_heads = 0, bool gated = false)
 {

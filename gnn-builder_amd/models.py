@@ -660,8 +660,8 @@ class ResGatedGraphConv_GNNB(nn.Module):
     accelerated path is ``runtime.CompiledModel.from_model`` with the ordinary ``forward`` / ``forward_pyg`` (C ABI
     ``include/gnnb_resgated.h``: one GEMM ``x -> [k | q | v | r]`` and one launch of csrc/k_resgated.hip per layer, the gate formed
     inside the aggregate).  This class ignores ``graph_input_edge_dim`` and ``edge_attr``: PyG's ``edge_dim`` form, which
-    concatenates ``e_ij`` to the inputs of key, query and value, is a model kind of its own and out of scope, as are
-    ``root_weight=False``, ``bias=False`` and other gates.  ``Project`` does not generate such designs."""
+    concatenates ``e_ij`` to the inputs of key, query and value, is a model kind of its own -- ``ResGatedGraphEConv_GNNB``
+    below.  Out of scope: ``root_weight=False``, ``bias=False`` and other gates.  ``Project`` does not generate such designs."""
 
     def __init__(self, in_channels: int, out_channels: int, p_in: int = 1, p_out: int = 1):
         super().__init__()
@@ -673,6 +673,62 @@ class ResGatedGraphConv_GNNB(nn.Module):
 
     def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
         return self.conv(x, edge_index)
+
+
+class _ResGatedGraphEConv(nn.Module):
+    """PyG's ``ResGatedGraphConv(in_channels, out_channels, act=Sigmoid(), edge_dim=d, root_weight=True, bias=True)``: the gated
+    graph conv whose key, query and value see the edge's attributes, concatenated behind the node's features per edge::
+
+        k_ij = lin_key([x_i | e_ij])   q_ij = lin_query([x_j | e_ij])   v_ij = lin_value([x_j | e_ij])     [out] each
+        out_i = sum_j sigmoid(k_ij + q_ij) * v_ij + lin_skip(x_i) + bias      for j in N(i), the input's edges as they are
+
+    Modules in PyG's order and with PyG's shapes, so that a PyG ``state_dict`` loads: ``lin_key``, ``lin_query``, ``lin_value``
+    -- each ``nn.Linear(in + d, out, bias=True)`` --, ``lin_skip`` -- ``nn.Linear(in, out, bias=False)`` --, and the conv's own
+    ``bias`` [out], zero-initialised.  No self loop is added and none is removed; an explicit ``(v, v)`` edge is an ordinary edge
+    with its own attribute row; a node without in-edges gets ``lin_skip(x_i) + bias`` alone.  Out of scope:
+    ``root_weight=False``, ``bias=False``, gates other than the sigmoid."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int):
+        super().__init__()
+        self.out_channels = out_channels
+        self.edge_dim = edge_dim
+        self.lin_key = nn.Linear(in_channels + edge_dim, out_channels)
+        self.lin_query = nn.Linear(in_channels + edge_dim, out_channels)
+        self.lin_value = nn.Linear(in_channels + edge_dim, out_channels)
+        self.lin_skip = nn.Linear(in_channels, out_channels, bias=False)
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        src, dst = edge_index[0].long(), edge_index[1].long()
+        e = edge_attr.to(x.dtype).reshape(src.numel(), self.edge_dim)
+        k = self.lin_key(torch.cat([x[dst], e], dim=-1))
+        q = self.lin_query(torch.cat([x[src], e], dim=-1))
+        v = self.lin_value(torch.cat([x[src], e], dim=-1))
+        out = x.new_zeros(x.shape[0], self.out_channels).index_add(0, dst, torch.sigmoid(k + q) * v)
+        return out + self.lin_skip(x) + self.bias
+
+
+class ResGatedGraphEConv_GNNB(nn.Module):
+    """The residual gated graph conv with edge features: PyG's ``ResGatedGraphConv(in_channels, out_channels, edge_dim=d)``.
+    ``GNNModel(..., graph_input_edge_dim=d, gnn_conv=ResGatedGraphEConv_GNNB)`` builds every layer with ``edge_dim=d`` (1 .. 16)
+    and ``forward(x, edge_index, batch, edge_attr)`` hands the same ``edge_attr`` [E, d] to each (``gnn_heads`` stays 1).  The
+    accelerated path is ``runtime.CompiledModel.from_model`` with ``forward_edges`` / ``forward_pyg_edges`` (C ABI
+    ``include/gnnb_resgated_edge.h``: one GEMM ``x -> [k | q | v | r]`` and one launch of csrc/k_resgated_edge.hip per layer).
+    Out of scope: ``root_weight=False``, ``bias=False`` and other gates.  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        if not isinstance(edge_dim, int) or isinstance(edge_dim, bool) or not 1 <= edge_dim <= 16:
+            raise ValueError(f"edge_dim must be an int in 1 .. 16 (got {edge_dim!r})")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.edge_dim = edge_dim
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _ResGatedGraphEConv(in_channels, out_channels, edge_dim)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        return self.conv(x, edge_index, edge_attr)
 
 
 # --------------------------------------------------------------------------------------- pooling / MLP
@@ -786,13 +842,15 @@ class MLP(nn.Module):
 
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
-                       GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB]
+                       GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB,
+                       ResGatedGraphEConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
               PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
-              TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated"}
+              TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated", ResGatedGraphEConv_GNNB: "resgatede"}
 # convs that take edge_attr, and what the messages call them
-_EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE"}
-MAX_EDGE_DIM = 16  # of a GINE, PNAE, GATv2E or TransformerE model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h, gnnb_transformer_edge.h)
+_EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE",
+               ResGatedGraphEConv_GNNB: "ResGatedE"}
+MAX_EDGE_DIM = 16  # of a GINE, PNAE, GATv2E, TransformerE or ResGatedE model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h, gnnb_transformer_edge.h, gnnb_resgated_edge.h)
 _GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # the GATv2 convs (heads and negative_slope travel beside a GCN description)
 _TF_CONVS = (TransformerConv_GNNB, TransformerEConv_GNNB)  # the TransformerConv convs (heads travel beside a GIN description)
 _HEAD_CONVS = _GAT_CONVS + _TF_CONVS  # convs with attention heads: the ones that take gnn_heads
@@ -878,7 +936,7 @@ class GNNModel(nn.Module):
         (node -> graph index, PyG ``Batch`` convention) every graph is pooled separately ->
         ``[num_graphs, out]``; the reference ignores ``batch`` and pools all nodes into one row
         (models.py:551-553,569; SURVEY finding 3), which has no meaning for independent graphs.
-        ``edge_attr`` [E, graph_input_edge_dim]: a GINE, PNAE, GATv2E or TransformerE model's edge features, the same for every layer (required
+        ``edge_attr`` [E, graph_input_edge_dim]: a GINE, PNAE, GATv2E, TransformerE or ResGatedE model's edge features, the same for every layer (required
         there; the other convs ignore it)."""
         gine = self.gnn_conv in _EDGE_CONVS
         if gine and edge_attr is None:
@@ -1008,6 +1066,7 @@ class GNNModel(nn.Module):
         # (key, query, value with their biases, lin_skip's weight -- it has no bias --, then the conv's own bias: include/gnnb_resgated.h)
         per_conv["resgated"] = [f"conv_lin_{n}_{t}" for n in ("key", "query", "value") for t in ("weight", "bias")] + [
             "conv_lin_skip_weight", "conv_bias"]
+        per_conv["resgatede"] = per_conv["resgated"]  # (the same eight; key, query and value weights are [out, in + edge_dim])
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

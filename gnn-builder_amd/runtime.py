@@ -30,15 +30,17 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
-# spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h)
-_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere")
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
+# spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h,
+# "resgatede": gnnb_resgated_edge.h)
+_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede")
 _GAT_CONVS = ("gatv2", "gatv2e")       # ... and of those with heads and negative_slope beside it
 # a TransformerConv model (include/gnnb_transformer.h, spec["conv"] == "transformer"): its description is GIN's -- the tables keep
 # explicit (v, v) edges --, heads travels beside it; with edge features ("transformere", include/gnnb_transformer_edge.h) edge_dim too
 _TRANSFORMER_CONVS = ("transformer", "transformere")
 MAX_TRANSFORMER_HEADS, MAX_TRANSFORMER_WIDTH = 8, 256
 # a ResGatedGraphConv model (include/gnnb_resgated.h, spec["conv"] == "resgated"): its description is GIN's too, a "gated" mark beside it
+# ... with edge features ("resgatede", include/gnnb_resgated_edge.h): edge_dim beside it too
 MAX_RESGATED_WIDTH = 256
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
@@ -222,6 +224,14 @@ ABI_RESGATED = {
 }
 
 
+# ... and of include/gnnb_resgated_edge.h (ResGatedGraphConv models with edge features), in its order (tests/test_abi_resgated_edge.py)
+ABI_RESGATED_EDGE = {
+    "gnnb_resgated_edge_model_num_params": (_I, [_DESC, _I]),
+    "gnnb_resgated_edge_model_create": (_I, [_DESC, _I, _PP, _I, _PP]),
+    "gnnb_aggregate_resgated_edges": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -266,7 +276,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
         for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER,
-                                           **ABI_TRANSFORMER_EDGE, **ABI_RESGATED}.items():
+                                           **ABI_TRANSFORMER_EDGE, **ABI_RESGATED, **ABI_RESGATED_EDGE}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -427,6 +437,7 @@ class CompiledModel:
         n_expect = (self.lib.gnnb_gat_edge_model_num_params(C.byref(self.desc), self.gat_heads, self.edge_dim) if spec.get("conv") == "gatv2e" else
                     self.lib.gnnb_transformer_edge_model_num_params(C.byref(self.desc), self.transformer_heads, self.edge_dim)
                     if spec.get("conv") == "transformere" else
+                    self.lib.gnnb_resgated_edge_model_num_params(C.byref(self.desc), self.edge_dim) if spec.get("conv") == "resgatede" else
                     num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
                     self.lib.gnnb_gat_model_num_params(C.byref(self.desc), self.gat_heads) if spec.get("conv") == "gatv2" else
                     self.lib.gnnb_transformer_model_num_params(C.byref(self.desc), self.transformer_heads) if spec.get("conv") == "transformer" else
@@ -443,6 +454,8 @@ class CompiledModel:
         elif spec.get("conv") == "transformere":  # (gnnb_transformer_edge.h: a GIN description, heads and edge_dim beside it)
             _check(self.lib.gnnb_transformer_edge_model_create(C.byref(self.desc), self.transformer_heads, self.edge_dim, arr, len(host),
                                                                C.byref(self._model)))
+        elif spec.get("conv") == "resgatede":  # (gnnb_resgated_edge.h: a GIN description, the "gated" mark and edge_dim beside it)
+            _check(self.lib.gnnb_resgated_edge_model_create(C.byref(self.desc), self.edge_dim, arr, len(host), C.byref(self._model)))
         elif self.edge_dim:
             _check(create(C.byref(self.desc), self.edge_dim, arr, len(host), C.byref(self._model)))
         elif spec.get("conv") == "gatv2":  # (gnnb_gat.h: a GCN description, heads and negative_slope beside it)
@@ -1019,6 +1032,43 @@ class CompiledModel:
         _check(self.lib.gnnb_aggregate_resgated(self._ws, _dptr(k), ld(k), _dptr(q), ld(q), _dptr(v), ld(v), _optr(root),
                                                 ld(root) if root is not None else w, _optr(skip), ACT[act], _dptr(out), w,
                                                 _stream_ptr(stream)))
+        return out
+
+    def aggregate_resgated_edges(self, k, q, v, edge_attr, w_gate, w_value, root=None, skip=None, act: str = "none", out=None, stream=None):
+        """One ResGatedGraphConv layer with edge features behind its GEMM (``gnnb_aggregate_resgated_edges``,
+        csrc/k_resgated_edge.hip) on the prepared batch of a workspace whose tables keep explicit self loops:
+        ``aggregate_resgated`` with the gate ``sigmoid((k_i + q_j) + w_gate e_ij)`` and the value ``v_j + w_value e_ij``, per
+        column.  ``k``, ``q``, ``v``, ``root``, ``skip`` as there; ``edge_attr`` [E, edge_dim <= 16] in COO order; ``w_gate`` (the
+        layer passes ``W_ke + W_qe``; the entry computes what it is given) and ``w_value`` [width, edge_dim], separate operands;
+        column slices of wider matrices are fine for them too: their row strides are passed on."""
+        _require_strided(k, "k", self._N, 1)
+        w = int(k.shape[1])
+        for name, t in (("q", q), ("v", v), ("root", root)):
+            if t is None and name == "root":
+                continue
+            _require_strided(t, name, self._N, w)
+            if int(t.shape[1]) != w or t.device != k.device:
+                raise GnnbError(f"{name} must be [{self._N}, {w}] on {k.device}, got {tuple(t.shape)} on {t.device}")
+        if w > MAX_RESGATED_WIDTH:
+            raise GnnbError(f"width {w}: a ResGatedGraphConv layer is at most {MAX_RESGATED_WIDTH} wide")
+        if act not in ACT:
+            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, k)
+        _require_strided(w_gate, "w_gate", w, 1)
+        ed = int(w_gate.shape[1])
+        if not 1 <= ed <= MAX_EDGE_DIM or w_gate.device != k.device:
+            raise GnnbError(f"w_gate must be [{w}, 1 .. {MAX_EDGE_DIM}] on {k.device}, got {tuple(w_gate.shape)} on {w_gate.device}")
+        _require_strided(w_value, "w_value", w, ed)
+        if int(w_value.shape[1]) != ed or w_value.device != k.device:
+            raise GnnbError(f"w_value must be [{w}, {ed}] on {k.device}, got {tuple(w_value.shape)} on {w_value.device}")
+        ea = self._require_edge_attr(edge_attr, self._E, k, ed)
+        out = _out(out, self._N, w, k)
+        ld = lambda t: int(t.stride(0)) if self._N > 1 else w  # noqa: E731  (one row: any stride describes it)
+        ldw = lambda t: int(t.stride(0)) if w > 1 else ed  # noqa: E731
+        _check(self.lib.gnnb_aggregate_resgated_edges(self._ws, _dptr(k), ld(k), _dptr(q), ld(q), _dptr(v), ld(v), _optr(root),
+                                                      ld(root) if root is not None else w, _optr(skip), ACT[act], ea, ed, _dptr(w_gate),
+                                                      ldw(w_gate), _dptr(w_value), ldw(w_value), _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def aggregate_transformer_edges(self, q, k, v, qe, edge_attr, w_edge, root=None, skip=None, act: str = "none", heads: int = 1,

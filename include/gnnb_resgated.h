@@ -31,7 +31,8 @@
  * edge weights; gnnb_forward_pyg_ordered refuses it and names gnnb_forward_pyg.  A model matches a workspace only if both are
  * gated.
  *
- * Out of scope: edge_dim (PyG concatenates e_ij to the inputs of key, query and value: a model kind of its own), root_weight =
+ * Out of scope: edge_dim (PyG concatenates e_ij to the inputs of key, query and value: a model kind of its own --
+ * gnnb_resgated_edge.h has it, with its own creation entry and stage entry; the entries below do not take it), root_weight =
  * False and bias = False at model level (the stage entry's root = NULL covers the kernel side), gates other than sigmoid, widths
  * above 256.
  */
