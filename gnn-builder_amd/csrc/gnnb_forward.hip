@@ -75,9 +75,9 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     G2Deep g;
     g.nl = 0;
     const int L = d.num_layers;
-    // a GINE model: no stack kernel forms the edge term; a GATv2 model, a TransformerConv model: none forms attention; a
-    // ResGatedGraphConv model: none forms the gate
-    if (model->edge_dim || model->gat_heads || model->tf_heads || model->gated)
+    // a GINE model: no stack kernel forms the edge term; a GATv2 model, a GAT v1 model, a TransformerConv model: none forms
+    // attention; a ResGatedGraphConv model: none forms the gate
+    if (model->edge_dim || model->gat_heads || model->gat1_heads || model->tf_heads || model->gated)
         return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
@@ -230,6 +230,27 @@ static int gat_layer(const LayerCtx &c)
     else if (c.M > 0)
         GNNB_HIP_TRY(launch_gatv2_aggregate(c.tv, lr, 2 * fo, lr + fo, 2 * fo, p.att, p.gat_bias, c.skip, d.activation, c.model->gat_heads,
                                             c.model->gat_slope, c.nxt, fo, c.hs()));
+    return GNNB_OK;
+}
+
+// GAT v1 (gnnb_gatconv.h; a GCN description with heads beside it): ONE GEMM x -> [xl | s_src | s_dst | pad] [N, fo + roundup4(2 heads)]
+// on w_gat = [W ; A_src W ; A_dst W ; 0] in the model's math mode, without a bias -- both per-node scores are linear in x, so att is
+// folded into the weight at upload and they cost 2 heads more output columns --, then ONE k_gat_aggregate launch: leaky_relu of the
+// sum of two scalars per (edge, head), softmax and weighted sum in one pass over the edges, with the bias, the skip term and the
+// activation in its epilogue.  None of the fused rungs
+static int gat1_layer(const LayerCtx &c)
+{
+    const gnnb_model_desc &d = c.model->desc;
+    const LayerWeights &p = c.model->conv[c.l];
+    const int fi = c.fi, fo = c.fo, heads = c.model->gat1_heads;
+    const int ld = fo + (int)gat_score_rows(heads);
+    float *xs = c.ws->tmp0;
+    int rc;
+    if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_gat, fi, nullptr, nullptr, c.rows(xs, ld), ld, GNNB_ACT_NONE)))
+        return rc;
+    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+        GNNB_HIP_TRY(launch_gat_aggregate(c.tv, xs, ld, xs + fo, ld, xs + fo + heads, ld, p.gat_bias, c.skip, d.activation, heads,
+                                          c.model->gat_slope, c.nxt, fo, c.hs()));
     return GNNB_OK;
 }
 
@@ -472,7 +493,7 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
         c.skip_fold = c.skip != nullptr && c.fi == c.fo && !c.fpx;
         int rc = GNNB_OK;
         switch (d.conv_type) {
-        case GNNB_CONV_GCN: rc = model->gat_heads ? gat_layer(c) : gcn_layer(c); break;
+        case GNNB_CONV_GCN: rc = model->gat_heads ? gat_layer(c) : model->gat1_heads ? gat1_layer(c) : gcn_layer(c); break;
         case GNNB_CONV_GIN: rc = model->tf_heads ? transformer_layer(c) : model->gated ? resgated_layer(c) : gin_layer(c); break;
         case GNNB_CONV_SAGE: rc = sage_layer(c); break;
         case GNNB_CONV_PNA: rc = pna_layer(c); break;
@@ -749,7 +770,8 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
     if (!ws->prepared)
         return fail(GNNB_ERR_INVALID, "workspace has no prepared batch");
     if (memcmp(&model->desc, &ws->desc, sizeof(gnnb_model_desc)) != 0 || model->edge_dim != ws->edge_dim ||
-        model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope || model->tf_heads != ws->tf_heads || model->gated != ws->gated)
+        model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope || model->gat1_heads != ws->gat1_heads ||
+        model->tf_heads != ws->tf_heads || model->gated != ws->gated)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;

@@ -14,6 +14,7 @@
 #include "gnnb_pna_edge.h"
 #include "gnnb_gat.h"
 #include "gnnb_gat_edge.h"
+#include "gnnb_gatconv.h"
 #include "gnnb_transformer.h"
 #include "gnnb_transformer_edge.h"
 #include "gnnb_resgated.h"
@@ -51,7 +52,9 @@ struct gnnb_model {
     int edge_dim = 0; // > 0: a GINE model (gnnb_edge_model_create) or PNA with edge features (gnnb_pna_edge_model_create: desc.conv_type says which) -- every layer has edge_w [in, edge_dim] and edge_b [in]
     int gat_heads = 0;      // > 0: a GATv2 model (gnnb_gat_model_create; desc is a GCN description) -- every layer has w_lr, b_lr, att, gat_bias;
                             // with edge_dim > 0 besides: GATv2 with edge features (gnnb_gat_edge_model_create) -- and w_edge [out, edge_dim]
-    float gat_slope = 0.0f; // ... and its leaky_relu slope
+    float gat_slope = 0.0f; // ... and its leaky_relu slope (a GAT v1 model's as well)
+    int gat1_heads = 0;     // > 0: a GAT v1 model (gnnb_gatconv_model_create; desc is a GCN description) -- every layer has w_gat and
+                            // gat_bias and none of GCN's slots.  Its own field: gnnb_model_gat_heads stays 0 for such a model
     int tf_heads = 0;       // > 0: a TransformerConv model (gnnb_transformer_model_create; desc is a GIN description) -- every layer has
                             // w_qkvr, b_qkvr and none of GIN's slots.  Its own field: gnnb_model_gat_heads stays 0 for such a model;
                             // with edge_dim > 0 besides: TransformerConv with edge features (gnnb_transformer_edge_model_create) --
@@ -80,6 +83,7 @@ struct gnnb_workspace {
     int edge_dim = 0;            // of the model the workspace was created for (0: no edge weights)
     int gat_heads = 0;           // ... and its heads and slope when it is a GATv2 model (0: it is not)
     float gat_slope = 0.0f;
+    int gat1_heads = 0;          // ... and its heads when it is a GAT v1 model (0: it is not; its slope is gat_slope)
     int tf_heads = 0;            // ... and its heads when it is a TransformerConv model (0: it is not)
     int gated = 0;               // ... and 1 when it is a ResGatedGraphConv model
     char *edge_blob = nullptr;   // gnnb_workspace_enable_edge_ingest: edge_attr in COO row order, [max_edges, edge_dim], one allocation
@@ -124,6 +128,9 @@ int refuse_edge_model(const gnnb_model *model, const gnnb_workspace *ws, const c
 
 // GNNB_OK, or GNNB_ERR_INVALID for a GATv2 model / its workspace at `entry`, which serves the stack kernels' promise only: says which entry runs it
 int refuse_gat_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
+
+// ... and for a GAT v1 model / its workspace (gnnb_gatconv.h)
+int refuse_gatconv_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
 
 // ... and for a TransformerConv model / its workspace (gnnb_transformer.h)
 int refuse_transformer_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);

@@ -205,6 +205,8 @@ int gnnb_forward_pyg_ordered(const gnnb_model *model, gnnb_workspace *ws, const 
         return rc;
     if (const int rc = refuse_gat_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg"))
         return rc;
+    if (const int rc = refuse_gatconv_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg"))
+        return rc;
     if (const int rc = refuse_transformer_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg"))
         return rc;
     if (const int rc = refuse_resgated_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg"))

@@ -322,6 +322,13 @@ hipError_t launch_gatv2_aggregate(const BatchTables &t, const float *xl, int ldl
 hipError_t launch_gatv2_edge_aggregate(const BatchTables &t, const float *xl, int ldl, const float *xr, int ldr, const float *att,
                                        const float *bias, const float *skip, int act, int heads, float slope, const float *edge_attr, int edge_dim,
                                        const float *we, int ldwe, float *out, int width, hipStream_t s);
+// GAT v1 (k_gat.hip): out [N, width] = act(sum_j softmax_j(s_ij) xl_j + bias + skip_i) over j in N(i) u {i}, per head of width / heads
+// columns, s_ij[h] = leaky_relu(ssrc_j[h] + sdst_i[h]); xl: rows of stride ldl >= width, ssrc / sdst: rows of `heads` floats at strides
+// lds / ldd >= heads (the column blocks of one GEMM output), bias [width] or nullptr, skip [N, width] or nullptr; heads and width
+// within GATv2's limits; the tables of a GCN workspace (no (v, v) edges: the kernel adds the self term).  hipErrorInvalidValue:
+// nothing launched
+hipError_t launch_gat_aggregate(const BatchTables &t, const float *xl, int ldl, const float *ssrc, int lds, const float *sdst, int ldd,
+                                const float *bias, const float *skip, int act, int heads, float slope, float *out, int width, hipStream_t s);
 // TransformerConv (k_transformer.hip): out [N, width] = act((sum_j softmax_j(s_ij) v_j + root_i) + skip_i) over j in N(i) as the tables
 // hold it, per head of width / heads columns, s_ij = (q_i . k_j) * scale; q / k / v / root: rows of stride ldq / ldk / ldv / ldr >=
 // width (the column blocks of one GEMM output), root [N, width] or nullptr (ldr ignored), skip [N, width] or nullptr; tables that

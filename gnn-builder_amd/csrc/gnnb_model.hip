@@ -119,6 +119,28 @@ int count_gat_params(const gnnb_model_desc *desc, int heads, int edge_dim = 0)
     return (GAT_PARAM_SLOTS + (edge_dim ? 1 : 0)) * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
+// parameter tensors of a GAT v1 model (gnnb_gatconv.h): GATv2's conditions on the description and on heads; four tensors per layer
+int count_gatconv_params(const gnnb_model_desc *desc, int heads)
+{
+    int rc = validate_desc(desc);
+    if (rc != GNNB_OK)
+        return rc;
+    if (heads < 1 || heads > GAT_MAX_HEADS)
+        return fail(GNNB_ERR_INVALID, "heads %d: a GAT model takes 1 .. %d heads", heads, GAT_MAX_HEADS);
+    if (desc->conv_type != GNNB_CONV_GCN)
+        return fail(GNNB_ERR_INVALID, "a GAT model's description is a GCN description (conv_type %d given)", desc->conv_type);
+    if (desc->fpx_w != 0)
+        return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover GAT models (fpx_w must be 0)");
+    for (int l = 0; l < desc->num_layers; l++) {
+        const int fo = layer_dims(*desc, l).fout;
+        if (fo % heads != 0)
+            return fail(GNNB_ERR_INVALID, "layer %d's output width %d is not divisible by heads %d", l, fo, heads);
+        if (fo > GAT_MAX_WIDTH)
+            return fail(GNNB_ERR_INVALID, "layer %d's output width %d: a GAT layer is at most %d wide", l, fo, GAT_MAX_WIDTH);
+    }
+    return GAT1_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+}
+
 // parameter tensors of a TransformerConv model (gnnb_transformer.h): a GIN description (its tables keep explicit (v, v) edges) without
 // the fixed-point emulation, heads 1 .. 8 dividing every layer's output width, which is at most 256
 // (edge_dim != 0: with edge features, gnnb_transformer_edge.h -- lin_edge's weight is a ninth tensor per layer)
@@ -175,13 +197,14 @@ int count_resgated_params(const gnnb_model_desc *desc, int edge_dim = 0)
 // TransformerConv model (gnnb_transformer_model_create: a GIN description), or heads and edge_dim
 // (gnnb_transformer_edge_model_create: TransformerConv with edge features), or the "gated" mark of a ResGatedGraphConv model
 // (gnnb_resgated_model_create: a GIN description), or that mark and edge_dim (gnnb_resgated_edge_model_create: ResGatedGraphConv with
-// edge features)
+// edge features), or heads and negative_slope of a GAT v1 model (gnnb_gatconv_model_create: a GCN description)
 struct ModelKind {
     int edge_dim = 0, base = GNNB_CONV_GIN;
     int gat_heads = 0;
     float gat_slope = 0.0f;
     int tf_heads = 0;
     bool gated = false;
+    int gat1_heads = 0; // (its slope: gat_slope)
     static ModelKind plain() { return {}; }
     static ModelKind edges(int edge_dim, int base)
     {
@@ -199,6 +222,12 @@ struct ModelKind {
     {
         ModelKind k = gatv2(heads, slope);
         k.edge_dim = edge_dim, k.base = GNNB_CONV_GCN;
+        return k;
+    }
+    static ModelKind gatconv(int heads, float slope)
+    {
+        ModelKind k;
+        k.gat1_heads = heads, k.gat_slope = slope;
         return k;
     }
     static ModelKind transformer(int heads)
@@ -227,20 +256,22 @@ struct ModelKind {
     }
 };
 
-// the body of the nine *_model_create entries
+// the body of the ten *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
         return fail(GNNB_ERR_INVALID, "null out_model");
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
-    int expect = kind.gated       ? count_resgated_params(desc, edge_dim)
+    const int gat1_heads = kind.gat1_heads;
+    int expect = gat1_heads != 0  ? count_gatconv_params(desc, gat1_heads)
+                 : kind.gated     ? count_resgated_params(desc, edge_dim)
                  : tf_heads != 0  ? count_transformer_params(desc, tf_heads, edge_dim)
                  : gat_heads != 0 ? count_gat_params(desc, gat_heads, edge_dim)
                                   : count_params(desc, edge_dim, kind.base);
     if (expect < 0)
         return expect;
-    if (gat_heads != 0 && !std::isfinite(kind.gat_slope))
+    if ((gat_heads != 0 || gat1_heads != 0) && !std::isfinite(kind.gat_slope))
         return fail(GNNB_ERR_INVALID, "negative_slope must be finite");
     if (num_params != expect || !host_params)
         return fail(GNNB_ERR_INVALID, "expected %d parameter tensors, got %d", expect, num_params);
@@ -251,7 +282,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
         return fail(GNNB_ERR_NO_DEVICE, "no HIP device visible: the MI355X path cannot run");
 
     const gnnb_model_desc &d = *desc;
-    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated);
+    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated, gat1_heads);
     const std::vector<float> &img = built.img;
     const WeightLayout &lo = built.layout;
 
@@ -259,7 +290,8 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     m->desc = d;
     m->edge_dim = edge_dim;
     m->gat_heads = gat_heads;
-    m->gat_slope = gat_heads ? kind.gat_slope : 0.0f;
+    m->gat_slope = gat_heads || gat1_heads ? kind.gat_slope : 0.0f;
+    m->gat1_heads = gat1_heads;
     m->tf_heads = tf_heads;
     m->gated = kind.gated ? 1 : 0;
     (void)hipGetDevice(&m->device);
@@ -377,6 +409,20 @@ int gnnb_gat_edge_model_create(const gnnb_model_desc *desc, int heads, float neg
                                       "without)");
     return model_create(desc, ModelKind::gatv2_edges(heads, negative_slope, edge_dim), host_params, num_params, out_model);
 }
+
+int gnnb_gatconv_model_num_params(const gnnb_model_desc *desc, int heads) { return count_gatconv_params(desc, heads); }
+
+int gnnb_gatconv_model_create(const gnnb_model_desc *desc, int heads, float negative_slope, const float *const *host_params, int num_params,
+                              gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (heads == 0) // (ModelKind reads 0 as "no GAT model")
+        return fail(GNNB_ERR_INVALID, "heads 0: a GAT model takes 1 .. %d heads", GAT_MAX_HEADS);
+    return model_create(desc, ModelKind::gatconv(heads, negative_slope), host_params, num_params, out_model);
+}
+
+int gnnb_model_gatconv_heads(const gnnb_model *model) { return model ? model->gat1_heads : 0; }
 
 int gnnb_transformer_model_num_params(const gnnb_model_desc *desc, int heads) { return count_transformer_params(desc, heads); }
 

@@ -68,6 +68,14 @@ int refuse_gat_model(const gnnb_model *model, const gnnb_workspace *ws, const ch
     return GNNB_OK;
 }
 
+int refuse_gatconv_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use)
+{
+    if ((model && model->gat1_heads) || (ws && ws->gat1_heads))
+        return fail(GNNB_ERR_INVALID, "%s: a GAT model (gnnb_gatconv_model_create) runs layer by layer and is not served here: call %s "
+                                      "(gnnb_gatconv.h)", entry, use);
+    return GNNB_OK;
+}
+
 int refuse_transformer_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use)
 {
     if ((model && model->tf_heads) || (ws && ws->tf_heads))
@@ -167,6 +175,9 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     if (model->gat_heads) // a GATv2 layer's GEMM writes [xl | xr] [N, 2 out] into tmp0
         for (int l = 0; l < d.num_layers; l++)
             tmpw = std::max(tmpw, 2 * layer_dims(d, l).fout);
+    if (model->gat1_heads) // a GAT v1 layer's GEMM writes [xl | s_src | s_dst | pad] [N, out + roundup4(2 heads)] into tmp0
+        for (int l = 0; l < d.num_layers; l++)
+            tmpw = std::max(tmpw, layer_dims(d, l).fout + (int)gat_score_rows(model->gat1_heads));
     if (model->tf_heads) // a TransformerConv layer's GEMM writes [q | k | v | r] [N, 4 out] into tmp0
         for (int l = 0; l < d.num_layers; l++)
             tmpw = std::max(tmpw, 4 * layer_dims(d, l).fout + // (with edge features: [.. | qe], padded to whole 16-byte pieces)
@@ -185,8 +196,8 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     // (the stage-cut planner's tables: opt-in -- carved only for workspaces created while the option is on; a workspace created
     // without them keeps equal tile counts whatever the option says later: round-5 advisor finding)
     const bool want_plan = options().stage_cut && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 &&
-                           model->gat_heads == 0 && model->tf_heads == 0 && model->gated == 0; // (a GATv2 model, a TransformerConv model,
-                                                                          // a ResGatedGraphConv model take no stack kernel: no stage plan)
+                           model->gat_heads == 0 && model->gat1_heads == 0 && model->tf_heads == 0 && model->gated == 0; // (a GATv2 model,
+                                            // a GAT v1 model, a TransformerConv model, a ResGatedGraphConv model take no stack kernel: no stage plan)
     const int pooledw = d.num_pools * gnn_out_width(d);
     const int mlpw = std::max(d.mlp_hidden, d.mlp_out);
     const int min_tile_rows = 4;
@@ -197,6 +208,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     ws->edge_dim = model->edge_dim;
     ws->gat_heads = model->gat_heads;
     ws->gat_slope = model->gat_slope;
+    ws->gat1_heads = model->gat1_heads;
     ws->tf_heads = model->tf_heads;
     ws->gated = model->gated;
     ws->max_graphs = max_graphs;
@@ -358,10 +370,10 @@ int gnnb_workspace_set_max_degree(gnnb_workspace *ws, int d)
 static bool stack_promised(const gnnb_workspace *ws)
 {
     const gnnb_model_desc &d = ws->desc;
-    // (a GINE model's workspace, a GATv2 model's, a TransformerConv model's, a ResGatedGraphConv model's: never -- their layers take
-    // no stack kernel, whatever the promise)
+    // (a GINE model's workspace, a GATv2 model's, a GAT v1 model's, a TransformerConv model's, a ResGatedGraphConv model's: never --
+    // their layers take no stack kernel, whatever the promise)
     return options().fuse_gcn2 && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 && ws->max_graph_nodes > 0 &&
-           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->tf_heads == 0 && ws->gated == 0;
+           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->gat1_heads == 0 && ws->tf_heads == 0 && ws->gated == 0;
 }
 
 // ... and the WHOLE batch is expected there: no large segment, no fixed-point emulation.  Such a batch needs neither the
@@ -400,11 +412,11 @@ static bool wants_degree_classes(const gnnb_workspace *ws)
 static bool may_plan_stage_cuts(const gnnb_workspace *ws) { return options().stage_cut && ws->plan_scratch; }
 
 // GCN: the coefficient table is produced behind the tables unless the whole batch is expected on the stack kernels
-// (a GATv2 workspace is a GCN description whose layers never read the table: not produced there; gnnb_aggregate(GNNB_AGG_GCN) as a
-// stage entry on such a workspace produces it lazily, ensure_gcoef)
+// (a GATv2 or GAT v1 workspace is a GCN description whose layers never read the table: not produced there; gnnb_aggregate(GNNB_AGG_GCN)
+// as a stage entry on such a workspace produces it lazily, ensure_gcoef)
 static bool wants_gcoef_at_prep(const gnnb_workspace *ws)
 {
-    return ws->desc.conv_type == GNNB_CONV_GCN && ws->gat_heads == 0 && !stack_expected(ws);
+    return ws->desc.conv_type == GNNB_CONV_GCN && ws->gat_heads == 0 && ws->gat1_heads == 0 && !stack_expected(ws);
 }
 
 // Can this workspace's graph prep run as a guest of the forward's readout kernel (k_head_small's extra workgroups)?  The molecule
@@ -754,6 +766,25 @@ int gnnb_aggregate_gatv2(gnnb_workspace *ws, const float *xl_dev, int ldl, const
                                       "gnnb_act, a finite negative_slope)", GAT_MAX_HEADS, GAT_MAX_WIDTH);
     GNNB_HIP_TRY(launch_gatv2_aggregate(ws->t, xl_dev, ldl, xr_dev, ldr, att_dev, bias_dev, skip_dev, act, heads, negative_slope, out_dev, width,
                                         (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_gat(gnnb_workspace *ws, const float *xl_dev, int ldl, const float *ssrc_dev, int lds, const float *sdst_dev, int ldd,
+                       const float *bias_dev, const float *skip_dev, int act, int heads, float negative_slope, float *out_dev, int width,
+                       void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gat needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type != GNNB_CONV_GCN) // (only there are the tables free of (v, v) edges: the kernel adds the self term)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gat takes the prepared batch of a GCN workspace (or a GAT model's): graph prep drops "
+                                      "explicit self loops there, the kernel adds the one self term");
+    if (!xl_dev || !ssrc_dev || !sdst_dev || !out_dev || heads < 1 || heads > GAT_MAX_HEADS || width < 1 || width > GAT_MAX_WIDTH ||
+        width % heads != 0 || ldl < width || lds < heads || ldd < heads || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE ||
+        !std::isfinite(negative_slope))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gat (heads 1 .. %d dividing width 1 .. %d, ldl >= width, lds and ldd >= "
+                                      "heads, a gnnb_act, a finite negative_slope)", GAT_MAX_HEADS, GAT_MAX_WIDTH);
+    GNNB_HIP_TRY(launch_gat_aggregate(ws->t, xl_dev, ldl, ssrc_dev, lds, sdst_dev, ldd, bias_dev, skip_dev, act, heads, negative_slope, out_dev,
+                                      width, (hipStream_t)stream));
     return GNNB_OK;
 }
 

@@ -93,6 +93,13 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //   GATv2 + edges  (gat_heads > 0 and edge_dim > 0, gnnb_gat_edge_model_create) GATv2's slots, and
 //              w_edge [out, edge_dim]               canonical 6: conv.lin_edge.weight (no bias), raw -- what k_gatv2_edge_aggregate
 //                                                   projects the edge attributes with, inside the score
+//   GAT v1     (gnnb_model::gat1_heads > 0, gnnb_gatconv_model_create: a GCN description) none of GCN's slots, but
+//              w_gat [out + roundup4(2 heads), in]  derived: [W ; A_src W ; A_dst W ; 0], canonical 0 (conv.lin.weight, no bias) on top
+//                                                   of the folded score rows (gat_score_fold): row out + h = sum_c att_src[h, c] W[h C + c],
+//                                                   row out + heads + h likewise with att_dst (canonical 1, 2: conv.att_src, conv.att_dst
+//                                                   [1, heads, out / heads]); zero rows up to a multiple of 4 -- ONE GEMM gives
+//                                                   [xl | s_src | s_dst | pad].  No GEMM bias
+//              gat_bias [out]                       canonical 3: conv.bias, added behind the aggregate
 //   TransformerConv  (gnnb_model::tf_heads > 0, gnnb_transformer_model_create: a GIN description) none of GIN's slots, but
 //              w_qkvr [4 out, in]                   derived: [W_q ; W_k ; W_v ; W_skip], canonical 2 (conv.lin_query.weight), 0
 //                                                   (conv.lin_key.weight), 4 (conv.lin_value.weight), 6 (conv.lin_skip.weight) on top
@@ -126,6 +133,7 @@ template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
     T edge_w = absent_slot<T>(), edge_b = absent_slot<T>();
     T w_lr = absent_slot<T>(), b_lr = absent_slot<T>(), att = absent_slot<T>(), gat_bias = absent_slot<T>(), w_edge = absent_slot<T>();
+    T w_gat = absent_slot<T>();
     T w_qkvr = absent_slot<T>(), b_qkvr = absent_slot<T>();
     T w_qkvre = absent_slot<T>(), b_qkvre = absent_slot<T>();
     T w_kqvr = absent_slot<T>(), b_kqvr = absent_slot<T>(), w_gv_edge = absent_slot<T>();
@@ -137,7 +145,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -399,6 +407,34 @@ inline WeightBias transformer_edge_fold(const float *w_q, const float *b_q, cons
     return f;
 }
 
+// GAT v1: both per-node scores as linear functions of x.  s_src_j[h] = sum_c att_src[h, c] (W x_j)[h C + c] = (A_src W x_j)[h], so
+//   w[fo + h][:] = sum_c att_src[h C + c] * W[h C + c][:],   w[fo + heads + h][:] = sum_c att_dst[h C + c] * W[h C + c][:]
+// (C = fo / heads; accumulated in double, c increasing, rounded once -- as resgated_edge_blocks and transformer_edge_fold) under W's
+// own fo rows, copied, and padded with zero rows to a multiple of 4 score rows: [fo + gat_score_rows(heads), fi].  w [fo, fi],
+// att_src / att_dst [fo] head-major
+inline size_t gat_score_rows(size_t heads) { return (2 * heads + 3) / 4 * 4; }
+inline std::vector<float> gat_score_fold(const float *w, const float *att_src, const float *att_dst, size_t fi, size_t fo, size_t heads)
+{
+    const size_t C = fo / heads;
+    std::vector<float> f((fo + gat_score_rows(heads)) * fi, 0.0f);
+    memcpy(f.data(), w, fo * fi * sizeof(float));
+    std::vector<double> acc(fi);
+    for (size_t side = 0; side < 2; side++)
+        for (size_t h = 0; h < heads; h++) {
+            const float *att = side ? att_dst : att_src;
+            std::fill(acc.begin(), acc.end(), 0.0);
+            for (size_t c = 0; c < C; c++) {
+                const double a = (double)att[h * C + c];
+                const float *wr = w + (h * C + c) * fi;
+                for (size_t k = 0; k < fi; k++)
+                    acc[k] += a * (double)wr[k];
+            }
+            for (size_t k = 0; k < fi; k++)
+                f[(fo + side * heads + h) * fi + k] = (float)acc[k];
+        }
+    return f;
+}
+
 // ResGatedGraphConv with edge features: a linear's [fo, fi + edge_dim] weight (x columns first) split.  x_cols: its [fo, fi] block
 inline std::vector<float> resgated_x_cols(const float *w, size_t fi, size_t fo, size_t edge_dim)
 {
@@ -425,15 +461,22 @@ constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_ga
 constexpr int TF_PARAM_SLOTS = 8;  // a TransformerConv layer's canonical tensors (gnnb_transformer.h); one more with edge features
                                    // (gnnb_transformer_edge.h)
 constexpr int RG_PARAM_SLOTS = 8;  // a ResGatedGraphConv layer's canonical tensors (gnnb_resgated.h)
+constexpr int GAT1_PARAM_SLOTS = 4; // a GAT v1 layer's canonical tensors (gnnb_gatconv.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
 // their offsets in the image
 inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0,
-                                    int tf_heads = 0, bool gated = false)
+                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (gat1_heads > 0) { // (a GCN description whose layers are GAT v1's; canonical order: lin.weight, att_src, att_dst, bias)
+        LayerOffsets g;
+        g.w_gat = im.push(gat_score_fold(p[0], p[1], p[2], fi, fo, (size_t)gat1_heads));
+        g.gat_bias = im.push(p[3], fo);
+        return g;
+    }
     if (gated) { // (a GIN description whose layers are ResGatedGraphConv's; canonical order: key, query, value, skip weight, conv.bias)
         LayerOffsets g;
         if (edge_dim > 0) { // (... with edge features, gnnb_resgated_edge.h: the same eight, key / query / value [fo, fi + edge_dim])
@@ -541,21 +584,23 @@ struct BuiltWeights {
 // tf_heads > 0: a TransformerConv model (a GIN description, eight tensors per layer; no execution-order copy -- no stack kernel);
 // with edge_dim > 0 besides, TransformerConv with edge features (nine tensors per layer).  gated: a ResGatedGraphConv model (a GIN
 // description, eight tensors per layer; no execution-order copy either); with edge_dim > 0 besides, ResGatedGraphConv with edge
-// features (the same eight, three of them [out, in + edge_dim]).
+// features (the same eight, three of them [out, in + edge_dim]).  gat1_heads > 0: a GAT v1 model (a GCN description, four tensors
+// per layer; no fragment copy -- it takes no stack kernel).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
-                                       int tf_heads = 0, bool gated = false)
+                                       int tf_heads = 0, bool gated = false, int gat1_heads = 0)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = gated           ? RG_PARAM_SLOTS
+    const int slots = gat1_heads > 0  ? GAT1_PARAM_SLOTS
+                      : gated         ? RG_PARAM_SLOTS
                       : tf_heads > 0  ? TF_PARAM_SLOTS + (edge_dim ? 1 : 0)
                       : gat_heads > 0 ? GAT_PARAM_SLOTS + (edge_dim ? 1 : 0)
                                       : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;
     for (int l = 0; l < d.num_layers; l++, pi += slots)
-        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated);
-    const bool have_w1f = gat_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads);
+    const bool have_w1f = gat_heads == 0 && gat1_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));
     // (a GINE model, a TransformerConv model, a ResGatedGraphConv model take no stack kernel: no execution-order copy)

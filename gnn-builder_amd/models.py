@@ -331,7 +331,8 @@ class GINEConv_GNNB(nn.Module):
 class GATConv_GNNB(nn.Module):
     """Listed by the reference's SUPPORTED_GNN_CONVS but it has no native kernel for it
     (gnn_builder_lib.h:2343 ``// TODO: GAT layer``; template TODO model.cpp.jinja:141-142);
-    out of scope here as well.  Attention models run as ``GATv2Conv_GNNB`` below (``GATv2EConv_GNNB`` with edge features)."""
+    out of scope here as well.  Attention models run as ``GATv2Conv_GNNB`` below (``GATv2EConv_GNNB`` with edge features);
+    PyG's ``GATConv`` itself runs as ``GATv1Conv_GNNB``.  This stub keeps the reference's behaviour."""
 
     def __init__(self, *args, **kwargs):
         super().__init__()
@@ -417,6 +418,81 @@ class GATv2Conv_GNNB(nn.Module):
 
     def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
         return self.conv(x, edge_index)
+
+
+# --------------------------------------------------------------------------------------- GAT (v1)
+class _GATConv(nn.Module):
+    """PyG's ``GATConv(in_channels, out_channels, heads, concat=True, negative_slope, add_self_loops=True, bias=True,
+    edge_dim=None, dropout=0, residual=False)`` with ``out_channels`` PER HEAD, as PyG counts it::
+
+        x' = lin(x) [N, H, C]
+        s_ij[h] = leaky_relu(sum_c att_src[h, c] * x'_j[h, c] + sum_c att_dst[h, c] * x'_i[h, c])     for j in N(i) u {i}
+        a_ij[h] = exp(s_ij[h] - max_j s_ij[h]) / (sum_j exp(s_ij[h] - max_j s_ij[h]) + 1e-16)
+        out_i[h, :] = sum_j a_ij[h] * x'_j[h, :]  + bias
+
+    Self loops are PyG's, as ``_GATv2Conv`` has them: explicit ``(v, v)`` edges are removed, then one is added per node.
+    Parameters: ``lin.weight`` [H C, in] (no bias), ``att_src`` [1, H, C], ``att_dst`` [1, H, C], ``bias`` [H C]; the weight and
+    both ``att`` glorot, the bias zero."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, negative_slope: float = 0.2):
+        super().__init__()
+        self.heads = heads
+        self.out_channels = out_channels
+        self.negative_slope = negative_slope
+        self.lin = nn.Linear(in_channels, heads * out_channels, bias=False)
+        self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.att_dst = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.bias = nn.Parameter(torch.zeros(heads * out_channels))
+        _glorot(self.lin.weight)
+        _glorot(self.att_src)
+        _glorot(self.att_dst)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        n, H, C = x.size(0), self.heads, self.out_channels
+        if edge_index.numel():
+            edge_index = edge_index[:, edge_index[0] != edge_index[1]]
+        loops = torch.arange(n, dtype=torch.long, device=x.device)
+        src = torch.cat([edge_index[0].long(), loops]) if edge_index.numel() else loops
+        dst = torch.cat([edge_index[1].long(), loops]) if edge_index.numel() else loops
+        xl = self.lin(x).view(n, H, C)
+        s_src = (xl * self.att_src).sum(dim=-1)  # [N, H]
+        s_dst = (xl * self.att_dst).sum(dim=-1)
+        s = nn.functional.leaky_relu(s_src[src] + s_dst[dst], self.negative_slope)  # [E + N, H]
+        idx = dst.unsqueeze(-1).expand(-1, H)
+        smax = s.new_full((n, H), float("-inf")).scatter_reduce(0, idx, s, reduce="amax", include_self=True)
+        e = (s - smax[dst]).exp()
+        a = e / (s.new_zeros(n, H).index_add(0, dst, e)[dst] + 1e-16)
+        out = x.new_zeros(n, H, C).index_add(0, dst, a.unsqueeze(-1) * xl[src])
+        return out.reshape(n, H * C) + self.bias
+
+
+class GATv1Conv_GNNB(nn.Module):
+    """GAT as PyG's ``GATConv`` computes it (the reference's ``GATConv_GNNB`` is a stub and stays one): ``out_channels`` is the
+    layer's WHOLE output width, split over ``heads`` (1 .. 8, dividing it) and concatenated -- PyG's ``GATConv(in_channels,
+    out_channels // heads, heads=heads)``.  ``GNNModel(..., gnn_conv=GATv1Conv_GNNB, gnn_heads=H)`` stacks it;
+    ``forward(x, edge_index)``.  The accelerated path is ``runtime.CompiledModel.from_model`` with the ordinary ``forward`` /
+    ``forward_pyg`` (C ABI ``include/gnnb_gatconv.h``: one GEMM, which also gives both per-node scores, and one launch of
+    csrc/k_gat.hip per layer).  This class ignores ``graph_input_edge_dim`` and ``edge_attr``.  ``Project`` does not generate such
+    designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, negative_slope: float = 0.2, p_in: int = 1,
+                 p_out: int = 1):
+        super().__init__()
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
+            raise ValueError(f"heads must be an int in 1 .. {MAX_GAT_HEADS} (got {heads!r})")
+        if out_channels % heads != 0:
+            raise ValueError(f"out_channels ({out_channels}) must be divisible by heads ({heads})")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.heads = heads
+        self.negative_slope = float(negative_slope)
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _GATConv(in_channels, out_channels // heads, heads, self.negative_slope)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        return self.conv(x, edge_index)
+
 
 class _GATv2EConv(_GATv2Conv):
     """``_GATv2Conv`` with edge features: PyG's ``GATv2Conv(..., edge_dim=d, fill_value='mean')``.  The edge term enters the score
@@ -843,17 +919,19 @@ class MLP(nn.Module):
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
                        GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB,
-                       ResGatedGraphEConv_GNNB]
+                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
               PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
-              TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated", ResGatedGraphEConv_GNNB: "resgatede"}
+              TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated", ResGatedGraphEConv_GNNB: "resgatede",
+              GATv1Conv_GNNB: "gat"}
 # convs that take edge_attr, and what the messages call them
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE",
                ResGatedGraphEConv_GNNB: "ResGatedE"}
 MAX_EDGE_DIM = 16  # of a GINE, PNAE, GATv2E, TransformerE or ResGatedE model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h, gnnb_transformer_edge.h, gnnb_resgated_edge.h)
 _GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # the GATv2 convs (heads and negative_slope travel beside a GCN description)
 _TF_CONVS = (TransformerConv_GNNB, TransformerEConv_GNNB)  # the TransformerConv convs (heads travel beside a GIN description)
-_HEAD_CONVS = _GAT_CONVS + _TF_CONVS  # convs with attention heads: the ones that take gnn_heads
+_GAT1_CONVS = (GATv1Conv_GNNB,)  # PyG's GATConv (heads and negative_slope travel beside a GCN description: include/gnnb_gatconv.h)
+_HEAD_CONVS = _GAT_CONVS + _TF_CONVS + _GAT1_CONVS  # convs with attention heads: the ones that take gnn_heads
 
 
 class GNNModel(nn.Module):
@@ -891,7 +969,7 @@ class GNNModel(nn.Module):
         self.gnn_heads = gnn_heads
         if self.gnn_conv in _HEAD_CONVS:
             if not isinstance(gnn_heads, int) or isinstance(gnn_heads, bool) or not 1 <= gnn_heads <= MAX_GAT_HEADS:
-                kind = "TransformerConv" if self.gnn_conv in _TF_CONVS else "GATv2"
+                kind = "TransformerConv" if self.gnn_conv in _TF_CONVS else "GAT" if self.gnn_conv in _GAT1_CONVS else "GATv2"
                 raise ValueError(f"a {kind} model needs gnn_heads, an int in 1 .. {MAX_GAT_HEADS} (got {gnn_heads!r})")
             widths = [gnn_output_dim] if gnn_num_layers <= 1 else [gnn_hidden_dim, gnn_output_dim]
             if gnn_num_layers >= 1 and any(w % gnn_heads for w in widths):
@@ -1019,7 +1097,7 @@ class GNNModel(nn.Module):
                                           "(nn.Softmax and nn.LogSoftmax do)")
         conv0 = self.gnn_convs[0] if len(self.gnn_convs) else None
         gat = {}
-        if self.gnn_conv in _GAT_CONVS:  # (a GCN description on the C side; these two travel beside it: include/gnnb_gat.h)
+        if self.gnn_conv in _GAT_CONVS + _GAT1_CONVS:  # (a GCN description on the C side; these two travel beside it: include/gnnb_gat.h, gnnb_gatconv.h)
             gat = {"heads": int(self.gnn_heads), "negative_slope": float(conv0.negative_slope) if conv0 is not None else 0.2}
         elif self.gnn_conv in _TF_CONVS:  # (a GIN description on the C side, heads beside it: include/gnnb_transformer.h, _edge.h)
             gat = {"heads": int(self.gnn_heads)}
@@ -1067,6 +1145,7 @@ class GNNModel(nn.Module):
         per_conv["resgated"] = [f"conv_lin_{n}_{t}" for n in ("key", "query", "value") for t in ("weight", "bias")] + [
             "conv_lin_skip_weight", "conv_bias"]
         per_conv["resgatede"] = per_conv["resgated"]  # (the same eight; key, query and value weights are [out, in + edge_dim])
+        per_conv["gat"] = ["conv_lin_weight", "conv_att_src", "conv_att_dst", "conv_bias"]  # (include/gnnb_gatconv.h)
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):
