@@ -248,7 +248,12 @@ static int gat1_layer(const LayerCtx &c)
     int rc;
     if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_gat, fi, nullptr, nullptr, c.rows(xs, ld), ld, GNNB_ACT_NONE)))
         return rc;
-    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+    if (c.M > 0 && c.model->edge_dim) // with edge features (gnnb_gatconv_edge.h): the same GEMM; the batch's edge attributes enter the
+                                      // score through the layer's folded a_edge [heads, roundup4(edge_dim)], d FMAs per (edge, head)
+        GNNB_HIP_TRY(launch_gat_edge_aggregate(c.tv, xs, ld, xs + fo, ld, xs + fo + heads, ld, p.gat_bias, c.skip, d.activation, heads,
+                                               c.model->gat_slope, c.edge_attr, c.model->edge_dim, p.a_edge,
+                                               (int)gat_edge_cols(c.model->edge_dim), c.nxt, fo, c.hs()));
+    else if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
         GNNB_HIP_TRY(launch_gat_aggregate(c.tv, xs, ld, xs + fo, ld, xs + fo + heads, ld, p.gat_bias, c.skip, d.activation, heads,
                                           c.model->gat_slope, c.nxt, fo, c.hs()));
     return GNNB_OK;

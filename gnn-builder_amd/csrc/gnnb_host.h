@@ -15,6 +15,7 @@
 #include "gnnb_gat.h"
 #include "gnnb_gat_edge.h"
 #include "gnnb_gatconv.h"
+#include "gnnb_gatconv_edge.h"
 #include "gnnb_transformer.h"
 #include "gnnb_transformer_edge.h"
 #include "gnnb_resgated.h"
@@ -54,7 +55,9 @@ struct gnnb_model {
                             // with edge_dim > 0 besides: GATv2 with edge features (gnnb_gat_edge_model_create) -- and w_edge [out, edge_dim]
     float gat_slope = 0.0f; // ... and its leaky_relu slope (a GAT v1 model's as well)
     int gat1_heads = 0;     // > 0: a GAT v1 model (gnnb_gatconv_model_create; desc is a GCN description) -- every layer has w_gat and
-                            // gat_bias and none of GCN's slots.  Its own field: gnnb_model_gat_heads stays 0 for such a model
+                            // gat_bias and none of GCN's slots.  Its own field: gnnb_model_gat_heads stays 0 for such a model;
+                            // with edge_dim > 0 besides: GAT v1 with edge features (gnnb_gatconv_edge_model_create) -- and a_edge
+                            // [heads, roundup4(edge_dim)]
     int tf_heads = 0;       // > 0: a TransformerConv model (gnnb_transformer_model_create; desc is a GIN description) -- every layer has
                             // w_qkvr, b_qkvr and none of GIN's slots.  Its own field: gnnb_model_gat_heads stays 0 for such a model;
                             // with edge_dim > 0 besides: TransformerConv with edge features (gnnb_transformer_edge_model_create) --

@@ -329,6 +329,12 @@ hipError_t launch_gatv2_edge_aggregate(const BatchTables &t, const float *xl, in
 // nothing launched
 hipError_t launch_gat_aggregate(const BatchTables &t, const float *xl, int ldl, const float *ssrc, int lds, const float *sdst, int ldd,
                                 const float *bias, const float *skip, int act, int heads, float slope, float *out, int width, hipStream_t s);
+// GAT v1 with edge features (k_gat_edge.hip): the same with s_ij[h] = leaky_relu(ssrc_j[h] + sdst_i[h] + ae[h] . e_ij), the self term
+// last with the mean of the row's edge terms; edge_attr [E, edge_dim] in COO row order (may be nullptr when the batch has no edges),
+// ae [heads, edge_dim] at row stride ldae >= edge_dim (att_edge folded into lin_edge), edge_dim 1 .. 16; the tables' eid
+hipError_t launch_gat_edge_aggregate(const BatchTables &t, const float *xl, int ldl, const float *ssrc, int lds, const float *sdst, int ldd,
+                                     const float *bias, const float *skip, int act, int heads, float slope, const float *edge_attr, int edge_dim,
+                                     const float *ae, int ldae, float *out, int width, hipStream_t s);
 // TransformerConv (k_transformer.hip): out [N, width] = act((sum_j softmax_j(s_ij) v_j + root_i) + skip_i) over j in N(i) as the tables
 // hold it, per head of width / heads columns, s_ij = (q_i . k_j) * scale; q / k / v / root: rows of stride ldq / ldk / ldv / ldr >=
 // width (the column blocks of one GEMM output), root [N, width] or nullptr (ldr ignored), skip [N, width] or nullptr; tables that

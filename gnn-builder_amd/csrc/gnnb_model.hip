@@ -120,13 +120,16 @@ int count_gat_params(const gnnb_model_desc *desc, int heads, int edge_dim = 0)
 }
 
 // parameter tensors of a GAT v1 model (gnnb_gatconv.h): GATv2's conditions on the description and on heads; four tensors per layer
-int count_gatconv_params(const gnnb_model_desc *desc, int heads)
+// (edge_dim != 0: with edge features, gnnb_gatconv_edge.h, 1 .. 16 -- att_edge and lin_edge's weight are two more per layer)
+int count_gatconv_params(const gnnb_model_desc *desc, int heads, int edge_dim = 0)
 {
     int rc = validate_desc(desc);
     if (rc != GNNB_OK)
         return rc;
     if (heads < 1 || heads > GAT_MAX_HEADS)
         return fail(GNNB_ERR_INVALID, "heads %d: a GAT model takes 1 .. %d heads", heads, GAT_MAX_HEADS);
+    if (edge_dim != 0 && (edge_dim < 1 || edge_dim > 16))
+        return fail(GNNB_ERR_INVALID, "edge_dim %d: a GAT model with edge features takes 1 .. 16 edge attributes", edge_dim);
     if (desc->conv_type != GNNB_CONV_GCN)
         return fail(GNNB_ERR_INVALID, "a GAT model's description is a GCN description (conv_type %d given)", desc->conv_type);
     if (desc->fpx_w != 0)
@@ -138,7 +141,7 @@ int count_gatconv_params(const gnnb_model_desc *desc, int heads)
         if (fo > GAT_MAX_WIDTH)
             return fail(GNNB_ERR_INVALID, "layer %d's output width %d: a GAT layer is at most %d wide", l, fo, GAT_MAX_WIDTH);
     }
-    return GAT1_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+    return (GAT1_PARAM_SLOTS + (edge_dim ? 2 : 0)) * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
 // parameter tensors of a TransformerConv model (gnnb_transformer.h): a GIN description (its tables keep explicit (v, v) edges) without
@@ -230,6 +233,12 @@ struct ModelKind {
         k.gat1_heads = heads, k.gat_slope = slope;
         return k;
     }
+    static ModelKind gatconv_edges(int heads, float slope, int edge_dim)
+    {
+        ModelKind k = gatconv(heads, slope);
+        k.edge_dim = edge_dim, k.base = GNNB_CONV_GCN;
+        return k;
+    }
     static ModelKind transformer(int heads)
     {
         ModelKind k;
@@ -256,7 +265,7 @@ struct ModelKind {
     }
 };
 
-// the body of the ten *_model_create entries
+// the body of the eleven *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
@@ -264,7 +273,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
     const int gat1_heads = kind.gat1_heads;
-    int expect = gat1_heads != 0  ? count_gatconv_params(desc, gat1_heads)
+    int expect = gat1_heads != 0  ? count_gatconv_params(desc, gat1_heads, edge_dim)
                  : kind.gated     ? count_resgated_params(desc, edge_dim)
                  : tf_heads != 0  ? count_transformer_params(desc, tf_heads, edge_dim)
                  : gat_heads != 0 ? count_gat_params(desc, gat_heads, edge_dim)
@@ -423,6 +432,27 @@ int gnnb_gatconv_model_create(const gnnb_model_desc *desc, int heads, float nega
 }
 
 int gnnb_model_gatconv_heads(const gnnb_model *model) { return model ? model->gat1_heads : 0; }
+
+int gnnb_gatconv_edge_model_num_params(const gnnb_model_desc *desc, int heads, int edge_dim)
+{
+    if (edge_dim == 0)
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a GAT model with edge features takes 1 .. 16 edge attributes (gnnb_gatconv_model_num_params: "
+                                      "models without)");
+    return count_gatconv_params(desc, heads, edge_dim);
+}
+
+int gnnb_gatconv_edge_model_create(const gnnb_model_desc *desc, int heads, float negative_slope, int edge_dim, const float *const *host_params,
+                                   int num_params, gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (heads == 0) // (ModelKind reads 0 as "no GAT model")
+        return fail(GNNB_ERR_INVALID, "heads 0: a GAT model takes 1 .. %d heads", GAT_MAX_HEADS);
+    if (edge_dim == 0)
+        return fail(GNNB_ERR_INVALID, "edge_dim 0: a GAT model with edge features takes 1 .. 16 edge attributes (gnnb_gatconv_model_create: "
+                                      "models without)");
+    return model_create(desc, ModelKind::gatconv_edges(heads, negative_slope, edge_dim), host_params, num_params, out_model);
+}
 
 int gnnb_transformer_model_num_params(const gnnb_model_desc *desc, int heads) { return count_transformer_params(desc, heads); }
 

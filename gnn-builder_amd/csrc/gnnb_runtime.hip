@@ -788,6 +788,28 @@ int gnnb_aggregate_gat(gnnb_workspace *ws, const float *xl_dev, int ldl, const f
     return GNNB_OK;
 }
 
+int gnnb_aggregate_gat_edges(gnnb_workspace *ws, const float *xl_dev, int ldl, const float *ssrc_dev, int lds, const float *sdst_dev, int ldd,
+                             const float *bias_dev, const float *skip_dev, int act, int heads, float negative_slope, const float *edge_attr_dev,
+                             int edge_dim, const float *ae_dev, int ldae, float *out_dev, int width, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gat_edges needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type != GNNB_CONV_GCN) // (only there are the tables free of (v, v) edges: the kernel adds the self term)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gat_edges takes the prepared batch of a GCN workspace (or a GAT model's): graph prep drops "
+                                      "explicit self loops there, the kernel adds the one self term");
+    if (!xl_dev || !ssrc_dev || !sdst_dev || !out_dev || heads < 1 || heads > GAT_MAX_HEADS || width < 1 || width > GAT_MAX_WIDTH ||
+        width % heads != 0 || ldl < width || lds < heads || ldd < heads || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE ||
+        !std::isfinite(negative_slope))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gat_edges (heads 1 .. %d dividing width 1 .. %d, ldl >= width, lds and "
+                                      "ldd >= heads, a gnnb_act, a finite negative_slope)", GAT_MAX_HEADS, GAT_MAX_WIDTH);
+    if (!ae_dev || edge_dim < 1 || edge_dim > 16 || ldae < edge_dim || (ws->t.num_edges > 0 && !edge_attr_dev))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gat_edges (ae, edge_dim 1 .. 16, ldae >= edge_dim, edge_attr for a batch "
+                                      "with edges)");
+    GNNB_HIP_TRY(launch_gat_edge_aggregate(ws->t, xl_dev, ldl, ssrc_dev, lds, sdst_dev, ldd, bias_dev, skip_dev, act, heads, negative_slope,
+                                           edge_attr_dev, edge_dim, ae_dev, ldae, out_dev, width, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
 int gnnb_aggregate_gatv2_edges(gnnb_workspace *ws, const float *xl_dev, int ldl, const float *xr_dev, int ldr, const float *att_dev,
                                const float *bias_dev, const float *skip_dev, int act, int heads, float negative_slope, const float *edge_attr_dev,
                                int edge_dim, const float *we_dev, int ldwe, float *out_dev, int width, void *stream)

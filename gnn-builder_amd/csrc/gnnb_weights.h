@@ -100,6 +100,12 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //                                                   [1, heads, out / heads]); zero rows up to a multiple of 4 -- ONE GEMM gives
 //                                                   [xl | s_src | s_dst | pad].  No GEMM bias
 //              gat_bias [out]                       canonical 3: conv.bias, added behind the aggregate
+//   GAT v1 + edges  (gat1_heads > 0 and edge_dim > 0, gnnb_gatconv_edge_model_create) GAT v1's slots -- w_gat is exactly the plain
+//              model's, so the GEMM is unchanged -- and
+//              a_edge [heads, roundup4(edge_dim)]   derived: row h = sum_c att_edge[h, c] W_e[h C + c, :] (gat_edge_fold), canonical 4
+//                                                   (conv.att_edge [1, heads, out / heads]) folded into canonical 5
+//                                                   (conv.lin_edge.weight [out, edge_dim], no bias); zero columns up to a multiple
+//                                                   of 4 -- what k_gat_edge_aggregate forms an edge's score term with
 //   TransformerConv  (gnnb_model::tf_heads > 0, gnnb_transformer_model_create: a GIN description) none of GIN's slots, but
 //              w_qkvr [4 out, in]                   derived: [W_q ; W_k ; W_v ; W_skip], canonical 2 (conv.lin_query.weight), 0
 //                                                   (conv.lin_key.weight), 4 (conv.lin_value.weight), 6 (conv.lin_skip.weight) on top
@@ -133,7 +139,7 @@ template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
     T edge_w = absent_slot<T>(), edge_b = absent_slot<T>();
     T w_lr = absent_slot<T>(), b_lr = absent_slot<T>(), att = absent_slot<T>(), gat_bias = absent_slot<T>(), w_edge = absent_slot<T>();
-    T w_gat = absent_slot<T>();
+    T w_gat = absent_slot<T>(), a_edge = absent_slot<T>();
     T w_qkvr = absent_slot<T>(), b_qkvr = absent_slot<T>();
     T w_qkvre = absent_slot<T>(), b_qkvre = absent_slot<T>();
     T w_kqvr = absent_slot<T>(), b_kqvr = absent_slot<T>(), w_gv_edge = absent_slot<T>();
@@ -145,7 +151,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -435,6 +441,31 @@ inline std::vector<float> gat_score_fold(const float *w, const float *att_src, c
     return f;
 }
 
+// GAT v1 with edge features: the edge term of the score as a linear function of the edge attribute.  a_edge[h] . (W_e e)[h C ..] =
+// (A_edge W_e)[h, :] . e, so
+//   f[h][:] = sum_c att_edge[h C + c] * W_e[h C + c][:]
+// (accumulated in double, c increasing, rounded once -- as gat_score_fold) at row stride gat_edge_cols(edge_dim), the pad columns
+// zero: [heads, roundup4(edge_dim)].  w_edge [fo, edge_dim], att_edge [fo] head-major
+inline size_t gat_edge_cols(size_t edge_dim) { return (edge_dim + 3) / 4 * 4; }
+inline std::vector<float> gat_edge_fold(const float *w_edge, const float *att_edge, size_t edge_dim, size_t fo, size_t heads)
+{
+    const size_t C = fo / heads, ld = gat_edge_cols(edge_dim);
+    std::vector<float> f(heads * ld, 0.0f);
+    std::vector<double> acc(edge_dim);
+    for (size_t h = 0; h < heads; h++) {
+        std::fill(acc.begin(), acc.end(), 0.0);
+        for (size_t c = 0; c < C; c++) {
+            const double a = (double)att_edge[h * C + c];
+            const float *wr = w_edge + (h * C + c) * edge_dim;
+            for (size_t k = 0; k < edge_dim; k++)
+                acc[k] += a * (double)wr[k];
+        }
+        for (size_t k = 0; k < edge_dim; k++)
+            f[h * ld + k] = (float)acc[k];
+    }
+    return f;
+}
+
 // ResGatedGraphConv with edge features: a linear's [fo, fi + edge_dim] weight (x columns first) split.  x_cols: its [fo, fi] block
 inline std::vector<float> resgated_x_cols(const float *w, size_t fi, size_t fo, size_t edge_dim)
 {
@@ -461,7 +492,7 @@ constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_ga
 constexpr int TF_PARAM_SLOTS = 8;  // a TransformerConv layer's canonical tensors (gnnb_transformer.h); one more with edge features
                                    // (gnnb_transformer_edge.h)
 constexpr int RG_PARAM_SLOTS = 8;  // a ResGatedGraphConv layer's canonical tensors (gnnb_resgated.h)
-constexpr int GAT1_PARAM_SLOTS = 4; // a GAT v1 layer's canonical tensors (gnnb_gatconv.h)
+constexpr int GAT1_PARAM_SLOTS = 4; // a GAT v1 layer's canonical tensors (gnnb_gatconv.h); two more with edge features (gnnb_gatconv_edge.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
@@ -475,6 +506,8 @@ inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, i
         LayerOffsets g;
         g.w_gat = im.push(gat_score_fold(p[0], p[1], p[2], fi, fo, (size_t)gat1_heads));
         g.gat_bias = im.push(p[3], fo);
+        if (edge_dim > 0) // (... with edge features, gnnb_gatconv_edge.h: att_edge and lin_edge.weight behind the four)
+            g.a_edge = im.push(gat_edge_fold(p[5], p[4], (size_t)edge_dim, fo, (size_t)gat1_heads));
         return g;
     }
     if (gated) { // (a GIN description whose layers are ResGatedGraphConv's; canonical order: key, query, value, skip weight, conv.bias)
@@ -585,14 +618,15 @@ struct BuiltWeights {
 // with edge_dim > 0 besides, TransformerConv with edge features (nine tensors per layer).  gated: a ResGatedGraphConv model (a GIN
 // description, eight tensors per layer; no execution-order copy either); with edge_dim > 0 besides, ResGatedGraphConv with edge
 // features (the same eight, three of them [out, in + edge_dim]).  gat1_heads > 0: a GAT v1 model (a GCN description, four tensors
-// per layer; no fragment copy -- it takes no stack kernel).
+// per layer; no fragment copy -- it takes no stack kernel); with edge_dim > 0 besides, GAT v1 with edge features (six tensors per
+// layer).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
                                        int tf_heads = 0, bool gated = false, int gat1_heads = 0)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = gat1_heads > 0  ? GAT1_PARAM_SLOTS
+    const int slots = gat1_heads > 0  ? GAT1_PARAM_SLOTS + (edge_dim ? 2 : 0)
                       : gated         ? RG_PARAM_SLOTS
                       : tf_heads > 0  ? TF_PARAM_SLOTS + (edge_dim ? 1 : 0)
                       : gat_heads > 0 ? GAT_PARAM_SLOTS + (edge_dim ? 1 : 0)

@@ -332,7 +332,7 @@ class GATConv_GNNB(nn.Module):
     """Listed by the reference's SUPPORTED_GNN_CONVS but it has no native kernel for it
     (gnn_builder_lib.h:2343 ``// TODO: GAT layer``; template TODO model.cpp.jinja:141-142);
     out of scope here as well.  Attention models run as ``GATv2Conv_GNNB`` below (``GATv2EConv_GNNB`` with edge features);
-    PyG's ``GATConv`` itself runs as ``GATv1Conv_GNNB``.  This stub keeps the reference's behaviour."""
+    PyG's ``GATConv`` itself runs as ``GATv1Conv_GNNB`` (``GATv1EConv_GNNB`` with ``edge_dim``).  This stub keeps the reference's behaviour."""
 
     def __init__(self, *args, **kwargs):
         super().__init__()
@@ -492,6 +492,82 @@ class GATv1Conv_GNNB(nn.Module):
 
     def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
         return self.conv(x, edge_index)
+
+
+class _GATEConv(_GATConv):
+    """``_GATConv`` with edge features: PyG's ``GATConv(..., edge_dim=d, fill_value='mean')``.  The edge term enters the score
+    only, as one scalar per head; the message stays ``x'_j``::
+
+        p_ij = lin_edge(e_ij) [H, C]                     lin_edge: Linear(d, H C, bias=False)
+        s_ij[h] = leaky_relu(att_src[h] . x'_j[h] + att_dst[h] . x'_i[h] + att_edge[h] . p_ij[h])     for j in N(i) u {i}
+
+    Self loops: explicit ``(v, v)`` rows of the input are removed TOGETHER WITH their attribute rows, one self loop is added per
+    node and its attribute is the mean of the attributes of the node's remaining in-edges (taken after the removal; 0 for a node
+    without in-edges).  Parameters: ``_GATConv``'s, then ``att_edge`` [1, H, C] and ``lin_edge.weight`` [H C, d], both glorot."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, heads: int = 1, negative_slope: float = 0.2):
+        super().__init__(in_channels, out_channels, heads, negative_slope)
+        self.att_edge = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.lin_edge = nn.Linear(edge_dim, heads * out_channels, bias=False)
+        _glorot(self.att_edge)
+        _glorot(self.lin_edge.weight)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        n, H, C = x.size(0), self.heads, self.out_channels
+        d = self.lin_edge.in_features
+        edge_attr = edge_attr.reshape(-1, d)
+        if edge_index.numel():
+            keep = edge_index[0] != edge_index[1]
+            edge_index, edge_attr = edge_index[:, keep], edge_attr[keep]
+        loops = torch.arange(n, dtype=torch.long, device=x.device)
+        esrc = edge_index[0].long() if edge_index.numel() else loops[:0]
+        edst = edge_index[1].long() if edge_index.numel() else loops[:0]
+        # fill_value='mean': the self loop's attribute is the mean over the remaining in-edges (count clamped to 1: 0 without any)
+        deg = x.new_zeros(n).index_add(0, edst, x.new_ones(edst.numel()))
+        loop_attr = x.new_zeros(n, d).index_add(0, edst, edge_attr) / deg.clamp(min=1).unsqueeze(-1)
+        src, dst = torch.cat([esrc, loops]), torch.cat([edst, loops])
+        p = self.lin_edge(torch.cat([edge_attr, loop_attr])).view(-1, H, C)
+        xl = self.lin(x).view(n, H, C)
+        s_src = (xl * self.att_src).sum(dim=-1)  # [N, H]
+        s_dst = (xl * self.att_dst).sum(dim=-1)
+        s_edge = (p * self.att_edge).sum(dim=-1)  # [E + N, H]
+        s = nn.functional.leaky_relu(s_src[src] + s_dst[dst] + s_edge, self.negative_slope)
+        idx = dst.unsqueeze(-1).expand(-1, H)
+        smax = s.new_full((n, H), float("-inf")).scatter_reduce(0, idx, s, reduce="amax", include_self=True)
+        e = (s - smax[dst]).exp()
+        a = e / (s.new_zeros(n, H).index_add(0, dst, e)[dst] + 1e-16)
+        out = x.new_zeros(n, H, C).index_add(0, dst, a.unsqueeze(-1) * xl[src])
+        return out.reshape(n, H * C) + self.bias
+
+
+class GATv1EConv_GNNB(nn.Module):
+    """GAT (v1) with edge features: ``GATv1Conv_GNNB`` whose scores see ``edge_attr`` -- PyG's ``GATConv(in_channels,
+    out_channels // heads, heads=heads, edge_dim=d)``.  ``GNNModel(..., graph_input_edge_dim=d, gnn_conv=GATv1EConv_GNNB,
+    gnn_heads=H)`` builds every layer with ``edge_dim=d`` (1 .. 16) and ``forward(x, edge_index, batch, edge_attr)`` hands the same
+    ``edge_attr`` [E, d] to each.  The accelerated path is ``runtime.CompiledModel.from_model`` with ``forward_edges`` /
+    ``forward_pyg_edges`` (C ABI ``include/gnnb_gatconv_edge.h``: ``att_edge`` is folded into ``lin_edge`` at upload, the edge term
+    is ``d`` FMAs per edge and head inside the aggregate kernel, csrc/k_gat_edge.hip).  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, heads: int = 1, negative_slope: float = 0.2,
+                 p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
+            raise ValueError(f"heads must be an int in 1 .. {MAX_GAT_HEADS} (got {heads!r})")
+        if out_channels % heads != 0:
+            raise ValueError(f"out_channels ({out_channels}) must be divisible by heads ({heads})")
+        if not isinstance(edge_dim, int) or isinstance(edge_dim, bool) or not 1 <= edge_dim <= 16:
+            raise ValueError(f"edge_dim must be an int in 1 .. 16 (got {edge_dim!r})")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.edge_dim = edge_dim
+        self.heads = heads
+        self.negative_slope = float(negative_slope)
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _GATEConv(in_channels, out_channels // heads, edge_dim, heads, self.negative_slope)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        return self.conv(x, edge_index, edge_attr)
 
 
 class _GATv2EConv(_GATv2Conv):
@@ -919,18 +995,18 @@ class MLP(nn.Module):
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
                        GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB,
-                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB]
+                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
               PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
               TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated", ResGatedGraphEConv_GNNB: "resgatede",
-              GATv1Conv_GNNB: "gat"}
+              GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate"}
 # convs that take edge_attr, and what the messages call them
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE",
-               ResGatedGraphEConv_GNNB: "ResGatedE"}
-MAX_EDGE_DIM = 16  # of a GINE, PNAE, GATv2E, TransformerE or ResGatedE model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h, gnnb_transformer_edge.h, gnnb_resgated_edge.h)
+               ResGatedGraphEConv_GNNB: "ResGatedE", GATv1EConv_GNNB: "GATE"}
+MAX_EDGE_DIM = 16  # of a GINE, PNAE, GATv2E, TransformerE, ResGatedE or GATE model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h, gnnb_transformer_edge.h, gnnb_resgated_edge.h, gnnb_gatconv_edge.h)
 _GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # the GATv2 convs (heads and negative_slope travel beside a GCN description)
 _TF_CONVS = (TransformerConv_GNNB, TransformerEConv_GNNB)  # the TransformerConv convs (heads travel beside a GIN description)
-_GAT1_CONVS = (GATv1Conv_GNNB,)  # PyG's GATConv (heads and negative_slope travel beside a GCN description: include/gnnb_gatconv.h)
+_GAT1_CONVS = (GATv1Conv_GNNB, GATv1EConv_GNNB)  # PyG's GATConv (heads and negative_slope travel beside a GCN description: include/gnnb_gatconv.h, gnnb_gatconv_edge.h)
 _HEAD_CONVS = _GAT_CONVS + _TF_CONVS + _GAT1_CONVS  # convs with attention heads: the ones that take gnn_heads
 
 
@@ -975,7 +1051,7 @@ class GNNModel(nn.Module):
             if gnn_num_layers >= 1 and any(w % gnn_heads for w in widths):
                 raise ValueError(f"gnn_hidden_dim and gnn_output_dim ({gnn_hidden_dim}, {gnn_output_dim}) must be divisible by "
                                  f"gnn_heads ({gnn_heads})")
-            conv_kwargs = {**conv_kwargs, "heads": gnn_heads}  # (GATv2E, TransformerE: edge_dim from above stays)
+            conv_kwargs = {**conv_kwargs, "heads": gnn_heads}  # (GATv2E, TransformerE, GATE: edge_dim from above stays)
         elif gnn_heads != 1:
             raise ValueError(f"gnn_heads={gnn_heads!r}: only a GATv2 model (gnn_conv=GATv2Conv_GNNB) has attention heads")
 
@@ -1014,7 +1090,7 @@ class GNNModel(nn.Module):
         (node -> graph index, PyG ``Batch`` convention) every graph is pooled separately ->
         ``[num_graphs, out]``; the reference ignores ``batch`` and pools all nodes into one row
         (models.py:551-553,569; SURVEY finding 3), which has no meaning for independent graphs.
-        ``edge_attr`` [E, graph_input_edge_dim]: a GINE, PNAE, GATv2E, TransformerE or ResGatedE model's edge features, the same for every layer (required
+        ``edge_attr`` [E, graph_input_edge_dim]: a GINE, PNAE, GATv2E, TransformerE, ResGatedE or GATE model's edge features, the same for every layer (required
         there; the other convs ignore it)."""
         gine = self.gnn_conv in _EDGE_CONVS
         if gine and edge_attr is None:
@@ -1146,6 +1222,8 @@ class GNNModel(nn.Module):
             "conv_lin_skip_weight", "conv_bias"]
         per_conv["resgatede"] = per_conv["resgated"]  # (the same eight; key, query and value weights are [out, in + edge_dim])
         per_conv["gat"] = ["conv_lin_weight", "conv_att_src", "conv_att_dst", "conv_bias"]  # (include/gnnb_gatconv.h)
+        # (GAT v1's four, then att_edge [1, heads, out / heads] and lin_edge [out, edge_dim]: include/gnnb_gatconv_edge.h)
+        per_conv["gate"] = per_conv["gat"] + ["conv_att_edge", "conv_lin_edge_weight"]
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

@@ -30,13 +30,14 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn"}  # spec["conv"] -> the conv its description carries, where that is another
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn"}  # spec["conv"] -> the conv its description carries, where that is another
 # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h,
-# "resgatede": gnnb_resgated_edge.h)
-_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede")
+# "resgatede": gnnb_resgated_edge.h, "gate": gnnb_gatconv_edge.h)
+_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede", "gate")
 _GAT_CONVS = ("gatv2", "gatv2e")       # ... and of those with heads and negative_slope beside it
 # a GAT v1 model (include/gnnb_gatconv.h, spec["conv"] == "gat"): a GCN description, heads and negative_slope beside it, within GATv2's
-# limits -- a model kind of its own
+# limits -- a model kind of its own; with edge features ("gate", include/gnnb_gatconv_edge.h) edge_dim too
+_GATCONV_CONVS = ("gat", "gate")
 # a TransformerConv model (include/gnnb_transformer.h, spec["conv"] == "transformer"): its description is GIN's -- the tables keep
 # explicit (v, v) edges --, heads travels beside it; with edge features ("transformere", include/gnnb_transformer_edge.h) edge_dim too
 _TRANSFORMER_CONVS = ("transformer", "transformere")
@@ -243,6 +244,14 @@ ABI_GATCONV = {
 }
 
 
+# ... and of include/gnnb_gatconv_edge.h (GAT v1 models with edge features), in its order (tests/test_abi_gatconv_edge.py)
+ABI_GATCONV_EDGE = {
+    "gnnb_gatconv_edge_model_num_params": (_I, [_DESC, _I, _I]),
+    "gnnb_gatconv_edge_model_create": (_I, [_DESC, _I, _F, _I, _PP, _I, _PP]),
+    "gnnb_aggregate_gat_edges": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _F, _P, _I, _P, _I, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -287,7 +296,8 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
         import torch  # noqa: F401  (HIP runtime first, see docstring)
         lib = C.CDLL(str(LIB_PATH))
         for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER,
-                                           **ABI_TRANSFORMER_EDGE, **ABI_RESGATED, **ABI_RESGATED_EDGE, **ABI_GATCONV}.items():
+                                           **ABI_TRANSFORMER_EDGE, **ABI_RESGATED, **ABI_RESGATED_EDGE, **ABI_GATCONV,
+                                           **ABI_GATCONV_EDGE}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -434,7 +444,7 @@ class CompiledModel:
         self.edge_dim = int(spec.get("edge_dim", 0) or 0) if spec.get("conv") in _EDGE_CONVS else 0
         self.gat_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _GAT_CONVS else 0
         self.transformer_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _TRANSFORMER_CONVS else 0
-        self.gatconv_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") == "gat" else 0
+        self.gatconv_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _GATCONV_CONVS else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
@@ -450,6 +460,8 @@ class CompiledModel:
                     self.lib.gnnb_transformer_edge_model_num_params(C.byref(self.desc), self.transformer_heads, self.edge_dim)
                     if spec.get("conv") == "transformere" else
                     self.lib.gnnb_resgated_edge_model_num_params(C.byref(self.desc), self.edge_dim) if spec.get("conv") == "resgatede" else
+                    self.lib.gnnb_gatconv_edge_model_num_params(C.byref(self.desc), self.gatconv_heads, self.edge_dim)
+                    if spec.get("conv") == "gate" else
                     num_params(C.byref(self.desc), self.edge_dim) if self.edge_dim else
                     self.lib.gnnb_gat_model_num_params(C.byref(self.desc), self.gat_heads) if spec.get("conv") == "gatv2" else
                     self.lib.gnnb_transformer_model_num_params(C.byref(self.desc), self.transformer_heads) if spec.get("conv") == "transformer" else
@@ -469,6 +481,9 @@ class CompiledModel:
                                                                C.byref(self._model)))
         elif spec.get("conv") == "resgatede":  # (gnnb_resgated_edge.h: a GIN description, the "gated" mark and edge_dim beside it)
             _check(self.lib.gnnb_resgated_edge_model_create(C.byref(self.desc), self.edge_dim, arr, len(host), C.byref(self._model)))
+        elif spec.get("conv") == "gate":  # (gnnb_gatconv_edge.h: a GCN description, heads, negative_slope and edge_dim beside it)
+            _check(self.lib.gnnb_gatconv_edge_model_create(C.byref(self.desc), self.gatconv_heads, float(spec.get("negative_slope", 0.2)),
+                                                           self.edge_dim, arr, len(host), C.byref(self._model)))
         elif self.edge_dim:
             _check(create(C.byref(self.desc), self.edge_dim, arr, len(host), C.byref(self._model)))
         elif spec.get("conv") == "gatv2":  # (gnnb_gat.h: a GCN description, heads and negative_slope beside it)
@@ -1206,6 +1221,47 @@ class CompiledModel:
                                                    int(xr.stride(0)) if self._N > 1 else w, _dptr(att), _optr(bias), _optr(skip), ACT[act],
                                                    heads, float(negative_slope), ea, ed, _dptr(w_edge), int(w_edge.stride(0)) if w > 1 else ed,
                                                    _dptr(out), w, _stream_ptr(stream)))
+        return out
+
+    def aggregate_gat_edges(self, xl, s_src, s_dst, edge_attr, a_edge, bias=None, skip=None, act: str = "none", heads: int = 1,
+                            negative_slope: float = 0.2, out=None, stream=None):
+        """One GAT (v1) layer with edge features behind its GEMM (``gnnb_aggregate_gat_edges``, csrc/k_gat_edge.hip) on the prepared
+        batch of a GCN, GAT or GATv2 model's workspace: ``aggregate_gat`` with ``s_ij[h] = leaky_relu(s_src[j, h] + s_dst[i, h] +
+        a_edge[h] . e_ij)``; the self term's edge term is the mean of the row's.  ``xl``, ``s_src``, ``s_dst``, ``bias``, ``skip``,
+        ``heads`` as there; ``edge_attr`` [E, edge_dim <= 16] in COO order, ``a_edge`` [heads, edge_dim]: ``att_edge`` folded into
+        ``lin_edge`` (a column slice of a wider matrix is fine: its row stride is passed on)."""
+        import torch
+        _require_strided(xl, "xl", self._N, 1)
+        w = int(xl.shape[1])
+        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
+            raise GnnbError(f"heads must be an int in 1 .. {MAX_GAT_HEADS}, got {heads!r}")
+        if w > MAX_GAT_WIDTH or w % heads:
+            raise GnnbError(f"width {w}: a GAT layer is at most {MAX_GAT_WIDTH} wide and divisible by heads ({heads})")
+        for t, name in ((s_src, "s_src"), (s_dst, "s_dst")):
+            _require_strided(t, name, self._N, heads)
+            if int(t.shape[1]) != heads or t.device != xl.device:
+                raise GnnbError(f"{name} must be [{self._N}, {heads}] on {xl.device}, got {tuple(t.shape)} on {t.device}")
+        if act not in ACT:
+            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        if bias is not None:
+            _require(bias, "bias", torch.float32, 1, w)
+            if bias.device != xl.device:
+                raise GnnbError(f"bias must be on {xl.device}")
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, xl)
+        _require_strided(a_edge, "a_edge", heads, 1)
+        ed = int(a_edge.shape[1])
+        if not 1 <= ed <= MAX_EDGE_DIM or a_edge.device != xl.device:
+            raise GnnbError(f"a_edge must be [{heads}, 1 .. {MAX_EDGE_DIM}] on {xl.device}, got {tuple(a_edge.shape)} on {a_edge.device}")
+        ea = self._require_edge_attr(edge_attr, self._E, xl, ed)
+        out = _out(out, self._N, w, xl)
+
+        def ld(t, cols):
+            return int(t.stride(0)) if self._N > 1 else cols
+        _check(self.lib.gnnb_aggregate_gat_edges(self._ws, _dptr(xl), ld(xl, w), _dptr(s_src), ld(s_src, heads), _dptr(s_dst),
+                                                 ld(s_dst, heads), _optr(bias), _optr(skip), ACT[act], heads, float(negative_slope), ea, ed,
+                                                 _dptr(a_edge), int(a_edge.stride(0)) if heads > 1 else ed, _dptr(out), w,
+                                                 _stream_ptr(stream)))
         return out
 
     def gine_conv(self, x, edge_attr, w_edge, b_edge, w0, b0, w1, b1, eps: float = 0.0, stream=None):
