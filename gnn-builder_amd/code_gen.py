@@ -28,7 +28,7 @@ import jinja2
 import numpy as np
 import torch
 
-from .models import (GATv1Conv_GNNB, GATv1EConv_GNNB, GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, PNAEConv_GNNB, ResGatedGraphConv_GNNB,
+from .models import (GATv1Conv_GNNB, GATv1EConv_GNNB, GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, GatedGraphConv_GNNB, PNAEConv_GNNB, ResGatedGraphConv_GNNB,
                      ResGatedGraphEConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB)
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
@@ -137,6 +137,10 @@ class Project:
                 "Project does not generate GAT designs with edge features: the generated shim and the templates have no attention "
                 "layer and carry no edge attributes; run the model through runtime.CompiledModel.from_model(model, ...)"
                 ".forward_edges / forward_pyg_edges")
+        if getattr(model, "gnn_conv", None) is GatedGraphConv_GNNB:
+            raise NotImplementedError(
+                "Project does not generate GatedGraphConv designs: the generated shim and the templates have no recurrent layer; run "
+                "the model through runtime.CompiledModel.from_model(model, ...).forward / forward_pyg")
         self.model = model
         self.dataset = dataset
         self.name = name

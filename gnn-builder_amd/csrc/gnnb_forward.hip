@@ -76,8 +76,8 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     g.nl = 0;
     const int L = d.num_layers;
     // a GINE model: no stack kernel forms the edge term; a GATv2 model, a GAT v1 model, a TransformerConv model: none forms
-    // attention; a ResGatedGraphConv model: none forms the gate
-    if (model->edge_dim || model->gat_heads || model->gat1_heads || model->tf_heads || model->gated)
+    // attention; a ResGatedGraphConv model: none forms the gate; a GatedGraphConv model: none forms the GRU cell
+    if (model->edge_dim || model->gat_heads || model->gat1_heads || model->tf_heads || model->gated || model->ggnn_steps)
         return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
@@ -322,6 +322,36 @@ static int resgated_layer(const LayerCtx &c)
     return GNNB_OK;
 }
 
+// GatedGraphConv (gnnb_ggnn.h; a GIN description with `steps` beside it, so the tables keep explicit (v, v) edges): steps x (ONE GEMM
+// h -> [p | gh] [N, 6 fo] on [W_p[t] ; weight_hh] with the bias [0 | bias_hh] in the model's math mode -- the message weight is
+// folded into the GRU's input weight at upload --, then ONE k_ggnn_aggregate launch: the sum of the neighbours' p rows and the whole
+// GRU cell in one pass over the edges).  Step 0 reads the layer's input at K = fi (h_0 = [x | 0]: the kernel takes h's columns from
+// fi on as 0); the inner steps write the two [N, fo] state buffers in ws->tmp1 in turn, without skip term or activation; the last
+// step writes the layer's output with both in its epilogue.  None of the fused rungs
+static int ggnn_layer(const LayerCtx &c)
+{
+    const gnnb_model_desc &d = c.model->desc;
+    const LayerWeights &p = c.model->conv[c.l];
+    const int fi = c.fi, fo = c.fo, steps = c.model->ggnn_steps;
+    float *pg = c.ws->tmp0;
+    // (tmp0 and tmp1 are [max_nodes, >= GGNN_TMP_BLOCKS fo], gnnb_host.h: room for [p | gh] and for both state buffers)
+    float *state[2] = {c.ws->tmp1, c.ws->tmp1 + ggnn_state_offset((size_t)c.ws->t.num_nodes, (size_t)fo)};
+    const float *h = c.cur;
+    int hw = fi, rc;
+    for (int t = 0; t < steps; t++) {
+        const bool last = t == steps - 1;
+        const float *w = t == 0 ? p.w_ggc : p.w_ggc_next + (size_t)(t - 1) * ggnn_step_stride(fo);
+        if ((rc = c.linear1(c.rows(h, hw), hw, w, hw, p.b_ggc, nullptr, c.rows(pg, 6 * fo), 6 * fo, GNNB_ACT_NONE)))
+            return rc;
+        float *o = last ? c.nxt : state[t & 1];
+        if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+            GNNB_HIP_TRY(launch_ggnn_aggregate(c.tv, pg, 6 * fo, pg + 3 * fo, 6 * fo, h, hw, hw, p.b_ih, last ? c.skip : nullptr,
+                                               last ? d.activation : GNNB_ACT_NONE, o, fo, c.hs()));
+        h = o, hw = fo;
+    }
+    return GNNB_OK;
+}
+
 // GIN's first linear + ReLU on the eps-weighted sum -> ws->tmp0
 static int gin_hidden(const LayerCtx &c)
 {
@@ -499,7 +529,9 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
         int rc = GNNB_OK;
         switch (d.conv_type) {
         case GNNB_CONV_GCN: rc = model->gat_heads ? gat_layer(c) : model->gat1_heads ? gat1_layer(c) : gcn_layer(c); break;
-        case GNNB_CONV_GIN: rc = model->tf_heads ? transformer_layer(c) : model->gated ? resgated_layer(c) : gin_layer(c); break;
+        case GNNB_CONV_GIN:
+            rc = model->tf_heads ? transformer_layer(c) : model->gated ? resgated_layer(c) : model->ggnn_steps ? ggnn_layer(c) : gin_layer(c);
+            break;
         case GNNB_CONV_SAGE: rc = sage_layer(c); break;
         case GNNB_CONV_PNA: rc = pna_layer(c); break;
         }
@@ -776,7 +808,8 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
         return fail(GNNB_ERR_INVALID, "workspace has no prepared batch");
     if (memcmp(&model->desc, &ws->desc, sizeof(gnnb_model_desc)) != 0 || model->edge_dim != ws->edge_dim ||
         model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope || model->gat1_heads != ws->gat1_heads ||
-        model->tf_heads != ws->tf_heads || model->gated != ws->gated)
+        model->tf_heads != ws->tf_heads || model->gated != ws->gated ||
+        model->ggnn_steps != ws->ggnn_steps)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;

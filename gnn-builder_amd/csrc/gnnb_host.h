@@ -20,6 +20,7 @@
 #include "gnnb_transformer_edge.h"
 #include "gnnb_resgated.h"
 #include "gnnb_resgated_edge.h"
+#include "gnnb_ggnn.h"
 
 namespace gnnb {
 
@@ -65,6 +66,8 @@ struct gnnb_model {
     int gated = 0;          // 1: a ResGatedGraphConv model (gnnb_resgated_model_create; desc is a GIN description) -- every layer has
                             // w_kqvr, b_kqvr and none of GIN's slots; with edge_dim > 0 besides: ResGatedGraphConv with edge features
                             // (gnnb_resgated_edge_model_create) -- w_kqvr of the x column blocks, b_kqvr and w_gv_edge [2 out, edge_dim]
+    int ggnn_steps = 0;     // > 0: a GatedGraphConv model (gnnb_ggnn_model_create; desc is a GIN description) of that many steps per
+                            // layer -- every layer has w_ggc, w_ggc_next (steps > 1), b_ggc, b_ih and none of GIN's slots
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };
@@ -89,6 +92,7 @@ struct gnnb_workspace {
     int gat1_heads = 0;          // ... and its heads when it is a GAT v1 model (0: it is not; its slope is gat_slope)
     int tf_heads = 0;            // ... and its heads when it is a TransformerConv model (0: it is not)
     int gated = 0;               // ... and 1 when it is a ResGatedGraphConv model
+    int ggnn_steps = 0;          // ... and its steps when it is a GatedGraphConv model (0: it is not)
     char *edge_blob = nullptr;   // gnnb_workspace_enable_edge_ingest: edge_attr in COO row order, [max_edges, edge_dim], one allocation
     char *order_blob = nullptr;  // gnnb_workspace_enable_ordered_ingest: the ordered batch and the staged outputs (order_place), one allocation
     int32_t *order_triple = nullptr, *order_triple_dev = nullptr; // host-mapped (first large graph, node row, edge row) of k_order_graphs, and
@@ -123,6 +127,15 @@ struct gnnb_workspace {
 };
 
 namespace gnnb {
+// A GatedGraphConv workspace's scratch (gnnb_ggnn.h), stated once for gnnb_workspace_create, which sizes it, and ggnn_layer, which
+// carves it: tmp0 and tmp1 are [max_nodes, tmpw] with tmpw >= GGNN_TMP_BLOCKS * out for every layer.  tmp0 takes a step's GEMM
+// output [p | gh] [N, 6 out]; tmp1 takes the two [N, out] state buffers, the second ggnn_state_offset floats behind the first (a
+// whole number of 16-byte pieces), so both end within 2 N out + 3 <= 3 N out floats of it
+constexpr int GGNN_TMP_BLOCKS = 6;
+static_assert(GGNN_TMP_BLOCKS >= 6, "tmp0 holds [p | gh]: six column blocks of a layer's output width");
+static_assert(GGNN_TMP_BLOCKS >= 3, "tmp1 holds two [N, out] state buffers and up to 3 floats of alignment between them");
+inline size_t ggnn_state_offset(size_t num_nodes, size_t fo) { return (num_nodes * fo + 3) / 4 * 4; }
+
 // the model's MLP head as the readout kernels take it (gnnb_model.hip): the ONLY place that fills a HeadArgs
 HeadArgs model_head_args(const gnnb_model *model);
 
@@ -140,6 +153,9 @@ int refuse_transformer_model(const gnnb_model *model, const gnnb_workspace *ws, 
 
 // ... and for a ResGatedGraphConv model / its workspace (gnnb_resgated.h)
 int refuse_resgated_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
+
+// ... and for a GatedGraphConv model / its workspace (gnnb_ggnn.h)
+int refuse_ggnn_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
 
 // gnnb_runtime.hip, for the forward (gnnb_forward.hip) -- each is described where it is defined
 int ensure_gcoef(gnnb_workspace *ws, void *stream);

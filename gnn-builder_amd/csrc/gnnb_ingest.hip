@@ -211,6 +211,8 @@ int gnnb_forward_pyg_ordered(const gnnb_model *model, gnnb_workspace *ws, const 
         return rc;
     if (const int rc = refuse_resgated_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg"))
         return rc;
+    if (const int rc = refuse_ggnn_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg"))
+        return rc;
     const float *x_ord = nullptr;
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr, *perm = nullptr;
     int g0 = 0, n0 = 0, e0 = 0;

@@ -360,6 +360,14 @@ hipError_t launch_transformer_edge_aggregate(const BatchTables &t, const float *
 constexpr int RG_MAX_WIDTH = 256;
 hipError_t launch_resgated_aggregate(const BatchTables &t, const float *k, int ldk, const float *q, int ldq, const float *v, int ldv,
                                      const float *root, int ldr, const float *skip, int act, float *out, int width, hipStream_t s);
+// GatedGraphConv (k_ggnn.hip): one step behind its GEMM -- acc_g = sum_j p_j[g] over j in N(i) as the tables hold it, g the three
+// column blocks r | z | n of rows of stride ldp >= 3 width; gi = acc + b_ih; r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z),
+// n = tanh(gi_n + r gh_n); out [N, width] = act(n + z (h - n) + skip).  gh: rows of stride ldgh >= 3 width; h: rows of h_width <=
+// width floats at stride ldh, its columns from h_width on are 0 and not loaded; b_ih [3 width] or nullptr, skip [N, width] or
+// nullptr; tables that keep explicit (v, v) edges (any but a GCN description's).  hipErrorInvalidValue: nothing launched
+constexpr int GG_MAX_WIDTH = 256;
+hipError_t launch_ggnn_aggregate(const BatchTables &t, const float *p, int ldp, const float *gh, int ldgh, const float *h, int ldh, int h_width,
+                                 const float *b_ih, const float *skip, int act, float *out, int width, hipStream_t s);
 // ResGatedGraphConv with edge features (k_resgated_edge.hip): the same with the gate's argument (k_i + q_j) + wg . e_ij and the value
 // v_j + wv . e_ij, per column; edge_attr [E, edge_dim] in COO row order (t.eid maps the CSR slots; nullptr only with num_edges == 0),
 // wg / wv [width, edge_dim] at row strides ldwg / ldwv >= edge_dim, edge_dim 1 .. 16.  The kernel computes what it is given:

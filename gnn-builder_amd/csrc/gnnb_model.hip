@@ -194,13 +194,38 @@ int count_resgated_params(const gnnb_model_desc *desc, int edge_dim = 0)
     return RG_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
+// parameter tensors of a GatedGraphConv model (gnnb_ggnn.h): a GIN description (its tables keep explicit (v, v) edges) without the
+// fixed-point emulation, steps 1 .. 8, every layer's input width at most its output width (h_0 = [x | 0]), which is at most 256
+int count_ggnn_params(const gnnb_model_desc *desc, int steps)
+{
+    int rc = validate_desc(desc);
+    if (rc != GNNB_OK)
+        return rc;
+    if (steps < 1 || steps > GGNN_MAX_STEPS)
+        return fail(GNNB_ERR_INVALID, "steps %d: a GatedGraphConv model takes 1 .. %d steps per layer", steps, GGNN_MAX_STEPS);
+    if (desc->conv_type != GNNB_CONV_GIN)
+        return fail(GNNB_ERR_INVALID, "a GatedGraphConv model's description is a GIN description (conv_type %d given)", desc->conv_type);
+    if (desc->fpx_w != 0)
+        return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover GatedGraphConv models (fpx_w must be 0)");
+    for (int l = 0; l < desc->num_layers; l++) {
+        const LayerDims ld = layer_dims(*desc, l);
+        if (ld.fin > ld.fout)
+            return fail(GNNB_ERR_INVALID, "layer %d's input width %d exceeds its output width %d: a GatedGraphConv layer pads its input with "
+                                          "zero columns and cannot narrow it", l, ld.fin, ld.fout);
+        if (ld.fout > GG_MAX_WIDTH)
+            return fail(GNNB_ERR_INVALID, "layer %d's output width %d: a GatedGraphConv layer is at most %d wide", l, ld.fout, GG_MAX_WIDTH);
+    }
+    return GGNN_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+}
+
 // What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
 // type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
 // (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features), or heads of a
 // TransformerConv model (gnnb_transformer_model_create: a GIN description), or heads and edge_dim
 // (gnnb_transformer_edge_model_create: TransformerConv with edge features), or the "gated" mark of a ResGatedGraphConv model
 // (gnnb_resgated_model_create: a GIN description), or that mark and edge_dim (gnnb_resgated_edge_model_create: ResGatedGraphConv with
-// edge features), or heads and negative_slope of a GAT v1 model (gnnb_gatconv_model_create: a GCN description)
+// edge features), or heads and negative_slope of a GAT v1 model (gnnb_gatconv_model_create: a GCN description), or the steps of a
+// GatedGraphConv model (gnnb_ggnn_model_create: a GIN description)
 struct ModelKind {
     int edge_dim = 0, base = GNNB_CONV_GIN;
     int gat_heads = 0;
@@ -208,6 +233,7 @@ struct ModelKind {
     int tf_heads = 0;
     bool gated = false;
     int gat1_heads = 0; // (its slope: gat_slope)
+    int ggnn_steps = 0;
     static ModelKind plain() { return {}; }
     static ModelKind edges(int edge_dim, int base)
     {
@@ -257,6 +283,12 @@ struct ModelKind {
         k.gated = true;
         return k;
     }
+    static ModelKind ggnn(int steps)
+    {
+        ModelKind k;
+        k.ggnn_steps = steps;
+        return k;
+    }
     static ModelKind resgated_edges(int edge_dim)
     {
         ModelKind k = resgated();
@@ -265,7 +297,7 @@ struct ModelKind {
     }
 };
 
-// the body of the eleven *_model_create entries
+// the body of the twelve *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
@@ -273,7 +305,8 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
     const int gat1_heads = kind.gat1_heads;
-    int expect = gat1_heads != 0  ? count_gatconv_params(desc, gat1_heads, edge_dim)
+    int expect = kind.ggnn_steps != 0 ? count_ggnn_params(desc, kind.ggnn_steps)
+                 : gat1_heads != 0 ? count_gatconv_params(desc, gat1_heads, edge_dim)
                  : kind.gated     ? count_resgated_params(desc, edge_dim)
                  : tf_heads != 0  ? count_transformer_params(desc, tf_heads, edge_dim)
                  : gat_heads != 0 ? count_gat_params(desc, gat_heads, edge_dim)
@@ -291,7 +324,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
         return fail(GNNB_ERR_NO_DEVICE, "no HIP device visible: the MI355X path cannot run");
 
     const gnnb_model_desc &d = *desc;
-    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated, gat1_heads);
+    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated, gat1_heads, kind.ggnn_steps);
     const std::vector<float> &img = built.img;
     const WeightLayout &lo = built.layout;
 
@@ -303,6 +336,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     m->gat1_heads = gat1_heads;
     m->tf_heads = tf_heads;
     m->gated = kind.gated ? 1 : 0;
+    m->ggnn_steps = kind.ggnn_steps;
     (void)hipGetDevice(&m->device);
     m->blob_floats = img.size();
     hipError_t e = hipMalloc((void **)&m->blob, std::max<size_t>(img.size(), 4) * sizeof(float));
@@ -514,6 +548,19 @@ int gnnb_resgated_edge_model_create(const gnnb_model_desc *desc, int edge_dim, c
         return fail(GNNB_ERR_INVALID, "edge_dim 0: a ResGatedGraphConv model with edge features takes edge_dim 1 .. %d", RGE_MAX_EDGE_DIM);
     return model_create(desc, ModelKind::resgated_edges(edge_dim), host_params, num_params, out_model);
 }
+
+int gnnb_ggnn_model_num_params(const gnnb_model_desc *desc, int steps) { return count_ggnn_params(desc, steps); }
+
+int gnnb_ggnn_model_create(const gnnb_model_desc *desc, int steps, const float *const *host_params, int num_params, gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (steps == 0) // (ModelKind reads 0 as "no GatedGraphConv model")
+        return fail(GNNB_ERR_INVALID, "steps 0: a GatedGraphConv model takes 1 .. %d steps per layer", GGNN_MAX_STEPS);
+    return model_create(desc, ModelKind::ggnn(steps), host_params, num_params, out_model);
+}
+
+int gnnb_model_ggnn_steps(const gnnb_model *model) { return model ? model->ggnn_steps : 0; }
 
 void gnnb_model_destroy(gnnb_model *model)
 {

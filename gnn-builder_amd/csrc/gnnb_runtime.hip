@@ -92,6 +92,14 @@ int refuse_resgated_model(const gnnb_model *model, const gnnb_workspace *ws, con
     return GNNB_OK;
 }
 
+int refuse_ggnn_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use)
+{
+    if ((model && model->ggnn_steps) || (ws && ws->ggnn_steps))
+        return fail(GNNB_ERR_INVALID, "%s: a GatedGraphConv model (gnnb_ggnn_model_create) runs layer by layer and is not served here: "
+                                      "call %s (gnnb_ggnn.h)", entry, use);
+    return GNNB_OK;
+}
+
 static thread_local int tl_math = -1; // >= 0: the calling thread is inside an entry point of a model with its own math mode
 static thread_local FlagWord tl_flag = {nullptr, nullptr};
 int launch_math() { return tl_math >= 0 ? tl_math : (int)options().math; }
@@ -185,6 +193,9 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     if (model->gated) // a ResGatedGraphConv layer's GEMM writes [k | q | v | r] [N, 4 out] into tmp0
         for (int l = 0; l < d.num_layers; l++)
             tmpw = std::max(tmpw, 4 * layer_dims(d, l).fout);
+    if (model->ggnn_steps) // a GatedGraphConv step's GEMM writes [p | gh] [N, 6 out] into tmp0; tmp1 holds the two [N, out] state buffers
+        for (int l = 0; l < d.num_layers; l++)
+            tmpw = std::max(tmpw, GGNN_TMP_BLOCKS * layer_dims(d, l).fout); // (gnnb_host.h: what ggnn_layer carves from them)
     // the widest GEMM K of the conv layers: from 1024 on k_linear_dma may cut its tiles along K (stream-K) and needs a scratch,
     // which belongs to the workspace -- forwards of different workspaces never share one, whatever streams or graphs run them
     int max_k = 0;
@@ -196,8 +207,8 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     // (the stage-cut planner's tables: opt-in -- carved only for workspaces created while the option is on; a workspace created
     // without them keeps equal tile counts whatever the option says later: round-5 advisor finding)
     const bool want_plan = options().stage_cut && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 &&
-                           model->gat_heads == 0 && model->gat1_heads == 0 && model->tf_heads == 0 && model->gated == 0; // (a GATv2 model,
-                                            // a GAT v1 model, a TransformerConv model, a ResGatedGraphConv model take no stack kernel: no stage plan)
+                           model->gat_heads == 0 && model->gat1_heads == 0 && model->tf_heads == 0 && model->gated == 0 && model->ggnn_steps == 0; // (a GATv2 model,
+                                            // a GAT v1 model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model take no stack kernel: no stage plan)
     const int pooledw = d.num_pools * gnn_out_width(d);
     const int mlpw = std::max(d.mlp_hidden, d.mlp_out);
     const int min_tile_rows = 4;
@@ -211,6 +222,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     ws->gat1_heads = model->gat1_heads;
     ws->tf_heads = model->tf_heads;
     ws->gated = model->gated;
+    ws->ggnn_steps = model->ggnn_steps;
     ws->max_graphs = max_graphs;
     ws->max_nodes = max_nodes;
     ws->max_edges = max_edges;
@@ -370,10 +382,10 @@ int gnnb_workspace_set_max_degree(gnnb_workspace *ws, int d)
 static bool stack_promised(const gnnb_workspace *ws)
 {
     const gnnb_model_desc &d = ws->desc;
-    // (a GINE model's workspace, a GATv2 model's, a GAT v1 model's, a TransformerConv model's, a ResGatedGraphConv model's: never --
-    // their layers take no stack kernel, whatever the promise)
+    // (a GINE model's workspace, a GATv2 model's, a GAT v1 model's, a TransformerConv model's, a ResGatedGraphConv model's, a
+    // GatedGraphConv model's: never -- their layers take no stack kernel, whatever the promise)
     return options().fuse_gcn2 && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 && ws->max_graph_nodes > 0 &&
-           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->gat1_heads == 0 && ws->tf_heads == 0 && ws->gated == 0;
+           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->gat1_heads == 0 && ws->tf_heads == 0 && ws->gated == 0 && ws->ggnn_steps == 0;
 }
 
 // ... and the WHOLE batch is expected there: no large segment, no fixed-point emulation.  Such a batch needs neither the
@@ -866,6 +878,26 @@ int gnnb_aggregate_resgated(gnnb_workspace *ws, const float *k_dev, int ldk, con
                                       "root's ldr >= width, a gnnb_act)", RG_MAX_WIDTH);
     GNNB_HIP_TRY(launch_resgated_aggregate(ws->t, k_dev, ldk, q_dev, ldq, v_dev, ldv, root_dev, ldr, skip_dev, act, out_dev, width,
                                            (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_ggnn(gnnb_workspace *ws, const float *p_dev, int ldp, const float *gh_dev, int ldgh, const float *h_dev, int ldh, int h_width,
+                        const float *b_ih_dev, const float *skip_dev, int act, float *out_dev, int width, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_ggnn needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's, a GAT v1 model's, with or without edge features)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_ggnn takes a prepared batch whose tables keep explicit self loops: graph prep drops the "
+                                      "(v, v) edges on a workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts "
+                                      "them as ordinary edges");
+    // (a prepared batch without nodes launches nothing and reads no operand: an empty tensor's NULL pointer is no error there)
+    const bool operands = ws->t.num_nodes <= 0 || (p_dev && gh_dev && h_dev && out_dev);
+    if (!operands || width < 1 || width > GG_MAX_WIDTH || h_width < 1 || h_width > width || ldp < 3 * width ||
+        ldgh < 3 * width || ldh < h_width || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE)
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_ggnn (p, gh, h and out not NULL unless the batch has no nodes, width 1 .. %d, h_width 1 .. width, ldp "
+                                      "and ldgh >= 3 width, ldh >= h_width, a gnnb_act)", GG_MAX_WIDTH);
+    GNNB_HIP_TRY(launch_ggnn_aggregate(ws->t, p_dev, ldp, gh_dev, ldgh, h_dev, ldh, h_width, b_ih_dev, skip_dev, act, out_dev, width,
+                                       (hipStream_t)stream));
     return GNNB_OK;
 }
 

@@ -134,6 +134,15 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //                                                   lin_query: both enter the gate's argument; added in double, rounded once --
 //                                                   resgated_edge_blocks), W_v = W_ve, copied -- what k_resgated_edge_aggregate adds
 //                                                   per edge to the gate's argument and to the value
+//   GatedGraphConv  (gnnb_model::ggnn_steps > 0, gnnb_ggnn_model_create: a GIN description) none of GIN's slots, but per (layer, step)
+//              w_ggc [6 out, in]                    derived, step 0: [W_p[0][:, :in] ; weight_hh[:, :in]], W_p[t] = weight_ih weight[t]^T
+//                                                   [3 out, out] (ggnn_fold: canonical 1, conv.rnn.weight_ih, folded into canonical 0,
+//                                                   conv.weight [steps, out, out]) on top of canonical 2 (conv.rnn.weight_hh) -- ONE
+//                                                   GEMM gives [p | gh] [N, 6 out].  Only the first `in` input columns: h_0 = [x | 0]
+//              w_ggc_next [steps - 1][6 out, out]   derived, steps 1 ..: [W_p[t] ; weight_hh], each at ggnn_step_stride(out) floats
+//              b_ggc [6 out]                        derived: [0 | bias_hh], canonical 4 -- the p block takes NO bias (it would be
+//                                                   counted once per edge)
+//              b_ih [3 out]                         canonical 3: conv.rnn.bias_ih, raw -- k_ggnn_aggregate adds it once per row
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
@@ -143,6 +152,7 @@ template <typename T> struct LayerSlots {
     T w_qkvr = absent_slot<T>(), b_qkvr = absent_slot<T>();
     T w_qkvre = absent_slot<T>(), b_qkvre = absent_slot<T>();
     T w_kqvr = absent_slot<T>(), b_kqvr = absent_slot<T>(), w_gv_edge = absent_slot<T>();
+    T w_ggc = absent_slot<T>(), w_ggc_next = absent_slot<T>(), b_ggc = absent_slot<T>(), b_ih = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -151,7 +161,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -488,20 +498,63 @@ inline std::vector<float> resgated_edge_blocks(const float *w_key, const float *
     return gv;
 }
 
+// GatedGraphConv: the message weight folded into the GRU's input weight.  m_i = sum_j h_j weight[t] (a plain matmul) and
+// gi = m weight_ih^T, so gi_i = sum_j h_j (weight[t] weight_ih^T) = sum_j W_p[t] h_j in nn.Linear layout with
+//   W_p[t][g][k] = sum_c weight_ih[g][c] * weight[t][k][c]          [3 fo, fo]
+// (accumulated in double, c increasing, rounded once -- as gat_score_fold) on top of weight_hh, both cut to their first `cols` input
+// columns: [6 fo, cols].  cols = the layer's input width at step 0 (h_0 = [x | 0]: the zero padding costs no flops), fo behind it.
+// weight_t [fo, fo] = weight[t], w_ih / w_hh [3 fo, fo]
+inline std::vector<float> ggnn_fold(const float *weight_t, const float *w_ih, const float *w_hh, size_t fo, size_t cols)
+{
+    std::vector<float> f(6 * fo * cols);
+    for (size_t g = 0; g < 3 * fo; g++)
+        for (size_t k = 0; k < cols; k++) {
+            double acc = 0.0;
+            for (size_t c = 0; c < fo; c++)
+                acc += (double)w_ih[g * fo + c] * (double)weight_t[k * fo + c];
+            f[g * cols + k] = (float)acc;
+        }
+    for (size_t g = 0; g < 3 * fo; g++)
+        memcpy(&f[(3 * fo + g) * cols], w_hh + g * fo, cols * sizeof(float));
+    return f;
+}
+// floats between the [6 fo, fo] matrices of steps 1 .. (whole 16-byte pieces, as every tensor of the image)
+inline size_t ggnn_step_stride(size_t fo) { return (6 * fo * fo + 3) / 4 * 4; }
+
 constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_gat.h); one more with edge features (gnnb_gat_edge.h)
 constexpr int TF_PARAM_SLOTS = 8;  // a TransformerConv layer's canonical tensors (gnnb_transformer.h); one more with edge features
                                    // (gnnb_transformer_edge.h)
 constexpr int RG_PARAM_SLOTS = 8;  // a ResGatedGraphConv layer's canonical tensors (gnnb_resgated.h)
+constexpr int GGNN_PARAM_SLOTS = 5; // a GatedGraphConv layer's canonical tensors (gnnb_ggnn.h)
+constexpr int GGNN_MAX_STEPS = 8;
 constexpr int GAT1_PARAM_SLOTS = 4; // a GAT v1 layer's canonical tensors (gnnb_gatconv.h); two more with edge features (gnnb_gatconv_edge.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
 // their offsets in the image
 inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0,
-                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0)
+                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (ggnn_steps > 0) { // (a GIN description whose layers are GatedGraphConv's; canonical order: weight, rnn.weight_ih, rnn.weight_hh,
+                          // rnn.bias_ih, rnn.bias_hh; fi <= fo by gnnb_ggnn_model_create's check)
+        LayerOffsets g;
+        g.w_ggc = im.push(ggnn_fold(p[0], p[1], p[2], fo, fi));
+        if (ggnn_steps > 1) {
+            std::vector<float> next((size_t)(ggnn_steps - 1) * ggnn_step_stride(fo), 0.0f);
+            for (int t = 1; t < ggnn_steps; t++) {
+                const std::vector<float> f = ggnn_fold(p[0] + (size_t)t * fo * fo, p[1], p[2], fo, fo);
+                memcpy(&next[(size_t)(t - 1) * ggnn_step_stride(fo)], f.data(), f.size() * sizeof(float));
+            }
+            g.w_ggc_next = im.push(next);
+        }
+        std::vector<float> b(6 * fo, 0.0f);
+        memcpy(&b[3 * fo], p[4], 3 * fo * sizeof(float));
+        g.b_ggc = im.push(b);
+        g.b_ih = im.push(p[3], 3 * fo);
+        return g;
+    }
     if (gat1_heads > 0) { // (a GCN description whose layers are GAT v1's; canonical order: lin.weight, att_src, att_dst, bias)
         LayerOffsets g;
         g.w_gat = im.push(gat_score_fold(p[0], p[1], p[2], fi, fo, (size_t)gat1_heads));
@@ -619,26 +672,28 @@ struct BuiltWeights {
 // description, eight tensors per layer; no execution-order copy either); with edge_dim > 0 besides, ResGatedGraphConv with edge
 // features (the same eight, three of them [out, in + edge_dim]).  gat1_heads > 0: a GAT v1 model (a GCN description, four tensors
 // per layer; no fragment copy -- it takes no stack kernel); with edge_dim > 0 besides, GAT v1 with edge features (six tensors per
-// layer).
+// layer).  ggnn_steps > 0: a GatedGraphConv model (a GIN description, five tensors per layer; no execution-order copy).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
-                                       int tf_heads = 0, bool gated = false, int gat1_heads = 0)
+                                       int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = gat1_heads > 0  ? GAT1_PARAM_SLOTS + (edge_dim ? 2 : 0)
+    const int slots = ggnn_steps > 0  ? GGNN_PARAM_SLOTS
+                      : gat1_heads > 0 ? GAT1_PARAM_SLOTS + (edge_dim ? 2 : 0)
                       : gated         ? RG_PARAM_SLOTS
                       : tf_heads > 0  ? TF_PARAM_SLOTS + (edge_dim ? 1 : 0)
                       : gat_heads > 0 ? GAT_PARAM_SLOTS + (edge_dim ? 1 : 0)
                                       : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;
     for (int l = 0; l < d.num_layers; l++, pi += slots)
-        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads);
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps);
     const bool have_w1f = gat_heads == 0 && gat1_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));
-    // (a GINE model, a TransformerConv model, a ResGatedGraphConv model take no stack kernel: no execution-order copy)
-    const bool have_gin = edge_dim == 0 && tf_heads == 0 && !gated && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
+    // (a GINE model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model take no stack kernel: no
+    // execution-order copy)
+    const bool have_gin = edge_dim == 0 && tf_heads == 0 && !gated && ggnn_steps == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
                           d.out_dim <= d.hidden_dim && d.out_dim % 4 == 0;
     if (have_gin) {
         const WeightBias g = gin_execution_order(d, im.img, lo.conv);

@@ -883,6 +883,71 @@ class ResGatedGraphEConv_GNNB(nn.Module):
         return self.conv(x, edge_index, edge_attr)
 
 
+# --------------------------------------------------------------------------------------- GatedGraphConv
+class _GatedGraphConv(nn.Module):
+    """PyG's ``GatedGraphConv(out_channels, num_layers, aggr='add', bias=True)`` -- the Gated Graph Neural Network of Li et al.,
+    the update function of Gilmer's MPNN family; the one layer whose update is recurrent::
+
+        h = [x | 0]                              x [N, in] padded with zero columns to out; in > out: ValueError
+        for t in 0 .. num_layers - 1:
+            m_i = sum_j (h_j @ weight[t])        weight [num_layers, out, out], a plain matmul; j in N(i), the input's edges
+            h   = rnn(m, h)                      ONE torch.nn.GRUCell(out, out), shared by all steps
+
+    No self loop is added and none is removed: an explicit ``(v, v)`` edge is an ordinary edge, duplicate edges count as often
+    as they occur, a node without in-edges gets ``rnn(0, h_i)``.  Parameters with PyG's ``state_dict`` names and shapes --
+    ``weight``, ``rnn.weight_ih``, ``rnn.weight_hh`` [3 out, out], ``rnn.bias_ih``, ``rnn.bias_hh`` [3 out] --, initialised as
+    PyG does (``weight`` uniform in +- 1 / sqrt(out), the cell torch's default).  Out of scope: ``aggr`` other than add,
+    ``bias=False``, ``edge_weight``."""
+
+    def __init__(self, in_channels: int, out_channels: int, num_layers: int):
+        super().__init__()
+        if in_channels > out_channels:
+            raise ValueError(f"GatedGraphConv pads its input with zero columns up to out_channels: in_channels ({in_channels}) must not "
+                             f"exceed out_channels ({out_channels})")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.num_layers = num_layers
+        self.weight = nn.Parameter(torch.empty(num_layers, out_channels, out_channels))
+        self.rnn = nn.GRUCell(out_channels, out_channels, bias=True)
+        bound = 1.0 / math.sqrt(out_channels)
+        nn.init.uniform_(self.weight, -bound, bound)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        if x.size(-1) > self.out_channels:
+            raise ValueError("The number of input channels is not allowed to be larger than the number of output channels")
+        src, dst = edge_index[0].long(), edge_index[1].long()
+        h = x
+        if h.size(-1) < self.out_channels:
+            h = torch.cat([h, h.new_zeros(h.size(0), self.out_channels - h.size(-1))], dim=1)
+        for t in range(self.num_layers):
+            m = torch.matmul(h, self.weight[t])
+            m = torch.zeros_like(m).index_add(0, dst, m[src])
+            h = self.rnn(m, h)
+        return h
+
+
+class GatedGraphConv_GNNB(nn.Module):
+    """The gated graph conv (no class of the reference): PyG's ``GatedGraphConv(out_channels, num_layers=steps)``.
+    ``GNNModel(..., gnn_conv=GatedGraphConv_GNNB, gnn_steps=T)`` stacks it (``T`` in 1 .. 8 steps per layer, every layer's input
+    at most as wide as its output); ``forward(x, edge_index)``.  The accelerated path is ``runtime.CompiledModel.from_model`` with
+    the ordinary ``forward`` / ``forward_pyg`` (C ABI ``include/gnnb_ggnn.h``: per step one GEMM ``h -> [p | gh]`` on the message
+    weight folded into the GRU's input weight and one launch of csrc/k_ggnn.hip, the whole GRU cell in the aggregate's epilogue).
+    This class ignores ``graph_input_edge_dim`` and ``edge_attr``; ``aggr`` other than add, ``bias=False`` and ``edge_weight``
+    are out of scope.  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, steps: int = 1, p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.steps = steps
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _GatedGraphConv(in_channels, out_channels, steps)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        return self.conv(x, edge_index)
+
+
 # --------------------------------------------------------------------------------------- pooling / MLP
 SUPPORTED_GLOBAL_POOLING_AGGRS = {"add": "SumAggregation", "max": "MaxAggregation", "mean": "MeanAggregation"}
 SUPPORTED_GLOBAL_POOLING_MODE = ["cat"]
@@ -995,11 +1060,11 @@ class MLP(nn.Module):
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
                        GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB,
-                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB]
+                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB, GatedGraphConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
               PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
               TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated", ResGatedGraphEConv_GNNB: "resgatede",
-              GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate"}
+              GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate", GatedGraphConv_GNNB: "ggnn"}
 # convs that take edge_attr, and what the messages call them
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE",
                ResGatedGraphEConv_GNNB: "ResGatedE", GATv1EConv_GNNB: "GATE"}
@@ -1008,6 +1073,7 @@ _GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # the GATv2 convs (heads and neg
 _TF_CONVS = (TransformerConv_GNNB, TransformerEConv_GNNB)  # the TransformerConv convs (heads travel beside a GIN description)
 _GAT1_CONVS = (GATv1Conv_GNNB, GATv1EConv_GNNB)  # PyG's GATConv (heads and negative_slope travel beside a GCN description: include/gnnb_gatconv.h, gnnb_gatconv_edge.h)
 _HEAD_CONVS = _GAT_CONVS + _TF_CONVS + _GAT1_CONVS  # convs with attention heads: the ones that take gnn_heads
+MAX_GGNN_STEPS = 8  # of a GatedGraphConv model (include/gnnb_ggnn.h): steps per layer, beside a GIN description
 
 
 class GNNModel(nn.Module):
@@ -1019,7 +1085,7 @@ class GNNModel(nn.Module):
                  gnn_conv: TorchModuleArg, gnn_activation: TorchModuleArg, gnn_skip_connection: bool,
                  global_pooling: GlobalPooling, mlp_head: MLP,
                  output_activation: TorchModuleArgOptional, gnn_p_in: int = 1, gnn_p_hidden: int = 1,
-                 gnn_p_out: int = 1, gnn_heads: int = 1) -> None:
+                 gnn_p_out: int = 1, gnn_heads: int = 1, gnn_steps: int = 1) -> None:
         super().__init__()
         self.graph_input_feature_dim = graph_input_feature_dim
         self.graph_input_edge_dim = graph_input_edge_dim
@@ -1054,6 +1120,20 @@ class GNNModel(nn.Module):
             conv_kwargs = {**conv_kwargs, "heads": gnn_heads}  # (GATv2E, TransformerE, GATE: edge_dim from above stays)
         elif gnn_heads != 1:
             raise ValueError(f"gnn_heads={gnn_heads!r}: only a GATv2 model (gnn_conv=GATv2Conv_GNNB) has attention heads")
+
+        self.gnn_steps = gnn_steps
+        if self.gnn_conv is GatedGraphConv_GNNB:
+            if not isinstance(gnn_steps, int) or isinstance(gnn_steps, bool) or not 1 <= gnn_steps <= MAX_GGNN_STEPS:
+                raise ValueError(f"a GatedGraphConv model needs gnn_steps, an int in 1 .. {MAX_GGNN_STEPS} (got {gnn_steps!r})")
+            # (h_0 = [x | 0]: a layer pads its input with zero columns and cannot narrow it)
+            chain = ([graph_input_feature_dim, gnn_output_dim] if gnn_num_layers == 1 else
+                     [graph_input_feature_dim, gnn_hidden_dim, gnn_output_dim] if gnn_num_layers >= 2 else [])
+            if any(a > b for a, b in zip(chain, chain[1:])):
+                raise ValueError(f"a GatedGraphConv layer's input must not be wider than its output: graph_input_feature_dim <= "
+                                 f"gnn_hidden_dim <= gnn_output_dim is needed (got {chain})")
+            conv_kwargs = {**conv_kwargs, "steps": gnn_steps}
+        elif gnn_steps != 1:
+            raise ValueError(f"gnn_steps={gnn_steps!r}: only a GatedGraphConv model (gnn_conv=GatedGraphConv_GNNB) has steps")
 
         self.global_pooling = global_pooling
         self.mlp_head = mlp_head  # registered before gnn_convs: parameter order mlp_head_*, gnn_convs_*
@@ -1177,6 +1257,8 @@ class GNNModel(nn.Module):
             gat = {"heads": int(self.gnn_heads), "negative_slope": float(conv0.negative_slope) if conv0 is not None else 0.2}
         elif self.gnn_conv in _TF_CONVS:  # (a GIN description on the C side, heads beside it: include/gnnb_transformer.h, _edge.h)
             gat = {"heads": int(self.gnn_heads)}
+        elif self.gnn_conv is GatedGraphConv_GNNB:  # (a GIN description on the C side, steps beside it: include/gnnb_ggnn.h)
+            gat = {"steps": int(self.gnn_steps)}
         return {
             "conv": _CONV_NAME[self.gnn_conv],
             "num_layers": self.gnn_num_layers,
@@ -1224,6 +1306,8 @@ class GNNModel(nn.Module):
         per_conv["gat"] = ["conv_lin_weight", "conv_att_src", "conv_att_dst", "conv_bias"]  # (include/gnnb_gatconv.h)
         # (GAT v1's four, then att_edge [1, heads, out / heads] and lin_edge [out, edge_dim]: include/gnnb_gatconv_edge.h)
         per_conv["gate"] = per_conv["gat"] + ["conv_att_edge", "conv_lin_edge_weight"]
+        # (PyG's state_dict order: the per-step message weights [steps, out, out], then the one GRU cell: include/gnnb_ggnn.h)
+        per_conv["ggnn"] = ["conv_weight", "conv_rnn_weight_ih", "conv_rnn_weight_hh", "conv_rnn_bias_ih", "conv_rnn_bias_hh"]
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

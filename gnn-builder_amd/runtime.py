@@ -30,7 +30,7 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn"}  # spec["conv"] -> the conv its description carries, where that is another
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
 # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h,
 # "resgatede": gnnb_resgated_edge.h, "gate": gnnb_gatconv_edge.h)
 _EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede", "gate")
@@ -45,6 +45,8 @@ MAX_TRANSFORMER_HEADS, MAX_TRANSFORMER_WIDTH = 8, 256
 # a ResGatedGraphConv model (include/gnnb_resgated.h, spec["conv"] == "resgated"): its description is GIN's too, a "gated" mark beside it
 # ... with edge features ("resgatede", include/gnnb_resgated_edge.h): edge_dim beside it too
 MAX_RESGATED_WIDTH = 256
+# a GatedGraphConv model (include/gnnb_ggnn.h, spec["conv"] == "ggnn"): its description is GIN's too, steps per layer beside it
+MAX_GGNN_STEPS, MAX_GGNN_WIDTH = 8, 256
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -252,6 +254,15 @@ ABI_GATCONV_EDGE = {
 }
 
 
+# ... and of include/gnnb_ggnn.h (GatedGraphConv models), in its order (tests/test_abi_ggnn.py)
+ABI_GGNN = {
+    "gnnb_ggnn_model_num_params": (_I, [_DESC, _I]),
+    "gnnb_ggnn_model_create": (_I, [_DESC, _I, _PP, _I, _PP]),
+    "gnnb_model_ggnn_steps": (_I, [_P]),
+    "gnnb_aggregate_ggnn": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _I, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -297,7 +308,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
         for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER,
                                            **ABI_TRANSFORMER_EDGE, **ABI_RESGATED, **ABI_RESGATED_EDGE, **ABI_GATCONV,
-                                           **ABI_GATCONV_EDGE}.items():
+                                           **ABI_GATCONV_EDGE, **ABI_GGNN}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -445,6 +456,7 @@ class CompiledModel:
         self.gat_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _GAT_CONVS else 0
         self.transformer_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _TRANSFORMER_CONVS else 0
         self.gatconv_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _GATCONV_CONVS else 0
+        self.ggnn_steps = int(spec.get("steps", 1) or 0) if spec.get("conv") == "ggnn" else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
@@ -467,6 +479,7 @@ class CompiledModel:
                     self.lib.gnnb_transformer_model_num_params(C.byref(self.desc), self.transformer_heads) if spec.get("conv") == "transformer" else
                     self.lib.gnnb_resgated_model_num_params(C.byref(self.desc)) if spec.get("conv") == "resgated" else
                     self.lib.gnnb_gatconv_model_num_params(C.byref(self.desc), self.gatconv_heads) if spec.get("conv") == "gat" else
+                    self.lib.gnnb_ggnn_model_num_params(C.byref(self.desc), self.ggnn_steps) if spec.get("conv") == "ggnn" else
                     self.lib.gnnb_model_num_params(C.byref(self.desc)))
         if n_expect < 0:
             _check(n_expect)
@@ -496,6 +509,8 @@ class CompiledModel:
         elif spec.get("conv") == "gat":  # (gnnb_gatconv.h: a GCN description, heads and negative_slope beside it)
             _check(self.lib.gnnb_gatconv_model_create(C.byref(self.desc), self.gatconv_heads, float(spec.get("negative_slope", 0.2)), arr,
                                                       len(host), C.byref(self._model)))
+        elif spec.get("conv") == "ggnn":  # (gnnb_ggnn.h: a GIN description, steps beside it)
+            _check(self.lib.gnnb_ggnn_model_create(C.byref(self.desc), self.ggnn_steps, arr, len(host), C.byref(self._model)))
         else:
             _check(self.lib.gnnb_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
         rc = self.lib.gnnb_workspace_create(self._model, self.max_graphs, self.max_nodes, self.max_edges, C.byref(self._ws))
@@ -1098,6 +1113,40 @@ class CompiledModel:
         _check(self.lib.gnnb_aggregate_resgated(self._ws, _dptr(k), ld(k), _dptr(q), ld(q), _dptr(v), ld(v), _optr(root),
                                                 ld(root) if root is not None else w, _optr(skip), ACT[act], _dptr(out), w,
                                                 _stream_ptr(stream)))
+        return out
+
+    def aggregate_ggnn(self, p, gh, h, b_ih=None, skip=None, act: str = "none", out=None, stream=None):
+        """One GatedGraphConv step behind its GEMM (``gnnb_aggregate_ggnn``, csrc/k_ggnn.hip) on the prepared batch of a workspace
+        whose tables keep explicit self loops (any but a GCN, GATv2 or GAT model's, which is refused): with ``acc = sum_j p_j`` over
+        ``j`` in ``N(i)`` as the batch holds it and ``gi = acc + b_ih``, per column ``r = sigmoid(gi_r + gh_r)``,
+        ``z = sigmoid(gi_z + gh_z)``, ``n = tanh(gi_n + r * gh_n)`` and ``act(n + z * (h - n) + skip)`` -> [N, width].  ``p`` and
+        ``gh`` [N, 3 width] in column blocks r | z | n (column slices of a wider matrix are fine -- the two halves of one
+        [N, 6 width] GEMM output: their row strides are passed on); ``h`` [N, h_width <= width], its missing columns taken as 0;
+        ``b_ih`` [3 width] contiguous or None; ``skip`` [N, width] contiguous or None; ``width`` <= 256."""
+        import torch
+        _require_strided(p, "p", self._N, 3)
+        if int(p.shape[1]) % 3:
+            raise GnnbError(f"p must be [{self._N}, 3 width], got {tuple(p.shape)}")
+        w = int(p.shape[1]) // 3
+        _require_strided(gh, "gh", self._N, 3 * w)
+        _require_strided(h, "h", self._N, 1)
+        hw = int(h.shape[1])
+        if int(gh.shape[1]) != 3 * w or gh.device != p.device or h.device != p.device or hw > w:
+            raise GnnbError(f"gh must be [{self._N}, {3 * w}] and h [{self._N}, <= {w}] on {p.device}, got {tuple(gh.shape)} on {gh.device} "
+                            f"and {tuple(h.shape)} on {h.device}")
+        if w > MAX_GGNN_WIDTH:
+            raise GnnbError(f"width {w}: a GatedGraphConv layer is at most {MAX_GGNN_WIDTH} wide")
+        if act not in ACT:
+            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        if b_ih is not None and (not isinstance(b_ih, torch.Tensor) or b_ih.dtype != torch.float32 or b_ih.device != p.device or
+                                 b_ih.dim() != 1 or b_ih.numel() != 3 * w or not b_ih.is_contiguous()):
+            raise GnnbError(f"b_ih must be a contiguous float32 [{3 * w}] on {p.device}")
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, p)
+        out = _out(out, self._N, w, p)
+        ld = lambda t: int(t.stride(0)) if self._N > 1 else int(t.shape[1])  # noqa: E731  (one row: any stride describes it)
+        _check(self.lib.gnnb_aggregate_ggnn(self._ws, _dptr(p), ld(p), _dptr(gh), ld(gh), _dptr(h), ld(h), hw, _optr(b_ih), _optr(skip),
+                                            ACT[act], _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def aggregate_resgated_edges(self, k, q, v, edge_attr, w_gate, w_value, root=None, skip=None, act: str = "none", out=None, stream=None):
