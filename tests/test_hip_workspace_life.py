@@ -86,8 +86,17 @@ def _stage_call(cm, family, c, dev, out):
     if family == "transformere":
         return cm.aggregate_transformer_edges(d("q"), d("k"), d("v"), d("qe"), d("edge_attr"), d("w_edge"), root=d("root"), heads=W.HEADS,
                                               scale=c["scale"], out=out)
-    assert family == "resgated", family
-    return cm.aggregate_resgated(d("k"), d("q"), d("v"), root=d("root"), out=out)
+    if family == "resgated":
+        return cm.aggregate_resgated(d("k"), d("q"), d("v"), root=d("root"), out=out)
+    if family == "resgatede":
+        return cm.aggregate_resgated_edges(d("k"), d("q"), d("v"), d("edge_attr"), d("w_gate"), d("w_value"), root=d("root"), out=out)
+    if family == "gat":
+        return cm.aggregate_gat(d("xl"), d("s_src"), d("s_dst"), bias=d("bias"), heads=W.HEADS, negative_slope=gatv2_util.SLOPE, out=out)
+    if family == "gate":
+        return cm.aggregate_gat_edges(d("xl"), d("s_src"), d("s_dst"), d("edge_attr"), d("a_edge"), bias=d("bias"), heads=W.HEADS,
+                                      negative_slope=gatv2_util.SLOPE, out=out)
+    assert family == "ggnn", family
+    return cm.aggregate_ggnn(d("p"), d("gh"), d("h"), b_ih=d("b_ih"), out=out)
 
 
 class Runner:
@@ -263,19 +272,35 @@ def _sizes_steps(family, hidden=32, layers=2, entries=None, stage=True):
     return model, steps
 
 
-@pytest.mark.parametrize("family", W.FAMILIES)
-def test_sizes_up_and_down(dev, family):
-    """Eight batches on one workspace sized for the maxima of the sequence, the entry point rotating with the step; step 8 is step
-    1 again and repeats its bits on the same object."""
-    model, steps = _sizes_steps(family)
+def _run_sizes(dev, family, hidden, label):
+    model, steps = _sizes_steps(family, hidden=hidden)
     _assert_pna_references_are_clear(family, model, steps)
     caps = W.capacities([s.batch for s in steps])
     long = Runner(family, model, caps, dev)
-    results = W.run_sequence(steps, _long(long), Fresh(family, model, caps, dev), References(family, model), _recorder(f"workspace_life/sizes/{family}"))
+    results = W.run_sequence(steps, _long(long), Fresh(family, model, caps, dev), References(family, model), _recorder(f"workspace_life/sizes/{label}"))
     # what ran: every step but the node-less one has an output, on the route the family has without a promise
     _assert_everything_ran(steps, results)
     assert {r["path"] for r in results if "path" in r} == {"layerwise"}  # (the route every family has without a promise)
     long.cm.check()
+    return steps
+
+
+@pytest.mark.parametrize("family", W.FAMILIES)
+def test_sizes_up_and_down(dev, family):
+    """Eight batches on one workspace sized for the maxima of the sequence, the entry point rotating with the step; step 8 is step
+    1 again and repeats its bits on the same object."""
+    _run_sizes(dev, family, 32, family)
+
+
+def test_sizes_up_and_down_ggnn_state_offset_moves(dev):
+    """GatedGraphConv at hidden 9 with three steps per layer: the second state buffer lies ``roundup4(9 N)`` floats into the
+    workspace's scratch, so with the sequence's node counts it moves from batch to batch, on and off a 16-byte boundary (which
+    form a step's kernel takes follows from it), and both state buffers are written and read in turn in memory that the batch
+    before carved differently.  The stage entry is the one of the test above, at width 32."""
+    counts = [b.num_nodes for b in W.family_sequence("ggnn", hidden=9)[1]]
+    assert len({(9 * n) % 4 for n in counts}) >= 3, counts  # (from the node counts alone, before anything runs)
+    steps = _run_sizes(dev, "ggnn", 9, "ggnn-h9")
+    assert [s.batch.num_nodes for s in steps] == counts
 
 
 # ---------------------------------------------------------------------------------------------------- b. routes and promises
@@ -411,7 +436,8 @@ class Pipeline:
         return res
 
 
-@pytest.mark.parametrize("family,hidden,promise,paths", [("gcn", 64, 64, {"stack_zf"}), ("transformer", 32, 64, {"layerwise"})])
+@pytest.mark.parametrize("family,hidden,promise,paths", [("gcn", 64, 64, {"stack_zf"}), ("transformer", 32, 64, {"layerwise"}),
+                                                         ("gat", 32, 64, {"layerwise"}), ("ggnn", 32, 64, {"layerwise"})])
 def test_two_alternating_workspaces(dev, family, hidden, promise, paths):
     """The sequence of a. through ``forward_prepared_prep_next`` under a promise of 64 nodes per graph -- with the hub batch's
     300-node graph left out (``edge_batch(..., hub=False)``): it would break the promise, and a malformed batch belongs to the
@@ -433,36 +459,59 @@ def test_two_alternating_workspaces(dev, family, hidden, promise, paths):
 
 
 # ---------------------------------------------------------------------------------------------------- d. a captured forward
-def test_a_captured_forward_between_unlike_eager_ones(dev):
-    """One layer-wise family (GraphSAGE), a single capture stream, no large segment: the graph has no parallel branches.  The
-    captured forward on batch A replays with A's eager bits after an eager forward on the hub batch has rewritten the workspace's
-    tables and activations; an eager forward on the reversed batch afterwards carries the fresh object's bits."""
-    family = "sage"
-    model, batches, _ = W.family_sequence(family)
+def _captured_between_unlike_eager_ones(dev, family, hidden=32):
+    """The captured forward on batch A replays with A's eager bits after an eager forward on the hub batch has rewritten the
+    workspace's tables, activations and scratch; an eager forward on the reversed batch afterwards carries the fresh object's
+    bits.  A single capture stream, no large segment: the graph has no parallel branches."""
+    model, batches, attrs = W.family_sequence(family, hidden=hidden)
+    edges = family in W.EDGE_FAMILIES
     a, hub, rev = batches[0], batches[2], batches[4]
     caps = W.capacities([a, hub, rev])
     long = Runner(family, model, caps, dev)
     cm = long.cm
     xa, cooa, nptra, eptra = to_dev(a, dev)
-    eager = cm.forward(xa, cooa, nptra, eptra).clone()  # (also the warm-up outside the capture: kernel attributes, caches)
+    ead = _t(attrs[0], dev) if edges else None  # (held alive beside x: the captured forward reads it at every replay)
+
+    def forward(**kw):
+        return cm.forward_edges(xa, ead, cooa, nptra, eptra, **kw) if edges else cm.forward(xa, cooa, nptra, eptra, **kw)
+    eager = forward().clone()  # (also the warm-up outside the capture: kernel attributes, caches)
     out = torch.zeros_like(eager)
     side, graph = torch.cuda.Stream(), torch.cuda.CUDAGraph()
     torch.cuda.synchronize()
     with torch.cuda.graph(graph, stream=side):  # (one stream, no parallel branches)
-        cm.forward(xa, cooa, nptra, eptra, out=out)
+        forward(out=out)
     torch.cuda.synchronize()
     fresh, refs = Fresh(family, model, caps, dev), References(family, model)
-    hub_step = W.Step("edge-batch", hub, "forward", tables=True, stage=W.stage_operands(family, hub, 1001))
-    rev_step = W.Step("qm9-96-reversed", rev, "forward", tables=True, stage=W.stage_operands(family, rev, 1002))
-    W.run_sequence([hub_step], _long(long), fresh, refs, _recorder("workspace_life/captured/sage"))
+    hub_step = W.Step("edge-batch", hub, "forward", edge_attr=attrs[2], tables=True, stage=W.stage_operands(family, hub, 1001))
+    rev_step = W.Step("qm9-96-reversed", rev, "forward", edge_attr=attrs[4], tables=True, stage=W.stage_operands(family, rev, 1002))
+    W.run_sequence([hub_step], _long(long), fresh, refs, _recorder(f"workspace_life/captured/{family}"))
     out.zero_()
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(out, eager)  # (the replay prepares A again: the hub batch's tables are gone, A's bits are back)
-    ref, base = W.model_refs(family, model, a, None)
+    ref, base = W.model_refs(family, model, a, attrs[0])
     R.budget(_host(out), ref, base, what="replay of A")
-    W.run_sequence([rev_step], _long(long), fresh, refs, _recorder("workspace_life/captured/sage"))
+    W.run_sequence([rev_step], _long(long), fresh, refs, _recorder(f"workspace_life/captured/{family}"))
     cm.check()
+
+
+def test_a_captured_forward_between_unlike_eager_ones(dev):
+    """One layer-wise family (GraphSAGE), a single capture stream, no large segment: the graph has no parallel branches.  The
+    captured forward on batch A replays with A's eager bits after an eager forward on the hub batch has rewritten the workspace's
+    tables and activations; an eager forward on the reversed batch afterwards carries the fresh object's bits."""
+    _captured_between_unlike_eager_ones(dev, "sage")
+
+
+@pytest.mark.parametrize("family", ["ggnn", "gate"])
+def test_a_captured_forward_between_unlike_eager_ones_of(dev, family):
+    """The test above (it keeps its name) for two of the newer families.  gate: the capture is of ``forward_edges``.  ggnn: three
+    steps per layer at hidden 9, where the captured graph has A's carve of the state buffers baked in -- the second one
+    ``roundup4(9 N)`` floats into the scratch -- and the eager forward of the hub batch in between carves the same memory for
+    another N, whose ``9 N`` has another remainder by 4."""
+    if family == "ggnn":
+        batches = W.family_sequence(family, hidden=9)[1]
+        assert (9 * batches[0].num_nodes) % 4 != (9 * batches[2].num_nodes) % 4  # (1742 and 489 nodes: 2 and 1)
+    _captured_between_unlike_eager_ones(dev, family, hidden=9 if family == "ggnn" else 32)
 
 
 # ---------------------------------------------------------------------------------------------------- e. setters behind graph_prep
@@ -559,7 +608,7 @@ def test_degree_promise_between_prep_and_forward(dev, first, then):
     R.budget(got["out"], ref, base, what=step.name)
 
 
-@pytest.mark.parametrize("family", ["gine", "transformere"])
+@pytest.mark.parametrize("family", ["gine", "transformere", "gate", "resgatede"])
 def test_setters_between_prep_and_forward_edges(dev, family):
     """``forward_prepared_edges`` goes through the same body: every setter between ``graph_prep`` and it leaves the route
     (``layerwise``) and the bits alone."""
@@ -574,4 +623,22 @@ def test_setters_between_prep_and_forward_edges(dev, family):
     W.assert_same_bits(got, want, "prepared forward against a fresh object")
     assert got["path"] == "layerwise"
     ref, base = W.model_refs(family, model, b, ea)
+    R.budget(got["out"], ref, base, what=family)
+
+
+@pytest.mark.parametrize("family", ["gat", "ggnn"])
+def test_setters_between_prep_and_forward_plain(dev, family):
+    """The plain twin: every setter between ``graph_prep`` and ``forward_prepared`` leaves the route (``layerwise``), the tables and
+    the bits alone."""
+    model, batches, _ = W.family_sequence(family)
+    b = batches[6]
+    caps = W.capacities([b])
+    step = W.Step("molhiv-40", b, "forward_prepared", tables=True)
+    half = (b.num_graphs // 2, int(b.node_ptr[b.num_graphs // 2]), int(b.edge_ptr[b.num_graphs // 2]))
+    between = (("set_max_graph_nodes", (64,)), ("set_max_degree", (15,)), ("set_large_segment", half))
+    got = _prepared_forward(Runner(family, model, caps, dev, addons=False), step, between, "forward_prepared")
+    want = Runner(family, model, caps, dev, addons=False).run(step, entry="forward")
+    W.assert_same_bits(got, want, "prepared forward against a fresh object")
+    assert got["path"] == "layerwise"
+    ref, base = W.model_refs(family, model, b, None)
     R.budget(got["out"], ref, base, what=family)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import ggnn_util
 import gine_util
 import pnae_util
 import ref64 as R
@@ -192,3 +193,76 @@ def test_the_pna_sequences_stay_clear_of_the_std_threshold(family):
     model, batches, attrs = W.family_sequence(family)
     for b, ea in zip(batches, attrs):
         assert W.variances_near_the_threshold(model, b, b.x, ea) == 0
+
+
+# ---------------------------------------------------------------------------------------------------- the four newer families
+NEWER = ("resgatede", "gat", "gate", "ggnn")
+
+
+@pytest.fixture(scope="module")
+def newer_sequences():
+    return {f: W.family_sequence(f) for f in NEWER}
+
+
+@pytest.mark.parametrize("family", NEWER)
+def test_the_newer_families_sequences_build(newer_sequences, family):
+    assert family in W.FAMILIES and (family in W.EDGE_FAMILIES) == (family in ("resgatede", "gate"))
+    model, batches, attrs = newer_sequences[family]
+    assert len(batches) == len(attrs) == len(W.SIZES_UP_AND_DOWN) and batches[7] is batches[0]
+    for b, ea in zip(batches, attrs):
+        if family in W.EDGE_FAMILIES and b.num_edges:
+            assert ea.shape == (b.num_edges, W.EDGE_DIM) and ea.dtype == np.float32
+        else:
+            assert ea is None
+    if family == "ggnn":  # (three steps per layer: both state buffers are written and read in turn)
+        assert W.GGNN_STEPS == 3 and all(c.conv.num_layers == 3 for c in model.gnn_convs)
+
+
+@pytest.mark.parametrize("family", NEWER)
+def test_the_newer_families_stage_cases_hold_on_every_batch(newer_sequences, family):
+    """``stage_operands`` and ``stage_refs`` on all eight batches, the hub's 1200 in-edges among them: the reference-only asserts
+    of ``stage_refs`` hold (exact scores, gate arguments, gated values, neighbour sums), and the fp32 restatement stays within
+    the budget of the float64 one in every in-degree class -- a condition on the inputs fails here, long before a GPU run."""
+    _, batches, _ = newer_sequences[family]
+    for i, b in enumerate(batches):
+        c = W.stage_operands(family, b, 700 + i)
+        if family in W.EDGE_FAMILIES:
+            assert c["edge_attr"].shape == (b.num_edges, W.EDGE_DIM)
+        if family == "ggnn":
+            assert c["h"].shape == (b.num_nodes, W.GGNN_H_WIDTH) and W.GGNN_H_WIDTH < W.STAGE_W
+        ref, base, coo = W.stage_refs(family, b, c)
+        assert ref.shape == base.shape == (b.num_nodes, W.STAGE_W) and ref.dtype == np.float64 and base.dtype == np.float32
+        if b.num_nodes:
+            gine_util.budget_by_degree(base, ref, base, coo, what=f"{family} {W.SIZES_UP_AND_DOWN[i]}")
+
+
+@pytest.mark.parametrize("family", NEWER)
+def test_the_newer_families_model_references_pair_up(newer_sequences, family):
+    model, batches, attrs = newer_sequences[family]
+    for i in (0, 1, 2, 3, 6):  # (one of each kind of batch: molecules, one node, the hub batch, lone nodes, larger molecules)
+        ref, base = W.model_refs(family, model, batches[i], attrs[i])
+        assert ref.dtype == np.float64 and base.dtype == np.float32 and ref.shape == base.shape == (batches[i].num_graphs, 19)
+        R.budget(base, ref, base, what=f"{family} {W.SIZES_UP_AND_DOWN[i]}")
+
+
+def test_the_ggnn_state_offset_moves_along_the_sequence():
+    """At hidden 9 the second state buffer lies ``roundup4(9 N)`` floats into the scratch: over the sequence ``9 N mod 4`` takes at
+    least three values, and the captured batch's differs from the hub batch's."""
+    counts = [b.num_nodes for b in W.family_sequence("ggnn", hidden=9)[1]]
+    assert counts == [1742, 1, 489, 64, 1742, 0, 1051, 1742]
+    assert len({(9 * n) % 4 for n in counts}) >= 3
+    assert ((9 * counts[0]) % 4, (9 * counts[2]) % 4) == (2, 1)
+
+
+@pytest.mark.parametrize("fault", ggnn_util.FAULTS)
+def test_the_stage_comparison_rejects_a_wrong_gru(newer_sequences, fault):
+    """A wrong kernel restated in fp32 (``ggnn_util.FAULTS``) in the place of ``got`` on the ``edge-batch`` step, at ``h_width`` 12:
+    ``stage_refs``' comparison rejects it in at least one in-degree class, and takes the right one."""
+    b = newer_sequences["ggnn"][1][2]
+    c = W.stage_operands("ggnn", b, 702)
+    ref, base, coo = W.stage_refs("ggnn", b, c)
+    gine_util.budget_by_degree(base, ref, base, coo, what="the right GRU")
+    wrong = ggnn_util.ggnn_ref(c["p"], c["gh"], c["h"], c["b_ih"], None, "none", b.coo, dtype=np.float32, fault=fault)
+    assert wrong.dtype == np.float32 and wrong.shape == base.shape
+    with pytest.raises(AssertionError):
+        gine_util.budget_by_degree(wrong, ref, base, coo, what=fault)

@@ -206,22 +206,31 @@ def variances_near_the_threshold(model, batch, x, edge_attr=None):
 
 
 # ---------------------------------------------------------------------------------------------------- one model per family
-FAMILIES = ("gcn", "gin", "sage", "pna", "gine", "pnae", "gatv2", "gatv2e", "transformer", "transformere", "resgated")
-EDGE_FAMILIES = ("gine", "pnae", "gatv2e", "transformere")
+FAMILIES = ("gcn", "gin", "sage", "pna", "gine", "pnae", "gatv2", "gatv2e", "transformer", "transformere", "resgated", "resgatede", "gat",
+            "gate", "ggnn")
+EDGE_FAMILIES = ("gine", "pnae", "gatv2e", "transformere", "resgatede", "gate")
+GGNN_STEPS, GGNN_H_WIDTH = 3, 12  # three steps: both state buffers are written and read in turn; the stage's h narrower than its width
 IN_DIM, EDGE_DIM, HEADS = 9, 3, 4
 
 
-def make_family_model(family, hidden=32, layers=2, seed=0):
-    """The family's model from its existing maker: ``in_dim`` 9, all three pools, 4 heads where there are heads, ``edge_dim`` 3."""
+def make_family_model(family, hidden=32, layers=2, seed=0, out_dim=None):
+    """The family's model from its existing maker: ``in_dim`` 9, all three pools, 4 heads where there are heads, ``edge_dim`` 3,
+    ``GGNN_STEPS`` steps per GatedGraphConv layer; ``out_dim``: the last layer's width (None: ``hidden``)."""
+    import gat_util
+    import gate_util
     import gatv2_util
     import gatv2e_util
     import gine_util
     import pnae_util
+    import ggnn_util
     import resgated_util
+    import resgatede_util
     import transformer_util
     import transformere_util
     from helpers import make_model
     kw = dict(in_dim=IN_DIM, hidden=hidden, layers=layers, seed=seed)
+    if out_dim is not None:
+        kw["out_dim"] = out_dim
     if family in ("gcn", "gin", "sage", "pna"):
         return make_model(family, **kw)
     if family == "gine":
@@ -236,8 +245,16 @@ def make_family_model(family, hidden=32, layers=2, seed=0):
         return transformer_util.make_transformer_model(heads=HEADS, **kw)
     if family == "transformere":
         return transformere_util.make_transformere_model(edge_dim=EDGE_DIM, heads=HEADS, **kw)
-    assert family == "resgated", family
-    return resgated_util.make_resgated_model(**kw)
+    if family == "resgated":
+        return resgated_util.make_resgated_model(**kw)
+    if family == "resgatede":
+        return resgatede_util.make_resgatede_model(edge_dim=EDGE_DIM, **kw)
+    if family == "gat":
+        return gat_util.make_gat_model(heads=HEADS, **kw)
+    if family == "gate":
+        return gate_util.make_gate_model(edge_dim=EDGE_DIM, heads=HEADS, **kw)
+    assert family == "ggnn", family
+    return ggnn_util.make_ggnn_model(steps=GGNN_STEPS, **kw)
 
 
 # Seeds of the pna / pnae sequences, chosen on the CPU (tests/test_workspace_life_driver.py asserts them): the model's seed, then
@@ -280,12 +297,17 @@ def _uniform(seed, shape, span=1.0):
 
 def stage_operands(family, batch, seed):
     """Fresh operands of width ``STAGE_W`` for the family's stage entry on ``batch`` (the batch as the tables hold it): uniform
-    for the plain aggregates, the family's own dyadic grids (its ``*_util.stage_case`` / ``edge_case``, "flat") for the others."""
+    for the plain aggregates, the family's own dyadic grids (its ``*_util.stage_case`` / ``edge_case``, "flat") for the others --
+    an edge family's ``edge_attr`` the one its helper made for this ``coo``."""
+    import gat_util
+    import gate_util
     import gatv2_util
     import gatv2e_util
     import gine_util
+    import ggnn_util
     import pnae_util
     import resgated_util
+    import resgatede_util
     import transformer_util
     import transformere_util
     n, e, w = batch.num_nodes, batch.num_edges, STAGE_W
@@ -306,18 +328,31 @@ def stage_operands(family, batch, seed):
         return transformer_util.stage_case(n, w, HEADS, "flat")
     if family == "transformere":
         return transformere_util.edge_case(batch.coo, n, w, HEADS, EDGE_DIM, "flat")
-    assert family == "resgated", family
-    return resgated_util.stage_case(n, w, "flat")
+    if family == "resgated":
+        return resgated_util.stage_case(n, w, "flat")
+    if family == "resgatede":
+        return resgatede_util.edge_case(batch.coo, n, w, EDGE_DIM, "flat")
+    if family == "gat":
+        return gat_util.stage_case(n, w, HEADS, "flat", seed=seed)
+    if family == "gate":
+        return gate_util.edge_case(batch.coo, n, w, HEADS, EDGE_DIM, "flat", seed=seed)
+    assert family == "ggnn", family
+    return ggnn_util.stage_case(n, w, GGNN_H_WIDTH, "flat")  # (h narrower than the stage: its zero-padded columns are exercised)
 
 
 def stage_refs(family, batch, c):
     """(float64 restatement, the same in fp32, the edges of the tables for the in-degree classes) of the family's stage entry on
     operands ``c``.  What a reference needs to hold for the comparison to leave nothing out is asserted here, on the reference
-    alone: no PNA variance near PyG's threshold."""
+    alone: no PNA variance near PyG's threshold; every non-self GAT score, every ResGated gate argument and gated value and every
+    GatedGraphConv neighbour sum and r and z argument exact in fp32."""
+    import gat_util
+    import gate_util
     import gatv2_util
     import gatv2e_util
+    import ggnn_util
     import pnae_util
     import resgated_util
+    import resgatede_util
     import transformer_util
     import transformere_util
     coo, n = batch.coo, batch.num_nodes
@@ -358,9 +393,28 @@ def stage_refs(family, batch, c):
     if family == "transformere":
         args = (c["q"], c["k"], c["v"], c["qe"], c["root"], None, "none", coo, c["edge_attr"], c["w_edge"], HEADS, c["scale"])
         return transformere_util.transformere_ref(*args), transformere_util.transformere_ref(*args, dtype=f4), coo
-    assert family == "resgated", family
-    args = (c["k"], c["q"], c["v"], c["root"], None, "none", coo)
-    return resgated_util.resgated_ref(*args), resgated_util.resgated_ref(*args, dtype=f4), coo
+    if family == "gate" and batch.num_edges == 0:  # (no attribute row: every self loop's mean attribute is 0 -- GAT on self loops)
+        family = "gat"
+    if family == "resgatede" and batch.num_edges == 0:  # (no edge: no gate and no value -- ResGatedGraphConv without a neighbour)
+        family = "resgated"
+    if family == "resgated":
+        args = (c["k"], c["q"], c["v"], c["root"], None, "none", coo)
+        return resgated_util.resgated_ref(*args), resgated_util.resgated_ref(*args, dtype=f4), coo
+    if family == "resgatede":
+        resgatede_util.assert_exact_terms(c, coo)
+        args = (c["k"], c["q"], c["v"], c["root"], None, "none", coo, c["edge_attr"], c["w_gate"], c["w_value"])
+        return resgatede_util.resgatede_ref(*args), resgatede_util.resgatede_ref(*args, dtype=f4), coo
+    if family == "gat":  # (a GAT workspace is a GCN description too: explicit self loops dropped, as gat_ref drops them)
+        args = (c["xl"], c["s_src"], c["s_dst"], c["bias"], None, "none", coo, HEADS, gat_util.SLOPE)
+        return gat_util.gat_ref(*args), gat_util.gat_ref(*args, dtype=f4), R.workspace_edges(coo, True)
+    if family == "gate":
+        gate_util.assert_exact_scores(c, coo, "flat")
+        args = (c["xl"], c["s_src"], c["s_dst"], c["a_edge"], c["bias"], None, "none", coo, c["edge_attr"], HEADS, gate_util.SLOPE)
+        return gate_util.gate_ref(*args, fill="mean"), gate_util.gate_ref(*args, dtype=f4, fill="mean"), R.workspace_edges(coo, True)
+    assert family == "ggnn", family
+    ggnn_util.arguments_are_exact(c, coo)
+    args = (c["p"], c["gh"], c["h"], c["b_ih"], None, "none", coo)
+    return ggnn_util.ggnn_ref(*args), ggnn_util.ggnn_ref(*args, dtype=f4), coo
 
 
 # ---------------------------------------------------------------------------------------------------- the CPU stand-ins
