@@ -118,7 +118,7 @@ def pack_graphs(graphs: Sequence[Tuple[np.ndarray, np.ndarray]], layout: str = "
     )
 
 
-def from_pyg_batch(x, edge_index, batch=None, ptr=None, num_graphs=None, edge_attr=None, return_edge_order=False):
+def from_pyg_batch(x, edge_index, batch=None, ptr=None, num_graphs=None, edge_attr=None, return_edge_order=False, edge_type=None):
     """Adapter for a PyG-style mini-batch (``torch_geometric.data.Batch`` attributes, passed as arrays
     or tensors so that PyG itself is not needed): ``x`` [N, F], ``edge_index`` [2, E] with batch-global
     node ids, and either ``batch`` [N] (graph id of every node, non-decreasing -- what ``Batch.batch``
@@ -130,13 +130,16 @@ def from_pyg_batch(x, edge_index, batch=None, ptr=None, num_graphs=None, edge_at
     ``edge_attr`` [E, d] (``Batch.edge_attr``, a GINE model's edge features): the rows follow their edges through the same
     stable order, and the call returns ``(GraphBatch, edge_attr_ord)`` with ``edge_attr_ord[i]`` the attributes of ``coo`` row
     ``i``.  ``return_edge_order=True`` appends the order itself (int64 [E]: ``coo`` row ``i`` is input edge ``order[i]``).
-    Without either the call returns the ``GraphBatch`` alone.
+    ``edge_type`` [E] (``Batch.edge_type``, an RGCNConv model's integer edge types): the types follow their edges likewise and
+    the call returns ``edge_type_ord`` (int32 [E], the type of ``coo`` row ``i`` -- what ``CompiledModel.forward_types`` takes)
+    behind ``edge_attr_ord`` and in front of the order.  Without any of the three the call returns the ``GraphBatch`` alone.
 
     This is the HOST form (numpy).  A mini-batch that already lives on the GPU goes through the device form instead, which
     returns the same three index arrays without a copy to the host or a synchronisation:
     ``runtime.CompiledModel.ingest_pyg`` / ``forward_pyg`` (``gnnb_ingest_pyg``, csrc/k_ingest.hip); with the oversized graphs
     ordered last as well (``order_large_last`` below): ``ingest_pyg_ordered`` / ``forward_pyg_ordered`` (csrc/k_order.hip); with
-    edge attributes: ``ingest_pyg_edges`` / ``forward_pyg_edges`` (``gnnb_ingest_pyg_edges``, csrc/k_ingest.hip)."""
+    edge attributes: ``ingest_pyg_edges`` / ``forward_pyg_edges`` (``gnnb_ingest_pyg_edges``, csrc/k_ingest.hip); with edge types:
+    ``ingest_pyg_types`` / ``forward_pyg_types`` (``gnnb_ingest_pyg_types``, csrc/k_ingest.hip)."""
     x = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
     ei = np.asarray(edge_index)
     if ei.ndim != 2 or ei.shape[0] != 2:
@@ -174,7 +177,7 @@ def from_pyg_batch(x, edge_index, batch=None, ptr=None, num_graphs=None, edge_at
     np.add.at(edge_ptr, g_dst + 1, 1)
     np.cumsum(edge_ptr, out=edge_ptr)
     gb = GraphBatch(x=x, coo=coo.reshape(-1, 2), node_ptr=node_ptr.astype(np.int32), edge_ptr=edge_ptr.astype(np.int32))
-    if edge_attr is None and not return_edge_order:
+    if edge_attr is None and edge_type is None and not return_edge_order:
         return gb
     res = (gb,)
     if edge_attr is not None:
@@ -182,6 +185,14 @@ def from_pyg_batch(x, edge_index, batch=None, ptr=None, num_graphs=None, edge_at
         if ea.ndim != 2 or ea.shape[0] != ei.shape[1]:
             raise ValueError("edge_attr must be [E, d]: one row per column of edge_index")
         res += (np.ascontiguousarray(ea[order]),)
+    if edge_type is not None:
+        et = np.asarray(edge_type)
+        if et.ndim != 1 or et.shape[0] != ei.shape[1] or et.dtype.kind not in "iu":
+            raise ValueError("edge_type must be [E] integers: one type per column of edge_index")
+        et = et.astype(np.int64)
+        if et.size and (et.min() < -2**31 or et.max() >= 2**31):
+            raise ValueError("edge_type does not fit an int32")
+        res += (np.ascontiguousarray(et[order].astype(np.int32)),)
     if return_edge_order:
         res += (order.astype(np.int64),)
     return res

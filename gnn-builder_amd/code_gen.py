@@ -28,7 +28,7 @@ import jinja2
 import numpy as np
 import torch
 
-from .models import (GATv1Conv_GNNB, GATv1EConv_GNNB, GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, GatedGraphConv_GNNB, PNAEConv_GNNB, ResGatedGraphConv_GNNB,
+from .models import (GATv1Conv_GNNB, GATv1EConv_GNNB, GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, GatedGraphConv_GNNB, PNAEConv_GNNB, RGCNConv_GNNB, ResGatedGraphConv_GNNB,
                      ResGatedGraphEConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB)
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
@@ -141,6 +141,10 @@ class Project:
             raise NotImplementedError(
                 "Project does not generate GatedGraphConv designs: the generated shim and the templates have no recurrent layer; run "
                 "the model through runtime.CompiledModel.from_model(model, ...).forward / forward_pyg")
+        if getattr(model, "gnn_conv", None) is RGCNConv_GNNB:
+            raise NotImplementedError(
+                "Project does not generate RGCNConv designs: the generated shim and the templates have no relational layer and carry "
+                "no edge types; run the model through runtime.CompiledModel.from_model(model, ...).forward_types / forward_pyg_types")
         self.model = model
         self.dataset = dataset
         self.name = name

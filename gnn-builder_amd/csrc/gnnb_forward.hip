@@ -76,8 +76,9 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     g.nl = 0;
     const int L = d.num_layers;
     // a GINE model: no stack kernel forms the edge term; a GATv2 model, a GAT v1 model, a TransformerConv model: none forms
-    // attention; a ResGatedGraphConv model: none forms the gate; a GatedGraphConv model: none forms the GRU cell
-    if (model->edge_dim || model->gat_heads || model->gat1_heads || model->tf_heads || model->gated || model->ggnn_steps)
+    // attention; a ResGatedGraphConv model: none forms the gate; a GatedGraphConv model: none forms the GRU cell; an RGCNConv
+    // model: none selects a weight by relation
+    if (model->edge_dim || model->gat_heads || model->gat1_heads || model->tf_heads || model->gated || model->ggnn_steps || model->rgcn_relations)
         return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
@@ -352,6 +353,25 @@ static int ggnn_layer(const LayerCtx &c)
     return GNNB_OK;
 }
 
+// RGCNConv (gnnb_rgcn.h; a GIN description with `relations` beside it, so the tables keep explicit (v, v) edges): ONE GEMM
+// x -> [p_0 | .. | p_{R-1} | root] [N, (R + 1) fo] on w_rgcn with the bias [0 | .. | 0 | bias] in the model's math mode -- the
+// per-relation transform is the GEMM's, the message is linear --, then ONE k_rgcn_aggregate launch on the slot records the _types
+// forward built into ws->rgcn_rec: one gathered row-width per edge, the skip term and the activation in its epilogue.  None of
+// the fused rungs
+static int rgcn_layer(const LayerCtx &c)
+{
+    const gnnb_model_desc &d = c.model->desc;
+    const LayerWeights &p = c.model->conv[c.l];
+    const int fi = c.fi, fo = c.fo, R = c.model->rgcn_relations, ld = rgcn_tmp_blocks(R) * fo;
+    float *pr = c.ws->tmp0; // ([max_nodes, >= (R + 1) fo]: gnnb_workspace_create)
+    int rc;
+    if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_rgcn, fi, p.b_rgcn, nullptr, c.rows(pr, ld), ld, GNNB_ACT_NONE)))
+        return rc;
+    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+        GNNB_HIP_TRY(launch_rgcn_aggregate(c.tv, c.ws->rgcn_rec, pr, ld, R, pr + (size_t)R * fo, ld, c.skip, d.activation, c.nxt, fo, c.hs()));
+    return GNNB_OK;
+}
+
 // GIN's first linear + ReLU on the eps-weighted sum -> ws->tmp0
 static int gin_hidden(const LayerCtx &c)
 {
@@ -530,7 +550,9 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
         switch (d.conv_type) {
         case GNNB_CONV_GCN: rc = model->gat_heads ? gat_layer(c) : model->gat1_heads ? gat1_layer(c) : gcn_layer(c); break;
         case GNNB_CONV_GIN:
-            rc = model->tf_heads ? transformer_layer(c) : model->gated ? resgated_layer(c) : model->ggnn_steps ? ggnn_layer(c) : gin_layer(c);
+            rc = model->tf_heads ? transformer_layer(c) : model->gated ? resgated_layer(c) : model->ggnn_steps ? ggnn_layer(c)
+                 : model->rgcn_relations                                                                                 ? rgcn_layer(c)
+                                                                                                                         : gin_layer(c);
             break;
         case GNNB_CONV_SAGE: rc = sage_layer(c); break;
         case GNNB_CONV_PNA: rc = pna_layer(c); break;
@@ -809,7 +831,7 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
     if (memcmp(&model->desc, &ws->desc, sizeof(gnnb_model_desc)) != 0 || model->edge_dim != ws->edge_dim ||
         model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope || model->gat1_heads != ws->gat1_heads ||
         model->tf_heads != ws->tf_heads || model->gated != ws->gated ||
-        model->ggnn_steps != ws->ggnn_steps)
+        model->ggnn_steps != ws->ggnn_steps || model->rgcn_relations != ws->rgcn_relations)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;
@@ -853,6 +875,8 @@ static int check_edge_forward(const gnnb_model *model, const gnnb_workspace *ws,
 {
     if (!model || !ws)
         return fail(GNNB_ERR_INVALID, "null argument to %s", entry);
+    if (const int rc = refuse_rgcn_model(model, ws, entry, strstr(entry, "prepared") ? "gnnb_forward_prepared_types" : "gnnb_forward_batched_types"))
+        return rc;
     if (!model->edge_dim)
         return fail(GNNB_ERR_INVALID, "%s takes a model of gnnb_edge_model_create; this one has no edge weights", entry);
     if (model->edge_dim != ws->edge_dim)
@@ -874,12 +898,68 @@ int gnnb::forward_batched_tail(const gnnb_model *model, gnnb_workspace *ws, cons
     return forward_prepared(model, ws, x_dev, edge_attr_dev, out_dev, stream);
 }
 
+// an RGCNConv model, its own workspace, and edge types for a batch of num_edges edges
+static int check_types_forward(const gnnb_model *model, const gnnb_workspace *ws, const int32_t *edge_type_dev, int num_edges, const char *entry)
+{
+    if (!model || !ws)
+        return fail(GNNB_ERR_INVALID, "null argument to %s", entry);
+    if (!model->rgcn_relations)
+        return fail(GNNB_ERR_INVALID, "%s takes a model of gnnb_rgcn_model_create; this one has no relations", entry);
+    if (model->rgcn_relations != ws->rgcn_relations || !ws->rgcn_rec)
+        return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
+    if (num_edges > 0 && !edge_type_dev)
+        return fail(GNNB_ERR_INVALID, "%s: edge_type_dev is NULL for a batch of %d edges", entry, num_edges);
+    return GNNB_OK;
+}
+
+// the slot records of the prepared batch into the workspace's own allocation, then the prepared forward (rgcn_layer reads them)
+static int forward_prepared_types(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int32_t *edge_type_dev, float *out_dev,
+                                  void *stream)
+{
+    if (!x_dev || !out_dev)
+        return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward");
+    if (!ws->prepared)
+        return fail(GNNB_ERR_INVALID, "workspace has no prepared batch");
+    GNNB_HIP_TRY(launch_rgcn_slots(ws->t, edge_type_dev, model->rgcn_relations, ws->rgcn_rec, (hipStream_t)stream));
+    return forward_prepared(model, ws, x_dev, nullptr, out_dev, stream);
+}
+
+int gnnb::forward_batched_types_tail(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int32_t *edge_type_dev,
+                                     const int32_t *coo_dev, const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev, int num_graphs,
+                                     int num_nodes, int num_edges, float *out_dev, void *stream, bool ingest_reported)
+{
+    if (const int rc = check_types_forward(model, ws, edge_type_dev, num_edges, "gnnb_forward_batched_types"))
+        return rc;
+    if (const int rc = graph_prep_impl(ws, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, model->desc.pna_delta, stream,
+                                       nullptr, ingest_reported))
+        return rc;
+    return forward_prepared_types(model, ws, x_dev, edge_type_dev, out_dev, stream);
+}
+
 extern "C" {
+
+int gnnb_forward_prepared_types(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int32_t *edge_type_dev, float *out_dev,
+                                void *stream)
+{
+    if (const int rc = check_types_forward(model, ws, edge_type_dev, ws && ws->prepared ? ws->t.num_edges : 0, "gnnb_forward_prepared_types"))
+        return rc;
+    return forward_prepared_types(model, ws, x_dev, edge_type_dev, out_dev, stream);
+}
+
+int gnnb_forward_batched_types(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int32_t *edge_type_dev,
+                               const int32_t *coo_dev, const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev, int num_graphs, int num_nodes,
+                               int num_edges, float *out_dev, void *stream)
+{
+    return forward_batched_types_tail(model, ws, x_dev, edge_type_dev, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, out_dev,
+                                      stream, false);
+}
 
 int gnnb_forward_prepared(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev,
                           float *out_dev, void *stream)
 {
     if (const int rc = refuse_edge_model(model, ws, "gnnb_forward_prepared", "gnnb_forward_prepared_edges"))
+        return rc;
+    if (const int rc = refuse_rgcn_model(model, ws, "gnnb_forward_prepared", "gnnb_forward_prepared_types"))
         return rc;
     return forward_prepared(model, ws, x_dev, nullptr, out_dev, stream);
 }
@@ -911,6 +991,8 @@ int gnnb_forward_batched(const gnnb_model *model, gnnb_workspace *ws, const floa
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_batched");
     if (const int erc = refuse_edge_model(model, ws, "gnnb_forward_batched", "gnnb_forward_batched_edges"))
         return erc;
+    if (const int erc = refuse_rgcn_model(model, ws, "gnnb_forward_batched", "gnnb_forward_batched_types"))
+        return erc;
     return forward_batched_tail(model, ws, x_dev, nullptr, coo_dev, node_ptr_dev, edge_ptr_dev, num_graphs, num_nodes, num_edges, out_dev, stream, false);
 }
 
@@ -926,6 +1008,10 @@ int gnnb_forward_prepared_prep_next(const gnnb_model *model, gnnb_workspace *ws,
     if (const int erc = refuse_edge_model(model, ws, "gnnb_forward_prepared_prep_next", "gnnb_forward_prepared_edges and gnnb_graph_prep"))
         return erc;
     if (const int erc = refuse_edge_model(nullptr, ws_next, "gnnb_forward_prepared_prep_next", "gnnb_forward_prepared_edges and gnnb_graph_prep"))
+        return erc;
+    if (const int erc = refuse_rgcn_model(model, ws, "gnnb_forward_prepared_prep_next", "gnnb_forward_prepared_types and gnnb_graph_prep"))
+        return erc;
+    if (const int erc = refuse_rgcn_model(nullptr, ws_next, "gnnb_forward_prepared_prep_next", "gnnb_forward_prepared_types and gnnb_graph_prep"))
         return erc;
     if (ws == ws_next)
         return fail(GNNB_ERR_INVALID, "gnnb_forward_prepared_prep_next: the next batch needs a workspace of its own (the forward reads "
@@ -969,6 +1055,8 @@ int gnnb_forward_batched_host(const gnnb_model *model, gnnb_workspace *ws, const
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_batched_host");
     if (const int erc = refuse_edge_model(model, ws, "gnnb_forward_batched_host", "gnnb_forward_batched_edges on device buffers"))
         return erc;
+    if (const int erc = refuse_rgcn_model(model, ws, "gnnb_forward_batched_host", "gnnb_forward_batched_types on device buffers"))
+        return erc;
     if (const int crc = check_batch_sizes(ws, num_graphs, num_nodes, num_edges))
         return crc;
     const gnnb_model_desc &d = model->desc;
@@ -1010,6 +1098,8 @@ int gnnb_gcn_stack_timed(const gnnb_model *model, gnnb_workspace *ws, const floa
     if (!model || !ws || !x_dev || iters < 1 || !out_us_per_launch)
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_gcn_stack_timed");
     if (const int erc = refuse_edge_model(model, ws, "gnnb_gcn_stack_timed", "gnnb_forward_prepared_edges: it runs layer by layer"))
+        return erc;
+    if (const int erc = refuse_rgcn_model(model, ws, "gnnb_gcn_stack_timed", "gnnb_forward_prepared_types: it runs layer by layer"))
         return erc;
     MathScope math_scope(model->desc.math, ws->t.err, ws->t.err_host_dev);
     if (!ws->prepared)

@@ -21,6 +21,7 @@
 #include "gnnb_resgated.h"
 #include "gnnb_resgated_edge.h"
 #include "gnnb_ggnn.h"
+#include "gnnb_rgcn.h"
 
 namespace gnnb {
 
@@ -68,6 +69,8 @@ struct gnnb_model {
                             // (gnnb_resgated_edge_model_create) -- w_kqvr of the x column blocks, b_kqvr and w_gv_edge [2 out, edge_dim]
     int ggnn_steps = 0;     // > 0: a GatedGraphConv model (gnnb_ggnn_model_create; desc is a GIN description) of that many steps per
                             // layer -- every layer has w_ggc, w_ggc_next (steps > 1), b_ggc, b_ih and none of GIN's slots
+    int rgcn_relations = 0; // > 0: an RGCNConv model (gnnb_rgcn_model_create; desc is a GIN description) of that many relations --
+                            // every layer has w_rgcn, b_rgcn and none of GIN's slots
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };
@@ -93,6 +96,10 @@ struct gnnb_workspace {
     int tf_heads = 0;            // ... and its heads when it is a TransformerConv model (0: it is not)
     int gated = 0;               // ... and 1 when it is a ResGatedGraphConv model
     int ggnn_steps = 0;          // ... and its steps when it is a GatedGraphConv model (0: it is not)
+    int rgcn_relations = 0;      // ... and its relations when it is an RGCNConv model (0: it is not)
+    gnnb::RgcnSlot *rgcn_rec = nullptr; // such a model's workspace only: the slot records of the batch (k_rgcn_slots), 8 max_edges bytes,
+                                 // rebuilt by every _types forward
+    char *type_blob = nullptr;   // gnnb_workspace_enable_type_ingest: edge_type in COO row order, int32 [max_edges], one allocation
     char *edge_blob = nullptr;   // gnnb_workspace_enable_edge_ingest: edge_attr in COO row order, [max_edges, edge_dim], one allocation
     char *order_blob = nullptr;  // gnnb_workspace_enable_ordered_ingest: the ordered batch and the staged outputs (order_place), one allocation
     int32_t *order_triple = nullptr, *order_triple_dev = nullptr; // host-mapped (first large graph, node row, edge row) of k_order_graphs, and
@@ -136,6 +143,9 @@ static_assert(GGNN_TMP_BLOCKS >= 6, "tmp0 holds [p | gh]: six column blocks of a
 static_assert(GGNN_TMP_BLOCKS >= 3, "tmp1 holds two [N, out] state buffers and up to 3 floats of alignment between them");
 inline size_t ggnn_state_offset(size_t num_nodes, size_t fo) { return (num_nodes * fo + 3) / 4 * 4; }
 
+// An RGCNConv workspace's scratch (gnnb_rgcn.h): tmp0 takes a layer's GEMM output [p_0 | .. | p_{R-1} | root] [N, (R + 1) out]
+inline int rgcn_tmp_blocks(int relations) { return relations + 1; }
+
 // the model's MLP head as the readout kernels take it (gnnb_model.hip): the ONLY place that fills a HeadArgs
 HeadArgs model_head_args(const gnnb_model *model);
 
@@ -157,6 +167,9 @@ int refuse_resgated_model(const gnnb_model *model, const gnnb_workspace *ws, con
 // ... and for a GatedGraphConv model / its workspace (gnnb_ggnn.h)
 int refuse_ggnn_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
 
+// ... and for an RGCNConv model / its workspace (gnnb_rgcn.h): `use` names the _types entry
+int refuse_rgcn_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
+
 // gnnb_runtime.hip, for the forward (gnnb_forward.hip) -- each is described where it is defined
 int ensure_gcoef(gnnb_workspace *ws, void *stream);
 int build_gemm(GemmArgs &g, const gnnb_gemm_seg *segs, int num_segs, const float *w, int ldw, int rows = 1);
@@ -177,6 +190,12 @@ BatchTables small_segment(const gnnb_workspace *ws);
 int forward_batched_tail(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev, const int32_t *coo_dev,
                          const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev, int num_graphs, int num_nodes, int num_edges,
                          float *out_dev, void *stream, bool ingest_reported);
+
+// ... and of gnnb_forward_batched_types / gnnb_forward_pyg_types (gnnb_rgcn.h): the model and workspace checks, graph prep, the slot
+// records from edge_type_dev (int32 [E] in COO row order; nullptr only with num_edges == 0), the prepared forward
+int forward_batched_types_tail(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int32_t *edge_type_dev,
+                               const int32_t *coo_dev, const int32_t *node_ptr_dev, const int32_t *edge_ptr_dev, int num_graphs, int num_nodes,
+                               int num_edges, float *out_dev, void *stream, bool ingest_reported);
 
 // the add-on allocations at a workspace's capacities: their arrays placed in the workspace's blob, and their size (the size alone
 // while the blob is not allocated)

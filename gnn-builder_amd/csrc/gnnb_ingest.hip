@@ -109,6 +109,8 @@ int gnnb_forward_pyg(const gnnb_model *model, gnnb_workspace *ws, const float *x
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg");
     if (const int rc = refuse_edge_model(model, ws, "gnnb_forward_pyg", "gnnb_forward_pyg_edges"))
         return rc;
+    if (const int rc = refuse_rgcn_model(model, ws, "gnnb_forward_pyg", "gnnb_forward_pyg_types"))
+        return rc;
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
     if (const int rc = gnnb_ingest_pyg(ws, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &coo, &node_ptr, &edge_ptr, stream))
         return rc;
@@ -213,6 +215,8 @@ int gnnb_forward_pyg_ordered(const gnnb_model *model, gnnb_workspace *ws, const 
         return rc;
     if (const int rc = refuse_ggnn_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg"))
         return rc;
+    if (const int rc = refuse_rgcn_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg_types"))
+        return rc;
     const float *x_ord = nullptr;
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr, *perm = nullptr;
     int g0 = 0, n0 = 0, e0 = 0;
@@ -279,6 +283,8 @@ int gnnb_forward_pyg_edges(const gnnb_model *model, gnnb_workspace *ws, const fl
 {
     if (!model || !ws)
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg_edges");
+    if (const int rc = refuse_rgcn_model(model, ws, "gnnb_forward_pyg_edges", "gnnb_forward_pyg_types"))
+        return rc;
     if (!model->edge_dim || model->edge_dim != ws->edge_dim)
         return fail(GNNB_ERR_INVALID, "gnnb_forward_pyg_edges takes a model of gnnb_edge_model_create and its workspace");
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
@@ -287,6 +293,62 @@ int gnnb_forward_pyg_edges(const gnnb_model *model, gnnb_workspace *ws, const fl
                                              &edge_ptr, &edge_attr, stream))
         return rc;
     return forward_batched_tail(model, ws, x_dev, edge_attr, coo, node_ptr, edge_ptr, num_graphs, num_nodes, num_edges, out_dev, stream, true);
+}
+
+// ---------------------------------------------------------------------------------------
+// RGCNConv models: PyG mini-batches with integer edge types (gnnb_rgcn.h; k_edge_type_order of k_ingest.hip)
+size_t gnnb_type_ingest_bytes(int max_edges)
+{
+    if (max_edges < 0)
+        return 0;
+    return arena_up((size_t)std::max(max_edges, 1) * sizeof(int32_t));
+}
+
+int gnnb_workspace_enable_type_ingest(gnnb_workspace *ws)
+{
+    if (ws && !ws->type_blob && !ws->rgcn_relations)
+        return fail(GNNB_ERR_INVALID, "gnnb_workspace_enable_type_ingest: the workspace belongs to a model without relations "
+                                      "(gnnb_rgcn_model_create makes one with)");
+    if (addon_pending(ws, &gnnb_workspace::type_blob))
+        if (const int rc = gnnb_workspace_enable_ingest(ws))
+            return rc;
+    return enable_addon(ws, &gnnb_workspace::type_blob, ws ? gnnb_type_ingest_bytes(ws->max_edges) : 0, "gnnb_workspace_enable_type_ingest",
+                        "the type ingest", "type-ingest");
+}
+
+int gnnb_ingest_pyg_types(gnnb_workspace *ws, const int64_t *edge_index_dev, const int64_t *edge_type_dev, const int64_t *batch_dev,
+                          const int64_t *ptr_dev, int num_graphs, int num_nodes, int num_edges, const int32_t **coo_dev,
+                          const int32_t **node_ptr_dev, const int32_t **edge_ptr_dev, const int32_t **edge_type_ord_dev, void *stream)
+{
+    if (!ws || !edge_type_ord_dev || (num_edges > 0 && !edge_type_dev))
+        return fail(GNNB_ERR_INVALID, "null argument to gnnb_ingest_pyg_types");
+    if (!ws->type_blob)
+        return fail(GNNB_ERR_INVALID, "gnnb_ingest_pyg_types: call gnnb_workspace_enable_type_ingest on the workspace first");
+    if (const int rc = gnnb_ingest_pyg(ws, edge_index_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, coo_dev, node_ptr_dev, edge_ptr_dev, stream))
+        return rc;
+    // the types follow their edges, as gnnb_ingest_pyg_edges' attribute rows do: which path ran is the state word, read by the kernel
+    IngestParams p;
+    (void)ingest_place(ws, p);
+    const int passes = ingest_sort_passes(num_graphs);
+    const int32_t *idx = (passes == 0 || num_edges < 2) ? nullptr : p.idx[passes & 1];
+    GNNB_HIP_TRY(launch_edge_type_order((const long long *)edge_type_dev, idx, p.state, (int32_t *)ws->type_blob, num_edges, (hipStream_t)stream));
+    *edge_type_ord_dev = (const int32_t *)ws->type_blob;
+    return GNNB_OK;
+}
+
+int gnnb_forward_pyg_types(const gnnb_model *model, gnnb_workspace *ws, const float *x_dev, const int64_t *edge_index_dev,
+                           const int64_t *edge_type_dev, const int64_t *batch_dev, const int64_t *ptr_dev, int num_graphs, int num_nodes,
+                           int num_edges, float *out_dev, void *stream)
+{
+    if (!model || !ws)
+        return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg_types");
+    if (!model->rgcn_relations || model->rgcn_relations != ws->rgcn_relations)
+        return fail(GNNB_ERR_INVALID, "gnnb_forward_pyg_types takes a model of gnnb_rgcn_model_create and its workspace");
+    const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr, *edge_type = nullptr;
+    if (const int rc = gnnb_ingest_pyg_types(ws, edge_index_dev, edge_type_dev, batch_dev, ptr_dev, num_graphs, num_nodes, num_edges, &coo, &node_ptr,
+                                             &edge_ptr, &edge_type, stream))
+        return rc;
+    return forward_batched_types_tail(model, ws, x_dev, edge_type, coo, node_ptr, edge_ptr, num_graphs, num_nodes, num_edges, out_dev, stream, true);
 }
 
 } // extern "C"

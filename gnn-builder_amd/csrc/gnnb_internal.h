@@ -65,6 +65,7 @@ constexpr int GNNB_FLAG_DEGREE = 32;       // k_deg_count: a node exceeds the ma
 // modes (gnnb_device.h: RangeProbe), reported as GNNB_ERR_RANGE
 constexpr int GNNB_FLAG_RANGE = 64;
 constexpr int GNNB_FLAG_INGEST = 128;      // k_ingest.hip: the PyG mini-batch was malformed
+constexpr int GNNB_FLAG_EDGE_TYPE = 256;   // k_rgcn_slots: an edge type outside [0, relations) (gnnb_rgcn.h)
 
 // The 256-byte arena of every device allocation that holds several arrays: each array starts on a 256-byte boundary, in the order
 // it is taken.  ONE statement per array names it, its element type and its length, and answers both "how many bytes" (off, after
@@ -376,6 +377,26 @@ constexpr int RGE_MAX_EDGE_DIM = 16;
 hipError_t launch_resgated_edge_aggregate(const BatchTables &t, const float *k, int ldk, const float *q, int ldq, const float *v, int ldv,
                                           const float *root, int ldr, const float *skip, int act, const float *edge_attr, int edge_dim,
                                           const float *wg, int ldwg, const float *wv, int ldwv, float *out, int width, hipStream_t s);
+// RGCNConv (k_rgcn.hip; gnnb_rgcn.h).  A slot record: the relation of a CSR slot's edge and the mean weight 1 / |N_rel(i)| of its
+// destination row, 8 bytes; {0, 0.0f} for a type outside [0, relations)
+struct RgcnSlot {
+    int32_t rel;
+    float w;
+};
+static_assert(sizeof(RgcnSlot) == 8, "a slot record is one 8-byte access");
+constexpr int RGCN_MAX_WIDTH = 256, RGCN_MAX_RELATIONS = 8;
+// rec[s] of every CSR slot s of the tables from edge_type [E] (int32, COO row order; t.eid maps the slots): the counts are integers,
+// the division is the correctly rounded one; a type outside [0, relations) sets GNNB_FLAG_EDGE_TYPE.  hipErrorInvalidValue: nothing
+// launched
+hipError_t launch_rgcn_slots(const BatchTables &t, const int32_t *edge_type, int relations, RgcnSlot *rec, hipStream_t s);
+// out [N, width] = act((sum over the row's slots s of rec[s].w * p[col[s], rec[s].rel * width + c] + root_ic) + skip_ic): p rows of
+// stride ldp >= relations width, root rows of stride ldr >= width or nullptr, skip [N, width] or nullptr; tables that keep explicit
+// (v, v) edges.  hipErrorInvalidValue: nothing launched
+hipError_t launch_rgcn_aggregate(const BatchTables &t, const RgcnSlot *rec, const float *p, int ldp, int relations, const float *root, int ldr,
+                                 const float *skip, int act, float *out, int width, hipStream_t s);
+// the ingest's edge types in COO row order (k_ingest.hip): out[i] = (int32) edge_type[state[INGEST_STATE_UNSORTED] ? idx[i] : i], -1
+// for a value that does not fit (k_rgcn_slots flags it); idx, state: as launch_edge_attr_order's
+hipError_t launch_edge_type_order(const long long *edge_type, const int32_t *idx, const int32_t *state, int32_t *out, int num_edges, hipStream_t s);
 // the ingest's edge attributes in COO row order (k_ingest.hip): out[i] = edge_attr[state[INGEST_STATE_UNSORTED] ? idx[i] : i]; idx:
 // the general path's sorted-position -> input-edge array (nullptr: that path was not launched), state: IngestParams::state
 hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, const int32_t *state, float *out, int num_edges, int edge_dim,

@@ -218,6 +218,26 @@ int count_ggnn_params(const gnnb_model_desc *desc, int steps)
     return GGNN_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
+// parameter tensors of an RGCNConv model (gnnb_rgcn.h): a GIN description (its tables keep explicit (v, v) edges) without the
+// fixed-point emulation, relations 1 .. 8, every layer's output width at most 256
+int count_rgcn_params(const gnnb_model_desc *desc, int relations)
+{
+    int rc = validate_desc(desc);
+    if (rc != GNNB_OK)
+        return rc;
+    if (relations < 1 || relations > RGCN_MAX_RELATIONS)
+        return fail(GNNB_ERR_INVALID, "relations %d: an RGCNConv model takes 1 .. %d relations", relations, RGCN_MAX_RELATIONS);
+    if (desc->conv_type != GNNB_CONV_GIN)
+        return fail(GNNB_ERR_INVALID, "an RGCNConv model's description is a GIN description (conv_type %d given)", desc->conv_type);
+    if (desc->fpx_w != 0)
+        return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover RGCNConv models (fpx_w must be 0)");
+    for (int l = 0; l < desc->num_layers; l++)
+        if (layer_dims(*desc, l).fout > RGCN_MAX_WIDTH)
+            return fail(GNNB_ERR_INVALID, "layer %d's output width %d: an RGCNConv layer is at most %d wide", l, layer_dims(*desc, l).fout,
+                        RGCN_MAX_WIDTH);
+    return RGCN_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+}
+
 // What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
 // type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
 // (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features), or heads of a
@@ -225,7 +245,8 @@ int count_ggnn_params(const gnnb_model_desc *desc, int steps)
 // (gnnb_transformer_edge_model_create: TransformerConv with edge features), or the "gated" mark of a ResGatedGraphConv model
 // (gnnb_resgated_model_create: a GIN description), or that mark and edge_dim (gnnb_resgated_edge_model_create: ResGatedGraphConv with
 // edge features), or heads and negative_slope of a GAT v1 model (gnnb_gatconv_model_create: a GCN description), or the steps of a
-// GatedGraphConv model (gnnb_ggnn_model_create: a GIN description)
+// GatedGraphConv model (gnnb_ggnn_model_create: a GIN description), or the relations of an RGCNConv model (gnnb_rgcn_model_create: a
+// GIN description)
 struct ModelKind {
     int edge_dim = 0, base = GNNB_CONV_GIN;
     int gat_heads = 0;
@@ -234,6 +255,7 @@ struct ModelKind {
     bool gated = false;
     int gat1_heads = 0; // (its slope: gat_slope)
     int ggnn_steps = 0;
+    int rgcn_relations = 0;
     static ModelKind plain() { return {}; }
     static ModelKind edges(int edge_dim, int base)
     {
@@ -289,6 +311,12 @@ struct ModelKind {
         k.ggnn_steps = steps;
         return k;
     }
+    static ModelKind rgcn(int relations)
+    {
+        ModelKind k;
+        k.rgcn_relations = relations;
+        return k;
+    }
     static ModelKind resgated_edges(int edge_dim)
     {
         ModelKind k = resgated();
@@ -297,7 +325,7 @@ struct ModelKind {
     }
 };
 
-// the body of the twelve *_model_create entries
+// the body of the thirteen *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
@@ -305,7 +333,8 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
     const int gat1_heads = kind.gat1_heads;
-    int expect = kind.ggnn_steps != 0 ? count_ggnn_params(desc, kind.ggnn_steps)
+    int expect = kind.rgcn_relations != 0 ? count_rgcn_params(desc, kind.rgcn_relations)
+                 : kind.ggnn_steps != 0 ? count_ggnn_params(desc, kind.ggnn_steps)
                  : gat1_heads != 0 ? count_gatconv_params(desc, gat1_heads, edge_dim)
                  : kind.gated     ? count_resgated_params(desc, edge_dim)
                  : tf_heads != 0  ? count_transformer_params(desc, tf_heads, edge_dim)
@@ -324,7 +353,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
         return fail(GNNB_ERR_NO_DEVICE, "no HIP device visible: the MI355X path cannot run");
 
     const gnnb_model_desc &d = *desc;
-    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated, gat1_heads, kind.ggnn_steps);
+    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated, gat1_heads, kind.ggnn_steps, kind.rgcn_relations);
     const std::vector<float> &img = built.img;
     const WeightLayout &lo = built.layout;
 
@@ -337,6 +366,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     m->tf_heads = tf_heads;
     m->gated = kind.gated ? 1 : 0;
     m->ggnn_steps = kind.ggnn_steps;
+    m->rgcn_relations = kind.rgcn_relations;
     (void)hipGetDevice(&m->device);
     m->blob_floats = img.size();
     hipError_t e = hipMalloc((void **)&m->blob, std::max<size_t>(img.size(), 4) * sizeof(float));
@@ -561,6 +591,19 @@ int gnnb_ggnn_model_create(const gnnb_model_desc *desc, int steps, const float *
 }
 
 int gnnb_model_ggnn_steps(const gnnb_model *model) { return model ? model->ggnn_steps : 0; }
+
+int gnnb_rgcn_model_num_params(const gnnb_model_desc *desc, int relations) { return count_rgcn_params(desc, relations); }
+
+int gnnb_rgcn_model_create(const gnnb_model_desc *desc, int relations, const float *const *host_params, int num_params, gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (relations == 0) // (ModelKind reads 0 as "no RGCNConv model")
+        return fail(GNNB_ERR_INVALID, "relations 0: an RGCNConv model takes 1 .. %d relations", RGCN_MAX_RELATIONS);
+    return model_create(desc, ModelKind::rgcn(relations), host_params, num_params, out_model);
+}
+
+int gnnb_model_rgcn_relations(const gnnb_model *model) { return model ? model->rgcn_relations : 0; }
 
 void gnnb_model_destroy(gnnb_model *model)
 {

@@ -100,6 +100,14 @@ int refuse_ggnn_model(const gnnb_model *model, const gnnb_workspace *ws, const c
     return GNNB_OK;
 }
 
+int refuse_rgcn_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use)
+{
+    if ((model && model->rgcn_relations) || (ws && ws->rgcn_relations))
+        return fail(GNNB_ERR_INVALID, "%s: an RGCNConv model (gnnb_rgcn_model_create) needs the batch's edge types and is not served here: "
+                                      "call %s (gnnb_rgcn.h)", entry, use);
+    return GNNB_OK;
+}
+
 static thread_local int tl_math = -1; // >= 0: the calling thread is inside an entry point of a model with its own math mode
 static thread_local FlagWord tl_flag = {nullptr, nullptr};
 int launch_math() { return tl_math >= 0 ? tl_math : (int)options().math; }
@@ -196,6 +204,9 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     if (model->ggnn_steps) // a GatedGraphConv step's GEMM writes [p | gh] [N, 6 out] into tmp0; tmp1 holds the two [N, out] state buffers
         for (int l = 0; l < d.num_layers; l++)
             tmpw = std::max(tmpw, GGNN_TMP_BLOCKS * layer_dims(d, l).fout); // (gnnb_host.h: what ggnn_layer carves from them)
+    if (model->rgcn_relations) // an RGCNConv layer's GEMM writes [p_0 | .. | p_{R-1} | root] [N, (R + 1) out] into tmp0
+        for (int l = 0; l < d.num_layers; l++)
+            tmpw = std::max(tmpw, rgcn_tmp_blocks(model->rgcn_relations) * layer_dims(d, l).fout); // (gnnb_host.h)
     // the widest GEMM K of the conv layers: from 1024 on k_linear_dma may cut its tiles along K (stream-K) and needs a scratch,
     // which belongs to the workspace -- forwards of different workspaces never share one, whatever streams or graphs run them
     int max_k = 0;
@@ -207,8 +218,8 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     // (the stage-cut planner's tables: opt-in -- carved only for workspaces created while the option is on; a workspace created
     // without them keeps equal tile counts whatever the option says later: round-5 advisor finding)
     const bool want_plan = options().stage_cut && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 &&
-                           model->gat_heads == 0 && model->gat1_heads == 0 && model->tf_heads == 0 && model->gated == 0 && model->ggnn_steps == 0; // (a GATv2 model,
-                                            // a GAT v1 model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model take no stack kernel: no stage plan)
+                           model->gat_heads == 0 && model->gat1_heads == 0 && model->tf_heads == 0 && model->gated == 0 && model->ggnn_steps == 0 && model->rgcn_relations == 0; // (a GATv2 model,
+                                            // a GAT v1 model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model, an RGCNConv model take no stack kernel: no stage plan)
     const int pooledw = d.num_pools * gnn_out_width(d);
     const int mlpw = std::max(d.mlp_hidden, d.mlp_out);
     const int min_tile_rows = 4;
@@ -223,6 +234,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     ws->tf_heads = model->tf_heads;
     ws->gated = model->gated;
     ws->ggnn_steps = model->ggnn_steps;
+    ws->rgcn_relations = model->rgcn_relations;
     ws->max_graphs = max_graphs;
     ws->max_nodes = max_nodes;
     ws->max_edges = max_edges;
@@ -269,6 +281,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
         ws->mlp[0] = a.take<float>(B * mlpw);
         ws->mlp[1] = a.take<float>(B * mlpw);
         sk_base = want_sk ? a.take<char>(stream_k_scratch_bytes()) : nullptr;
+        ws->rgcn_rec = ws->rgcn_relations ? a.take<RgcnSlot>(E) : nullptr; // (last: every other workspace's layout is what it was)
         return a.off;
     };
     ws->bytes = place(Arena{nullptr});
@@ -318,6 +331,8 @@ void gnnb_workspace_destroy(gnnb_workspace *ws)
         (void)hipFree(ws->order_blob);
     if (ws->edge_blob)
         (void)hipFree(ws->edge_blob);
+    if (ws->type_blob)
+        (void)hipFree(ws->type_blob);
     if (ws->order_triple)
         (void)hipHostFree(ws->order_triple);
     if (ws->stage)
@@ -383,9 +398,9 @@ static bool stack_promised(const gnnb_workspace *ws)
 {
     const gnnb_model_desc &d = ws->desc;
     // (a GINE model's workspace, a GATv2 model's, a GAT v1 model's, a TransformerConv model's, a ResGatedGraphConv model's, a
-    // GatedGraphConv model's: never -- their layers take no stack kernel, whatever the promise)
+    // GatedGraphConv model's, an RGCNConv model's: never -- their layers take no stack kernel, whatever the promise)
     return options().fuse_gcn2 && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 && ws->max_graph_nodes > 0 &&
-           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->gat1_heads == 0 && ws->tf_heads == 0 && ws->gated == 0 && ws->ggnn_steps == 0;
+           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->gat1_heads == 0 && ws->tf_heads == 0 && ws->gated == 0 && ws->ggnn_steps == 0 && ws->rgcn_relations == 0;
 }
 
 // ... and the WHOLE batch is expected there: no large segment, no fixed-point emulation.  Such a batch needs neither the
@@ -658,14 +673,14 @@ int gnnb_workspace_check(gnnb_workspace *ws, void *stream)
     if (ws->err_host)
         *(volatile int32_t *)ws->err_host = 0;
     static_assert(GNNB_FLAG_PTR_ENDS == 1 && GNNB_FLAG_PTR_ORDER == 2 && GNNB_FLAG_EDGE == 4 && GNNB_FLAG_GRAPH_NODES == 8 &&
-                      GNNB_FLAG_LARGE_SEGMENT == 16 && GNNB_FLAG_DEGREE == 32 && GNNB_FLAG_RANGE == 64 && GNNB_FLAG_INGEST == 128,
+                      GNNB_FLAG_LARGE_SEGMENT == 16 && GNNB_FLAG_DEGREE == 32 && GNNB_FLAG_RANGE == 64 && GNNB_FLAG_INGEST == 128 && GNNB_FLAG_EDGE_TYPE == 256,
                   "the message below names the bits by value");
     if (err & ~GNNB_FLAG_RANGE)
         return fail(GNNB_ERR_GRAPH, "malformed batch (flags 0x%x): 1/2 ptr arrays not monotone/complete, 4 an edge leaves "
                                     "its graph, 8 a graph exceeds the max_graph_nodes promise, 16 the large-segment offsets "
                                     "disagree with node_ptr / edge_ptr, 32 a node exceeds the max_degree promise, 64 a reduced-precision "
                                     "kernel produced a non-finite value, 128 gnnb_ingest_pyg: endpoint outside [0, N), edge between two "
-                                    "graphs, or broken batch / ptr", err);
+                                    "graphs, or broken batch / ptr, 256 an edge type outside [0, relations) of an RGCNConv model", err);
     if (err & GNNB_FLAG_RANGE)
         return fail(GNNB_ERR_RANGE, "a reduced-precision math mode (bf16x3 / f16x3) produced a non-finite value since the last check: an "
                                     "activation or a weight beyond fp16's range (65504), or non-finite inputs; the results of that forward "
@@ -897,6 +912,45 @@ int gnnb_aggregate_ggnn(gnnb_workspace *ws, const float *p_dev, int ldp, const f
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_ggnn (p, gh, h and out not NULL unless the batch has no nodes, width 1 .. %d, h_width 1 .. width, ldp "
                                       "and ldgh >= 3 width, ldh >= h_width, a gnnb_act)", GG_MAX_WIDTH);
     GNNB_HIP_TRY(launch_ggnn_aggregate(ws->t, p_dev, ldp, gh_dev, ldgh, h_dev, ldh, h_width, b_ih_dev, skip_dev, act, out_dev, width,
+                                       (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_rgcn_slots(gnnb_workspace *ws, const int32_t *edge_type_dev, int relations, void *slot_rec_dev, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_rgcn_slots needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's, a GAT v1 model's, with or without edge features)
+        return fail(GNNB_ERR_INVALID, "gnnb_rgcn_slots takes a prepared batch whose tables keep explicit self loops: graph prep drops the "
+                                      "(v, v) edges on a workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts "
+                                      "them as ordinary edges");
+    // (a prepared batch without edges launches nothing and reads no operand)
+    const bool operands = ws->t.num_edges <= 0 || (edge_type_dev && slot_rec_dev);
+    if (!operands || relations < 1 || relations > RGCN_MAX_RELATIONS || ((uintptr_t)slot_rec_dev & 7) != 0)
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_rgcn_slots (edge_type and slot_rec not NULL unless the batch has no edges, slot_rec "
+                                      "8-byte aligned, relations 1 .. %d)", RGCN_MAX_RELATIONS);
+    GNNB_HIP_TRY(launch_rgcn_slots(ws->t, edge_type_dev, relations, (RgcnSlot *)slot_rec_dev, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_rgcn(gnnb_workspace *ws, const void *slot_rec_dev, const float *p_dev, int ldp, int relations, const float *root_dev, int ldr,
+                        const float *skip_dev, int act, float *out_dev, int width, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_rgcn needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type == GNNB_CONV_GCN)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_rgcn takes a prepared batch whose tables keep explicit self loops: graph prep drops the "
+                                      "(v, v) edges on a workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts "
+                                      "them as ordinary edges");
+    // (a prepared batch without nodes launches nothing and reads no operand: an empty tensor's NULL pointer is no error there)
+    const bool operands = ws->t.num_nodes <= 0 || (p_dev && out_dev && (slot_rec_dev || ws->t.num_edges <= 0));
+    if (!operands || width < 1 || width > RGCN_MAX_WIDTH || relations < 1 || relations > RGCN_MAX_RELATIONS ||
+        (int64_t)ldp < (int64_t)relations * width || (root_dev && ldr < width) || ((uintptr_t)slot_rec_dev & 7) != 0 || act < GNNB_ACT_RELU ||
+        act > GNNB_ACT_NONE)
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_rgcn (slot_rec, p and out not NULL unless the batch has no edges / nodes, "
+                                      "slot_rec 8-byte aligned, width 1 .. %d, relations 1 .. %d, ldp >= relations width, ldr >= width, a "
+                                      "gnnb_act)", RGCN_MAX_WIDTH, RGCN_MAX_RELATIONS);
+    GNNB_HIP_TRY(launch_rgcn_aggregate(ws->t, (const RgcnSlot *)slot_rec_dev, p_dev, ldp, relations, root_dev, ldr, skip_dev, act, out_dev, width,
                                        (hipStream_t)stream));
     return GNNB_OK;
 }

@@ -143,6 +143,13 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //              b_ggc [6 out]                        derived: [0 | bias_hh], canonical 4 -- the p block takes NO bias (it would be
 //                                                   counted once per edge)
 //              b_ih [3 out]                         canonical 3: conv.rnn.bias_ih, raw -- k_ggnn_aggregate adds it once per row
+//   RGCNConv  (gnnb_model::rgcn_relations = R > 0, gnnb_rgcn_model_create: a GIN description) none of GIN's slots, but
+//              w_rgcn [(R + 1) out, in]             derived: [weight[0]^T ; .. ; weight[R-1]^T ; root^T] -- canonical 0, conv.weight
+//                                                   [R, in, out], and canonical 1, conv.root [in, out], both applied as x @ W: pure
+//                                                   transposes into nn.Linear layout, no arithmetic (rgcn_stack) -- ONE GEMM gives
+//                                                   [p_0 | .. | p_{R-1} | root] [N, (R + 1) out]
+//              b_rgcn [(R + 1) out]                 derived: [0 | .. | 0 | bias], canonical 2 -- the relation blocks take NO bias
+//                                                   (it would be counted once per edge)
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
@@ -153,6 +160,7 @@ template <typename T> struct LayerSlots {
     T w_qkvre = absent_slot<T>(), b_qkvre = absent_slot<T>();
     T w_kqvr = absent_slot<T>(), b_kqvr = absent_slot<T>(), w_gv_edge = absent_slot<T>();
     T w_ggc = absent_slot<T>(), w_ggc_next = absent_slot<T>(), b_ggc = absent_slot<T>(), b_ih = absent_slot<T>();
+    T w_rgcn = absent_slot<T>(), b_rgcn = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -161,7 +169,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_rgcn), f(b_rgcn), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -521,22 +529,45 @@ inline std::vector<float> ggnn_fold(const float *weight_t, const float *w_ih, co
 // floats between the [6 fo, fo] matrices of steps 1 .. (whole 16-byte pieces, as every tensor of the image)
 inline size_t ggnn_step_stride(size_t fo) { return (6 * fo * fo + 3) / 4 * 4; }
 
+// RGCNConv: the R relation weights and the root weight, each [fi, fo] and applied as x @ W, stacked in nn.Linear layout:
+// [(R + 1) fo, fi], block r = weight[r]^T, block R = root^T.  Pure transposes: every float of the result is a float of the input
+inline std::vector<float> rgcn_stack(const float *weight, const float *root, size_t relations, size_t fi, size_t fo)
+{
+    std::vector<float> w((relations + 1) * fo * fi);
+    for (size_t r = 0; r <= relations; r++) {
+        const float *src = r < relations ? weight + r * fi * fo : root;
+        for (size_t o = 0; o < fo; o++)
+            for (size_t k = 0; k < fi; k++)
+                w[(r * fo + o) * fi + k] = src[k * fo + o];
+    }
+    return w;
+}
+
 constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_gat.h); one more with edge features (gnnb_gat_edge.h)
 constexpr int TF_PARAM_SLOTS = 8;  // a TransformerConv layer's canonical tensors (gnnb_transformer.h); one more with edge features
                                    // (gnnb_transformer_edge.h)
 constexpr int RG_PARAM_SLOTS = 8;  // a ResGatedGraphConv layer's canonical tensors (gnnb_resgated.h)
 constexpr int GGNN_PARAM_SLOTS = 5; // a GatedGraphConv layer's canonical tensors (gnnb_ggnn.h)
 constexpr int GGNN_MAX_STEPS = 8;
+constexpr int RGCN_PARAM_SLOTS = 3; // an RGCNConv layer's canonical tensors (gnnb_rgcn.h)
 constexpr int GAT1_PARAM_SLOTS = 4; // a GAT v1 layer's canonical tensors (gnnb_gatconv.h); two more with edge features (gnnb_gatconv_edge.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
 // their offsets in the image
 inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0,
-                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0)
+                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (rgcn_relations > 0) { // (a GIN description whose layers are RGCNConv's; canonical order: weight, root, bias)
+        LayerOffsets g;
+        g.w_rgcn = im.push(rgcn_stack(p[0], p[1], (size_t)rgcn_relations, fi, fo));
+        std::vector<float> b(((size_t)rgcn_relations + 1) * fo, 0.0f);
+        memcpy(&b[(size_t)rgcn_relations * fo], p[2], fo * sizeof(float));
+        g.b_rgcn = im.push(b);
+        return g;
+    }
     if (ggnn_steps > 0) { // (a GIN description whose layers are GatedGraphConv's; canonical order: weight, rnn.weight_ih, rnn.weight_hh,
                           // rnn.bias_ih, rnn.bias_hh; fi <= fo by gnnb_ggnn_model_create's check)
         LayerOffsets g;
@@ -673,13 +704,15 @@ struct BuiltWeights {
 // features (the same eight, three of them [out, in + edge_dim]).  gat1_heads > 0: a GAT v1 model (a GCN description, four tensors
 // per layer; no fragment copy -- it takes no stack kernel); with edge_dim > 0 besides, GAT v1 with edge features (six tensors per
 // layer).  ggnn_steps > 0: a GatedGraphConv model (a GIN description, five tensors per layer; no execution-order copy).
+// rgcn_relations > 0: an RGCNConv model (a GIN description, three tensors per layer; no execution-order copy).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
-                                       int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0)
+                                       int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = ggnn_steps > 0  ? GGNN_PARAM_SLOTS
+    const int slots = rgcn_relations > 0 ? RGCN_PARAM_SLOTS
+                      : ggnn_steps > 0 ? GGNN_PARAM_SLOTS
                       : gat1_heads > 0 ? GAT1_PARAM_SLOTS + (edge_dim ? 2 : 0)
                       : gated         ? RG_PARAM_SLOTS
                       : tf_heads > 0  ? TF_PARAM_SLOTS + (edge_dim ? 1 : 0)
@@ -687,13 +720,13 @@ inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, c
                                       : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;
     for (int l = 0; l < d.num_layers; l++, pi += slots)
-        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps);
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps, rgcn_relations);
     const bool have_w1f = gat_heads == 0 && gat1_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));
-    // (a GINE model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model take no stack kernel: no
-    // execution-order copy)
-    const bool have_gin = edge_dim == 0 && tf_heads == 0 && !gated && ggnn_steps == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
+    // (a GINE model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model, an RGCNConv model take no stack
+    // kernel: no execution-order copy)
+    const bool have_gin = edge_dim == 0 && tf_heads == 0 && !gated && ggnn_steps == 0 && rgcn_relations == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
                           d.out_dim <= d.hidden_dim && d.out_dim % 4 == 0;
     if (have_gin) {
         const WeightBias g = gin_execution_order(d, im.img, lo.conv);

@@ -21,6 +21,8 @@
 // k_edge_attr_order: edge_attr_ord[i] = edge_attr[src(i)], src(i) = i on the ingest's grouped path and idx[i] on its general
 // path (the sorted-position -> input-edge array k_ingest_finish consumes); the path is read from the ingest's state word, as
 // the ingest's own kernels do: no read-back, the same launch for grouped and shuffled input.
+// k_edge_type_order: its twin for an RGCNConv model's integer edge types (gnnb_rgcn.h), int64 in, int32 out, -1 for a value that
+// does not fit.
 #include <algorithm>
 
 #include "gnnb_device.h"
@@ -325,6 +327,27 @@ hipError_t launch_edge_attr_order(const float *edge_attr, const int32_t *idx, co
         return hipSuccess;
     const long long n = (long long)num_edges * edge_dim;
     hipLaunchKernelGGL(k_edge_attr_order, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, s, edge_attr, idx, state, out, num_edges, edge_dim);
+    return hipGetLastError();
+}
+
+// ---- ... and its edge types (gnnb_rgcn.h): int64 in, int32 out; a value that does not fit the int32 becomes -1, which k_rgcn_slots
+// flags as any type outside [0, relations)
+__global__ __launch_bounds__(WG) void k_edge_type_order(const long long *__restrict__ edge_type, const int32_t *__restrict__ idx,
+                                                        const int32_t *__restrict__ state, int32_t *__restrict__ out, int E)
+{
+    const int i = blockIdx.x * WG + threadIdx.x; // one edge per thread
+    if (i >= E)
+        return;
+    const int src = (idx && state[INGEST_STATE_UNSORTED]) ? min(max(idx[i], 0), E - 1) : i;
+    const long long v = edge_type[src];
+    out[i] = (v < 0 || v > 0x7fffffffll) ? -1 : (int32_t)v;
+}
+
+hipError_t launch_edge_type_order(const long long *edge_type, const int32_t *idx, const int32_t *state, int32_t *out, int num_edges, hipStream_t s)
+{
+    if (num_edges <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_edge_type_order, dim3((unsigned)((num_edges + WG - 1) / WG)), dim3(WG), 0, s, edge_type, idx, state, out, num_edges);
     return hipGetLastError();
 }
 

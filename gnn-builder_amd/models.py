@@ -948,6 +948,69 @@ class GatedGraphConv_GNNB(nn.Module):
         return self.conv(x, edge_index)
 
 
+# --------------------------------------------------------------------------------------- RGCNConv
+class _RGCNConv(nn.Module):
+    """PyG's ``RGCNConv(in_channels, out_channels, num_relations, aggr='mean', root_weight=True, bias=True)`` without basis or
+    block decomposition -- the relational GCN of Schlichtkrull et al., for graphs whose edges carry an integer type::
+
+        out_i = x_i @ root + bias + sum_{r < R} (1 / |N_r(i)|) * sum_{j in N_r(i)} x_j @ weight[r]
+
+    ``N_r(i)``: the in-edges of ``i`` with type ``r``; duplicate edges count as often as they occur, an explicit ``(v, v)`` edge
+    is an ordinary edge, no self loop is added or removed, a relation without an edge into ``i`` contributes 0.  Parameters with
+    PyG's ``state_dict`` names and shapes -- ``weight`` [R, in, out], ``root`` [in, out] (both applied as ``x @ W``), ``bias``
+    [out] --, initialised as PyG does (glorot, glorot, zeros).  Out of scope: ``num_bases``, ``num_blocks``, ``aggr`` other than
+    mean, ``root_weight=False``, ``bias=False``."""
+
+    def __init__(self, in_channels: int, out_channels: int, num_relations: int):
+        super().__init__()
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.num_relations = num_relations
+        self.weight = nn.Parameter(torch.empty(num_relations, in_channels, out_channels))
+        self.root = nn.Parameter(torch.empty(in_channels, out_channels))
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+        for t in (self.weight, self.root):  # (PyG's glorot: uniform in +- sqrt(6 / (size(-2) + size(-1))))
+            bound = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
+            nn.init.uniform_(t, -bound, bound)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_type: Tensor) -> Tensor:
+        src, dst = edge_index[0].long(), edge_index[1].long()
+        edge_type = edge_type.reshape(-1).long()
+        if edge_type.numel() != src.numel():
+            raise ValueError(f"edge_type must hold one type per edge: {src.numel()} edges, {edge_type.numel()} types")
+        if edge_type.numel() and (int(edge_type.min()) < 0 or int(edge_type.max()) >= self.num_relations):
+            raise ValueError(f"edge_type must lie in [0, {self.num_relations}): got {int(edge_type.min())} .. {int(edge_type.max())}")
+        out = x @ self.root + self.bias
+        for r in range(self.num_relations):  # (per relation, as PyG evaluates it: the mean of the neighbours, then the transform)
+            m = edge_type == r
+            s, d = src[m], dst[m]
+            cnt = x.new_zeros(x.size(0)).index_add(0, d, x.new_ones(d.numel()))
+            h = torch.zeros_like(x).index_add(0, d, x[s]) / cnt.clamp(min=1).unsqueeze(-1)
+            out = out + h @ self.weight[r]
+        return out
+
+
+class RGCNConv_GNNB(nn.Module):
+    """The relational graph conv (no class of the reference): PyG's ``RGCNConv(in_channels, out_channels, num_relations=R)``.
+    ``GNNModel(..., gnn_conv=RGCNConv_GNNB, gnn_relations=R)`` stacks it (``R`` in 1 .. 8); ``forward(x, edge_index, edge_type)``
+    with ``edge_type`` int64 [E] in ``[0, R)``, the same for every layer.  The accelerated path is
+    ``runtime.CompiledModel.from_model`` with ``forward_types`` / ``forward_pyg_types`` (C ABI ``include/gnnb_rgcn.h``: one GEMM
+    ``x -> [p_0 | .. | p_{R-1} | root]`` and one launch of csrc/k_rgcn.hip per layer, one gathered row per edge).  This class
+    ignores ``graph_input_edge_dim`` and ``edge_attr``.  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, relations: int = 1, p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.relations = relations
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _RGCNConv(in_channels, out_channels, relations)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_type: Tensor) -> Tensor:
+        return self.conv(x, edge_index, edge_type)
+
+
 # --------------------------------------------------------------------------------------- pooling / MLP
 SUPPORTED_GLOBAL_POOLING_AGGRS = {"add": "SumAggregation", "max": "MaxAggregation", "mean": "MeanAggregation"}
 SUPPORTED_GLOBAL_POOLING_MODE = ["cat"]
@@ -1060,11 +1123,11 @@ class MLP(nn.Module):
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
                        GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB,
-                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB, GatedGraphConv_GNNB]
+                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB, GatedGraphConv_GNNB, RGCNConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
               PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
               TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated", ResGatedGraphEConv_GNNB: "resgatede",
-              GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate", GatedGraphConv_GNNB: "ggnn"}
+              GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate", GatedGraphConv_GNNB: "ggnn", RGCNConv_GNNB: "rgcn"}
 # convs that take edge_attr, and what the messages call them
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE",
                ResGatedGraphEConv_GNNB: "ResGatedE", GATv1EConv_GNNB: "GATE"}
@@ -1073,6 +1136,7 @@ _GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # the GATv2 convs (heads and neg
 _TF_CONVS = (TransformerConv_GNNB, TransformerEConv_GNNB)  # the TransformerConv convs (heads travel beside a GIN description)
 _GAT1_CONVS = (GATv1Conv_GNNB, GATv1EConv_GNNB)  # PyG's GATConv (heads and negative_slope travel beside a GCN description: include/gnnb_gatconv.h, gnnb_gatconv_edge.h)
 _HEAD_CONVS = _GAT_CONVS + _TF_CONVS + _GAT1_CONVS  # convs with attention heads: the ones that take gnn_heads
+MAX_RGCN_RELATIONS = 8  # of an RGCNConv model (include/gnnb_rgcn.h): edge types in [0, relations), beside a GIN description
 MAX_GGNN_STEPS = 8  # of a GatedGraphConv model (include/gnnb_ggnn.h): steps per layer, beside a GIN description
 
 
@@ -1085,7 +1149,7 @@ class GNNModel(nn.Module):
                  gnn_conv: TorchModuleArg, gnn_activation: TorchModuleArg, gnn_skip_connection: bool,
                  global_pooling: GlobalPooling, mlp_head: MLP,
                  output_activation: TorchModuleArgOptional, gnn_p_in: int = 1, gnn_p_hidden: int = 1,
-                 gnn_p_out: int = 1, gnn_heads: int = 1, gnn_steps: int = 1) -> None:
+                 gnn_p_out: int = 1, gnn_heads: int = 1, gnn_steps: int = 1, gnn_relations: int = 1) -> None:
         super().__init__()
         self.graph_input_feature_dim = graph_input_feature_dim
         self.graph_input_edge_dim = graph_input_edge_dim
@@ -1135,6 +1199,14 @@ class GNNModel(nn.Module):
         elif gnn_steps != 1:
             raise ValueError(f"gnn_steps={gnn_steps!r}: only a GatedGraphConv model (gnn_conv=GatedGraphConv_GNNB) has steps")
 
+        self.gnn_relations = gnn_relations
+        if self.gnn_conv is RGCNConv_GNNB:
+            if not isinstance(gnn_relations, int) or isinstance(gnn_relations, bool) or not 1 <= gnn_relations <= MAX_RGCN_RELATIONS:
+                raise ValueError(f"an RGCNConv model needs gnn_relations, an int in 1 .. {MAX_RGCN_RELATIONS} (got {gnn_relations!r})")
+            conv_kwargs = {**conv_kwargs, "relations": gnn_relations}
+        elif gnn_relations != 1:
+            raise ValueError(f"gnn_relations={gnn_relations!r}: only an RGCNConv model (gnn_conv=RGCNConv_GNNB) has relations")
+
         self.global_pooling = global_pooling
         self.mlp_head = mlp_head  # registered before gnn_convs: parameter order mlp_head_*, gnn_convs_*
         self.output_activation = output_activation
@@ -1165,20 +1237,25 @@ class GNNModel(nn.Module):
             self.gnn_convs.append(self.gnn_conv(dims[0], dims[1], p_in=dims[2], p_out=dims[3], **conv_kwargs))
             self.gnn_activations.append(self.gnn_activation())
 
-    def forward(self, x: Tensor, edge_index: Tensor, batch: Optional[Tensor] = None, edge_attr: Optional[Tensor] = None) -> Tensor:
+    def forward(self, x: Tensor, edge_index: Tensor, batch: Optional[Tensor] = None, edge_attr: Optional[Tensor] = None,
+                edge_type: Optional[Tensor] = None) -> Tensor:
         """``batch=None``: one graph -> ``[1, out]``, exactly the reference.  With ``batch``
         (node -> graph index, PyG ``Batch`` convention) every graph is pooled separately ->
         ``[num_graphs, out]``; the reference ignores ``batch`` and pools all nodes into one row
         (models.py:551-553,569; SURVEY finding 3), which has no meaning for independent graphs.
         ``edge_attr`` [E, graph_input_edge_dim]: a GINE, PNAE, GATv2E, TransformerE, ResGatedE or GATE model's edge features, the same for every layer (required
-        there; the other convs ignore it)."""
+        there; the other convs ignore it).  ``edge_type`` int64 [E] in [0, gnn_relations): an RGCNConv model's edge types, the same
+        for every layer (required there; the other convs ignore it)."""
         gine = self.gnn_conv in _EDGE_CONVS
+        typed = self.gnn_conv is RGCNConv_GNNB
+        if typed and edge_type is None:
+            raise ValueError("an RGCNConv model needs edge_type [E], integers in [0, gnn_relations)")
         if gine and edge_attr is None:
             raise ValueError(f"a {_EDGE_CONVS[self.gnn_conv]} model needs edge_attr [E, graph_input_edge_dim]")
         h = x
         for i, (conv, act) in enumerate(zip(self.gnn_convs, self.gnn_activations)):
             h_in = h
-            h = conv(h, edge_index, edge_attr) if gine else conv(h, edge_index)
+            h = conv(h, edge_index, edge_attr) if gine else conv(h, edge_index, edge_type) if typed else conv(h, edge_index)
             if self.gnn_skip_connection and i != 0 and i != self.gnn_num_layers - 1:
                 h = h + h_in
             h = act(h)
@@ -1259,6 +1336,8 @@ class GNNModel(nn.Module):
             gat = {"heads": int(self.gnn_heads)}
         elif self.gnn_conv is GatedGraphConv_GNNB:  # (a GIN description on the C side, steps beside it: include/gnnb_ggnn.h)
             gat = {"steps": int(self.gnn_steps)}
+        elif self.gnn_conv is RGCNConv_GNNB:  # (a GIN description on the C side, relations beside it: include/gnnb_rgcn.h)
+            gat = {"relations": int(self.gnn_relations)}
         return {
             "conv": _CONV_NAME[self.gnn_conv],
             "num_layers": self.gnn_num_layers,
@@ -1308,6 +1387,7 @@ class GNNModel(nn.Module):
         per_conv["gate"] = per_conv["gat"] + ["conv_att_edge", "conv_lin_edge_weight"]
         # (PyG's state_dict order: the per-step message weights [steps, out, out], then the one GRU cell: include/gnnb_ggnn.h)
         per_conv["ggnn"] = ["conv_weight", "conv_rnn_weight_ih", "conv_rnn_weight_hh", "conv_rnn_bias_ih", "conv_rnn_bias_hh"]
+        per_conv["rgcn"] = ["conv_weight", "conv_root", "conv_bias"]  # (PyG's state_dict order: include/gnnb_rgcn.h)
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

@@ -30,7 +30,7 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin", "rgcn": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
 # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h,
 # "resgatede": gnnb_resgated_edge.h, "gate": gnnb_gatconv_edge.h)
 _EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede", "gate")
@@ -47,6 +47,8 @@ MAX_TRANSFORMER_HEADS, MAX_TRANSFORMER_WIDTH = 8, 256
 MAX_RESGATED_WIDTH = 256
 # a GatedGraphConv model (include/gnnb_ggnn.h, spec["conv"] == "ggnn"): its description is GIN's too, steps per layer beside it
 MAX_GGNN_STEPS, MAX_GGNN_WIDTH = 8, 256
+# an RGCNConv model (include/gnnb_rgcn.h, spec["conv"] == "rgcn"): its description is GIN's too, the relation count beside it
+MAX_RGCN_RELATIONS, MAX_RGCN_WIDTH = 8, 256
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -263,6 +265,22 @@ ABI_GGNN = {
 }
 
 
+# ... and of include/gnnb_rgcn.h (RGCNConv models with integer edge types), in its order (tests/test_abi_rgcn.py)
+ABI_RGCN = {
+    "gnnb_rgcn_model_num_params": (_I, [_DESC, _I]),
+    "gnnb_rgcn_model_create": (_I, [_DESC, _I, _PP, _I, _PP]),
+    "gnnb_model_rgcn_relations": (_I, [_P]),
+    "gnnb_forward_batched_types": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "gnnb_forward_prepared_types": (_I, [_P, _P, _P, _P, _P, _P]),
+    "gnnb_type_ingest_bytes": (_Z, [_I]),
+    "gnnb_workspace_enable_type_ingest": (_I, [_P]),
+    "gnnb_ingest_pyg_types": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _PP, _PP, _PP, _PP, _P]),
+    "gnnb_forward_pyg_types": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "gnnb_rgcn_slots": (_I, [_P, _P, _I, _P, _P]),
+    "gnnb_aggregate_rgcn": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -279,6 +297,12 @@ def edge_ingest_bytes(max_edges: int, edge_dim: int) -> int:
     """Size of the allocation ``CompiledModel.enable_edge_ingest`` makes beside the ingest's (``gnnb_edge_ingest_bytes``): the edge
     attributes in COO row order.  Pure host arithmetic, no GPU needed; 0 for an ``edge_dim`` outside 1 .. 16."""
     return int(load_library(require_gpu=False).gnnb_edge_ingest_bytes(int(max_edges), int(edge_dim)))
+
+
+def type_ingest_bytes(max_edges: int) -> int:
+    """Size of the allocation ``CompiledModel.enable_type_ingest`` makes beside the ingest's (``gnnb_type_ingest_bytes``): the edge
+    types in COO row order, int32.  Pure host arithmetic, no GPU needed."""
+    return int(load_library(require_gpu=False).gnnb_type_ingest_bytes(int(max_edges)))
 
 
 def build_library(force: bool = False) -> Path:
@@ -308,7 +332,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
         for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER,
                                            **ABI_TRANSFORMER_EDGE, **ABI_RESGATED, **ABI_RESGATED_EDGE, **ABI_GATCONV,
-                                           **ABI_GATCONV_EDGE, **ABI_GGNN}.items():
+                                           **ABI_GATCONV_EDGE, **ABI_GGNN, **ABI_RGCN}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -426,8 +450,9 @@ _NOT_ENABLED = {
     "ingest": "ingest is not enabled on this model's workspace: call enable_ingest() once after construction",
     "ordered": "the ordered ingest is not enabled on this model's workspace: call enable_ordered_ingest() once after construction",
     "edges": "the edge ingest is not enabled on this model's workspace: call enable_edge_ingest() once after construction",
+    "types": "the type ingest is not enabled on this model's workspace: call enable_type_ingest() once after construction",
 }
-_INGEST_OUTS = {"ingest": 3, "ordered": 5, "edges": 4}  # arrays its ingest returns (CompiledModel._view_specs)
+_INGEST_OUTS = {"ingest": 3, "ordered": 5, "edges": 4, "types": 4}  # arrays its ingest returns (CompiledModel._view_specs)
 
 
 class _Borrowed:
@@ -457,6 +482,7 @@ class CompiledModel:
         self.transformer_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _TRANSFORMER_CONVS else 0
         self.gatconv_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _GATCONV_CONVS else 0
         self.ggnn_steps = int(spec.get("steps", 1) or 0) if spec.get("conv") == "ggnn" else 0
+        self.rgcn_relations = int(spec.get("relations", 1) or 0) if spec.get("conv") == "rgcn" else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
@@ -480,6 +506,7 @@ class CompiledModel:
                     self.lib.gnnb_resgated_model_num_params(C.byref(self.desc)) if spec.get("conv") == "resgated" else
                     self.lib.gnnb_gatconv_model_num_params(C.byref(self.desc), self.gatconv_heads) if spec.get("conv") == "gat" else
                     self.lib.gnnb_ggnn_model_num_params(C.byref(self.desc), self.ggnn_steps) if spec.get("conv") == "ggnn" else
+                    self.lib.gnnb_rgcn_model_num_params(C.byref(self.desc), self.rgcn_relations) if spec.get("conv") == "rgcn" else
                     self.lib.gnnb_model_num_params(C.byref(self.desc)))
         if n_expect < 0:
             _check(n_expect)
@@ -511,6 +538,8 @@ class CompiledModel:
                                                       len(host), C.byref(self._model)))
         elif spec.get("conv") == "ggnn":  # (gnnb_ggnn.h: a GIN description, steps beside it)
             _check(self.lib.gnnb_ggnn_model_create(C.byref(self.desc), self.ggnn_steps, arr, len(host), C.byref(self._model)))
+        elif spec.get("conv") == "rgcn":  # (gnnb_rgcn.h: a GIN description, the relation count beside it)
+            _check(self.lib.gnnb_rgcn_model_create(C.byref(self.desc), self.rgcn_relations, arr, len(host), C.byref(self._model)))
         else:
             _check(self.lib.gnnb_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
         rc = self.lib.gnnb_workspace_create(self._model, self.max_graphs, self.max_nodes, self.max_edges, C.byref(self._ws))
@@ -696,7 +725,8 @@ class CompiledModel:
         coo = [((cap_e, 2), "<i4"), ((G + 1,), "<i4"), ((G + 1,), "<i4")]  # coo, node_ptr, edge_ptr
         return {"ingest": coo,
                 "ordered": [((self.max_nodes, max(int(self.desc.in_dim), 1)), "<f4")] + coo + [((G,), "<i4")],  # x_ord ..., perm
-                "edges": coo + [((cap_e, self.edge_dim), "<f4")]}[addon]  # ..., edge_attr_ord
+                "edges": coo + [((cap_e, self.edge_dim), "<f4")],  # ..., edge_attr_ord
+                "types": coo + [((cap_e,), "<i4")]}[addon]  # ..., edge_type_ord
 
     def _ingest(self, addon: str, fn, lead, batch, ptr, sizes, dev, stream, ints: int = 0):
         """What the three ingests share: ``fn(ws, *lead, batch, ptr, *sizes, <the add-on's out-pointers>, <ints int*>, stream)``;
@@ -879,6 +909,85 @@ class CompiledModel:
         (``gnnb_forward_pyg_edges``)."""
         self._require_edge_model("forward_pyg_edges")
         return self._forward_pyg(self.lib.gnnb_forward_pyg_edges, "edges", x, edge_index, edge_attr, batch, ptr, num_graphs, out, stream)
+
+    # ------------------------------------------------------------------ RGCNConv models: forwards with integer edge types
+    def _require_edge_type(self, edge_type, E: int, like, dtype):
+        """``edge_type`` of an entry point that reads one integer per edge: ``dtype`` [E], contiguous, on ``like``'s device; an
+        empty batch's may be None.  Returns its device pointer (None: NULL)."""
+        if edge_type is None:
+            if E:
+                raise GnnbError(f"edge_type is required: the batch has {E} edges")
+            return None
+        _require(edge_type, "edge_type", dtype, 1)
+        if edge_type.numel() != E or edge_type.device != like.device:
+            raise GnnbError(f"edge_type must be [{E}] on {like.device}, got {tuple(edge_type.shape)} on {edge_type.device}")
+        return _dptr(edge_type) if E else None
+
+    def _require_rgcn_model(self, what: str) -> None:
+        if not self.rgcn_relations:
+            raise GnnbError(f"{what} takes an RGCNConv model (a GNNModel of RGCNConv_GNNB layers: relations); this model has none")
+
+    def forward_types(self, x, edge_type, coo, node_ptr, edge_ptr, out=None, stream=None):
+        """``forward`` of an RGCNConv model: ``edge_type`` [E] int32, entry ``i`` belongs to ``coo`` row ``i``
+        (``gnnb_forward_batched_types``).  A type outside ``[0, relations)`` is flagged, not refused: ``check()`` raises (flag
+        0x100).  Everything else as ``forward``."""
+        import torch
+        self._require_rgcn_model("forward_types")
+        B, N, E = self._check_batch(x, coo, node_ptr, edge_ptr)
+        et = self._require_edge_type(edge_type, E, x, torch.int32)
+        out = _out(out, B, self.out_dim, x)
+        _check(self.lib.gnnb_forward_batched_types(self._model, self._ws, _dptr(x), et, _dptr(coo), _dptr(node_ptr), _dptr(edge_ptr), B, N, E,
+                                                   _dptr(out), _stream_ptr(stream)))
+        self._prepared(B, N, E, (coo, node_ptr, edge_ptr))
+        return out
+
+    def forward_prepared_types(self, x, edge_type, out=None, stream=None):
+        """``forward_prepared`` of an RGCNConv model on the batch ``graph_prep`` left in the workspace."""
+        import torch
+        self._require_rgcn_model("forward_prepared_types")
+        self._require_x(x, int(self.desc.in_dim))
+        et = self._require_edge_type(edge_type, self._E, x, torch.int32)
+        out = _out(out, self._B, self.out_dim, x)
+        _check(self.lib.gnnb_forward_prepared_types(self._model, self._ws, _dptr(x), et, _dptr(out), _stream_ptr(stream)))
+        return out
+
+    def enable_type_ingest(self) -> None:
+        """``enable_ingest`` (if that has not been done) and one more device allocation (``type_ingest_bytes``) for
+        ``ingest_pyg_types`` / ``forward_pyg_types``.  Synchronous: call it once, right after construction, outside stream
+        capture."""
+        self._require_rgcn_model("enable_type_ingest")
+        _check(self.lib.gnnb_workspace_enable_type_ingest(self._ws))
+        self._addons |= {"ingest", "types"}
+
+    def ingest_pyg_types(self, edge_index, edge_type, batch=None, ptr=None, num_graphs=None, stream=None, num_nodes=None):
+        """``ingest_pyg`` with the mini-batch's ``edge_type`` [E] int64 (``Batch.edge_type``, in ``edge_index``'s column order):
+        returns ``(coo, node_ptr, edge_ptr, edge_type_ord)`` with ``edge_type_ord[i]`` (int32) the type of ``coo`` row ``i`` -- what
+        ``batching.from_pyg_batch(..., edge_type=...)`` computes on the host, with no synchronisation (``gnnb_ingest_pyg_types``).
+        VIEWS of the workspace: valid until the next ingest on it."""
+        import torch
+        if "types" not in self._addons:
+            raise GnnbError(_NOT_ENABLED["types"])
+        batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, num_nodes)
+        et = self._require_edge_type(edge_type, E, edge_index, torch.int64)
+        (coo, nptr, eptr, et_ord), _ = self._ingest("types", self.lib.gnnb_ingest_pyg_types, (_dptr(edge_index), et), batch, ptr, (B, N, E),
+                                                    edge_index.device, stream)
+        return coo[:E], nptr[:B + 1], eptr[:B + 1], et_ord[:E]
+
+    def forward_pyg_types(self, x, edge_index, edge_type, batch=None, ptr=None, num_graphs=None, out=None, stream=None):
+        """``forward_pyg`` of an RGCNConv model: ``edge_type`` [E] int64 in ``edge_index``'s column order; ingest (the types
+        follow their edges) and forward on one stream, no host synchronisation, capturable (``gnnb_forward_pyg_types``)."""
+        import torch
+        self._require_rgcn_model("forward_pyg_types")
+        _require(x, "x", torch.float32, 2, int(self.desc.in_dim))
+        if "types" not in self._addons:
+            raise GnnbError(_NOT_ENABLED["types"])
+        batch, ptr, B, N, E = self._pyg_args(edge_index, batch, ptr, num_graphs, int(x.shape[0]))
+        et = self._require_edge_type(edge_type, E, x, torch.int64)
+        out = _out(out, B, self.out_dim, x)
+        _check(self.lib.gnnb_forward_pyg_types(self._model, self._ws, _dptr(x), _dptr(edge_index), et, _optr(batch), _optr(ptr), B, N, E,
+                                               _dptr(out), _stream_ptr(stream)))
+        self._prepared(B, N, E, None)  # (the batch's index arrays live in the workspace)
+        return out
 
     # ------------------------------------------------------------------ stage-level entry points
     # (raw pointers cross the C ABI: each checks every operand's dtype, layout, device and rows against the prepared batch, so
@@ -1147,6 +1256,61 @@ class CompiledModel:
         ld = lambda t: int(t.stride(0)) if self._N > 1 else int(t.shape[1])  # noqa: E731  (one row: any stride describes it)
         _check(self.lib.gnnb_aggregate_ggnn(self._ws, _dptr(p), ld(p), _dptr(gh), ld(gh), _dptr(h), ld(h), hw, _optr(b_ih), _optr(skip),
                                             ACT[act], _dptr(out), w, _stream_ptr(stream)))
+        return out
+
+    def rgcn_slots(self, edge_type, relations: int, stream=None):
+        """The slot records of the prepared batch (``gnnb_rgcn_slots``, csrc/k_rgcn.hip) on a workspace whose tables keep explicit
+        self loops: ``edge_type`` [E] int32 in COO row order -> an int32 tensor [E, 2], row ``s`` = (relation, the bits of the
+        float32 ``1 / |N_rel(i)|``) of CSR slot ``s`` -- ``rec[:, 1].view(torch.float32)`` gives the weights.  A type outside
+        ``[0, relations)`` gives (0, 0.0) and flags the batch (``check()``: flag 0x100).  What ``aggregate_rgcn`` takes."""
+        import torch
+        if not isinstance(relations, int) or isinstance(relations, bool) or not 1 <= relations <= MAX_RGCN_RELATIONS:
+            raise GnnbError(f"relations must be an int in 1 .. {MAX_RGCN_RELATIONS}, got {relations!r}")
+        if edge_type is None and self._E:
+            raise GnnbError(f"edge_type is required: the batch has {self._E} edges")
+        if edge_type is not None:
+            _require(edge_type, "edge_type", torch.int32, 1)
+            if edge_type.numel() != self._E:
+                raise GnnbError(f"edge_type must be [{self._E}], got {tuple(edge_type.shape)}")
+        dev = edge_type.device if edge_type is not None else torch.device("cuda")
+        # (zeros: a slot no row owns -- none on the workspaces this entry accepts -- would otherwise hold what the allocator left)
+        rec = torch.zeros((self._E, 2), dtype=torch.int32, device=dev)
+        _check(self.lib.gnnb_rgcn_slots(self._ws, _optr(edge_type) if self._E else None, relations, _dptr(rec) if self._E else None,
+                                        _stream_ptr(stream)))
+        return rec
+
+    def aggregate_rgcn(self, rec, p, relations: int, root=None, skip=None, act: str = "none", out=None, stream=None):
+        """One RGCNConv layer behind its GEMM (``gnnb_aggregate_rgcn``, csrc/k_rgcn.hip) on the prepared batch of a workspace whose
+        tables keep explicit self loops: ``act((sum_s w_s * p[col_s, rel_s * width + c] + root) + skip)`` -> [N, width] over the
+        row's slots ``s`` with ``rec`` (``rgcn_slots``) naming each slot's relation block and mean weight.  ``p`` [N, >= relations
+        * width] with ``width = p.shape[1] // relations`` and ``root`` [N, width] or None may be column slices of one wider matrix
+        (the blocks of one [N, (relations + 1) width] GEMM output: their row strides are passed on); ``skip`` [N, width] contiguous
+        or None; ``width`` <= 256."""
+        import torch
+        if not isinstance(relations, int) or isinstance(relations, bool) or not 1 <= relations <= MAX_RGCN_RELATIONS:
+            raise GnnbError(f"relations must be an int in 1 .. {MAX_RGCN_RELATIONS}, got {relations!r}")
+        _require_strided(p, "p", self._N, relations)
+        if int(p.shape[1]) % relations:
+            raise GnnbError(f"p must be [{self._N}, relations * width], got {tuple(p.shape)} for {relations} relations")
+        w = int(p.shape[1]) // relations
+        if w > MAX_RGCN_WIDTH:
+            raise GnnbError(f"width {w}: an RGCNConv layer is at most {MAX_RGCN_WIDTH} wide")
+        _require(rec, "rec", torch.int32, 2, 2)
+        if int(rec.shape[0]) != self._E or rec.device != p.device or rec.data_ptr() % 8:
+            raise GnnbError(f"rec must be the [{self._E}, 2] int32 records of rgcn_slots on {p.device}, 8-byte aligned; got "
+                            f"{tuple(rec.shape)} on {rec.device}")
+        if root is not None:
+            _require_strided(root, "root", self._N, w)
+            if int(root.shape[1]) != w or root.device != p.device:
+                raise GnnbError(f"root must be [{self._N}, {w}] on {p.device}, got {tuple(root.shape)} on {root.device}")
+        if act not in ACT:
+            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, p)
+        out = _out(out, self._N, w, p)
+        ld = lambda t: int(t.stride(0)) if self._N > 1 else int(t.shape[1])  # noqa: E731  (one row: any stride describes it)
+        _check(self.lib.gnnb_aggregate_rgcn(self._ws, _dptr(rec) if self._E else None, _dptr(p), ld(p), relations, _optr(root),
+                                            ld(root) if root is not None else 0, _optr(skip), ACT[act], _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def aggregate_resgated_edges(self, k, q, v, edge_attr, w_gate, w_value, root=None, skip=None, act: str = "none", out=None, stream=None):

@@ -29,6 +29,7 @@ from .models import (
     GatedGraphConv_GNNB,
     PNAConv_GNNB,
     PNAEConv_GNNB,
+    RGCNConv_GNNB,
     ResGatedGraphConv_GNNB,
     ResGatedGraphEConv_GNNB,
     SAGEConv_GNNB,
@@ -48,7 +49,7 @@ from .batching import GraphBatch, from_pyg_batch, order_large_last, pack_graphs,
 __all__ = [
     "Project", "FPX",
     "MLP", "GATConv_GNNB", "GATv1Conv_GNNB", "GATv1EConv_GNNB", "GATv2Conv_GNNB", "GATv2EConv_GNNB", "GCNConv_GNNB", "GIN_MLP", "GINConv_GNNB", "GINEConv_GNNB", "GatedGraphConv_GNNB", "GlobalPooling", "GNNModel",
-    "PNAConv_GNNB", "PNAEConv_GNNB", "ResGatedGraphConv_GNNB", "ResGatedGraphEConv_GNNB", "SAGEConv_GNNB", "TransformerConv_GNNB", "TransformerEConv_GNNB",
+    "PNAConv_GNNB", "PNAEConv_GNNB", "RGCNConv_GNNB", "ResGatedGraphConv_GNNB", "ResGatedGraphEConv_GNNB", "SAGEConv_GNNB", "TransformerConv_GNNB", "TransformerEConv_GNNB",
     "compute_average_degree", "compute_average_nodes_and_edges", "compute_max_nodes_and_edges",
     "compute_median_degree", "compute_median_nodes_and_edges",
     "GraphBatch", "from_pyg_batch", "order_large_last", "pack_graphs", "shard_batch", "shard_bounds",
