@@ -28,7 +28,7 @@ import jinja2
 import numpy as np
 import torch
 
-from .models import (GATv1Conv_GNNB, GATv1EConv_GNNB, GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, GatedGraphConv_GNNB, PNAEConv_GNNB, RGCNConv_GNNB, ResGatedGraphConv_GNNB,
+from .models import (GATv1Conv_GNNB, GATv1EConv_GNNB, GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, GatedGraphConv_GNNB, NNConv_GNNB, PNAEConv_GNNB, RGCNConv_GNNB, ResGatedGraphConv_GNNB,
                      ResGatedGraphEConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB)
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
@@ -145,6 +145,10 @@ class Project:
             raise NotImplementedError(
                 "Project does not generate RGCNConv designs: the generated shim and the templates have no relational layer and carry "
                 "no edge types; run the model through runtime.CompiledModel.from_model(model, ...).forward_types / forward_pyg_types")
+        if getattr(model, "gnn_conv", None) is NNConv_GNNB:
+            raise NotImplementedError(
+                "Project does not generate NNConv designs: the generated shim and the templates have no edge-conditioned layer; run "
+                "the model through runtime.CompiledModel.from_model(model, ...).forward_edges / forward_pyg_edges")
         self.model = model
         self.dataset = dataset
         self.name = name

@@ -78,7 +78,8 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     // a GINE model: no stack kernel forms the edge term; a GATv2 model, a GAT v1 model, a TransformerConv model: none forms
     // attention; a ResGatedGraphConv model: none forms the gate; a GatedGraphConv model: none forms the GRU cell; an RGCNConv
     // model: none selects a weight by relation
-    if (model->edge_dim || model->gat_heads || model->gat1_heads || model->tf_heads || model->gated || model->ggnn_steps || model->rgcn_relations)
+    if (model->edge_dim || model->gat_heads || model->gat1_heads || model->tf_heads || model->gated || model->ggnn_steps || model->rgcn_relations ||
+        model->nn_coefs)
         return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
@@ -372,6 +373,24 @@ static int rgcn_layer(const LayerCtx &c)
     return GNNB_OK;
 }
 
+// NNConv (gnnb_nnconv.h; a GIN description with edge_dim and the edge network's shape beside it, so the tables keep explicit (v, v)
+// edges): the AGGREGATE-FIRST order.  ONE k_nnconv_aggregate launch forms A [N, (K' + 1) fi] in ws->tmp0 from the layer's input and
+// the batch's edge attributes -- one gathered row of the INPUT width per edge --, then ONE GEMM on the two K-segments [A | x] and
+// w_nn = [W_fold^T | lin.weight] with the bias, the skip term and the activation in its epilogue, in the model's math mode.  None
+// of the fused rungs
+static int nnconv_layer(const LayerCtx &c)
+{
+    const gnnb_model_desc &d = c.model->desc;
+    const LayerWeights &p = c.model->conv[c.l];
+    const int fi = c.fi, fo = c.fo, lda = c.model->nn_coefs * fi;
+    float *A = c.ws->tmp0; // ([max_nodes, >= (K' + 1) fi]: gnnb_workspace_create)
+    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+        GNNB_HIP_TRY(launch_nnconv_aggregate(c.tv, c.cur, fi, c.edge_attr, c.model->edge_dim, p.w_nn1, p.b_nn1, c.model->nn_hidden,
+                                             c.model->nn_mean, A, lda, c.hs()));
+    gnnb_gemm_seg segs[2] = {{c.rows(A, lda), nullptr, lda, lda}, {c.rows(c.cur, fi), nullptr, fi, fi}};
+    return c.linear(segs, 2, p.w_nn, lda + fi, p.b_nn, c.rows(c.skip, fi), c.rows(c.nxt, fo), fo, d.activation);
+}
+
 // GIN's first linear + ReLU on the eps-weighted sum -> ws->tmp0
 static int gin_hidden(const LayerCtx &c)
 {
@@ -552,6 +571,7 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
         case GNNB_CONV_GIN:
             rc = model->tf_heads ? transformer_layer(c) : model->gated ? resgated_layer(c) : model->ggnn_steps ? ggnn_layer(c)
                  : model->rgcn_relations                                                                                 ? rgcn_layer(c)
+                 : model->nn_coefs                                                                                       ? nnconv_layer(c)
                                                                                                                          : gin_layer(c);
             break;
         case GNNB_CONV_SAGE: rc = sage_layer(c); break;
@@ -831,7 +851,8 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
     if (memcmp(&model->desc, &ws->desc, sizeof(gnnb_model_desc)) != 0 || model->edge_dim != ws->edge_dim ||
         model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope || model->gat1_heads != ws->gat1_heads ||
         model->tf_heads != ws->tf_heads || model->gated != ws->gated ||
-        model->ggnn_steps != ws->ggnn_steps || model->rgcn_relations != ws->rgcn_relations)
+        model->ggnn_steps != ws->ggnn_steps || model->rgcn_relations != ws->rgcn_relations || model->nn_coefs != ws->nn_coefs ||
+        model->nn_hidden != ws->nn_hidden || model->nn_mean != ws->nn_mean)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;

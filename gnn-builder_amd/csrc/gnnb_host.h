@@ -22,6 +22,7 @@
 #include "gnnb_resgated_edge.h"
 #include "gnnb_ggnn.h"
 #include "gnnb_rgcn.h"
+#include "gnnb_nnconv.h"
 
 namespace gnnb {
 
@@ -71,6 +72,10 @@ struct gnnb_model {
                             // layer -- every layer has w_ggc, w_ggc_next (steps > 1), b_ggc, b_ih and none of GIN's slots
     int rgcn_relations = 0; // > 0: an RGCNConv model (gnnb_rgcn_model_create; desc is a GIN description) of that many relations --
                             // every layer has w_rgcn, b_rgcn and none of GIN's slots
+    int nn_coefs = 0;       // > 0: an NNConv model (gnnb_nnconv_model_create; desc is a GIN description, edge_dim beside it) of K' + 1
+                            // coefficients per edge -- every layer has w_nn, b_nn (and w_nn1, b_nn1 with nn_hidden > 0) and none of GIN's slots
+    int nn_hidden = 0;      // ... its edge network's hidden width K (0: the linear edge network, K' = edge_dim)
+    int nn_mean = 0;        // ... and 1 for aggr = mean (0: add)
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };
@@ -97,6 +102,7 @@ struct gnnb_workspace {
     int gated = 0;               // ... and 1 when it is a ResGatedGraphConv model
     int ggnn_steps = 0;          // ... and its steps when it is a GatedGraphConv model (0: it is not)
     int rgcn_relations = 0;      // ... and its relations when it is an RGCNConv model (0: it is not)
+    int nn_coefs = 0, nn_hidden = 0, nn_mean = 0; // ... and its coefficient count, hidden width and aggr when it is an NNConv model
     gnnb::RgcnSlot *rgcn_rec = nullptr; // such a model's workspace only: the slot records of the batch (k_rgcn_slots), 8 max_edges bytes,
                                  // rebuilt by every _types forward
     char *type_blob = nullptr;   // gnnb_workspace_enable_type_ingest: edge_type in COO row order, int32 [max_edges], one allocation

@@ -394,6 +394,13 @@ hipError_t launch_rgcn_slots(const BatchTables &t, const int32_t *edge_type, int
 // (v, v) edges.  hipErrorInvalidValue: nothing launched
 hipError_t launch_rgcn_aggregate(const BatchTables &t, const RgcnSlot *rec, const float *p, int ldp, int relations, const float *root, int ldr,
                                  const float *skip, int act, float *out, int width, hipStream_t s);
+// NNConv aggregated before the transform (k_nnconv.hip; gnnb_nnconv.h): out[i, k width + c] = sum over row i's in-edges of
+// coef_k(e_ij) * x[j, c], k = 0 .. K', rows of stride ldo >= (K' + 1) width.  hidden == 0: K' = edge_dim, coef = [e ; 1]; hidden > 0:
+// K' = hidden, coef = [relu(w1 e + b1) ; 1] with w1 [hidden, edge_dim], b1 [hidden].  mean != 0: the row times 1 / in-degree (0 for
+// in-degree 0).  Tables that keep explicit (v, v) edges.  hipErrorInvalidValue: nothing launched
+constexpr int NN_MAX_WIDTH = 256, NN_MAX_EDGE_DIM = 16, NN_MAX_HIDDEN = 16;
+hipError_t launch_nnconv_aggregate(const BatchTables &t, const float *x, int width, const float *edge_attr, int edge_dim, const float *w1,
+                                   const float *b1, int hidden, int mean, float *out, int ldo, hipStream_t s);
 // the ingest's edge types in COO row order (k_ingest.hip): out[i] = (int32) edge_type[state[INGEST_STATE_UNSORTED] ? idx[i] : i], -1
 // for a value that does not fit (k_rgcn_slots flags it); idx, state: as launch_edge_attr_order's
 hipError_t launch_edge_type_order(const long long *edge_type, const int32_t *idx, const int32_t *state, int32_t *out, int num_edges, hipStream_t s);

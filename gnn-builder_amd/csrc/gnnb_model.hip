@@ -238,6 +238,30 @@ int count_rgcn_params(const gnnb_model_desc *desc, int relations)
     return RGCN_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
+// parameter tensors of an NNConv model (gnnb_nnconv.h): a GIN description (its tables keep explicit (v, v) edges) without the
+// fixed-point emulation, edge_dim 1 .. 16, hidden 0 (the linear edge network) .. 16, every layer width at most 256
+int count_nnconv_params(const gnnb_model_desc *desc, int edge_dim, int hidden)
+{
+    int rc = validate_desc(desc);
+    if (rc != GNNB_OK)
+        return rc;
+    if (edge_dim < 1 || edge_dim > NN_MAX_EDGE_DIM)
+        return fail(GNNB_ERR_INVALID, "edge_dim %d: an NNConv model takes edge_dim 1 .. %d", edge_dim, NN_MAX_EDGE_DIM);
+    if (hidden < 0 || hidden > NN_MAX_HIDDEN)
+        return fail(GNNB_ERR_INVALID, "hidden %d: an NNConv model's edge network has a hidden width of 1 .. %d, or 0 for a single linear", hidden,
+                    NN_MAX_HIDDEN);
+    if (desc->conv_type != GNNB_CONV_GIN)
+        return fail(GNNB_ERR_INVALID, "an NNConv model's description is a GIN description (conv_type %d given)", desc->conv_type);
+    if (desc->fpx_w != 0)
+        return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover NNConv models (fpx_w must be 0)");
+    for (int l = 0; l < desc->num_layers; l++) {
+        const LayerDims ld = layer_dims(*desc, l);
+        if (ld.fin > NN_MAX_WIDTH || ld.fout > NN_MAX_WIDTH)
+            return fail(GNNB_ERR_INVALID, "layer %d's widths %d -> %d: an NNConv layer is at most %d wide", l, ld.fin, ld.fout, NN_MAX_WIDTH);
+    }
+    return nnconv_param_slots(hidden) * desc->num_layers + 2 * desc->mlp_num_linear;
+}
+
 // What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
 // type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
 // (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features), or heads of a
@@ -256,6 +280,7 @@ struct ModelKind {
     int gat1_heads = 0; // (its slope: gat_slope)
     int ggnn_steps = 0;
     int rgcn_relations = 0;
+    int nn_coefs = 0, nn_hidden = 0, nn_mean = 0; // an NNConv model (gnnb_nnconv_model_create: a GIN description, edge_dim too)
     static ModelKind plain() { return {}; }
     static ModelKind edges(int edge_dim, int base)
     {
@@ -317,6 +342,14 @@ struct ModelKind {
         k.rgcn_relations = relations;
         return k;
     }
+    static ModelKind nnconv(int edge_dim, int hidden, int mean)
+    {
+        ModelKind k = edges(edge_dim, GNNB_CONV_GIN);
+        k.nn_coefs = (hidden > 0 ? hidden : edge_dim) + 1;
+        k.nn_hidden = hidden;
+        k.nn_mean = mean ? 1 : 0;
+        return k;
+    }
     static ModelKind resgated_edges(int edge_dim)
     {
         ModelKind k = resgated();
@@ -325,7 +358,7 @@ struct ModelKind {
     }
 };
 
-// the body of the thirteen *_model_create entries
+// the body of the fourteen *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
@@ -333,7 +366,8 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
     const int gat1_heads = kind.gat1_heads;
-    int expect = kind.rgcn_relations != 0 ? count_rgcn_params(desc, kind.rgcn_relations)
+    int expect = kind.nn_coefs != 0 ? count_nnconv_params(desc, edge_dim, kind.nn_hidden)
+                 : kind.rgcn_relations != 0 ? count_rgcn_params(desc, kind.rgcn_relations)
                  : kind.ggnn_steps != 0 ? count_ggnn_params(desc, kind.ggnn_steps)
                  : gat1_heads != 0 ? count_gatconv_params(desc, gat1_heads, edge_dim)
                  : kind.gated     ? count_resgated_params(desc, edge_dim)
@@ -353,7 +387,8 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
         return fail(GNNB_ERR_NO_DEVICE, "no HIP device visible: the MI355X path cannot run");
 
     const gnnb_model_desc &d = *desc;
-    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated, gat1_heads, kind.ggnn_steps, kind.rgcn_relations);
+    const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated, gat1_heads, kind.ggnn_steps, kind.rgcn_relations,
+                                                  kind.nn_coefs, kind.nn_hidden);
     const std::vector<float> &img = built.img;
     const WeightLayout &lo = built.layout;
 
@@ -367,6 +402,9 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     m->gated = kind.gated ? 1 : 0;
     m->ggnn_steps = kind.ggnn_steps;
     m->rgcn_relations = kind.rgcn_relations;
+    m->nn_coefs = kind.nn_coefs;
+    m->nn_hidden = kind.nn_hidden;
+    m->nn_mean = kind.nn_mean;
     (void)hipGetDevice(&m->device);
     m->blob_floats = img.size();
     hipError_t e = hipMalloc((void **)&m->blob, std::max<size_t>(img.size(), 4) * sizeof(float));
@@ -604,6 +642,22 @@ int gnnb_rgcn_model_create(const gnnb_model_desc *desc, int relations, const flo
 }
 
 int gnnb_model_rgcn_relations(const gnnb_model *model) { return model ? model->rgcn_relations : 0; }
+
+int gnnb_nnconv_model_num_params(const gnnb_model_desc *desc, int edge_dim, int hidden) { return count_nnconv_params(desc, edge_dim, hidden); }
+
+int gnnb_nnconv_model_create(const gnnb_model_desc *desc, int edge_dim, int hidden, int aggr, const float *const *host_params, int num_params,
+                             gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (aggr != GNNB_NN_AGGR_ADD && aggr != GNNB_NN_AGGR_MEAN)
+        return fail(GNNB_ERR_INVALID, "aggr %d: an NNConv model aggregates with GNNB_NN_AGGR_ADD or GNNB_NN_AGGR_MEAN", aggr);
+    if (const int rc = count_nnconv_params(desc, edge_dim, hidden); rc < 0) // (ModelKind reads edge_dim 0 as "no edge model")
+        return rc;
+    return model_create(desc, ModelKind::nnconv(edge_dim, hidden, aggr == GNNB_NN_AGGR_MEAN), host_params, num_params, out_model);
+}
+
+int gnnb_model_nnconv_hidden(const gnnb_model *model) { return model && model->nn_coefs ? model->nn_hidden : -1; }
 
 void gnnb_model_destroy(gnnb_model *model)
 {

@@ -207,12 +207,17 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     if (model->rgcn_relations) // an RGCNConv layer's GEMM writes [p_0 | .. | p_{R-1} | root] [N, (R + 1) out] into tmp0
         for (int l = 0; l < d.num_layers; l++)
             tmpw = std::max(tmpw, rgcn_tmp_blocks(model->rgcn_relations) * layer_dims(d, l).fout); // (gnnb_host.h)
+    if (model->nn_coefs) // an NNConv layer's aggregate writes A [N, (K' + 1) in] into tmp0
+        for (int l = 0; l < d.num_layers; l++)
+            tmpw = std::max(tmpw, model->nn_coefs * layer_dims(d, l).fin);
     // the widest GEMM K of the conv layers: from 1024 on k_linear_dma may cut its tiles along K (stream-K) and needs a scratch,
     // which belongs to the workspace -- forwards of different workspaces never share one, whatever streams or graphs run them
     int max_k = 0;
     for (int l = 0; l < d.num_layers; l++) {
         const LayerDims ld = layer_dims(d, l);
         max_k = std::max(max_k, d.conv_type == GNNB_CONV_PNA ? 13 * ld.fin : d.conv_type == GNNB_CONV_SAGE ? 2 * ld.fin : std::max(ld.fin, ld.fout));
+        if (model->nn_coefs) // ([A | x]: K = (K' + 2) in, up to 18 x 256 = 4608; the launch plan sets no bound on K)
+            max_k = std::max(max_k, (model->nn_coefs + 1) * ld.fin);
     }
     const bool want_sk = max_k >= 1024;
     // (the stage-cut planner's tables: opt-in -- carved only for workspaces created while the option is on; a workspace created
@@ -235,6 +240,9 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     ws->gated = model->gated;
     ws->ggnn_steps = model->ggnn_steps;
     ws->rgcn_relations = model->rgcn_relations;
+    ws->nn_coefs = model->nn_coefs;
+    ws->nn_hidden = model->nn_hidden;
+    ws->nn_mean = model->nn_mean;
     ws->max_graphs = max_graphs;
     ws->max_nodes = max_nodes;
     ws->max_edges = max_edges;
@@ -913,6 +921,28 @@ int gnnb_aggregate_ggnn(gnnb_workspace *ws, const float *p_dev, int ldp, const f
                                       "and ldgh >= 3 width, ldh >= h_width, a gnnb_act)", GG_MAX_WIDTH);
     GNNB_HIP_TRY(launch_ggnn_aggregate(ws->t, p_dev, ldp, gh_dev, ldgh, h_dev, ldh, h_width, b_ih_dev, skip_dev, act, out_dev, width,
                                        (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_nnconv(gnnb_workspace *ws, const float *x_dev, int width, const float *edge_attr_dev, int edge_dim, const float *w1_dev,
+                          const float *b1_dev, int hidden, int aggr, float *out_dev, int ldo, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_nnconv needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type == GNNB_CONV_GCN)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_nnconv takes a prepared batch whose tables keep explicit self loops: graph prep drops the "
+                                      "(v, v) edges on a workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts "
+                                      "them as ordinary edges");
+    // (a prepared batch without nodes launches nothing and reads no operand; one without edges reads no attribute row)
+    const bool operands = ws->t.num_nodes <= 0 || (x_dev && out_dev && (edge_attr_dev || ws->t.num_edges <= 0));
+    const int kq = hidden > 0 ? hidden : edge_dim;
+    if (!operands || width < 1 || width > NN_MAX_WIDTH || edge_dim < 1 || edge_dim > NN_MAX_EDGE_DIM || hidden < 0 || hidden > NN_MAX_HIDDEN ||
+        (hidden > 0 && (!w1_dev || !b1_dev)) || (aggr != GNNB_NN_AGGR_ADD && aggr != GNNB_NN_AGGR_MEAN) || (int64_t)ldo < (int64_t)(kq + 1) * width)
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_nnconv (x, edge_attr and out not NULL unless the batch has no nodes / edges, "
+                                      "width 1 .. %d, edge_dim 1 .. %d, hidden 0 .. %d with w1 and b1 when it is not 0, aggr add or mean, "
+                                      "ldo >= (K' + 1) width)", NN_MAX_WIDTH, NN_MAX_EDGE_DIM, NN_MAX_HIDDEN);
+    GNNB_HIP_TRY(launch_nnconv_aggregate(ws->t, x_dev, width, edge_attr_dev, edge_dim, w1_dev, b1_dev, hidden, aggr == GNNB_NN_AGGR_MEAN, out_dev, ldo,
+                                         (hipStream_t)stream));
     return GNNB_OK;
 }
 

@@ -150,6 +150,13 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //                                                   [p_0 | .. | p_{R-1} | root] [N, (R + 1) out]
 //              b_rgcn [(R + 1) out]                 derived: [0 | .. | 0 | bias], canonical 2 -- the relation blocks take NO bias
 //                                                   (it would be counted once per edge)
+//   NNConv    (gnnb_model::nn_coefs = K' + 1 > 0, gnnb_nnconv_model_create: a GIN description) none of GIN's slots, but
+//              w_nn [out, (K' + 2) in]              derived: [W_fold^T | lin.weight] -- W_fold[k in + col, o] = W2[col out + o, k] for
+//                                                   k < K' and b2[col out + o] for k = K', (W2, b2) the edge network's last linear: a
+//                                                   pure permutation, no arithmetic (nnconv_fold) -- ONE GEMM on [A | x] gives
+//                                                   sum_j x_j Theta(e_ij) + root x_i
+//              b_nn [out]                           the conv's bias, raw
+//              w_nn1 [K, edge_dim], b_nn1 [K]       the edge network's first linear, raw (the hidden variant only)
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
@@ -161,6 +168,7 @@ template <typename T> struct LayerSlots {
     T w_kqvr = absent_slot<T>(), b_kqvr = absent_slot<T>(), w_gv_edge = absent_slot<T>();
     T w_ggc = absent_slot<T>(), w_ggc_next = absent_slot<T>(), b_ggc = absent_slot<T>(), b_ih = absent_slot<T>();
     T w_rgcn = absent_slot<T>(), b_rgcn = absent_slot<T>();
+    T w_nn = absent_slot<T>(), b_nn = absent_slot<T>(), w_nn1 = absent_slot<T>(), b_nn1 = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -169,7 +177,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_rgcn), f(b_rgcn), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_rgcn), f(b_rgcn), f(w_nn), f(b_nn), f(w_nn1), f(b_nn1), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -543,6 +551,24 @@ inline std::vector<float> rgcn_stack(const float *weight, const float *root, siz
     return w;
 }
 
+// NNConv: the GEMM weight of the aggregate-first order, nn.Linear layout [fo, (kq + 2) fi] for the operand [A | x] with
+// A[i, k fi + col] = sum_j c_ijk x_j[col]: column k fi + col of row o is W2[col fo + o, k] (k < kq; W2 [fi fo, kq] the edge network's
+// last weight, indexed as PyG's .view(in, out) does), b2[col fo + o] for k = kq, and lin_w[o, col] (the root weight) behind them.
+// A pure permutation: every float of the result is a float of the input
+inline std::vector<float> nnconv_fold(const float *w2, const float *b2, const float *lin_w, size_t kq, size_t fi, size_t fo)
+{
+    const size_t ld = (kq + 2) * fi;
+    std::vector<float> w(fo * ld);
+    for (size_t o = 0; o < fo; o++)
+        for (size_t col = 0; col < fi; col++) {
+            for (size_t k = 0; k < kq; k++)
+                w[o * ld + k * fi + col] = w2[(col * fo + o) * kq + k];
+            w[o * ld + kq * fi + col] = b2[col * fo + o];
+            w[o * ld + (kq + 1) * fi + col] = lin_w[o * fi + col];
+        }
+    return w;
+}
+
 constexpr int GAT_PARAM_SLOTS = 6; // a GATv2 layer's canonical tensors (gnnb_gat.h); one more with edge features (gnnb_gat_edge.h)
 constexpr int TF_PARAM_SLOTS = 8;  // a TransformerConv layer's canonical tensors (gnnb_transformer.h); one more with edge features
                                    // (gnnb_transformer_edge.h)
@@ -550,16 +576,32 @@ constexpr int RG_PARAM_SLOTS = 8;  // a ResGatedGraphConv layer's canonical tens
 constexpr int GGNN_PARAM_SLOTS = 5; // a GatedGraphConv layer's canonical tensors (gnnb_ggnn.h)
 constexpr int GGNN_MAX_STEPS = 8;
 constexpr int RGCN_PARAM_SLOTS = 3; // an RGCNConv layer's canonical tensors (gnnb_rgcn.h)
+// an NNConv layer's canonical tensors (gnnb_nnconv.h): 4 with the linear edge network, 6 with the hidden one
+inline int nnconv_param_slots(int hidden) { return hidden > 0 ? 6 : 4; }
 constexpr int GAT1_PARAM_SLOTS = 4; // a GAT v1 layer's canonical tensors (gnnb_gatconv.h); two more with edge features (gnnb_gatconv_edge.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
 // their offsets in the image
 inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0,
-                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0)
+                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0, int nn_hidden = 0)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (nn_coefs > 0) { // (a GIN description whose layers are NNConv's; canonical order: nn.0.weight, nn.0.bias, [nn.2.weight,
+                        // nn.2.bias,] lin.weight, bias -- the bracketed pair with nn_hidden > 0 only; nn_coefs = K' + 1)
+        const size_t kq = (size_t)nn_coefs - 1;
+        const bool hid = nn_hidden > 0;
+        LayerOffsets g;
+        const float *const *q = hid ? p + 2 : p;
+        g.w_nn = im.push(nnconv_fold(q[0], q[1], q[2], kq, fi, fo));
+        g.b_nn = im.push(q[3], fo);
+        if (hid) {
+            g.w_nn1 = im.push(p[0], kq * (size_t)edge_dim);
+            g.b_nn1 = im.push(p[1], kq);
+        }
+        return g;
+    }
     if (rgcn_relations > 0) { // (a GIN description whose layers are RGCNConv's; canonical order: weight, root, bias)
         LayerOffsets g;
         g.w_rgcn = im.push(rgcn_stack(p[0], p[1], (size_t)rgcn_relations, fi, fo));
@@ -705,13 +747,16 @@ struct BuiltWeights {
 // per layer; no fragment copy -- it takes no stack kernel); with edge_dim > 0 besides, GAT v1 with edge features (six tensors per
 // layer).  ggnn_steps > 0: a GatedGraphConv model (a GIN description, five tensors per layer; no execution-order copy).
 // rgcn_relations > 0: an RGCNConv model (a GIN description, three tensors per layer; no execution-order copy).
+// nn_coefs > 0: an NNConv model (a GIN description with edge_dim; four tensors per layer, six with nn_hidden > 0; no execution-order copy).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
-                                       int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0)
+                                       int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0,
+                                       int nn_hidden = 0)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = rgcn_relations > 0 ? RGCN_PARAM_SLOTS
+    const int slots = nn_coefs > 0     ? nnconv_param_slots(nn_hidden)
+                      : rgcn_relations > 0 ? RGCN_PARAM_SLOTS
                       : ggnn_steps > 0 ? GGNN_PARAM_SLOTS
                       : gat1_heads > 0 ? GAT1_PARAM_SLOTS + (edge_dim ? 2 : 0)
                       : gated         ? RG_PARAM_SLOTS
@@ -720,13 +765,13 @@ inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, c
                                       : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;
     for (int l = 0; l < d.num_layers; l++, pi += slots)
-        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps, rgcn_relations);
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps, rgcn_relations, nn_coefs, nn_hidden);
     const bool have_w1f = gat_heads == 0 && gat1_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));
     // (a GINE model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model, an RGCNConv model take no stack
     // kernel: no execution-order copy)
-    const bool have_gin = edge_dim == 0 && tf_heads == 0 && !gated && ggnn_steps == 0 && rgcn_relations == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
+    const bool have_gin = edge_dim == 0 && nn_coefs == 0 && tf_heads == 0 && !gated && ggnn_steps == 0 && rgcn_relations == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
                           d.out_dim <= d.hidden_dim && d.out_dim % 4 == 0;
     if (have_gin) {
         const WeightBias g = gin_execution_order(d, im.img, lo.conv);

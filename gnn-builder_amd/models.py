@@ -1011,6 +1011,66 @@ class RGCNConv_GNNB(nn.Module):
         return self.conv(x, edge_index, edge_type)
 
 
+# --------------------------------------------------------------------------------------- NNConv
+class _NNConv(nn.Module):
+    """PyG's ``NNConv(in_channels, out_channels, nn, aggr='add' | 'mean', root_weight=True, bias=True)`` -- the edge-conditioned
+    convolution of Gilmer et al.'s MPNN: the edge features produce the weight matrix the neighbour is multiplied by::
+
+        out_i = lin(x_i) + bias + aggr_{j -> i} x_j @ nn(e_ij).view(in, out)
+
+    ``nn`` is ``Sequential(Linear(d, in * out))`` (``hidden=0``) or ``Sequential(Linear(d, K), ReLU(), Linear(K, in * out))``
+    (``hidden=K``).  Duplicate edges count as often as they occur, an explicit ``(v, v)`` edge is an ordinary edge, no self loop is
+    added or removed; ``mean`` divides by the in-degree and gives 0 for a node without in-edges.  Parameters with PyG's
+    ``state_dict`` names -- ``nn.0.weight``, ``nn.0.bias``, (``nn.2.weight``, ``nn.2.bias``,) ``lin.weight`` [out, in], ``bias``
+    [out].  This plain form materialises ``[E, in, out]``."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, hidden: int = 0, aggr: str = "add"):
+        super().__init__()
+        self.in_channels, self.out_channels, self.edge_dim, self.hidden, self.aggr = in_channels, out_channels, edge_dim, hidden, aggr
+        if hidden:
+            self.nn = nn.Sequential(nn.Linear(edge_dim, hidden), nn.ReLU(), nn.Linear(hidden, in_channels * out_channels))
+        else:
+            self.nn = nn.Sequential(nn.Linear(edge_dim, in_channels * out_channels))
+        self.lin = nn.Linear(in_channels, out_channels, bias=False)
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        src, dst = edge_index[0].long(), edge_index[1].long()
+        e = edge_attr.to(x.dtype).reshape(src.numel(), self.edge_dim)
+        theta = self.nn(e).view(-1, self.in_channels, self.out_channels)
+        msg = torch.matmul(x[src].unsqueeze(1), theta).squeeze(1)
+        agg = x.new_zeros(x.size(0), self.out_channels).index_add(0, dst, msg)
+        if self.aggr == "mean":
+            cnt = x.new_zeros(x.size(0)).index_add(0, dst, x.new_ones(dst.numel()))
+            agg = agg / cnt.clamp(min=1).unsqueeze(-1)
+        return agg + self.lin(x) + self.bias
+
+
+class NNConv_GNNB(nn.Module):
+    """The edge-conditioned convolution (no class of the reference): PyG's ``NNConv``.  ``GNNModel(..., gnn_conv=NNConv_GNNB,
+    graph_input_edge_dim=d, gnn_edge_hidden=K, gnn_aggr="add" | "mean")`` stacks it (``d`` in 1 .. 16, ``K`` in 0 .. 16, ``K = 0``: the
+    single-linear edge network); ``forward(x, edge_index, edge_attr)`` with the same ``edge_attr`` for every layer.  The accelerated
+    path is ``runtime.CompiledModel.from_model`` with ``forward_edges`` / ``forward_pyg_edges`` (C ABI ``include/gnnb_nnconv.h``: one
+    launch of csrc/k_nnconv.hip -- aggregated BEFORE the transform -- and one GEMM per layer).  ``Project`` does not generate such
+    designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, hidden: int = 0, aggr: str = "add", p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        if not isinstance(edge_dim, int) or isinstance(edge_dim, bool) or not 1 <= edge_dim <= 16:
+            raise ValueError(f"edge_dim must be an int in 1 .. 16 (got {edge_dim!r})")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.edge_dim = edge_dim
+        self.hidden = hidden
+        self.aggr = aggr
+        self.p_in = p_in
+        self.p_out = p_out
+        self.conv = _NNConv(in_channels, out_channels, edge_dim, hidden, aggr)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        return self.conv(x, edge_index, edge_attr)
+
+
 # --------------------------------------------------------------------------------------- pooling / MLP
 SUPPORTED_GLOBAL_POOLING_AGGRS = {"add": "SumAggregation", "max": "MaxAggregation", "mean": "MeanAggregation"}
 SUPPORTED_GLOBAL_POOLING_MODE = ["cat"]
@@ -1123,20 +1183,21 @@ class MLP(nn.Module):
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
                        GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB,
-                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB, GatedGraphConv_GNNB, RGCNConv_GNNB]
+                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB, GatedGraphConv_GNNB, RGCNConv_GNNB, NNConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
               PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
               TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated", ResGatedGraphEConv_GNNB: "resgatede",
-              GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate", GatedGraphConv_GNNB: "ggnn", RGCNConv_GNNB: "rgcn"}
+              GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate", GatedGraphConv_GNNB: "ggnn", RGCNConv_GNNB: "rgcn", NNConv_GNNB: "nnconv"}
 # convs that take edge_attr, and what the messages call them
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE",
-               ResGatedGraphEConv_GNNB: "ResGatedE", GATv1EConv_GNNB: "GATE"}
+               ResGatedGraphEConv_GNNB: "ResGatedE", GATv1EConv_GNNB: "GATE", NNConv_GNNB: "NNConv"}
 MAX_EDGE_DIM = 16  # of a GINE, PNAE, GATv2E, TransformerE, ResGatedE or GATE model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h, gnnb_transformer_edge.h, gnnb_resgated_edge.h, gnnb_gatconv_edge.h)
 _GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # the GATv2 convs (heads and negative_slope travel beside a GCN description)
 _TF_CONVS = (TransformerConv_GNNB, TransformerEConv_GNNB)  # the TransformerConv convs (heads travel beside a GIN description)
 _GAT1_CONVS = (GATv1Conv_GNNB, GATv1EConv_GNNB)  # PyG's GATConv (heads and negative_slope travel beside a GCN description: include/gnnb_gatconv.h, gnnb_gatconv_edge.h)
 _HEAD_CONVS = _GAT_CONVS + _TF_CONVS + _GAT1_CONVS  # convs with attention heads: the ones that take gnn_heads
 MAX_RGCN_RELATIONS = 8  # of an RGCNConv model (include/gnnb_rgcn.h): edge types in [0, relations), beside a GIN description
+MAX_NNCONV_HIDDEN = 16  # of an NNConv model (include/gnnb_nnconv.h): the edge network's hidden width, 0 for a single linear
 MAX_GGNN_STEPS = 8  # of a GatedGraphConv model (include/gnnb_ggnn.h): steps per layer, beside a GIN description
 
 
@@ -1149,7 +1210,8 @@ class GNNModel(nn.Module):
                  gnn_conv: TorchModuleArg, gnn_activation: TorchModuleArg, gnn_skip_connection: bool,
                  global_pooling: GlobalPooling, mlp_head: MLP,
                  output_activation: TorchModuleArgOptional, gnn_p_in: int = 1, gnn_p_hidden: int = 1,
-                 gnn_p_out: int = 1, gnn_heads: int = 1, gnn_steps: int = 1, gnn_relations: int = 1) -> None:
+                 gnn_p_out: int = 1, gnn_heads: int = 1, gnn_steps: int = 1, gnn_relations: int = 1,
+                 gnn_edge_hidden: int = 0, gnn_aggr: str = "add") -> None:
         super().__init__()
         self.graph_input_feature_dim = graph_input_feature_dim
         self.graph_input_edge_dim = graph_input_edge_dim
@@ -1206,6 +1268,17 @@ class GNNModel(nn.Module):
             conv_kwargs = {**conv_kwargs, "relations": gnn_relations}
         elif gnn_relations != 1:
             raise ValueError(f"gnn_relations={gnn_relations!r}: only an RGCNConv model (gnn_conv=RGCNConv_GNNB) has relations")
+
+        self.gnn_edge_hidden, self.gnn_aggr = gnn_edge_hidden, gnn_aggr
+        if self.gnn_conv is NNConv_GNNB:
+            if not isinstance(gnn_edge_hidden, int) or isinstance(gnn_edge_hidden, bool) or not 0 <= gnn_edge_hidden <= MAX_NNCONV_HIDDEN:
+                raise ValueError(f"an NNConv model needs gnn_edge_hidden, an int in 0 .. {MAX_NNCONV_HIDDEN} (got {gnn_edge_hidden!r})")
+            if gnn_aggr not in ("add", "mean"):
+                raise ValueError(f"an NNConv model needs gnn_aggr 'add' or 'mean' (got {gnn_aggr!r})")
+            conv_kwargs = {**conv_kwargs, "hidden": gnn_edge_hidden, "aggr": gnn_aggr}
+        elif gnn_edge_hidden != 0 or gnn_aggr != "add":
+            raise ValueError(f"gnn_edge_hidden={gnn_edge_hidden!r}, gnn_aggr={gnn_aggr!r}: only an NNConv model (gnn_conv=NNConv_GNNB) has "
+                             "an edge network and an aggr")
 
         self.global_pooling = global_pooling
         self.mlp_head = mlp_head  # registered before gnn_convs: parameter order mlp_head_*, gnn_convs_*
@@ -1338,6 +1411,8 @@ class GNNModel(nn.Module):
             gat = {"steps": int(self.gnn_steps)}
         elif self.gnn_conv is RGCNConv_GNNB:  # (a GIN description on the C side, relations beside it: include/gnnb_rgcn.h)
             gat = {"relations": int(self.gnn_relations)}
+        elif self.gnn_conv is NNConv_GNNB:  # (a GIN description on the C side, edge_dim, hidden and aggr beside it: include/gnnb_nnconv.h)
+            gat = {"edge_hidden": int(self.gnn_edge_hidden), "aggr": str(self.gnn_aggr)}
         return {
             "conv": _CONV_NAME[self.gnn_conv],
             "num_layers": self.gnn_num_layers,
@@ -1388,6 +1463,9 @@ class GNNModel(nn.Module):
         # (PyG's state_dict order: the per-step message weights [steps, out, out], then the one GRU cell: include/gnnb_ggnn.h)
         per_conv["ggnn"] = ["conv_weight", "conv_rnn_weight_ih", "conv_rnn_weight_hh", "conv_rnn_bias_ih", "conv_rnn_bias_hh"]
         per_conv["rgcn"] = ["conv_weight", "conv_root", "conv_bias"]  # (PyG's state_dict order: include/gnnb_rgcn.h)
+        # (the edge network, then the root weight and the bias: include/gnnb_nnconv.h)
+        per_conv["nnconv"] = ["conv_nn_0_weight", "conv_nn_0_bias"] + (["conv_nn_2_weight", "conv_nn_2_bias"] if self.gnn_edge_hidden else []) + [
+            "conv_lin_weight", "conv_bias"]
         per_conv = per_conv[self.spec()["conv"]]
         names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):

@@ -30,10 +30,10 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin", "rgcn": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin", "rgcn": "gin", "nnconv": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
 # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h,
 # "resgatede": gnnb_resgated_edge.h, "gate": gnnb_gatconv_edge.h)
-_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede", "gate")
+_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede", "gate", "nnconv")
 _GAT_CONVS = ("gatv2", "gatv2e")       # ... and of those with heads and negative_slope beside it
 # a GAT v1 model (include/gnnb_gatconv.h, spec["conv"] == "gat"): a GCN description, heads and negative_slope beside it, within GATv2's
 # limits -- a model kind of its own; with edge features ("gate", include/gnnb_gatconv_edge.h) edge_dim too
@@ -49,6 +49,10 @@ MAX_RESGATED_WIDTH = 256
 MAX_GGNN_STEPS, MAX_GGNN_WIDTH = 8, 256
 # an RGCNConv model (include/gnnb_rgcn.h, spec["conv"] == "rgcn"): its description is GIN's too, the relation count beside it
 MAX_RGCN_RELATIONS, MAX_RGCN_WIDTH = 8, 256
+# an NNConv model (include/gnnb_nnconv.h, spec["conv"] == "nnconv"): its description is GIN's too; edge_dim, the edge network's
+# hidden width (0: a single linear) and aggr beside it
+MAX_NNCONV_HIDDEN, MAX_NNCONV_WIDTH = 16, 256
+NN_AGGR = {"add": 0, "mean": 1}  # gnnb_nn_aggr
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -281,6 +285,15 @@ ABI_RGCN = {
 }
 
 
+# ... and of include/gnnb_nnconv.h (NNConv models, aggregated before the transform), in its order
+ABI_NNCONV = {
+    "gnnb_nnconv_model_num_params": (_I, [_DESC, _I, _I]),
+    "gnnb_nnconv_model_create": (_I, [_DESC, _I, _I, _I, _PP, _I, _PP]),
+    "gnnb_model_nnconv_hidden": (_I, [_P]),
+    "gnnb_aggregate_nnconv": (_I, [_P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -332,7 +345,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
         for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER,
                                            **ABI_TRANSFORMER_EDGE, **ABI_RESGATED, **ABI_RESGATED_EDGE, **ABI_GATCONV,
-                                           **ABI_GATCONV_EDGE, **ABI_GGNN, **ABI_RGCN}.items():
+                                           **ABI_GATCONV_EDGE, **ABI_GGNN, **ABI_RGCN, **ABI_NNCONV}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -483,6 +496,7 @@ class CompiledModel:
         self.gatconv_heads = int(spec.get("heads", 1) or 0) if spec.get("conv") in _GATCONV_CONVS else 0
         self.ggnn_steps = int(spec.get("steps", 1) or 0) if spec.get("conv") == "ggnn" else 0
         self.rgcn_relations = int(spec.get("relations", 1) or 0) if spec.get("conv") == "rgcn" else 0
+        self.nnconv_hidden = int(spec.get("edge_hidden", 0) or 0) if spec.get("conv") == "nnconv" else 0
         self.spec, self.desc = dict(spec), None
         self.max_graphs, self.max_nodes, self.max_edges = int(max_graphs), int(max_nodes), int(max_edges)
         self.lib = load_library(require_gpu=True)
@@ -494,7 +508,10 @@ class CompiledModel:
         # (an edge model's own pair of entries: gnnb_edge.h for GINE, gnnb_pna_edge.h for PNA with edge features)
         num_params, create = ((self.lib.gnnb_pna_edge_model_num_params, self.lib.gnnb_pna_edge_model_create) if spec.get("conv") == "pnae" else
                               (self.lib.gnnb_edge_model_num_params, self.lib.gnnb_edge_model_create))
-        n_expect = (self.lib.gnnb_gat_edge_model_num_params(C.byref(self.desc), self.gat_heads, self.edge_dim) if spec.get("conv") == "gatv2e" else
+        if spec.get("conv") == "nnconv" and spec.get("aggr", "add") not in NN_AGGR:
+            raise GnnbError(f"an NNConv model needs spec['aggr'] in {sorted(NN_AGGR)}, got {spec.get('aggr')!r}")
+        n_expect = (self.lib.gnnb_nnconv_model_num_params(C.byref(self.desc), self.edge_dim, self.nnconv_hidden) if spec.get("conv") == "nnconv" else
+                    self.lib.gnnb_gat_edge_model_num_params(C.byref(self.desc), self.gat_heads, self.edge_dim) if spec.get("conv") == "gatv2e" else
                     self.lib.gnnb_transformer_edge_model_num_params(C.byref(self.desc), self.transformer_heads, self.edge_dim)
                     if spec.get("conv") == "transformere" else
                     self.lib.gnnb_resgated_edge_model_num_params(C.byref(self.desc), self.edge_dim) if spec.get("conv") == "resgatede" else
@@ -513,7 +530,10 @@ class CompiledModel:
         if len(host) != n_expect:
             raise GnnbError(f"model needs {n_expect} parameter tensors, got {len(host)}")
         arr = (C.c_void_p * len(host))(*[h.ctypes.data for h in host])
-        if spec.get("conv") == "gatv2e":  # (gnnb_gat_edge.h: a GCN description, heads, negative_slope and edge_dim beside it)
+        if spec.get("conv") == "nnconv":  # (gnnb_nnconv.h: a GIN description, edge_dim, the hidden width and aggr beside it)
+            _check(self.lib.gnnb_nnconv_model_create(C.byref(self.desc), self.edge_dim, self.nnconv_hidden, NN_AGGR[spec.get("aggr", "add")], arr,
+                                                     len(host), C.byref(self._model)))
+        elif spec.get("conv") == "gatv2e":  # (gnnb_gat_edge.h: a GCN description, heads, negative_slope and edge_dim beside it)
             _check(self.lib.gnnb_gat_edge_model_create(C.byref(self.desc), self.gat_heads, float(spec.get("negative_slope", 0.2)), self.edge_dim,
                                                        arr, len(host), C.byref(self._model)))
         elif spec.get("conv") == "transformere":  # (gnnb_transformer_edge.h: a GIN description, heads and edge_dim beside it)
@@ -1256,6 +1276,45 @@ class CompiledModel:
         ld = lambda t: int(t.stride(0)) if self._N > 1 else int(t.shape[1])  # noqa: E731  (one row: any stride describes it)
         _check(self.lib.gnnb_aggregate_ggnn(self._ws, _dptr(p), ld(p), _dptr(gh), ld(gh), _dptr(h), ld(h), hw, _optr(b_ih), _optr(skip),
                                             ACT[act], _dptr(out), w, _stream_ptr(stream)))
+        return out
+
+    def aggregate_nnconv(self, x, edge_attr, w1=None, b1=None, aggr: str = "add", out=None, stream=None):
+        """An NNConv layer's aggregate, in front of its GEMM (``gnnb_aggregate_nnconv``, csrc/k_nnconv.hip) on the prepared batch of a
+        workspace whose tables keep explicit self loops: ``A[i, k * width + c] = aggr_{j -> i} coef_k(e_ij) * x[j, c]`` ->
+        [N, (K' + 1) * width].  ``w1=None``: ``K' = edge_dim``, ``coef = [e ; 1]``; ``w1`` [K, edge_dim] and ``b1`` [K], ``K <= 16``:
+        ``K' = K``, ``coef = [relu(w1 e + b1) ; 1]``.  ``x`` [N, width <= 256], ``edge_attr`` [E, edge_dim <= 16] in COO order; ``aggr``
+        "add" or "mean"; ``out`` may be a column slice of a wider matrix (its row stride is passed on)."""
+        import torch
+        _require(x, "x", torch.float32, 2)
+        w = int(x.shape[1])
+        if int(x.shape[0]) != self._N or not 1 <= w <= MAX_NNCONV_WIDTH:
+            raise GnnbError(f"x must be [{self._N}, 1 .. {MAX_NNCONV_WIDTH}], got {tuple(x.shape)}")
+        if edge_attr is None or edge_attr.dim() != 2 or not 1 <= int(edge_attr.shape[1]) <= MAX_EDGE_DIM:
+            raise GnnbError(f"edge_attr must be [{self._E}, 1 .. {MAX_EDGE_DIM}]")
+        ed = int(edge_attr.shape[1])
+        _require_rows(edge_attr, "edge_attr", self._E, ed, x)
+        if (w1 is None) != (b1 is None):
+            raise GnnbError("w1 and b1 come together (both None: the linear edge network)")
+        hidden = 0
+        if w1 is not None:
+            _require(w1, "w1", torch.float32, 2, ed)
+            hidden = int(w1.shape[0])
+            if not 1 <= hidden <= MAX_NNCONV_HIDDEN or w1.device != x.device:
+                raise GnnbError(f"w1 must be [1 .. {MAX_NNCONV_HIDDEN}, {ed}] on {x.device}, got {tuple(w1.shape)} on {w1.device}")
+            _require(b1, "b1", torch.float32, 1, hidden)
+            if b1.device != x.device:
+                raise GnnbError(f"b1 must be on {x.device}")
+        if aggr not in NN_AGGR:
+            raise GnnbError(f"aggr must be one of {sorted(NN_AGGR)}, got {aggr!r}")
+        cols = ((hidden or ed) + 1) * w
+        if out is None:
+            out = torch.empty((self._N, cols), dtype=torch.float32, device=x.device)
+        _require_strided(out, "out", self._N, cols)
+        if int(out.shape[1]) != cols or out.device != x.device:
+            raise GnnbError(f"out must be [{self._N}, {cols}] on {x.device}, got {tuple(out.shape)} on {out.device}")
+        ldo = int(out.stride(0)) if self._N > 1 else cols
+        _check(self.lib.gnnb_aggregate_nnconv(self._ws, _dptr(x), w, _dptr(edge_attr) if self._E else None, ed, _optr(w1), _optr(b1), hidden,
+                                              NN_AGGR[aggr], _dptr(out), ldo, _stream_ptr(stream)))
         return out
 
     def rgcn_slots(self, edge_type, relations: int, stream=None):
