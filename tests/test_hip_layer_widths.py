@@ -1,6 +1,7 @@
-"""Whole models whose layers are unlike in width on the MI355X: ``out_dim != hidden`` for the eleven families whose scratch
+"""Whole models whose layers are unlike in width on the MI355X: ``out_dim != hidden`` for the twelve families whose scratch
 layout follows the layer's own width -- ``[k | q | v | r]`` [N, 4 fo], ``[xl | s_src | s_dst | pad]`` [N, fo + roundup4(2 heads)],
-``[q | k | v | r | qe]`` [N, 4 fo + roundup4(heads * edge_dim)], ``[p | gh]`` [N, 6 fo] with the per-step weight stride -- carved
+``[q | k | v | r | qe]`` [N, 4 fo + roundup4(heads * edge_dim)], ``[p | gh]`` [N, 6 fo] with the per-step weight stride, NNConv's
+``A`` [N, (K' + 1) fi] in front of a GEMM on the two K-segments ``[A | x]`` -- carved
 from scratch that the workspace sizes as a maximum over the layers, before a pooling and a head that read ``out_dim`` columns.  A
 stride, a scratch maximum or a derived weight slot taken from the wrong layer gives the right result whenever all layers are
 equally wide; here they are not: three layers (in 9 -> hidden -> hidden -> out), the widths the smallest that separate them -- a
@@ -20,6 +21,7 @@ import torch
 
 import ggnn_util
 import gine_util
+import nnconv_util
 import ref64 as R
 import workspace_life_util as W
 from gnnbuilder_amd import runtime, synthetic
@@ -34,7 +36,11 @@ GATED = ("resgated", "resgatede", "gine", "pnae")
 # (family, hidden, out_dim, layers, GatedGraphConv steps)
 CASES = [(f, h, o, 3, 0) for f in HEADED for h, o in ((32, 20), (20, 32))] + \
         [(f, h, o, 3, 0) for f in GATED for h, o in ((32, 21), (12, 40))] + \
-        [("ggnn", 12, 40, 3, 3), ("ggnn", 9, 12, 3, 2), ("ggnn", 4, 16, 1, 2)]  # (in <= hidden <= out; one layer: hidden is no layer's width)
+        [("ggnn", 12, 40, 3, 3), ("ggnn", 9, 12, 3, 2), ("ggnn", 4, 16, 1, 2)] + \
+        [("nnconv", 32, 21, 3, 0), ("nnconv", 12, 40, 3, 0)]  # (ggnn: in <= hidden <= out; one layer: hidden is no layer's width)
+# nnconv's edge network per (hidden, out): K = 0 (the linear one, K' = edge_dim 3) and K = 5; A's row stride (K' + 1) in is
+# 36 | 128 | 128 and 54 | 72 | 72 over the three layers
+NNCONV_EDGE_HIDDEN = {(32, 21): 0, (12, 40): W.NN_EDGE_HIDDEN}
 # pnae runs on grid features: (model seed, feature seed) per (hidden, out), chosen on the CPU the way PNA_SEEDS were -- the first
 # pair, feature seeds counted up from 160, that leaves no variance of the float64 reference within the margin of PyG's 1e-5
 # (variances_near_the_threshold, asserted below on the reference alone); the other families: model seed 0, features 160
@@ -64,6 +70,8 @@ def _t(a, dev):
 def widths_model(family, hidden, out_dim, layers, steps, seed=0):
     if family == "ggnn":
         return ggnn_util.make_ggnn_model(in_dim=W.IN_DIM, hidden=hidden, layers=layers, out_dim=out_dim, steps=steps, seed=seed)
+    if family == "nnconv":
+        return nnconv_util.make_model(W.IN_DIM, hidden, layers, W.EDGE_DIM, NNCONV_EDGE_HIDDEN[(hidden, out_dim)], seed=seed, out_dim=out_dim)
     return W.make_family_model(family, hidden=hidden, layers=layers, seed=seed, out_dim=out_dim)
 
 

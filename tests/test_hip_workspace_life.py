@@ -1,4 +1,6 @@
-"""One workspace across a stream of unlike batches on the MI355X, every conv family (``tests/workspace_life_util.py``).
+"""One workspace across a stream of unlike batches on the MI355X, every conv family (``tests/workspace_life_util.py``) but one:
+RGCN's entry point (``forward_types``) is a third kind that the runner does not have, and
+``test_hip_rgcn.test_one_workspace_rebuilds_its_records_for_every_batch`` covers its workspace.
 
 A ``CompiledModel`` that lives for a whole sequence sees batches whose graph, node and edge counts go up and down, through every
 entry point in turn, with the setters called between batches; after every forward one stage entry of the family runs on the
@@ -95,6 +97,8 @@ def _stage_call(cm, family, c, dev, out):
     if family == "gate":
         return cm.aggregate_gat_edges(d("xl"), d("s_src"), d("s_dst"), d("edge_attr"), d("a_edge"), bias=d("bias"), heads=W.HEADS,
                                       negative_slope=gatv2_util.SLOPE, out=out)
+    if family == "nnconv":  # (the entry takes the edge_dim from edge_attr's shape: a batch without an edge hands over [0, edge_dim])
+        return cm.aggregate_nnconv(d("x"), _t(c["ea"], dev), d("w1"), d("b1"), aggr="add", out=out)
     assert family == "ggnn", family
     return cm.aggregate_ggnn(d("p"), d("gh"), d("h"), b_ih=d("b_ih"), out=out)
 
@@ -166,7 +170,7 @@ class Runner:
                 row_ptr, col, in_deg = cm.tables_to_host()
                 res["tables"] = (row_ptr.copy(), col.copy(), in_deg.copy(), cm.edge_index_table_to_host().copy())
             if step.stage is not None:
-                wide = 4 * W.STAGE_W if self.family in ("pna", "pnae") else W.STAGE_W
+                wide = {"pna": 4, "pnae": 4, "nnconv": W.NN_EDGE_HIDDEN + 1}.get(self.family, 1) * W.STAGE_W
                 out = torch.full((tb.num_nodes, wide), float("nan"), dtype=torch.float32, device=dev)
                 try:
                     got = _stage_call(cm, self.family, step.stage, dev, out)
@@ -502,9 +506,10 @@ def test_a_captured_forward_between_unlike_eager_ones(dev):
     _captured_between_unlike_eager_ones(dev, "sage")
 
 
-@pytest.mark.parametrize("family", ["ggnn", "gate"])
+@pytest.mark.parametrize("family", ["ggnn", "gate", "nnconv"])
 def test_a_captured_forward_between_unlike_eager_ones_of(dev, family):
-    """The test above (it keeps its name) for two of the newer families.  gate: the capture is of ``forward_edges``.  ggnn: three
+    """The test above (it keeps its name) for three of the newer families.  gate, nnconv: the capture is of ``forward_edges``
+    (nnconv: ``A``'s row stride ``(K' + 1) in`` is 54 in the first layer and 192 in the second, inside one ``tmp0``).  ggnn: three
     steps per layer at hidden 9, where the captured graph has A's carve of the state buffers baked in -- the second one
     ``roundup4(9 N)`` floats into the scratch -- and the eager forward of the hub batch in between carves the same memory for
     another N, whose ``9 N`` has another remainder by 4."""
@@ -608,7 +613,7 @@ def test_degree_promise_between_prep_and_forward(dev, first, then):
     R.budget(got["out"], ref, base, what=step.name)
 
 
-@pytest.mark.parametrize("family", ["gine", "transformere", "gate", "resgatede"])
+@pytest.mark.parametrize("family", ["gine", "transformere", "gate", "resgatede", "nnconv"])
 def test_setters_between_prep_and_forward_edges(dev, family):
     """``forward_prepared_edges`` goes through the same body: every setter between ``graph_prep`` and it leaves the route
     (``layerwise``) and the bits alone."""

@@ -195,8 +195,8 @@ def test_the_pna_sequences_stay_clear_of_the_std_threshold(family):
         assert W.variances_near_the_threshold(model, b, b.x, ea) == 0
 
 
-# ---------------------------------------------------------------------------------------------------- the four newer families
-NEWER = ("resgatede", "gat", "gate", "ggnn")
+# ---------------------------------------------------------------------------------------------------- the five newer families
+NEWER = ("resgatede", "gat", "gate", "ggnn", "nnconv")
 
 
 @pytest.fixture(scope="module")
@@ -206,7 +206,7 @@ def newer_sequences():
 
 @pytest.mark.parametrize("family", NEWER)
 def test_the_newer_families_sequences_build(newer_sequences, family):
-    assert family in W.FAMILIES and (family in W.EDGE_FAMILIES) == (family in ("resgatede", "gate"))
+    assert family in W.FAMILIES and (family in W.EDGE_FAMILIES) == (family in ("resgatede", "gate", "nnconv"))
     model, batches, attrs = newer_sequences[family]
     assert len(batches) == len(attrs) == len(W.SIZES_UP_AND_DOWN) and batches[7] is batches[0]
     for b, ea in zip(batches, attrs):
@@ -216,6 +216,8 @@ def test_the_newer_families_sequences_build(newer_sequences, family):
             assert ea is None
     if family == "ggnn":  # (three steps per layer: both state buffers are written and read in turn)
         assert W.GGNN_STEPS == 3 and all(c.conv.num_layers == 3 for c in model.gnn_convs)
+    if family == "nnconv":  # (K' = 5 on rung 8, edge_dim 3 padded to 4: both strictly inside their rungs)
+        assert all((c.edge_dim, c.hidden) == (3, 5) for c in model.gnn_convs) and W.EDGE_DIM == 3 and W.NN_EDGE_HIDDEN == 5
 
 
 @pytest.mark.parametrize("family", NEWER)
@@ -227,11 +229,12 @@ def test_the_newer_families_stage_cases_hold_on_every_batch(newer_sequences, fam
     for i, b in enumerate(batches):
         c = W.stage_operands(family, b, 700 + i)
         if family in W.EDGE_FAMILIES:
-            assert c["edge_attr"].shape == (b.num_edges, W.EDGE_DIM)
+            assert c["ea" if family == "nnconv" else "edge_attr"].shape == (b.num_edges, W.EDGE_DIM)
         if family == "ggnn":
             assert c["h"].shape == (b.num_nodes, W.GGNN_H_WIDTH) and W.GGNN_H_WIDTH < W.STAGE_W
         ref, base, coo = W.stage_refs(family, b, c)
-        assert ref.shape == base.shape == (b.num_nodes, W.STAGE_W) and ref.dtype == np.float64 and base.dtype == np.float32
+        wide = (W.NN_EDGE_HIDDEN + 1 if family == "nnconv" else 1) * W.STAGE_W
+        assert ref.shape == base.shape == (b.num_nodes, wide) and ref.dtype == np.float64 and base.dtype == np.float32
         if b.num_nodes:
             gine_util.budget_by_degree(base, ref, base, coo, what=f"{family} {W.SIZES_UP_AND_DOWN[i]}")
 

@@ -89,7 +89,8 @@ def run_sequence(steps, run_long, run_fresh, reference, record=None):
         if step.same_as is not None:
             assert_same_bits(long, longs[step.same_as], f"(a) {what}: against step {step.same_as + 1} on the same object")
         refs = reference(step)
-        need = {k for k in ("out", "stage") if k in long}  # every number the object produced has a reference
+        # every number the object produced has a reference (NNConv's stage entry takes a batch without a node: [0, w] holds none)
+        need = {k for k in ("out", "stage") if k in long and np.size(long[k])}
         assert need <= set(refs), f"(b) {what}: no reference for {sorted(need - set(refs))}"
         if "out" in need:
             ref, base = refs["out"]
@@ -207,15 +208,17 @@ def variances_near_the_threshold(model, batch, x, edge_attr=None):
 
 # ---------------------------------------------------------------------------------------------------- one model per family
 FAMILIES = ("gcn", "gin", "sage", "pna", "gine", "pnae", "gatv2", "gatv2e", "transformer", "transformere", "resgated", "resgatede", "gat",
-            "gate", "ggnn")
-EDGE_FAMILIES = ("gine", "pnae", "gatv2e", "transformere", "resgatede", "gate")
+            "gate", "ggnn", "nnconv")
+EDGE_FAMILIES = ("gine", "pnae", "gatv2e", "transformere", "resgatede", "gate", "nnconv")
 GGNN_STEPS, GGNN_H_WIDTH = 3, 12  # three steps: both state buffers are written and read in turn; the stage's h narrower than its width
+NN_EDGE_HIDDEN = 5  # NNConv's edge network Linear(3, 5) -> ReLU -> Linear(5, in out): K' = 5 on rung 8, edge_dim 3 padded to 4
 IN_DIM, EDGE_DIM, HEADS = 9, 3, 4
 
 
 def make_family_model(family, hidden=32, layers=2, seed=0, out_dim=None):
     """The family's model from its existing maker: ``in_dim`` 9, all three pools, 4 heads where there are heads, ``edge_dim`` 3,
-    ``GGNN_STEPS`` steps per GatedGraphConv layer; ``out_dim``: the last layer's width (None: ``hidden``)."""
+    ``GGNN_STEPS`` steps per GatedGraphConv layer, ``NN_EDGE_HIDDEN`` hidden units in NNConv's edge network; ``out_dim``: the last
+    layer's width (None: ``hidden``)."""
     import gat_util
     import gate_util
     import gatv2_util
@@ -223,6 +226,7 @@ def make_family_model(family, hidden=32, layers=2, seed=0, out_dim=None):
     import gine_util
     import pnae_util
     import ggnn_util
+    import nnconv_util
     import resgated_util
     import resgatede_util
     import transformer_util
@@ -253,6 +257,8 @@ def make_family_model(family, hidden=32, layers=2, seed=0, out_dim=None):
         return gat_util.make_gat_model(heads=HEADS, **kw)
     if family == "gate":
         return gate_util.make_gate_model(edge_dim=EDGE_DIM, heads=HEADS, **kw)
+    if family == "nnconv":
+        return nnconv_util.make_model(edge_dim=EDGE_DIM, edge_hidden=NN_EDGE_HIDDEN, **kw)
     assert family == "ggnn", family
     return ggnn_util.make_ggnn_model(steps=GGNN_STEPS, **kw)
 
@@ -336,6 +342,9 @@ def stage_operands(family, batch, seed):
         return gat_util.stage_case(n, w, HEADS, "flat", seed=seed)
     if family == "gate":
         return gate_util.edge_case(batch.coo, n, w, HEADS, EDGE_DIM, "flat", seed=seed)
+    if family == "nnconv":  # (w1 / sqrt(d) against a b1 of at most 0.3: the ReLU cuts some edges of every hidden unit and passes others)
+        return dict(x=_uniform(seed, (n, w)), ea=gine_util.edge_attrs(e, EDGE_DIM, seed + 1),
+                    w1=_uniform(seed + 2, (NN_EDGE_HIDDEN, EDGE_DIM)) / np.float32(np.sqrt(EDGE_DIM)), b1=_uniform(seed + 3, NN_EDGE_HIDDEN, 0.3))
     assert family == "ggnn", family
     return ggnn_util.stage_case(n, w, GGNN_H_WIDTH, "flat")  # (h narrower than the stage: its zero-padded columns are exercised)
 
@@ -344,12 +353,14 @@ def stage_refs(family, batch, c):
     """(float64 restatement, the same in fp32, the edges of the tables for the in-degree classes) of the family's stage entry on
     operands ``c``.  What a reference needs to hold for the comparison to leave nothing out is asserted here, on the reference
     alone: no PNA variance near PyG's threshold; every non-self GAT score, every ResGated gate argument and gated value and every
-    GatedGraphConv neighbour sum and r and z argument exact in fp32."""
+    GatedGraphConv neighbour sum and r and z argument exact in fp32; every hidden unit of NNConv's edge network zero on some edge
+    and positive on another."""
     import gat_util
     import gate_util
     import gatv2_util
     import gatv2e_util
     import ggnn_util
+    import nnconv_util
     import pnae_util
     import resgated_util
     import resgatede_util
@@ -377,6 +388,12 @@ def stage_refs(family, batch, c):
     if family == "gine":
         ref = R.gine_agg64(c["x"], coo, c["ea"].astype(f8) @ c["we"].astype(f8).T + c["be"].astype(f8), STAGE_EPS)
         return ref, R.gine_agg64(c["x"], coo, (c["ea"] @ c["we"].T + c["be"]).astype(f4), STAGE_EPS, dtype=f4), coo
+    if family == "nnconv":  # [N, (NN_EDGE_HIDDEN + 1) STAGE_W], "add"
+        args = (c["x"], coo, c["ea"], c["w1"], c["b1"], "add")
+        if batch.num_edges:  # every hidden unit is cut by the ReLU on some edge and passes on another
+            hid = nnconv_util.coefs(c["ea"], c["w1"], c["b1"], f8)[:, :-1]
+            assert (hid == 0).any(0).all() and (hid > 0).any(0).all()
+        return nnconv_util.aggregate_ref(*args), nnconv_util.aggregate_ref(*args, dtype=f4), coo
     if family == "gatv2e" and batch.num_edges == 0:  # (no attribute row: every self loop's mean attribute is 0 -- GATv2 on self loops)
         family = "gatv2"
     if family == "transformere" and batch.num_edges == 0:  # (no edge: nothing to project -- TransformerConv, every row its root)
