@@ -28,7 +28,7 @@ import jinja2
 import numpy as np
 import torch
 
-from .models import (GATv1Conv_GNNB, GATv1EConv_GNNB, GATv2Conv_GNNB, GATv2EConv_GNNB, GINEConv_GNNB, GNNModel, GatedGraphConv_GNNB, NNConv_GNNB, PNAEConv_GNNB, RGCNConv_GNNB, ResGatedGraphConv_GNNB,
+from .models import (GATv1Conv_GNNB, GATv1EConv_GNNB, GATv2Conv_GNNB, GATv2EConv_GNNB, GENConv_GNNB, GENEConv_GNNB, GINEConv_GNNB, GNNModel, GatedGraphConv_GNNB, NNConv_GNNB, PNAEConv_GNNB, RGCNConv_GNNB, ResGatedGraphConv_GNNB,
                      ResGatedGraphEConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB)
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
@@ -149,6 +149,11 @@ class Project:
             raise NotImplementedError(
                 "Project does not generate NNConv designs: the generated shim and the templates have no edge-conditioned layer; run "
                 "the model through runtime.CompiledModel.from_model(model, ...).forward_edges / forward_pyg_edges")
+        if getattr(model, "gnn_conv", None) in (GENConv_GNNB, GENEConv_GNNB):
+            raise NotImplementedError(
+                "Project does not generate GENConv designs: the generated shim and the templates have no softmax aggregate; run the "
+                "model through runtime.CompiledModel.from_model(model, ...).forward / forward_pyg (GENEConv_GNNB: forward_edges / "
+                "forward_pyg_edges)")
         self.model = model
         self.dataset = dataset
         self.name = name

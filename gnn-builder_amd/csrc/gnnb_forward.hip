@@ -79,7 +79,7 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     // attention; a ResGatedGraphConv model: none forms the gate; a GatedGraphConv model: none forms the GRU cell; an RGCNConv
     // model: none selects a weight by relation
     if (model->edge_dim || model->gat_heads || model->gat1_heads || model->tf_heads || model->gated || model->ggnn_steps || model->rgcn_relations ||
-        model->nn_coefs)
+        model->nn_coefs || model->gen) // (an NNConv model, a GENConv model: no stack kernel forms their aggregates)
         return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
@@ -391,6 +391,31 @@ static int nnconv_layer(const LayerCtx &c)
     return c.linear(segs, 2, p.w_nn, lda + fi, p.b_nn, c.rows(c.skip, fi), c.rows(c.nxt, fo), fo, d.activation);
 }
 
+// GENConv (gnnb_gen.h; a GIN description with the "gen" mark and edge_dim 0 .. 16 beside it, so the tables keep explicit (v, v) edges).
+// in != out: ONE GEMM x -> [s | r] [N, 2 fo] in ws->tmp0 on w_sr = [lin_src.weight ; lin_dst.weight] in the model's math mode; in ==
+// out (every middle layer): none, s = r = x.  Then ONE k_gen_aggregate launch -- the per-column softmax of the messages, the root
+// term in its epilogue -- into ws->agg, and the MLP's two GEMMs, hidden [N, 2 fo] in ws->tmp0 (the [s | r] it overwrites has been
+// read by then: one stream), the skip term and the activation in the second's epilogue: GINE's tail.  None of the fused rungs
+static int gen_layer(const LayerCtx &c)
+{
+    const LayerWeights &p = c.model->conv[c.l];
+    const int fi = c.fi, fo = c.fo, ed = c.model->edge_dim;
+    const float *s = c.cur, *r = c.cur;
+    int ld = fi, rc;
+    if (fi != fo) {
+        float *sr = c.ws->tmp0; // ([max_nodes, >= 2 fo]: gnnb_workspace_create)
+        if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_sr, fi, p.b_sr, nullptr, c.rows(sr, 2 * fo), 2 * fo, GNNB_ACT_NONE)))
+            return rc;
+        s = sr, r = sr + fo, ld = 2 * fo;
+    }
+    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+        GNNB_HIP_TRY(launch_gen_aggregate(c.tv, s, ld, r, ld, fo, c.edge_attr, ed, p.edge_w, ed, p.edge_b, c.model->gen_t[c.l], GEN_EPS_M, c.ws->agg,
+                                          fo, c.hs()));
+    if ((rc = c.linear1(c.rows(c.ws->agg, fo), fo, p.w0, fo, p.b0, nullptr, c.rows(c.ws->tmp0, 2 * fo), 2 * fo, GNNB_ACT_RELU)))
+        return rc;
+    return c.linear1(c.rows(c.ws->tmp0, 2 * fo), 2 * fo, p.w1, 2 * fo, p.b1, c.rows(c.skip, fo), c.rows(c.nxt, fo), fo, c.model->desc.activation);
+}
+
 // GIN's first linear + ReLU on the eps-weighted sum -> ws->tmp0
 static int gin_hidden(const LayerCtx &c)
 {
@@ -572,6 +597,7 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
             rc = model->tf_heads ? transformer_layer(c) : model->gated ? resgated_layer(c) : model->ggnn_steps ? ggnn_layer(c)
                  : model->rgcn_relations                                                                                 ? rgcn_layer(c)
                  : model->nn_coefs                                                                                       ? nnconv_layer(c)
+                 : model->gen                                                                                            ? gen_layer(c)
                                                                                                                          : gin_layer(c);
             break;
         case GNNB_CONV_SAGE: rc = sage_layer(c); break;
@@ -852,7 +878,7 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
         model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope || model->gat1_heads != ws->gat1_heads ||
         model->tf_heads != ws->tf_heads || model->gated != ws->gated ||
         model->ggnn_steps != ws->ggnn_steps || model->rgcn_relations != ws->rgcn_relations || model->nn_coefs != ws->nn_coefs ||
-        model->nn_hidden != ws->nn_hidden || model->nn_mean != ws->nn_mean)
+        model->nn_hidden != ws->nn_hidden || model->nn_mean != ws->nn_mean || model->gen != ws->gen)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;
@@ -898,6 +924,9 @@ static int check_edge_forward(const gnnb_model *model, const gnnb_workspace *ws,
         return fail(GNNB_ERR_INVALID, "null argument to %s", entry);
     if (const int rc = refuse_rgcn_model(model, ws, entry, strstr(entry, "prepared") ? "gnnb_forward_prepared_types" : "gnnb_forward_batched_types"))
         return rc;
+    if (model->gen && !model->edge_dim)
+        return fail(GNNB_ERR_INVALID, "%s: a GENConv model without edge features (gnnb_gen_model_create, edge_dim 0) takes no edge attributes: "
+                                      "call %s (gnnb_gen.h)", entry, strstr(entry, "prepared") ? "gnnb_forward_prepared" : "gnnb_forward_batched");
     if (!model->edge_dim)
         return fail(GNNB_ERR_INVALID, "%s takes a model of gnnb_edge_model_create; this one has no edge weights", entry);
     if (model->edge_dim != ws->edge_dim)

@@ -23,6 +23,7 @@
 #include "gnnb_ggnn.h"
 #include "gnnb_rgcn.h"
 #include "gnnb_nnconv.h"
+#include "gnnb_gen.h"
 
 namespace gnnb {
 
@@ -76,6 +77,10 @@ struct gnnb_model {
                             // coefficients per edge -- every layer has w_nn, b_nn (and w_nn1, b_nn1 with nn_hidden > 0) and none of GIN's slots
     int nn_hidden = 0;      // ... its edge network's hidden width K (0: the linear edge network, K' = edge_dim)
     int nn_mean = 0;        // ... and 1 for aggr = mean (0: add)
+    int gen = 0;            // 1: a GENConv model (gnnb_gen_model_create; desc is a GIN description, edge_dim 0 .. 16 beside it) -- every layer
+                            // has GIN's w0 [2 out, out], b0, w1 [out, 2 out], b1 as its MLP, w_sr, b_sr where in != out, and edge_w [out,
+                            // edge_dim], edge_b with edge_dim > 0
+    std::vector<float> gen_t; // ... and its softmax temperature per layer, read at upload and passed by value at every launch
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };
@@ -103,6 +108,7 @@ struct gnnb_workspace {
     int ggnn_steps = 0;          // ... and its steps when it is a GatedGraphConv model (0: it is not)
     int rgcn_relations = 0;      // ... and its relations when it is an RGCNConv model (0: it is not)
     int nn_coefs = 0, nn_hidden = 0, nn_mean = 0; // ... and its coefficient count, hidden width and aggr when it is an NNConv model
+    int gen = 0;                 // ... and 1 when it is a GENConv model
     gnnb::RgcnSlot *rgcn_rec = nullptr; // such a model's workspace only: the slot records of the batch (k_rgcn_slots), 8 max_edges bytes,
                                  // rebuilt by every _types forward
     char *type_blob = nullptr;   // gnnb_workspace_enable_type_ingest: edge_type in COO row order, int32 [max_edges], one allocation
@@ -175,6 +181,9 @@ int refuse_ggnn_model(const gnnb_model *model, const gnnb_workspace *ws, const c
 
 // ... and for an RGCNConv model / its workspace (gnnb_rgcn.h): `use` names the _types entry
 int refuse_rgcn_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
+
+// ... and for a GENConv model / its workspace (gnnb_gen.h)
+int refuse_gen_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
 
 // gnnb_runtime.hip, for the forward (gnnb_forward.hip) -- each is described where it is defined
 int ensure_gcoef(gnnb_workspace *ws, void *stream);

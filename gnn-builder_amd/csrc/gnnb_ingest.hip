@@ -217,6 +217,8 @@ int gnnb_forward_pyg_ordered(const gnnb_model *model, gnnb_workspace *ws, const 
         return rc;
     if (const int rc = refuse_rgcn_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg_types"))
         return rc;
+    if (const int rc = refuse_gen_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg"))
+        return rc;
     const float *x_ord = nullptr;
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr, *perm = nullptr;
     int g0 = 0, n0 = 0, e0 = 0;

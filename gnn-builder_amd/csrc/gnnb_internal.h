@@ -401,6 +401,15 @@ hipError_t launch_rgcn_aggregate(const BatchTables &t, const RgcnSlot *rec, cons
 constexpr int NN_MAX_WIDTH = 256, NN_MAX_EDGE_DIM = 16, NN_MAX_HIDDEN = 16;
 hipError_t launch_nnconv_aggregate(const BatchTables &t, const float *x, int width, const float *edge_attr, int edge_dim, const float *w1,
                                    const float *b1, int hidden, int mean, float *out, int ldo, hipStream_t s);
+// GENConv's softmax aggregate (k_gen.hip; gnnb_gen.h): out[i, c] = sum_j a_ijc m_ijc + r[i, c] with m_ij = relu(s[j] + we e_ij + be) +
+// eps_m and a_ij the per-column softmax of t m over row i's in-edges; s, r, out rows of stride lds, ldr, ldo >= width (the column
+// blocks of one GEMM result), r may be nullptr; edge_dim 0: no edge term, edge_attr / we / be unread.  Tables that keep explicit
+// (v, v) edges.  hipErrorInvalidValue: nothing launched
+constexpr int GEN_MAX_WIDTH = 256;
+constexpr float GEN_EPS_M = 1e-7f; // what a GENConv layer adds to every message (PyG's eps)
+hipError_t launch_gen_aggregate(const BatchTables &t, const float *s, int lds, const float *r, int ldr, int width, const float *edge_attr,
+                                int edge_dim, const float *we, int ldwe, const float *be, float temp, float eps_m, float *out, int ldo,
+                                hipStream_t st);
 // the ingest's edge types in COO row order (k_ingest.hip): out[i] = (int32) edge_type[state[INGEST_STATE_UNSORTED] ? idx[i] : i], -1
 // for a value that does not fit (k_rgcn_slots flags it); idx, state: as launch_edge_attr_order's
 hipError_t launch_edge_type_order(const long long *edge_type, const int32_t *idx, const int32_t *state, int32_t *out, int num_edges, hipStream_t s);

@@ -262,6 +262,29 @@ int count_nnconv_params(const gnnb_model_desc *desc, int edge_dim, int hidden)
     return nnconv_param_slots(hidden) * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
+// parameter tensors of a GENConv model (gnnb_gen.h): a GIN description (its tables keep explicit (v, v) edges) without the fixed-point
+// emulation, edge_dim 0 (no edge features) .. 16, every layer width at most 256; a layer's count depends on its widths
+int count_gen_params(const gnnb_model_desc *desc, int edge_dim)
+{
+    int rc = validate_desc(desc);
+    if (rc != GNNB_OK)
+        return rc;
+    if (edge_dim < 0 || edge_dim > 16)
+        return fail(GNNB_ERR_INVALID, "edge_dim %d: a GENConv model takes edge_dim 1 .. 16, or 0 for none", edge_dim);
+    if (desc->conv_type != GNNB_CONV_GIN)
+        return fail(GNNB_ERR_INVALID, "a GENConv model's description is a GIN description (conv_type %d given)", desc->conv_type);
+    if (desc->fpx_w != 0)
+        return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover GENConv models (fpx_w must be 0)");
+    int n = 2 * desc->mlp_num_linear;
+    for (int l = 0; l < desc->num_layers; l++) {
+        const LayerDims ld = layer_dims(*desc, l);
+        if (ld.fin > GEN_MAX_WIDTH || ld.fout > GEN_MAX_WIDTH)
+            return fail(GNNB_ERR_INVALID, "layer %d's widths %d -> %d: a GENConv layer is at most %d wide", l, ld.fin, ld.fout, GEN_MAX_WIDTH);
+        n += gen_param_slots(ld.fin, ld.fout, edge_dim);
+    }
+    return n;
+}
+
 // What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
 // type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
 // (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features), or heads of a
@@ -281,6 +304,8 @@ struct ModelKind {
     int ggnn_steps = 0;
     int rgcn_relations = 0;
     int nn_coefs = 0, nn_hidden = 0, nn_mean = 0; // an NNConv model (gnnb_nnconv_model_create: a GIN description, edge_dim too)
+    const float *gen_t = nullptr; // non-null: a GENConv model (gnnb_gen_model_create: a GIN description, edge_dim 0 .. 16 too) and its
+                                  // temperatures, one per layer
     static ModelKind plain() { return {}; }
     static ModelKind edges(int edge_dim, int base)
     {
@@ -350,6 +375,12 @@ struct ModelKind {
         k.nn_mean = mean ? 1 : 0;
         return k;
     }
+    static ModelKind gen(int edge_dim, const float *t_per_layer)
+    {
+        ModelKind k = edges(edge_dim, GNNB_CONV_GIN);
+        k.gen_t = t_per_layer;
+        return k;
+    }
     static ModelKind resgated_edges(int edge_dim)
     {
         ModelKind k = resgated();
@@ -358,7 +389,7 @@ struct ModelKind {
     }
 };
 
-// the body of the fourteen *_model_create entries
+// the body of the fifteen *_model_create entries
 int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float *const *host_params, int num_params, gnnb_model **out_model)
 {
     if (!out_model)
@@ -366,7 +397,8 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
     const int gat1_heads = kind.gat1_heads;
-    int expect = kind.nn_coefs != 0 ? count_nnconv_params(desc, edge_dim, kind.nn_hidden)
+    int expect = kind.gen_t != nullptr ? count_gen_params(desc, edge_dim)
+                 : kind.nn_coefs != 0 ? count_nnconv_params(desc, edge_dim, kind.nn_hidden)
                  : kind.rgcn_relations != 0 ? count_rgcn_params(desc, kind.rgcn_relations)
                  : kind.ggnn_steps != 0 ? count_ggnn_params(desc, kind.ggnn_steps)
                  : gat1_heads != 0 ? count_gatconv_params(desc, gat1_heads, edge_dim)
@@ -388,7 +420,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
 
     const gnnb_model_desc &d = *desc;
     const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated, gat1_heads, kind.ggnn_steps, kind.rgcn_relations,
-                                                  kind.nn_coefs, kind.nn_hidden);
+                                                  kind.nn_coefs, kind.nn_hidden, kind.gen_t != nullptr);
     const std::vector<float> &img = built.img;
     const WeightLayout &lo = built.layout;
 
@@ -405,6 +437,10 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     m->nn_coefs = kind.nn_coefs;
     m->nn_hidden = kind.nn_hidden;
     m->nn_mean = kind.nn_mean;
+    if (kind.gen_t) {
+        m->gen = 1;
+        m->gen_t.assign(kind.gen_t, kind.gen_t + d.num_layers);
+    }
     (void)hipGetDevice(&m->device);
     m->blob_floats = img.size();
     hipError_t e = hipMalloc((void **)&m->blob, std::max<size_t>(img.size(), 4) * sizeof(float));
@@ -658,6 +694,25 @@ int gnnb_nnconv_model_create(const gnnb_model_desc *desc, int edge_dim, int hidd
 }
 
 int gnnb_model_nnconv_hidden(const gnnb_model *model) { return model && model->nn_coefs ? model->nn_hidden : -1; }
+
+int gnnb_gen_model_num_params(const gnnb_model_desc *desc, int edge_dim) { return count_gen_params(desc, edge_dim); }
+
+int gnnb_gen_model_create(const gnnb_model_desc *desc, int edge_dim, const float *t_per_layer, const float *const *host_params, int num_params,
+                          gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (const int rc = count_gen_params(desc, edge_dim); rc < 0)
+        return rc;
+    if (!t_per_layer)
+        return fail(GNNB_ERR_INVALID, "a GENConv model needs t_per_layer, one temperature per conv layer");
+    for (int l = 0; l < desc->num_layers; l++)
+        if (!std::isfinite(t_per_layer[l]))
+            return fail(GNNB_ERR_INVALID, "layer %d's temperature must be finite", l);
+    return model_create(desc, ModelKind::gen(edge_dim, t_per_layer), host_params, num_params, out_model);
+}
+
+int gnnb_model_gen(const gnnb_model *model) { return model ? model->gen : 0; }
 
 void gnnb_model_destroy(gnnb_model *model)
 {

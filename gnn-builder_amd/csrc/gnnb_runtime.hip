@@ -108,6 +108,14 @@ int refuse_rgcn_model(const gnnb_model *model, const gnnb_workspace *ws, const c
     return GNNB_OK;
 }
 
+int refuse_gen_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use)
+{
+    if ((model && model->gen) || (ws && ws->gen))
+        return fail(GNNB_ERR_INVALID, "%s: a GENConv model (gnnb_gen_model_create) runs layer by layer and is not served here: call %s "
+                                      "(gnnb_gen.h)", entry, use);
+    return GNNB_OK;
+}
+
 static thread_local int tl_math = -1; // >= 0: the calling thread is inside an entry point of a model with its own math mode
 static thread_local FlagWord tl_flag = {nullptr, nullptr};
 int launch_math() { return tl_math >= 0 ? tl_math : (int)options().math; }
@@ -210,12 +218,20 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     if (model->nn_coefs) // an NNConv layer's aggregate writes A [N, (K' + 1) in] into tmp0
         for (int l = 0; l < d.num_layers; l++)
             tmpw = std::max(tmpw, model->nn_coefs * layer_dims(d, l).fin);
+    if (model->gen) // a GENConv layer's first GEMM writes [s | r] [N, 2 out] into tmp0, its MLP's hidden is [N, 2 out] there too; the
+                    // aggregate [N, out] goes to agg
+        for (int l = 0; l < d.num_layers; l++) {
+            tmpw = std::max(tmpw, 2 * layer_dims(d, l).fout);
+            aggw = std::max(aggw, layer_dims(d, l).fout);
+        }
     // the widest GEMM K of the conv layers: from 1024 on k_linear_dma may cut its tiles along K (stream-K) and needs a scratch,
     // which belongs to the workspace -- forwards of different workspaces never share one, whatever streams or graphs run them
     int max_k = 0;
     for (int l = 0; l < d.num_layers; l++) {
         const LayerDims ld = layer_dims(d, l);
         max_k = std::max(max_k, d.conv_type == GNNB_CONV_PNA ? 13 * ld.fin : d.conv_type == GNNB_CONV_SAGE ? 2 * ld.fin : std::max(ld.fin, ld.fout));
+        if (model->gen) // (the MLP's second linear: K = 2 out)
+            max_k = std::max(max_k, 2 * ld.fout);
         if (model->nn_coefs) // ([A | x]: K = (K' + 2) in, up to 18 x 256 = 4608; the launch plan sets no bound on K)
             max_k = std::max(max_k, (model->nn_coefs + 1) * ld.fin);
     }
@@ -223,7 +239,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     // (the stage-cut planner's tables: opt-in -- carved only for workspaces created while the option is on; a workspace created
     // without them keeps equal tile counts whatever the option says later: round-5 advisor finding)
     const bool want_plan = options().stage_cut && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 &&
-                           model->gat_heads == 0 && model->gat1_heads == 0 && model->tf_heads == 0 && model->gated == 0 && model->ggnn_steps == 0 && model->rgcn_relations == 0; // (a GATv2 model,
+                           model->gat_heads == 0 && model->gat1_heads == 0 && model->tf_heads == 0 && model->gated == 0 && model->ggnn_steps == 0 && model->rgcn_relations == 0 && model->gen == 0; // (a GATv2 model,
                                             // a GAT v1 model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model, an RGCNConv model take no stack kernel: no stage plan)
     const int pooledw = d.num_pools * gnn_out_width(d);
     const int mlpw = std::max(d.mlp_hidden, d.mlp_out);
@@ -243,6 +259,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     ws->nn_coefs = model->nn_coefs;
     ws->nn_hidden = model->nn_hidden;
     ws->nn_mean = model->nn_mean;
+    ws->gen = model->gen;
     ws->max_graphs = max_graphs;
     ws->max_nodes = max_nodes;
     ws->max_edges = max_edges;
@@ -408,7 +425,7 @@ static bool stack_promised(const gnnb_workspace *ws)
     // (a GINE model's workspace, a GATv2 model's, a GAT v1 model's, a TransformerConv model's, a ResGatedGraphConv model's, a
     // GatedGraphConv model's, an RGCNConv model's: never -- their layers take no stack kernel, whatever the promise)
     return options().fuse_gcn2 && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 && ws->max_graph_nodes > 0 &&
-           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->gat1_heads == 0 && ws->tf_heads == 0 && ws->gated == 0 && ws->ggnn_steps == 0 && ws->rgcn_relations == 0;
+           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->gat1_heads == 0 && ws->tf_heads == 0 && ws->gated == 0 && ws->ggnn_steps == 0 && ws->rgcn_relations == 0 && ws->gen == 0;
 }
 
 // ... and the WHOLE batch is expected there: no large segment, no fixed-point emulation.  Such a batch needs neither the
@@ -943,6 +960,27 @@ int gnnb_aggregate_nnconv(gnnb_workspace *ws, const float *x_dev, int width, con
                                       "ldo >= (K' + 1) width)", NN_MAX_WIDTH, NN_MAX_EDGE_DIM, NN_MAX_HIDDEN);
     GNNB_HIP_TRY(launch_nnconv_aggregate(ws->t, x_dev, width, edge_attr_dev, edge_dim, w1_dev, b1_dev, hidden, aggr == GNNB_NN_AGGR_MEAN, out_dev, ldo,
                                          (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_gen(gnnb_workspace *ws, const float *s_dev, int lds, const float *r_dev, int ldr, int width, const float *edge_attr_dev,
+                       int edge_dim, const float *we_dev, int ldwe, const float *be_dev, float t, float eps_m, float *out_dev, int ldo, void *stream)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gen needs a prepared batch (gnnb_graph_prep)");
+    if (ws->desc.conv_type == GNNB_CONV_GCN)
+        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gen takes a prepared batch whose tables keep explicit self loops: graph prep drops the "
+                                      "(v, v) edges on a workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts "
+                                      "them as ordinary edges");
+    // (a prepared batch without nodes launches nothing and reads no operand; one without edges reads no attribute row)
+    const bool operands = ws->t.num_nodes <= 0 || (s_dev && out_dev && (edge_dim <= 0 || edge_attr_dev || ws->t.num_edges <= 0));
+    if (!operands || width < 1 || width > GEN_MAX_WIDTH || edge_dim < 0 || edge_dim > 16 || (edge_dim > 0 && (!we_dev || !be_dev || ldwe < edge_dim)) ||
+        lds < width || ldo < width || (r_dev && ldr < width))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gen (s and out not NULL unless the batch has no nodes, edge_attr not NULL "
+                                      "unless it has no edges or edge_dim is 0, width 1 .. %d, edge_dim 0 .. 16 with we, be and ldwe >= edge_dim "
+                                      "when it is not 0, lds, ldr and ldo >= width)", GEN_MAX_WIDTH);
+    GNNB_HIP_TRY(launch_gen_aggregate(ws->t, s_dev, lds, r_dev, ldr, width, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, t, eps_m, out_dev, ldo,
+                                      (hipStream_t)stream));
     return GNNB_OK;
 }
 

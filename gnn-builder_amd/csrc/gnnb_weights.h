@@ -157,6 +157,11 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //                                                   sum_j x_j Theta(e_ij) + root x_i
 //              b_nn [out]                           the conv's bias, raw
 //              w_nn1 [K, edge_dim], b_nn1 [K]       the edge network's first linear, raw (the hidden variant only)
+//   GENConv   (gnnb_model::gen, gnnb_gen_model_create: a GIN description, edge_dim 0 .. 16 beside it) GIN's four slots as the layer's MLP
+//              w0 [2 out, out], b0 [2 out]          conv.mlp.0, raw;   w1 [out, 2 out], b1 [out]: conv.mlp.2, raw
+//              w_sr [2 out, in], b_sr [2 out]       derived, layers with in != out only: [lin_src.weight ; lin_dst.weight] and the
+//                                                   stacked bias (stack_rows) -- ONE GEMM gives [s | r] [N, 2 out]
+//              edge_w [out, edge_dim], edge_b [out] conv.lin_edge, raw (edge_dim > 0 only; the OUTPUT width, unlike GINE's)
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
@@ -169,6 +174,7 @@ template <typename T> struct LayerSlots {
     T w_ggc = absent_slot<T>(), w_ggc_next = absent_slot<T>(), b_ggc = absent_slot<T>(), b_ih = absent_slot<T>();
     T w_rgcn = absent_slot<T>(), b_rgcn = absent_slot<T>();
     T w_nn = absent_slot<T>(), b_nn = absent_slot<T>(), w_nn1 = absent_slot<T>(), b_nn1 = absent_slot<T>();
+    T w_sr = absent_slot<T>(), b_sr = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -177,7 +183,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_rgcn), f(b_rgcn), f(w_nn), f(b_nn), f(w_nn1), f(b_nn1), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_rgcn), f(b_rgcn), f(w_nn), f(b_nn), f(w_nn1), f(b_nn1), f(w_sr), f(b_sr), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -578,16 +584,38 @@ constexpr int GGNN_MAX_STEPS = 8;
 constexpr int RGCN_PARAM_SLOTS = 3; // an RGCNConv layer's canonical tensors (gnnb_rgcn.h)
 // an NNConv layer's canonical tensors (gnnb_nnconv.h): 4 with the linear edge network, 6 with the hidden one
 inline int nnconv_param_slots(int hidden) { return hidden > 0 ? 6 : 4; }
+// a GENConv layer's canonical tensors (gnnb_gen.h): the MLP's four, lin_src / lin_dst's four in front where in != out, lin_edge's two
+// between them with edge features
+inline int gen_param_slots(int fin, int fout, int edge_dim) { return (fin != fout ? 4 : 0) + (edge_dim > 0 ? 2 : 0) + 4; }
 constexpr int GAT1_PARAM_SLOTS = 4; // a GAT v1 layer's canonical tensors (gnnb_gatconv.h); two more with edge features (gnnb_gatconv_edge.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
 // their offsets in the image
 inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0,
-                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0, int nn_hidden = 0)
+                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0, int nn_hidden = 0, bool gen = false)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (gen) { // (a GIN description whose layers are GENConv's; canonical order: [lin_src.weight, lin_src.bias, lin_dst.weight,
+               // lin_dst.bias,] [lin_edge.weight, lin_edge.bias,] mlp.0.weight, mlp.0.bias, mlp.2.weight, mlp.2.bias: gen_param_slots)
+        LayerOffsets g;
+        if (fi != fo) {
+            g.w_sr = im.push(stack_rows({p[0], p[2]}, fo, fi));
+            g.b_sr = im.push(stack_rows({p[1], p[3]}, fo, 1));
+            p += 4;
+        }
+        if (edge_dim > 0) {
+            g.edge_w = im.push(p[0], fo * (size_t)edge_dim);
+            g.edge_b = im.push(p[1], fo);
+            p += 2;
+        }
+        g.w0 = im.push(p[0], 2 * fo * fo);
+        g.b0 = im.push(p[1], 2 * fo);
+        g.w1 = im.push(p[2], 2 * fo * fo);
+        g.b1 = im.push(p[3], fo);
+        return g;
+    }
     if (nn_coefs > 0) { // (a GIN description whose layers are NNConv's; canonical order: nn.0.weight, nn.0.bias, [nn.2.weight,
                         // nn.2.bias,] lin.weight, bias -- the bracketed pair with nn_hidden > 0 only; nn_coefs = K' + 1)
         const size_t kq = (size_t)nn_coefs - 1;
@@ -748,9 +776,10 @@ struct BuiltWeights {
 // layer).  ggnn_steps > 0: a GatedGraphConv model (a GIN description, five tensors per layer; no execution-order copy).
 // rgcn_relations > 0: an RGCNConv model (a GIN description, three tensors per layer; no execution-order copy).
 // nn_coefs > 0: an NNConv model (a GIN description with edge_dim; four tensors per layer, six with nn_hidden > 0; no execution-order copy).
+// gen: a GENConv model (a GIN description, edge_dim 0 .. 16; four to ten tensors per layer; no execution-order copy).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
                                        int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0,
-                                       int nn_hidden = 0)
+                                       int nn_hidden = 0, bool gen = false)
 {
     WeightImage im(d);
     WeightLayout lo;
@@ -764,14 +793,15 @@ inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, c
                       : gat_heads > 0 ? GAT_PARAM_SLOTS + (edge_dim ? 1 : 0)
                                       : conv_slots(d.conv_type) + (edge_dim ? 2 : 0);
     int pi = 0;
-    for (int l = 0; l < d.num_layers; l++, pi += slots)
-        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps, rgcn_relations, nn_coefs, nn_hidden);
+    // (a GENConv layer's count depends on its widths: gen_param_slots)
+    for (int l = 0; l < d.num_layers; pi += gen ? gen_param_slots(layer_dims(d, l).fin, layer_dims(d, l).fout, edge_dim) : slots, l++)
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps, rgcn_relations, nn_coefs, nn_hidden, gen);
     const bool have_w1f = gat_heads == 0 && gat1_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));
     // (a GINE model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model, an RGCNConv model take no stack
     // kernel: no execution-order copy)
-    const bool have_gin = edge_dim == 0 && nn_coefs == 0 && tf_heads == 0 && !gated && ggnn_steps == 0 && rgcn_relations == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
+    const bool have_gin = edge_dim == 0 && nn_coefs == 0 && !gen && tf_heads == 0 && !gated && ggnn_steps == 0 && rgcn_relations == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
                           d.out_dim <= d.hidden_dim && d.out_dim % 4 == 0;
     if (have_gin) {
         const WeightBias g = gin_execution_order(d, im.img, lo.conv);

@@ -1071,6 +1071,87 @@ class NNConv_GNNB(nn.Module):
         return self.conv(x, edge_index, edge_attr)
 
 
+# --------------------------------------------------------------------------------------- GENConv
+GEN_EPS = 1e-7  # what a GENConv layer adds to every message (PyG's eps)
+
+
+class _GENConv(nn.Module):
+    """The layer of DeeperGCN (Li et al.), PyG's ``GENConv(in, out, aggr='softmax', t, learn_t=True, num_layers=2, expansion=2,
+    norm=None, edge_dim)``: the aggregate is a per-column softmax-weighted sum of the messages themselves::
+
+        s = lin_src(x) if in != out else x,   r = lin_dst(x) if in != out else x
+        m_ij = relu(s_j + lin_edge(e_ij)) + 1e-7                    (edge_dim = 0: no edge term)
+        a_ij[c] = exp(t m_ij[c]) / sum_{k -> i} exp(t m_ik[c])      (softmax over i's in-edges, per column)
+        out_i = mlp(sum_j a_ij * m_ij + r_i),   mlp = Linear(out, 2 out) -> ReLU -> Linear(2 out, out)
+
+    Duplicate edges count as often as they occur, an explicit ``(v, v)`` edge is an ordinary edge, no self loop is added or removed; a
+    node without in-edges aggregates 0.  ``t`` is one learnable scalar per layer: 0 is the mean of the messages, a large ``t``
+    approaches their max, a negative one their min.  PyG's ``+ 1e-16`` in the softmax denominator is dropped (behind the max shift
+    the denominator is >= 1).  Every linear carries a bias here; PyG's default ``bias=False`` model is this one with zero biases.
+    The parameter names -- ``lin_src``, ``lin_dst``, ``lin_edge``, ``mlp.0``, ``mlp.2``, ``t`` -- follow PyG's as far as they are
+    remembered: the formula above is what is pinned, not the names."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int = 0, t: float = 1.0):
+        super().__init__()
+        self.in_channels, self.out_channels, self.edge_dim = in_channels, out_channels, edge_dim
+        if in_channels != out_channels:
+            self.lin_src = nn.Linear(in_channels, out_channels)
+            self.lin_dst = nn.Linear(in_channels, out_channels)
+        if edge_dim:
+            self.lin_edge = nn.Linear(edge_dim, out_channels)
+        self.mlp = nn.Sequential(nn.Linear(out_channels, 2 * out_channels), nn.ReLU(), nn.Linear(2 * out_channels, out_channels))
+        self.t = nn.Parameter(torch.tensor(float(t)))
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor] = None) -> Tensor:
+        src, dst = edge_index[0].long(), edge_index[1].long()
+        same = self.in_channels == self.out_channels
+        s, r = (x, x) if same else (self.lin_src(x), self.lin_dst(x))
+        m = s[src]
+        if self.edge_dim:
+            m = m + self.lin_edge(edge_attr.to(x.dtype).reshape(src.numel(), self.edge_dim))
+        m = torch.relu(m) + GEN_EPS
+        z = self.t.to(x.dtype) * m
+        idx = dst.unsqueeze(-1).expand_as(z)
+        zmax = torch.full_like(r, float("-inf")).scatter_reduce(0, idx, z, "amax", include_self=True)
+        w = torch.exp(z - zmax[dst])
+        den = torch.zeros_like(r).index_add(0, dst, w)
+        num = torch.zeros_like(r).index_add(0, dst, w * m)
+        agg = torch.where(den > 0, num / den.clamp(min=1), torch.zeros_like(num))
+        return self.mlp(agg + r)
+
+
+class GENConv_GNNB(nn.Module):
+    """GENConv without edge features (no class of the reference): ``_GENConv`` with ``edge_dim = 0``.  ``GNNModel(...,
+    gnn_conv=GENConv_GNNB, gnn_softmax_t=t0)`` stacks it; ``forward(x, edge_index)``.  The accelerated path is
+    ``runtime.CompiledModel.from_model`` with ``forward`` / ``forward_pyg`` (C ABI ``include/gnnb_gen.h``: one launch of
+    csrc/k_gen.hip per layer between the layer's GEMMs).  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, t: float = 1.0, p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        self.in_channels, self.out_channels, self.p_in, self.p_out = in_channels, out_channels, p_in, p_out
+        self.conv = _GENConv(in_channels, out_channels, 0, t)
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        return self.conv(x, edge_index)
+
+
+class GENEConv_GNNB(nn.Module):
+    """GENConv with edge features: ``_GENConv`` with ``edge_dim`` in 1 .. 16.  ``GNNModel(..., gnn_conv=GENEConv_GNNB,
+    graph_input_edge_dim=d, gnn_softmax_t=t0)`` stacks it; ``forward(x, edge_index, edge_attr)`` with the same ``edge_attr`` for
+    every layer.  The accelerated path is ``runtime.CompiledModel.from_model`` with ``forward_edges`` / ``forward_pyg_edges``
+    (``include/gnnb_gen.h``).  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int, t: float = 1.0, p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        if not isinstance(edge_dim, int) or isinstance(edge_dim, bool) or not 1 <= edge_dim <= 16:
+            raise ValueError(f"edge_dim must be an int in 1 .. 16 (got {edge_dim!r})")
+        self.in_channels, self.out_channels, self.edge_dim, self.p_in, self.p_out = in_channels, out_channels, edge_dim, p_in, p_out
+        self.conv = _GENConv(in_channels, out_channels, edge_dim, t)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        return self.conv(x, edge_index, edge_attr)
+
+
 # --------------------------------------------------------------------------------------- pooling / MLP
 SUPPORTED_GLOBAL_POOLING_AGGRS = {"add": "SumAggregation", "max": "MaxAggregation", "mean": "MeanAggregation"}
 SUPPORTED_GLOBAL_POOLING_MODE = ["cat"]
@@ -1183,18 +1264,21 @@ class MLP(nn.Module):
 
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
                        GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB,
-                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB, GatedGraphConv_GNNB, RGCNConv_GNNB, NNConv_GNNB]
+                       ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB, GatedGraphConv_GNNB, RGCNConv_GNNB, NNConv_GNNB,
+                       GENConv_GNNB, GENEConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
               PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
               TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated", ResGatedGraphEConv_GNNB: "resgatede",
-              GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate", GatedGraphConv_GNNB: "ggnn", RGCNConv_GNNB: "rgcn", NNConv_GNNB: "nnconv"}
+              GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate", GatedGraphConv_GNNB: "ggnn", RGCNConv_GNNB: "rgcn", NNConv_GNNB: "nnconv",
+              GENConv_GNNB: "gen", GENEConv_GNNB: "gene"}
 # convs that take edge_attr, and what the messages call them
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE",
-               ResGatedGraphEConv_GNNB: "ResGatedE", GATv1EConv_GNNB: "GATE", NNConv_GNNB: "NNConv"}
+               ResGatedGraphEConv_GNNB: "ResGatedE", GATv1EConv_GNNB: "GATE", NNConv_GNNB: "NNConv", GENEConv_GNNB: "GENE"}
 MAX_EDGE_DIM = 16  # of a GINE, PNAE, GATv2E, TransformerE, ResGatedE or GATE model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h, gnnb_transformer_edge.h, gnnb_resgated_edge.h, gnnb_gatconv_edge.h)
 _GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # the GATv2 convs (heads and negative_slope travel beside a GCN description)
 _TF_CONVS = (TransformerConv_GNNB, TransformerEConv_GNNB)  # the TransformerConv convs (heads travel beside a GIN description)
 _GAT1_CONVS = (GATv1Conv_GNNB, GATv1EConv_GNNB)  # PyG's GATConv (heads and negative_slope travel beside a GCN description: include/gnnb_gatconv.h, gnnb_gatconv_edge.h)
+_GEN_CONVS = (GENConv_GNNB, GENEConv_GNNB)  # GENConv (edge_dim and the per-layer temperatures travel beside a GIN description: include/gnnb_gen.h)
 _HEAD_CONVS = _GAT_CONVS + _TF_CONVS + _GAT1_CONVS  # convs with attention heads: the ones that take gnn_heads
 MAX_RGCN_RELATIONS = 8  # of an RGCNConv model (include/gnnb_rgcn.h): edge types in [0, relations), beside a GIN description
 MAX_NNCONV_HIDDEN = 16  # of an NNConv model (include/gnnb_nnconv.h): the edge network's hidden width, 0 for a single linear
@@ -1211,7 +1295,7 @@ class GNNModel(nn.Module):
                  global_pooling: GlobalPooling, mlp_head: MLP,
                  output_activation: TorchModuleArgOptional, gnn_p_in: int = 1, gnn_p_hidden: int = 1,
                  gnn_p_out: int = 1, gnn_heads: int = 1, gnn_steps: int = 1, gnn_relations: int = 1,
-                 gnn_edge_hidden: int = 0, gnn_aggr: str = "add") -> None:
+                 gnn_edge_hidden: int = 0, gnn_aggr: str = "add", gnn_softmax_t: float = 1.0) -> None:
         super().__init__()
         self.graph_input_feature_dim = graph_input_feature_dim
         self.graph_input_edge_dim = graph_input_edge_dim
@@ -1279,6 +1363,15 @@ class GNNModel(nn.Module):
         elif gnn_edge_hidden != 0 or gnn_aggr != "add":
             raise ValueError(f"gnn_edge_hidden={gnn_edge_hidden!r}, gnn_aggr={gnn_aggr!r}: only an NNConv model (gnn_conv=NNConv_GNNB) has "
                              "an edge network and an aggr")
+
+        self.gnn_softmax_t = gnn_softmax_t  # (the INITIAL temperature of every layer: each layer's conv.t is a parameter of its own)
+        if self.gnn_conv in _GEN_CONVS:
+            if isinstance(gnn_softmax_t, bool) or not isinstance(gnn_softmax_t, (int, float)) or not math.isfinite(gnn_softmax_t):
+                raise ValueError(f"a GENConv model needs gnn_softmax_t, a finite number (got {gnn_softmax_t!r})")
+            conv_kwargs = {**conv_kwargs, "t": float(gnn_softmax_t)}
+        elif gnn_softmax_t != 1.0:
+            raise ValueError(f"gnn_softmax_t={gnn_softmax_t!r}: only a GENConv model (gnn_conv=GENConv_GNNB or GENEConv_GNNB) has a softmax "
+                             "temperature")
 
         self.global_pooling = global_pooling
         self.mlp_head = mlp_head  # registered before gnn_convs: parameter order mlp_head_*, gnn_convs_*
@@ -1413,6 +1506,8 @@ class GNNModel(nn.Module):
             gat = {"relations": int(self.gnn_relations)}
         elif self.gnn_conv is NNConv_GNNB:  # (a GIN description on the C side, edge_dim, hidden and aggr beside it: include/gnnb_nnconv.h)
             gat = {"edge_hidden": int(self.gnn_edge_hidden), "aggr": str(self.gnn_aggr)}
+        elif self.gnn_conv in _GEN_CONVS:  # (a GIN description on the C side, edge_dim and the temperatures beside it: include/gnnb_gen.h)
+            gat = {"softmax_t": [float(c.conv.t.detach()) for c in self.gnn_convs]}  # (read from the parameters: what an upload takes)
         return {
             "conv": _CONV_NAME[self.gnn_conv],
             "num_layers": self.gnn_num_layers,
@@ -1466,8 +1561,16 @@ class GNNModel(nn.Module):
         # (the edge network, then the root weight and the bias: include/gnnb_nnconv.h)
         per_conv["nnconv"] = ["conv_nn_0_weight", "conv_nn_0_bias"] + (["conv_nn_2_weight", "conv_nn_2_bias"] if self.gnn_edge_hidden else []) + [
             "conv_lin_weight", "conv_bias"]
-        per_conv = per_conv[self.spec()["conv"]]
-        names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
+        if self.gnn_conv in _GEN_CONVS:  # (a layer's list depends on its widths: include/gnnb_gen.h; conv.t travels in spec()["softmax_t"])
+            names = []
+            for l, c in enumerate(self.gnn_convs):
+                per = [f"conv_lin_{n}_{t}" for n in ("src", "dst") for t in ("weight", "bias")] if c.in_channels != c.out_channels else []
+                per += ["conv_lin_edge_weight", "conv_lin_edge_bias"] if self.gnn_conv is GENEConv_GNNB else []
+                per += ["conv_mlp_0_weight", "conv_mlp_0_bias", "conv_mlp_2_weight", "conv_mlp_2_bias"]
+                names += [f"gnn_convs_{l}_{p}" for p in per]
+        else:
+            per_conv = per_conv[self.spec()["conv"]]
+            names = [f"gnn_convs_{l}_{p}" for l in range(self.gnn_num_layers) for p in per_conv]
         for i in range(self.mlp_head.num_of_layers):
             names += [f"mlp_head_linear_layers_{i}_weight", f"mlp_head_linear_layers_{i}_bias"]
         return names

@@ -30,10 +30,10 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin", "rgcn": "gin", "nnconv": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin", "rgcn": "gin", "nnconv": "gin", "gen": "gin", "gene": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
 # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h,
 # "resgatede": gnnb_resgated_edge.h, "gate": gnnb_gatconv_edge.h)
-_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede", "gate", "nnconv")
+_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede", "gate", "nnconv", "gene")
 _GAT_CONVS = ("gatv2", "gatv2e")       # ... and of those with heads and negative_slope beside it
 # a GAT v1 model (include/gnnb_gatconv.h, spec["conv"] == "gat"): a GCN description, heads and negative_slope beside it, within GATv2's
 # limits -- a model kind of its own; with edge features ("gate", include/gnnb_gatconv_edge.h) edge_dim too
@@ -53,6 +53,10 @@ MAX_RGCN_RELATIONS, MAX_RGCN_WIDTH = 8, 256
 # hidden width (0: a single linear) and aggr beside it
 MAX_NNCONV_HIDDEN, MAX_NNCONV_WIDTH = 16, 256
 NN_AGGR = {"add": 0, "mean": 1}  # gnnb_nn_aggr
+# a GENConv model (include/gnnb_gen.h, spec["conv"] == "gen" without and "gene" with edge features): its description is GIN's too;
+# edge_dim (0 for "gen") and the per-layer softmax temperatures spec["softmax_t"] beside it
+_GEN_CONVS = ("gen", "gene")
+MAX_GEN_WIDTH = 256
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -294,6 +298,15 @@ ABI_NNCONV = {
 }
 
 
+# ... and of include/gnnb_gen.h (GENConv models, the per-column softmax aggregate), in its order
+ABI_GEN = {
+    "gnnb_gen_model_num_params": (_I, [_DESC, _I]),
+    "gnnb_gen_model_create": (_I, [_DESC, _I, _P, _PP, _I, _PP]),
+    "gnnb_model_gen": (_I, [_P]),
+    "gnnb_aggregate_gen": (_I, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, C.c_float, C.c_float, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -345,7 +358,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
         for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER,
                                            **ABI_TRANSFORMER_EDGE, **ABI_RESGATED, **ABI_RESGATED_EDGE, **ABI_GATCONV,
-                                           **ABI_GATCONV_EDGE, **ABI_GGNN, **ABI_RGCN, **ABI_NNCONV}.items():
+                                           **ABI_GATCONV_EDGE, **ABI_GGNN, **ABI_RGCN, **ABI_NNCONV, **ABI_GEN}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -510,7 +523,15 @@ class CompiledModel:
                               (self.lib.gnnb_edge_model_num_params, self.lib.gnnb_edge_model_create))
         if spec.get("conv") == "nnconv" and spec.get("aggr", "add") not in NN_AGGR:
             raise GnnbError(f"an NNConv model needs spec['aggr'] in {sorted(NN_AGGR)}, got {spec.get('aggr')!r}")
-        n_expect = (self.lib.gnnb_nnconv_model_num_params(C.byref(self.desc), self.edge_dim, self.nnconv_hidden) if spec.get("conv") == "nnconv" else
+        gen_t = None
+        if spec.get("conv") in _GEN_CONVS:  # (gnnb_gen.h: one finite temperature per conv layer)
+            ts = spec.get("softmax_t", 1.0)
+            ts = [float(ts)] * int(spec["num_layers"]) if isinstance(ts, (int, float)) else [float(t) for t in ts]
+            if len(ts) != int(spec["num_layers"]) or not all(np.isfinite(ts)):
+                raise GnnbError(f"a GENConv model needs spec['softmax_t']: {spec['num_layers']} finite temperatures (or one number), got {ts!r}")
+            gen_t = (C.c_float * max(len(ts), 1))(*ts)
+        n_expect = (self.lib.gnnb_gen_model_num_params(C.byref(self.desc), self.edge_dim) if gen_t is not None else
+                    self.lib.gnnb_nnconv_model_num_params(C.byref(self.desc), self.edge_dim, self.nnconv_hidden) if spec.get("conv") == "nnconv" else
                     self.lib.gnnb_gat_edge_model_num_params(C.byref(self.desc), self.gat_heads, self.edge_dim) if spec.get("conv") == "gatv2e" else
                     self.lib.gnnb_transformer_edge_model_num_params(C.byref(self.desc), self.transformer_heads, self.edge_dim)
                     if spec.get("conv") == "transformere" else
@@ -530,7 +551,9 @@ class CompiledModel:
         if len(host) != n_expect:
             raise GnnbError(f"model needs {n_expect} parameter tensors, got {len(host)}")
         arr = (C.c_void_p * len(host))(*[h.ctypes.data for h in host])
-        if spec.get("conv") == "nnconv":  # (gnnb_nnconv.h: a GIN description, edge_dim, the hidden width and aggr beside it)
+        if gen_t is not None:  # (gnnb_gen.h: a GIN description, edge_dim -- 0 without edge features -- and the temperatures beside it)
+            _check(self.lib.gnnb_gen_model_create(C.byref(self.desc), self.edge_dim, gen_t, arr, len(host), C.byref(self._model)))
+        elif spec.get("conv") == "nnconv":  # (gnnb_nnconv.h: a GIN description, edge_dim, the hidden width and aggr beside it)
             _check(self.lib.gnnb_nnconv_model_create(C.byref(self.desc), self.edge_dim, self.nnconv_hidden, NN_AGGR[spec.get("aggr", "add")], arr,
                                                      len(host), C.byref(self._model)))
         elif spec.get("conv") == "gatv2e":  # (gnnb_gat_edge.h: a GCN description, heads, negative_slope and edge_dim beside it)
@@ -883,6 +906,9 @@ class CompiledModel:
         return _dptr(edge_attr) if E else None
 
     def _require_edge_model(self, what: str) -> None:
+        if self.spec.get("conv") == "gen":  # (gnnb_gen.h: the C entries refuse it the same way)
+            raise GnnbError(f"{what}: a GENConv model without edge features (GENConv_GNNB) takes no edge attributes: call "
+                            f"{what.replace('_edges', '')}")
         if not self.edge_dim:
             raise GnnbError(f"{what} takes a GINE or PNAE model, or GATv2 with edge features (a GNNModel of GINEConv_GNNB, PNAEConv_GNNB or "
                             "GATv2EConv_GNNB layers: edge weights); this model has none")
@@ -1315,6 +1341,45 @@ class CompiledModel:
         ldo = int(out.stride(0)) if self._N > 1 else cols
         _check(self.lib.gnnb_aggregate_nnconv(self._ws, _dptr(x), w, _dptr(edge_attr) if self._E else None, ed, _optr(w1), _optr(b1), hidden,
                                               NN_AGGR[aggr], _dptr(out), ldo, _stream_ptr(stream)))
+        return out
+
+    def aggregate_gen(self, s, r=None, edge_attr=None, we=None, be=None, t: float = 1.0, eps: float = 1e-7, out=None, stream=None):
+        """A GENConv layer's aggregate (``gnnb_aggregate_gen``, csrc/k_gen.hip) on the prepared batch of a workspace whose tables keep
+        explicit self loops: ``out[i, c] = sum_j a_ij[c] m_ij[c] + r[i, c]`` with ``m_ij = relu(s[j] + we e_ij + be) + eps`` and
+        ``a_ij`` the per-column softmax of ``t * m`` over row ``i``'s in-edges; a row without in-edges is ``r[i]``.  ``s`` and ``r``
+        [N, width <= 256] may be column blocks of a wider matrix (the two halves of one GEMM result: their row strides are passed
+        on), and so may ``out``; ``r=None``: the bare aggregate.  ``edge_attr`` [E, d <= 16] in COO order with ``we`` [width, d] and
+        ``be`` [width], or all three None: no edge term."""
+        import torch
+        _require_strided(s, "s", self._N)
+        w = int(s.shape[1])
+        if not 1 <= w <= MAX_GEN_WIDTH:
+            raise GnnbError(f"s must be [{self._N}, 1 .. {MAX_GEN_WIDTH}], got {tuple(s.shape)}")
+        if r is not None:
+            _require_strided(r, "r", self._N)
+            if int(r.shape[1]) != w or r.device != s.device:
+                raise GnnbError(f"r must be [{self._N}, {w}] on {s.device}, got {tuple(r.shape)} on {r.device}")
+        if (edge_attr is None) != (we is None) or (we is None) != (be is None):
+            raise GnnbError("edge_attr, we and be come together (all None: no edge term)")
+        ed = 0
+        if edge_attr is not None:
+            if edge_attr.dim() != 2 or not 1 <= int(edge_attr.shape[1]) <= MAX_EDGE_DIM:
+                raise GnnbError(f"edge_attr must be [{self._E}, 1 .. {MAX_EDGE_DIM}]")
+            ed = int(edge_attr.shape[1])
+            _require_rows(edge_attr, "edge_attr", self._E, ed, s)
+            _require_rows(we, "we", w, ed, s)
+            _require(be, "be", torch.float32, 1, w)
+            if be.device != s.device:
+                raise GnnbError(f"be must be on {s.device}")
+        if out is None:
+            out = torch.empty((self._N, w), dtype=torch.float32, device=s.device)
+        _require_strided(out, "out", self._N)
+        if int(out.shape[1]) != w or out.device != s.device:
+            raise GnnbError(f"out must be [{self._N}, {w}] on {s.device}, got {tuple(out.shape)} on {out.device}")
+        ld = lambda a: int(a.stride(0)) if self._N > 1 else w  # noqa: E731
+        _check(self.lib.gnnb_aggregate_gen(self._ws, _dptr(s), ld(s), _optr(r), ld(r) if r is not None else w, w,
+                                           _dptr(edge_attr) if ed and self._E else None, ed, _optr(we), ed, _optr(be), float(t), float(eps),
+                                           _dptr(out), ld(out), _stream_ptr(stream)))
         return out
 
     def rgcn_slots(self, edge_type, relations: int, stream=None):
