@@ -768,11 +768,53 @@ int gnnb_edge_index_table_to_host(gnnb_workspace *ws, int32_t *edge_index_table,
     return mark_unused_slots(ws, edge_index_table, (hipStream_t)stream);
 }
 
+// ---- stage entries: one family kernel on the prepared batch.  Each is the prologue, its own argument check (shared with its
+// _edges sibling, which adds the edge operands) and its launch
+// (loop-free: the kernel adds the one self term itself; keep-loops: the layer counts (v, v) edges as ordinary edges)
+enum StageTables { TABLES_ANY, TABLES_LOOP_FREE, TABLES_KEEP_LOOPS };
+
+// a refusal of a callee (which has called fail) is the caller's: GNNB_HIP_TRY's counterpart for a gnnb_status
+#define GNNB_TRY(expr)                                                                            \
+    do {                                                                                          \
+        if (const int rc_ = (expr))                                                               \
+            return rc_;                                                                           \
+    } while (0)
+
+// the refusals every entry opens with; graph prep drops explicit self loops on a workspace of a GCN description and nowhere else.
+// `model`: whose workspaces, besides a GCN model's, a loop-free entry names
+static int stage_entry(const gnnb_workspace *ws, const char *entry, StageTables tables, const char *model = nullptr)
+{
+    if (!ws || !ws->prepared)
+        return fail(GNNB_ERR_INVALID, "%s needs a prepared batch (gnnb_graph_prep)", entry);
+    const bool loop_free = ws->desc.conv_type == GNNB_CONV_GCN;
+    if (tables == TABLES_LOOP_FREE && !loop_free)
+        return fail(GNNB_ERR_INVALID, "%s takes the prepared batch of a GCN workspace (or a %s model's): graph prep drops explicit self loops "
+                                      "there, the kernel adds the one self term", entry, model);
+    if (tables == TABLES_KEEP_LOOPS && loop_free)
+        return fail(GNNB_ERR_INVALID, "%s takes a prepared batch whose tables keep explicit self loops: graph prep drops the (v, v) edges on a "
+                                      "workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts them as ordinary "
+                                      "edges", entry);
+    return GNNB_OK;
+}
+
+static bool bad_act(int act) { return act < GNNB_ACT_RELU || act > GNNB_ACT_NONE; }
+static bool bad_heads(int heads, int width, int max_heads, int max_width) { return heads < 1 || heads > max_heads || width < 1 || width > max_width || width % heads != 0; }
+
+// the bound of the families whose kernels name theirs in their own file (GINE, PNA, GATv2 and GAT with edge features, GENConv)
+constexpr int EDGE_MAX_DIM = 16;
+static_assert(TFE_MAX_EDGE_DIM == EDGE_MAX_DIM && RGE_MAX_EDGE_DIM == EDGE_MAX_DIM && NN_MAX_EDGE_DIM == EDGE_MAX_DIM, "one bound, whatever its name");
+
+// the edge operands of an entry with edge features: the attribute rows, which only a batch without edges may lack, and the matrix
+// [., edge_dim] at row stride ldw applied to them
+static bool bad_edge_operands(const gnnb_workspace *ws, const float *edge_attr, int edge_dim, int max_edge_dim, const float *w, int ldw)
+{
+    return !w || edge_dim < 1 || edge_dim > max_edge_dim || ldw < edge_dim || (ws->t.num_edges > 0 && !edge_attr);
+}
+
 int gnnb_aggregate_edges(gnnb_workspace *ws, const float *x_dev, const float *edge_term_dev, float *out_dev,
                          int width, float eps, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_edges needs a prepared batch (gnnb_graph_prep)");
+    GNNB_TRY(stage_entry(ws, "gnnb_aggregate_edges", TABLES_ANY));
     if (!x_dev || !out_dev || width < 1 || (ws->t.num_edges > 0 && !edge_term_dev))
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_edges");
     GNNB_HIP_TRY(launch_aggregate_edges(ws->t, x_dev, edge_term_dev, out_dev, width, eps, (hipStream_t)stream));
@@ -782,11 +824,9 @@ int gnnb_aggregate_edges(gnnb_workspace *ws, const float *x_dev, const float *ed
 int gnnb_aggregate_edges_fused(gnnb_workspace *ws, const float *x_dev, const float *edge_attr_dev, int edge_dim, const float *we_dev, int ldwe,
                                const float *be_dev, float *out_dev, int width, float eps, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_edges_fused needs a prepared batch (gnnb_graph_prep)");
-    if (!x_dev || !out_dev || !we_dev || !be_dev || width < 1 || edge_dim < 1 || edge_dim > 16 || ldwe < edge_dim ||
-        (ws->t.num_edges > 0 && !edge_attr_dev))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_edges_fused (edge_dim 1 .. 16, ldwe >= edge_dim)");
+    GNNB_TRY(stage_entry(ws, "gnnb_aggregate_edges_fused", TABLES_ANY));
+    if (!x_dev || !out_dev || !be_dev || width < 1 || bad_edge_operands(ws, edge_attr_dev, edge_dim, EDGE_MAX_DIM, we_dev, ldwe))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_edges_fused (edge_dim 1 .. %d, ldwe >= edge_dim)", EDGE_MAX_DIM);
     GNNB_HIP_TRY(launch_gine_aggregate(ws->t, x_dev, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, out_dev, width, eps, (hipStream_t)stream));
     return GNNB_OK;
 }
@@ -794,12 +834,22 @@ int gnnb_aggregate_edges_fused(gnnb_workspace *ws, const float *x_dev, const flo
 int gnnb_aggregate_pna_edges(gnnb_workspace *ws, const float *p_dev, const float *q_dev, const float *edge_attr_dev, int edge_dim,
                              const float *we_dev, int ldwe, const float *be_dev, float *out_dev, int width, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_pna_edges needs a prepared batch (gnnb_graph_prep)");
-    if (!p_dev || !out_dev || !we_dev || !be_dev || width < 1 || edge_dim < 1 || edge_dim > 16 || ldwe < edge_dim ||
-        (ws->t.num_edges > 0 && !edge_attr_dev))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_pna_edges (edge_dim 1 .. 16, ldwe >= edge_dim)");
+    GNNB_TRY(stage_entry(ws, "gnnb_aggregate_pna_edges", TABLES_ANY));
+    if (!p_dev || !out_dev || !be_dev || width < 1 || bad_edge_operands(ws, edge_attr_dev, edge_dim, EDGE_MAX_DIM, we_dev, ldwe))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_pna_edges (edge_dim 1 .. %d, ldwe >= edge_dim)", EDGE_MAX_DIM);
     GNNB_HIP_TRY(launch_pna_edge_aggregate(ws->t, p_dev, q_dev, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, out_dev, width, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+// gnnb_aggregate_gatv2 and gnnb_aggregate_gatv2_edges: the prologue and what both take
+static int gatv2_entry(const gnnb_workspace *ws, const char *entry, const float *xl, int ldl, const float *xr, int ldr, const float *att, int act,
+                       int heads, float slope, const float *out, int width)
+{
+    GNNB_TRY(stage_entry(ws, entry, TABLES_LOOP_FREE, "GATv2"));
+    if (!xl || !xr || !att || !out || bad_heads(heads, width, GAT_MAX_HEADS, GAT_MAX_WIDTH) || ldl < width || ldr < width || bad_act(act) ||
+        !std::isfinite(slope))
+        return fail(GNNB_ERR_INVALID, "bad argument to %s (heads 1 .. %d dividing width 1 .. %d, ldl and ldr >= width, a gnnb_act, a finite "
+                                      "negative_slope)", entry, GAT_MAX_HEADS, GAT_MAX_WIDTH);
     return GNNB_OK;
 }
 
@@ -807,17 +857,21 @@ int gnnb_aggregate_gatv2(gnnb_workspace *ws, const float *xl_dev, int ldl, const
                          const float *bias_dev, const float *skip_dev, int act, int heads, float negative_slope, float *out_dev, int width,
                          void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gatv2 needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type != GNNB_CONV_GCN) // (only there are the tables free of (v, v) edges: the kernel adds the self term)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gatv2 takes the prepared batch of a GCN workspace (or a GATv2 model's): graph prep drops "
-                                      "explicit self loops there, the kernel adds the one self term");
-    if (!xl_dev || !xr_dev || !att_dev || !out_dev || heads < 1 || heads > GAT_MAX_HEADS || width < 1 || width > GAT_MAX_WIDTH ||
-        width % heads != 0 || ldl < width || ldr < width || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE || !std::isfinite(negative_slope))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gatv2 (heads 1 .. %d dividing width 1 .. %d, ldl and ldr >= width, a "
-                                      "gnnb_act, a finite negative_slope)", GAT_MAX_HEADS, GAT_MAX_WIDTH);
+    GNNB_TRY(gatv2_entry(ws, "gnnb_aggregate_gatv2", xl_dev, ldl, xr_dev, ldr, att_dev, act, heads, negative_slope, out_dev, width));
     GNNB_HIP_TRY(launch_gatv2_aggregate(ws->t, xl_dev, ldl, xr_dev, ldr, att_dev, bias_dev, skip_dev, act, heads, negative_slope, out_dev, width,
                                         (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+// gnnb_aggregate_gat and gnnb_aggregate_gat_edges: the prologue and what both take
+static int gat_entry(const gnnb_workspace *ws, const char *entry, const float *xl, int ldl, const float *ssrc, int lds, const float *sdst, int ldd,
+                     int act, int heads, float slope, const float *out, int width)
+{
+    GNNB_TRY(stage_entry(ws, entry, TABLES_LOOP_FREE, "GAT"));
+    if (!xl || !ssrc || !sdst || !out || bad_heads(heads, width, GAT_MAX_HEADS, GAT_MAX_WIDTH) || ldl < width || lds < heads || ldd < heads ||
+        bad_act(act) || !std::isfinite(slope))
+        return fail(GNNB_ERR_INVALID, "bad argument to %s (heads 1 .. %d dividing width 1 .. %d, ldl >= width, lds and ldd >= heads, a gnnb_act, "
+                                      "a finite negative_slope)", entry, GAT_MAX_HEADS, GAT_MAX_WIDTH);
     return GNNB_OK;
 }
 
@@ -825,16 +879,7 @@ int gnnb_aggregate_gat(gnnb_workspace *ws, const float *xl_dev, int ldl, const f
                        const float *bias_dev, const float *skip_dev, int act, int heads, float negative_slope, float *out_dev, int width,
                        void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gat needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type != GNNB_CONV_GCN) // (only there are the tables free of (v, v) edges: the kernel adds the self term)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gat takes the prepared batch of a GCN workspace (or a GAT model's): graph prep drops "
-                                      "explicit self loops there, the kernel adds the one self term");
-    if (!xl_dev || !ssrc_dev || !sdst_dev || !out_dev || heads < 1 || heads > GAT_MAX_HEADS || width < 1 || width > GAT_MAX_WIDTH ||
-        width % heads != 0 || ldl < width || lds < heads || ldd < heads || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE ||
-        !std::isfinite(negative_slope))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gat (heads 1 .. %d dividing width 1 .. %d, ldl >= width, lds and ldd >= "
-                                      "heads, a gnnb_act, a finite negative_slope)", GAT_MAX_HEADS, GAT_MAX_WIDTH);
+    GNNB_TRY(gat_entry(ws, "gnnb_aggregate_gat", xl_dev, ldl, ssrc_dev, lds, sdst_dev, ldd, act, heads, negative_slope, out_dev, width));
     GNNB_HIP_TRY(launch_gat_aggregate(ws->t, xl_dev, ldl, ssrc_dev, lds, sdst_dev, ldd, bias_dev, skip_dev, act, heads, negative_slope, out_dev,
                                       width, (hipStream_t)stream));
     return GNNB_OK;
@@ -844,19 +889,10 @@ int gnnb_aggregate_gat_edges(gnnb_workspace *ws, const float *xl_dev, int ldl, c
                              const float *bias_dev, const float *skip_dev, int act, int heads, float negative_slope, const float *edge_attr_dev,
                              int edge_dim, const float *ae_dev, int ldae, float *out_dev, int width, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gat_edges needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type != GNNB_CONV_GCN) // (only there are the tables free of (v, v) edges: the kernel adds the self term)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gat_edges takes the prepared batch of a GCN workspace (or a GAT model's): graph prep drops "
-                                      "explicit self loops there, the kernel adds the one self term");
-    if (!xl_dev || !ssrc_dev || !sdst_dev || !out_dev || heads < 1 || heads > GAT_MAX_HEADS || width < 1 || width > GAT_MAX_WIDTH ||
-        width % heads != 0 || ldl < width || lds < heads || ldd < heads || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE ||
-        !std::isfinite(negative_slope))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gat_edges (heads 1 .. %d dividing width 1 .. %d, ldl >= width, lds and "
-                                      "ldd >= heads, a gnnb_act, a finite negative_slope)", GAT_MAX_HEADS, GAT_MAX_WIDTH);
-    if (!ae_dev || edge_dim < 1 || edge_dim > 16 || ldae < edge_dim || (ws->t.num_edges > 0 && !edge_attr_dev))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gat_edges (ae, edge_dim 1 .. 16, ldae >= edge_dim, edge_attr for a batch "
-                                      "with edges)");
+    GNNB_TRY(gat_entry(ws, "gnnb_aggregate_gat_edges", xl_dev, ldl, ssrc_dev, lds, sdst_dev, ldd, act, heads, negative_slope, out_dev, width));
+    if (bad_edge_operands(ws, edge_attr_dev, edge_dim, EDGE_MAX_DIM, ae_dev, ldae))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gat_edges (ae, edge_dim 1 .. %d, ldae >= edge_dim, edge_attr for a batch "
+                                      "with edges)", EDGE_MAX_DIM);
     GNNB_HIP_TRY(launch_gat_edge_aggregate(ws->t, xl_dev, ldl, ssrc_dev, lds, sdst_dev, ldd, bias_dev, skip_dev, act, heads, negative_slope,
                                            edge_attr_dev, edge_dim, ae_dev, ldae, out_dev, width, (hipStream_t)stream));
     return GNNB_OK;
@@ -866,20 +902,24 @@ int gnnb_aggregate_gatv2_edges(gnnb_workspace *ws, const float *xl_dev, int ldl,
                                const float *bias_dev, const float *skip_dev, int act, int heads, float negative_slope, const float *edge_attr_dev,
                                int edge_dim, const float *we_dev, int ldwe, float *out_dev, int width, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gatv2_edges needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type != GNNB_CONV_GCN) // (only there are the tables free of (v, v) edges: the kernel adds the self term)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gatv2_edges takes the prepared batch of a GCN workspace (or a GATv2 model's): graph prep "
-                                      "drops explicit self loops there, the kernel adds the one self term");
-    if (!xl_dev || !xr_dev || !att_dev || !out_dev || heads < 1 || heads > GAT_MAX_HEADS || width < 1 || width > GAT_MAX_WIDTH ||
-        width % heads != 0 || ldl < width || ldr < width || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE || !std::isfinite(negative_slope))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gatv2_edges (heads 1 .. %d dividing width 1 .. %d, ldl and ldr >= width, a "
-                                      "gnnb_act, a finite negative_slope)", GAT_MAX_HEADS, GAT_MAX_WIDTH);
-    if (!we_dev || edge_dim < 1 || edge_dim > 16 || ldwe < edge_dim || (ws->t.num_edges > 0 && !edge_attr_dev))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gatv2_edges (edge_dim 1 .. 16, ldwe >= edge_dim, edge_attr for a batch "
-                                      "with edges)");
+    GNNB_TRY(gatv2_entry(ws, "gnnb_aggregate_gatv2_edges", xl_dev, ldl, xr_dev, ldr, att_dev, act, heads, negative_slope, out_dev, width));
+    if (bad_edge_operands(ws, edge_attr_dev, edge_dim, EDGE_MAX_DIM, we_dev, ldwe))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gatv2_edges (edge_dim 1 .. %d, ldwe >= edge_dim, edge_attr for a batch "
+                                      "with edges)", EDGE_MAX_DIM);
     GNNB_HIP_TRY(launch_gatv2_edge_aggregate(ws->t, xl_dev, ldl, xr_dev, ldr, att_dev, bias_dev, skip_dev, act, heads, negative_slope, edge_attr_dev,
                                              edge_dim, we_dev, ldwe, out_dev, width, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+// gnnb_aggregate_transformer and gnnb_aggregate_transformer_edges: the prologue and what both take
+static int transformer_entry(const gnnb_workspace *ws, const char *entry, const float *q, int ldq, const float *k, int ldk, const float *v, int ldv,
+                             const float *root, int ldr, int act, int heads, float scale, const float *out, int width)
+{
+    GNNB_TRY(stage_entry(ws, entry, TABLES_KEEP_LOOPS));
+    if (!q || !k || !v || !out || bad_heads(heads, width, TF_MAX_HEADS, TF_MAX_WIDTH) || ldq < width || ldk < width || ldv < width ||
+        (root && ldr < width) || bad_act(act) || !std::isfinite(scale))
+        return fail(GNNB_ERR_INVALID, "bad argument to %s (heads 1 .. %d dividing width 1 .. %d, ldq, ldk, ldv and root's ldr >= width, a "
+                                      "gnnb_act, a finite scale)", entry, TF_MAX_HEADS, TF_MAX_WIDTH);
     return GNNB_OK;
 }
 
@@ -887,35 +927,29 @@ int gnnb_aggregate_transformer(gnnb_workspace *ws, const float *q_dev, int ldq, 
                                const float *root_dev, int ldr, const float *skip_dev, int act, int heads, float scale, float *out_dev, int width,
                                void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_transformer needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's with or without edge features)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_transformer takes a prepared batch whose tables keep explicit self loops: graph prep "
-                                      "drops the (v, v) edges on a workspace of a GCN description (a GCN or GATv2 model's), and this layer "
-                                      "counts them as ordinary edges");
-    if (!q_dev || !k_dev || !v_dev || !out_dev || heads < 1 || heads > TF_MAX_HEADS || width < 1 || width > TF_MAX_WIDTH || width % heads != 0 ||
-        ldq < width || ldk < width || ldv < width || (root_dev && ldr < width) || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE ||
-        !std::isfinite(scale))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_transformer (heads 1 .. %d dividing width 1 .. %d, ldq, ldk, ldv and "
-                                      "root's ldr >= width, a gnnb_act, a finite scale)", TF_MAX_HEADS, TF_MAX_WIDTH);
+    GNNB_TRY(transformer_entry(ws, "gnnb_aggregate_transformer", q_dev, ldq, k_dev, ldk, v_dev, ldv, root_dev, ldr, act, heads, scale, out_dev,
+                                   width));
     GNNB_HIP_TRY(launch_transformer_aggregate(ws->t, q_dev, ldq, k_dev, ldk, v_dev, ldv, root_dev, ldr, skip_dev, act, heads, scale, out_dev,
                                               width, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+// gnnb_aggregate_resgated and gnnb_aggregate_resgated_edges: the prologue and what both take
+static int resgated_entry(const gnnb_workspace *ws, const char *entry, const float *k, int ldk, const float *q, int ldq, const float *v, int ldv,
+                          const float *root, int ldr, int act, const float *out, int width)
+{
+    GNNB_TRY(stage_entry(ws, entry, TABLES_KEEP_LOOPS));
+    if (!k || !q || !v || !out || width < 1 || width > RG_MAX_WIDTH || ldk < width || ldq < width || ldv < width || (root && ldr < width) ||
+        bad_act(act))
+        return fail(GNNB_ERR_INVALID, "bad argument to %s (k, q, v and out not NULL, width 1 .. %d, ldk, ldq, ldv and root's ldr >= width, a "
+                                      "gnnb_act)", entry, RG_MAX_WIDTH);
     return GNNB_OK;
 }
 
 int gnnb_aggregate_resgated(gnnb_workspace *ws, const float *k_dev, int ldk, const float *q_dev, int ldq, const float *v_dev, int ldv,
                             const float *root_dev, int ldr, const float *skip_dev, int act, float *out_dev, int width, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_resgated needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's with or without edge features)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_resgated takes a prepared batch whose tables keep explicit self loops: graph prep "
-                                      "drops the (v, v) edges on a workspace of a GCN description (a GCN or GATv2 model's), and this layer "
-                                      "counts them as ordinary edges");
-    if (!k_dev || !q_dev || !v_dev || !out_dev || width < 1 || width > RG_MAX_WIDTH || ldk < width || ldq < width || ldv < width ||
-        (root_dev && ldr < width) || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE)
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_resgated (k, q, v and out not NULL, width 1 .. %d, ldk, ldq, ldv and "
-                                      "root's ldr >= width, a gnnb_act)", RG_MAX_WIDTH);
+    GNNB_TRY(resgated_entry(ws, "gnnb_aggregate_resgated", k_dev, ldk, q_dev, ldq, v_dev, ldv, root_dev, ldr, act, out_dev, width));
     GNNB_HIP_TRY(launch_resgated_aggregate(ws->t, k_dev, ldk, q_dev, ldq, v_dev, ldv, root_dev, ldr, skip_dev, act, out_dev, width,
                                            (hipStream_t)stream));
     return GNNB_OK;
@@ -924,16 +958,11 @@ int gnnb_aggregate_resgated(gnnb_workspace *ws, const float *k_dev, int ldk, con
 int gnnb_aggregate_ggnn(gnnb_workspace *ws, const float *p_dev, int ldp, const float *gh_dev, int ldgh, const float *h_dev, int ldh, int h_width,
                         const float *b_ih_dev, const float *skip_dev, int act, float *out_dev, int width, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_ggnn needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's, a GAT v1 model's, with or without edge features)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_ggnn takes a prepared batch whose tables keep explicit self loops: graph prep drops the "
-                                      "(v, v) edges on a workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts "
-                                      "them as ordinary edges");
+    GNNB_TRY(stage_entry(ws, "gnnb_aggregate_ggnn", TABLES_KEEP_LOOPS));
     // (a prepared batch without nodes launches nothing and reads no operand: an empty tensor's NULL pointer is no error there)
     const bool operands = ws->t.num_nodes <= 0 || (p_dev && gh_dev && h_dev && out_dev);
     if (!operands || width < 1 || width > GG_MAX_WIDTH || h_width < 1 || h_width > width || ldp < 3 * width ||
-        ldgh < 3 * width || ldh < h_width || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE)
+        ldgh < 3 * width || ldh < h_width || bad_act(act))
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_ggnn (p, gh, h and out not NULL unless the batch has no nodes, width 1 .. %d, h_width 1 .. width, ldp "
                                       "and ldgh >= 3 width, ldh >= h_width, a gnnb_act)", GG_MAX_WIDTH);
     GNNB_HIP_TRY(launch_ggnn_aggregate(ws->t, p_dev, ldp, gh_dev, ldgh, h_dev, ldh, h_width, b_ih_dev, skip_dev, act, out_dev, width,
@@ -944,12 +973,7 @@ int gnnb_aggregate_ggnn(gnnb_workspace *ws, const float *p_dev, int ldp, const f
 int gnnb_aggregate_nnconv(gnnb_workspace *ws, const float *x_dev, int width, const float *edge_attr_dev, int edge_dim, const float *w1_dev,
                           const float *b1_dev, int hidden, int aggr, float *out_dev, int ldo, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_nnconv needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type == GNNB_CONV_GCN)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_nnconv takes a prepared batch whose tables keep explicit self loops: graph prep drops the "
-                                      "(v, v) edges on a workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts "
-                                      "them as ordinary edges");
+    GNNB_TRY(stage_entry(ws, "gnnb_aggregate_nnconv", TABLES_KEEP_LOOPS));
     // (a prepared batch without nodes launches nothing and reads no operand; one without edges reads no attribute row)
     const bool operands = ws->t.num_nodes <= 0 || (x_dev && out_dev && (edge_attr_dev || ws->t.num_edges <= 0));
     const int kq = hidden > 0 ? hidden : edge_dim;
@@ -966,19 +990,14 @@ int gnnb_aggregate_nnconv(gnnb_workspace *ws, const float *x_dev, int width, con
 int gnnb_aggregate_gen(gnnb_workspace *ws, const float *s_dev, int lds, const float *r_dev, int ldr, int width, const float *edge_attr_dev,
                        int edge_dim, const float *we_dev, int ldwe, const float *be_dev, float t, float eps_m, float *out_dev, int ldo, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gen needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type == GNNB_CONV_GCN)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_gen takes a prepared batch whose tables keep explicit self loops: graph prep drops the "
-                                      "(v, v) edges on a workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts "
-                                      "them as ordinary edges");
+    GNNB_TRY(stage_entry(ws, "gnnb_aggregate_gen", TABLES_KEEP_LOOPS));
     // (a prepared batch without nodes launches nothing and reads no operand; one without edges reads no attribute row)
     const bool operands = ws->t.num_nodes <= 0 || (s_dev && out_dev && (edge_dim <= 0 || edge_attr_dev || ws->t.num_edges <= 0));
-    if (!operands || width < 1 || width > GEN_MAX_WIDTH || edge_dim < 0 || edge_dim > 16 || (edge_dim > 0 && (!we_dev || !be_dev || ldwe < edge_dim)) ||
-        lds < width || ldo < width || (r_dev && ldr < width))
+    if (!operands || width < 1 || width > GEN_MAX_WIDTH || edge_dim < 0 || edge_dim > EDGE_MAX_DIM ||
+        (edge_dim > 0 && (!we_dev || !be_dev || ldwe < edge_dim)) || lds < width || ldo < width || (r_dev && ldr < width))
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_gen (s and out not NULL unless the batch has no nodes, edge_attr not NULL "
-                                      "unless it has no edges or edge_dim is 0, width 1 .. %d, edge_dim 0 .. 16 with we, be and ldwe >= edge_dim "
-                                      "when it is not 0, lds, ldr and ldo >= width)", GEN_MAX_WIDTH);
+                                      "unless it has no edges or edge_dim is 0, width 1 .. %d, edge_dim 0 .. %d with we, be and ldwe >= edge_dim "
+                                      "when it is not 0, lds, ldr and ldo >= width)", GEN_MAX_WIDTH, EDGE_MAX_DIM);
     GNNB_HIP_TRY(launch_gen_aggregate(ws->t, s_dev, lds, r_dev, ldr, width, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, t, eps_m, out_dev, ldo,
                                       (hipStream_t)stream));
     return GNNB_OK;
@@ -986,12 +1005,7 @@ int gnnb_aggregate_gen(gnnb_workspace *ws, const float *s_dev, int lds, const fl
 
 int gnnb_rgcn_slots(gnnb_workspace *ws, const int32_t *edge_type_dev, int relations, void *slot_rec_dev, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_rgcn_slots needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's, a GAT v1 model's, with or without edge features)
-        return fail(GNNB_ERR_INVALID, "gnnb_rgcn_slots takes a prepared batch whose tables keep explicit self loops: graph prep drops the "
-                                      "(v, v) edges on a workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts "
-                                      "them as ordinary edges");
+    GNNB_TRY(stage_entry(ws, "gnnb_rgcn_slots", TABLES_KEEP_LOOPS));
     // (a prepared batch without edges launches nothing and reads no operand)
     const bool operands = ws->t.num_edges <= 0 || (edge_type_dev && slot_rec_dev);
     if (!operands || relations < 1 || relations > RGCN_MAX_RELATIONS || ((uintptr_t)slot_rec_dev & 7) != 0)
@@ -1004,17 +1018,11 @@ int gnnb_rgcn_slots(gnnb_workspace *ws, const int32_t *edge_type_dev, int relati
 int gnnb_aggregate_rgcn(gnnb_workspace *ws, const void *slot_rec_dev, const float *p_dev, int ldp, int relations, const float *root_dev, int ldr,
                         const float *skip_dev, int act, float *out_dev, int width, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_rgcn needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type == GNNB_CONV_GCN)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_rgcn takes a prepared batch whose tables keep explicit self loops: graph prep drops the "
-                                      "(v, v) edges on a workspace of a GCN description (a GCN, GATv2 or GAT model's), and this layer counts "
-                                      "them as ordinary edges");
+    GNNB_TRY(stage_entry(ws, "gnnb_aggregate_rgcn", TABLES_KEEP_LOOPS));
     // (a prepared batch without nodes launches nothing and reads no operand: an empty tensor's NULL pointer is no error there)
     const bool operands = ws->t.num_nodes <= 0 || (p_dev && out_dev && (slot_rec_dev || ws->t.num_edges <= 0));
     if (!operands || width < 1 || width > RGCN_MAX_WIDTH || relations < 1 || relations > RGCN_MAX_RELATIONS ||
-        (int64_t)ldp < (int64_t)relations * width || (root_dev && ldr < width) || ((uintptr_t)slot_rec_dev & 7) != 0 || act < GNNB_ACT_RELU ||
-        act > GNNB_ACT_NONE)
+        (int64_t)ldp < (int64_t)relations * width || (root_dev && ldr < width) || ((uintptr_t)slot_rec_dev & 7) != 0 || bad_act(act))
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_rgcn (slot_rec, p and out not NULL unless the batch has no edges / nodes, "
                                       "slot_rec 8-byte aligned, width 1 .. %d, relations 1 .. %d, ldp >= relations width, ldr >= width, a "
                                       "gnnb_act)", RGCN_MAX_WIDTH, RGCN_MAX_RELATIONS);
@@ -1027,18 +1035,8 @@ int gnnb_aggregate_resgated_edges(gnnb_workspace *ws, const float *k_dev, int ld
                                   const float *root_dev, int ldr, const float *skip_dev, int act, const float *edge_attr_dev, int edge_dim,
                                   const float *wg_dev, int ldwg, const float *wv_dev, int ldwv, float *out_dev, int width, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_resgated_edges needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's with or without edge features)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_resgated_edges takes a prepared batch whose tables keep explicit self loops: graph prep "
-                                      "drops the (v, v) edges on a workspace of a GCN description (a GCN or GATv2 model's), and this layer "
-                                      "counts them as ordinary edges");
-    if (!k_dev || !q_dev || !v_dev || !out_dev || width < 1 || width > RG_MAX_WIDTH || ldk < width || ldq < width || ldv < width ||
-        (root_dev && ldr < width) || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE)
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_resgated_edges (k, q, v and out not NULL, width 1 .. %d, ldk, ldq, ldv "
-                                      "and root's ldr >= width, a gnnb_act)", RG_MAX_WIDTH);
-    if (!wg_dev || !wv_dev || edge_dim < 1 || edge_dim > RGE_MAX_EDGE_DIM || ldwg < edge_dim || ldwv < edge_dim ||
-        (ws->t.num_edges > 0 && !edge_attr_dev))
+    GNNB_TRY(resgated_entry(ws, "gnnb_aggregate_resgated_edges", k_dev, ldk, q_dev, ldq, v_dev, ldv, root_dev, ldr, act, out_dev, width));
+    if (bad_edge_operands(ws, edge_attr_dev, edge_dim, RGE_MAX_EDGE_DIM, wg_dev, ldwg) || !wv_dev || ldwv < edge_dim)
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_resgated_edges (wg and wv, edge_dim 1 .. %d, ldwg and ldwv >= edge_dim, "
                                       "edge_attr for a batch with edges)", RGE_MAX_EDGE_DIM);
     GNNB_HIP_TRY(launch_resgated_edge_aggregate(ws->t, k_dev, ldk, q_dev, ldq, v_dev, ldv, root_dev, ldr, skip_dev, act, edge_attr_dev, edge_dim,
@@ -1051,19 +1049,9 @@ int gnnb_aggregate_transformer_edges(gnnb_workspace *ws, const float *q_dev, int
                                      float scale, const float *edge_attr_dev, int edge_dim, const float *we_dev, int ldwe, float *out_dev,
                                      int width, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_transformer_edges needs a prepared batch (gnnb_graph_prep)");
-    if (ws->desc.conv_type == GNNB_CONV_GCN) // (a GCN model's, a GATv2 model's with or without edge features)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate_transformer_edges takes a prepared batch whose tables keep explicit self loops: graph prep "
-                                      "drops the (v, v) edges on a workspace of a GCN description (a GCN or GATv2 model's), and this layer "
-                                      "counts them as ordinary edges, with their attribute rows");
-    if (!q_dev || !k_dev || !v_dev || !out_dev || heads < 1 || heads > TF_MAX_HEADS || width < 1 || width > TF_MAX_WIDTH || width % heads != 0 ||
-        ldq < width || ldk < width || ldv < width || (root_dev && ldr < width) || act < GNNB_ACT_RELU || act > GNNB_ACT_NONE ||
-        !std::isfinite(scale))
-        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_transformer_edges (heads 1 .. %d dividing width 1 .. %d, ldq, ldk, ldv and "
-                                      "root's ldr >= width, a gnnb_act, a finite scale)", TF_MAX_HEADS, TF_MAX_WIDTH);
-    if (!qe_dev || !we_dev || edge_dim < 1 || edge_dim > TFE_MAX_EDGE_DIM || ldqe < heads * edge_dim || ldwe < edge_dim ||
-        (ws->t.num_edges > 0 && !edge_attr_dev))
+    GNNB_TRY(transformer_entry(ws, "gnnb_aggregate_transformer_edges", q_dev, ldq, k_dev, ldk, v_dev, ldv, root_dev, ldr, act, heads, scale,
+                                   out_dev, width));
+    if (bad_edge_operands(ws, edge_attr_dev, edge_dim, TFE_MAX_EDGE_DIM, we_dev, ldwe) || !qe_dev || ldqe < heads * edge_dim)
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_transformer_edges (qe and we, edge_dim 1 .. %d, ldqe >= heads * edge_dim, "
                                       "ldwe >= edge_dim, edge_attr for a batch with edges)", TFE_MAX_EDGE_DIM);
     GNNB_HIP_TRY(launch_transformer_edge_aggregate(ws->t, q_dev, ldq, k_dev, ldk, v_dev, ldv, qe_dev, ldqe, root_dev, ldr, skip_dev, act, heads,
@@ -1074,8 +1062,7 @@ int gnnb_aggregate_transformer_edges(gnnb_workspace *ws, const float *q_dev, int
 int gnnb_pna_product_aggregate(gnnb_workspace *ws, const float *x_dev, const float *wb_dev, int ldw, float *out_dev, int width,
                                void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_pna_product_aggregate needs a prepared batch (gnnb_graph_prep)");
+    GNNB_TRY(stage_entry(ws, "gnnb_pna_product_aggregate", TABLES_ANY));
     MathScope math_scope(ws->desc.math);
     if (!x_dev || !wb_dev || !out_dev || width < 1 || ldw < width)
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_pna_product_aggregate");
@@ -1091,8 +1078,7 @@ int gnnb_pna_product_aggregate(gnnb_workspace *ws, const float *x_dev, const flo
 int gnnb_aggregate(gnnb_workspace *ws, int agg_kind, const float *x_dev, const float *self_dev,
                    float *out_dev, int width, float eps, void *stream)
 {
-    if (!ws || !ws->prepared)
-        return fail(GNNB_ERR_INVALID, "gnnb_aggregate needs a prepared batch (gnnb_graph_prep)");
+    GNNB_TRY(stage_entry(ws, "gnnb_aggregate", TABLES_ANY));
     if (!x_dev || !out_dev || width < 1)
         return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate");
     if (agg_kind < GNNB_AGG_GCN || agg_kind > GNNB_AGG_COPY)
@@ -1100,11 +1086,8 @@ int gnnb_aggregate(gnnb_workspace *ws, int agg_kind, const float *x_dev, const f
     // (PNA with self_dev == NULL: no destination term -- the statistics of p_j alone, what the degree-class form aggregates)
     if (ws->t.num_nodes == 0)
         return GNNB_OK;
-    if (agg_kind == GNNB_AGG_GCN) {
-        int rc = ensure_gcoef(ws, stream);
-        if (rc != GNNB_OK)
-            return rc;
-    }
+    if (agg_kind == GNNB_AGG_GCN)
+        GNNB_TRY(ensure_gcoef(ws, stream));
     GNNB_HIP_TRY(launch_aggregate(ws->t, agg_kind, x_dev, self_dev, out_dev, width, eps,
                                   (hipStream_t)stream));
     return GNNB_OK;

@@ -471,6 +471,54 @@ def _require_strided(t, name: str, rows: Optional[int] = None, min_cols: int = 0
                         (f"at least {min_cols} columns" if rows is None else f"{rows} rows"))
 
 
+# ---- the operand vocabulary of the stage entry points (CompiledModel.aggregate_* ...): each check once, each message once
+def _ld(t, cols: int) -> int:
+    """The row stride that crosses the ABI beside a matrix's pointer; ``cols`` for a matrix of one row or none (any stride
+    describes it, and a view's own may be below what the C side requires)."""
+    return int(t.stride(0)) if t.shape[0] > 1 else cols
+
+
+def _require_block(t, name: str, rows: int, w: int, like, min_cols: Optional[int] = None) -> None:
+    """``_require_strided`` for a column block the kernels read as exactly [rows, w] beside ``like``."""
+    _require_strided(t, name, rows, w if min_cols is None else min_cols)
+    if int(t.shape[1]) != w or t.device != like.device:
+        raise GnnbError(f"{name} must be [{rows}, {w}] on {like.device}, got {tuple(t.shape)} on {t.device}")
+
+
+def _require_vector(t, name: str, w: int, like) -> None:
+    """A bias-like operand: fp32 [w], contiguous, on ``like``'s device."""
+    import torch
+    _require(t, name, torch.float32, 1, w)
+    if t.device != like.device:
+        raise GnnbError(f"{name} must be on {like.device}")
+
+
+def _require_edge_weight(wm, name: str, rows: int, like) -> int:
+    """A matrix applied to the attribute rows, [rows, edge_dim] with its row stride passed on; returns ``edge_dim``."""
+    _require_strided(wm, name, rows, 1)
+    ed = int(wm.shape[1])
+    if not 1 <= ed <= MAX_EDGE_DIM or wm.device != like.device:
+        raise GnnbError(f"{name} must be [{rows}, 1 .. {MAX_EDGE_DIM}] on {like.device}, got {tuple(wm.shape)} on {wm.device}")
+    return ed
+
+
+def _require_heads(heads, w: int, max_heads: int, max_width: int, layer: str) -> None:
+    if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= max_heads:
+        raise GnnbError(f"heads must be an int in 1 .. {max_heads}, got {heads!r}")
+    if w > max_width or w % heads:
+        raise GnnbError(f"width {w}: a {layer} layer is at most {max_width} wide and divisible by heads ({heads})")
+
+
+def _require_act(act) -> None:
+    if act not in ACT:
+        raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+
+
+def _require_relations(relations) -> None:
+    if not isinstance(relations, int) or isinstance(relations, bool) or not 1 <= relations <= MAX_RGCN_RELATIONS:
+        raise GnnbError(f"relations must be an int in 1 .. {MAX_RGCN_RELATIONS}, got {relations!r}")
+
+
 # the add-ons of a workspace (CompiledModel.enable_*): the refusal of a call made before its enable
 _NOT_ENABLED = {
     "ingest": "ingest is not enabled on this model's workspace: call enable_ingest() once after construction",
@@ -1092,24 +1140,22 @@ class CompiledModel:
                                              float(eps), _stream_ptr(stream)))
         return out
 
+    def _edge_projection(self, edge_attr, w_edge, b_edge, w: int, like):
+        """The edge operands of GINE's and PNA's fused aggregates; returns (``edge_attr``'s pointer or None, edge_dim)."""
+        ed = _require_edge_weight(w_edge, "w_edge", w, like)
+        _require_vector(b_edge, "b_edge", w, like)
+        return self._require_edge_attr(edge_attr, self._E, like, ed), ed
+
     def aggregate_edges_fused(self, x, edge_attr, w_edge, b_edge, eps: float = 0.0, out=None, stream=None):
         """GINE aggregate with the edge projection inside the kernel (``gnnb_aggregate_edges_fused``, csrc/k_gine.hip):
         ``(1 + eps) x_i + sum_j relu(x_j + w_edge e_ij + b_edge)``; ``edge_attr`` [E, edge_dim <= 16] in COO order, ``w_edge``
         [width, edge_dim] (a column slice of a wider matrix is fine: its row stride is passed on), ``b_edge`` [width]."""
-        import torch
         self._require_x(x)
         w = int(x.shape[1])
-        _require_strided(w_edge, "w_edge", w, 1)
-        ed = int(w_edge.shape[1])
-        if not 1 <= ed <= MAX_EDGE_DIM or w_edge.device != x.device:
-            raise GnnbError(f"w_edge must be [{w}, 1 .. {MAX_EDGE_DIM}] on {x.device}, got {tuple(w_edge.shape)} on {w_edge.device}")
-        _require(b_edge, "b_edge", torch.float32, 1, w)
-        if b_edge.device != x.device:
-            raise GnnbError(f"b_edge must be on {x.device}")
-        ea = self._require_edge_attr(edge_attr, self._E, x, ed)
+        ea, ed = self._edge_projection(edge_attr, w_edge, b_edge, w, x)
         out = _out(out, self._N, w, x)
-        _check(self.lib.gnnb_aggregate_edges_fused(self._ws, _dptr(x), ea, ed, _dptr(w_edge), int(w_edge.stride(0)) if w > 1 else ed,
-                                                   _dptr(b_edge), _dptr(out), w, float(eps), _stream_ptr(stream)))
+        _check(self.lib.gnnb_aggregate_edges_fused(self._ws, _dptr(x), ea, ed, _dptr(w_edge), _ld(w_edge, ed), _dptr(b_edge), _dptr(out), w,
+                                                   float(eps), _stream_ptr(stream)))
         return out
 
     def aggregate_pna_edges(self, p, q, edge_attr, w_edge, b_edge, out=None, stream=None):
@@ -1118,43 +1164,24 @@ class CompiledModel:
         ``aggregate("pna", ...)``; ``p`` [N, width], ``q`` [N, width] or None (no destination term), ``edge_attr``
         [E, edge_dim <= 16] in COO order, ``w_edge`` [width, edge_dim] (a column slice of a wider matrix is fine: its row stride is
         passed on), ``b_edge`` [width]."""
-        import torch
         self._require_x(p)
         w = int(p.shape[1])
         if q is not None:
             _require_rows(q, "q", self._N, w, p)
-        _require_strided(w_edge, "w_edge", w, 1)
-        ed = int(w_edge.shape[1])
-        if not 1 <= ed <= MAX_EDGE_DIM or w_edge.device != p.device:
-            raise GnnbError(f"w_edge must be [{w}, 1 .. {MAX_EDGE_DIM}] on {p.device}, got {tuple(w_edge.shape)} on {w_edge.device}")
-        _require(b_edge, "b_edge", torch.float32, 1, w)
-        if b_edge.device != p.device:
-            raise GnnbError(f"b_edge must be on {p.device}")
-        ea = self._require_edge_attr(edge_attr, self._E, p, ed)
+        ea, ed = self._edge_projection(edge_attr, w_edge, b_edge, w, p)
         out = _out(out, self._N, 4 * w, p)
-        _check(self.lib.gnnb_aggregate_pna_edges(self._ws, _dptr(p), _optr(q), ea, ed, _dptr(w_edge), int(w_edge.stride(0)) if w > 1 else ed,
-                                                 _dptr(b_edge), _dptr(out), w, _stream_ptr(stream)))
+        _check(self.lib.gnnb_aggregate_pna_edges(self._ws, _dptr(p), _optr(q), ea, ed, _dptr(w_edge), _ld(w_edge, ed), _dptr(b_edge), _dptr(out),
+                                                 w, _stream_ptr(stream)))
         return out
 
-    def aggregate_gatv2(self, xl, xr, att, bias=None, skip=None, act: str = "none", heads: int = 1, negative_slope: float = 0.2, out=None,
-                        stream=None):
-        """One GATv2 layer behind its GEMM (``gnnb_aggregate_gatv2``, csrc/k_gatv2.hip) on the prepared batch of a GCN or GATv2
-        model's workspace: ``act(sum_j softmax_j(s_ij) xl_j + bias + skip_i)`` over ``j`` in ``N(i)`` and ``i`` itself, per head,
-        ``s_ij = att_h . leaky_relu(xl_j + xr_i)`` -> [N, width].  ``xl``, ``xr`` [N, width] (column slices of a wider matrix are
-        fine -- the two halves of one [N, 2 width] GEMM output: their row strides are passed on), ``att`` [width] (or PyG's
-        [1, heads, width / heads]), ``bias`` [width] or None, ``skip`` [N, width] or None; ``heads`` 1 .. 8 dividing ``width`` <= 256."""
+    def _gatv2_operands(self, xl, xr, att, bias, skip, act, heads):
+        """What ``aggregate_gatv2`` and ``aggregate_gatv2_edges`` both take, checked; returns (width, ``att`` as [width])."""
         import torch
         _require_strided(xl, "xl", self._N, 1)
         w = int(xl.shape[1])
-        _require_strided(xr, "xr", self._N, w)
-        if int(xr.shape[1]) != w or xr.device != xl.device:
-            raise GnnbError(f"xr must be [{self._N}, {w}] on {xl.device}, got {tuple(xr.shape)} on {xr.device}")
-        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
-            raise GnnbError(f"heads must be an int in 1 .. {MAX_GAT_HEADS}, got {heads!r}")
-        if w > MAX_GAT_WIDTH or w % heads:
-            raise GnnbError(f"width {w}: a GATv2 layer is at most {MAX_GAT_WIDTH} wide and divisible by heads ({heads})")
-        if act not in ACT:
-            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        _require_block(xr, "xr", self._N, w, xl)
+        _require_heads(heads, w, MAX_GAT_HEADS, MAX_GAT_WIDTH, "GATv2")
+        _require_act(act)
         if not isinstance(att, torch.Tensor) or att.numel() != w:
             raise GnnbError(f"att must hold {w} values ([{w}] or [1, {heads}, {w // heads}])")
         att = att.reshape(w)
@@ -1165,11 +1192,34 @@ class CompiledModel:
             raise GnnbError(f"att and bias must be on {xl.device}")
         if skip is not None:
             _require_rows(skip, "skip", self._N, w, xl)
+        return w, att
+
+    def aggregate_gatv2(self, xl, xr, att, bias=None, skip=None, act: str = "none", heads: int = 1, negative_slope: float = 0.2, out=None,
+                        stream=None):
+        """One GATv2 layer behind its GEMM (``gnnb_aggregate_gatv2``, csrc/k_gatv2.hip) on the prepared batch of a GCN or GATv2
+        model's workspace: ``act(sum_j softmax_j(s_ij) xl_j + bias + skip_i)`` over ``j`` in ``N(i)`` and ``i`` itself, per head,
+        ``s_ij = att_h . leaky_relu(xl_j + xr_i)`` -> [N, width].  ``xl``, ``xr`` [N, width] (column slices of a wider matrix are
+        fine -- the two halves of one [N, 2 width] GEMM output: their row strides are passed on), ``att`` [width] (or PyG's
+        [1, heads, width / heads]), ``bias`` [width] or None, ``skip`` [N, width] or None; ``heads`` 1 .. 8 dividing ``width`` <= 256."""
+        w, att = self._gatv2_operands(xl, xr, att, bias, skip, act, heads)
         out = _out(out, self._N, w, xl)
-        _check(self.lib.gnnb_aggregate_gatv2(self._ws, _dptr(xl), int(xl.stride(0)) if self._N > 1 else w, _dptr(xr),
-                                             int(xr.stride(0)) if self._N > 1 else w, _dptr(att), _optr(bias), _optr(skip), ACT[act], heads,
-                                             float(negative_slope), _dptr(out), w, _stream_ptr(stream)))
+        _check(self.lib.gnnb_aggregate_gatv2(self._ws, _dptr(xl), _ld(xl, w), _dptr(xr), _ld(xr, w), _dptr(att), _optr(bias), _optr(skip), ACT[act],
+                                             heads, float(negative_slope), _dptr(out), w, _stream_ptr(stream)))
         return out
+
+    def _gat_operands(self, xl, s_src, s_dst, bias, skip, act, heads) -> int:
+        """What ``aggregate_gat`` and ``aggregate_gat_edges`` both take, checked; returns the width."""
+        _require_strided(xl, "xl", self._N, 1)
+        w = int(xl.shape[1])
+        _require_heads(heads, w, MAX_GAT_HEADS, MAX_GAT_WIDTH, "GAT")
+        _require_block(s_src, "s_src", self._N, heads, xl)
+        _require_block(s_dst, "s_dst", self._N, heads, xl)
+        _require_act(act)
+        if bias is not None:
+            _require_vector(bias, "bias", w, xl)
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, xl)
+        return w
 
     def aggregate_gat(self, xl, s_src, s_dst, bias=None, skip=None, act: str = "none", heads: int = 1, negative_slope: float = 0.2,
                       out=None, stream=None):
@@ -1178,95 +1228,75 @@ class CompiledModel:
         ``s_ij[h] = leaky_relu(s_src[j, h] + s_dst[i, h])`` -> [N, width].  ``xl`` [N, width], ``s_src`` and ``s_dst`` [N, heads]
         (column slices of a wider matrix are fine -- the blocks of one GEMM output: their row strides are passed on), ``bias``
         [width] or None, ``skip`` [N, width] or None; ``heads`` 1 .. 8 dividing ``width`` <= 256."""
-        import torch
-        _require_strided(xl, "xl", self._N, 1)
-        w = int(xl.shape[1])
-        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
-            raise GnnbError(f"heads must be an int in 1 .. {MAX_GAT_HEADS}, got {heads!r}")
-        if w > MAX_GAT_WIDTH or w % heads:
-            raise GnnbError(f"width {w}: a GAT layer is at most {MAX_GAT_WIDTH} wide and divisible by heads ({heads})")
-        for t, name in ((s_src, "s_src"), (s_dst, "s_dst")):
-            _require_strided(t, name, self._N, heads)
-            if int(t.shape[1]) != heads or t.device != xl.device:
-                raise GnnbError(f"{name} must be [{self._N}, {heads}] on {xl.device}, got {tuple(t.shape)} on {t.device}")
-        if act not in ACT:
-            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
-        if bias is not None:
-            _require(bias, "bias", torch.float32, 1, w)
-            if bias.device != xl.device:
-                raise GnnbError(f"bias must be on {xl.device}")
-        if skip is not None:
-            _require_rows(skip, "skip", self._N, w, xl)
+        w = self._gat_operands(xl, s_src, s_dst, bias, skip, act, heads)
         out = _out(out, self._N, w, xl)
-
-        def ld(t, cols):
-            return int(t.stride(0)) if self._N > 1 else cols
-        _check(self.lib.gnnb_aggregate_gat(self._ws, _dptr(xl), ld(xl, w), _dptr(s_src), ld(s_src, heads), _dptr(s_dst), ld(s_dst, heads),
+        _check(self.lib.gnnb_aggregate_gat(self._ws, _dptr(xl), _ld(xl, w), _dptr(s_src), _ld(s_src, heads), _dptr(s_dst), _ld(s_dst, heads),
                                            _optr(bias), _optr(skip), ACT[act], heads, float(negative_slope), _dptr(out), w,
                                            _stream_ptr(stream)))
         return out
 
-    def aggregate_transformer(self, q, k, v, root=None, skip=None, act: str = "none", heads: int = 1, scale: Optional[float] = None,
-                              out=None, stream=None):
-        """One TransformerConv layer behind its GEMM (``gnnb_aggregate_transformer``, csrc/k_transformer.hip) on the prepared batch
-        of a workspace whose tables keep explicit self loops (any but a GCN or GATv2 model's, which is refused):
-        ``act((sum_j softmax_j(s_ij) v_j + root_i) + skip_i)`` over ``j`` in ``N(i)`` as the batch holds it, per head,
-        ``s_ij = (q_i . k_j) * scale`` -> [N, width].  ``q``, ``k``, ``v`` [N, width] and ``root`` [N, width] or None (column
-        slices of a wider matrix are fine -- the four blocks of one [N, 4 width] GEMM output: their row strides are passed on),
-        ``skip`` [N, width] contiguous or None; ``heads`` 1 .. 8 dividing ``width`` <= 256; ``scale=None``: ``1 / sqrt(width /
-        heads)``."""
-        _require_strided(q, "q", self._N, 1)
-        w = int(q.shape[1])
-        for name, t in (("k", k), ("v", v), ("root", root)):
-            if t is None and name == "root":
-                continue
-            _require_strided(t, name, self._N, w)
-            if int(t.shape[1]) != w or t.device != q.device:
-                raise GnnbError(f"{name} must be [{self._N}, {w}] on {q.device}, got {tuple(t.shape)} on {t.device}")
-        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_TRANSFORMER_HEADS:
-            raise GnnbError(f"heads must be an int in 1 .. {MAX_TRANSFORMER_HEADS}, got {heads!r}")
-        if w > MAX_TRANSFORMER_WIDTH or w % heads:
-            raise GnnbError(f"width {w}: a TransformerConv layer is at most {MAX_TRANSFORMER_WIDTH} wide and divisible by heads ({heads})")
-        if act not in ACT:
-            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+    def _require_blocks(self, named, root) -> int:
+        """The column blocks of one GEMM output, ``named`` = ((name, tensor), ...): the first sets the width, the others and
+        ``root`` (or None) are as wide beside it; returns the width."""
+        (name, first), *rest = named
+        _require_strided(first, name, self._N, 1)
+        w = int(first.shape[1])
+        for name, t in rest:
+            _require_block(t, name, self._N, w, first)
+        if root is not None:
+            _require_block(root, "root", self._N, w, first)
+        return w
+
+    def _transformer_operands(self, q, k, v, root, skip, act, heads, scale):
+        """What ``aggregate_transformer`` and ``aggregate_transformer_edges`` both take, checked; returns (width, scale)."""
+        w = self._require_blocks((("q", q), ("k", k), ("v", v)), root)
+        _require_heads(heads, w, MAX_TRANSFORMER_HEADS, MAX_TRANSFORMER_WIDTH, "TransformerConv")
+        _require_act(act)
         if scale is None:
             scale = float(np.float32(1.0) / np.sqrt(np.float32(w // heads)))  # (in fp32, as the layer's own)
         if not np.isfinite(scale):
             raise GnnbError(f"scale must be finite, got {scale!r}")
         if skip is not None:
             _require_rows(skip, "skip", self._N, w, q)
+        return w, scale
+
+    def aggregate_transformer(self, q, k, v, root=None, skip=None, act: str = "none", heads: int = 1, scale: Optional[float] = None,
+                              out=None, stream=None):
+        """One TransformerConv layer behind its GEMM (``gnnb_aggregate_transformer``, csrc/k_transformer.hip) on the prepared batch
+        of a workspace whose tables keep explicit self loops (any but a GCN, GATv2 or GAT model's, which is refused):
+        ``act((sum_j softmax_j(s_ij) v_j + root_i) + skip_i)`` over ``j`` in ``N(i)`` as the batch holds it, per head,
+        ``s_ij = (q_i . k_j) * scale`` -> [N, width].  ``q``, ``k``, ``v`` [N, width] and ``root`` [N, width] or None (column
+        slices of a wider matrix are fine -- the four blocks of one [N, 4 width] GEMM output: their row strides are passed on),
+        ``skip`` [N, width] contiguous or None; ``heads`` 1 .. 8 dividing ``width`` <= 256; ``scale=None``: ``1 / sqrt(width /
+        heads)``."""
+        w, scale = self._transformer_operands(q, k, v, root, skip, act, heads, scale)
         out = _out(out, self._N, w, q)
-        ld = lambda t: int(t.stride(0)) if self._N > 1 else w  # noqa: E731  (one row: any stride describes it)
-        _check(self.lib.gnnb_aggregate_transformer(self._ws, _dptr(q), ld(q), _dptr(k), ld(k), _dptr(v), ld(v), _optr(root),
-                                                   ld(root) if root is not None else w, _optr(skip), ACT[act], heads, float(scale),
+        _check(self.lib.gnnb_aggregate_transformer(self._ws, _dptr(q), _ld(q, w), _dptr(k), _ld(k, w), _dptr(v), _ld(v, w), _optr(root),
+                                                   _ld(root, w) if root is not None else w, _optr(skip), ACT[act], heads, float(scale),
                                                    _dptr(out), w, _stream_ptr(stream)))
         return out
 
+    def _resgated_operands(self, k, q, v, root, skip, act) -> int:
+        """What ``aggregate_resgated`` and ``aggregate_resgated_edges`` both take, checked; returns the width."""
+        w = self._require_blocks((("k", k), ("q", q), ("v", v)), root)
+        if w > MAX_RESGATED_WIDTH:
+            raise GnnbError(f"width {w}: a ResGatedGraphConv layer is at most {MAX_RESGATED_WIDTH} wide")
+        _require_act(act)
+        if skip is not None:
+            _require_rows(skip, "skip", self._N, w, k)
+        return w
+
     def aggregate_resgated(self, k, q, v, root=None, skip=None, act: str = "none", out=None, stream=None):
         """One ResGatedGraphConv layer behind its GEMM (``gnnb_aggregate_resgated``, csrc/k_resgated.hip) on the prepared batch of a
-        workspace whose tables keep explicit self loops (any but a GCN or GATv2 model's, which is refused):
+        workspace whose tables keep explicit self loops (any but a GCN, GATv2 or GAT model's, which is refused):
         ``act((sum_j sigmoid(k_i + q_j) * v_j + root_i) + skip_i)`` over ``j`` in ``N(i)`` as the batch holds it, the gate per
         column -> [N, width].  ``k``, ``q``, ``v`` [N, width] and ``root`` [N, width] or None (column slices of a wider matrix are
         fine -- the four blocks of one [N, 4 width] GEMM output: their row strides are passed on), ``skip`` [N, width] contiguous
         or None; ``width`` <= 256."""
-        _require_strided(k, "k", self._N, 1)
-        w = int(k.shape[1])
-        for name, t in (("q", q), ("v", v), ("root", root)):
-            if t is None and name == "root":
-                continue
-            _require_strided(t, name, self._N, w)
-            if int(t.shape[1]) != w or t.device != k.device:
-                raise GnnbError(f"{name} must be [{self._N}, {w}] on {k.device}, got {tuple(t.shape)} on {t.device}")
-        if w > MAX_RESGATED_WIDTH:
-            raise GnnbError(f"width {w}: a ResGatedGraphConv layer is at most {MAX_RESGATED_WIDTH} wide")
-        if act not in ACT:
-            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
-        if skip is not None:
-            _require_rows(skip, "skip", self._N, w, k)
+        w = self._resgated_operands(k, q, v, root, skip, act)
         out = _out(out, self._N, w, k)
-        ld = lambda t: int(t.stride(0)) if self._N > 1 else w  # noqa: E731  (one row: any stride describes it)
-        _check(self.lib.gnnb_aggregate_resgated(self._ws, _dptr(k), ld(k), _dptr(q), ld(q), _dptr(v), ld(v), _optr(root),
-                                                ld(root) if root is not None else w, _optr(skip), ACT[act], _dptr(out), w,
+        _check(self.lib.gnnb_aggregate_resgated(self._ws, _dptr(k), _ld(k, w), _dptr(q), _ld(q, w), _dptr(v), _ld(v, w), _optr(root),
+                                                _ld(root, w) if root is not None else w, _optr(skip), ACT[act], _dptr(out), w,
                                                 _stream_ptr(stream)))
         return out
 
@@ -1291,17 +1321,15 @@ class CompiledModel:
                             f"and {tuple(h.shape)} on {h.device}")
         if w > MAX_GGNN_WIDTH:
             raise GnnbError(f"width {w}: a GatedGraphConv layer is at most {MAX_GGNN_WIDTH} wide")
-        if act not in ACT:
-            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        _require_act(act)
         if b_ih is not None and (not isinstance(b_ih, torch.Tensor) or b_ih.dtype != torch.float32 or b_ih.device != p.device or
                                  b_ih.dim() != 1 or b_ih.numel() != 3 * w or not b_ih.is_contiguous()):
             raise GnnbError(f"b_ih must be a contiguous float32 [{3 * w}] on {p.device}")
         if skip is not None:
             _require_rows(skip, "skip", self._N, w, p)
         out = _out(out, self._N, w, p)
-        ld = lambda t: int(t.stride(0)) if self._N > 1 else int(t.shape[1])  # noqa: E731  (one row: any stride describes it)
-        _check(self.lib.gnnb_aggregate_ggnn(self._ws, _dptr(p), ld(p), _dptr(gh), ld(gh), _dptr(h), ld(h), hw, _optr(b_ih), _optr(skip),
-                                            ACT[act], _dptr(out), w, _stream_ptr(stream)))
+        _check(self.lib.gnnb_aggregate_ggnn(self._ws, _dptr(p), _ld(p, 3 * w), _dptr(gh), _ld(gh, 3 * w), _dptr(h), _ld(h, hw), hw, _optr(b_ih),
+                                            _optr(skip), ACT[act], _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def aggregate_nnconv(self, x, edge_attr, w1=None, b1=None, aggr: str = "add", out=None, stream=None):
@@ -1327,20 +1355,15 @@ class CompiledModel:
             hidden = int(w1.shape[0])
             if not 1 <= hidden <= MAX_NNCONV_HIDDEN or w1.device != x.device:
                 raise GnnbError(f"w1 must be [1 .. {MAX_NNCONV_HIDDEN}, {ed}] on {x.device}, got {tuple(w1.shape)} on {w1.device}")
-            _require(b1, "b1", torch.float32, 1, hidden)
-            if b1.device != x.device:
-                raise GnnbError(f"b1 must be on {x.device}")
+            _require_vector(b1, "b1", hidden, x)
         if aggr not in NN_AGGR:
             raise GnnbError(f"aggr must be one of {sorted(NN_AGGR)}, got {aggr!r}")
         cols = ((hidden or ed) + 1) * w
         if out is None:
             out = torch.empty((self._N, cols), dtype=torch.float32, device=x.device)
-        _require_strided(out, "out", self._N, cols)
-        if int(out.shape[1]) != cols or out.device != x.device:
-            raise GnnbError(f"out must be [{self._N}, {cols}] on {x.device}, got {tuple(out.shape)} on {out.device}")
-        ldo = int(out.stride(0)) if self._N > 1 else cols
+        _require_block(out, "out", self._N, cols, x)
         _check(self.lib.gnnb_aggregate_nnconv(self._ws, _dptr(x), w, _dptr(edge_attr) if self._E else None, ed, _optr(w1), _optr(b1), hidden,
-                                              NN_AGGR[aggr], _dptr(out), ldo, _stream_ptr(stream)))
+                                              NN_AGGR[aggr], _dptr(out), _ld(out, cols), _stream_ptr(stream)))
         return out
 
     def aggregate_gen(self, s, r=None, edge_attr=None, we=None, be=None, t: float = 1.0, eps: float = 1e-7, out=None, stream=None):
@@ -1356,9 +1379,7 @@ class CompiledModel:
         if not 1 <= w <= MAX_GEN_WIDTH:
             raise GnnbError(f"s must be [{self._N}, 1 .. {MAX_GEN_WIDTH}], got {tuple(s.shape)}")
         if r is not None:
-            _require_strided(r, "r", self._N)
-            if int(r.shape[1]) != w or r.device != s.device:
-                raise GnnbError(f"r must be [{self._N}, {w}] on {s.device}, got {tuple(r.shape)} on {r.device}")
+            _require_block(r, "r", self._N, w, s, min_cols=0)
         if (edge_attr is None) != (we is None) or (we is None) != (be is None):
             raise GnnbError("edge_attr, we and be come together (all None: no edge term)")
         ed = 0
@@ -1368,18 +1389,13 @@ class CompiledModel:
             ed = int(edge_attr.shape[1])
             _require_rows(edge_attr, "edge_attr", self._E, ed, s)
             _require_rows(we, "we", w, ed, s)
-            _require(be, "be", torch.float32, 1, w)
-            if be.device != s.device:
-                raise GnnbError(f"be must be on {s.device}")
+            _require_vector(be, "be", w, s)
         if out is None:
             out = torch.empty((self._N, w), dtype=torch.float32, device=s.device)
-        _require_strided(out, "out", self._N)
-        if int(out.shape[1]) != w or out.device != s.device:
-            raise GnnbError(f"out must be [{self._N}, {w}] on {s.device}, got {tuple(out.shape)} on {out.device}")
-        ld = lambda a: int(a.stride(0)) if self._N > 1 else w  # noqa: E731
-        _check(self.lib.gnnb_aggregate_gen(self._ws, _dptr(s), ld(s), _optr(r), ld(r) if r is not None else w, w,
+        _require_block(out, "out", self._N, w, s, min_cols=0)
+        _check(self.lib.gnnb_aggregate_gen(self._ws, _dptr(s), _ld(s, w), _optr(r), _ld(r, w) if r is not None else w, w,
                                            _dptr(edge_attr) if ed and self._E else None, ed, _optr(we), ed, _optr(be), float(t), float(eps),
-                                           _dptr(out), ld(out), _stream_ptr(stream)))
+                                           _dptr(out), _ld(out, w), _stream_ptr(stream)))
         return out
 
     def rgcn_slots(self, edge_type, relations: int, stream=None):
@@ -1388,8 +1404,7 @@ class CompiledModel:
         float32 ``1 / |N_rel(i)|``) of CSR slot ``s`` -- ``rec[:, 1].view(torch.float32)`` gives the weights.  A type outside
         ``[0, relations)`` gives (0, 0.0) and flags the batch (``check()``: flag 0x100).  What ``aggregate_rgcn`` takes."""
         import torch
-        if not isinstance(relations, int) or isinstance(relations, bool) or not 1 <= relations <= MAX_RGCN_RELATIONS:
-            raise GnnbError(f"relations must be an int in 1 .. {MAX_RGCN_RELATIONS}, got {relations!r}")
+        _require_relations(relations)
         if edge_type is None and self._E:
             raise GnnbError(f"edge_type is required: the batch has {self._E} edges")
         if edge_type is not None:
@@ -1411,8 +1426,7 @@ class CompiledModel:
         (the blocks of one [N, (relations + 1) width] GEMM output: their row strides are passed on); ``skip`` [N, width] contiguous
         or None; ``width`` <= 256."""
         import torch
-        if not isinstance(relations, int) or isinstance(relations, bool) or not 1 <= relations <= MAX_RGCN_RELATIONS:
-            raise GnnbError(f"relations must be an int in 1 .. {MAX_RGCN_RELATIONS}, got {relations!r}")
+        _require_relations(relations)
         _require_strided(p, "p", self._N, relations)
         if int(p.shape[1]) % relations:
             raise GnnbError(f"p must be [{self._N}, relations * width], got {tuple(p.shape)} for {relations} relations")
@@ -1424,17 +1438,13 @@ class CompiledModel:
             raise GnnbError(f"rec must be the [{self._E}, 2] int32 records of rgcn_slots on {p.device}, 8-byte aligned; got "
                             f"{tuple(rec.shape)} on {rec.device}")
         if root is not None:
-            _require_strided(root, "root", self._N, w)
-            if int(root.shape[1]) != w or root.device != p.device:
-                raise GnnbError(f"root must be [{self._N}, {w}] on {p.device}, got {tuple(root.shape)} on {root.device}")
-        if act not in ACT:
-            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
+            _require_block(root, "root", self._N, w, p)
+        _require_act(act)
         if skip is not None:
             _require_rows(skip, "skip", self._N, w, p)
         out = _out(out, self._N, w, p)
-        ld = lambda t: int(t.stride(0)) if self._N > 1 else int(t.shape[1])  # noqa: E731  (one row: any stride describes it)
-        _check(self.lib.gnnb_aggregate_rgcn(self._ws, _dptr(rec) if self._E else None, _dptr(p), ld(p), relations, _optr(root),
-                                            ld(root) if root is not None else 0, _optr(skip), ACT[act], _dptr(out), w, _stream_ptr(stream)))
+        _check(self.lib.gnnb_aggregate_rgcn(self._ws, _dptr(rec) if self._E else None, _dptr(p), _ld(p, relations * w), relations, _optr(root),
+                                            _ld(root, w) if root is not None else 0, _optr(skip), ACT[act], _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def aggregate_resgated_edges(self, k, q, v, edge_attr, w_gate, w_value, root=None, skip=None, act: str = "none", out=None, stream=None):
@@ -1444,34 +1454,14 @@ class CompiledModel:
         column.  ``k``, ``q``, ``v``, ``root``, ``skip`` as there; ``edge_attr`` [E, edge_dim <= 16] in COO order; ``w_gate`` (the
         layer passes ``W_ke + W_qe``; the entry computes what it is given) and ``w_value`` [width, edge_dim], separate operands;
         column slices of wider matrices are fine for them too: their row strides are passed on."""
-        _require_strided(k, "k", self._N, 1)
-        w = int(k.shape[1])
-        for name, t in (("q", q), ("v", v), ("root", root)):
-            if t is None and name == "root":
-                continue
-            _require_strided(t, name, self._N, w)
-            if int(t.shape[1]) != w or t.device != k.device:
-                raise GnnbError(f"{name} must be [{self._N}, {w}] on {k.device}, got {tuple(t.shape)} on {t.device}")
-        if w > MAX_RESGATED_WIDTH:
-            raise GnnbError(f"width {w}: a ResGatedGraphConv layer is at most {MAX_RESGATED_WIDTH} wide")
-        if act not in ACT:
-            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
-        if skip is not None:
-            _require_rows(skip, "skip", self._N, w, k)
-        _require_strided(w_gate, "w_gate", w, 1)
-        ed = int(w_gate.shape[1])
-        if not 1 <= ed <= MAX_EDGE_DIM or w_gate.device != k.device:
-            raise GnnbError(f"w_gate must be [{w}, 1 .. {MAX_EDGE_DIM}] on {k.device}, got {tuple(w_gate.shape)} on {w_gate.device}")
-        _require_strided(w_value, "w_value", w, ed)
-        if int(w_value.shape[1]) != ed or w_value.device != k.device:
-            raise GnnbError(f"w_value must be [{w}, {ed}] on {k.device}, got {tuple(w_value.shape)} on {w_value.device}")
+        w = self._resgated_operands(k, q, v, root, skip, act)
+        ed = _require_edge_weight(w_gate, "w_gate", w, k)
+        _require_block(w_value, "w_value", w, ed, k)
         ea = self._require_edge_attr(edge_attr, self._E, k, ed)
         out = _out(out, self._N, w, k)
-        ld = lambda t: int(t.stride(0)) if self._N > 1 else w  # noqa: E731  (one row: any stride describes it)
-        ldw = lambda t: int(t.stride(0)) if w > 1 else ed  # noqa: E731
-        _check(self.lib.gnnb_aggregate_resgated_edges(self._ws, _dptr(k), ld(k), _dptr(q), ld(q), _dptr(v), ld(v), _optr(root),
-                                                      ld(root) if root is not None else w, _optr(skip), ACT[act], ea, ed, _dptr(w_gate),
-                                                      ldw(w_gate), _dptr(w_value), ldw(w_value), _dptr(out), w, _stream_ptr(stream)))
+        _check(self.lib.gnnb_aggregate_resgated_edges(self._ws, _dptr(k), _ld(k, w), _dptr(q), _ld(q, w), _dptr(v), _ld(v, w), _optr(root),
+                                                      _ld(root, w) if root is not None else w, _optr(skip), ACT[act], ea, ed, _dptr(w_gate),
+                                                      _ld(w_gate, ed), _dptr(w_value), _ld(w_value, ed), _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def aggregate_transformer_edges(self, q, k, v, qe, edge_attr, w_edge, root=None, skip=None, act: str = "none", heads: int = 1,
@@ -1483,40 +1473,17 @@ class CompiledModel:
         ``qe`` [N, heads * edge_dim] (the layer passes ``W_e[h]^T q_i[h]``; the entry computes what it is given), ``edge_attr``
         [E, edge_dim <= 16] in COO order, ``w_edge`` [width, edge_dim]; column slices of wider matrices are fine for ``qe`` and
         ``w_edge`` too: their row strides are passed on."""
-        _require_strided(q, "q", self._N, 1)
-        w = int(q.shape[1])
-        for name, t in (("k", k), ("v", v), ("root", root)):
-            if t is None and name == "root":
-                continue
-            _require_strided(t, name, self._N, w)
-            if int(t.shape[1]) != w or t.device != q.device:
-                raise GnnbError(f"{name} must be [{self._N}, {w}] on {q.device}, got {tuple(t.shape)} on {t.device}")
-        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_TRANSFORMER_HEADS:
-            raise GnnbError(f"heads must be an int in 1 .. {MAX_TRANSFORMER_HEADS}, got {heads!r}")
-        if w > MAX_TRANSFORMER_WIDTH or w % heads:
-            raise GnnbError(f"width {w}: a TransformerConv layer is at most {MAX_TRANSFORMER_WIDTH} wide and divisible by heads ({heads})")
-        if act not in ACT:
-            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
-        if scale is None:
-            scale = float(np.float32(1.0) / np.sqrt(np.float32(w // heads)))  # (in fp32, as the layer's own)
-        if not np.isfinite(scale):
-            raise GnnbError(f"scale must be finite, got {scale!r}")
-        if skip is not None:
-            _require_rows(skip, "skip", self._N, w, q)
-        _require_strided(w_edge, "w_edge", w, 1)
-        ed = int(w_edge.shape[1])
-        if not 1 <= ed <= MAX_EDGE_DIM or w_edge.device != q.device:
-            raise GnnbError(f"w_edge must be [{w}, 1 .. {MAX_EDGE_DIM}] on {q.device}, got {tuple(w_edge.shape)} on {w_edge.device}")
+        w, scale = self._transformer_operands(q, k, v, root, skip, act, heads, scale)
+        ed = _require_edge_weight(w_edge, "w_edge", w, q)
         _require_strided(qe, "qe", self._N, heads * ed)
         if int(qe.shape[1]) != heads * ed or qe.device != q.device:
             raise GnnbError(f"qe must be [{self._N}, heads * edge_dim = {heads * ed}] on {q.device}, got {tuple(qe.shape)} on {qe.device}")
         ea = self._require_edge_attr(edge_attr, self._E, q, ed)
         out = _out(out, self._N, w, q)
-        ld = lambda t, cols: int(t.stride(0)) if self._N > 1 else cols  # noqa: E731  (one row: any stride describes it)
-        _check(self.lib.gnnb_aggregate_transformer_edges(self._ws, _dptr(q), ld(q, w), _dptr(k), ld(k, w), _dptr(v), ld(v, w), _dptr(qe),
-                                                         ld(qe, heads * ed), _optr(root), ld(root, w) if root is not None else w, _optr(skip),
-                                                         ACT[act], heads, float(scale), ea, ed, _dptr(w_edge),
-                                                         int(w_edge.stride(0)) if w > 1 else ed, _dptr(out), w, _stream_ptr(stream)))
+        _check(self.lib.gnnb_aggregate_transformer_edges(self._ws, _dptr(q), _ld(q, w), _dptr(k), _ld(k, w), _dptr(v), _ld(v, w), _dptr(qe),
+                                                         _ld(qe, heads * ed), _optr(root), _ld(root, w) if root is not None else w,
+                                                         _optr(skip), ACT[act], heads, float(scale), ea, ed, _dptr(w_edge), _ld(w_edge, ed),
+                                                         _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def aggregate_gatv2_edges(self, xl, xr, att, edge_attr, w_edge, bias=None, skip=None, act: str = "none", heads: int = 1,
@@ -1526,38 +1493,13 @@ class CompiledModel:
         w_edge e_ij)``; the self term's ``e_ii`` is the mean of the row's attribute rows.  ``xl``, ``xr``, ``att``, ``bias``, ``skip``,
         ``heads`` as there; ``edge_attr`` [E, edge_dim <= 16] in COO order, ``w_edge`` [width, edge_dim] (a column slice of a wider
         matrix is fine: its row stride is passed on)."""
-        import torch
-        _require_strided(xl, "xl", self._N, 1)
-        w = int(xl.shape[1])
-        _require_strided(xr, "xr", self._N, w)
-        if int(xr.shape[1]) != w or xr.device != xl.device:
-            raise GnnbError(f"xr must be [{self._N}, {w}] on {xl.device}, got {tuple(xr.shape)} on {xr.device}")
-        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
-            raise GnnbError(f"heads must be an int in 1 .. {MAX_GAT_HEADS}, got {heads!r}")
-        if w > MAX_GAT_WIDTH or w % heads:
-            raise GnnbError(f"width {w}: a GATv2 layer is at most {MAX_GAT_WIDTH} wide and divisible by heads ({heads})")
-        if act not in ACT:
-            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
-        if not isinstance(att, torch.Tensor) or att.numel() != w:
-            raise GnnbError(f"att must hold {w} values ([{w}] or [1, {heads}, {w // heads}])")
-        att = att.reshape(w)
-        _require(att, "att", torch.float32, 1, w)
-        if bias is not None:
-            _require(bias, "bias", torch.float32, 1, w)
-        if att.device != xl.device or (bias is not None and bias.device != xl.device):
-            raise GnnbError(f"att and bias must be on {xl.device}")
-        if skip is not None:
-            _require_rows(skip, "skip", self._N, w, xl)
-        _require_strided(w_edge, "w_edge", w, 1)
-        ed = int(w_edge.shape[1])
-        if not 1 <= ed <= MAX_EDGE_DIM or w_edge.device != xl.device:
-            raise GnnbError(f"w_edge must be [{w}, 1 .. {MAX_EDGE_DIM}] on {xl.device}, got {tuple(w_edge.shape)} on {w_edge.device}")
+        w, att = self._gatv2_operands(xl, xr, att, bias, skip, act, heads)
+        ed = _require_edge_weight(w_edge, "w_edge", w, xl)
         ea = self._require_edge_attr(edge_attr, self._E, xl, ed)
         out = _out(out, self._N, w, xl)
-        _check(self.lib.gnnb_aggregate_gatv2_edges(self._ws, _dptr(xl), int(xl.stride(0)) if self._N > 1 else w, _dptr(xr),
-                                                   int(xr.stride(0)) if self._N > 1 else w, _dptr(att), _optr(bias), _optr(skip), ACT[act],
-                                                   heads, float(negative_slope), ea, ed, _dptr(w_edge), int(w_edge.stride(0)) if w > 1 else ed,
-                                                   _dptr(out), w, _stream_ptr(stream)))
+        _check(self.lib.gnnb_aggregate_gatv2_edges(self._ws, _dptr(xl), _ld(xl, w), _dptr(xr), _ld(xr, w), _dptr(att), _optr(bias), _optr(skip),
+                                                   ACT[act], heads, float(negative_slope), ea, ed, _dptr(w_edge), _ld(w_edge, ed), _dptr(out), w,
+                                                   _stream_ptr(stream)))
         return out
 
     def aggregate_gat_edges(self, xl, s_src, s_dst, edge_attr, a_edge, bias=None, skip=None, act: str = "none", heads: int = 1,
@@ -1567,38 +1509,13 @@ class CompiledModel:
         a_edge[h] . e_ij)``; the self term's edge term is the mean of the row's.  ``xl``, ``s_src``, ``s_dst``, ``bias``, ``skip``,
         ``heads`` as there; ``edge_attr`` [E, edge_dim <= 16] in COO order, ``a_edge`` [heads, edge_dim]: ``att_edge`` folded into
         ``lin_edge`` (a column slice of a wider matrix is fine: its row stride is passed on)."""
-        import torch
-        _require_strided(xl, "xl", self._N, 1)
-        w = int(xl.shape[1])
-        if not isinstance(heads, int) or isinstance(heads, bool) or not 1 <= heads <= MAX_GAT_HEADS:
-            raise GnnbError(f"heads must be an int in 1 .. {MAX_GAT_HEADS}, got {heads!r}")
-        if w > MAX_GAT_WIDTH or w % heads:
-            raise GnnbError(f"width {w}: a GAT layer is at most {MAX_GAT_WIDTH} wide and divisible by heads ({heads})")
-        for t, name in ((s_src, "s_src"), (s_dst, "s_dst")):
-            _require_strided(t, name, self._N, heads)
-            if int(t.shape[1]) != heads or t.device != xl.device:
-                raise GnnbError(f"{name} must be [{self._N}, {heads}] on {xl.device}, got {tuple(t.shape)} on {t.device}")
-        if act not in ACT:
-            raise GnnbError(f"act must be one of {sorted(ACT)}, got {act!r}")
-        if bias is not None:
-            _require(bias, "bias", torch.float32, 1, w)
-            if bias.device != xl.device:
-                raise GnnbError(f"bias must be on {xl.device}")
-        if skip is not None:
-            _require_rows(skip, "skip", self._N, w, xl)
-        _require_strided(a_edge, "a_edge", heads, 1)
-        ed = int(a_edge.shape[1])
-        if not 1 <= ed <= MAX_EDGE_DIM or a_edge.device != xl.device:
-            raise GnnbError(f"a_edge must be [{heads}, 1 .. {MAX_EDGE_DIM}] on {xl.device}, got {tuple(a_edge.shape)} on {a_edge.device}")
+        w = self._gat_operands(xl, s_src, s_dst, bias, skip, act, heads)
+        ed = _require_edge_weight(a_edge, "a_edge", heads, xl)
         ea = self._require_edge_attr(edge_attr, self._E, xl, ed)
         out = _out(out, self._N, w, xl)
-
-        def ld(t, cols):
-            return int(t.stride(0)) if self._N > 1 else cols
-        _check(self.lib.gnnb_aggregate_gat_edges(self._ws, _dptr(xl), ld(xl, w), _dptr(s_src), ld(s_src, heads), _dptr(s_dst),
-                                                 ld(s_dst, heads), _optr(bias), _optr(skip), ACT[act], heads, float(negative_slope), ea, ed,
-                                                 _dptr(a_edge), int(a_edge.stride(0)) if heads > 1 else ed, _dptr(out), w,
-                                                 _stream_ptr(stream)))
+        _check(self.lib.gnnb_aggregate_gat_edges(self._ws, _dptr(xl), _ld(xl, w), _dptr(s_src), _ld(s_src, heads), _dptr(s_dst),
+                                                 _ld(s_dst, heads), _optr(bias), _optr(skip), ACT[act], heads, float(negative_slope), ea, ed,
+                                                 _dptr(a_edge), _ld(a_edge, ed), _dptr(out), w, _stream_ptr(stream)))
         return out
 
     def gine_conv(self, x, edge_attr, w_edge, b_edge, w0, b0, w1, b1, eps: float = 0.0, stream=None):
