@@ -79,7 +79,7 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     // attention; a ResGatedGraphConv model: none forms the gate; a GatedGraphConv model: none forms the GRU cell; an RGCNConv
     // model: none selects a weight by relation
     if (model->edge_dim || model->gat_heads || model->gat1_heads || model->tf_heads || model->gated || model->ggnn_steps || model->rgcn_relations ||
-        model->nn_coefs || model->gen) // (an NNConv model, a GENConv model: no stack kernel forms their aggregates)
+        model->nn_coefs || model->gen || model->schnet) // (an NNConv, a GENConv, a SchNet model: no stack kernel forms their aggregates)
         return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
@@ -416,6 +416,28 @@ static int gen_layer(const LayerCtx &c)
     return c.linear1(c.rows(c.ws->tmp0, 2 * fo), 2 * fo, p.w1, 2 * fo, p.b1, c.rows(c.skip, fo), c.rows(c.nxt, fo), fo, c.model->desc.activation);
 }
 
+// SchNet (gnnb_schnet.h; a GIN description with gaussians and cutoff beside it and edge_dim 1, so the tables keep explicit (v, v)
+// edges): the GEMM x -> x1 [N, fo] in ws->tmp0 on conv.lin1.weight (no bias) in the model's math mode, ONE k_schnet_cfconv launch --
+// the filter MLP on the matrix cores inside the aggregate, on the slot -> row map run_conv_layers built for the batch -- into ws->agg,
+// the GEMM lin2 into ws->tmp0 (x1 has been read by then: one stream), ssp in place (a row kernel of k_schnet.hip; the GEMM epilogue
+// is the follow-up: DESIGN 3.2p), and the GEMM lin with the skip term and the activation in its epilogue.  None of the fused rungs
+static int schnet_layer(const LayerCtx &c)
+{
+    const LayerWeights &p = c.model->conv[c.l];
+    const int fi = c.fi, fo = c.fo;
+    float *x1 = c.ws->tmp0; // ([max_nodes, >= fo]: gnnb_workspace_create)
+    int rc;
+    if ((rc = c.linear1(c.rows(c.cur, fi), fi, p.w_cf1, fi, nullptr, nullptr, c.rows(x1, fo), fo, GNNB_ACT_NONE)))
+        return rc;
+    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+        GNNB_HIP_TRY(launch_schnet_cfconv(c.tv, c.ws->schnet_sc, x1, fo, fo, c.edge_attr, p.w0, c.model->schnet, p.b0, p.w1, fo, p.b1, c.model->schnet,
+                                          c.model->schnet_cutoff, c.ws->agg, fo, c.hs()));
+    if ((rc = c.linear1(c.rows(c.ws->agg, fo), fo, p.w_cf2, fo, p.b_cf2, nullptr, c.rows(c.ws->tmp0, fo), fo, GNNB_ACT_NONE)))
+        return rc;
+    GNNB_HIP_TRY(launch_schnet_ssp(c.rows(c.ws->tmp0, fo), (size_t)std::max(c.M, 0) * fo, c.hs()));
+    return c.linear1(c.rows(c.ws->tmp0, fo), fo, p.w_lin, fo, p.b_lin, c.rows(c.skip, fo), c.rows(c.nxt, fo), fo, c.model->desc.activation);
+}
+
 // GIN's first linear + ReLU on the eps-weighted sum -> ws->tmp0
 static int gin_hidden(const LayerCtx &c)
 {
@@ -581,6 +603,8 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
     c.tv.tile_lo = tile_lo;
     c.cur = x_dev;
     int which = 0;
+    if (model->schnet && d.num_layers > 0) // (a SchNet model: the slot -> row map of the batch, once for all layers)
+        GNNB_HIP_TRY(launch_schnet_slots(ws->t, ws->schnet_sc, c.hs()));
     for (c.l = 0; c.l < d.num_layers; c.l++) {
         const LayerDims ld = layer_dims(d, c.l);
         const LayerIO io = layer_io(d, ws, c.l, c.cur, which);
@@ -598,6 +622,7 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
                  : model->rgcn_relations                                                                                 ? rgcn_layer(c)
                  : model->nn_coefs                                                                                       ? nnconv_layer(c)
                  : model->gen                                                                                            ? gen_layer(c)
+                 : model->schnet                                                                                         ? schnet_layer(c)
                                                                                                                          : gin_layer(c);
             break;
         case GNNB_CONV_SAGE: rc = sage_layer(c); break;
@@ -878,7 +903,8 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
         model->gat_heads != ws->gat_heads || model->gat_slope != ws->gat_slope || model->gat1_heads != ws->gat1_heads ||
         model->tf_heads != ws->tf_heads || model->gated != ws->gated ||
         model->ggnn_steps != ws->ggnn_steps || model->rgcn_relations != ws->rgcn_relations || model->nn_coefs != ws->nn_coefs ||
-        model->nn_hidden != ws->nn_hidden || model->nn_mean != ws->nn_mean || model->gen != ws->gen)
+        model->nn_hidden != ws->nn_hidden || model->nn_mean != ws->nn_mean || model->gen != ws->gen ||
+        model->schnet != ws->schnet || model->schnet_cutoff != ws->schnet_cutoff)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;

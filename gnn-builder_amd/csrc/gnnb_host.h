@@ -24,6 +24,7 @@
 #include "gnnb_rgcn.h"
 #include "gnnb_nnconv.h"
 #include "gnnb_gen.h"
+#include "gnnb_schnet.h"
 
 namespace gnnb {
 
@@ -81,6 +82,10 @@ struct gnnb_model {
                             // has GIN's w0 [2 out, out], b0, w1 [out, 2 out], b1 as its MLP, w_sr, b_sr where in != out, and edge_w [out,
                             // edge_dim], edge_b with edge_dim > 0
     std::vector<float> gen_t; // ... and its softmax temperature per layer, read at upload and passed by value at every launch
+    int schnet = 0;         // > 0: a SchNet model (gnnb_schnet_model_create; desc is a GIN description, edge_dim 1 beside it) of that many
+                            // gaussians -- every layer has w_cf1, GIN's w0 [out, gaussians], b0, w1 [out, out], b1 as its filter MLP,
+                            // w_cf2, b_cf2 and w_lin, b_lin
+    float schnet_cutoff = 0.0f; // ... and its cutoff
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };
@@ -109,6 +114,10 @@ struct gnnb_workspace {
     int rgcn_relations = 0;      // ... and its relations when it is an RGCNConv model (0: it is not)
     int nn_coefs = 0, nn_hidden = 0, nn_mean = 0; // ... and its coefficient count, hidden width and aggr when it is an NNConv model
     int gen = 0;                 // ... and 1 when it is a GENConv model
+    int schnet = 0;              // ... and its gaussians and cutoff when it is a SchNet model (0: it is not)
+    float schnet_cutoff = 0.0f;
+    char *schnet_blob = nullptr; // k_schnet_cfconv's scratch (SchnetScratch: the slot -> row map, the tiles' partial rows), one allocation:
+    gnnb::SchnetScratch schnet_sc{}; // made by gnnb_workspace_create for a SchNet model, by the first gnnb_aggregate_cfconv on any other
     gnnb::RgcnSlot *rgcn_rec = nullptr; // such a model's workspace only: the slot records of the batch (k_rgcn_slots), 8 max_edges bytes,
                                  // rebuilt by every _types forward
     char *type_blob = nullptr;   // gnnb_workspace_enable_type_ingest: edge_type in COO row order, int32 [max_edges], one allocation

@@ -410,6 +410,26 @@ constexpr float GEN_EPS_M = 1e-7f; // what a GENConv layer adds to every message
 hipError_t launch_gen_aggregate(const BatchTables &t, const float *s, int lds, const float *r, int ldr, int width, const float *edge_attr,
                                 int edge_dim, const float *we, int ldwe, const float *be, float temp, float eps_m, float *out, int ldo,
                                 hipStream_t st);
+// SchNet's continuous-filter convolution (k_schnet.hip; gnnb_schnet.h): out[i] = sum_j x1[j] * ((w2 ssp(w1 rbf(d_ij) + b1) + b2) C(d_ij)),
+// the filter MLP on the matrix cores inside the aggregate, tiles of SCHNET_TE_MIN or 64 CSR slots.  SchnetScratch: the slot -> row
+// map of the prepared batch (launch_schnet_slots, once per batch, in front of the first launch_schnet_cfconv) and the tiles' partial
+// rows, part[tile][leading | trailing][part_w]; schnet_scratch_bytes / _at size and carve it for an edge capacity and a widest
+// layer.  x1, out rows of stride ldx, ldo >= width; edge_dist [E] in COO row order; w1 [width, gaussians], w2 [width, width] rows of
+// stride ldw1, ldw2.  Tables that keep explicit (v, v) edges.  launch_schnet_ssp: y = ssp(y) in place.  hipErrorInvalidValue:
+// nothing launched
+constexpr int SCHNET_MAX_WIDTH = 256, SCHNET_MAX_GAUSSIANS = 64, SCHNET_TE_MIN = 32;
+struct SchnetScratch {
+    int32_t *slot_row; // [max_edges] destination row of every CSR slot, -1 for a slot no row owns
+    float *part;       // [ceil(max_edges / SCHNET_TE_MIN)][2][part_w]
+    int part_w, max_edges;
+};
+size_t schnet_scratch_bytes(int max_edges, int width);
+SchnetScratch schnet_scratch_at(char *base, int max_edges, int width);
+hipError_t launch_schnet_slots(const BatchTables &t, const SchnetScratch &sc, hipStream_t s);
+hipError_t launch_schnet_cfconv(const BatchTables &t, const SchnetScratch &sc, const float *x1, int ldx, int width, const float *edge_dist,
+                                const float *w1, int ldw1, const float *b1, const float *w2, int ldw2, const float *b2, int gaussians,
+                                float cutoff, float *out, int ldo, hipStream_t s);
+hipError_t launch_schnet_ssp(float *y, size_t n, hipStream_t s);
 // the ingest's edge types in COO row order (k_ingest.hip): out[i] = (int32) edge_type[state[INGEST_STATE_UNSORTED] ? idx[i] : i], -1
 // for a value that does not fit (k_rgcn_slots flags it); idx, state: as launch_edge_attr_order's
 hipError_t launch_edge_type_order(const long long *edge_type, const int32_t *idx, const int32_t *state, int32_t *out, int num_edges, hipStream_t s);

@@ -285,6 +285,27 @@ int count_gen_params(const gnnb_model_desc *desc, int edge_dim)
     return n;
 }
 
+// parameter tensors of a SchNet model (gnnb_schnet.h): a GIN description (its tables keep explicit (v, v) edges) without the fixed-point
+// emulation, gaussians 1 .. 64, every layer width at most 256; nine per layer
+int count_schnet_params(const gnnb_model_desc *desc, int gaussians)
+{
+    int rc = validate_desc(desc);
+    if (rc != GNNB_OK)
+        return rc;
+    if (gaussians < 1 || gaussians > SCHNET_MAX_GAUSSIANS)
+        return fail(GNNB_ERR_INVALID, "gaussians %d: a SchNet model takes 1 .. %d gaussians", gaussians, SCHNET_MAX_GAUSSIANS);
+    if (desc->conv_type != GNNB_CONV_GIN)
+        return fail(GNNB_ERR_INVALID, "a SchNet model's description is a GIN description (conv_type %d given)", desc->conv_type);
+    if (desc->fpx_w != 0)
+        return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover SchNet models (fpx_w must be 0)");
+    for (int l = 0; l < desc->num_layers; l++) {
+        const LayerDims ld = layer_dims(*desc, l);
+        if (ld.fin > SCHNET_MAX_WIDTH || ld.fout > SCHNET_MAX_WIDTH)
+            return fail(GNNB_ERR_INVALID, "layer %d's widths %d -> %d: a SchNet layer is at most %d wide", l, ld.fin, ld.fout, SCHNET_MAX_WIDTH);
+    }
+    return SCHNET_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+}
+
 // What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
 // type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
 // (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features), or heads of a
@@ -306,7 +327,15 @@ struct ModelKind {
     int nn_coefs = 0, nn_hidden = 0, nn_mean = 0; // an NNConv model (gnnb_nnconv_model_create: a GIN description, edge_dim too)
     const float *gen_t = nullptr; // non-null: a GENConv model (gnnb_gen_model_create: a GIN description, edge_dim 0 .. 16 too) and its
                                   // temperatures, one per layer
+    int schnet = 0;               // > 0: a SchNet model (gnnb_schnet_model_create: a GIN description, edge_dim 1 too) of that many gaussians
+    float schnet_cutoff = 0.0f;   // ... and its cutoff
     static ModelKind plain() { return {}; }
+    static ModelKind schnet_of(int gaussians, float cutoff)
+    {
+        ModelKind k = edges(1, GNNB_CONV_GIN);
+        k.schnet = gaussians, k.schnet_cutoff = cutoff;
+        return k;
+    }
     static ModelKind edges(int edge_dim, int base)
     {
         ModelKind k;
@@ -397,7 +426,8 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
     const int gat1_heads = kind.gat1_heads;
-    int expect = kind.gen_t != nullptr ? count_gen_params(desc, edge_dim)
+    int expect = kind.schnet != 0 ? count_schnet_params(desc, kind.schnet)
+                 : kind.gen_t != nullptr ? count_gen_params(desc, edge_dim)
                  : kind.nn_coefs != 0 ? count_nnconv_params(desc, edge_dim, kind.nn_hidden)
                  : kind.rgcn_relations != 0 ? count_rgcn_params(desc, kind.rgcn_relations)
                  : kind.ggnn_steps != 0 ? count_ggnn_params(desc, kind.ggnn_steps)
@@ -420,7 +450,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
 
     const gnnb_model_desc &d = *desc;
     const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated, gat1_heads, kind.ggnn_steps, kind.rgcn_relations,
-                                                  kind.nn_coefs, kind.nn_hidden, kind.gen_t != nullptr);
+                                                  kind.nn_coefs, kind.nn_hidden, kind.gen_t != nullptr, kind.schnet);
     const std::vector<float> &img = built.img;
     const WeightLayout &lo = built.layout;
 
@@ -437,6 +467,8 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     m->nn_coefs = kind.nn_coefs;
     m->nn_hidden = kind.nn_hidden;
     m->nn_mean = kind.nn_mean;
+    m->schnet = kind.schnet;
+    m->schnet_cutoff = kind.schnet_cutoff;
     if (kind.gen_t) {
         m->gen = 1;
         m->gen_t.assign(kind.gen_t, kind.gen_t + d.num_layers);
@@ -713,6 +745,22 @@ int gnnb_gen_model_create(const gnnb_model_desc *desc, int edge_dim, const float
 }
 
 int gnnb_model_gen(const gnnb_model *model) { return model ? model->gen : 0; }
+
+int gnnb_schnet_model_num_params(const gnnb_model_desc *desc, int gaussians) { return count_schnet_params(desc, gaussians); }
+
+int gnnb_schnet_model_create(const gnnb_model_desc *desc, int gaussians, float cutoff, const float *const *host_params, int num_params,
+                             gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (const int rc = count_schnet_params(desc, gaussians); rc < 0)
+        return rc;
+    if (!(cutoff > 0.0f) || !std::isfinite(cutoff))
+        return fail(GNNB_ERR_INVALID, "cutoff %g: a SchNet model's cutoff is positive and finite", (double)cutoff);
+    return model_create(desc, ModelKind::schnet_of(gaussians, cutoff), host_params, num_params, out_model);
+}
+
+int gnnb_model_schnet(const gnnb_model *model) { return model ? model->schnet : 0; }
 
 void gnnb_model_destroy(gnnb_model *model)
 {

@@ -224,6 +224,9 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
             tmpw = std::max(tmpw, 2 * layer_dims(d, l).fout);
             aggw = std::max(aggw, layer_dims(d, l).fout);
         }
+    if (model->schnet) // a SchNet layer's x1 and lin2's output [N, out] go to tmp0 (maxw covers them), its aggregate [N, out] to agg
+        for (int l = 0; l < d.num_layers; l++)
+            aggw = std::max(aggw, layer_dims(d, l).fout);
     // the widest GEMM K of the conv layers: from 1024 on k_linear_dma may cut its tiles along K (stream-K) and needs a scratch,
     // which belongs to the workspace -- forwards of different workspaces never share one, whatever streams or graphs run them
     int max_k = 0;
@@ -260,6 +263,8 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     ws->nn_hidden = model->nn_hidden;
     ws->nn_mean = model->nn_mean;
     ws->gen = model->gen;
+    ws->schnet = model->schnet;
+    ws->schnet_cutoff = model->schnet_cutoff;
     ws->max_graphs = max_graphs;
     ws->max_nodes = max_nodes;
     ws->max_edges = max_edges;
@@ -318,6 +323,17 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
                     hipGetErrorString(e));
     }
     (void)place(Arena{ws->blob});
+    if (model->schnet) { // k_schnet_cfconv's scratch, an allocation of its own: the forward must not allocate
+        int w = 1;
+        for (int l = 0; l < d.num_layers; l++)
+            w = std::max(w, layer_dims(d, l).fout);
+        e = hipMalloc((void **)&ws->schnet_blob, schnet_scratch_bytes(max_edges, w));
+        if (e != hipSuccess) {
+            gnnb_workspace_destroy(ws);
+            return fail(GNNB_ERR_HIP, "workspace allocation of %zu bytes failed: %s", schnet_scratch_bytes(max_edges, w), hipGetErrorString(e));
+        }
+        ws->schnet_sc = schnet_scratch_at(ws->schnet_blob, max_edges, w);
+    }
     ws->t.agg_cut_n = 0;
     ws->t.stage_cut_n = 0;
     ws->t.stage_cut_cap = 1024;
@@ -358,6 +374,8 @@ void gnnb_workspace_destroy(gnnb_workspace *ws)
         (void)hipFree(ws->edge_blob);
     if (ws->type_blob)
         (void)hipFree(ws->type_blob);
+    if (ws->schnet_blob)
+        (void)hipFree(ws->schnet_blob);
     if (ws->order_triple)
         (void)hipHostFree(ws->order_triple);
     if (ws->stage)
@@ -1000,6 +1018,44 @@ int gnnb_aggregate_gen(gnnb_workspace *ws, const float *s_dev, int lds, const fl
                                       "when it is not 0, lds, ldr and ldo >= width)", GEN_MAX_WIDTH, EDGE_MAX_DIM);
     GNNB_HIP_TRY(launch_gen_aggregate(ws->t, s_dev, lds, r_dev, ldr, width, edge_attr_dev, edge_dim, we_dev, ldwe, be_dev, t, eps_m, out_dev, ldo,
                                       (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+// k_schnet_cfconv's scratch for the workspace's edge capacity and layers of `width`: one allocation (gnnb_workspace_create for a SchNet
+// model; the first gnnb_aggregate_cfconv on any other workspace, and again should a later call be wider)
+static int ensure_schnet_scratch(gnnb_workspace *ws, int width)
+{
+    if (ws->schnet_blob && ws->schnet_sc.part_w >= width)
+        return GNNB_OK;
+    if (ws->schnet_blob) {
+        GNNB_HIP_TRY(hipDeviceSynchronize()); // (a launch in flight may still read the narrower one)
+        (void)hipFree(ws->schnet_blob);
+        ws->schnet_blob = nullptr;
+        ws->schnet_sc = SchnetScratch{};
+    }
+    GNNB_HIP_TRY(hipMalloc((void **)&ws->schnet_blob, schnet_scratch_bytes(ws->max_edges, width)));
+    ws->schnet_sc = schnet_scratch_at(ws->schnet_blob, ws->max_edges, width);
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_cfconv(gnnb_workspace *ws, const float *x1_dev, int ldx, int width, const float *edge_dist_dev, const float *w1_dev, int ldw1,
+                          const float *b1_dev, const float *w2_dev, int ldw2, const float *b2_dev, int gaussians, float cutoff, float *out_dev,
+                          int ldo, void *stream)
+{
+    GNNB_TRY(stage_entry(ws, "gnnb_aggregate_cfconv", TABLES_KEEP_LOOPS));
+    // (a prepared batch without nodes launches nothing and reads no operand; one without edges reads no distance)
+    const bool operands = ws->t.num_nodes <= 0 || (x1_dev && out_dev && w1_dev && b1_dev && w2_dev && b2_dev && (edge_dist_dev || ws->t.num_edges <= 0));
+    if (!operands || width < 1 || width > SCHNET_MAX_WIDTH || gaussians < 1 || gaussians > SCHNET_MAX_GAUSSIANS || !(cutoff > 0.0f) ||
+        !std::isfinite(cutoff) || ldx < width || ldo < width || ldw1 < gaussians || ldw2 < width)
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_cfconv (x1, out and the four weight operands not NULL unless the batch has no "
+                                      "nodes, edge_dist not NULL unless it has no edges, width 1 .. %d, gaussians 1 .. %d, cutoff positive and "
+                                      "finite, ldx, ldo and ldw2 >= width, ldw1 >= gaussians)", SCHNET_MAX_WIDTH, SCHNET_MAX_GAUSSIANS);
+    if (ws->t.num_nodes <= 0)
+        return GNNB_OK;
+    GNNB_TRY(ensure_schnet_scratch(ws, width));
+    GNNB_HIP_TRY(launch_schnet_slots(ws->t, ws->schnet_sc, (hipStream_t)stream));
+    GNNB_HIP_TRY(launch_schnet_cfconv(ws->t, ws->schnet_sc, x1_dev, ldx, width, edge_dist_dev, w1_dev, ldw1, b1_dev, w2_dev, ldw2, b2_dev, gaussians,
+                                      cutoff, out_dev, ldo, (hipStream_t)stream));
     return GNNB_OK;
 }
 

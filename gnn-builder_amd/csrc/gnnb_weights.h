@@ -162,6 +162,11 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //              w_sr [2 out, in], b_sr [2 out]       derived, layers with in != out only: [lin_src.weight ; lin_dst.weight] and the
 //                                                   stacked bias (stack_rows) -- ONE GEMM gives [s | r] [N, 2 out]
 //              edge_w [out, edge_dim], edge_b [out] conv.lin_edge, raw (edge_dim > 0 only; the OUTPUT width, unlike GINE's)
+//   SchNet    (gnnb_model::schnet, gnnb_schnet_model_create: a GIN description, edge_dim 1, gaussians and cutoff beside it) GIN's four
+//             slots as the layer's filter MLP, all raw
+//              w_cf1 [out, in]                      conv.lin1.weight (no bias): x -> x1
+//              w0 [out, gaussians], b0 [out]        mlp.0;   w1 [out, out], b1 [out]: mlp.2 -- k_schnet_cfconv's operands
+//              w_cf2 [out, out], b_cf2 [out]        conv.lin2;   w_lin [out, out], b_lin [out]: lin
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
@@ -175,6 +180,7 @@ template <typename T> struct LayerSlots {
     T w_rgcn = absent_slot<T>(), b_rgcn = absent_slot<T>();
     T w_nn = absent_slot<T>(), b_nn = absent_slot<T>(), w_nn1 = absent_slot<T>(), b_nn1 = absent_slot<T>();
     T w_sr = absent_slot<T>(), b_sr = absent_slot<T>();
+    T w_cf1 = absent_slot<T>(), w_cf2 = absent_slot<T>(), b_cf2 = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -183,7 +189,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_rgcn), f(b_rgcn), f(w_nn), f(b_nn), f(w_nn1), f(b_nn1), f(w_sr), f(b_sr), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_rgcn), f(b_rgcn), f(w_nn), f(b_nn), f(w_nn1), f(b_nn1), f(w_sr), f(b_sr), f(w_cf1), f(w_cf2), f(b_cf2), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -587,16 +593,31 @@ inline int nnconv_param_slots(int hidden) { return hidden > 0 ? 6 : 4; }
 // a GENConv layer's canonical tensors (gnnb_gen.h): the MLP's four, lin_src / lin_dst's four in front where in != out, lin_edge's two
 // between them with edge features
 inline int gen_param_slots(int fin, int fout, int edge_dim) { return (fin != fout ? 4 : 0) + (edge_dim > 0 ? 2 : 0) + 4; }
+constexpr int SCHNET_PARAM_SLOTS = 9; // a SchNet layer's canonical tensors (gnnb_schnet.h)
 constexpr int GAT1_PARAM_SLOTS = 4; // a GAT v1 layer's canonical tensors (gnnb_gatconv.h); two more with edge features (gnnb_gatconv_edge.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
 // their offsets in the image
 inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0,
-                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0, int nn_hidden = 0, bool gen = false)
+                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0, int nn_hidden = 0, bool gen = false, int schnet = 0)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (schnet > 0) { // (a GIN description whose layers are SchNet's; canonical order: conv.lin1.weight, mlp.0.weight, mlp.0.bias,
+                      // mlp.2.weight, mlp.2.bias, conv.lin2.weight, conv.lin2.bias, lin.weight, lin.bias; schnet = gaussians)
+        LayerOffsets g;
+        g.w_cf1 = im.push(p[0], fo * fi);
+        g.w0 = im.push(p[1], fo * (size_t)schnet);
+        g.b0 = im.push(p[2], fo);
+        g.w1 = im.push(p[3], fo * fo);
+        g.b1 = im.push(p[4], fo);
+        g.w_cf2 = im.push(p[5], fo * fo);
+        g.b_cf2 = im.push(p[6], fo);
+        g.w_lin = im.push(p[7], fo * fo);
+        g.b_lin = im.push(p[8], fo);
+        return g;
+    }
     if (gen) { // (a GIN description whose layers are GENConv's; canonical order: [lin_src.weight, lin_src.bias, lin_dst.weight,
                // lin_dst.bias,] [lin_edge.weight, lin_edge.bias,] mlp.0.weight, mlp.0.bias, mlp.2.weight, mlp.2.bias: gen_param_slots)
         LayerOffsets g;
@@ -777,14 +798,16 @@ struct BuiltWeights {
 // rgcn_relations > 0: an RGCNConv model (a GIN description, three tensors per layer; no execution-order copy).
 // nn_coefs > 0: an NNConv model (a GIN description with edge_dim; four tensors per layer, six with nn_hidden > 0; no execution-order copy).
 // gen: a GENConv model (a GIN description, edge_dim 0 .. 16; four to ten tensors per layer; no execution-order copy).
+// schnet > 0: a SchNet model of that many gaussians (a GIN description, edge_dim 1; nine tensors per layer; no execution-order copy).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
                                        int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0,
-                                       int nn_hidden = 0, bool gen = false)
+                                       int nn_hidden = 0, bool gen = false, int schnet = 0)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = nn_coefs > 0     ? nnconv_param_slots(nn_hidden)
+    const int slots = schnet > 0       ? SCHNET_PARAM_SLOTS
+                      : nn_coefs > 0   ? nnconv_param_slots(nn_hidden)
                       : rgcn_relations > 0 ? RGCN_PARAM_SLOTS
                       : ggnn_steps > 0 ? GGNN_PARAM_SLOTS
                       : gat1_heads > 0 ? GAT1_PARAM_SLOTS + (edge_dim ? 2 : 0)
@@ -795,7 +818,7 @@ inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, c
     int pi = 0;
     // (a GENConv layer's count depends on its widths: gen_param_slots)
     for (int l = 0; l < d.num_layers; pi += gen ? gen_param_slots(layer_dims(d, l).fin, layer_dims(d, l).fout, edge_dim) : slots, l++)
-        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps, rgcn_relations, nn_coefs, nn_hidden, gen);
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps, rgcn_relations, nn_coefs, nn_hidden, gen, schnet);
     const bool have_w1f = gat_heads == 0 && gat1_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));

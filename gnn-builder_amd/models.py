@@ -1152,6 +1152,82 @@ class GENEConv_GNNB(nn.Module):
         return self.conv(x, edge_index, edge_attr)
 
 
+# --------------------------------------------------------------------------------------- SchNet
+MAX_SCHNET_GAUSSIANS = 64  # of a SchNet model (include/gnnb_schnet.h): gaussians and cutoff travel beside a GIN description
+
+
+class _ShiftedSoftplus(nn.Module):
+    """``ssp(v) = softplus(v) - ln 2`` (PyG's ``ShiftedSoftplus``)."""
+
+    def forward(self, v: Tensor) -> Tensor:
+        return nn.functional.softplus(v) - math.log(2.0)
+
+
+class _CFConv(nn.Module):
+    """PyG's ``CFConv``: ``lin2(sum_j lin1(x)_j * (nn(rbf_ij) C(d_ij)))`` with ``C(d) = 0.5 (cos(pi d / cutoff) + 1)`` (no clamp beyond
+    the cutoff, as PyG); ``nn`` is the interaction block's filter MLP (the same module: its parameters appear under both names in the
+    ``state_dict``, as in PyG)."""
+
+    def __init__(self, in_channels: int, out_channels: int, num_filters: int, filter_nn: nn.Module, cutoff: float):
+        super().__init__()
+        self.lin1 = nn.Linear(in_channels, num_filters, bias=False)
+        self.lin2 = nn.Linear(num_filters, out_channels)
+        self.nn, self.cutoff = filter_nn, cutoff
+
+    def forward(self, x: Tensor, edge_index: Tensor, dist: Tensor, rbf: Tensor) -> Tensor:
+        src, dst = edge_index[0].long(), edge_index[1].long()
+        w = self.nn(rbf) * (0.5 * (torch.cos(dist * math.pi / self.cutoff) + 1.0)).unsqueeze(-1)
+        x1 = self.lin1(x)
+        return self.lin2(torch.zeros_like(x1).index_add(0, dst, x1[src] * w))
+
+
+class _SchNetConv(nn.Module):
+    """SchNet's interaction block (Schuett et al.), PyG's ``torch_geometric.nn.models.schnet.InteractionBlock`` with
+    ``num_filters = out`` and the Gaussian smearing of the distances inside, parameter names as PyG's::
+
+        x1    = conv.lin1(x)                              no bias
+        rbf_k = exp(coeff (d_ij - mu_k)^2),  mu = linspace(0, cutoff, G),  coeff = -0.5 / (mu_1 - mu_0)^2
+        w_ij  = mlp.2(ssp(mlp.0(rbf))) * 0.5 (cos(pi d_ij / cutoff) + 1)
+        out_i = lin(ssp(conv.lin2(sum_{j -> i} x1_j * w_ij)))
+
+    ``d_ij = edge_attr[e, 0]``.  ``G = 1``: the one centre is 0 and ``coeff = -0.5 / cutoff^2`` (PyG divides by zero there).  No self
+    loop is added or removed, duplicate edges count as often as they occur, a node without in-edges aggregates 0."""
+
+    def __init__(self, in_channels: int, out_channels: int, gaussians: int = 50, cutoff: float = 10.0):
+        super().__init__()
+        self.in_channels, self.out_channels, self.gaussians, self.cutoff = in_channels, out_channels, gaussians, float(cutoff)
+        self.mlp = nn.Sequential(nn.Linear(gaussians, out_channels), _ShiftedSoftplus(), nn.Linear(out_channels, out_channels))
+        self.conv = _CFConv(in_channels, out_channels, out_channels, self.mlp, self.cutoff)
+        self.act = _ShiftedSoftplus()
+        self.lin = nn.Linear(out_channels, out_channels)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        dist = edge_attr.to(x.dtype).reshape(-1)
+        mu = torch.linspace(0.0, self.cutoff, self.gaussians, dtype=x.dtype, device=x.device)
+        coeff = -0.5 / float(mu[1] - mu[0]) ** 2 if self.gaussians > 1 else -0.5 / self.cutoff ** 2
+        rbf = torch.exp(coeff * (dist.unsqueeze(-1) - mu) ** 2)
+        return self.lin(self.act(self.conv(x, edge_index, dist, rbf)))
+
+
+class SchNetConv_GNNB(nn.Module):
+    """SchNet's continuous-filter convolution (no class of the reference): ``_SchNetConv``.  ``GNNModel(..., gnn_conv=SchNetConv_GNNB,
+    graph_input_edge_dim=1, gnn_gaussians=G, gnn_cutoff=c)`` stacks it (``G`` in 1 .. 64, ``c > 0``); ``forward(x, edge_index, edge_attr)``
+    with the distances ``edge_attr [E, 1]``, the same for every layer.  The accelerated path is ``runtime.CompiledModel.from_model`` with
+    ``forward_edges`` / ``forward_prepared_edges`` / ``forward_pyg_edges`` (C ABI ``include/gnnb_schnet.h``: the filter MLP runs on the
+    matrix cores inside the aggregate, csrc/k_schnet.hip).  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int = 1, gaussians: int = 50, cutoff: float = 10.0, p_in: int = 1,
+                 p_out: int = 1):
+        super().__init__()
+        if edge_dim != 1:
+            raise ValueError(f"a SchNet model's edge_attr is the distance alone: edge_dim must be 1 (got {edge_dim!r})")
+        self.in_channels, self.out_channels, self.edge_dim, self.p_in, self.p_out = in_channels, out_channels, 1, p_in, p_out
+        self.conv = _SchNetConv(in_channels, out_channels, gaussians, cutoff)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor) -> Tensor:
+        return self.conv(x, edge_index, edge_attr)
+
+
 # --------------------------------------------------------------------------------------- pooling / MLP
 SUPPORTED_GLOBAL_POOLING_AGGRS = {"add": "SumAggregation", "max": "MaxAggregation", "mean": "MeanAggregation"}
 SUPPORTED_GLOBAL_POOLING_MODE = ["cat"]
@@ -1265,15 +1341,16 @@ class MLP(nn.Module):
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
                        GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB,
                        ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB, GatedGraphConv_GNNB, RGCNConv_GNNB, NNConv_GNNB,
-                       GENConv_GNNB, GENEConv_GNNB]
+                       GENConv_GNNB, GENEConv_GNNB, SchNetConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
               PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
               TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated", ResGatedGraphEConv_GNNB: "resgatede",
               GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate", GatedGraphConv_GNNB: "ggnn", RGCNConv_GNNB: "rgcn", NNConv_GNNB: "nnconv",
-              GENConv_GNNB: "gen", GENEConv_GNNB: "gene"}
+              GENConv_GNNB: "gen", GENEConv_GNNB: "gene", SchNetConv_GNNB: "schnet"}
 # convs that take edge_attr, and what the messages call them
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE",
-               ResGatedGraphEConv_GNNB: "ResGatedE", GATv1EConv_GNNB: "GATE", NNConv_GNNB: "NNConv", GENEConv_GNNB: "GENE"}
+               ResGatedGraphEConv_GNNB: "ResGatedE", GATv1EConv_GNNB: "GATE", NNConv_GNNB: "NNConv", GENEConv_GNNB: "GENE",
+               SchNetConv_GNNB: "SchNet"}
 MAX_EDGE_DIM = 16  # of a GINE, PNAE, GATv2E, TransformerE, ResGatedE or GATE model (include/gnnb_edge.h, gnnb_pna_edge.h, gnnb_gat_edge.h, gnnb_transformer_edge.h, gnnb_resgated_edge.h, gnnb_gatconv_edge.h)
 _GAT_CONVS = (GATv2Conv_GNNB, GATv2EConv_GNNB)  # the GATv2 convs (heads and negative_slope travel beside a GCN description)
 _TF_CONVS = (TransformerConv_GNNB, TransformerEConv_GNNB)  # the TransformerConv convs (heads travel beside a GIN description)
@@ -1295,7 +1372,8 @@ class GNNModel(nn.Module):
                  global_pooling: GlobalPooling, mlp_head: MLP,
                  output_activation: TorchModuleArgOptional, gnn_p_in: int = 1, gnn_p_hidden: int = 1,
                  gnn_p_out: int = 1, gnn_heads: int = 1, gnn_steps: int = 1, gnn_relations: int = 1,
-                 gnn_edge_hidden: int = 0, gnn_aggr: str = "add", gnn_softmax_t: float = 1.0) -> None:
+                 gnn_edge_hidden: int = 0, gnn_aggr: str = "add", gnn_softmax_t: float = 1.0,
+                 gnn_gaussians: int = 50, gnn_cutoff: float = 10.0) -> None:
         super().__init__()
         self.graph_input_feature_dim = graph_input_feature_dim
         self.graph_input_edge_dim = graph_input_edge_dim
@@ -1372,6 +1450,19 @@ class GNNModel(nn.Module):
         elif gnn_softmax_t != 1.0:
             raise ValueError(f"gnn_softmax_t={gnn_softmax_t!r}: only a GENConv model (gnn_conv=GENConv_GNNB or GENEConv_GNNB) has a softmax "
                              "temperature")
+
+        self.gnn_gaussians, self.gnn_cutoff = gnn_gaussians, gnn_cutoff
+        if self.gnn_conv is SchNetConv_GNNB:
+            if self.graph_input_edge_dim != 1:
+                raise ValueError(f"a SchNet model's edge_attr is the distance alone: graph_input_edge_dim must be 1 (got {graph_input_edge_dim!r})")
+            if not isinstance(gnn_gaussians, int) or isinstance(gnn_gaussians, bool) or not 1 <= gnn_gaussians <= MAX_SCHNET_GAUSSIANS:
+                raise ValueError(f"a SchNet model needs gnn_gaussians, an int in 1 .. {MAX_SCHNET_GAUSSIANS} (got {gnn_gaussians!r})")
+            if isinstance(gnn_cutoff, bool) or not isinstance(gnn_cutoff, (int, float)) or not math.isfinite(gnn_cutoff) or gnn_cutoff <= 0:
+                raise ValueError(f"a SchNet model needs gnn_cutoff, a positive finite number (got {gnn_cutoff!r})")
+            conv_kwargs = {**conv_kwargs, "gaussians": gnn_gaussians, "cutoff": float(gnn_cutoff)}
+        elif gnn_gaussians != 50 or gnn_cutoff != 10.0:
+            raise ValueError(f"gnn_gaussians={gnn_gaussians!r}, gnn_cutoff={gnn_cutoff!r}: only a SchNet model (gnn_conv=SchNetConv_GNNB) has "
+                             "gaussians and a cutoff")
 
         self.global_pooling = global_pooling
         self.mlp_head = mlp_head  # registered before gnn_convs: parameter order mlp_head_*, gnn_convs_*
@@ -1508,6 +1599,8 @@ class GNNModel(nn.Module):
             gat = {"edge_hidden": int(self.gnn_edge_hidden), "aggr": str(self.gnn_aggr)}
         elif self.gnn_conv in _GEN_CONVS:  # (a GIN description on the C side, edge_dim and the temperatures beside it: include/gnnb_gen.h)
             gat = {"softmax_t": [float(c.conv.t.detach()) for c in self.gnn_convs]}  # (read from the parameters: what an upload takes)
+        elif self.gnn_conv is SchNetConv_GNNB:  # (a GIN description on the C side, edge_dim 1, gaussians and cutoff beside it: include/gnnb_schnet.h)
+            gat = {"gaussians": int(self.gnn_gaussians), "cutoff": float(self.gnn_cutoff)}
         return {
             "conv": _CONV_NAME[self.gnn_conv],
             "num_layers": self.gnn_num_layers,
@@ -1561,6 +1654,9 @@ class GNNModel(nn.Module):
         # (the edge network, then the root weight and the bias: include/gnnb_nnconv.h)
         per_conv["nnconv"] = ["conv_nn_0_weight", "conv_nn_0_bias"] + (["conv_nn_2_weight", "conv_nn_2_bias"] if self.gnn_edge_hidden else []) + [
             "conv_lin_weight", "conv_bias"]
+        # (the order of the formula: include/gnnb_schnet.h; conv.conv.nn.* are conv.mlp.*'s second names)
+        per_conv["schnet"] = ["conv_conv_lin1_weight", "conv_mlp_0_weight", "conv_mlp_0_bias", "conv_mlp_2_weight", "conv_mlp_2_bias",
+                              "conv_conv_lin2_weight", "conv_conv_lin2_bias", "conv_lin_weight", "conv_lin_bias"]
         if self.gnn_conv in _GEN_CONVS:  # (a layer's list depends on its widths: include/gnnb_gen.h; conv.t travels in spec()["softmax_t"])
             names = []
             for l, c in enumerate(self.gnn_convs):

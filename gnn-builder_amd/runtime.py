@@ -30,10 +30,10 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin", "rgcn": "gin", "nnconv": "gin", "gen": "gin", "gene": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin", "rgcn": "gin", "nnconv": "gin", "gen": "gin", "gene": "gin", "schnet": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
 # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h,
 # "resgatede": gnnb_resgated_edge.h, "gate": gnnb_gatconv_edge.h)
-_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede", "gate", "nnconv", "gene")
+_EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede", "gate", "nnconv", "gene", "schnet")
 _GAT_CONVS = ("gatv2", "gatv2e")       # ... and of those with heads and negative_slope beside it
 # a GAT v1 model (include/gnnb_gatconv.h, spec["conv"] == "gat"): a GCN description, heads and negative_slope beside it, within GATv2's
 # limits -- a model kind of its own; with edge features ("gate", include/gnnb_gatconv_edge.h) edge_dim too
@@ -57,6 +57,9 @@ NN_AGGR = {"add": 0, "mean": 1}  # gnnb_nn_aggr
 # edge_dim (0 for "gen") and the per-layer softmax temperatures spec["softmax_t"] beside it
 _GEN_CONVS = ("gen", "gene")
 MAX_GEN_WIDTH = 256
+# a SchNet model (include/gnnb_schnet.h, spec["conv"] == "schnet"): its description is GIN's too; edge_dim is 1 (the distance), the
+# gaussians spec["gaussians"] and the cutoff spec["cutoff"] travel beside it
+MAX_SCHNET_GAUSSIANS, MAX_SCHNET_WIDTH = 64, 256
 ACT = {"relu": 0, "gelu": 1, "sigmoid": 2, "tanh": 3, "none": 4}                 # gnnb_act
 POOL = {"add": 0, "mean": 1, "max": 2}                                           # gnnb_pool
 OUT_ACT = {None: 0, "none": 0, "softmax": 1, "log_softmax": 2}                   # gnnb_out_act
@@ -307,6 +310,15 @@ ABI_GEN = {
 }
 
 
+# ... and of include/gnnb_schnet.h (SchNet models, the filter MLP inside the aggregate), in its order
+ABI_SCHNET = {
+    "gnnb_schnet_model_num_params": (_I, [_DESC, _I]),
+    "gnnb_schnet_model_create": (_I, [_DESC, _I, C.c_float, _PP, _I, _PP]),
+    "gnnb_model_schnet": (_I, [_P]),
+    "gnnb_aggregate_cfconv": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, C.c_float, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -358,7 +370,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
         for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER,
                                            **ABI_TRANSFORMER_EDGE, **ABI_RESGATED, **ABI_RESGATED_EDGE, **ABI_GATCONV,
-                                           **ABI_GATCONV_EDGE, **ABI_GGNN, **ABI_RGCN, **ABI_NNCONV, **ABI_GEN}.items():
+                                           **ABI_GATCONV_EDGE, **ABI_GGNN, **ABI_RGCN, **ABI_NNCONV, **ABI_GEN, **ABI_SCHNET}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -571,6 +583,9 @@ class CompiledModel:
                               (self.lib.gnnb_edge_model_num_params, self.lib.gnnb_edge_model_create))
         if spec.get("conv") == "nnconv" and spec.get("aggr", "add") not in NN_AGGR:
             raise GnnbError(f"an NNConv model needs spec['aggr'] in {sorted(NN_AGGR)}, got {spec.get('aggr')!r}")
+        schnet = spec.get("conv") == "schnet"  # (gnnb_schnet.h: the distance is the one edge attribute)
+        if schnet and self.edge_dim != 1:
+            raise GnnbError(f"a SchNet model's edge_attr is the distance alone: spec['edge_dim'] must be 1, got {spec.get('edge_dim')!r}")
         gen_t = None
         if spec.get("conv") in _GEN_CONVS:  # (gnnb_gen.h: one finite temperature per conv layer)
             ts = spec.get("softmax_t", 1.0)
@@ -578,7 +593,8 @@ class CompiledModel:
             if len(ts) != int(spec["num_layers"]) or not all(np.isfinite(ts)):
                 raise GnnbError(f"a GENConv model needs spec['softmax_t']: {spec['num_layers']} finite temperatures (or one number), got {ts!r}")
             gen_t = (C.c_float * max(len(ts), 1))(*ts)
-        n_expect = (self.lib.gnnb_gen_model_num_params(C.byref(self.desc), self.edge_dim) if gen_t is not None else
+        n_expect = (self.lib.gnnb_schnet_model_num_params(C.byref(self.desc), int(spec.get("gaussians", 50))) if schnet else
+                    self.lib.gnnb_gen_model_num_params(C.byref(self.desc), self.edge_dim) if gen_t is not None else
                     self.lib.gnnb_nnconv_model_num_params(C.byref(self.desc), self.edge_dim, self.nnconv_hidden) if spec.get("conv") == "nnconv" else
                     self.lib.gnnb_gat_edge_model_num_params(C.byref(self.desc), self.gat_heads, self.edge_dim) if spec.get("conv") == "gatv2e" else
                     self.lib.gnnb_transformer_edge_model_num_params(C.byref(self.desc), self.transformer_heads, self.edge_dim)
@@ -599,7 +615,10 @@ class CompiledModel:
         if len(host) != n_expect:
             raise GnnbError(f"model needs {n_expect} parameter tensors, got {len(host)}")
         arr = (C.c_void_p * len(host))(*[h.ctypes.data for h in host])
-        if gen_t is not None:  # (gnnb_gen.h: a GIN description, edge_dim -- 0 without edge features -- and the temperatures beside it)
+        if schnet:  # (gnnb_schnet.h: a GIN description, the gaussians and the cutoff beside it)
+            _check(self.lib.gnnb_schnet_model_create(C.byref(self.desc), int(spec.get("gaussians", 50)), float(spec.get("cutoff", 10.0)), arr,
+                                                     len(host), C.byref(self._model)))
+        elif gen_t is not None:  # (gnnb_gen.h: a GIN description, edge_dim -- 0 without edge features -- and the temperatures beside it)
             _check(self.lib.gnnb_gen_model_create(C.byref(self.desc), self.edge_dim, gen_t, arr, len(host), C.byref(self._model)))
         elif spec.get("conv") == "nnconv":  # (gnnb_nnconv.h: a GIN description, edge_dim, the hidden width and aggr beside it)
             _check(self.lib.gnnb_nnconv_model_create(C.byref(self.desc), self.edge_dim, self.nnconv_hidden, NN_AGGR[spec.get("aggr", "add")], arr,
