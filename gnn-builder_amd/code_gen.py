@@ -28,7 +28,7 @@ import jinja2
 import numpy as np
 import torch
 
-from .models import (GATv1Conv_GNNB, GATv1EConv_GNNB, GATv2Conv_GNNB, GATv2EConv_GNNB, GENConv_GNNB, GENEConv_GNNB, GINEConv_GNNB, GNNModel, GatedGraphConv_GNNB, NNConv_GNNB, PNAEConv_GNNB, RGCNConv_GNNB, ResGatedGraphConv_GNNB,
+from .models import (EdgeConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB, GATv2Conv_GNNB, GATv2EConv_GNNB, GENConv_GNNB, GENEConv_GNNB, GINEConv_GNNB, GNNModel, GatedGraphConv_GNNB, NNConv_GNNB, PNAEConv_GNNB, RGCNConv_GNNB, ResGatedGraphConv_GNNB,
                      ResGatedGraphEConv_GNNB, SchNetConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB)
 from .utils import layer_param_name_combiner, serialize_tensor, write_file
 
@@ -154,6 +154,10 @@ class Project:
                 "Project does not generate GENConv designs: the generated shim and the templates have no softmax aggregate; run the "
                 "model through runtime.CompiledModel.from_model(model, ...).forward / forward_pyg (GENEConv_GNNB: forward_edges / "
                 "forward_pyg_edges)")
+        if getattr(model, "gnn_conv", None) is EdgeConv_GNNB:
+            raise NotImplementedError(
+                "Project does not generate EdgeConv designs: the generated shim, the templates and tb_data have no per-edge product under a "
+                "max; run the model through runtime.CompiledModel.from_model(model, ...).forward / forward_pyg")
         if getattr(model, "gnn_conv", None) is SchNetConv_GNNB:
             raise NotImplementedError(
                 "Project does not generate SchNet designs: the generated shim and the templates have no continuous-filter convolution; run "

@@ -79,7 +79,7 @@ static G2Deep gcn_stack_middle_layers(const gnnb_model *model)
     // attention; a ResGatedGraphConv model: none forms the gate; a GatedGraphConv model: none forms the GRU cell; an RGCNConv
     // model: none selects a weight by relation
     if (model->edge_dim || model->gat_heads || model->gat1_heads || model->tf_heads || model->gated || model->ggnn_steps || model->rgcn_relations ||
-        model->nn_coefs || model->gen || model->schnet) // (an NNConv, a GENConv, a SchNet model: no stack kernel forms their aggregates)
+        model->nn_coefs || model->gen || model->schnet || model->edgeconv) // (an NNConv, a GENConv, a SchNet, an EdgeConv model: no stack kernel forms their aggregates)
         return g;
     if (d.conv_type == GNNB_CONV_GIN && L >= 2 && L <= GNNB_MAX_LAYERS && model->gin_w && model->gin_b) {
         // (the execution-order copy made at upload: one stride by construction, the last layer padded to hidden x hidden)
@@ -438,6 +438,23 @@ static int schnet_layer(const LayerCtx &c)
     return c.linear1(c.rows(c.ws->tmp0, fo), fo, p.w_lin, fo, p.b_lin, c.rows(c.skip, fo), c.rows(c.nxt, fo), fo, c.model->desc.activation);
 }
 
+// EdgeConv (gnnb_edgeconv.h; a GIN description with the "edgeconv" mark beside it, so the tables keep explicit (v, v) edges): ONE GEMM
+// x -> [a | b] [N, 2 fo] in ws->tmp0 on w_ec = [(W1a - W1b) ; W1b], b_ec = [b1 ; 0] in the model's math mode, then ONE k_edgeconv_max
+// launch with its fix-up pass -- relu(a_i + b_j) . W2^T on the matrix cores under a segmented max, on the slot -> row map
+// run_conv_layers built for the batch; nn.2's bias, the skip term and the activation in its store.  None of the fused rungs
+static int edgeconv_layer(const LayerCtx &c)
+{
+    const LayerWeights &p = c.model->conv[c.l];
+    const int fi = c.fi, fo = c.fo;
+    float *ab = c.ws->tmp0; // ([max_nodes, >= 2 fo]: gnnb_workspace_create)
+    if (const int rc = c.linear1(c.rows(c.cur, fi), fi, p.w_ec, fi, p.b_ec, nullptr, c.rows(ab, 2 * fo), 2 * fo, GNNB_ACT_NONE))
+        return rc;
+    if (c.M > 0) // (always the whole batch: such a model takes no stack kernel, so no large segment runs beside one)
+        GNNB_HIP_TRY(launch_edgeconv_max(c.tv, c.ws->schnet_sc, ab, 2 * fo, fo, p.w1, fo, p.b1, fo, c.skip, fo, c.model->desc.activation, c.nxt, fo,
+                                         c.hs()));
+    return GNNB_OK;
+}
+
 // GIN's first linear + ReLU on the eps-weighted sum -> ws->tmp0
 static int gin_hidden(const LayerCtx &c)
 {
@@ -603,7 +620,7 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
     c.tv.tile_lo = tile_lo;
     c.cur = x_dev;
     int which = 0;
-    if (model->schnet && d.num_layers > 0) // (a SchNet model: the slot -> row map of the batch, once for all layers)
+    if ((model->schnet || model->edgeconv) && d.num_layers > 0) // (a SchNet, an EdgeConv model: the slot -> row map of the batch, once for all layers)
         GNNB_HIP_TRY(launch_schnet_slots(ws->t, ws->schnet_sc, c.hs()));
     for (c.l = 0; c.l < d.num_layers; c.l++) {
         const LayerDims ld = layer_dims(d, c.l);
@@ -623,6 +640,7 @@ static int run_conv_layers(const gnnb_model *model, gnnb_workspace *ws, const fl
                  : model->nn_coefs                                                                                       ? nnconv_layer(c)
                  : model->gen                                                                                            ? gen_layer(c)
                  : model->schnet                                                                                         ? schnet_layer(c)
+                 : model->edgeconv                                                                                       ? edgeconv_layer(c)
                                                                                                                          : gin_layer(c);
             break;
         case GNNB_CONV_SAGE: rc = sage_layer(c); break;
@@ -904,7 +922,7 @@ static int forward_prepared_body(const gnnb_model *model, gnnb_workspace *ws, co
         model->tf_heads != ws->tf_heads || model->gated != ws->gated ||
         model->ggnn_steps != ws->ggnn_steps || model->rgcn_relations != ws->rgcn_relations || model->nn_coefs != ws->nn_coefs ||
         model->nn_hidden != ws->nn_hidden || model->nn_mean != ws->nn_mean || model->gen != ws->gen ||
-        model->schnet != ws->schnet || model->schnet_cutoff != ws->schnet_cutoff)
+        model->schnet != ws->schnet || model->schnet_cutoff != ws->schnet_cutoff || model->edgeconv != ws->edgeconv)
         return fail(GNNB_ERR_INVALID, "workspace was created for a different model");
     const gnnb_model_desc &d = model->desc;
     const int N = ws->t.num_nodes, B = ws->t.num_graphs;
@@ -950,6 +968,8 @@ static int check_edge_forward(const gnnb_model *model, const gnnb_workspace *ws,
         return fail(GNNB_ERR_INVALID, "null argument to %s", entry);
     if (const int rc = refuse_rgcn_model(model, ws, entry, strstr(entry, "prepared") ? "gnnb_forward_prepared_types" : "gnnb_forward_batched_types"))
         return rc;
+    if (const int rc = refuse_edgeconv_model(model, ws, entry, strstr(entry, "prepared") ? "gnnb_forward_prepared" : "gnnb_forward_batched"))
+        return rc;
     if (model->gen && !model->edge_dim)
         return fail(GNNB_ERR_INVALID, "%s: a GENConv model without edge features (gnnb_gen_model_create, edge_dim 0) takes no edge attributes: "
                                       "call %s (gnnb_gen.h)", entry, strstr(entry, "prepared") ? "gnnb_forward_prepared" : "gnnb_forward_batched");
@@ -979,6 +999,8 @@ static int check_types_forward(const gnnb_model *model, const gnnb_workspace *ws
 {
     if (!model || !ws)
         return fail(GNNB_ERR_INVALID, "null argument to %s", entry);
+    if (const int rc = refuse_edgeconv_model(model, ws, entry, strstr(entry, "prepared") ? "gnnb_forward_prepared" : "gnnb_forward_batched"))
+        return rc;
     if (!model->rgcn_relations)
         return fail(GNNB_ERR_INVALID, "%s takes a model of gnnb_rgcn_model_create; this one has no relations", entry);
     if (model->rgcn_relations != ws->rgcn_relations || !ws->rgcn_rec)

@@ -25,6 +25,7 @@
 #include "gnnb_nnconv.h"
 #include "gnnb_gen.h"
 #include "gnnb_schnet.h"
+#include "gnnb_edgeconv.h"
 
 namespace gnnb {
 
@@ -86,6 +87,8 @@ struct gnnb_model {
                             // gaussians -- every layer has w_cf1, GIN's w0 [out, gaussians], b0, w1 [out, out], b1 as its filter MLP,
                             // w_cf2, b_cf2 and w_lin, b_lin
     float schnet_cutoff = 0.0f; // ... and its cutoff
+    int edgeconv = 0;       // 1: an EdgeConv model (gnnb_edgeconv_model_create; desc is a GIN description) -- every layer has w_ec [2 out, in],
+                            // b_ec (nn.0 folded: x -> [a | b]) and nn.2 in GIN's w1 [out, out], b1
     int device = 0;
     ~gnnb_model(); // frees blob and head_dev (gnnb_model.hip)
 };
@@ -116,6 +119,7 @@ struct gnnb_workspace {
     int gen = 0;                 // ... and 1 when it is a GENConv model
     int schnet = 0;              // ... and its gaussians and cutoff when it is a SchNet model (0: it is not)
     float schnet_cutoff = 0.0f;
+    int edgeconv = 0;            // ... and 1 when it is an EdgeConv model (its kernel shares the scratch below)
     char *schnet_blob = nullptr; // k_schnet_cfconv's scratch (SchnetScratch: the slot -> row map, the tiles' partial rows), one allocation:
     gnnb::SchnetScratch schnet_sc{}; // made by gnnb_workspace_create for a SchNet model, by the first gnnb_aggregate_cfconv on any other
     gnnb::RgcnSlot *rgcn_rec = nullptr; // such a model's workspace only: the slot records of the batch (k_rgcn_slots), 8 max_edges bytes,
@@ -193,6 +197,7 @@ int refuse_rgcn_model(const gnnb_model *model, const gnnb_workspace *ws, const c
 
 // ... and for a GENConv model / its workspace (gnnb_gen.h)
 int refuse_gen_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
+int refuse_edgeconv_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use);
 
 // gnnb_runtime.hip, for the forward (gnnb_forward.hip) -- each is described where it is defined
 int ensure_gcoef(gnnb_workspace *ws, void *stream);

@@ -219,6 +219,8 @@ int gnnb_forward_pyg_ordered(const gnnb_model *model, gnnb_workspace *ws, const 
         return rc;
     if (const int rc = refuse_gen_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg"))
         return rc;
+    if (const int rc = refuse_edgeconv_model(model, ws, "gnnb_forward_pyg_ordered", "gnnb_forward_pyg"))
+        return rc;
     const float *x_ord = nullptr;
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr, *perm = nullptr;
     int g0 = 0, n0 = 0, e0 = 0;
@@ -287,6 +289,8 @@ int gnnb_forward_pyg_edges(const gnnb_model *model, gnnb_workspace *ws, const fl
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg_edges");
     if (const int rc = refuse_rgcn_model(model, ws, "gnnb_forward_pyg_edges", "gnnb_forward_pyg_types"))
         return rc;
+    if (const int rc = refuse_edgeconv_model(model, ws, "gnnb_forward_pyg_edges", "gnnb_forward_pyg"))
+        return rc;
     if (!model->edge_dim || model->edge_dim != ws->edge_dim)
         return fail(GNNB_ERR_INVALID, "gnnb_forward_pyg_edges takes a model of gnnb_edge_model_create and its workspace");
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr;
@@ -344,6 +348,8 @@ int gnnb_forward_pyg_types(const gnnb_model *model, gnnb_workspace *ws, const fl
 {
     if (!model || !ws)
         return fail(GNNB_ERR_INVALID, "null argument to gnnb_forward_pyg_types");
+    if (const int rc = refuse_edgeconv_model(model, ws, "gnnb_forward_pyg_types", "gnnb_forward_pyg"))
+        return rc;
     if (!model->rgcn_relations || model->rgcn_relations != ws->rgcn_relations)
         return fail(GNNB_ERR_INVALID, "gnnb_forward_pyg_types takes a model of gnnb_rgcn_model_create and its workspace");
     const int32_t *coo = nullptr, *node_ptr = nullptr, *edge_ptr = nullptr, *edge_type = nullptr;

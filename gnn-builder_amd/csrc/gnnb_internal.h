@@ -430,6 +430,15 @@ hipError_t launch_schnet_cfconv(const BatchTables &t, const SchnetScratch &sc, c
                                 const float *w1, int ldw1, const float *b1, const float *w2, int ldw2, const float *b2, int gaussians,
                                 float cutoff, float *out, int ldo, hipStream_t s);
 hipError_t launch_schnet_ssp(float *y, size_t n, hipStream_t s);
+// EdgeConv's aggregate (k_edgeconv.hip; gnnb_edgeconv.h): out[i] = act(max_{j -> i} (w2 relu(a[i] + b[j])) + b2 + skip[i]), a row without
+// in-edges act(skip[i]) -- the second linear on the matrix cores under a segmented max, tiles of SCHNET_TE_MIN or 64 CSR slots, on
+// SchnetScratch (the slot -> row map of launch_schnet_slots and the tiles' partial rows: the same sizing).  ab [N, >= 2 hidden] rows
+// of stride ldab: a in columns [0, hidden), b in [hidden, 2 hidden); w2 [width, hidden] rows of stride ldw2; b2 [width] or nullptr;
+// skip rows of stride lds or nullptr; out rows of stride ldo, no alias of an input.  Tables that keep explicit (v, v) edges.
+// hipErrorInvalidValue: nothing launched
+constexpr int EDGECONV_MAX_WIDTH = 256;
+hipError_t launch_edgeconv_max(const BatchTables &t, const SchnetScratch &sc, const float *ab, int ldab, int hidden, const float *w2, int ldw2,
+                               const float *b2, int width, const float *skip, int lds, int act, float *out, int ldo, hipStream_t s);
 // the ingest's edge types in COO row order (k_ingest.hip): out[i] = (int32) edge_type[state[INGEST_STATE_UNSORTED] ? idx[i] : i], -1
 // for a value that does not fit (k_rgcn_slots flags it); idx, state: as launch_edge_attr_order's
 hipError_t launch_edge_type_order(const long long *edge_type, const int32_t *idx, const int32_t *state, int32_t *out, int num_edges, hipStream_t s);

@@ -306,6 +306,25 @@ int count_schnet_params(const gnnb_model_desc *desc, int gaussians)
     return SCHNET_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
 }
 
+// parameter tensors of an EdgeConv model (gnnb_edgeconv.h): a GIN description (its tables keep explicit (v, v) edges) without the
+// fixed-point emulation, every layer width at most 256; four per layer
+int count_edgeconv_params(const gnnb_model_desc *desc)
+{
+    int rc = validate_desc(desc);
+    if (rc != GNNB_OK)
+        return rc;
+    if (desc->conv_type != GNNB_CONV_GIN)
+        return fail(GNNB_ERR_INVALID, "an EdgeConv model's description is a GIN description (conv_type %d given)", desc->conv_type);
+    if (desc->fpx_w != 0)
+        return fail(GNNB_ERR_INVALID, "the fixed-point emulation does not cover EdgeConv models (fpx_w must be 0)");
+    for (int l = 0; l < desc->num_layers; l++) {
+        const LayerDims ld = layer_dims(*desc, l);
+        if (ld.fin > EDGECONV_MAX_WIDTH || ld.fout > EDGECONV_MAX_WIDTH)
+            return fail(GNNB_ERR_INVALID, "layer %d's widths %d -> %d: an EdgeConv layer is at most %d wide", l, ld.fin, ld.fout, EDGECONV_MAX_WIDTH);
+    }
+    return EDGECONV_PARAM_SLOTS * desc->num_layers + 2 * desc->mlp_num_linear;
+}
+
 // What travels beside a description, by name: nothing (gnnb_model_create), edge_dim of an edge model whose description has conv
 // type `base` (gnnb_edge_model_create: GIN, gnnb_pna_edge_model_create: PNA), or heads and negative_slope of a GATv2 model
 // (gnnb_gat_model_create: a GCN description), or all three (gnnb_gat_edge_model_create: GATv2 with edge features), or heads of a
@@ -329,7 +348,14 @@ struct ModelKind {
                                   // temperatures, one per layer
     int schnet = 0;               // > 0: a SchNet model (gnnb_schnet_model_create: a GIN description, edge_dim 1 too) of that many gaussians
     float schnet_cutoff = 0.0f;   // ... and its cutoff
+    bool edgeconv = false;        // an EdgeConv model (gnnb_edgeconv_model_create: a GIN description)
     static ModelKind plain() { return {}; }
+    static ModelKind edgeconv_of()
+    {
+        ModelKind k;
+        k.edgeconv = true;
+        return k;
+    }
     static ModelKind schnet_of(int gaussians, float cutoff)
     {
         ModelKind k = edges(1, GNNB_CONV_GIN);
@@ -426,7 +452,8 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     *out_model = nullptr;
     const int edge_dim = kind.edge_dim, gat_heads = kind.gat_heads, tf_heads = kind.tf_heads;
     const int gat1_heads = kind.gat1_heads;
-    int expect = kind.schnet != 0 ? count_schnet_params(desc, kind.schnet)
+    int expect = kind.edgeconv ? count_edgeconv_params(desc)
+                 : kind.schnet != 0 ? count_schnet_params(desc, kind.schnet)
                  : kind.gen_t != nullptr ? count_gen_params(desc, edge_dim)
                  : kind.nn_coefs != 0 ? count_nnconv_params(desc, edge_dim, kind.nn_hidden)
                  : kind.rgcn_relations != 0 ? count_rgcn_params(desc, kind.rgcn_relations)
@@ -450,7 +477,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
 
     const gnnb_model_desc &d = *desc;
     const BuiltWeights built = build_weight_image(d, edge_dim, host_params, gat_heads, tf_heads, kind.gated, gat1_heads, kind.ggnn_steps, kind.rgcn_relations,
-                                                  kind.nn_coefs, kind.nn_hidden, kind.gen_t != nullptr, kind.schnet);
+                                                  kind.nn_coefs, kind.nn_hidden, kind.gen_t != nullptr, kind.schnet, kind.edgeconv);
     const std::vector<float> &img = built.img;
     const WeightLayout &lo = built.layout;
 
@@ -469,6 +496,7 @@ int model_create(const gnnb_model_desc *desc, const ModelKind &kind, const float
     m->nn_mean = kind.nn_mean;
     m->schnet = kind.schnet;
     m->schnet_cutoff = kind.schnet_cutoff;
+    m->edgeconv = kind.edgeconv ? 1 : 0;
     if (kind.gen_t) {
         m->gen = 1;
         m->gen_t.assign(kind.gen_t, kind.gen_t + d.num_layers);
@@ -761,6 +789,19 @@ int gnnb_schnet_model_create(const gnnb_model_desc *desc, int gaussians, float c
 }
 
 int gnnb_model_schnet(const gnnb_model *model) { return model ? model->schnet : 0; }
+
+int gnnb_edgeconv_model_num_params(const gnnb_model_desc *desc) { return count_edgeconv_params(desc); }
+
+int gnnb_edgeconv_model_create(const gnnb_model_desc *desc, const float *const *host_params, int num_params, gnnb_model **out_model)
+{
+    if (out_model)
+        *out_model = nullptr;
+    if (const int rc = count_edgeconv_params(desc); rc < 0)
+        return rc;
+    return model_create(desc, ModelKind::edgeconv_of(), host_params, num_params, out_model);
+}
+
+int gnnb_model_edgeconv(const gnnb_model *model) { return model ? model->edgeconv : 0; }
 
 void gnnb_model_destroy(gnnb_model *model)
 {

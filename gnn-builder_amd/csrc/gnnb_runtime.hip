@@ -116,6 +116,14 @@ int refuse_gen_model(const gnnb_model *model, const gnnb_workspace *ws, const ch
     return GNNB_OK;
 }
 
+int refuse_edgeconv_model(const gnnb_model *model, const gnnb_workspace *ws, const char *entry, const char *use)
+{
+    if ((model && model->edgeconv) || (ws && ws->edgeconv))
+        return fail(GNNB_ERR_INVALID, "%s: an EdgeConv model (gnnb_edgeconv_model_create) takes neither edge attributes nor edge types, runs layer "
+                                      "by layer and is not served here: call %s (gnnb_edgeconv.h)", entry, use);
+    return GNNB_OK;
+}
+
 static thread_local int tl_math = -1; // >= 0: the calling thread is inside an entry point of a model with its own math mode
 static thread_local FlagWord tl_flag = {nullptr, nullptr};
 int launch_math() { return tl_math >= 0 ? tl_math : (int)options().math; }
@@ -224,6 +232,9 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
             tmpw = std::max(tmpw, 2 * layer_dims(d, l).fout);
             aggw = std::max(aggw, layer_dims(d, l).fout);
         }
+    if (model->edgeconv) // an EdgeConv layer's GEMM writes [a | b] [N, 2 out] into tmp0; the kernel stores the layer's output itself
+        for (int l = 0; l < d.num_layers; l++)
+            tmpw = std::max(tmpw, 2 * layer_dims(d, l).fout);
     if (model->schnet) // a SchNet layer's x1 and lin2's output [N, out] go to tmp0 (maxw covers them), its aggregate [N, out] to agg
         for (int l = 0; l < d.num_layers; l++)
             aggw = std::max(aggw, layer_dims(d, l).fout);
@@ -242,7 +253,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     // (the stage-cut planner's tables: opt-in -- carved only for workspaces created while the option is on; a workspace created
     // without them keeps equal tile counts whatever the option says later: round-5 advisor finding)
     const bool want_plan = options().stage_cut && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 &&
-                           model->gat_heads == 0 && model->gat1_heads == 0 && model->tf_heads == 0 && model->gated == 0 && model->ggnn_steps == 0 && model->rgcn_relations == 0 && model->gen == 0; // (a GATv2 model,
+                           model->gat_heads == 0 && model->gat1_heads == 0 && model->tf_heads == 0 && model->gated == 0 && model->ggnn_steps == 0 && model->rgcn_relations == 0 && model->gen == 0 && model->edgeconv == 0; // (a GATv2 model,
                                             // a GAT v1 model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model, an RGCNConv model take no stack kernel: no stage plan)
     const int pooledw = d.num_pools * gnn_out_width(d);
     const int mlpw = std::max(d.mlp_hidden, d.mlp_out);
@@ -265,6 +276,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
     ws->gen = model->gen;
     ws->schnet = model->schnet;
     ws->schnet_cutoff = model->schnet_cutoff;
+    ws->edgeconv = model->edgeconv;
     ws->max_graphs = max_graphs;
     ws->max_nodes = max_nodes;
     ws->max_edges = max_edges;
@@ -323,7 +335,7 @@ int gnnb_workspace_create(const gnnb_model *model, int max_graphs, int max_nodes
                     hipGetErrorString(e));
     }
     (void)place(Arena{ws->blob});
-    if (model->schnet) { // k_schnet_cfconv's scratch, an allocation of its own: the forward must not allocate
+    if (model->schnet || model->edgeconv) { // k_schnet_cfconv's / k_edgeconv_max's scratch, an allocation of its own: the forward must not allocate
         int w = 1;
         for (int l = 0; l < d.num_layers; l++)
             w = std::max(w, layer_dims(d, l).fout);
@@ -443,7 +455,7 @@ static bool stack_promised(const gnnb_workspace *ws)
     // (a GINE model's workspace, a GATv2 model's, a GAT v1 model's, a TransformerConv model's, a ResGatedGraphConv model's, a
     // GatedGraphConv model's, an RGCNConv model's: never -- their layers take no stack kernel, whatever the promise)
     return options().fuse_gcn2 && (d.conv_type == GNNB_CONV_GCN || d.conv_type == GNNB_CONV_GIN) && d.num_layers >= 2 && ws->max_graph_nodes > 0 &&
-           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->gat1_heads == 0 && ws->tf_heads == 0 && ws->gated == 0 && ws->ggnn_steps == 0 && ws->rgcn_relations == 0 && ws->gen == 0;
+           ws->edge_dim == 0 && ws->gat_heads == 0 && ws->gat1_heads == 0 && ws->tf_heads == 0 && ws->gated == 0 && ws->ggnn_steps == 0 && ws->rgcn_relations == 0 && ws->gen == 0 && ws->edgeconv == 0;
 }
 
 // ... and the WHOLE batch is expected there: no large segment, no fixed-point emulation.  Such a batch needs neither the
@@ -1056,6 +1068,25 @@ int gnnb_aggregate_cfconv(gnnb_workspace *ws, const float *x1_dev, int ldx, int 
     GNNB_HIP_TRY(launch_schnet_slots(ws->t, ws->schnet_sc, (hipStream_t)stream));
     GNNB_HIP_TRY(launch_schnet_cfconv(ws->t, ws->schnet_sc, x1_dev, ldx, width, edge_dist_dev, w1_dev, ldw1, b1_dev, w2_dev, ldw2, b2_dev, gaussians,
                                       cutoff, out_dev, ldo, (hipStream_t)stream));
+    return GNNB_OK;
+}
+
+int gnnb_aggregate_edgeconv(gnnb_workspace *ws, const float *ab_dev, int ldab, int hidden, const float *w2_dev, int ldw2, const float *b2_dev,
+                            int width, const float *skip_dev, int act, float *out_dev, int ldo, void *stream)
+{
+    GNNB_TRY(stage_entry(ws, "gnnb_aggregate_edgeconv", TABLES_KEEP_LOOPS));
+    // (a prepared batch without nodes launches nothing and reads no operand)
+    const bool operands = ws->t.num_nodes <= 0 || (ab_dev && w2_dev && out_dev);
+    if (!operands || hidden < 1 || hidden > EDGECONV_MAX_WIDTH || width < 1 || width > EDGECONV_MAX_WIDTH || ldab < 2 * hidden || ldw2 < hidden ||
+        ldo < width || bad_act(act))
+        return fail(GNNB_ERR_INVALID, "bad argument to gnnb_aggregate_edgeconv (ab, w2 and out not NULL unless the batch has no nodes, hidden and "
+                                      "width 1 .. %d, ldab >= 2 hidden, ldw2 >= hidden, ldo >= width, act a gnnb_act)", EDGECONV_MAX_WIDTH);
+    if (ws->t.num_nodes <= 0)
+        return GNNB_OK;
+    GNNB_TRY(ensure_schnet_scratch(ws, width));
+    GNNB_HIP_TRY(launch_schnet_slots(ws->t, ws->schnet_sc, (hipStream_t)stream));
+    GNNB_HIP_TRY(launch_edgeconv_max(ws->t, ws->schnet_sc, ab_dev, ldab, hidden, w2_dev, ldw2, b2_dev, width, skip_dev, width, act, out_dev, ldo,
+                                     (hipStream_t)stream));
     return GNNB_OK;
 }
 

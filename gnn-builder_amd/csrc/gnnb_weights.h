@@ -167,6 +167,10 @@ template <> constexpr size_t absent_slot<size_t>() { return NO_OFFSET; }
 //              w_cf1 [out, in]                      conv.lin1.weight (no bias): x -> x1
 //              w0 [out, gaussians], b0 [out]        mlp.0;   w1 [out, out], b1 [out]: mlp.2 -- k_schnet_cfconv's operands
 //              w_cf2 [out, out], b_cf2 [out]        conv.lin2;   w_lin [out, out], b_lin [out]: lin
+//   EdgeConv  (gnnb_model::edgeconv, gnnb_edgeconv_model_create: a GIN description) nn.2 in GIN's second pair, raw
+//              w_ec [2 out, in], b_ec [2 out]       derived: [(W1a - W1b) ; W1b] of nn.0.weight = [W1a | W1b] [out, 2 in] (edgeconv_fold)
+//                                                   and [nn.0.bias ; 0] -- ONE GEMM gives [a | b] [N, 2 out], nn.0 = a_i + b_j
+//              w1 [out, out], b1 [out]              nn.2 -- k_edgeconv_max's operands
 // (GCN's pair has the names of GIN's first linear: the stack kernels and k_conv_rows take either through the same operands)
 template <typename T> struct LayerSlots {
     T w0 = absent_slot<T>(), b0 = absent_slot<T>(), w1 = absent_slot<T>(), b1 = absent_slot<T>();
@@ -181,6 +185,7 @@ template <typename T> struct LayerSlots {
     T w_nn = absent_slot<T>(), b_nn = absent_slot<T>(), w_nn1 = absent_slot<T>(), b_nn1 = absent_slot<T>();
     T w_sr = absent_slot<T>(), b_sr = absent_slot<T>();
     T w_cf1 = absent_slot<T>(), w_cf2 = absent_slot<T>(), b_cf2 = absent_slot<T>();
+    T w_ec = absent_slot<T>(), b_ec = absent_slot<T>();
     T w_cat = absent_slot<T>(), b_cat = absent_slot<T>(), w_cat_skip = absent_slot<T>();
     T w_pre = absent_slot<T>(), b_pre = absent_slot<T>(), w_post = absent_slot<T>(), b_post = absent_slot<T>();
     T w_lin = absent_slot<T>(), b_lin = absent_slot<T>();
@@ -189,7 +194,7 @@ template <typename T> struct LayerSlots {
     // the same slots with f applied to each (offsets -> pointers)
     template <typename F> auto map(F f) const -> LayerSlots<decltype(f(w0))>
     {
-        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_rgcn), f(b_rgcn), f(w_nn), f(b_nn), f(w_nn1), f(b_nn1), f(w_sr), f(b_sr), f(w_cf1), f(w_cf2), f(b_cf2), f(w_cat),
+        return {f(w0),    f(b0),    f(w1),     f(b1),     f(edge_w), f(edge_b), f(w_lr),   f(b_lr),    f(att),        f(gat_bias), f(w_edge), f(w_gat), f(a_edge), f(w_qkvr), f(b_qkvr), f(w_qkvre), f(b_qkvre), f(w_kqvr), f(b_kqvr), f(w_gv_edge), f(w_ggc), f(w_ggc_next), f(b_ggc), f(b_ih), f(w_rgcn), f(b_rgcn), f(w_nn), f(b_nn), f(w_nn1), f(b_nn1), f(w_sr), f(b_sr), f(w_cf1), f(w_cf2), f(b_cf2), f(w_ec), f(b_ec), f(w_cat),
                 f(b_cat), f(w_cat_skip), f(w_pre), f(b_pre), f(w_post), f(b_post), f(w_lin), f(b_lin), f(w_fold), f(b_fold), f(w_class),
                 f(b_class)};
     }
@@ -451,6 +456,23 @@ inline WeightBias transformer_edge_fold(const float *w_q, const float *b_q, cons
     return f;
 }
 
+// EdgeConv: the first linear of nn on [x_i | x_j - x_i] as a function of the two rows.  W1 = [W1a | W1b] [fo, 2 fi], so
+//   W1 [x_i | x_j - x_i] + b1 = (W1a - W1b) x_i + b1 + W1b x_j:   w = [(W1a - W1b) ; W1b] [2 fo, fi],  b = [b1 ; 0] [2 fo]
+// (the difference taken in double and rounded once, as the other folds)
+inline WeightBias edgeconv_fold(const float *w1, const float *b1, size_t fi, size_t fo)
+{
+    WeightBias f{std::vector<float>(2 * fo * fi), std::vector<float>(2 * fo, 0.0f)};
+    for (size_t n = 0; n < fo; n++) {
+        const float *row = w1 + n * 2 * fi;
+        for (size_t k = 0; k < fi; k++) {
+            f.w[n * fi + k] = (float)((double)row[k] - (double)row[fi + k]);
+            f.w[(fo + n) * fi + k] = row[fi + k];
+        }
+        f.b[n] = b1[n];
+    }
+    return f;
+}
+
 // GAT v1: both per-node scores as linear functions of x.  s_src_j[h] = sum_c att_src[h, c] (W x_j)[h C + c] = (A_src W x_j)[h], so
 //   w[fo + h][:] = sum_c att_src[h C + c] * W[h C + c][:],   w[fo + heads + h][:] = sum_c att_dst[h C + c] * W[h C + c][:]
 // (C = fo / heads; accumulated in double, c increasing, rounded once -- as resgated_edge_blocks and transformer_edge_fold) under W's
@@ -594,16 +616,26 @@ inline int nnconv_param_slots(int hidden) { return hidden > 0 ? 6 : 4; }
 // between them with edge features
 inline int gen_param_slots(int fin, int fout, int edge_dim) { return (fin != fout ? 4 : 0) + (edge_dim > 0 ? 2 : 0) + 4; }
 constexpr int SCHNET_PARAM_SLOTS = 9; // a SchNet layer's canonical tensors (gnnb_schnet.h)
+constexpr int EDGECONV_PARAM_SLOTS = 4; // an EdgeConv layer's canonical tensors (gnnb_edgeconv.h)
 constexpr int GAT1_PARAM_SLOTS = 4; // a GAT v1 layer's canonical tensors (gnnb_gatconv.h); two more with edge features (gnnb_gatconv_edge.h)
 
 // One conv layer's canonical tensors p[] (in the order of include/gnnb_hip.h; an edge model's two behind GIN's four / PNA's six; a
 // GATv2 model's six in gnnb_gat.h's order, lin_edge's weight behind them when it has edge features) and the derived forms its conv type has, pushed in the order of LayerSlots' comment ->
 // their offsets in the image
 inline LayerOffsets push_conv_layer(WeightImage &im, const gnnb_model_desc &d, int l, const float *const *p, int edge_dim, int gat_heads = 0,
-                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0, int nn_hidden = 0, bool gen = false, int schnet = 0)
+                                    int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0, int nn_hidden = 0, bool gen = false, int schnet = 0, bool edgeconv = false)
 {
     const LayerDims ld = layer_dims(d, l);
     const size_t fi = ld.fin, fo = ld.fout;
+    if (edgeconv) { // (a GIN description whose layers are EdgeConv's; canonical order: nn.0.weight [out, 2 in], nn.0.bias, nn.2.weight, nn.2.bias)
+        LayerOffsets g;
+        const WeightBias ec = edgeconv_fold(p[0], p[1], fi, fo);
+        g.w_ec = im.push(ec.w);
+        g.b_ec = im.push(ec.b);
+        g.w1 = im.push(p[2], fo * fo);
+        g.b1 = im.push(p[3], fo);
+        return g;
+    }
     if (schnet > 0) { // (a GIN description whose layers are SchNet's; canonical order: conv.lin1.weight, mlp.0.weight, mlp.0.bias,
                       // mlp.2.weight, mlp.2.bias, conv.lin2.weight, conv.lin2.bias, lin.weight, lin.bias; schnet = gaussians)
         LayerOffsets g;
@@ -799,14 +831,16 @@ struct BuiltWeights {
 // nn_coefs > 0: an NNConv model (a GIN description with edge_dim; four tensors per layer, six with nn_hidden > 0; no execution-order copy).
 // gen: a GENConv model (a GIN description, edge_dim 0 .. 16; four to ten tensors per layer; no execution-order copy).
 // schnet > 0: a SchNet model of that many gaussians (a GIN description, edge_dim 1; nine tensors per layer; no execution-order copy).
+// edgeconv: an EdgeConv model (a GIN description; four tensors per layer; no execution-order copy).
 inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, const float *const *host_params, int gat_heads = 0,
                                        int tf_heads = 0, bool gated = false, int gat1_heads = 0, int ggnn_steps = 0, int rgcn_relations = 0, int nn_coefs = 0,
-                                       int nn_hidden = 0, bool gen = false, int schnet = 0)
+                                       int nn_hidden = 0, bool gen = false, int schnet = 0, bool edgeconv = false)
 {
     WeightImage im(d);
     WeightLayout lo;
     lo.conv.resize(d.num_layers);
-    const int slots = schnet > 0       ? SCHNET_PARAM_SLOTS
+    const int slots = edgeconv         ? EDGECONV_PARAM_SLOTS
+                      : schnet > 0     ? SCHNET_PARAM_SLOTS
                       : nn_coefs > 0   ? nnconv_param_slots(nn_hidden)
                       : rgcn_relations > 0 ? RGCN_PARAM_SLOTS
                       : ggnn_steps > 0 ? GGNN_PARAM_SLOTS
@@ -818,13 +852,13 @@ inline BuiltWeights build_weight_image(const gnnb_model_desc &d, int edge_dim, c
     int pi = 0;
     // (a GENConv layer's count depends on its widths: gen_param_slots)
     for (int l = 0; l < d.num_layers; pi += gen ? gen_param_slots(layer_dims(d, l).fin, layer_dims(d, l).fout, edge_dim) : slots, l++)
-        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps, rgcn_relations, nn_coefs, nn_hidden, gen, schnet);
+        lo.conv[l] = push_conv_layer(im, d, l, host_params + pi, edge_dim, gat_heads, tf_heads, gated, gat1_heads, ggnn_steps, rgcn_relations, nn_coefs, nn_hidden, gen, schnet, edgeconv);
     const bool have_w1f = gat_heads == 0 && gat1_heads == 0 && d.conv_type == GNNB_CONV_GCN && d.num_layers == 2 && d.hidden_dim % 16 == 0 && d.hidden_dim <= 128 && d.out_dim <= 128;
     if (have_w1f) // (from the image copy: already on the fixed-point grid when fpx is set; push() quantising again is harmless -- the grid is idempotent)
         lo.zf_w1f = im.push(zf_fragment_order(&im.img[lo.conv[1].w0], d.hidden_dim, d.out_dim));
     // (a GINE model, a TransformerConv model, a ResGatedGraphConv model, a GatedGraphConv model, an RGCNConv model take no stack
     // kernel: no execution-order copy)
-    const bool have_gin = edge_dim == 0 && nn_coefs == 0 && !gen && tf_heads == 0 && !gated && ggnn_steps == 0 && rgcn_relations == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
+    const bool have_gin = edge_dim == 0 && nn_coefs == 0 && !gen && !edgeconv && tf_heads == 0 && !gated && ggnn_steps == 0 && rgcn_relations == 0 && d.conv_type == GNNB_CONV_GIN && d.num_layers >= 2 && (d.hidden_dim == 32 || d.hidden_dim == 64 || d.hidden_dim == 128) &&
                           d.out_dim <= d.hidden_dim && d.out_dim % 4 == 0;
     if (have_gin) {
         const WeightBias g = gin_execution_order(d, im.img, lo.conv);

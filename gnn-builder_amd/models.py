@@ -1228,6 +1228,33 @@ class SchNetConv_GNNB(nn.Module):
         return self.conv(x, edge_index, edge_attr)
 
 
+# --------------------------------------------------------------------------------------- EdgeConv
+class EdgeConv_GNNB(nn.Module):
+    """DGCNN's EdgeConv (Wang et al.; no class of the reference), PyG's ``EdgeConv(nn, aggr="max")`` with
+    ``nn = Linear(2 in, out) -> ReLU -> Linear(out, out)`` (the hidden width is ``out``, as GIN's MLP)::
+
+        out_i = max_{j -> i} nn([x_i | x_j - x_i])
+
+    ``i = edge_index[1]``; a node without in-edges gives 0 (no bias).  No self loop is added or removed.  ``GNNModel(...,
+    gnn_conv=EdgeConv_GNNB, gnn_aggr="max")`` stacks it; ``forward(x, edge_index)``.  PyG's ``state_dict`` keys (``nn.0.*``, ``nn.2.*``)
+    load.  The accelerated path is ``runtime.CompiledModel.from_model`` with ``forward`` / ``forward_prepared`` / ``forward_pyg`` (C ABI
+    ``include/gnnb_edgeconv.h``: the first linear folded into one node GEMM, the second on the matrix cores under the max,
+    csrc/k_edgeconv.hip).  ``Project`` does not generate such designs."""
+
+    def __init__(self, in_channels: int, out_channels: int, p_in: int = 1, p_out: int = 1):
+        super().__init__()
+        self.in_channels, self.out_channels, self.p_in, self.p_out = in_channels, out_channels, p_in, p_out
+        self.nn = nn.Sequential(nn.Linear(2 * in_channels, out_channels), nn.ReLU(), nn.Linear(out_channels, out_channels))
+
+    def forward(self, x: Tensor, edge_index: Tensor) -> Tensor:
+        src, dst = edge_index[0].long(), edge_index[1].long()
+        m = self.nn(torch.cat([x[dst], x[src] - x[dst]], dim=-1))
+        out = torch.full((x.shape[0], self.out_channels), float("-inf"), dtype=m.dtype, device=m.device)
+        out = out.scatter_reduce(0, dst.unsqueeze(-1).expand_as(m), m, "amax", include_self=True)
+        has = torch.zeros(x.shape[0], dtype=torch.bool, device=m.device).index_fill(0, dst, True)
+        return torch.where(has.unsqueeze(-1), out, torch.zeros_like(out))
+
+
 # --------------------------------------------------------------------------------------- pooling / MLP
 SUPPORTED_GLOBAL_POOLING_AGGRS = {"add": "SumAggregation", "max": "MaxAggregation", "mean": "MeanAggregation"}
 SUPPORTED_GLOBAL_POOLING_MODE = ["cat"]
@@ -1341,12 +1368,13 @@ class MLP(nn.Module):
 SUPPORTED_GNN_CONVS = [GCNConv_GNNB, GINConv_GNNB, GATConv_GNNB, PNAConv_GNNB, SAGEConv_GNNB, GINEConv_GNNB, PNAEConv_GNNB,
                        GATv2Conv_GNNB, GATv2EConv_GNNB, TransformerConv_GNNB, TransformerEConv_GNNB, ResGatedGraphConv_GNNB,
                        ResGatedGraphEConv_GNNB, GATv1Conv_GNNB, GATv1EConv_GNNB, GatedGraphConv_GNNB, RGCNConv_GNNB, NNConv_GNNB,
-                       GENConv_GNNB, GENEConv_GNNB, SchNetConv_GNNB]
+                       GENConv_GNNB, GENEConv_GNNB, SchNetConv_GNNB, EdgeConv_GNNB]
 _CONV_NAME = {GCNConv_GNNB: "gcn", GINConv_GNNB: "gin", SAGEConv_GNNB: "sage", PNAConv_GNNB: "pna", GINEConv_GNNB: "gine",
               PNAEConv_GNNB: "pnae", GATv2Conv_GNNB: "gatv2", GATv2EConv_GNNB: "gatv2e", TransformerConv_GNNB: "transformer",
               TransformerEConv_GNNB: "transformere", ResGatedGraphConv_GNNB: "resgated", ResGatedGraphEConv_GNNB: "resgatede",
               GATv1Conv_GNNB: "gat", GATv1EConv_GNNB: "gate", GatedGraphConv_GNNB: "ggnn", RGCNConv_GNNB: "rgcn", NNConv_GNNB: "nnconv",
-              GENConv_GNNB: "gen", GENEConv_GNNB: "gene", SchNetConv_GNNB: "schnet"}
+              GENConv_GNNB: "gen", GENEConv_GNNB: "gene", SchNetConv_GNNB: "schnet",
+              EdgeConv_GNNB: "edgeconv"}
 # convs that take edge_attr, and what the messages call them
 _EDGE_CONVS = {GINEConv_GNNB: "GINE", PNAEConv_GNNB: "PNAE", GATv2EConv_GNNB: "GATv2E", TransformerEConv_GNNB: "TransformerE",
                ResGatedGraphEConv_GNNB: "ResGatedE", GATv1EConv_GNNB: "GATE", NNConv_GNNB: "NNConv", GENEConv_GNNB: "GENE",
@@ -1438,6 +1466,11 @@ class GNNModel(nn.Module):
             if gnn_aggr not in ("add", "mean"):
                 raise ValueError(f"an NNConv model needs gnn_aggr 'add' or 'mean' (got {gnn_aggr!r})")
             conv_kwargs = {**conv_kwargs, "hidden": gnn_edge_hidden, "aggr": gnn_aggr}
+        elif self.gnn_conv is EdgeConv_GNNB:
+            if gnn_aggr != "max" or gnn_edge_hidden != 0:
+                raise ValueError(f"an EdgeConv model needs gnn_aggr 'max' (got gnn_aggr={gnn_aggr!r}, gnn_edge_hidden={gnn_edge_hidden!r}): 'add' "
+                                 "and 'mean' are the aggregate-first follow-up (sum_j relu(a_i + b_j), then W2 as a node GEMM, with no "
+                                 "per-edge matrix work)")
         elif gnn_edge_hidden != 0 or gnn_aggr != "add":
             raise ValueError(f"gnn_edge_hidden={gnn_edge_hidden!r}, gnn_aggr={gnn_aggr!r}: only an NNConv model (gnn_conv=NNConv_GNNB) has "
                              "an edge network and an aggr")
@@ -1657,6 +1690,7 @@ class GNNModel(nn.Module):
         # (the order of the formula: include/gnnb_schnet.h; conv.conv.nn.* are conv.mlp.*'s second names)
         per_conv["schnet"] = ["conv_conv_lin1_weight", "conv_mlp_0_weight", "conv_mlp_0_bias", "conv_mlp_2_weight", "conv_mlp_2_bias",
                               "conv_conv_lin2_weight", "conv_conv_lin2_bias", "conv_lin_weight", "conv_lin_bias"]
+        per_conv["edgeconv"] = ["nn_0_weight", "nn_0_bias", "nn_2_weight", "nn_2_bias"]  # (PyG's state_dict order: include/gnnb_edgeconv.h)
         if self.gnn_conv in _GEN_CONVS:  # (a layer's list depends on its widths: include/gnnb_gen.h; conv.t travels in spec()["softmax_t"])
             names = []
             for l, c in enumerate(self.gnn_convs):

@@ -30,7 +30,7 @@ CONV = {"gcn": 0, "gin": 1, "sage": 2, "pna": 3}                                
 MAX_EDGE_DIM = 16  # of a GINE model (include/gnnb_edge.h): its description is GIN's, edge_dim travels beside it; likewise PNA with edge features (gnnb_pna_edge.h)
 _EDGE_BASE = {"gine": "gin", "pnae": "pna"}  # spec["conv"] of an edge model -> the conv its description carries
 MAX_GAT_HEADS, MAX_GAT_WIDTH = 8, 256  # of a GATv2 model (include/gnnb_gat.h): its description is GCN's, heads and negative_slope travel beside it
-_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin", "rgcn": "gin", "nnconv": "gin", "gen": "gin", "gene": "gin", "schnet": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
+_DESC_BASE = {**_EDGE_BASE, "gatv2": "gcn", "gatv2e": "gcn", "transformer": "gin", "transformere": "gin", "resgated": "gin", "resgatede": "gin", "gat": "gcn", "gate": "gcn", "ggnn": "gin", "rgcn": "gin", "nnconv": "gin", "gen": "gin", "gene": "gin", "schnet": "gin", "edgeconv": "gin"}  # spec["conv"] -> the conv its description carries, where that is another
 # spec["conv"] of the models with edge_dim beside the description ("gatv2e": include/gnnb_gat_edge.h, "transformere": gnnb_transformer_edge.h,
 # "resgatede": gnnb_resgated_edge.h, "gate": gnnb_gatconv_edge.h)
 _EDGE_CONVS = (*_EDGE_BASE, "gatv2e", "transformere", "resgatede", "gate", "nnconv", "gene", "schnet")
@@ -319,6 +319,15 @@ ABI_SCHNET = {
 }
 
 
+# ... and of include/gnnb_edgeconv.h (EdgeConv models, the edge MLP's second linear under the max), in its order
+ABI_EDGECONV = {
+    "gnnb_edgeconv_model_num_params": (_I, [_DESC]),
+    "gnnb_edgeconv_model_create": (_I, [_DESC, _PP, _I, _PP]),
+    "gnnb_model_edgeconv": (_I, [_P]),
+    "gnnb_aggregate_edgeconv": (_I, [_P, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P]),
+}
+
+
 def ingest_bytes(max_graphs: int, max_nodes: int, max_edges: int) -> int:
     """Size of the allocation ``CompiledModel.enable_ingest`` makes for a workspace of these capacities
     (``gnnb_ingest_bytes``): the three output arrays and the sort scratch.  Pure host arithmetic, no GPU needed."""
@@ -370,7 +379,7 @@ def load_library(require_gpu: bool = True) -> C.CDLL:
         lib = C.CDLL(str(LIB_PATH))
         for name, (restype, argtypes) in {**ABI, **ABI_ORDER, **ABI_EDGE, **ABI_PNA_EDGE, **ABI_GAT, **ABI_GAT_EDGE, **ABI_TRANSFORMER,
                                            **ABI_TRANSFORMER_EDGE, **ABI_RESGATED, **ABI_RESGATED_EDGE, **ABI_GATCONV,
-                                           **ABI_GATCONV_EDGE, **ABI_GGNN, **ABI_RGCN, **ABI_NNCONV, **ABI_GEN, **ABI_SCHNET}.items():
+                                           **ABI_GATCONV_EDGE, **ABI_GGNN, **ABI_RGCN, **ABI_NNCONV, **ABI_GEN, **ABI_SCHNET, **ABI_EDGECONV}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -593,7 +602,9 @@ class CompiledModel:
             if len(ts) != int(spec["num_layers"]) or not all(np.isfinite(ts)):
                 raise GnnbError(f"a GENConv model needs spec['softmax_t']: {spec['num_layers']} finite temperatures (or one number), got {ts!r}")
             gen_t = (C.c_float * max(len(ts), 1))(*ts)
-        n_expect = (self.lib.gnnb_schnet_model_num_params(C.byref(self.desc), int(spec.get("gaussians", 50))) if schnet else
+        edgeconv = spec.get("conv") == "edgeconv"  # (gnnb_edgeconv.h: a GIN description, nothing beside it)
+        n_expect = (self.lib.gnnb_edgeconv_model_num_params(C.byref(self.desc)) if edgeconv else
+                    self.lib.gnnb_schnet_model_num_params(C.byref(self.desc), int(spec.get("gaussians", 50))) if schnet else
                     self.lib.gnnb_gen_model_num_params(C.byref(self.desc), self.edge_dim) if gen_t is not None else
                     self.lib.gnnb_nnconv_model_num_params(C.byref(self.desc), self.edge_dim, self.nnconv_hidden) if spec.get("conv") == "nnconv" else
                     self.lib.gnnb_gat_edge_model_num_params(C.byref(self.desc), self.gat_heads, self.edge_dim) if spec.get("conv") == "gatv2e" else
@@ -615,7 +626,9 @@ class CompiledModel:
         if len(host) != n_expect:
             raise GnnbError(f"model needs {n_expect} parameter tensors, got {len(host)}")
         arr = (C.c_void_p * len(host))(*[h.ctypes.data for h in host])
-        if schnet:  # (gnnb_schnet.h: a GIN description, the gaussians and the cutoff beside it)
+        if edgeconv:
+            _check(self.lib.gnnb_edgeconv_model_create(C.byref(self.desc), arr, len(host), C.byref(self._model)))
+        elif schnet:  # (gnnb_schnet.h: a GIN description, the gaussians and the cutoff beside it)
             _check(self.lib.gnnb_schnet_model_create(C.byref(self.desc), int(spec.get("gaussians", 50)), float(spec.get("cutoff", 10.0)), arr,
                                                      len(host), C.byref(self._model)))
         elif gen_t is not None:  # (gnnb_gen.h: a GIN description, edge_dim -- 0 without edge features -- and the temperatures beside it)
@@ -976,6 +989,8 @@ class CompiledModel:
         if self.spec.get("conv") == "gen":  # (gnnb_gen.h: the C entries refuse it the same way)
             raise GnnbError(f"{what}: a GENConv model without edge features (GENConv_GNNB) takes no edge attributes: call "
                             f"{what.replace('_edges', '')}")
+        if self.spec.get("conv") == "edgeconv":  # (gnnb_edgeconv.h: the C entries refuse it the same way)
+            raise GnnbError(f"{what}: an EdgeConv model (EdgeConv_GNNB) takes no edge attributes: call {what.replace('_edges', '')}")
         if not self.edge_dim:
             raise GnnbError(f"{what} takes a GINE or PNAE model, or GATv2 with edge features (a GNNModel of GINEConv_GNNB, PNAEConv_GNNB or "
                             "GATv2EConv_GNNB layers: edge weights); this model has none")
@@ -1037,6 +1052,8 @@ class CompiledModel:
         return _dptr(edge_type) if E else None
 
     def _require_rgcn_model(self, what: str) -> None:
+        if self.spec.get("conv") == "edgeconv":  # (gnnb_edgeconv.h: the C entries refuse it the same way)
+            raise GnnbError(f"{what}: an EdgeConv model (EdgeConv_GNNB) takes no edge types: call {what.replace('_types', '')}")
         if not self.rgcn_relations:
             raise GnnbError(f"{what} takes an RGCNConv model (a GNNModel of RGCNConv_GNNB layers: relations); this model has none")
 

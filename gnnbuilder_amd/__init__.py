@@ -14,6 +14,7 @@ from pathlib import Path as _Path
 __path__ = [str(_Path(__file__).resolve().parent.parent / "gnn-builder_amd")]
 
 from .models import (
+    EdgeConv_GNNB,
     MLP,
     GATConv_GNNB,
     GATv1Conv_GNNB,
@@ -52,7 +53,7 @@ from .batching import GraphBatch, from_pyg_batch, order_large_last, pack_graphs,
 
 __all__ = [
     "Project", "FPX",
-    "MLP", "GATConv_GNNB", "GATv1Conv_GNNB", "GATv1EConv_GNNB", "GATv2Conv_GNNB", "GATv2EConv_GNNB", "GCNConv_GNNB", "GENConv_GNNB", "GENEConv_GNNB", "GIN_MLP", "GINConv_GNNB", "GINEConv_GNNB", "GatedGraphConv_GNNB", "GlobalPooling", "GNNModel",
+    "MLP", "EdgeConv_GNNB", "GATConv_GNNB", "GATv1Conv_GNNB", "GATv1EConv_GNNB", "GATv2Conv_GNNB", "GATv2EConv_GNNB", "GCNConv_GNNB", "GENConv_GNNB", "GENEConv_GNNB", "GIN_MLP", "GINConv_GNNB", "GINEConv_GNNB", "GatedGraphConv_GNNB", "GlobalPooling", "GNNModel",
     "NNConv_GNNB", "PNAConv_GNNB", "PNAEConv_GNNB", "RGCNConv_GNNB", "ResGatedGraphConv_GNNB", "ResGatedGraphEConv_GNNB", "SAGEConv_GNNB", "SchNetConv_GNNB", "TransformerConv_GNNB", "TransformerEConv_GNNB",
     "compute_average_degree", "compute_average_nodes_and_edges", "compute_max_nodes_and_edges",
     "compute_median_degree", "compute_median_nodes_and_edges",
